@@ -297,6 +297,25 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_SAMPLE = 1 << 21        # entries kept per dumped vector: the three stay under 64 MB in float64
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step handed back, as float64 .npy files: the ELBO and the sum of the KL terms
+    (elbo.npy) and, over the free state in optimize()'s order, the gradient w.r.t. the constrained parameters (grad.npy),
+    the free state after the Adam update (free_state.npy) and the constrained parameters it maps to (params.npy).  A free
+    state longer than DUMP_SAMPLE is cut to one fixed, seeded sample of its positions (sorted), the same in all three."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = model._free_index()[1]
+    if idx.numel() > DUMP_SAMPLE:
+        keep = np.sort(np.random.RandomState(0).choice(idx.numel(), DUMP_SAMPLE, replace=False))
+        idx = idx[torch.as_tensor(keep, device=idx.device)]
+    np.save(os.path.join(out_dir, "elbo.npy"), model._elbo_dev.cpu().numpy())
+    for name, vec in (("grad", model._grad), ("free_state", model._free), ("params", model._params)):
+        np.save(os.path.join(out_dir, name + ".npy"), vec.index_select(0, idx).cpu().numpy())
+
+
 def run_timed(args, shard, rank, dist):
     """warm-up, then exactly args.steps steps bracketed by barrier + synchronize on both sides; MAX over ranks."""
     import torch
@@ -379,7 +398,11 @@ def main():
     ap.add_argument("--no-pitch-line", action="store_true",
                     help="multi-GPU window mode: skip the extra pitch-sharded (strong-scaling) measurement")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's model) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -405,6 +428,8 @@ def main():
             dist.init_process_group(args.backend)
 
     res = run_timed(args, args.shard, rank, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res["model"], args.dump_outputs)
     model, h, elapsed, elbo_final, timers = res["model"], res["handle"], res["elapsed"], res["elbo_final"], res["timers"]
     local_gps = model._gps()         # latent GPs in this rank's launches
     n_act_local = sum(1 for g in local_gps if any(g[0] is k for k in model.kern_act))

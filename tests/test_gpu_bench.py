@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,25 @@ def test_bench_single_process_line():
     assert abs(d["mfma_frac_step"]["achieved"]
                - d["mfma_frac_step"]["algorithmic_flops_per_step"] / (d["ms_per_step"] * 1e-3) / 1e12) < 1e-6
     assert d["config"]["workload"].startswith("pdgp ELBO step")
+
+
+def test_bench_dumps_the_last_steps_outputs(tmp_path):
+    """--dump-outputs: the last timed step's ELBO, gradient and updated parameters as float64 .npy files, the same for two
+    runs with the same arguments (seeded inputs), the ELBO the one the result line reports"""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / str(run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_line(r.stdout)
+        out = {n: np.load(str(d / (n + ".npy"))) for n in ("elbo", "grad", "free_state", "params")}
+        assert all(v.dtype == np.float64 for v in out.values())
+        assert out["elbo"][0] == line["elbo_final"] and line["steps"] == 2
+        assert out["grad"].shape == out["free_state"].shape == out["params"].shape and out["grad"].size > 0
+        dumps.append(out)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)
 
 
 @pytest.mark.parametrize("shard,scaling", [("window", "weak"), ("pitch", "strong"), ("gp", "strong")])
