@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "gp_timers_enable", "gp_timers_reset", "gp_timers_read",
     "gp_comm_unique_id", "gp_comm_create", "gp_comm_destroy", "gp_comm_world", "gp_comm_rank", "gp_comm_allreduce_sum",
     "gp_pdgp_elbo_pitch_sharded", "gp_pdgp_elbo_gp_sharded", "gp_sgpr_bound_grad_sharded",
+    "gp_segment_gram_workspace_bytes", "gp_segment_gram", "gp_autocorr", "gp_kernfit_eval",
 ]
 
 
@@ -202,6 +203,10 @@ def load_library():
         "gp_pdgp_elbo_gp_sharded": (i32, [vp, vp, vp, vp, vp, i32, dbl, i32, i32, vp, vp, vp, vp, C.POINTER(dbl), vp,
                                         C.POINTER(AdamArgs)]),
         "gp_sgpr_bound_grad_sharded": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, C.POINTER(dbl), vp]),
+        "gp_segment_gram_workspace_bytes": (sz, [i32, i32, i32]),
+        "gp_segment_gram": (i32, [vp, vp, i64, vp, vp, i32, vp, i32, i32, vp, vp, sz]),
+        "gp_autocorr": (i32, [vp, vp, i64, i32, vp]),
+        "gp_kernfit_eval": (i32, [vp, i32, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol

@@ -157,10 +157,14 @@ def minimize_many(fun_and_grad_batch, x0s, maxiter=15000, **kw):
     """Minimise len(x0s) independent objectives that are evaluated together.
 
     fun_and_grad_batch(X, active) -> (f, G): X is (W, n) with one point per problem (rows of finished problems hold
-    their last point), `active` the indices whose values will be used; f (W,), G (W, n).
+    their last point), `active` the indices whose values will be used; f (W,), G (W, n).  When the problems differ in
+    dimension, X is a list of W 1-D arrays and G any sequence whose G[i] has problem i's dimension.
     Returns the list of LbfgsbRC states (x, fun, nfev, nit, status)."""
     runs = [LbfgsbRC(x0, maxiter=maxiter, **kw) for x0 in x0s]
-    X = np.stack([r.x for r in runs])
+    if len(set(r.n for r in runs)) > 1:
+        X = [r.x.copy() for r in runs]
+    else:
+        X = np.stack([r.x for r in runs])
     active = list(range(len(runs)))
     # scipy's ScalarFunction evaluates x0 on construction: the first round is that evaluation
     while active:

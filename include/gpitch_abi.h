@@ -462,6 +462,34 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan p, const double* params, const d
                                   const double* Xnew, int32_t n, int32_t count, double* mean, double* var,
                                   void* workspace, size_t workspace_bytes);
 
+/* ---- kernel learning from an isolated-note recording (the drivers' init_kernel(train=True) branch,
+ *      gpitch/transcription.py:176-195, gpitch/separation.py:185-204) -------------------------------------------------
+ * gp_segment_gram replaces samplecov.get_samples + comatrix (samplecov.py:5-53: one tf.matmul session call per segment):
+ *   C_b = (1/K) sum_k s_k s_k^T,  s_k = y[start_host[b K + k] : start_host[b K + k] + L],  b < B,
+ * written as B row-major L x L matrices (both triangles, exactly symmetric).  y holds all B recordings (recording b is
+ * y[rec_off_host[b] : rec_off_host[b] + rec_len_host[b]]; start_host holds ABSOLUTE element offsets into y, int32, read
+ * on the host and uploaded into the workspace); every segment must lie inside its own recording and y must not exceed
+ * GP_SEGMENT_GRAM_MAX_Y_BYTES (the kernel addresses y through 32-bit buffer offsets): GP_ERR_BAD_ARG otherwise — split
+ * the batch.  The sum over k runs in chunks of a fixed length, so C_b is bit-identical from run to run, from device to
+ * device and whatever else shares the batch.  Workspace: gp_segment_gram_workspace_bytes(B, K, L), 256-byte aligned. */
+#define GP_SEGMENT_GRAM_MAX_Y_BYTES (2147483648LL - 4096)
+size_t gp_segment_gram_workspace_bytes(int32_t B, int32_t K, int32_t L);
+gp_status gp_segment_gram(gp_handle h, const double* y, int64_t ny, const int64_t* rec_off_host, const int64_t* rec_len_host,
+                          int32_t B, const int32_t* start_host, int32_t K, int32_t L, double* C, void* workspace,
+                          size_t workspace_bytes);
+/* samplecov.autocorr (samplecov.py:56-74), before its normalisation: r[j] = sum_{i < n-L} y[i] y[i+j], j < L (n > L),
+ * a fixed-order reduction over i. */
+gp_status gp_autocorr(gp_handle h, const double* y, int64_t n, int32_t L, double* r);
+/* kernelfit.loss_func / approximate_kernel (kernelfit.py:28-51) for W problems in one launch, one wavefront each.
+ * Problem w: points x[w ld + j], targets y[w ld + j], j < npts[w] <= ld; m_w = npar[w] <= m_max <= 64 partials; parameter
+ * row p[w P ..], P = 2 + 2 m_max: [bias, lengthscale, v_1..v_{m_w}, f_1..f_{m_w}, padding];
+ *   k(x) = (1 + sqrt(3)|x|/|l|) exp(-sqrt(3)|x|/|l|) sum_i |v_i| cos(2 pi |f_i| |x|)   (+ 0 |bias|),
+ *   f[w] = sqrt(mean_j (k(x_j) - y_j)^2);  g[w P ..] = df/dp in the same layout (sign(p) of the |.|, 0 for the bias and
+ *   the padding);  k[w ld + j] = k(x_j) when k != NULL.  npts / npar are device int32 arrays.  A problem's results depend
+ * on its own row only (bit-identical whatever shares the launch). */
+gp_status gp_kernfit_eval(gp_handle h, int32_t W, const double* x, const double* y, int64_t ld, const int32_t* npts,
+                          const int32_t* npar, int32_t m_max, const double* p, double* f, double* g, double* k);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * HIP-event timing of the dominant kernels on the handle's own stream.  Returns the accumulated time of
  * kernel class `which` since the last reset and the number of launches. */
