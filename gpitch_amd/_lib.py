@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "gp_comm_unique_id", "gp_comm_create", "gp_comm_destroy", "gp_comm_world", "gp_comm_rank", "gp_comm_allreduce_sum",
     "gp_pdgp_elbo_pitch_sharded", "gp_pdgp_elbo_gp_sharded", "gp_sgpr_bound_grad_sharded",
     "gp_segment_gram_workspace_bytes", "gp_segment_gram", "gp_autocorr", "gp_kernfit_eval",
+    "gp_pdgpb_create", "gp_pdgpb_destroy", "gp_pdgpb_num_params", "gp_pdgpb_layout", "gp_pdgpb_set_grad_needs",
+    "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
 ]
 
 
@@ -76,6 +78,13 @@ class SgprConfig(C.Structure):
     _fields_ = [("num_kernels", C.c_int32), ("max_N", C.c_int32), ("M", C.c_int32),
                 ("kern_type", C.POINTER(C.c_int32)), ("partials", C.POINTER(C.c_int32)),
                 ("jitter", C.c_double), ("reg", C.c_int32)]
+
+
+class PdgpBatchConfig(C.Structure):
+    """gp_pdgpb_config: many independent Pdgp models (per-model arrays, then per-latent-GP arrays model by model)"""
+    _fields_ = [("num_models", C.c_int32), ("num_sources", C.POINTER(C.c_int32)), ("batch", C.POINTER(C.c_int32)),
+                ("nlin", C.POINTER(C.c_int32)), ("num_data", C.POINTER(C.c_double)), ("M", C.POINTER(C.c_int32)),
+                ("kern_type", C.POINTER(C.c_int32)), ("partials", C.POINTER(C.c_int32)), ("jitter", C.c_double)]
 
 
 _lib = None
@@ -207,6 +216,16 @@ def load_library():
         "gp_segment_gram": (i32, [vp, vp, i64, vp, vp, i32, vp, i32, i32, vp, vp, sz]),
         "gp_autocorr": (i32, [vp, vp, i64, i32, vp]),
         "gp_kernfit_eval": (i32, [vp, i32, vp, vp, i64, vp, vp, i32, vp, vp, vp, vp]),
+        "gp_pdgpb_create": (i32, [vp, C.POINTER(PdgpBatchConfig), C.POINTER(vp)]),
+        "gp_pdgpb_destroy": (i32, [vp]),
+        "gp_pdgpb_num_params": (i64, [vp]),
+        "gp_pdgpb_layout": (i32, [vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "gp_pdgpb_set_grad_needs": (i32, [vp, i32, i32, i32]),
+        "gp_pdgpb_workspace_bytes": (sz, [vp]),
+        "gp_pdgpb_set_workspace": (i32, [vp, vp, sz]),
+        "gp_pdgpb_objective": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "gp_pdgpb_adam": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl]),
+        "gp_pdgpb_not_pd": (i32, [vp, C.POINTER(i32), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol

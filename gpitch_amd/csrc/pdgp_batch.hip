@@ -1,0 +1,745 @@
+// pdgp_batch.hip — many small, independent Pdgp models per launch sequence (gfx950).
+//
+// Replaces, for a list of models, the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)
+//   Pdgp.build_likelihood   gpitch/pdgp.py:113-170 (whitened: gauss_kl without K, conditional with whiten=True)
+//   AdamOptimizer steps     demos/scripts/demo-modgp.py:44-45 (TF-1.2 update on GPflow's free state)
+// At the demo's size (minibatch 100, about 100 inducing points per GP) one model's step is a few dozen launches of
+// 100 x 100 problems, bound by launch overhead.  Here one step of ALL models is four launches whatever their number:
+//   pdgpb_fwd_kernel   one workgroup per latent GP: Kuu + jitter I factored and inverted in LDS, Kuf, A = L^-1 Kuf,
+//                      S' = Lq Lq^T - I, U = S' A, fmean = A^T q_mu, fvar = Kdiag + A^T S' A (per column), whitened KL
+//   pdgpb_lik_kernel   one workgroup per model: Gauss-Hermite expectations, d/dfmean, d/dfvar, d/dnoise, the ELBO
+//   pdgpb_bwd_kernel   one workgroup per latent GP: gradients of q_mu, tril(Lq), the hyper-parameters and z
+//   pdgpb_adam_kernel  the TF-1.2 Adam update over the concatenated free state, frozen per model after a failed Cholesky
+// Every reduction is one thread's sequential loop or a fixed tree: two runs give bit-identical results.
+#include "common.h"
+#include "gh_quad.h"
+#include <algorithm>
+
+#define PB_THREADS 256
+#define PB_MAX_M 128
+#define PB_MAX_B 1024
+#define PB_MAX_PARTIALS 32
+#define PB_TILE 64
+#define PB_KT 16
+#define PB_TILE_DOUBLES (2 * PB_TILE * PB_KT)
+
+struct PbGp {
+  int model, row, type, m, M, B, need_theta, need_z;
+  int64_t off_theta, off_z, off_qmu, off_qsq;
+  int64_t ws;          // this GP's scratch (doubles from the plan's scratch base)
+  int64_t f_off;       // row offset in the model-major fmean / fvar / gm / gv arrays
+  int64_t batch_off;   // offset of the model's frames in the step's index vector
+};
+struct PbModel {
+  int P, B, nlin, g0;
+  int64_t off_noise, p0, p1;   // parameter range [p0, p1) (Adam freeze)
+  int64_t f_base, batch_off;
+  double num_data;
+};
+
+struct gp_pdgpb_plan_s {
+  gp_handle h = nullptr;
+  int nm = 0, G = 0, maxM = 0, maxB = 0, maxm = 0, sumB = 0;
+  double jitter = 1e-6;
+  int64_t nparams = 0, f_len = 0, scratch = 0;
+  std::vector<PbGp> gps;
+  std::vector<PbModel> models;
+  std::vector<int32_t> owner;
+  // device (inside the caller's workspace)
+  PbGp* d_gps = nullptr; PbModel* d_models = nullptr; int32_t* d_owner = nullptr; int32_t* d_status = nullptr;
+  double *d_fm = nullptr, *d_fv = nullptr, *d_gm = nullptr, *d_gv = nullptr, *d_kl = nullptr, *d_grad = nullptr,
+         *d_elbo = nullptr, *d_scr = nullptr;
+  bool ready = false;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// covariance entries and their derivatives (the reference's kernels; the squared distance keeps GPflow's expansion,
+// as cov.hip does: r2 = ((-2 (a b)) + a a) + b b with a = x / l, b = x' / l, each operation rounded)
+__device__ __forceinline__ double pb_r2(double xa, double xb, double ls) {
+  const double a = xa / ls, b = xb / ls;
+  return __dadd_rn(__dadd_rn(-2.0 * __dmul_rn(a, b), __dmul_rn(a, a)), __dmul_rn(b, b));
+}
+
+__device__ double pb_kern(int type, int m, const double* __restrict__ th, double xa, double xb) {
+  const double v = th[0], ls = th[1];
+  if (type == GP_KERN_MATERN32SM) {                    // kernels.py:232-247 (broadcast form)
+    const double d = __dadd_rn(__dadd_rn(xa, -xb), 1e-12);
+    const double r = fabs(d);
+    const double r1 = 1.7320508075688772 * (r / ls);
+    double s = 0.0;
+    for (int p = 0; p < m; p++) s += th[2 + p] * cos(6.283185307179586 * th[2 + m + p] * r);
+    return v * ((1.0 + r1) * exp(-r1)) * s;
+  }
+  const double r2 = pb_r2(xa, xb, ls);
+  if (type == GP_KERN_RBF) return v * exp(-0.5 * r2);
+  const double r = sqrt(r2 + 1e-12);
+  if (type == GP_KERN_MATERN12) return v * exp(-r);
+  if (type == GP_KERN_MATERN32) return v * (1.0 + 1.7320508075688772 * r) * exp(-1.7320508075688772 * r);
+  if (type == GP_KERN_MATERN52) {
+    const double s5 = 2.23606797749979;
+    return v * (1.0 + s5 * r + (5.0 / 3.0) * (r * r)) * exp(-s5 * r);
+  }
+  // MercerMatern12sm (matern12_spectral_mixture.py:102-133): v exp(-r) sum_k e_k cos(2 pi f_k (x - x'))
+  const double d = xa - xb;
+  double s = 0.0;
+  for (int p = 0; p < m; p++) s += th[2 + p] * cos(6.283185307179586 * th[2 + m + p] * d);
+  return v * exp(-r) * s;
+}
+
+__device__ __forceinline__ double pb_kdiag(int type, int m, const double* __restrict__ th) {
+  if (type == GP_KERN_MERCER_MATERN12SM || type == GP_KERN_MATERN32SM) {
+    double s = th[2];
+    for (int p = 1; p < m; p++) s += th[2 + p];
+    return th[0] * s;
+  }
+  return th[0];
+}
+
+// acc[c] += w * dK(xa, xb)/dtheta_c (theta = [v, l, e_0.., f_0..]); returns dK/dxa
+__device__ double pb_kern_grad(int type, int m, const double* __restrict__ th, double xa, double xb, double w,
+                               double* __restrict__ acc, bool want_theta) {
+  const double v = th[0], ls = th[1];
+  const double TWO_PI = 6.283185307179586;
+  if (type == GP_KERN_MATERN32SM) {
+    const double d = __dadd_rn(__dadd_rn(xa, -xb), 1e-12);
+    const double r = fabs(d), sg = d >= 0.0 ? 1.0 : -1.0;
+    const double r1 = 1.7320508075688772 * (r / ls);
+    const double e1 = exp(-r1), E = (1.0 + r1) * e1;
+    double s = 0.0, ds = 0.0;
+    for (int p = 0; p < m; p++) {
+      const double om = TWO_PI * th[2 + m + p];
+      double sn, cs;
+      sincos(om * r, &sn, &cs);
+      s += th[2 + p] * cs;
+      ds -= th[2 + p] * om * sn;
+      if (want_theta) {
+        acc[2 + p] += w * v * E * cs;
+        acc[2 + m + p] += w * v * E * th[2 + p] * (-TWO_PI * r * sn);
+      }
+    }
+    if (want_theta) {
+      acc[0] += w * E * s;
+      acc[1] += w * v * s * r1 * r1 * e1 / ls;
+    }
+    return sg * v * (s * (-r1 * e1) * (1.7320508075688772 / ls) + E * ds);
+  }
+  const double a = xa / ls, b = xb / ls;
+  const double r2 = pb_r2(xa, xb, ls);
+  const double dr2_da = (2.0 * a - 2.0 * b) / ls;      // d r2 / d xa
+  const double dr2_dl = -2.0 * r2 / ls;
+  if (type == GP_KERN_RBF) {
+    const double e = exp(-0.5 * r2), K = v * e;
+    if (want_theta) { acc[0] += w * e; acc[1] += w * K * (-0.5) * dr2_dl; }
+    return K * (-0.5) * dr2_da;
+  }
+  const double r = sqrt(r2 + 1e-12);
+  const double dr_da = 0.5 * dr2_da / r, dr_dl = 0.5 * dr2_dl / r;
+  double prof, dprof;                                  // K = v prof(r) [* S]
+  if (type == GP_KERN_MATERN32) {
+    const double s3 = 1.7320508075688772, e = exp(-s3 * r);
+    prof = (1.0 + s3 * r) * e; dprof = -3.0 * r * e;
+  } else if (type == GP_KERN_MATERN52) {
+    const double s5 = 2.23606797749979, e = exp(-s5 * r);
+    prof = (1.0 + s5 * r + (5.0 / 3.0) * (r * r)) * e; dprof = -(5.0 / 3.0) * r * (1.0 + s5 * r) * e;
+  } else {                                             // Matern12 and the Mercer envelope
+    prof = exp(-r); dprof = -prof;
+  }
+  if (type != GP_KERN_MERCER_MATERN12SM) {
+    if (want_theta) { acc[0] += w * prof; acc[1] += w * v * dprof * dr_dl; }
+    return v * dprof * dr_da;
+  }
+  const double d = xa - xb;
+  double s = 0.0, ds = 0.0;
+  for (int p = 0; p < m; p++) {
+    const double om = TWO_PI * th[2 + m + p];
+    double sn, cs;
+    sincos(om * d, &sn, &cs);
+    s += th[2 + p] * cs;
+    ds -= th[2 + p] * om * sn;
+    if (want_theta) {
+      acc[2 + p] += w * v * prof * cs;
+      acc[2 + m + p] += w * v * prof * th[2 + p] * (-TWO_PI * d * sn);
+    }
+  }
+  if (want_theta) { acc[0] += w * prof * s; acc[1] += w * v * dprof * dr_dl * s; }
+  return v * (dprof * dr_da * s + prof * ds);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// C (M x N, row stride ldc) = alpha op(A) op(B) + beta C with op(A)(i, k) = A[i ars + k acs], op(B)(k, j) = B[k brs + j bcs].
+// 64 x 64 output tiles, 16-deep k slices through LDS, 4 x 4 outputs per thread, k in ascending order (deterministic).
+struct PbMat { const double* p; int64_t rs, cs; };
+__device__ void pb_gemm(int M, int N, int K, PbMat A, PbMat B, double* C, int64_t ldc, double alpha, double beta,
+                        double* __restrict__ sm) {
+  double* As = sm;
+  double* Bs = sm + PB_TILE * PB_KT;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  for (int i0 = 0; i0 < M; i0 += PB_TILE)
+    for (int j0 = 0; j0 < N; j0 += PB_TILE) {
+      double acc[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) acc[r][c] = 0.0;
+      for (int k0 = 0; k0 < K; k0 += PB_KT) {
+        for (int e = tid; e < PB_TILE * PB_KT; e += PB_THREADS) {
+          const int kk = e / PB_TILE, ii = e % PB_TILE;
+          const int gi = i0 + ii, gj = j0 + ii, gk = k0 + kk;
+          As[e] = (gi < M && gk < K) ? A.p[gi * A.rs + gk * A.cs] : 0.0;
+          Bs[e] = (gj < N && gk < K) ? B.p[gk * B.rs + gj * B.cs] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < PB_KT; kk++) {
+          double a[4], b[4];
+#pragma unroll
+          for (int r = 0; r < 4; r++) a[r] = As[kk * PB_TILE + ty * 4 + r];
+#pragma unroll
+          for (int c = 0; c < 4; c++) b[c] = Bs[kk * PB_TILE + tx * 4 + c];
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) acc[r][c] = fma(a[r], b[c], acc[r][c]);
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const int gi = i0 + ty * 4 + r, gj = j0 + tx * 4 + c;
+          if (gi < M && gj < N) {
+            double* o = C + (int64_t)gi * ldc + gj;
+            *o = beta != 0.0 ? alpha * acc[r][c] + beta * *o : alpha * acc[r][c];
+          }
+        }
+    }
+  __syncthreads();
+}
+
+// scratch of one latent GP (doubles): six M x M and six M x B blocks
+__host__ __device__ inline int64_t pb_gp_scratch(int M, int B) { return 6 * (int64_t)M * M + 6 * (int64_t)M * B; }
+struct PbScr { double *L, *W, *Lq, *S, *T1, *T2, *K, *A, *U, *Ab, *Kb, *TB; };
+__device__ inline PbScr pb_scr(double* base, int M, int B) {
+  PbScr s;
+  const int64_t mm = (int64_t)M * M, mb = (int64_t)M * B;
+  s.L = base; s.W = s.L + mm; s.Lq = s.W + mm; s.S = s.Lq + mm; s.T1 = s.S + mm; s.T2 = s.T1 + mm;
+  s.K = s.T2 + mm; s.A = s.K + mb; s.U = s.A + mb; s.Ab = s.U + mb; s.Kb = s.Ab + mb; s.TB = s.Kb + mb;
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// forward: one workgroup per latent GP.  LDS: [maxM^2 factor | maxB frames | maxM z | maxM tmp | gemm tiles]
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_fwd_kernel(const PbGp* __restrict__ gps, const double* __restrict__ params,
+                                                               const double* __restrict__ xall, const int32_t* __restrict__ idx,
+                                                               double* __restrict__ scr_base, double* __restrict__ fmean,
+                                                               double* __restrict__ fvar, double* __restrict__ kl,
+                                                               int32_t* __restrict__ status, double jitter, int maxM, int maxB) {
+  extern __shared__ double pb_sm[];
+  const PbGp g = gps[blockIdx.x];
+  const int M = g.M, B = g.B, tid = threadIdx.x;
+  double* Ls = pb_sm;
+  double* xs = Ls + (int64_t)maxM * maxM;
+  double* zs = xs + maxB;
+  double* tmp = zs + maxM;
+  double* tiles = tmp + maxM;
+  __shared__ int bad_pivot;
+  const double* th = params + g.off_theta;
+  const double* z = params + g.off_z;
+  const double* qmu = params + g.off_qmu;
+  const double* qsq = params + g.off_qsq;
+  PbScr s = pb_scr(scr_base + g.ws, M, B);
+  for (int n = tid; n < B; n += PB_THREADS) xs[n] = xall[idx[g.batch_off + n]];
+  for (int i = tid; i < M; i += PB_THREADS) zs[i] = z[i];
+  if (tid == 0) bad_pivot = -1;
+  __syncthreads();
+  // Kuu + jitter I (pdgp.py:126-129 / GPflow conditional), full matrix, row-major ld = M
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    Ls[e] = pb_kern(g.type, g.m, th, zs[i], zs[j]) + (i == j ? jitter : 0.0);
+  }
+  __syncthreads();
+  // right-looking Cholesky in place (lower); a non-positive pivot is recorded and replaced by 1 so that the rest of the
+  // pass stays finite (the model is frozen by the Adam kernel and reported to the host)
+  for (int k = 0; k < M; k++) {
+    if (tid == 0) {
+      double d = Ls[k * M + k];
+      if (!(d > 0.0)) { if (bad_pivot < 0) bad_pivot = k; d = 1.0; }
+      Ls[k * M + k] = sqrt(d);
+    }
+    __syncthreads();
+    const double dk = Ls[k * M + k];
+    for (int i = k + 1 + tid; i < M; i += PB_THREADS) Ls[i * M + k] /= dk;
+    __syncthreads();
+    const int n = M - k - 1;
+    for (int e = tid; e < n * n; e += PB_THREADS) {
+      const int i = k + 1 + e / n, j = k + 1 + e % n;
+      if (j <= i) Ls[i * M + j] = fma(-Ls[i * M + k], Ls[j * M + k], Ls[i * M + j]);
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    if (j > i) Ls[e] = 0.0;
+  }
+  __syncthreads();
+  // status word of the model: 0, or INT_MAX - (128 row + pivot); the maximum keeps the failure with the smallest
+  // (row, pivot) whatever order the model's workgroups finish in
+  if (tid == 0 && bad_pivot >= 0) atomicMax(&status[g.model], 0x7fffffff - (PB_MAX_M * g.row + bad_pivot));
+  for (int e = tid; e < M * M; e += PB_THREADS) s.L[e] = Ls[e];
+  __syncthreads();
+  // W = L^-1 in place (LAPACK trti2, lower, columns from the last): W[j+1:, j] = -W[j+1:, j+1:] L[j+1:, j] / L[j, j]
+  for (int j = M - 1; j >= 0; j--) {
+    if (tid > j && tid < M) tmp[tid] = Ls[tid * M + j];
+    __syncthreads();
+    const double ajj = -1.0 / Ls[j * M + j];
+    if (tid > j && tid < M) {
+      double y = 0.0;
+      for (int k = j + 1; k <= tid; k++) y = fma(Ls[tid * M + k], tmp[k], y);
+      Ls[tid * M + j] = y * ajj;
+    }
+    __syncthreads();
+    if (tid == 0) Ls[j * M + j] = -ajj;
+    __syncthreads();
+  }
+  for (int e = tid; e < M * M; e += PB_THREADS) s.W[e] = Ls[e];
+  // tril(q_sqrt) (band_part in GPflow's conditional / gauss_kl)
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    s.Lq[e] = j <= i ? qsq[e] : 0.0;
+  }
+  // Kuf (M x B)
+  for (int e = tid; e < M * B; e += PB_THREADS) {
+    const int i = e / B, n = e % B;
+    s.K[e] = pb_kern(g.type, g.m, th, zs[i], xs[n]);
+  }
+  __syncthreads();
+  // A = W Kuf; S' = Lq Lq^T - I; U = S' A
+  pb_gemm(M, B, M, PbMat{s.W, M, 1}, PbMat{s.K, B, 1}, s.A, B, 1.0, 0.0, tiles);
+  pb_gemm(M, M, M, PbMat{s.Lq, M, 1}, PbMat{s.Lq, 1, M}, s.S, M, 1.0, 0.0, tiles);
+  for (int i = tid; i < M; i += PB_THREADS) s.S[(int64_t)i * M + i] -= 1.0;
+  __syncthreads();
+  pb_gemm(M, B, M, PbMat{s.S, M, 1}, PbMat{s.A, B, 1}, s.U, B, 1.0, 0.0, tiles);
+  // fmean = A^T q_mu, fvar = Kdiag + sum_i A U (GPflow: Kdiag - sum A^2 + sum (Lq^T A)^2)
+  const double kd = pb_kdiag(g.type, g.m, th);
+  for (int n = tid; n < B; n += PB_THREADS) {
+    double fm = 0.0, q = 0.0;
+    for (int i = 0; i < M; i++) {
+      const double a = s.A[(int64_t)i * B + n];
+      fm = fma(a, qmu[i], fm);
+      q = fma(a, s.U[(int64_t)i * B + n], q);
+    }
+    fmean[g.f_off + n] = fm;
+    fvar[g.f_off + n] = kd + q;
+  }
+  // whitened KL (GPflow gauss_kl, K = None): 0.5 (|q_mu|^2 - M - sum log Lq_ii^2 + |tril Lq|^2); one thread, fixed order
+  if (tid == 0) {
+    double a = 0.0, ld = 0.0, tr = 0.0;
+    for (int i = 0; i < M; i++) {
+      a = fma(qmu[i], qmu[i], a);
+      const double dq = qsq[(int64_t)i * M + i];
+      ld += log(dq * dq);
+      for (int j = 0; j <= i; j++) { const double l = qsq[(int64_t)i * M + j]; tr = fma(l, l, tr); }
+    }
+    kl[blockIdx.x] = 0.5 * (a - (double)M - ld + tr);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// likelihood: one workgroup per model (likelihoods.py:422-447 and :47-68, scaled by N / B: pdgp.py:166-170)
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_lik_kernel(const PbModel* __restrict__ models, const double* __restrict__ params,
+                                                               const double* __restrict__ yall, const int32_t* __restrict__ idx,
+                                                               const double* __restrict__ fmean, const double* __restrict__ fvar,
+                                                               const double* __restrict__ kl, double* __restrict__ gm,
+                                                               double* __restrict__ gv, double* __restrict__ grad,
+                                                               double* __restrict__ elbo) {
+  const PbModel md = models[blockIdx.x];
+  const int P = md.P, B = md.B, tid = threadIdx.x;
+  const double s2 = params[md.off_noise];
+  const double scale = md.num_data / (double)B;
+  const double* Fm = fmean + md.f_base;
+  const double* Fv = fvar + md.f_base;
+  const bool want_grad = grad != nullptr;
+  double ve = 0.0, dnoise = 0.0;
+  for (int n = tid; n < B; n += PB_THREADS) {
+    const double Y = yall[idx[md.batch_off + n]];
+    double A = 0.0, Bs = 0.0, Cpair = 0.0;
+    for (int i = 0; i < P; i++) {
+      const Quad q = gh_quad(md.nlin, Fm[(int64_t)i * B + n], Fv[(int64_t)i * B + n], false);
+      const double mf = Fm[(int64_t)(i + P) * B + n], vf = Fv[(int64_t)(i + P) * B + n];
+      const double a = q.E1 * mf;
+      Cpair = fma(a, A, Cpair);
+      A += a;
+      Bs = fma(q.E2, vf + mf * mf, Bs);
+    }
+    const double resid = Y * Y - 2.0 * Y * A + Bs + 2.0 * Cpair;
+    const double LOG2PI = 1.8378770664093453;
+    ve += scale * (-0.5 * ((1.0 / s2) * resid + LOG2PI + log(s2)));
+    if (!want_grad) continue;
+    dnoise += scale * (0.5 * resid / (s2 * s2) - 0.5 / s2);
+    const double qf = -0.5 * scale / s2;
+    for (int i = 0; i < P; i++) {
+      const double mg = Fm[(int64_t)i * B + n], vg = Fv[(int64_t)i * B + n];
+      const double mf = Fm[(int64_t)(i + P) * B + n], vf = Fv[(int64_t)(i + P) * B + n];
+      const Quad q = gh_quad(md.nlin, mg, vg, true);
+      const double a = q.E1 * mf;
+      const double da = qf * (-2.0 * Y + 2.0 * (A - a));
+      const double dE1 = da * mf, dE2 = qf * (vf + mf * mf);
+      const double sd = sqrt(2.0 * vg);
+      const double inv_sd = sd > 0.0 ? 1.0 / sd : 0.0;
+      gm[md.f_base + (int64_t)i * B + n] = dE1 * q.dE1m + dE2 * q.dE2m;
+      gv[md.f_base + (int64_t)i * B + n] = (dE1 * q.dE1s + dE2 * q.dE2s) * inv_sd;
+      gm[md.f_base + (int64_t)(i + P) * B + n] = da * q.E1 + qf * q.E2 * 2.0 * mf;
+      gv[md.f_base + (int64_t)(i + P) * B + n] = qf * q.E2;
+    }
+  }
+  __shared__ double red[2][PB_THREADS];
+  red[0][tid] = ve; red[1][tid] = dnoise;
+  __syncthreads();
+  for (int o = PB_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double k = 0.0;
+    for (int g = 0; g < 2 * P; g++) k += kl[md.g0 + g];
+    elbo[blockIdx.x] = red[0][0] - k;
+    if (want_grad) grad[md.off_noise] = red[1][0];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// backward: one workgroup per latent GP (the whitened path of bwd.hip, restated per GP).  With Abar = dELBO/dA:
+//   Abar = q_mu gm^T + 2 U diag(gv);  d q_mu = A gm - q_mu;  d Lq = tril(2 (A diag(gv) A^T) Lq) - Lq + diag(1 / Lq_ii)
+//   Kbar = W^T Abar (d/dKuf);  Lbar = -tril(Kbar A^T);  Kuu_bar = sym(W^T Phi(L^T Lbar) W)  (Cholesky backward)
+//   d theta = <Kuu_bar, dKuu> + <Kbar, dKuf> + sum_n gv_n dKdiag;  d z_i = 2 sum_{j != i} Kuu_bar_ij dK(z_i, z_j)/dz_i
+//             + sum_n Kbar_in dK(z_i, x_n)/dz_i
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_bwd_kernel(const PbGp* __restrict__ gps, const double* __restrict__ params,
+                                                               const double* __restrict__ xall, const int32_t* __restrict__ idx,
+                                                               double* __restrict__ scr_base, const double* __restrict__ gm_all,
+                                                               const double* __restrict__ gv_all, double* __restrict__ grad,
+                                                               int maxM, int maxB, int maxth) {
+  extern __shared__ double pb_sm[];
+  const PbGp g = gps[blockIdx.x];
+  const int M = g.M, B = g.B, tid = threadIdx.x, NT = GP_THETA_LEN(g.m);
+  double* xs = pb_sm;
+  double* zs = xs + maxB;
+  double* tiles = zs + maxM;
+  double* thacc = tiles + PB_TILE_DOUBLES;      // [maxM][maxth]
+  const double* th = params + g.off_theta;
+  const double* z = params + g.off_z;
+  const double* qmu = params + g.off_qmu;
+  const double* gm = gm_all + g.f_off;
+  const double* gv = gv_all + g.f_off;
+  PbScr s = pb_scr(scr_base + g.ws, M, B);
+  for (int n = tid; n < B; n += PB_THREADS) xs[n] = xall[idx[g.batch_off + n]];
+  for (int i = tid; i < M; i += PB_THREADS) zs[i] = z[i];
+  // Abar and A diag(gv)
+  for (int e = tid; e < M * B; e += PB_THREADS) {
+    const int i = e / B, n = e % B;
+    s.Ab[e] = fma(qmu[i], gm[n], 2.0 * s.U[e] * gv[n]);
+    s.TB[e] = s.A[e] * gv[n];
+  }
+  // d q_mu (the KL's -q_mu included)
+  for (int i = tid; i < M; i += PB_THREADS) {
+    double a = 0.0;
+    for (int n = 0; n < B; n++) a = fma(s.A[(int64_t)i * B + n], gm[n], a);
+    grad[g.off_qmu + i] = a - qmu[i];
+  }
+  __syncthreads();
+  // H = A diag(gv) A^T -> T1; T2 = H Lq; d Lq = tril(2 T2) - Lq + diag(1 / Lq_ii)
+  pb_gemm(M, M, B, PbMat{s.TB, B, 1}, PbMat{s.A, 1, B}, s.T1, M, 1.0, 0.0, tiles);
+  pb_gemm(M, M, M, PbMat{s.T1, M, 1}, PbMat{s.Lq, M, 1}, s.T2, M, 2.0, 0.0, tiles);
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    double d = 0.0;
+    if (j <= i) {
+      d = s.T2[e] - s.Lq[e];
+      if (i == j) d += 1.0 / s.Lq[e];
+    }
+    grad[g.off_qsq + e] = d;
+  }
+  __syncthreads();
+  if (!g.need_theta && !g.need_z) {      // every hyper-parameter and z fixed: their slots read 0
+    for (int c = tid; c < NT; c += PB_THREADS) grad[g.off_theta + c] = 0.0;
+    for (int i = tid; i < M; i += PB_THREADS) grad[g.off_z + i] = 0.0;
+    return;
+  }
+  // Kbar = W^T Abar; T1 = Lbar = -tril(Kbar A^T); T2 = Phi(L^T Lbar) (lower, halved diagonal); T1 = T2 W; S-block
+  // reuse: X = W^T T1 -> T2, Kuu_bar = sym(X)
+  pb_gemm(M, B, M, PbMat{s.W, 1, M}, PbMat{s.Ab, B, 1}, s.Kb, B, 1.0, 0.0, tiles);
+  pb_gemm(M, M, B, PbMat{s.Kb, B, 1}, PbMat{s.A, 1, B}, s.T1, M, -1.0, 0.0, tiles);
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    if (j > i) s.T1[e] = 0.0;
+  }
+  __syncthreads();
+  pb_gemm(M, M, M, PbMat{s.L, 1, M}, PbMat{s.T1, M, 1}, s.T2, M, 1.0, 0.0, tiles);
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    if (j > i) s.T2[e] = 0.0;
+    else if (j == i) s.T2[e] *= 0.5;
+  }
+  __syncthreads();
+  pb_gemm(M, M, M, PbMat{s.T2, M, 1}, PbMat{s.W, M, 1}, s.T1, M, 1.0, 0.0, tiles);
+  pb_gemm(M, M, M, PbMat{s.W, 1, M}, PbMat{s.T1, M, 1}, s.T2, M, 1.0, 0.0, tiles);
+  // contraction: thread i < M takes row i of Kuu and Kuf; theta partial sums per row in LDS, summed over rows in order
+  const bool want_theta = g.need_theta != 0;
+  if (tid < M) {
+    const int i = tid;
+    double* acc = thacc + (int64_t)i * maxth;
+    for (int c = 0; c < NT; c++) acc[c] = 0.0;
+    double dz = 0.0;
+    const double zi = zs[i];
+    for (int j = 0; j < M; j++) {
+      const double w = 0.5 * (s.T2[(int64_t)i * M + j] + s.T2[(int64_t)j * M + i]);
+      const double dk = pb_kern_grad(g.type, g.m, th, zi, zs[j], w, acc, want_theta);
+      if (j != i) dz = fma(2.0 * w, dk, dz);
+    }
+    for (int n = 0; n < B; n++) {
+      const double w = s.Kb[(int64_t)i * B + n];
+      dz = fma(w, pb_kern_grad(g.type, g.m, th, zi, xs[n], w, acc, want_theta), dz);
+    }
+    grad[g.off_z + i] = dz;
+  }
+  __syncthreads();
+  if (tid < NT) {
+    double a = 0.0;
+    for (int i = 0; i < M; i++) a += thacc[(int64_t)i * maxth + tid];
+    // Kdiag: d/dv of v (stationary) or v sum e (spectral mixtures), d/de_k = v
+    double sgv = 0.0;
+    for (int n = 0; n < B; n++) sgv += gv[n];
+    const bool energy = (g.type == GP_KERN_MERCER_MATERN12SM || g.type == GP_KERN_MATERN32SM);
+    if (tid == 0) {
+      double e = 1.0;
+      if (energy) { e = th[2]; for (int p = 1; p < g.m; p++) e += th[2 + p]; }
+      a = fma(sgv, e, a);
+    } else if (energy && tid >= 2 && tid < 2 + g.m) {
+      a = fma(sgv, th[0], a);
+    }
+    grad[g.off_theta + tid] = a;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// TF-1.2 Adam on the concatenated free state (opt.hip adam_kernel, per-model step size and freeze)
+__device__ __forceinline__ double pb_softplus_pos(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))) + 1e-6; }
+
+__global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs, double* __restrict__ params,
+                                                         const double* __restrict__ grad, const uint8_t* __restrict__ tc,
+                                                         double* __restrict__ m, double* __restrict__ v,
+                                                         const int32_t* __restrict__ owner, const int32_t* __restrict__ status,
+                                                         const double* __restrict__ lr_t, int64_t n, double b1, double b2,
+                                                         double eps, GpLogisticTable T) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const uint8_t t = tc[i];
+    const int k = owner[i];
+    if (t == 2 || status[k] != 0) continue;
+    double x = fs[i];
+    double g = -grad[i];
+    if (t == 1) g *= 1.0 / (1.0 + exp(-x));
+    else if (t >= 3) { const double s = 1.0 / (1.0 + exp(-x)); g *= (T.b[t - 3] - T.a[t - 3]) * s * (1.0 - s); }
+    const double mi = b1 * m[i] + (1.0 - b1) * g;
+    const double vi = b2 * v[i] + (1.0 - b2) * g * g;
+    m[i] = mi; v[i] = vi;
+    x -= lr_t[k] * mi / (sqrt(vi) + eps);
+    fs[i] = x;
+    params[i] = (t == 1) ? pb_softplus_pos(x)
+                         : (t >= 3 ? T.a[t - 3] + (T.b[t - 3] - T.a[t - 3]) / (1.0 + exp(-x)) : x);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+static size_t pb_fwd_lds(const gp_pdgpb_plan_s* p) {
+  return ((size_t)p->maxM * p->maxM + p->maxB + 2 * (size_t)p->maxM + PB_TILE_DOUBLES) * sizeof(double);
+}
+static int pb_maxth(const gp_pdgpb_plan_s* p) { return GP_THETA_LEN(p->maxm); }
+static size_t pb_bwd_lds(const gp_pdgpb_plan_s* p) {
+  return ((size_t)p->maxB + p->maxM + PB_TILE_DOUBLES + (size_t)p->maxM * pb_maxth(p)) * sizeof(double);
+}
+
+static gp_status pb_eval(gp_pdgpb_plan_s* p, const double* params, const double* x, const double* y, const int32_t* idx,
+                         double* elbo, double* grad) {
+  gp_handle h = p->h;
+  hipLaunchKernelGGL(pdgpb_fwd_kernel, dim3(p->G), dim3(PB_THREADS), pb_fwd_lds(p), h->stream, p->d_gps, params, x, idx,
+                     p->d_scr, p->d_fm, p->d_fv, p->d_kl, p->d_status, p->jitter, p->maxM, p->maxB);
+  GP_HIP_CHECK(h, hipGetLastError());
+  hipLaunchKernelGGL(pdgpb_lik_kernel, dim3(p->nm), dim3(PB_THREADS), 0, h->stream, p->d_models, params, y, idx, p->d_fm,
+                     p->d_fv, p->d_kl, p->d_gm, p->d_gv, grad, elbo);
+  GP_HIP_CHECK(h, hipGetLastError());
+  if (!grad) return GP_OK;
+  hipLaunchKernelGGL(pdgpb_bwd_kernel, dim3(p->G), dim3(PB_THREADS), pb_bwd_lds(p), h->stream, p->d_gps, params, x, idx,
+                     p->d_scr, p->d_gm, p->d_gv, grad, p->maxM, p->maxB, pb_maxth(p));
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
+extern "C" {
+
+gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan* out) {
+  if (!h || !out) return GP_ERR_BAD_ARG;
+  *out = nullptr;
+  if (!cfg || cfg->num_models < 1 || !cfg->num_sources || !cfg->batch || !cfg->nlin || !cfg->num_data || !cfg->M ||
+      !cfg->kern_type || !cfg->partials)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_create: bad config");
+  gp_pdgpb_plan_s* p = new gp_pdgpb_plan_s();
+  p->h = h; p->nm = cfg->num_models; p->jitter = cfg->jitter;
+  int64_t off = 0, f = 0, scr = 0, bo = 0;
+  int g = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int P = cfg->num_sources[k], B = cfg->batch[k], nl = cfg->nlin[k];
+    if (P < 1 || B < 1 || B > PB_MAX_B || nl < 0 || nl > 2 || !(cfg->num_data[k] >= B)) {
+      delete p;
+      return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_create: a model's minibatch is outside 1..1024 frames or its "
+                                            "sources / nonlinearity are invalid (train it with gp_pdgp_*)");
+    }
+    PbModel md{P, B, nl, g, off, off, 0, f, bo, cfg->num_data[k]};
+    p->owner.push_back(k);
+    off += 1;
+    for (int r = 0; r < 2 * P; r++, g++) {
+      const int M = cfg->M[g], t = cfg->kern_type[g], m = cfg->partials[g];
+      const bool sm = (t == GP_KERN_MERCER_MATERN12SM || t == GP_KERN_MATERN32SM);
+      const bool ok_t = sm || t == GP_KERN_MATERN12 || t == GP_KERN_MATERN32 || t == GP_KERN_MATERN52 || t == GP_KERN_RBF;
+      if (M < 1 || M > PB_MAX_M || !ok_t || (sm && (m < 1 || m > PB_MAX_PARTIALS)) || (!sm && m != 0)) {
+        delete p;
+        return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_create: a latent GP has M > 128 or a kernel type the batch does not "
+                                              "take (train it with gp_pdgp_*)");
+      }
+      PbGp gp;
+      gp.model = k; gp.row = r; gp.type = t; gp.m = m; gp.M = M; gp.B = B; gp.need_theta = 1; gp.need_z = 1;
+      gp.off_theta = off; off += GP_THETA_LEN(m);
+      gp.off_z = off; off += M;
+      gp.off_qmu = off; off += M;
+      gp.off_qsq = off; off += (int64_t)M * M;
+      gp.ws = scr; scr += gp_align_up(pb_gp_scratch(M, B), 32);
+      gp.f_off = f + (int64_t)r * B;
+      gp.batch_off = bo;
+      p->gps.push_back(gp);
+      p->maxM = std::max(p->maxM, M);
+      p->maxm = std::max(p->maxm, m);
+    }
+    md.p1 = off;
+    for (int64_t i = md.p0 + 1; i < off; i++) p->owner.push_back(k);
+    f += 2 * (int64_t)P * B;
+    bo += B;
+    p->maxB = std::max(p->maxB, B);
+    p->models.push_back(md);
+  }
+  p->G = g; p->nparams = off; p->f_len = f; p->scratch = scr; p->sumB = (int)bo;
+  if (pb_fwd_lds(p) > 160 * 1024 || pb_bwd_lds(p) > 160 * 1024) {
+    delete p;
+    return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_create: shapes exceed the workgroup's LDS");
+  }
+  *out = p;
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_destroy(gp_pdgpb_plan p) { delete p; return GP_OK; }
+int64_t gp_pdgpb_num_params(gp_pdgpb_plan p) { return p ? p->nparams : 0; }
+
+gp_status gp_pdgpb_layout(gp_pdgpb_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu, int64_t* off_qsqrt) {
+  if (!p || g < 0 || g >= p->G || !off_theta || !off_z || !off_qmu || !off_qsqrt) return GP_ERR_BAD_ARG;
+  const PbGp& gp = p->gps[g];
+  *off_theta = gp.off_theta; *off_z = gp.off_z; *off_qmu = gp.off_qmu; *off_qsqrt = gp.off_qsq;
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_set_grad_needs(gp_pdgpb_plan p, int32_t g, int32_t need_theta, int32_t need_z) {
+  if (!p || g < 0 || g >= p->G) return GP_ERR_BAD_ARG;
+  p->gps[g].need_theta = need_theta != 0;
+  p->gps[g].need_z = need_z != 0;
+  p->ready = false;      // descriptors go up again at the next call
+  return GP_OK;
+}
+
+static size_t pb_region_bytes(const gp_pdgpb_plan_s* p) {
+  size_t b = 0;
+  b += gp_align_up(p->gps.size() * sizeof(PbGp), 256);
+  b += gp_align_up(p->models.size() * sizeof(PbModel), 256);
+  b += gp_align_up((size_t)p->nparams * sizeof(int32_t), 256);
+  b += gp_align_up((size_t)p->nm * sizeof(int32_t), 256);
+  b += 4 * gp_align_up((size_t)p->f_len * sizeof(double), 256);
+  b += gp_align_up((size_t)p->G * sizeof(double), 256);
+  b += gp_align_up((size_t)p->nparams * sizeof(double), 256);
+  b += gp_align_up((size_t)p->nm * sizeof(double), 256);
+  b += gp_align_up((size_t)p->scratch * sizeof(double), 256);
+  return b;
+}
+
+size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p) { return p ? pb_region_bytes(p) + 256 : 0; }
+
+gp_status gp_pdgpb_set_workspace(gp_pdgpb_plan p, void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!workspace || bytes < gp_pdgpb_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_workspace: workspace too small or not 256-byte aligned");
+  GpArena ar(workspace, bytes);
+  p->d_gps = ar.take<PbGp>(p->gps.size());
+  p->d_models = ar.take<PbModel>(p->models.size());
+  p->d_owner = ar.take<int32_t>(p->nparams);
+  p->d_status = ar.take<int32_t>(p->nm);
+  p->d_fm = ar.take<double>(p->f_len); p->d_fv = ar.take<double>(p->f_len);
+  p->d_gm = ar.take<double>(p->f_len); p->d_gv = ar.take<double>(p->f_len);
+  p->d_kl = ar.take<double>(p->G);
+  p->d_grad = ar.take<double>(p->nparams);
+  p->d_elbo = ar.take<double>(p->nm);
+  p->d_scr = ar.take<double>(p->scratch);
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_workspace: arena overflow");
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_owner, p->owner.data(), p->owner.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
+  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_fwd_lds(p)));
+  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_bwd_lds(p)));
+  p->ready = false;
+  return GP_OK;
+}
+
+static gp_status pb_upload(gp_pdgpb_plan_s* p) {
+  if (p->ready) return GP_OK;
+  gp_handle h = p->h;
+  if (!p->d_gps) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb: no workspace set");
+  // synchronous: the host vectors may change (gp_pdgpb_set_grad_needs) while a copy from pageable memory is pending
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_gps, p->gps.data(), p->gps.size() * sizeof(PbGp), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_models, p->models.data(), p->models.size() * sizeof(PbModel), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  p->ready = true;
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_objective(gp_pdgpb_plan p, const double* params, const double* x, const double* y, const int32_t* idx,
+                             double* elbo_dev, double* grad) {
+  if (!p || !params || !x || !y || !idx || !elbo_dev) return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_objective: bad argument") : GP_ERR_BAD_ARG;
+  GP_CHECK(pb_upload(p));
+  return pb_eval(p, params, x, y, idx, elbo_dev, grad);
+}
+
+gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
+                        const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
+                        double beta1, double beta2, double eps) {
+  if (!p || !free_state || !params || !tcode || !m || !v || !x || !y || !idx || !lr_t || steps < 0)
+    return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_adam: bad argument") : GP_ERR_BAD_ARG;
+  GP_CHECK(pb_upload(p));
+  gp_handle h = p->h;
+  const int64_t n = p->nparams;
+  const int blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n + 255) / 256));
+  for (int s = 0; s < steps; s++) {
+    GP_CHECK(pb_eval(p, params, x, y, idx + (int64_t)s * p->sumB, p->d_elbo, p->d_grad));
+    hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
+                       p->d_owner, p->d_status, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps, h->logistic);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear) {
+  if (!p || !host_status) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->d_status) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_not_pd: no workspace set");
+  GP_HIP_CHECK(h, hipMemcpyAsync(host_status, p->d_status, p->nm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k < p->nm; k++)
+    if (host_status[k] != 0) host_status[k] = 1 + (0x7fffffff - host_status[k]);
+  if (clear) GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
+  return GP_OK;
+}
+
+}  // extern "C"

@@ -214,6 +214,42 @@ class Pdgp(Parameterized):
             _, blk = gp_exchange_layout(2 * self.num_sources, self._shard[1], self._max_batch)
             self._gp_send = h.zeros(blk)
             self._gp_recv = h.zeros(blk * self._shard[1])
+        pending = self.__dict__.pop("_pending_adam", None)
+        if pending is not None:
+            self._set_adam_state(pending)
+
+    def _param_order(self):
+        """every Param of the flat vector in the order of _segments(), without a plan"""
+        out = [self.likelihood.variance]
+        for kern, z, q_mu, q_sqrt in self._gps():
+            out += list(kern.theta_params()) + [z, q_mu, q_sqrt]
+        return out
+
+    def _adam_state(self):
+        """[(m, v)] per Param in _param_order(): the Adam moments the next optimize() continues from (None: fresh)"""
+        if self._plan is None:
+            return self.__dict__.get("_pending_adam")
+        m, v = self._adam_m.cpu().numpy(), self._adam_v.cpu().numpy()
+        return [(m[o:o + p.size].copy(), v[o:o + p.size].copy()) for o, p in self._segments()]
+
+    def _set_adam_state(self, state):
+        """install Adam moments trained elsewhere (pdgp_batch.optimize_many), one (m, v) per Param in _param_order();
+        kept by position (so that a copy of the model keeps them too) until the plan exists"""
+        if self._plan is None:
+            self._pending_adam = [(np.array(a, copy=True), np.array(b, copy=True)) for a, b in state]
+            return
+        m, v = self._adam_m.cpu().numpy(), self._adam_v.cpu().numpy()
+        for (o, p), (ms, vs) in zip(self._segments(), state):
+            m[o:o + p.size], v[o:o + p.size] = ms, vs
+        t = self._handle.torch
+        self._adam_m.copy_(t.as_tensor(m))
+        self._adam_v.copy_(t.as_tensor(v))
+
+    def _invalidate_device_state(self):
+        """Params were written from outside: drop the packed copy and the memoised prediction factorisation"""
+        self._packed_key = None
+        self._pred_state = None
+        self._pred_memo = None
 
     def _segments(self):
         """[(offset, Param)] of every Param in the flat vector"""

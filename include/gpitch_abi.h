@@ -74,6 +74,7 @@ typedef struct gp_handle_s* gp_handle;
 typedef struct gp_pdgp_plan_s* gp_pdgp_plan;
 typedef struct gp_sgpr_plan_s* gp_sgpr_plan;
 typedef struct gp_sgprb_plan_s* gp_sgprb_plan;
+typedef struct gp_pdgpb_plan_s* gp_pdgpb_plan;
 
 /* ---- runtime -------------------------------------------------------------------------------- */
 /* replaces gpitch.init_settings / the global TF session (gpitch/methods.py:155-180).
@@ -461,6 +462,53 @@ size_t gp_sgprb_predict_source_workspace_bytes(gp_sgprb_plan p, int32_t count, i
 gp_status gp_sgprb_predict_source(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
                                   const double* Xnew, int32_t n, int32_t count, double* mean, double* var,
                                   void* workspace, size_t workspace_bytes);
+
+/* ---- many small, independent Pdgp models per launch sequence ------------------------------------------------------
+ * replaces the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)  over single-pitch models trained
+ * one by one (init_models.py:74-121; demo-modgp.py:44-45): each step is Pdgp.build_likelihood (pdgp.py:113-170) and its
+ * gradient, then tf.train.AdamOptimizer's update, for EVERY model, as four launches whatever the number of models.
+ * Whitened, float64, unsharded models only; per latent GP M <= 128, minibatch <= 1024 frames, kernels Matern12 / 32 / 52,
+ * RBF, MercerMatern12sm, Matern32sm (others: GP_ERR_UNSUPPORTED; train them with gp_pdgp_*).
+ * Latent GPs are listed model by model, each model's rows in the order [g_0..g_{P-1}, f_0..f_{P-1}].
+ * Parameter vector: per model [ noise_var | per latent GP: theta | z | q_mu | q_sqrt (M x M) ], models concatenated. */
+typedef struct {
+  int32_t num_models;
+  const int32_t* num_sources;     /* host, [num_models]: P */
+  const int32_t* batch;           /* host, [num_models]: minibatch frames B (the pdgp.py:76-77 minibatch_size) */
+  const int32_t* nlin;            /* host, [num_models]: GP_NLIN_* */
+  const double* num_data;         /* host, [num_models]: N (the ELBO's N / B scale, pdgp.py:166-170) */
+  const int32_t* M;               /* host, [sum 2 P]: inducing points per latent GP */
+  const int32_t* kern_type;       /* host, [sum 2 P]: GP_KERN_* */
+  const int32_t* partials;        /* host, [sum 2 P] */
+  double jitter;                  /* pdgp.py:14 */
+} gp_pdgpb_config;
+gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan* out);
+gp_status gp_pdgpb_destroy(gp_pdgpb_plan p);
+int64_t gp_pdgpb_num_params(gp_pdgpb_plan p);
+/* offsets of latent GP g (global index) in the parameter vector; a model's noise variance sits right before its first GP */
+gp_status gp_pdgpb_layout(gp_pdgpb_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
+                          int64_t* off_qsqrt);
+/* as gp_pdgp_set_grad_needs: skip the hyper-parameter / z gradients of a latent GP whose Params are all `.fixed` */
+gp_status gp_pdgpb_set_grad_needs(gp_pdgpb_plan p, int32_t g, int32_t need_theta, int32_t need_z);
+/* scratch sized by the batch's own shapes (about 6 M^2 + 6 M B doubles per latent GP); 256-byte aligned */
+size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p);
+gp_status gp_pdgpb_set_workspace(gp_pdgpb_plan p, void* workspace, size_t bytes);
+/* Pdgp.build_likelihood of every model (pdgp.py:133-170) on its minibatch and, when grad != NULL, dELBO / dparams.
+ * x, y: every model's frames, concatenated (device); idx: [sum B] int32 device indices into x / y, model by model, each
+ * model's frames in time order; elbo_dev: [num_models]. */
+gp_status gp_pdgpb_objective(gp_pdgpb_plan p, const double* params, const double* x, const double* y, const int32_t* idx,
+                             double* elbo_dev, double* grad);
+/* `steps` Adam steps (gp_adam_step's update, demo-modgp.py:44-45) of every model: step s evaluates on
+ * idx + s * sum B and moves model k with step size lr_t[s * num_models + k] = lr sqrt(1 - b2^t) / (1 - b1^t) of that
+ * model's t.  A model whose Cholesky fails is frozen from that step on (free state, params and moments untouched) while
+ * the others go on; gp_pdgpb_not_pd reports it. */
+gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
+                        const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
+                        double beta1, double beta2, double eps);
+/* per model: 0, or 1 + 128 row + pivot of its failed Cholesky with the smallest (latent GP row, pivot index) since the
+ * status was last cleared (TF's InvalidArgumentError in the reference); synchronises the stream.  clear != 0 resets the
+ * status afterwards. */
+gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear);
 
 /* ---- kernel learning from an isolated-note recording (the drivers' init_kernel(train=True) branch,
  *      gpitch/transcription.py:176-195, gpitch/separation.py:185-204) -------------------------------------------------

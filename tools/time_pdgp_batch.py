@@ -1,0 +1,79 @@
+"""Steps per second of many demo-size Pdgp models trained together (gpitch_amd.optimize_many) against the same
+models trained one after another by Pdgp.optimize.
+
+Every model is the real-audio notebook model (tests/golden/init_liv_real_audio.npz: 32 000 frames, init_liv -> 109
+inducing points, Matern32 + MercerMatern12sm with 5 partials, minibatch 100, z fixed).  Device-synchronised wall
+time, warm-up steps excluded; one JSON line per W on stdout.
+
+    python tools/time_pdgp_batch.py [--models 1 12 88] [--steps 200] [--warmup 20] [--seq-steps 100]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def demo_model():
+    import gpitch_amd
+    from gpitch_amd.kernels import Matern32
+    from gpitch_amd.matern12_spectral_mixture import MercerMatern12sm
+    d = np.load(os.path.join(ROOT, "tests", "golden", "init_liv_real_audio.npz"))
+    y = np.asarray(d["y"], dtype=np.float64).reshape(-1, 1)
+    fs = int(d["fs"])
+    x = np.linspace(0., (y.size - 1.) / fs, y.size).reshape(-1, 1)
+    f0 = gpitch_amd.find_ideal_f0([str(d["fname"])])
+    z, _ = gpitch_amd.init_liv(x=x, y=y, win_size=31, thres=0.033, dec=9)
+    kcom = MercerMatern12sm(input_dim=1, energy=np.ones(5), frequency=f0 * np.arange(1, 6))
+    m = gpitch_amd.pdgp.Pdgp(x=x, y=y, z=z, kern=[[Matern32(1, lengthscales=1.0, variance=1.0)], [kcom]],
+                             minibatch_size=100)
+    m.za.fixed = True
+    m.zc.fixed = True
+    return m
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", type=int, nargs="+", default=[1, 12, 88])
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--seq-steps", type=int, default=100, help="Adam steps per model on the one-after-another path")
+    a = ap.parse_args()
+    import copy
+    import torch
+    import gpitch_amd
+    from gpitch_amd.pdgp_batch import PdgpBatch
+    tok = gpitch_amd.train.AdamOptimizer(0.0025)
+    base = demo_model()
+    for W in a.models:
+        models = [copy.deepcopy(base) for _ in range(W)]
+        batch = PdgpBatch(models)
+        batch.optimize(tok, a.warmup)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batch.optimize(tok, a.steps)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        seq = [copy.deepcopy(base) for _ in range(W)]
+        for m in seq:
+            m.optimize(method=tok, maxiter=a.warmup)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for m in seq:
+            m.optimize(method=tok, maxiter=a.seq_steps)
+        torch.cuda.synchronize()
+        ds = time.perf_counter() - t0
+        print(json.dumps({"models": W, "steps": a.steps, "batched_steps_per_s": a.steps / dt,
+                          "batched_ms_per_step": 1e3 * dt / a.steps, "batched_model_steps_per_s": W * a.steps / dt,
+                          "sequential_model_steps_per_s": W * a.seq_steps / ds,
+                          "sequential_ms_per_model_step": 1e3 * ds / (W * a.seq_steps),
+                          "speedup": (W * a.steps / dt) / (W * a.seq_steps / ds)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
