@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "gp_segment_gram_workspace_bytes", "gp_segment_gram", "gp_autocorr", "gp_kernfit_eval",
     "gp_pdgpb_create", "gp_pdgpb_destroy", "gp_pdgpb_num_params", "gp_pdgpb_layout", "gp_pdgpb_set_grad_needs",
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
+    "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
 ]
 
 
@@ -226,6 +227,9 @@ def load_library():
         "gp_pdgpb_objective": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "gp_pdgpb_adam": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl]),
         "gp_pdgpb_not_pd": (i32, [vp, C.POINTER(i32), i32]),
+        "gp_pdgpb_predict_workspace_bytes": (sz, [vp]),
+        "gp_pdgpb_predict_prepare": (i32, [vp, vp, vp, sz]),
+        "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol

@@ -10,6 +10,7 @@
 //   pdgpb_lik_kernel   one workgroup per model: Gauss-Hermite expectations, d/dfmean, d/dfvar, d/dnoise, the ELBO
 //   pdgpb_bwd_kernel   one workgroup per latent GP: gradients of q_mu, tril(Lq), the hyper-parameters and z
 //   pdgpb_adam_kernel  the TF-1.2 Adam update over the concatenated free state, frozen per model after a failed Cholesky
+// and, for  [m.predict_act_n_com(x) for m, x in zip(models, xnews)], the prediction kernels pdgpb_pred_* further down.
 // Every reduction is one thread's sequential loop or a fixed tree: two runs give bit-identical results.
 #include "common.h"
 #include "gh_quad.h"
@@ -26,7 +27,7 @@
 struct PbGp {
   int model, row, type, m, M, B, need_theta, need_z;
   int64_t off_theta, off_z, off_qmu, off_qsq;
-  int64_t ws;          // this GP's scratch (doubles from the plan's scratch base)
+  int64_t ws;          // this GP's scratch (doubles from the plan's scratch base); prediction plans: its G block
   int64_t f_off;       // row offset in the model-major fmean / fvar / gm / gv arrays
   int64_t batch_off;   // offset of the model's frames in the step's index vector
 };
@@ -37,8 +38,18 @@ struct PbModel {
   double num_data;
 };
 
+// prediction (gp_pdgpb_predict): one record per latent GP and call
+struct PbPredGp {
+  int64_t x_off;       // the model's first frame in xnew
+  int64_t out_off;     // this GP's row in fmean / fvar (model-major: per model 2P rows of n frames)
+  int64_t src_off;     // activation rows: the source's row in mean_source (per model P rows of n frames)
+  int64_t n;           // frames of the model
+  int32_t P, nlin;
+};
+
 struct gp_pdgpb_plan_s {
   gp_handle h = nullptr;
+  bool predict_only = false;     // created with cfg->batch == NULL
   int nm = 0, G = 0, maxM = 0, maxB = 0, maxm = 0, sumB = 0;
   double jitter = 1e-6;
   int64_t nparams = 0, f_len = 0, scratch = 0;
@@ -50,6 +61,13 @@ struct gp_pdgpb_plan_s {
   double *d_fm = nullptr, *d_fv = nullptr, *d_gm = nullptr, *d_gv = nullptr, *d_kl = nullptr, *d_grad = nullptr,
          *d_elbo = nullptr, *d_scr = nullptr;
   bool ready = false;
+  // prediction-only plans: G blocks (doubles; PbGp::ws is a GP's offset among them), the per-call records, and the
+  // workspace / parameters of the last gp_pdgpb_predict_prepare
+  int64_t pred_g = 0;
+  std::vector<PbPredGp> pgs;
+  std::vector<int64_t> tiles;
+  PbPredGp* d_pgs = nullptr; int64_t* d_tiles = nullptr; double* d_G = nullptr;
+  const void* pred_ws = nullptr; const double* pred_params = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -229,34 +247,18 @@ __device__ inline PbScr pb_scr(double* base, int M, int B) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// forward: one workgroup per latent GP.  LDS: [maxM^2 factor | maxB frames | maxM z | maxM tmp | gemm tiles]
-__global__ void __launch_bounds__(PB_THREADS) pdgpb_fwd_kernel(const PbGp* __restrict__ gps, const double* __restrict__ params,
-                                                               const double* __restrict__ xall, const int32_t* __restrict__ idx,
-                                                               double* __restrict__ scr_base, double* __restrict__ fmean,
-                                                               double* __restrict__ fvar, double* __restrict__ kl,
-                                                               int32_t* __restrict__ status, double jitter, int maxM, int maxB) {
-  extern __shared__ double pb_sm[];
-  const PbGp g = gps[blockIdx.x];
-  const int M = g.M, B = g.B, tid = threadIdx.x;
-  double* Ls = pb_sm;
-  double* xs = Ls + (int64_t)maxM * maxM;
-  double* zs = xs + maxB;
-  double* tmp = zs + maxM;
-  double* tiles = tmp + maxM;
-  __shared__ int bad_pivot;
-  const double* th = params + g.off_theta;
-  const double* z = params + g.off_z;
-  const double* qmu = params + g.off_qmu;
-  const double* qsq = params + g.off_qsq;
-  PbScr s = pb_scr(scr_base + g.ws, M, B);
-  for (int n = tid; n < B; n += PB_THREADS) xs[n] = xall[idx[g.batch_off + n]];
-  for (int i = tid; i < M; i += PB_THREADS) zs[i] = z[i];
-  if (tid == 0) bad_pivot = -1;
-  __syncthreads();
+// Kuu + jitter I of one latent GP factored and inverted in LDS by the whole workgroup (pdgpb_fwd_kernel and
+// pdgpb_pred_prep_kernel): on return Ls (M x M, row-major ld = M) holds W = L^-1, lower, zeros above the diagonal; L
+// itself is copied to Lcopy (global) when COPY_L.  zs: the z of the GP in LDS; tmp: M doubles of LDS.
+template <bool COPY_L>
+__device__ __forceinline__ void pb_factor_invert(int type, int m, const double* __restrict__ th, const double* zs, int M,
+                                                 double jitter, double* Ls, double* tmp, int& bad_pivot,
+                                                 int32_t* __restrict__ status, int model, int row, double* Lcopy) {
+  const int tid = threadIdx.x;
   // Kuu + jitter I (pdgp.py:126-129 / GPflow conditional), full matrix, row-major ld = M
   for (int e = tid; e < M * M; e += PB_THREADS) {
     const int i = e / M, j = e % M;
-    Ls[e] = pb_kern(g.type, g.m, th, zs[i], zs[j]) + (i == j ? jitter : 0.0);
+    Ls[e] = pb_kern(type, m, th, zs[i], zs[j]) + (i == j ? jitter : 0.0);
   }
   __syncthreads();
   // right-looking Cholesky in place (lower); a non-positive pivot is recorded and replaced by 1 so that the rest of the
@@ -285,8 +287,9 @@ __global__ void __launch_bounds__(PB_THREADS) pdgpb_fwd_kernel(const PbGp* __res
   __syncthreads();
   // status word of the model: 0, or INT_MAX - (128 row + pivot); the maximum keeps the failure with the smallest
   // (row, pivot) whatever order the model's workgroups finish in
-  if (tid == 0 && bad_pivot >= 0) atomicMax(&status[g.model], 0x7fffffff - (PB_MAX_M * g.row + bad_pivot));
-  for (int e = tid; e < M * M; e += PB_THREADS) s.L[e] = Ls[e];
+  if (tid == 0 && bad_pivot >= 0) atomicMax(&status[model], 0x7fffffff - (PB_MAX_M * row + bad_pivot));
+  if (COPY_L)
+    for (int e = tid; e < M * M; e += PB_THREADS) Lcopy[e] = Ls[e];
   __syncthreads();
   // W = L^-1 in place (LAPACK trti2, lower, columns from the last): W[j+1:, j] = -W[j+1:, j+1:] L[j+1:, j] / L[j, j]
   for (int j = M - 1; j >= 0; j--) {
@@ -302,6 +305,34 @@ __global__ void __launch_bounds__(PB_THREADS) pdgpb_fwd_kernel(const PbGp* __res
     if (tid == 0) Ls[j * M + j] = -ajj;
     __syncthreads();
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// forward: one workgroup per latent GP.  LDS: [maxM^2 factor | maxB frames | maxM z | maxM tmp | gemm tiles]
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_fwd_kernel(const PbGp* __restrict__ gps, const double* __restrict__ params,
+                                                               const double* __restrict__ xall, const int32_t* __restrict__ idx,
+                                                               double* __restrict__ scr_base, double* __restrict__ fmean,
+                                                               double* __restrict__ fvar, double* __restrict__ kl,
+                                                               int32_t* __restrict__ status, double jitter, int maxM, int maxB) {
+  extern __shared__ double pb_sm[];
+  const PbGp g = gps[blockIdx.x];
+  const int M = g.M, B = g.B, tid = threadIdx.x;
+  double* Ls = pb_sm;
+  double* xs = Ls + (int64_t)maxM * maxM;
+  double* zs = xs + maxB;
+  double* tmp = zs + maxM;
+  double* tiles = tmp + maxM;
+  __shared__ int bad_pivot;
+  const double* th = params + g.off_theta;
+  const double* z = params + g.off_z;
+  const double* qmu = params + g.off_qmu;
+  const double* qsq = params + g.off_qsq;
+  PbScr s = pb_scr(scr_base + g.ws, M, B);
+  for (int n = tid; n < B; n += PB_THREADS) xs[n] = xall[idx[g.batch_off + n]];
+  for (int i = tid; i < M; i += PB_THREADS) zs[i] = z[i];
+  if (tid == 0) bad_pivot = -1;
+  __syncthreads();
+  pb_factor_invert<true>(g.type, g.m, th, zs, M, jitter, Ls, tmp, bad_pivot, status, g.model, g.row, s.L);
   for (int e = tid; e < M * M; e += PB_THREADS) s.W[e] = Ls[e];
   // tril(q_sqrt) (band_part in GPflow's conditional / gauss_kl)
   for (int e = tid; e < M * M; e += PB_THREADS) {
@@ -550,12 +581,195 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// prediction: Pdgp.predict_act_n_com (pdgp.py:190-208; GPflow conditional, whiten=True, full_cov=False) of every model at
+// its own inputs.  Two launches and the source means:
+//   pdgpb_pred_prep_kernel    one workgroup per latent GP: Kuu + jitter I factored and inverted in LDS (pb_factor_invert),
+//                             then G = [W ; tril(Lq)^T W] (W = L^-1) to the workspace: 2 Mp x Mp stored transposed,
+//                             Mp = M rounded up to 16, zero rows and columns beyond M
+//   pdgpb_pred_kernel         one workgroup per (latent GP, tile of PB_PT frames), GP-major: the Kuf tile in LDS,
+//                             [A ; Lq^T A] = G Kuf_tile on v_mfma_f64_16x16x4_f64, per frame fmean = A^T q_mu and
+//                             fvar = Kdiag - sum A^2 + sum (Lq^T A)^2 (GPflow's expression: A's entries are bounded by
+//                             sqrt(Kdiag), so nothing of size |W|^2 ~ 1 / jitter is formed or cancelled)
+//   pdgpb_pred_source_kernel  mean_source = nlin(fmean_act) * fmean_com (lik.hip mean_source_kernel, per model)
+// Every sum is one lane's sequential loop or a fixed butterfly: two calls give bit-identical results, and a model's results
+// do not depend on the other models of the call nor on how its frames are split between calls.
+#define PB_PT 64      // frames per (latent GP, frame tile) entry: four column groups of 16
+#define PB_PRED_THREADS 512
+
+typedef double pb_d4 __attribute__((ext_vector_type(4)));
+typedef double pb_d2 __attribute__((ext_vector_type(2)));
+
+__host__ __device__ inline int pb_pad16(int M) { return (M + 15) & ~15; }
+__host__ __device__ inline int64_t pb_pred_g_doubles(int M) { return 2 * (int64_t)pb_pad16(M) * pb_pad16(M); }
+
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_pred_prep_kernel(const PbGp* __restrict__ gps, const double* __restrict__ params,
+                                                                     double* __restrict__ g_all, int32_t* __restrict__ status,
+                                                                     double jitter, int maxM) {
+  extern __shared__ double pb_sm[];
+  const PbGp g = gps[blockIdx.x];
+  const int M = g.M, Mp = pb_pad16(M), tid = threadIdx.x;
+  double* Ls = pb_sm;
+  double* zs = Ls + (int64_t)maxM * maxM;
+  double* tmp = zs + maxM;
+  __shared__ int bad_pivot;
+  const double* th = params + g.off_theta;
+  const double* z = params + g.off_z;
+  const double* qsq = params + g.off_qsq;
+  for (int i = tid; i < M; i += PB_THREADS) zs[i] = z[i];
+  if (tid == 0) bad_pivot = -1;
+  __syncthreads();
+  pb_factor_invert<false>(g.type, g.m, th, zs, M, jitter, Ls, tmp, bad_pivot, status, g.model, g.row, nullptr);
+  // G[r][k]: r < M: W[r][k];  r = Mp + i, i < M: (tril(Lq)^T W)[i][k] = sum_{j >= max(i, k)} Lq[j][i] W[j][k] in ascending j
+  // (the strict upper triangle of q_sqrt is masked away, matrix_band_part in GPflow's conditional).  Stored transposed,
+  // GT[k][r] (ld 2 Mp): the 16 rows of an MFMA fragment are 128 contiguous bytes
+  double* Gt = g_all + g.ws;
+  for (int e = tid; e < 2 * Mp * Mp; e += PB_THREADS) {
+    const int k = e / (2 * Mp), r = e % (2 * Mp);
+    double v = 0.0;
+    if (k < M) {
+      if (r < M) {
+        v = Ls[r * M + k];
+      } else if (r >= Mp && r - Mp < M) {
+        const int i = r - Mp;
+        for (int j = max(i, k); j < M; j++) v = fma(qsq[(int64_t)j * M + i], Ls[j * M + k], v);
+      }
+    }
+    Gt[e] = v;
+  }
+}
+
+// the entry's products and per-frame sums.  Wavefront w owns the 16 frames 16 (w & 3) .. + 15 of the tile and one half of
+// G's row tiles: h = w >> 2 = 0 the NB tiles of W (A = W Kuf: fm = A^T q_mu, sa = sum A^2), h = 1 those of tril(Lq)^T W
+// (sb = sum (Lq^T A)^2).  v_mfma_f64_16x16x4_f64 operands as gemm_wave.hip: A lane (kq, lc) = G[row lc][k0 + kq], B lane
+// (kq, lc) = Kuf[k0 + kq][frame lc]; C/D: acc[a][r] = (G Kuf)[h Mp + 16 a + 4 r + kq][16 (w & 3) + lc].  G^T (L2-resident,
+// shared by the GP's tiles) is read straight from memory, four 128-byte rows per load; four wavefronts per SIMD hide its
+// latency.
+template <int NB>
+__device__ __forceinline__ void pb_pred_products(const double* __restrict__ Gt, const double* Ks, const double* qs, int w,
+                                                 int lane, double& fm, double& sq) {
+  constexpr int Mp = 16 * NB;
+  const int lc = lane & 15, kq = lane >> 4, h = w >> 2;
+  pb_d4 acc[NB];
+#pragma unroll
+  for (int a = 0; a < NB; a++) acc[a] = pb_d4{0.0, 0.0, 0.0, 0.0};
+  const double* ga = Gt + (int64_t)kq * 2 * Mp + h * Mp + lc;
+  const double* kb = Ks + kq * PB_PT + 16 * (w & 3) + lc;
+#pragma unroll 2
+  for (int k0 = 0; k0 < Mp; k0 += 4) {
+    double af[NB];
+#pragma unroll
+    for (int a = 0; a < NB; a++) af[a] = ga[(int64_t)k0 * 2 * Mp + 16 * a];
+    const double bf = kb[k0 * PB_PT];
+#pragma unroll
+    for (int a = 0; a < NB; a++) acc[a] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf, acc[a], 0, 0, 0);
+  }
+  fm = 0.0; sq = 0.0;
+#pragma unroll
+  for (int a = 0; a < NB; a++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const double v = acc[a][r];
+      if (h == 0) fm = fma(v, qs[16 * a + 4 * r + kq], fm);
+      sq = fma(v, v, sq);
+    }
+}
+
+// the latent GP of entry b: the last g with tile_start[g] <= b (tile_start ascending, G + 1 entries)
+__device__ __forceinline__ int pb_entry_gp(const int64_t* __restrict__ tile_start, int G, int64_t b) {
+  int lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tile_start[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// LDS: [maxMp x PB_PT Kuf tile | PB_PT frames | maxMp z | maxMp q_mu]; eight wavefronts, two workgroups per CU
+__global__ void __launch_bounds__(PB_PRED_THREADS) __attribute__((amdgpu_waves_per_eu(4))) pdgpb_pred_kernel(const PbGp* __restrict__ gps, const PbPredGp* __restrict__ pgs,
+                                                                        const int64_t* __restrict__ tile_start, int G,
+                                                                        const double* __restrict__ params, const double* __restrict__ g_all,
+                                                                        const double* __restrict__ xnew, double* __restrict__ fmean,
+                                                                        double* __restrict__ fvar, int maxMp) {
+  extern __shared__ double pb_sm[];
+  __shared__ double sb_tile[PB_PT];
+  const int64_t b = blockIdx.x;
+  const int gi = pb_entry_gp(tile_start, G, b);
+  const PbGp g = gps[gi];
+  const PbPredGp pg = pgs[gi];
+  const int M = g.M, Mp = pb_pad16(M), tid = threadIdx.x;
+  const int64_t t0 = (b - tile_start[gi]) * PB_PT;
+  const int nv = (int)min((int64_t)PB_PT, pg.n - t0);        // frames of this tile (ragged tail: masked)
+  double* Ks = pb_sm;
+  double* xs = Ks + (int64_t)maxMp * PB_PT;
+  double* zs = xs + PB_PT;
+  double* qs = zs + maxMp;
+  const double* th = params + g.off_theta;
+  const double* z = params + g.off_z;
+  const double* qmu = params + g.off_qmu;
+  for (int c = tid; c < PB_PT; c += PB_PRED_THREADS) xs[c] = c < nv ? xnew[pg.x_off + t0 + c] : 0.0;
+  for (int i = tid; i < Mp; i += PB_PRED_THREADS) {
+    zs[i] = i < M ? z[i] : 0.0;
+    qs[i] = i < M ? qmu[i] : 0.0;
+  }
+  __syncthreads();
+  // Kuf tile (Mp x PB_PT, row-major): zero rows beyond M and columns beyond the model's frames
+  for (int e = tid; e < Mp * PB_PT; e += PB_PRED_THREADS) {
+    const int i = e / PB_PT, c = e % PB_PT;
+    Ks[e] = (i < M && c < nv) ? pb_kern(g.type, g.m, th, zs[i], xs[c]) : 0.0;
+  }
+  __syncthreads();
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const double* Gt = g_all + g.ws;
+  double fm = 0.0, sq = 0.0;
+  switch (Mp >> 4) {
+    case 1: pb_pred_products<1>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 2: pb_pred_products<2>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 3: pb_pred_products<3>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 4: pb_pred_products<4>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 5: pb_pred_products<5>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 6: pb_pred_products<6>(Gt, Ks, qs, w, lane, fm, sq); break;
+    case 7: pb_pred_products<7>(Gt, Ks, qs, w, lane, fm, sq); break;
+    default: pb_pred_products<8>(Gt, Ks, qs, w, lane, fm, sq); break;
+  }
+  // the four lanes of a frame (kq = 0..3) combined by a fixed butterfly: (kq 0 + 1) + (kq 2 + 3) in every lane
+  fm += __shfl_xor(fm, 16); fm += __shfl_xor(fm, 32);
+  sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
+  const int c = 16 * (w & 3) + (lane & 15);
+  if (w >= 4 && lane < 16) sb_tile[c] = sq;
+  __syncthreads();
+  if (w < 4 && lane < 16 && c < nv) {
+    fmean[pg.out_off + t0 + c] = fm;
+    fvar[pg.out_off + t0 + c] = (pb_kdiag(g.type, g.m, th) - sq) + sb_tile[c];
+  }
+}
+
+// mean_source over the same entries: the activation rows' entries form nlin(g_i) f_i for their frames, the others return
+__global__ void __launch_bounds__(PB_PT) pdgpb_pred_source_kernel(const PbGp* __restrict__ gps, const PbPredGp* __restrict__ pgs,
+                                                                  const int64_t* __restrict__ tile_start, int G,
+                                                                  const double* __restrict__ fmean, double* __restrict__ src) {
+  const int64_t b = blockIdx.x;
+  const int gi = pb_entry_gp(tile_start, G, b);
+  const PbPredGp pg = pgs[gi];
+  if (gps[gi].row >= pg.P) return;
+  const int64_t n = (b - tile_start[gi]) * PB_PT + threadIdx.x;
+  if (n >= pg.n) return;
+  double s, ds;
+  nlin_eval(pg.nlin, fmean[pg.out_off + n], s, ds);
+  src[pg.src_off + n] = s * fmean[pg.out_off + (int64_t)pg.P * pg.n + n];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 static size_t pb_fwd_lds(const gp_pdgpb_plan_s* p) {
   return ((size_t)p->maxM * p->maxM + p->maxB + 2 * (size_t)p->maxM + PB_TILE_DOUBLES) * sizeof(double);
 }
 static int pb_maxth(const gp_pdgpb_plan_s* p) { return GP_THETA_LEN(p->maxm); }
 static size_t pb_bwd_lds(const gp_pdgpb_plan_s* p) {
   return ((size_t)p->maxB + p->maxM + PB_TILE_DOUBLES + (size_t)p->maxM * pb_maxth(p)) * sizeof(double);
+}
+static size_t pb_prep_lds(const gp_pdgpb_plan_s* p) { return ((size_t)p->maxM * p->maxM + 2 * (size_t)p->maxM) * sizeof(double); }
+static size_t pb_pred_lds(const gp_pdgpb_plan_s* p) {
+  const size_t mp = pb_pad16(p->maxM);
+  return (mp * PB_PT + PB_PT + 2 * mp) * sizeof(double);
 }
 
 static gp_status pb_eval(gp_pdgpb_plan_s* p, const double* params, const double* x, const double* y, const int32_t* idx,
@@ -579,22 +793,23 @@ extern "C" {
 gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan* out) {
   if (!h || !out) return GP_ERR_BAD_ARG;
   *out = nullptr;
-  if (!cfg || cfg->num_models < 1 || !cfg->num_sources || !cfg->batch || !cfg->nlin || !cfg->num_data || !cfg->M ||
+  const bool pred = cfg && !cfg->batch;          // a prediction-only plan
+  if (!cfg || cfg->num_models < 1 || !cfg->num_sources || !cfg->nlin || (!pred && !cfg->num_data) || !cfg->M ||
       !cfg->kern_type || !cfg->partials)
     return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_create: bad config");
   gp_pdgpb_plan_s* p = new gp_pdgpb_plan_s();
-  p->h = h; p->nm = cfg->num_models; p->jitter = cfg->jitter;
+  p->h = h; p->nm = cfg->num_models; p->jitter = cfg->jitter; p->predict_only = pred;
   int64_t off = 0, f = 0, scr = 0, bo = 0;
   int g = 0;
   for (int k = 0; k < p->nm; k++) {
-    const int P = cfg->num_sources[k], B = cfg->batch[k], nl = cfg->nlin[k];
-    if (P < 1 || B < 1 || B > PB_MAX_B || nl < 0 || nl > 2 || !(cfg->num_data[k] >= B)) {
+    const int P = cfg->num_sources[k], B = pred ? 0 : cfg->batch[k], nl = cfg->nlin[k];
+    if (P < 1 || nl < 0 || nl > 2 || (!pred && (B < 1 || B > PB_MAX_B || !(cfg->num_data[k] >= B)))) {
       delete p;
       return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_create: a model's minibatch is outside 1..1024 frames or its "
                                             "sources / nonlinearity are invalid (train it with gp_pdgp_*)");
     }
-    PbModel md{P, B, nl, g, off, off, 0, f, bo, cfg->num_data[k]};
-    p->owner.push_back(k);
+    PbModel md{P, B, nl, g, off, off, 0, f, bo, pred ? 0.0 : cfg->num_data[k]};
+    if (!pred) p->owner.push_back(k);     // the Adam kernel's parameter -> model map (training only)
     off += 1;
     for (int r = 0; r < 2 * P; r++, g++) {
       const int M = cfg->M[g], t = cfg->kern_type[g], m = cfg->partials[g];
@@ -611,7 +826,8 @@ gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan
       gp.off_z = off; off += M;
       gp.off_qmu = off; off += M;
       gp.off_qsq = off; off += (int64_t)M * M;
-      gp.ws = scr; scr += gp_align_up(pb_gp_scratch(M, B), 32);
+      if (pred) { gp.ws = p->pred_g; p->pred_g += gp_align_up(pb_pred_g_doubles(M), 32); }
+      else { gp.ws = scr; scr += gp_align_up(pb_gp_scratch(M, B), 32); }
       gp.f_off = f + (int64_t)r * B;
       gp.batch_off = bo;
       p->gps.push_back(gp);
@@ -619,14 +835,15 @@ gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan
       p->maxm = std::max(p->maxm, m);
     }
     md.p1 = off;
-    for (int64_t i = md.p0 + 1; i < off; i++) p->owner.push_back(k);
+    if (!pred)
+      for (int64_t i = md.p0 + 1; i < off; i++) p->owner.push_back(k);
     f += 2 * (int64_t)P * B;
     bo += B;
     p->maxB = std::max(p->maxB, B);
     p->models.push_back(md);
   }
   p->G = g; p->nparams = off; p->f_len = f; p->scratch = scr; p->sumB = (int)bo;
-  if (pb_fwd_lds(p) > 160 * 1024 || pb_bwd_lds(p) > 160 * 1024) {
+  if (pred ? pb_prep_lds(p) > 160 * 1024 : (pb_fwd_lds(p) > 160 * 1024 || pb_bwd_lds(p) > 160 * 1024)) {
     delete p;
     return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_create: shapes exceed the workgroup's LDS");
   }
@@ -666,11 +883,12 @@ static size_t pb_region_bytes(const gp_pdgpb_plan_s* p) {
   return b;
 }
 
-size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p) { return p ? pb_region_bytes(p) + 256 : 0; }
+size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p) { return (p && !p->predict_only) ? pb_region_bytes(p) + 256 : 0; }
 
 gp_status gp_pdgpb_set_workspace(gp_pdgpb_plan p, void* workspace, size_t bytes) {
   if (!p) return GP_ERR_BAD_ARG;
   gp_handle h = p->h;
+  if (p->predict_only) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_set_workspace: a prediction-only plan (its workspace goes to gp_pdgpb_predict_prepare)");
   if (!workspace || bytes < gp_pdgpb_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_workspace: workspace too small or not 256-byte aligned");
   GpArena ar(workspace, bytes);
@@ -707,7 +925,8 @@ static gp_status pb_upload(gp_pdgpb_plan_s* p) {
 
 gp_status gp_pdgpb_objective(gp_pdgpb_plan p, const double* params, const double* x, const double* y, const int32_t* idx,
                              double* elbo_dev, double* grad) {
-  if (!p || !params || !x || !y || !idx || !elbo_dev) return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_objective: bad argument") : GP_ERR_BAD_ARG;
+  if (!p || !params || !x || !y || !idx || !elbo_dev || p->predict_only)
+    return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_objective: bad argument or a prediction-only plan") : GP_ERR_BAD_ARG;
   GP_CHECK(pb_upload(p));
   return pb_eval(p, params, x, y, idx, elbo_dev, grad);
 }
@@ -715,8 +934,8 @@ gp_status gp_pdgpb_objective(gp_pdgpb_plan p, const double* params, const double
 gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
                         const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
                         double beta1, double beta2, double eps) {
-  if (!p || !free_state || !params || !tcode || !m || !v || !x || !y || !idx || !lr_t || steps < 0)
-    return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_adam: bad argument") : GP_ERR_BAD_ARG;
+  if (!p || !free_state || !params || !tcode || !m || !v || !x || !y || !idx || !lr_t || steps < 0 || p->predict_only)
+    return p ? gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_adam: bad argument or a prediction-only plan") : GP_ERR_BAD_ARG;
   GP_CHECK(pb_upload(p));
   gp_handle h = p->h;
   const int64_t n = p->nparams;
@@ -733,12 +952,104 @@ gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, con
 gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear) {
   if (!p || !host_status) return GP_ERR_BAD_ARG;
   gp_handle h = p->h;
-  if (!p->d_status) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_not_pd: no workspace set");
+  if (!p->d_status) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_not_pd: no workspace set (prediction: no gp_pdgpb_predict_prepare yet)");
   GP_HIP_CHECK(h, hipMemcpyAsync(host_status, p->d_status, p->nm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   for (int k = 0; k < p->nm; k++)
     if (host_status[k] != 0) host_status[k] = 1 + (0x7fffffff - host_status[k]);
   if (clear) GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
+  return GP_OK;
+}
+
+// ---- prediction ----------------------------------------------------------------------------------------------------
+static size_t pb_pred_region_bytes(const gp_pdgpb_plan_s* p) {
+  size_t b = 0;
+  b += gp_align_up(p->gps.size() * sizeof(PbGp), 256);
+  b += gp_align_up((size_t)p->nm * sizeof(int32_t), 256);
+  b += gp_align_up(p->gps.size() * sizeof(PbPredGp), 256);
+  b += gp_align_up((p->gps.size() + 1) * sizeof(int64_t), 256);
+  b += gp_align_up((size_t)p->pred_g * sizeof(double), 256);
+  return b;
+}
+
+size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p) { return (p && p->predict_only) ? pb_pred_region_bytes(p) + 256 : 0; }
+
+gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->predict_only || !params)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_prepare: bad argument or a training plan (create the plan with cfg->batch == NULL)");
+  if (!workspace || bytes < gp_pdgpb_predict_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_prepare: workspace too small or not 256-byte aligned");
+  GpArena ar(workspace, bytes);
+  p->d_gps = ar.take<PbGp>(p->gps.size());
+  p->d_status = ar.take<int32_t>(p->nm);
+  p->d_pgs = ar.take<PbPredGp>(p->gps.size());
+  p->d_tiles = ar.take<int64_t>(p->gps.size() + 1);
+  p->d_G = ar.take<double>(p->pred_g);
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_prepare: arena overflow");
+  p->pred_ws = nullptr;
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_gps, p->gps.data(), p->gps.size() * sizeof(PbGp), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
+  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_pred_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_prep_lds(p)));
+  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_pred_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_pred_lds(p)));
+  hipLaunchKernelGGL(pdgpb_pred_prep_kernel, dim3(p->G), dim3(PB_THREADS), pb_prep_lds(p), h->stream, p->d_gps, params, p->d_G,
+                     p->d_status, p->jitter, p->maxM);
+  GP_HIP_CHECK(h, hipGetLastError());
+  // the descriptors were copied from pageable host memory: wait before the host vectors can change
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  p->pred_ws = workspace;
+  p->pred_params = params;
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off, double* fmean,
+                           double* fvar, double* mean_source, void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->predict_only || !xnew_off)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument or a training plan (create the plan with cfg->batch == NULL)");
+  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
+  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: xnew_off[0] must be 0");
+  p->pgs.resize(p->G);
+  p->tiles.resize(p->G + 1);
+  int64_t fbase = 0, sbase = 0, tiles = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int64_t n = xnew_off[k + 1] - xnew_off[k];
+    if (n < 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: xnew_off must not decrease");
+    const PbModel& md = p->models[k];
+    for (int r = 0; r < 2 * md.P; r++) {
+      const int g = md.g0 + r;
+      PbPredGp& pg = p->pgs[g];
+      pg.x_off = xnew_off[k];
+      pg.out_off = fbase + (int64_t)r * n;
+      pg.src_off = r < md.P ? sbase + (int64_t)r * n : -1;
+      pg.n = n;
+      pg.P = md.P;
+      pg.nlin = md.nlin;
+      p->tiles[g] = tiles;
+      tiles += (n + PB_PT - 1) / PB_PT;
+    }
+    fbase += 2 * (int64_t)md.P * n;
+    sbase += (int64_t)md.P * n;
+  }
+  p->tiles[p->G] = tiles;
+  if (tiles == 0) return GP_OK;
+  if (!xnew || !fmean || !fvar) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument");
+  if (tiles > 0x7fffffff) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: more than 2^31 - 1 frame tiles in one call");
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_pgs, p->pgs.data(), p->pgs.size() * sizeof(PbPredGp), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_tiles, p->tiles.data(), p->tiles.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  // pageable host vectors again: the next call rewrites them
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  hipLaunchKernelGGL(pdgpb_pred_kernel, dim3((unsigned)tiles), dim3(PB_PRED_THREADS), pb_pred_lds(p), h->stream, p->d_gps, p->d_pgs,
+                     p->d_tiles, p->G, params, p->d_G, xnew, fmean, fvar, pb_pad16(p->maxM));
+  GP_HIP_CHECK(h, hipGetLastError());
+  if (mean_source) {
+    hipLaunchKernelGGL(pdgpb_pred_source_kernel, dim3((unsigned)tiles), dim3(PB_PT), 0, h->stream, p->d_gps, p->d_pgs, p->d_tiles,
+                       p->G, fmean, mean_source);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
   return GP_OK;
 }
 

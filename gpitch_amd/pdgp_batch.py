@@ -8,6 +8,12 @@ init_kernel_with_trained_models (gpitch/init_models.py:74-121) and the segments 
 model as that loop would: parameters, Adam step count and moments, and the minibatch generators advanced by the same
 draws (GPflow's final fresh-minibatch fun / jac evaluation included).  Whitened float64 unsharded models, Adam only;
 everything else is refused by check_batchable() before any device work.
+
+    preds = predict_many(models, xnews)
+
+replaces  [m.predict_act_n_com(x) for m, x in zip(models, xnews)]  with one factorisation launch for every latent GP and
+one launch for every (latent GP, frame tile) pair, without building any single-model engine plan (check_predictable()
+takes the same models, without the minibatch limit).
 """
 import ctypes as C
 
@@ -26,43 +32,49 @@ _KERNELS = {_lib.KERN_MATERN12: "Matern12", _lib.KERN_MATERN32: "Matern32", _lib
 _SINGLE = "train this model on its own with Pdgp.optimize"
 
 
+def _check_models(models, entry, single, minibatch):
+    """the scope both batched entries share (check_batchable, check_predictable): a list of distinct whitened float64
+    unsharded Pdgp models whose latent GPs the batch's kernels take; `minibatch` adds the training minibatch limit"""
+    from .pdgp import Pdgp
+    models = list(models)
+    if not models:
+        raise ValueError("%s needs at least one model" % entry)
+    if len(set(id(m) for m in models)) != len(models):
+        raise ValueError("%s: the same model appears twice in the list" % entry)
+    for k, m in enumerate(models):
+        if not isinstance(m, Pdgp):
+            raise ValueError("%s: item %d is not a Pdgp" % (entry, k))
+        if not m.whiten:
+            raise NotImplementedError("model %d: whiten=False is not batched; %s" % (k, single))
+        if m._bits != 64:
+            raise NotImplementedError("model %d: float_type %r is not batched (float64 only); %s" % (k, m._bits, single))
+        if m._shard is not None:
+            raise NotImplementedError("model %d: sharded models are not batched; %s" % (k, single))
+        nlin_code(m.nlinfun)
+        if minibatch and (m.minibatch_size > MAX_MINIBATCH or min(m.minibatch_size, m.num_data) > MAX_MINIBATCH):
+            raise ValueError("model %d: minibatch of %d frames > %d; %s" % (k, m.minibatch_size, MAX_MINIBATCH, single))
+        for kern, M in [(m.kern_act[i], m.num_inducing_a[i]) for i in range(m.num_sources)] + \
+                       [(m.kern_com[i], m.num_inducing_c[i]) for i in range(m.num_sources)]:
+            if M > MAX_M:
+                raise ValueError("model %d: %d inducing points in one latent GP > %d; %s" % (k, M, MAX_M, single))
+            t = getattr(kern, "type_code", None)
+            if t not in _KERNELS:
+                raise NotImplementedError("model %d: kernel %s is not batched (takes %s); %s"
+                                          % (k, type(kern).__name__, ", ".join(sorted(_KERNELS.values())), single))
+            mp = int(kern.num_partials)
+            if t in (_lib.KERN_MERCER_MATERN12SM, _lib.KERN_MATERN32SM) and not 1 <= mp <= MAX_PARTIALS:
+                raise ValueError("model %d: %d partials outside 1..%d; %s" % (k, mp, MAX_PARTIALS, single))
+    return models
+
+
 def check_batchable(models, method=None, callback=None):
     """Host-only scope check of optimize_many / PdgpBatch: raises NotImplementedError (a feature the batch does not
     have) or ValueError (a shape it does not take) naming the single-model path.  No device work."""
-    from .pdgp import Pdgp
     if method is not None and not isinstance(method, AdamOptimizer):
         raise NotImplementedError("optimize_many trains with AdamOptimizer only (got %r); %s" % (method, _SINGLE))
     if callback is not None:
         raise NotImplementedError("optimize_many takes no callback; %s" % _SINGLE)
-    models = list(models)
-    if not models:
-        raise ValueError("optimize_many needs at least one model")
-    if len(set(id(m) for m in models)) != len(models):
-        raise ValueError("optimize_many: the same model appears twice in the list")
-    for k, m in enumerate(models):
-        if not isinstance(m, Pdgp):
-            raise ValueError("optimize_many: item %d is not a Pdgp" % k)
-        if not m.whiten:
-            raise NotImplementedError("model %d: whiten=False is not batched; %s" % (k, _SINGLE))
-        if m._bits != 64:
-            raise NotImplementedError("model %d: float_type %r is not batched (float64 only); %s" % (k, m._bits, _SINGLE))
-        if m._shard is not None:
-            raise NotImplementedError("model %d: sharded models are not batched; %s" % (k, _SINGLE))
-        nlin_code(m.nlinfun)
-        if m.minibatch_size > MAX_MINIBATCH or min(m.minibatch_size, m.num_data) > MAX_MINIBATCH:
-            raise ValueError("model %d: minibatch of %d frames > %d; %s" % (k, m.minibatch_size, MAX_MINIBATCH, _SINGLE))
-        for kern, M in [(m.kern_act[i], m.num_inducing_a[i]) for i in range(m.num_sources)] + \
-                       [(m.kern_com[i], m.num_inducing_c[i]) for i in range(m.num_sources)]:
-            if M > MAX_M:
-                raise ValueError("model %d: %d inducing points in one latent GP > %d; %s" % (k, M, MAX_M, _SINGLE))
-            t = getattr(kern, "type_code", None)
-            if t not in _KERNELS:
-                raise NotImplementedError("model %d: kernel %s is not batched (takes %s); %s"
-                                          % (k, type(kern).__name__, ", ".join(sorted(_KERNELS.values())), _SINGLE))
-            mp = int(kern.num_partials)
-            if t in (_lib.KERN_MERCER_MATERN12SM, _lib.KERN_MATERN32SM) and not 1 <= mp <= MAX_PARTIALS:
-                raise ValueError("model %d: %d partials outside 1..%d; %s" % (k, mp, MAX_PARTIALS, _SINGLE))
-    return models
+    return _check_models(models, "optimize_many", _SINGLE, minibatch=True)
 
 
 def _gps(m):
@@ -330,3 +342,185 @@ def optimize_many(models, method=None, maxiter=1000, callback=None):
     method = AdamOptimizer() if method is None else method
     models = check_batchable(models, method, callback)
     return PdgpBatch(models).optimize(method, maxiter)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# prediction: Pdgp.predict_act_n_com of many models (csrc/pdgp_batch.hip pdgpb_pred_*, gp_pdgpb_predict)
+MAX_PREDICT_FRAMES = 1 << 22   # latent-GP frames (2 P x frames, summed over models) per gp_pdgpb_predict launch
+PREDICT_TILE = 64              # frames per (latent GP, frame tile) entry of pdgpb_pred_kernel (PB_PT)
+_SINGLE_PREDICT = "predict this model on its own with Pdgp.predict_act_n_com"
+
+
+def _frames(x, k):
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 1):
+        raise ValueError("predict_many: inputs of model %d have shape %r, not (n,) or (n, 1)" % (k, a.shape))
+    return a.reshape(-1)
+
+
+def check_predictable(models, xnews):
+    """Host-only scope check of predict_many, in the style of check_batchable: NotImplementedError (a feature the batch
+    does not have) or ValueError (a shape it does not take) naming the single-model path.  No minibatch limit: the
+    prediction does not use the minibatch.  Returns the models and their inputs as flat float64 arrays; `xnews` is a
+    list with one array per model or one array for every model."""
+    models = _check_models(models, "predict_many", _SINGLE_PREDICT, minibatch=False)
+    if isinstance(xnews, (list, tuple)):
+        if len(xnews) != len(models):
+            raise ValueError("predict_many: %d input arrays for %d models" % (len(xnews), len(models)))
+        xs = [_frames(x, k) for k, x in enumerate(xnews)]
+    else:
+        x = _frames(xnews, 0)
+        xs = [x] * len(models)
+    return models, xs
+
+
+def predict_layout(num_sources, counts, tile=PREDICT_TILE):
+    """The work list and output offsets of one gp_pdgpb_predict call (what the call builds from xnew_off), host only.
+    Latent GPs are listed model by model, rows [g_0..g_{P-1}, f_0..f_{P-1}].  Returns a dict of int64 arrays:
+      tile_start [G + 1]  first (latent GP, frame tile) entry of each GP, GP-major; the last item is the entry count
+      gp_out [G]          each GP's first element in fmean / fvar (model-major: per model 2 P rows of n_k frames)
+      gp_src [G]          activation rows: the source's first element in mean_source (P rows of n_k per model), else -1
+      out_base, src_base [num_models + 1]  each model's block in fmean / fvar and in mean_source
+      x_off [num_models + 1]  each model's first frame in xnew (the call's xnew_off)"""
+    P = np.asarray(num_sources, dtype=np.int64)
+    n = np.asarray(counts, dtype=np.int64)
+    assert P.shape == n.shape and np.all(P >= 1) and np.all(n >= 0)
+    cum = lambda a: np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
+    out_base, src_base, x_off = cum(2 * P * n), cum(P * n), cum(n)
+    gp_out, gp_src, ntile = [], [], []
+    for k in range(P.size):
+        for r in range(2 * int(P[k])):
+            gp_out.append(out_base[k] + r * n[k])
+            gp_src.append(src_base[k] + r * n[k] if r < P[k] else -1)
+            ntile.append((n[k] + tile - 1) // tile)
+    i64 = lambda a: np.asarray(a, dtype=np.int64)
+    return dict(tile_start=cum(i64(ntile)), gp_out=i64(gp_out), gp_src=i64(gp_src), out_base=out_base,
+                src_base=src_base, x_off=x_off)
+
+
+def predict_chunks(num_sources, counts, limit=MAX_PREDICT_FRAMES):
+    """Split the frames of one predict_many call into launches of at most `limit` latent-GP frames (2 P per frame of a
+    model; a single frame of a model with 2 P > limit goes alone).  Each chunk is a (num_models, 2) int64 array of
+    (first frame, frame count) per model, models in order, frames in order; together they cover every frame once."""
+    nm = len(counts)
+    chunks, cur, used = [], np.zeros((nm, 2), dtype=np.int64), 0
+    for k in range(nm):
+        per = 2 * int(num_sources[k])
+        start, left = 0, int(counts[k])
+        while left > 0:
+            take = min(left, (limit - used) // per)
+            if take == 0:
+                if used == 0:
+                    take = 1
+                else:
+                    chunks.append(cur)
+                    cur, used = np.zeros((nm, 2), dtype=np.int64), 0
+                    continue
+            cur[k] = (start, take)
+            start, left, used = start + take, left - take, used + take * per
+    if used > 0 or not chunks:
+        chunks.append(cur)
+    return chunks
+
+
+def predict_many(models, xnews):
+    """Pdgp.predict_act_n_com of every model at its own inputs, all models together:
+
+        preds = predict_many(models, xnews)
+        preds[k] == models[k].predict_act_n_com(xnews[k])   # (mu_a, var_a, mu_c, var_c, m_src), lists of (n_k, 1)
+
+    xnews: one array per model or one array for every model.  Reads each model's current Params and changes nothing
+    (no Param, flag, generator or Adam state; no single-model engine plan, no prediction memo).  One launch factors
+    every latent GP's Kuu, then one launch per MAX_PREDICT_FRAMES chunk predicts every (latent GP, frame tile) pair and
+    one more forms the source means.  A failed Kuu factorisation raises NotPositiveDefiniteError naming the model."""
+    models, xs = check_predictable(models, xnews)
+    h = _lib.default_handle()
+    t = h.torch
+    nm = len(models)
+    P = [m.num_sources for m in models]
+    counts = [x.size for x in xs]
+    i32 = C.c_int32
+    gps = [g for m in models for g in _gps(m)]
+    keep = dict(P=(i32 * nm)(*P), nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in models]),
+                M=(i32 * len(gps))(*[g[1].size for g in gps]), kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
+                mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
+    from .pdgp import jitter
+    cfg = _lib.PdgpBatchConfig(nm, keep["P"], None, keep["nlin"], None, keep["M"], keep["kt"], keep["mp"], jitter)
+    segs, base = [], 0
+    for m in models:
+        sm, n = model_segments(m, base)
+        segs += sm
+        base += n
+    plan = C.c_void_p()
+    h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
+    try:
+        if int(h.lib.gp_pdgpb_num_params(plan)) != base:
+            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
+        # every Param written once into a page-locked vector, copied to the device on the stream
+        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
+        host = ppin.numpy()
+        for off, p in segs:
+            v = p.value.reshape(-1)
+            host[off:off + v.size] = v
+        params = ppin.to(h.device, non_blocking=True)
+        nbytes = h.lib.gp_pdgpb_predict_workspace_bytes(plan)
+        ws = h.workspace(nbytes)
+        h.check(h.lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
+        # host results in the layout of one call over every frame: a call that fits one launch lands there directly,
+        # the chunks of a larger one are copied into it; every model's arrays are views of these three buffers
+        whole = predict_layout(P, counts)
+        chunks = predict_chunks(P, counts, MAX_PREDICT_FRAMES)
+        fm_all, fv_all, src_all = (np.zeros(int(whole["out_base"][-1])), np.zeros(int(whole["out_base"][-1])),
+                                   np.zeros(int(whole["src_base"][-1])))
+        for chunk in chunks:
+            c = chunk[:, 1]
+            if not c.any():
+                continue
+            lay = predict_layout(P, c)
+            # transfers go through page-locked staging buffers (torch's caching host allocator): pageable copies of
+            # tens of MB cost several times the kernels
+            xpin = t.empty(int(lay["x_off"][-1]), dtype=t.float64, pin_memory=True)
+            np.concatenate([xs[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy())
+            xd = xpin.to(h.device, non_blocking=True)
+            nf, ns = int(lay["out_base"][-1]), int(lay["src_base"][-1])
+            buf = h.empty(2 * nf + ns)                  # fmean | fvar | mean_source: one copy back to the host
+            off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
+            h.check(h.lib.gp_pdgpb_predict(plan, params.data_ptr(), xd.data_ptr(), off, buf.data_ptr(),
+                                           buf[nf:].data_ptr(), buf[2 * nf:].data_ptr(), ws.data_ptr(), ws.numel()))
+            pin = t.empty(2 * nf + ns, dtype=t.float64, pin_memory=True)
+            pin.copy_(buf, non_blocking=True)
+            h.sync()
+            got = pin.numpy().copy()                    # the results live in ordinary memory; the staging goes back
+            del xpin, pin
+            fm_h, fv_h, src_h = got[:nf], got[nf:2 * nf], got[2 * nf:]
+            if len(chunks) == 1:
+                fm_all, fv_all, src_all = fm_h, fv_h, src_h
+                continue
+            for k, (s, n) in enumerate(chunk):
+                if n == 0:
+                    continue
+                for dst, part, key, rows in ((fm_all, fm_h, "out_base", 2 * P[k]), (fv_all, fv_h, "out_base", 2 * P[k]),
+                                             (src_all, src_h, "src_base", P[k])):
+                    d = dst[whole[key][k]:whole[key][k + 1]].reshape(rows, counts[k])
+                    d[:, s:s + n] = part[lay[key][k]:lay[key][k + 1]].reshape(rows, n)
+        del ppin
+        bad = (C.c_int32 * nm)()
+        h.check(h.lib.gp_pdgpb_not_pd(plan, bad, 1))
+    finally:
+        h.sync()
+        h.lib.gp_pdgpb_destroy(plan)
+    for k in range(nm):
+        if bad[k]:
+            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "predict_many: model %d: Cholesky failed: %s"
+                                                % (k, _describe_not_pd(bad[k])))
+    out = []
+    for k in range(nm):
+        Pk, n, ob, sb = P[k], counts[k], whole["out_base"], whole["src_base"]
+        fm = fm_all[ob[k]:ob[k + 1]].reshape(2 * Pk, n)
+        fv = fv_all[ob[k]:ob[k + 1]].reshape(2 * Pk, n)
+        src = src_all[sb[k]:sb[k + 1]].reshape(Pk, n)
+        col = lambda a, i: a[i].reshape(-1, 1)
+        out.append(([col(fm, i) for i in range(Pk)], [col(fv, i) for i in range(Pk)],
+                    [col(fm, Pk + i) for i in range(Pk)], [col(fv, Pk + i) for i in range(Pk)],
+                    [col(src, i) for i in range(Pk)]))
+    return out

@@ -474,9 +474,11 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan p, const double* params, const d
 typedef struct {
   int32_t num_models;
   const int32_t* num_sources;     /* host, [num_models]: P */
-  const int32_t* batch;           /* host, [num_models]: minibatch frames B (the pdgp.py:76-77 minibatch_size) */
+  const int32_t* batch;           /* host, [num_models]: minibatch frames B (the pdgp.py:76-77 minibatch_size);
+                                     NULL: a prediction-only plan (gp_pdgpb_predict) */
   const int32_t* nlin;            /* host, [num_models]: GP_NLIN_* */
-  const double* num_data;         /* host, [num_models]: N (the ELBO's N / B scale, pdgp.py:166-170) */
+  const double* num_data;         /* host, [num_models]: N (the ELBO's N / B scale, pdgp.py:166-170); unused when
+                                     batch is NULL */
   const int32_t* M;               /* host, [sum 2 P]: inducing points per latent GP */
   const int32_t* kern_type;       /* host, [sum 2 P]: GP_KERN_* */
   const int32_t* partials;        /* host, [sum 2 P] */
@@ -509,6 +511,23 @@ gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, con
  * status was last cleared (TF's InvalidArgumentError in the reference); synchronises the stream.  clear != 0 resets the
  * status afterwards. */
 gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear);
+/* ---- prediction of many models: Pdgp.predict_act_n_com (pdgp.py:190-208) of every model at its own inputs --------------
+ * A prediction-only plan is created by gp_pdgpb_create with cfg->batch == NULL (num_data is then ignored).  It has the
+ * parameter layout of a training plan (gp_pdgpb_layout) and no training workspace: gp_pdgpb_workspace_bytes returns 0,
+ * and gp_pdgpb_set_workspace, gp_pdgpb_objective and gp_pdgpb_adam return GP_ERR_BAD_ARG on it.  The prediction entries
+ * return GP_ERR_BAD_ARG on a training plan.
+ * gp_pdgpb_predict_prepare factors Kuu + jitter I of every latent GP and stores [L^-1 ; tril(Lq)^T L^-1] in the workspace
+ * (one launch; a failed pivot goes to the per-model status that gp_pdgpb_not_pd reads).  gp_pdgpb_predict then predicts
+ * every model at its frames of xnew (device, every model's inputs concatenated; xnew_off: host, [num_models + 1],
+ * xnew_off[0] = 0, model k's frames [xnew_off[k], xnew_off[k + 1]), empty models allowed) with the parameters and
+ * workspace of the last prepare, as often as wanted.  Outputs are model-major, offsets 64-bit: per model its 2P rows
+ * [g_0..g_{P-1}, f_0..f_{P-1}] of n_k frames in fmean / fvar (GPflow conditional, full_cov = False) and its P rows
+ * nlin(mean g_i) * mean f_i in mean_source (may be NULL).  Both entries wait until their descriptors are on the device;
+ * the kernels run asynchronously on the handle's stream. */
+size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p);
+gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* workspace, size_t bytes);
+gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
+                           double* fmean, double* fvar, double* mean_source, void* workspace, size_t bytes);
 
 /* ---- kernel learning from an isolated-note recording (the drivers' init_kernel(train=True) branch,
  *      gpitch/transcription.py:176-195, gpitch/separation.py:185-204) -------------------------------------------------
