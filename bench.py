@@ -12,6 +12,11 @@ Multi-GPU (torchrun, one rank per GPU): the reference scales N by independent wi
 (window_overlap.py:194, transcription.py:265-288), so every rank owns one independent 32768-frame
 window with the full 12-pitch model (weak scaling) and the scalar ELBO is all-reduced over RCCL each
 step; there is no other data-path collective.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line with the figures
+derived from those steps alone (roofline and per-kernel figures from the timed steps' own event timers).  --full also
+measures what takes runs of its own: forward-only evaluations, the Kuf builds alone and at m = 5, BASELINE configs[2]
+(cfg3) and configs[4] (cfg5), the window loop, the torch-CPU baselines and, multi-GPU, the pitch- and GP-sharded forms.
 """
 import argparse
 import json
@@ -376,6 +381,10 @@ def main():
     ap.add_argument("--P", type=int, default=12)
     ap.add_argument("--partials", type=int, default=20)
     ap.add_argument("--lr", type=float, default=0.0025)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the extra lines (forward-only, Kuf alone and at m=5, cfg3, cfg5, "
+                         "window loop, CPU baselines; multi-GPU: pitch- and gp-sharded); the --no-* and --cpu-* options "
+                         "below select among them")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-baseline steps (after 2 warm-ups)")
     ap.add_argument("--cpu-full", type=int, default=1,
                     help="also time this many whole P-pitch CPU steps (validates the 1/P scaling; ~1 min each)")
@@ -435,7 +444,7 @@ def main():
     n_act_local = sum(1 for g in local_gps if any(g[0] is k for k in model.kern_act))
     n_com_local = len(local_gps) - n_act_local
     extra_pitch = extra_gp = None
-    if world > 1 and args.shard == "window" and not args.no_pitch_line:
+    if args.full and world > 1 and args.shard == "window" and not args.no_pitch_line:
         # the same job as ONE model spread over the ranks (strong scaling): extra keys of the same JSON line
         model = res = None
         torch.cuda.empty_cache()
@@ -454,7 +463,7 @@ def main():
         del rg
 
     forward_only = None
-    if world == 1:
+    if args.full and world == 1:
         # forward-only ELBO evaluations per second as a secondary line (fresh batch + ELBO, no gradient, no Adam)
         for _ in range(2):
             model._elbo(False, sync=False)
@@ -466,7 +475,7 @@ def main():
         dtf = time.perf_counter() - t0
         forward_only = {"value": args.steps / dtf, "unit": "ELBO evaluations/s", "ms_per_evaluation": dtf / args.steps * 1e3}
     kuf_alone = None
-    if world == 1 and args.overlap != 0 and not args.no_f32_line:
+    if args.full and world == 1 and args.overlap != 0 and not args.no_f32_line:
         # the Kuf builds alone on the device (helper stream off), forward passes of the model just timed: in the step the
         # resident Kuu factorisation holds 24 of the 256 CUs beside them
         h.check(h.lib.gp_pdgp_set_overlap(model._plan, 0))
@@ -481,7 +490,7 @@ def main():
         kuf_alone = {k: h.timers()[k] for k in ("kuf_build", "kuf_build_sm")}
         h.check(h.lib.gp_pdgp_set_overlap(model._plan, args.overlap))
     kuf_m5 = None
-    if world == 1 and (args.N, args.M, args.P) == (32768, 512, 12) and args.partials != 5 and not args.no_f32_line:
+    if args.full and world == 1 and (args.N, args.M, args.P) == (32768, 512, 12) and args.partials != 5 and not args.no_f32_line:
         # the HBM-bound regime of the spectral-mixture Kuf build (m = 5 partials, the demo's size): forward passes only
         model = res = None
         torch.cuda.empty_cache()
@@ -524,7 +533,7 @@ def main():
         m5 = None
         torch.cuda.empty_cache()
     cfg3 = None
-    if world == 1 and not args.no_f32_line and (args.N, args.M, args.P) == (32768, 512, 12) and args.float_type == "f64":
+    if args.full and world == 1 and not args.no_f32_line and (args.N, args.M, args.P) == (32768, 512, 12) and args.float_type == "f64":
         # BASELINE configs[2] at its own precision: 12-pitch transcription model, N=32768, M=256 per pitch, fp32 (an extra
         # key; the headline above stays float64).  Same step, same timing protocol; float64 beside it.
         model = res = None
@@ -682,14 +691,14 @@ def main():
             out["gp_sharded"] = extra_gp
         if cfg3 is not None:
             out["cfg3_fp32"] = cfg3
-        if world == 1 and not args.no_sgpr_lines and not args.no_f32_line and (args.N, args.M, args.P) == (32768, 512, 12):
+        if args.full and world == 1 and not args.no_sgpr_lines and not args.no_f32_line and (args.N, args.M, args.P) == (32768, 512, 12):
             # the other two workloads of the path, same run: BASELINE configs[4] and the reference's window loop
             model = res = None
             torch.cuda.empty_cache()
             out["cfg5_sgpr"] = bench_cfg5(args, not args.no_cpu)
             torch.cuda.empty_cache()
             out["windows"] = bench_windows(args, not args.no_cpu)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args)
             out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out))

@@ -34,6 +34,19 @@ def test_bench_single_process_line():
     assert abs(d["mfma_frac_step"]["achieved"]
                - d["mfma_frac_step"]["algorithmic_flops_per_step"] / (d["ms_per_step"] * 1e-3) / 1e12) < 1e-6
     assert d["config"]["workload"].startswith("pdgp ELBO step")
+    # a plain run measures nothing but its timed steps: the extra lines are --full's
+    assert "forward_only" not in d
+
+
+def test_bench_full_adds_the_extra_lines():
+    """--full: the same headline, then the lines that take runs of their own; at this size, the forward-only evaluations
+    (cfg3, cfg5, the window loop and the Kuf builds alone belong to the full-size workload, and SMALL passes --no-cpu)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--full"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    assert d["metric"] == "ELBO-steps/sec" and d["dtype"] == "f64" and d["value"] > 0 and d["steps"] == 2
+    assert d["forward_only"]["value"] > 0 and d["forward_only"]["unit"] == "ELBO evaluations/s"
 
 
 def test_bench_dumps_the_last_steps_outputs(tmp_path):
@@ -69,9 +82,9 @@ def test_bench_two_rank_rehearsal(shard, scaling):
 
 def test_bench_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2` with NO launcher around it (the driver's form of the command) must start two ranks
-    and say so; the extra pitch-sharded strong-scaling line rides on the same JSON."""
+    and say so; with --full (handed on to the ranks) the extra strong-scaling lines ride on the same JSON."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo"] + SMALL,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full"] + SMALL,
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = _json_line(r.stdout)

@@ -5,8 +5,8 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r02prof
 mkdir -p $O
-B="--no-cpu --no-f32-line"
-echo "== bench default" && timeout -k 10 300 python3 bench.py --no-cpu --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
+B="--full --no-cpu --no-f32-line"
+echo "== bench default" && timeout -k 10 300 python3 bench.py --full --no-cpu --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "== bench overlap0" && timeout -k 10 300 python3 bench.py $B --overlap 0 --steps 20 --warmup 5 > $O/bench_overlap0.json 2> $O/bench_overlap0.err || exit 1
 echo "== bench f32" && timeout -k 10 300 python3 bench.py $B --float-type f32 --steps 20 --warmup 5 > $O/bench_f32.json 2> $O/bench_f32.err || exit 1
 echo "== stats default" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o s -- python3 bench.py $B --steps 5 --warmup 2 > $O/stats_default.log 2>&1 || exit 1

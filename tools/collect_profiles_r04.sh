@@ -7,11 +7,11 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04prof
 mkdir -p $O
-B="--no-cpu --no-f32-line --no-sgpr-lines"
+B="--full --no-cpu --no-f32-line --no-sgpr-lines"
 PARTS=${PARTS:-"bench stats pmc mfma cfg5 chol probe"}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-echo "== bench default (the driver's command + steps; whole-step CPU check included)" && timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1
+echo "== bench with every extra line (whole-step CPU check included)" && timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1
 echo "== bench overlap0" && timeout -k 10 300 python3 bench.py $B --overlap 0 --steps 20 --warmup 5 > $O/bench_overlap0.json 2> $O/bench_overlap0.err || exit 1
 echo "== bench round-3 strip kernels (strip_wave=0)" && GPITCH_AMD_SWITCHES=strip_wave=0 timeout -k 10 300 python3 bench.py $B --steps 20 --warmup 5 > $O/bench_r03_kernels.json 2> $O/bench_r03_kernels.err || exit 1
 echo "== bench round-3 strip kernels overlap0" && GPITCH_AMD_SWITCHES=strip_wave=0 timeout -k 10 300 python3 bench.py $B --overlap 0 --steps 20 --warmup 5 > $O/bench_r03_kernels_overlap0.json 2> $O/bench_r03_kernels_overlap0.err || exit 1
