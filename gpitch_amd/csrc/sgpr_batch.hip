@@ -10,12 +10,24 @@
 //
 // All windows share N, M and the kernel structure (number of kernels, their types and partial counts); parameters,
 // X, Y, Z differ.  Layout: params [W][nparams], X / Y [W][N], Z [W][M], bound [W], grad [W][nparams], contiguous.
+//
+// Ragged windows (gp_sgprb_set_inducing_counts): slot w holds k = kw[w] <= M inducing points.  M stays the plan's size
+// (every launch, grid and the recorded graph keep their geometry); the window is carried as the exact M-point problem
+//   Kuu = [K(z, z) + jitter I, 0; 0, I],   Kuf = [K(z, x); 0]
+// whose bound is the k-point window's: L, W = L^-1, chol(B) and its inverse are block diagonal with identity pad blocks,
+// A = W Kuf, H, u, c, ubar have zero pad rows, so log det chol(B) gains log 1 = 0 and E2 (= Kuu_bar) and G (= Kuf_bar)
+// have zero pad rows and columns.  The descriptors carry k where Z is read (feature tables, covariance builds, the
+// hyper-parameter contractions: their items bound rows / columns per item), so the pad rows of Z are never read;
+// sgb_kuu_pad_kernel writes the pad block of Kuu before every factorisation (the Cholesky runs in place), the pad rows
+// of the Kuf strip are zeroed once per descriptor upload (only the k-row builds write that strip afterwards).
 #include "engine.h"
 #include <string.h>
 
 struct SgbWin {            // per-window device pointers (device array, indexed by the window slot)
   const double* params; const double* Y;
   double *H, *LB, *WB, *s1, *u, *c, *scal, *E2, *Binv, *ubar, *grad;
+  double *L, *Kuf;           // Kuu -> its factor (M x M), the Kuf strip (M x ld)
+  int kw, pad_;              // inducing points of this window (<= M; the rest is identity padding)
 };
 
 struct gp_sgprb_plan_s {
@@ -46,6 +58,8 @@ struct gp_sgprb_plan_s {
   hipGraphExec_t gexec = nullptr; int graphs = 1; int64_t n_eager = 0, n_captured = 0, n_replayed = 0; int graph_count = -1;
   int np_uf = 0, np_uu = 0;
   char* d_pred_desc = nullptr; size_t pred_desc_bytes = 0;    // descriptors of gp_sgprb_predict_f (uploaded per call)
+  std::vector<int> kw;         // inducing points per window slot (all M unless gp_sgprb_set_inducing_counts said otherwise)
+  bool ragged = false;         // some kw[w] < M: the pad launches run
   ~gp_sgprb_plan_s() { if (gexec) (void)hipGraphExecDestroy(gexec); }
 };
 typedef gp_sgprb_plan_s* gp_sgprb_plan_t;
@@ -174,6 +188,27 @@ __global__ void __launch_bounds__(256) sgb_noise_grad_kernel(const SgbWin* __res
   for (int i = threadIdx.x; i < M; i += 256) w.ubar[i] /= s;
 }
 
+// Kuu pad block of the ragged windows: identity on the diagonal, zero cross terms (no jitter); grid (16, window)
+__global__ void __launch_bounds__(256) sgb_kuu_pad_kernel(const SgbWin* __restrict__ wins, int M) {
+  const SgbWin w = wins[blockIdx.y];
+  const int k = w.kw;
+  if (k >= M) return;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < (int64_t)M * M; idx += (int64_t)gridDim.x * 256) {
+    const int i = (int)(idx / M), j = (int)(idx % M);
+    if (i >= k || j >= k) w.L[idx] = (i == j ? 1.0 : 0.0);
+  }
+}
+
+// zero rows kw..M-1 of the Kuf strip (ld columns); grid (blocks, window)
+__global__ void __launch_bounds__(256) sgb_kuf_pad_kernel(const SgbWin* __restrict__ wins, int M, int64_t ld) {
+  const SgbWin w = wins[blockIdx.y];
+  const int k = w.kw;
+  if (k >= M) return;
+  const int64_t n = (int64_t)(M - k) * ld;
+  double* base = w.Kuf + (int64_t)k * ld;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * 256) base[idx] = 0.0;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------
 static inline int64_t sgb_ld(int N) { return (N + 1) & ~1; }
 static size_t sgb_feat_stride(const gp_sgprb_plan_s* p) {
@@ -241,6 +276,7 @@ gp_status gp_sgprb_create(gp_handle h, const gp_sgpr_config* cfg, int32_t num_wi
   }
   p->nparams = off;
   p->nsplit = gemm_nt_nsplit(p->M, p->N, p->W);
+  p->kw.assign(p->W, p->M);
   sgb_layout(p);
   *out = p;
   return GP_OK;
@@ -324,10 +360,11 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
     const double* par = params + (size_t)w * p->nparams;
     const double* Xw = X + (size_t)w * N; const double* Yw = Y + (size_t)w * N; const double* Zw = Z + (size_t)w * M;
     double* gw = grad + (size_t)w * p->nparams;
+    const int kw = p->kw[w];          // the window's own inducing points (M unless ragged): the Z side of every item
     SgbWin& sw = wins[w];
     sw.params = par; sw.Y = Yw; sw.H = b + p->o_H; sw.LB = b + p->o_LB; sw.WB = b + p->o_WB; sw.s1 = b + p->o_s1;
     sw.u = b + p->o_u; sw.c = b + p->o_c; sw.scal = b + p->o_scal; sw.E2 = b + p->o_E2; sw.Binv = b + p->o_Binv;
-    sw.ubar = b + p->o_ubar; sw.grad = gw;
+    sw.ubar = b + p->o_ubar; sw.grad = gw; sw.L = b + p->o_L; sw.Kuf = b + p->o_Kuf; sw.kw = kw; sw.pad_ = 0;
     pL[w] = b + p->o_L; pW[w] = b + p->o_W; pLB[w] = b + p->o_LB; pWB[w] = b + p->o_WB; pM[w] = M; pld[w] = M;
     auto prob = [&](int q) -> GemmProblem& {
       GemmProblem& r = *((GemmProblem*)(hd + p->off_prob[q]) + w);
@@ -361,20 +398,22 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
       double* ft = b + p->o_feat + (size_t)i * p->feat_stride;
       const int mp = sm_mpad(k.m);
       const size_t idx = (size_t)i * W + w;
-      feat[idx] = FeatItem{k, Zw, ft, M, 0};
-      feat[(size_t)W * P + idx] = FeatItem{k, Xw, ft + gp_align_up((size_t)2 * mp * M, 32), N, 0};
-      cov_item_fill(&cuu[idx], k, Zw, M, nullptr, M, L, M, i > 0, i == 0 ? p->jitter : 0.0, ft);
-      cov_item_fill(&cuf[idx], k, Zw, M, Xw, N, Kuf, ld, i > 0, 0.0, ft);
+      double* fx = ft + gp_align_up((size_t)2 * mp * M, 32);      // frame features (the Z table holds kw <= M points)
+      feat[idx] = FeatItem{k, Zw, ft, kw, 0};
+      feat[(size_t)W * P + idx] = FeatItem{k, Xw, fx, N, 0};
+      cov_item_fill(&cuu[idx], k, Zw, kw, nullptr, kw, L, M, i > 0, i == 0 ? p->jitter : 0.0, ft);
+      cov_item_fill(&cuf[idx], k, Zw, kw, Xw, N, Kuf, ld, i > 0, 0.0, ft);
+      if (cuf[idx].f2) cuf[idx].f2 = fx;
       double* hy = b + p->o_hyp + (size_t)i * ns * rec_uf;
       double* hyuu = b + p->o_hyp_uu + (size_t)i * ns * rec_uu;
       const bool mer = gp_kern_is_mercer(k.type);
       HyperItem& a = hyf[idx];
       memset(&a, 0, sizeof(a));
-      a.k = k; a.x1 = Zw; a.n1 = M; a.x2 = Xw; a.n2 = N; a.G = G; a.ldg = ld; a.alpha = alpha; a.gm = Yw; a.symmetric = 0;
-      a.f1 = mer ? ft : nullptr; a.f2 = mer ? ft + gp_align_up((size_t)2 * mp * M, 32) : nullptr; a.partials = hy;
+      a.k = k; a.x1 = Zw; a.n1 = kw; a.x2 = Xw; a.n2 = N; a.G = G; a.ldg = ld; a.alpha = alpha; a.gm = Yw; a.symmetric = 0;
+      a.f1 = mer ? ft : nullptr; a.f2 = mer ? fx : nullptr; a.partials = hy;
       HyperItem& c2 = hyu[idx];
       memset(&c2, 0, sizeof(c2));
-      c2.k = k; c2.x1 = Zw; c2.n1 = M; c2.x2 = Zw; c2.n2 = M; c2.G = E2; c2.ldg = M; c2.symmetric = 1;
+      c2.k = k; c2.x1 = Zw; c2.n1 = kw; c2.x2 = Zw; c2.n2 = kw; c2.G = E2; c2.ldg = M; c2.symmetric = 1;
       c2.f1 = mer ? ft : nullptr; c2.f2 = mer ? ft : nullptr; c2.partials = hyuu;
       HyperFinishItem& f = fin[idx];
       memset(&f, 0, sizeof(f));
@@ -403,6 +442,7 @@ static gp_status sgb_enqueue(gp_sgprb_plan_t p, int count, double* bound_dev, bo
     }
     GP_CHECK(launch_kernel_build_items(h, p->ktype[i], p->m[i], cuu + (size_t)i * p->W, W, M, M, nullptr, 0));
   }
+  if (p->ragged) hipLaunchKernelGGL(sgb_kuu_pad_kernel, dim3(16, W), dim3(256), 0, h->stream, wins, M);
   GP_CHECK(launch_cholesky_inverse_batched(h, (double* const*)(dd + p->off_ptr_L), (double* const*)(dd + p->off_ptr_W),
                                            (const int*)(dd + p->off_M), (const int*)(dd + p->off_ld), W, M));
   for (int i = 0; i < P; i++)
@@ -474,6 +514,27 @@ gp_status gp_sgprb_set_graphs(gp_sgprb_plan_t p, int32_t enable) {
   return GP_OK;
 }
 
+gp_status gp_sgprb_set_inducing_counts(gp_sgprb_plan_t p, const int32_t* counts_host, int32_t count) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!counts_host || count < 1 || count > p->W)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgprb_set_inducing_counts: bad argument (1 <= count <= num_windows)");
+  std::vector<int> kw(p->W, p->M);
+  for (int w = 0; w < count; w++) {
+    if (counts_host[w] < 1 || counts_host[w] > p->M)
+      return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgprb_set_inducing_counts: every count must be in [1, M]");
+    kw[w] = counts_host[w];
+  }
+  if (kw == p->kw) return GP_OK;
+  // the counts are baked into the descriptors (item sizes) and the recorded graph: rebuild both at the next evaluation
+  p->kw.swap(kw);
+  p->ragged = false;
+  for (int v : p->kw) if (v < p->M) p->ragged = true;
+  p->desc_valid = false;
+  if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
+  return GP_OK;
+}
+
 gp_status gp_sgprb_eval_counts(gp_sgprb_plan_t p, int64_t* eager, int64_t* captured, int64_t* replayed) {
   if (!p) return GP_ERR_BAD_ARG;
   if (eager) *eager = p->n_eager;
@@ -505,6 +566,11 @@ gp_status gp_sgprb_bound_grad(gp_sgprb_plan_t p, const double* params, const dou
       for (size_t i = 0; i < (size_t)p->W * p->P; i++) { fin[i].np_uf = p->np_uf; fin[i].np_uu = p->np_uu; }
     }
     GP_HIP_CHECK(h, hipMemcpyAsync(p->d_desc, p->h_desc.data(), p->desc_bytes, hipMemcpyHostToDevice, h->stream));
+    if (p->ragged) {      // pad rows of the Kuf strips: zero from here on (the builds write the kw real rows only)
+      hipLaunchKernelGGL(sgb_kuf_pad_kernel, dim3(64, p->W), dim3(256), 0, h->stream, (const SgbWin*)(p->d_desc + p->off_win),
+                         p->M, sgb_ld(p->N));
+      GP_HIP_CHECK(h, hipGetLastError());
+    }
     p->k_params = params; p->k_X = X; p->k_Y = Y; p->k_Z = Z; p->k_grad = grad; p->k_bound = bound_dev; p->desc_valid = true;
     GP_CHECK(sgb_enqueue(p, count, bound_dev, grad != nullptr));
     p->n_eager++;
@@ -645,6 +711,7 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
     const double* par = params + (size_t)w * p->nparams;
     const double* Zw = Z + (size_t)w * M;
     const double* Xn = Xnew + (size_t)w * n;
+    const int kw = p->kw[w];
     double *Wm = b + p->o_W, *WB = b + p->o_WB, *Kus = b + p->o_Kuf, *A = b + p->o_A, *c = b + p->o_c;
     double* s1 = b + p->o_s1;                         // [rb][n]
     double* s2 = b + p->o_G;                          // [rb][n]   (G: M x ld doubles, free here)
@@ -654,8 +721,10 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
       double* ft = b + p->o_feat + (size_t)i * p->feat_stride;     // [Z features | frame features]: the frame half is rebuilt for Xnew
       const int mp = sm_mpad(k.m);
       const size_t idx = (size_t)i * W + w;
-      feat[idx] = FeatItem{k, Xn, ft + gp_align_up((size_t)2 * mp * M, 32), n, 0};
-      cov_item_fill(&cov[idx], k, Zw, M, Xn, n, Kus, ld, i > 0, 0.0, ft);
+      double* fx = ft + gp_align_up((size_t)2 * mp * M, 32);
+      feat[idx] = FeatItem{k, Xn, fx, n, 0};
+      cov_item_fill(&cov[idx], k, Zw, kw, Xn, n, Kus, ld, i > 0, 0.0, ft);      // kw rows: the pad rows of Kus stay zero
+      if (cov[idx].f2) cov[idx].f2 = fx;
     }
     { GemmProblem& r = p1[w]; memset(&r, 0, sizeof(r));
       r.A = Wm; r.lda = M; r.B = Kus; r.ldb = ld; r.C = A; r.ldc = ld; r.M = M; r.N = n; r.K = M; r.o0 = s1; }

@@ -98,8 +98,9 @@ def fit_windows(make_model, windows, maxiter=10, num_streams=4, reset=default_re
 # device-batched form: W windows per launch sequence (include/gpitch_abi.h gp_sgprb_*), scipy's L-BFGS-B per window
 # driven in reverse communication (lbfgsb_batch.py)
 class SgprWindowBatch(object):
-    """Device side of a batch of W SGPRSS windows that share N, M and the kernel structure of `template` (an SGPRSS):
-    bound and gradient of all of them from one launch sequence."""
+    """Device side of a batch of W SGPRSS windows that share N and the kernel structure of `template` (an SGPRSS):
+    bound and gradient of all of them from one launch sequence.  M is the largest inducing-point count a window may
+    have; a window with fewer is padded exactly (gp_sgprb_set_inducing_counts)."""
 
     def __init__(self, template, num_windows, N, M, handle=None):
         import ctypes as C
@@ -127,15 +128,33 @@ class SgprWindowBatch(object):
         self._st_host = t.zeros(4, dtype=t.int32).pin_memory()      # not-positive-definite status of the evaluation in flight
         self._ev, self._pending = None, None
         self.last_status = (0, 0, 0)
+        self._ragged = False         # the plan holds inducing counts other than M
 
     def load(self, xs, ys, zs):
-        """put `len(xs)` windows into the first slots (the others keep whatever they held: still valid problems)"""
-        t = self.h.torch
+        """put `len(xs)` windows into the first slots (the others keep whatever they held: still valid problems).
+        A window's Z may hold 1..M points: shorter ones are padded here (the pad is never read) and the counts go to the
+        plan, which evaluates each window as its own-size problem.  All windows at M: no counts are set."""
+        import ctypes as C
+        h = self.h
+        t = h.torch
         n = len(xs)
+        zl = [np.asarray(z, dtype=np.float64).reshape(-1) for z in zs]
+        counts = [int(z.size) for z in zl]
+        for i, c in enumerate(counts):
+            if not 1 <= c <= self.M:
+                raise ValueError("SgprWindowBatch.load: window %d has %d inducing points; this plan takes 1..%d"
+                                 % (i, c, self.M))
+        ragged = any(c != self.M for c in counts)
+        if ragged:
+            zl = [np.concatenate([z, np.full(self.M - z.size, z[-1])]) for z in zl]
         self.X[:n].copy_(t.as_tensor(np.stack([np.asarray(x, dtype=np.float64).reshape(-1) for x in xs])))
         self.Y[:n].copy_(t.as_tensor(np.stack([np.asarray(y, dtype=np.float64).reshape(-1) for y in ys])))
-        self.Z[:n].copy_(t.as_tensor(np.stack([np.asarray(z, dtype=np.float64).reshape(-1) for z in zs])))
+        self.Z[:n].copy_(t.as_tensor(np.stack(zl)))
+        if ragged or self._ragged:   # (back to all-M: the plan drops its counts, slots from n on take M)
+            h.check(h.lib.gp_sgprb_set_inducing_counts(self.plan, (C.c_int32 * n)(*counts), n))
+            self._ragged = ragged
         self.count = n
+        self.counts = counts
 
     def submit(self, params_host, with_grad=True):
         """enqueue one evaluation (parameter upload, the launch sequence, result download) and return at once; `collect`
@@ -242,6 +261,34 @@ class SgprWindowBatch(object):
             pass
 
 
+def ragged_batches(counts, batch, granule=16, cap=256):
+    """How fit_windows_batched groups windows by inducing-point count (host only).
+
+    counts[i] = inducing points of window i.  Returns (batches, single): batches is a list of (plan_M, positions) with at
+    most `batch` positions each, single the positions whose count exceeds `cap` (fitted one window at a time).  Equal
+    counts: consecutive batches in input order on one plan of exactly that M (no padding).  Otherwise the windows are
+    sorted by count (stable) and cut into runs of at most `batch`; a run's plan takes its largest count rounded up to a
+    multiple of `granule`, at most `cap`, so that the padded work stays small and few plan sizes occur."""
+    counts = [int(c) for c in counts]
+    for i, c in enumerate(counts):
+        if c < 1:
+            raise ValueError("ragged_batches: window %d has no inducing point" % i)
+    B = max(1, int(batch))
+    single = [i for i, c in enumerate(counts) if c > cap]
+    rest = [i for i, c in enumerate(counts) if c <= cap]
+    if not rest:
+        return [], single
+    if len({counts[i] for i in rest}) == 1:
+        return [(counts[rest[0]], rest[b0:b0 + B]) for b0 in range(0, len(rest), B)], single
+    order = sorted(rest, key=lambda i: counts[i])       # (stable)
+    out = []
+    for b0 in range(0, len(order), B):
+        ids = order[b0:b0 + B]
+        m = max(counts[i] for i in ids)
+        out.append((min(int(cap), -(-m // int(granule)) * int(granule)), ids))
+    return out, single
+
+
 def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default_reset, handle=None, rank=0,
                         world_size=1, params0=None, predict=False, inflight=2):
     """fit_windows with the device work batched: `batch` windows go through every bound + gradient evaluation together
@@ -250,10 +297,15 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
 
     Every window starts from the parameter values of make_model(handle) after `reset(model, x, y, z)` (unit noise and
     kernel variances by default, transcription.py:253-263) — i.e. carry_kernel_state=False of fit_windows — or from
-    params0[i] (constrained vector [noise | theta_0 | ...]) when given.  All windows must share N and M.
+    params0[i] (constrained vector [noise | theta_0 | ...]) when given.  All windows must share N (see below for M).
     predict=True adds what SoSp.optimize computes after every window's optimisation (separation.py:300-313), batched the
     same way: "mean", "var" (predict_f at the window's frames, (N, 1)) and "smean", "svar" (predict_s: lists over the
     sources of (N, 1) arrays).
+    Windows must share N; their inducing-point counts may differ (each window's Z from its own audio, as the drivers'
+    init_liv picks it).  Windows of different counts are sorted by count and batched with their neighbours
+    (`ragged_batches`), each batch on a plan sized by its largest count; plans are made when first needed and freed once no
+    pending batch needs their size.  A window with more than 256 inducing points is fitted in the same call by the
+    one-window engine (as fit_windows does it; "engine": "single" in its result).
     `inflight` batches are kept going at once (default 2: the host's stepping of one overlaps the device's evaluation of
     the other; 1 = one after another).
     `reset` is evaluated ONCE, on this rank's first window, to obtain the starting parameter values of every window (the
@@ -275,6 +327,15 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     results = [None] * len(windows)
     if not mine:
         return results
+    # the windows' shapes, before any device work
+    N = int(np.asarray(windows[mine[0]][0]).size)
+    counts = []
+    for i in mine:
+        if np.asarray(windows[i][0]).size != N:
+            raise ValueError("fit_windows_batched: all windows must have the same number of frames")
+        counts.append(int(np.asarray(windows[i][2]).size))
+        if counts[-1] < 1:
+            raise ValueError("fit_windows_batched: window %d has no inducing point" % i)
     if handle is None:
         # a stream of its own: the launch sequence of an evaluation is recorded into a hipGraph and replayed, which the
         # legacy null stream cannot do
@@ -292,6 +353,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                 hs.close()
     h = handle
     model = make_model(h)
+    init_vals = [p.value.copy() for p in model._param_list()]      # (the single-engine windows start from these)
     # what the batched plan takes from the template model: kernel structure, `reg`, the parameter values after ONE
     # reset() (on this rank's first window).  It does not carry a mean function or float32 strips: refuse, do not drop.
     if getattr(model, "mean_function", None) is not None and type(model.mean_function).__name__ != "Zero":
@@ -305,18 +367,28 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     st = model._objective_setup()
     ps, free_idx = st["ps"], st["free_idx"]
     vals0 = st["vals0"]
-    N, M = int(np.asarray(x0w).size), int(np.asarray(z0w).size)
-    for i in mine:
-        if np.asarray(windows[i][0]).size != N or np.asarray(windows[i][2]).size != M:
-            raise ValueError("fit_windows_batched: all windows must have the same number of frames and inducing points")
-    B = max(1, min(int(batch), len(mine)))
+    groups, single = ragged_batches(counts, batch)
+    chunks = [(m, [mine[q] for q in ids]) for m, ids in groups]       # (plan M, window indices)
+    single = [mine[q] for q in single]
+    B = max(1, min(int(batch), sum(len(ids) for _, ids in chunks)))
     back = np.array([ps[i].transform.backward(np.atleast_1d(vals0[i]))[0] for i in free_idx])
     var_idx = [int(o) for o in np.cumsum([1] + [2 + 2 * int(k.num_partials) for k in model.kern.kern_list])[:-1]]
-    chunks = [mine[b0:b0 + B] for b0 in range(0, len(mine), B)]
     # Two batches in flight, each on a device plan of its own: while the host steps the L-BFGS-B instances of one batch
     # (setulb and the transforms: as long as a device evaluation at W = 256), the device evaluates the other.
-    nslots = min(int(inflight), len(chunks))
-    devs = [SgprWindowBatch(model, B, N, M, handle=h) for _ in range(max(1, nslots))]
+    nslots = max(1, min(int(inflight), len(chunks)))
+    # plans for the first batches up front; later ones when first needed.  A plan stays while a pending batch needs its
+    # size and is freed when a new plan is made (sizes only grow along the sorted batches: at most 2 x inflight plans)
+    idle = [SgprWindowBatch(model, B, N, m, handle=h) for m, _ in chunks[:nslots]]
+
+    def plan_for(m):
+        for d in idle:
+            if d.M == m:
+                idle.remove(d)
+                return d
+        for d in [d for d in idle if all(d.M != mm for mm, _ in pending)]:
+            idle.remove(d)
+            d.close()
+        return SgprWindowBatch(model, B, N, m, handle=h)
 
     class _Run(object):
         pass
@@ -402,19 +474,45 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
 
     pending = list(chunks)
     live = []
-    for dev in devs:
-        if pending:
-            live.append(start(dev, pending.pop(0)))
+    while pending and len(live) < nslots:
+        m, ids = pending.pop(0)
+        live.append(start(plan_for(m), ids))
     while live:
         for r in list(live):
             if advance(r):
                 continue
             finish(r)
             live.remove(r)
+            idle.append(r.dev)
             if pending:
-                live.append(start(r.dev, pending.pop(0)))
-    for dev in devs:
+                m, ids = pending.pop(0)
+                live.append(start(plan_for(m), ids))
+    for dev in idle:
         dev.close()
+    # windows beyond the batched plans' 256 inducing points: the one-window engine, as fit_windows fits a window
+    for i in single:
+        for p, v in zip(model._param_list(), init_vals):
+            p.value = v
+        x, y, z = windows[i][:3]
+        reset(model, x, y, z)
+        ps1 = model._param_list()
+        if params0 is not None:
+            for p, v in zip(ps1, np.asarray(params0[i], dtype=np.float64)):
+                p.value = np.array([v])
+        start_vals = np.array([float(p.value[0]) for p in ps1])
+        try:
+            res = model.optimize(method='L-BFGS-B', maxiter=maxiter)
+        except _lib.NotPositiveDefiniteError as e:
+            results[i] = {"bound": float("nan"), "nfev": 0, "nit": 0, "variances": start_vals[var_idx].copy(),
+                          "noise": float(start_vals[0]), "params": start_vals, "engine": "single", "error": str(e)}
+            continue
+        pv = np.array([float(p.value[0]) for p in ps1])
+        results[i] = {"bound": -float(res.fun), "nfev": int(res.nfev), "nit": int(res.nit),
+                      "variances": pv[var_idx].copy(), "noise": float(pv[0]), "params": pv, "engine": "single"}
+        if predict:
+            m1, v1 = model.predict_f(x)
+            ms, vs = model.predict_s(x)
+            results[i].update(mean=m1, var=v1, smean=list(ms), svar=list(vs))
     model._destroy()
     return results
 

@@ -438,7 +438,8 @@ gp_status gp_sgpr_predict_source(gp_sgpr_plan p, const double* params, const dou
  * All windows share max_N (= N), M and the kernel structure of `cfg`; contiguous layouts:
  *   params [W][gp_sgprb_num_params], X [W][N], Y [W][N], Z [W][M], bound_dev [W], grad [W][num_params] (may be NULL).
  * `count` <= W windows (the first `count` slots) are evaluated.  Asynchronous on the handle's stream; from the second
- * call with the same buffers the sequence is replayed from a hipGraph.  M <= 256. */
+ * call with the same buffers the sequence is replayed from a hipGraph.  M <= 256: the largest inducing-point count of
+ * the plan (gp_sgprb_set_inducing_counts gives each slot its own). */
 gp_status gp_sgprb_create(gp_handle h, const gp_sgpr_config* cfg, int32_t num_windows, gp_sgprb_plan* out);
 gp_status gp_sgprb_destroy(gp_sgprb_plan p);
 int64_t gp_sgprb_num_params(gp_sgprb_plan p);
@@ -449,6 +450,13 @@ gp_status gp_sgprb_bound_grad(gp_sgprb_plan p, const double* params, const doubl
                               int32_t count, double* bound_dev, double* grad);
 gp_status gp_sgprb_set_graphs(gp_sgprb_plan p, int32_t enable);
 gp_status gp_sgprb_eval_counts(gp_sgprb_plan p, int64_t* eager, int64_t* captured, int64_t* replayed);
+/* Windows whose inducing-point counts differ (the drivers pick each window's Z from its own audio: init_liv).
+ * counts_host[i] = inducing points of window slot i (1..M) for i < count; slots from `count` on take M.  Z rows beyond
+ * counts[i] are ignored (never read).  Each window is evaluated as the exact M-point problem with an identity pad block
+ * in Kuu and zero pad rows in Kuf: its bound, gradient and predictions are those of the counts[i]-point window up to
+ * rounding, independent of the other slots.  Never called = every slot has M (today's results, bit for bit).  A change
+ * of counts rebuilds the descriptors and the recorded graph at the next evaluation. */
+gp_status gp_sgprb_set_inducing_counts(gp_sgprb_plan p, const int32_t* counts_host, int32_t count);
 /* The rest of SoSp.optimize's loop body (gpitch/separation.py:300-313), window-batched: after a window's optimisation
  * the reference calls model.predict_f(X_i) (GPflow 0.5 SGPR.build_predict) and model.predict_s(X_i) (sgpr_ss.py:73-114).
  * gp_sgprb_predict_f: Xnew [count][n] (n <= N), mean / var [count][n]; runs the forward pass at `params` first.
