@@ -25,7 +25,7 @@ TIMER_NAMES = ["kuf_build", "cond_A", "cond_LTA", "nt_gemm", "kuf_bar", "chol", 
 
 # every symbol include/gpitch_abi.h declares
 ABI_SYMBOLS = [
-    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_last_not_pd_index",
+    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_last_not_pd_index",
     "gp_kernel_build", "gp_kernel_build_f32", "gp_kernel_diag", "gp_chol_workspace_bytes", "gp_kuu_cholesky", "gp_cholesky_inplace",
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
     "gp_pdgp_create", "gp_pdgp_destroy", "gp_pdgp_num_params", "gp_pdgp_layout", "gp_pdgp_workspace_bytes",
@@ -127,6 +127,7 @@ def load_library():
         "gp_sync": (i32, [vp]),
         "gp_last_error": (C.c_char_p, [vp]),
         "gp_abi_version": (i32, []),
+        "gp_debug_wave_takes": (i32, [i32, i32, i32, i32]),
         "gp_last_not_pd_index": (i32, [vp]),
         "gp_kernel_build": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),
         "gp_kernel_build_f32": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),

@@ -296,6 +296,12 @@ gp_status launch_gemm_f32_nt_reduce_batched(gp_handle h, const GemmProblem* d_pr
                                             int nsplit, int sym, int scale_by_k, double alpha, int uniform_aligned = 0);
 // leading dimension (in elements) of an M x N strip: even for float64, a multiple of 4 for float32 (16-byte rows)
 static inline int64_t gp_strip_ld(int N, bool f32) { return f32 ? (((int64_t)N + 3) & ~(int64_t)3) : (((int64_t)N + 1) & ~(int64_t)1); }
+// the wave forms (gemm_wave.hip, gemm_wave_f32.hip) address their strips through buffer resources: 32-bit byte offsets
+// and num_records = 2^31 - 1.  An M x ld strip of 2^31 bytes or more would be read as zeros and stored partly nowhere, so
+// such a strip takes the strip forms (64-bit addresses).
+static inline bool gp_strip_below_2gib(int M, int N, bool f32) {
+  return (int64_t)M * gp_strip_ld(N, f32) * (f32 ? 4 : 8) < ((int64_t)1 << 31);
+}
 // doubles that hold an M x ld strip of either type
 static inline size_t gp_strip_doubles(size_t M, int N, bool f32) {
   const size_t e = M * (size_t)gp_strip_ld(N, f32);

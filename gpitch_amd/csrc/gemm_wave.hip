@@ -29,8 +29,9 @@
 //    (wave-uniform), and the matrices themselves carry exact zeros above (below) the diagonal — no masks.
 // Column scaling of role 3 (D = 2 gv, indexed by the frame = output column) commutes with the product: it is applied to
 // the finished tile (64 multiplies per tile instead of 4 per k-step).
-// Whole, aligned problems only (M a multiple of 64, N of 256, K-structure = M, even leading dimensions): the launcher
-// returns false otherwise and gemm_strip.hip / gemm.hip run.
+// Whole, aligned problems only (M a multiple of 64, N of 256, K-structure = M, even leading dimensions) whose strips stay
+// below 2^31 bytes (the buffer resources' range: common.h gp_strip_below_2gib): the launcher returns false otherwise and
+// gemm_strip.hip / gemm.hip run.
 #include "common.h"
 #include <stdlib.h>
 #include <atomic>
@@ -400,7 +401,7 @@ static int gw_roles() { return gp_switches().strip_wave_roles; }      // bitmask
 // would a launch of that role and shape take the wave form?  (engine.hip sizes the partial-sum rows by it: 64-row tiles)
 bool gemm_wave_takes(int role, int maxM, int maxN, int uniform_aligned) {
   if (!gw_enabled() || !uniform_aligned || role < 1 || (role > 3 && role != 5) || !((gw_roles() >> role) & 1)) return false;
-  return maxM > 0 && (maxM % GW_T) == 0 && (maxN % 256) == 0;
+  return maxM > 0 && (maxM % GW_T) == 0 && (maxN % 256) == 0 && gp_strip_below_2gib(maxM, maxN, false);
 }
 
 template <int TAG, int KT = -1>
@@ -425,7 +426,7 @@ static gp_status gw_launch(gp_handle h, const GemmProblem* d_probs, int batch, i
 // Returns true when the wave form took the launch (*st = its status).  `uniform_aligned` = the caller vouches that every
 // problem of the batch has M = K-structure maxM, N = maxN, 16-byte aligned operands, even leading dimensions.
 bool launch_gemm_wave(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxN, const GemmFlags& f, gp_status* st) {
-  if (!gemm_wave_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
+  if (!gp_strip_below_2gib(maxM, maxN, false) || !gemm_wave_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
   if (f.beta != 0.0 || f.triC != TRI_NONE) return false;
   if (f.role >= 3 ? !(f.scale_mode == 1 && (f.alpha == 1.0 || f.alpha == 2.0 || f.alpha == 0.5 || f.alpha == 4.0)) : (f.alpha != 1.0)) return false;
   if (f.role == 5) {       // (the caller has asked gemm_fused_contraction_records first: it cannot fall back from here)
@@ -452,4 +453,9 @@ int gemm_fused_contraction_records(int maxM, int maxN, int ktype) {
   if (!gemm_strip_fused_contraction_ok(maxM, maxN, ktype)) return 0;
   if (gemm_wave_takes(5, maxM, maxN, 1)) return (maxM / GW_T) * (maxN / GW_T);
   return (maxM / 128) * (maxN / 128);
+}
+
+// host-only: would a uniform, aligned launch of that role and shape take a wave form (f32 != 0: gemm_wave_f32.hip)?
+extern "C" int32_t gp_debug_wave_takes(int32_t role, int32_t M, int32_t N, int32_t f32) {
+  return (f32 ? gemm_wave_f32_takes(role, M, N, 1) : gemm_wave_takes(role, M, N, 1)) ? 1 : 0;
 }

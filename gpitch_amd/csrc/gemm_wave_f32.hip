@@ -23,8 +23,9 @@
 //    MFMA-tile skipping, as gemm_wave.hip.  Stores: the 16 payloads of a tile (a row's four columns side by side) in 16
 //    different register quads, reductions first, stores last, the wavefront waits for them before its next tile (the
 //    store-data hazard of gemm_wave.hip).
-// Whole aligned problems only (M a multiple of 64, N of 256, float32 scratch for the M x M operand in every problem's xb);
-// the launcher returns false otherwise and gemm_strip_f32.hip / gemm_f32.hip run.
+// Whole aligned problems only (M a multiple of 64, N of 256, float32 scratch for the M x M operand in every problem's xb)
+// whose strips stay below 2^31 bytes (the buffer resources' range: common.h gp_strip_below_2gib); the launcher returns
+// false otherwise and gemm_strip_f32.hip / gemm_f32.hip run.
 #include "common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -314,7 +315,7 @@ __global__ void __launch_bounds__(256, GWF_OCC) gemm_wave_f32_kernel(const GemmP
 bool gemm_wave_f32_takes(int role, int maxM, int maxN, int uniform_aligned) {
   const GpSwitches& sw = gp_switches();
   if (!sw.strip_wave || !uniform_aligned || role < 1 || (role > 3 && role != 5) || !((sw.strip_wave_f32 >> role) & 1)) return false;
-  return maxM > 0 && (maxM % GF_T) == 0 && (maxN % 256) == 0;
+  return maxM > 0 && (maxM % GF_T) == 0 && (maxN % 256) == 0 && gp_strip_below_2gib(maxM, maxN, true);
 }
 
 template <int TAG, int KT = -1>
@@ -341,7 +342,7 @@ static gp_status gwf_launch(gp_handle h, const GemmProblem* d_probs, int batch, 
 // Returns true when the wave form took the launch (*st = its status).  f.a32_ok: every problem's xb points to M * M floats of
 // scratch for the float32 copy of its M x M operand; roles 1 / 2 also need f.rows64_ok (partial rows per 64-row tile).
 bool launch_gemm_wave_f32(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxN, const GemmFlags& f, gp_status* st) {
-  if (!f.a32_ok || !gemm_wave_f32_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
+  if (!f.a32_ok || !gp_strip_below_2gib(maxM, maxN, true) || !gemm_wave_f32_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
   if ((f.role == 1 || f.role == 2) && !f.rows64_ok) return false;
   if (f.beta != 0.0 || f.triC != TRI_NONE) return false;
   if (f.role >= 3 ? !(f.scale_mode == 1 && (f.alpha == 1.0 || f.alpha == 2.0 || f.alpha == 0.5 || f.alpha == 4.0)) : (f.alpha != 1.0)) return false;

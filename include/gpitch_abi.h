@@ -84,6 +84,10 @@ gp_status gp_destroy(gp_handle h);
 gp_status gp_sync(gp_handle h);
 const char* gp_last_error(gp_handle h);       /* text of the last failure on this handle */
 int32_t gp_abi_version(void);
+/* host-only query, no device work: would a uniform, aligned strip product of that role (1: A = W Kuf, 2: Lq^T A,
+ * 3: Kuf_bar, 5: Kuf_bar with the stationary contraction) over an M x N strip take the wave form (f32 != 0: float32
+ * strips)?  Strips of 2^31 bytes or more never do. */
+int32_t gp_debug_wave_takes(int32_t role, int32_t M, int32_t N, int32_t f32);
 /* pivot index reported by the last GP_ERR_NOT_PD (−1 if none) */
 int32_t gp_last_not_pd_index(gp_handle h);
 

@@ -14,13 +14,10 @@ def oracle_elbo(prob, whiten=True, nlin_code=0, xp=None):
                          prob["noise_var"], whiten=whiten, nlin_code=nlin_code, xp=xp)
 
 
-def oracle_elbo_and_grads(prob, nlin_code=0, whiten=True):
-    """ELBO and its gradient w.r.t. every constrained parameter by torch-CPU autograd through the
-    oracle's restatement (mirrors TF reverse-mode)."""
+def _torch_pdgp_leaves(prob):
+    """torch-CPU leaves (requires_grad) for every constrained parameter of a make_problem dict, and the oracle-format
+    kernel / inducing / variational arguments built on them"""
     import torch
-    from oracle import gpflow05 as orc
-    from oracle.backend import TorchBackend
-    tb = TorchBackend()
     T = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), requires_grad=True)
     P = prob["P"]
     leaves = {"noise": T(prob["noise_var"])}
@@ -40,11 +37,153 @@ def oracle_elbo_and_grads(prob, nlin_code=0, whiten=True):
     qmc = [leaves.setdefault("q_mu_com%d" % i, T(prob["q_mu_com"][i])) for i in range(P)]
     qsa = [leaves.setdefault("q_sqrt_act%d" % i, T(prob["q_sqrt_act"][i])) for i in range(P)]
     qsc = [leaves.setdefault("q_sqrt_com%d" % i, T(prob["q_sqrt_com"][i])) for i in range(P)]
+    return leaves, (za, zc, ka, kc, qma, qsa, qmc, qsc)
+
+
+def _leaf_grads(leaves):
+    return {k: (v.grad.numpy().copy() if v.grad is not None else None) for k, v in leaves.items()}
+
+
+def oracle_elbo_and_grads(prob, nlin_code=0, whiten=True):
+    """ELBO and its gradient w.r.t. every constrained parameter by torch-CPU autograd through the
+    oracle's restatement (mirrors TF reverse-mode)."""
+    import torch
+    from oracle import gpflow05 as orc
+    from oracle.backend import TorchBackend
+    leaves, args = _torch_pdgp_leaves(prob)
     x = torch.tensor(prob["x"]); y = torch.tensor(prob["y"])
-    elbo = orc.pdgp_elbo(x, y, za, zc, ka, kc, qma, qsa, qmc, qsc, leaves["noise"], whiten=whiten,
-                         nlin_code=nlin_code, xp=tb)
+    elbo = orc.pdgp_elbo(x, y, *args, leaves["noise"], whiten=whiten, nlin_code=nlin_code, xp=TorchBackend())
     elbo.backward()
-    return float(elbo.detach()), {k: (v.grad.numpy().copy() if v.grad is not None else None) for k, v in leaves.items()}
+    return float(elbo.detach()), _leaf_grads(leaves)
+
+
+# ---- frame-chunked forms of the oracle: whole recordings of 2^19 frames and more at M = 512, in bounded host memory ----
+ORACLE_CHUNK = 65536
+
+
+def oracle_elbo_and_grads_chunked(prob, chunk=ORACLE_CHUNK, nlin_code=0, whiten=True):
+    """oracle_elbo_and_grads over frame chunks: the ELBO at full batch (num_data = None) is the sum over frames of the
+    variational expectations minus the KL term, so each chunk's sum is differentiated on its own (its graph freed before
+    the next one) and the KL term is counted once.  Same return value as oracle_elbo_and_grads."""
+    import torch
+    from oracle import gpflow05 as orc
+    from oracle.backend import TorchBackend
+    tb = TorchBackend()
+    leaves, (za, zc, ka, kc, qma, qsa, qmc, qsc) = _torch_pdgp_leaves(prob)
+    P = prob["P"]
+    kl = orc.pdgp_prior_kl(za, zc, ka, kc, qma, qsa, qmc, qsc, whiten, tb)
+    kl.backward(-torch.ones_like(kl))
+    total = -float(kl.detach())
+    x, y = prob["x"], prob["y"]
+    for s in range(0, x.shape[0], chunk):
+        xc, yc = torch.tensor(x[s:s + chunk]), torch.tensor(y[s:s + chunk])
+        fmean, fvar = orc.pdgp_conditionals(xc, za, zc, ka, kc, qma, qsa, qmc, qsc, whiten, tb)
+        ve = tb.sum(orc.mpd_variational_expectations(fmean, fvar, yc, leaves["noise"], P, nlin_code, tb))
+        ve.backward()
+        total += float(ve.detach())
+    return total, _leaf_grads(leaves)
+
+
+def oracle_predict_act_n_com_chunked(prob, xnew, chunk=ORACLE_CHUNK, whiten=True, nlin_code=0):
+    """oracle.gpflow05.pdgp_predict_act_n_com over chunks of xnew (the predictions are per frame: concatenated)"""
+    from oracle import gpflow05 as orc
+    parts = [orc.pdgp_predict_act_n_com(xnew[s:s + chunk], prob["za"], prob["zc"], prob["kern_act"], prob["kern_com"],
+                                        prob["q_mu_act"], prob["q_sqrt_act"], prob["q_mu_com"], prob["q_sqrt_com"],
+                                        whiten=whiten, nlin_code=nlin_code)
+             for s in range(0, xnew.shape[0], chunk)]
+    return tuple([np.concatenate([pt[k][i] for pt in parts], 0) for i in range(len(parts[0][k]))] for k in range(5))
+
+
+def _sgpr_chunked_state(X, Y, Z, kern_list, noise_var, chunk, xp, checkpoint=False):
+    """oracle.gpflow05.sgpr_common from sufficient statistics summed over frame chunks: A A^T, A err, sum Kdiag, sum err^2
+    (A = L^-1 Kuf / sigma).  checkpoint=True (torch): every chunk's statistics under torch.utils.checkpoint, so the
+    backward pass recomputes a chunk's M x chunk strips instead of keeping all of them.  Returns L, LB, c, AAT, sums."""
+    from oracle import gpflow05 as orc
+    M = Z.shape[0]
+    Kuu = orc.K_sum(kern_list, Z, None, xp) + xp.eye(M) * orc.JITTER
+    L = xp.cholesky(Kuu)
+    sigma = xp.sqrt(noise_var)
+
+    def stats(Xc, Yc, L, sigma):
+        A = xp.trsm(L, orc.K_sum(kern_list, Z, Xc, xp), lower=True) / sigma
+        return xp.matmul(A, xp.t(A)), xp.matmul(A, Yc), xp.sum(orc.Kdiag_sum(kern_list, Xc, xp)), xp.sum(xp.square(Yc))
+    acc = None
+    for s in range(0, X.shape[0], chunk):
+        Xc, Yc = xp.asarray(X[s:s + chunk]), xp.asarray(Y[s:s + chunk])
+        if checkpoint:
+            import torch.utils.checkpoint
+            st = torch.utils.checkpoint.checkpoint(stats, Xc, Yc, L, sigma, use_reentrant=False)
+        else:
+            st = stats(Xc, Yc, L, sigma)
+        acc = st if acc is None else tuple(a + b for a, b in zip(acc, st))
+    AAT, Aerr, sum_kdiag, sum_err2 = acc
+    LB = xp.cholesky(AAT + xp.eye(M))
+    c = xp.trsm(LB, Aerr, lower=True) / sigma
+    return L, LB, c, AAT, sum_kdiag, sum_err2
+
+
+def _sgpr_bound_from_state(state, num_data, output_dim, kern_list, noise_var, reg, xp):
+    """the lines of oracle.gpflow05.sgpr_bound after sgpr_common"""
+    _, LB, c, AAT, sum_kdiag, sum_err2 = state
+    bound = -0.5 * num_data * output_dim * np.log(2 * np.pi)
+    bound = bound - output_dim * xp.sum(xp.log(xp.diag_part(LB)))
+    bound = bound - 0.5 * num_data * output_dim * xp.log(noise_var)
+    bound = bound - 0.5 * sum_err2 / noise_var
+    bound = bound + 0.5 * xp.sum(xp.square(c))
+    bound = bound - 0.5 * output_dim * sum_kdiag / noise_var
+    bound = bound + 0.5 * output_dim * xp.sum(xp.diag_part(AAT))
+    if reg:
+        s = xp.abs(xp.scalar(kern_list[0]["variance"]))
+        for k in kern_list[1:]:
+            s = s + xp.abs(xp.scalar(k["variance"]))
+        bound = bound - 1000. * s
+    return bound
+
+
+def oracle_sgpr_bound_chunked(X, Y, Z, kern_list, noise_var, reg=False, chunk=ORACLE_CHUNK):
+    """oracle.gpflow05.sgpr_bound (numpy) from chunk-summed sufficient statistics"""
+    from oracle.backend import NP
+    st = _sgpr_chunked_state(X, Y, Z, kern_list, noise_var, chunk, NP)
+    return float(_sgpr_bound_from_state(st, float(Y.shape[0]), float(Y.shape[1]), kern_list, noise_var, reg, NP))
+
+
+def oracle_sgpr_bound_and_grads_chunked(X, Y, Z, kern_list, noise_var, reg=False, chunk=ORACLE_CHUNK):
+    """the SGPRSS bound and its gradient w.r.t. [noise, then per kernel variance, lengthscales, energies, frequencies] (the
+    order of the engine's parameter vector) by torch autograd through the chunked statistics, each chunk checkpointed"""
+    import torch
+    from oracle.backend import TorchBackend
+    tb = TorchBackend()
+    T = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), requires_grad=True)
+    nv = T(noise_var)
+    leaves, tk = [nv], []
+    for d in kern_list:
+        o = dict(d)
+        o["variance"] = T(d["variance"]); o["lengthscales"] = T(d["lengthscales"])
+        o["energy"] = [T(e) for e in d["energy"]]; o["frequency"] = [T(f) for f in d["frequency"]]
+        leaves += [o["variance"], o["lengthscales"]] + o["energy"] + o["frequency"]
+        tk.append(o)
+    st = _sgpr_chunked_state(X, Y, torch.tensor(Z), tk, nv, chunk, tb, checkpoint=True)
+    b = _sgpr_bound_from_state(st, float(Y.shape[0]), float(Y.shape[1]), tk, nv, reg, tb)
+    b.backward()
+    return float(b.detach()), np.array([float(l.grad) for l in leaves])
+
+
+def oracle_sgpr_predict_f_chunked(Xnew, X, Y, Z, kern_list, noise_var, chunk=ORACLE_CHUNK):
+    """oracle.gpflow05.sgpr_predict_f (full_cov = False) from the chunked statistics, over chunks of Xnew"""
+    from oracle import gpflow05 as orc
+    from oracle.backend import NP as xp
+    L, LB, c = _sgpr_chunked_state(X, Y, Z, kern_list, noise_var, chunk, xp)[:3]
+    means, variances = [], []
+    for s in range(0, Xnew.shape[0], chunk):
+        Xs = Xnew[s:s + chunk]
+        tmp1 = xp.trsm(L, orc.K_sum(kern_list, Z, Xs, xp), lower=True)
+        tmp2 = xp.trsm(LB, tmp1, lower=True)
+        means.append(xp.matmul(xp.t(tmp2), c))
+        variances.append((orc.Kdiag_sum(kern_list, Xs, xp) + xp.sum(xp.square(tmp2), 0)
+                          - xp.sum(xp.square(tmp1), 0)).reshape(-1, 1))
+    mean, var = np.concatenate(means, 0), np.concatenate(variances, 0)
+    D = Y.shape[1]
+    return mean, (var if D == 1 else np.concatenate([var] * D, 1))
 
 
 def model_grad_dict(m):

@@ -175,3 +175,24 @@ def test_init_cparam_and_kernel_initialisers():
     xs = np.linspace(-4, 4, 9)
     np.testing.assert_allclose(t.backward(t.forward(xs)), xs, atol=1e-12)
     np.testing.assert_allclose(t.dforward(xs), (t.forward(xs + 1e-6) - t.forward(xs - 1e-6)) / 2e-6, rtol=1e-6)
+
+
+def test_wave_forms_take_only_strips_below_2GiB():
+    """gemm_wave.hip / gemm_wave_f32.hip address strips through buffer resources (32-bit byte offsets, num_records
+    2^31 - 1): a strip of M x N elements takes the wave form only while M * N * bytes < 2^31 (N a multiple of 256, so
+    ld = N).  Host-only query: no GPU needed."""
+    from gpitch_amd import _lib
+    lib = _lib.load_library()
+    takes = lambda role, M, N, f32: lib.gp_debug_wave_takes(role, M, N, f32) == 1
+    for f32, elem in ((0, 8), (1, 4)):
+        for M in (64, 256, 512):
+            n_edge = (1 << 31) // (M * elem)          # the first N whose strip is 2^31 bytes
+            for role in (1, 2, 3, 5):
+                assert takes(role, M, n_edge - 256, f32), (role, M, f32)
+                assert not takes(role, M, n_edge, f32), (role, M, f32)
+                assert not takes(role, M, n_edge + 3 * 256, f32), (role, M, f32)
+    # the sizes of tests/test_gpu_large_strips.py
+    assert takes(1, 512, 524032, 0) and not takes(1, 512, 524288, 0) and not takes(1, 512, 525056, 0)
+    assert takes(1, 512, 1048320, 1) and not takes(1, 512, 1048576, 1) and not takes(1, 512, 1048832, 1)
+    # shapes the wave forms never take, whatever the size: M not a multiple of 64, N not of 256, role 4
+    assert not takes(1, 96, 4096, 0) and not takes(1, 512, 4000, 0) and not takes(4, 512, 4096, 0)
