@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_last_not_pd_index",
     "gp_kernel_build", "gp_kernel_build_f32", "gp_kernel_diag", "gp_chol_workspace_bytes", "gp_kuu_cholesky", "gp_cholesky_inplace",
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
+    "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
     "gp_pdgp_create", "gp_pdgp_destroy", "gp_pdgp_num_params", "gp_pdgp_layout", "gp_pdgp_workspace_bytes",
     "gp_pdgp_set_workspace", "gp_pdgp_set_precision", "gp_pdgp_set_gp_precision", "gp_pdgp_set_grad_needs", "gp_pdgp_set_overlap", "gp_pdgp_elbo", "gp_pdgp_elbo_begin", "gp_pdgp_elbo_end", "gp_pdgp_create_subset", "gp_pdgp_cond_begin", "gp_pdgp_cond_end", "gp_pdgp_predict", "gp_pdgp_predict_reuse",
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
@@ -44,6 +45,7 @@ ABI_SYMBOLS = [
     "gp_pdgpb_create", "gp_pdgpb_destroy", "gp_pdgpb_num_params", "gp_pdgpb_layout", "gp_pdgpb_set_grad_needs",
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
     "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
+    "gp_pdgpb_predict_moments_workspace_bytes", "gp_pdgpb_predict_moments",
 ]
 
 
@@ -145,6 +147,7 @@ def load_library():
         "gp_gauss_kl": (i32, [vp, vp, vp, i32, KD, vp, dbl, C.POINTER(dbl), vp, sz]),
         "gp_gauss_kl_matrix": (i32, [vp, vp, vp, i32, vp, C.POINTER(dbl), vp, sz]),
         "gp_mpd_varexp": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(dbl)]),
+        "gp_mpd_predict_moments": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "gp_pdgp_create": (i32, [vp, C.POINTER(PdgpConfig), C.POINTER(vp)]),
         "gp_pdgp_destroy": (i32, [vp]),
         "gp_pdgp_num_params": (i64, [vp]),
@@ -163,6 +166,8 @@ def load_library():
         "gp_pdgp_cond_end": (i32, [vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, C.POINTER(dbl), vp]),
         "gp_pdgp_predict": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "gp_pdgp_predict_reuse": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "gp_pdgp_predict_moments": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "gp_pdgp_predict_moments_reuse": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "gp_overlap_merge": (i32, [vp, vp, i32, i32, i64, i32, i32, vp]),
         "gp_transform_register_logistic": (i32, [vp, dbl, dbl, C.POINTER(C.c_uint8)]),
         "gp_transform_forward": (i32, [vp, vp, vp, i64, vp]),
@@ -233,6 +238,8 @@ def load_library():
         "gp_pdgpb_predict_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_predict_prepare": (i32, [vp, vp, vp, sz]),
         "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),
+        "gp_pdgpb_predict_moments_workspace_bytes": (sz, [vp, i64]),
+        "gp_pdgpb_predict_moments": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol

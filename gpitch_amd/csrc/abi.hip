@@ -421,6 +421,18 @@ gp_status gp_mpd_varexp(gp_handle h, const double* Fmu, const double* Fvar, cons
   return s;
 }
 
+gp_status gp_mpd_predict_moments(gp_handle h, const double* Fmu, const double* Fvar, const double* y, int32_t N, int32_t P,
+                                 int32_t nlin, const double* noise_var, double* smean, double* svar, double* ymean,
+                                 double* yvar, double* logp) {
+  if (!h) return GP_ERR_BAD_ARG;
+  if (N < 0 || P < 1 || nlin < 0 || nlin > 2 || (logp && (!y || !noise_var)))
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_mpd_predict_moments: bad argument (logp needs y and noise_var)");
+  if (N == 0) return GP_OK;
+  if (!Fmu || !Fvar) return gp_fail(h, GP_ERR_BAD_ARG, "gp_mpd_predict_moments: bad argument");
+  return launch_mpd_moments(h, Fmu, Fvar, (int64_t)2 * P, 1, y, N, P, nlin, noise_var, noise_var != nullptr, smean, svar, ymean,
+                            yvar, logp);
+}
+
 size_t gp_gauss_kl_workspace_bytes(int32_t M, int32_t with_kernel) {
   if (M <= 0 || !with_kernel) return 4096;
   const size_t mm = gp_align_up((size_t)M * M * sizeof(double), 256);

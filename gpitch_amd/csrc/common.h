@@ -332,6 +332,11 @@ gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)
 #define GP_KL_BLOCKS 16
 int mpd_lik_blocks(int N);   // block partials (2 doubles each) one launch over N frames leaves
+// lik.hip: posterior moments of the sources / mixture and the expected log density (gp_mpd_predict_moments); Fmu/Fvar element
+// (frame n, column c) at [n * f_rs + c * f_cs]; smean / svar P x N row-major; any output may be NULL; yvar takes the noise variance when add_noise
+gp_status launch_mpd_moments(gp_handle h, const double* Fmu, const double* Fvar, int64_t f_rs, int64_t f_cs, const double* y,
+                             int N, int P, int nlin, const double* noise_var, int add_noise, double* smean, double* svar,
+                             double* ymean, double* yvar, double* logp);
 gp_status launch_mpd_lik(gp_handle h, const double* Fmu, const double* Fvar, int64_t f_rs, int64_t f_cs,
                          const double* y, int N, int P, int nlin, const double* noise_var, double scale,
                          double* per_frame, double* partial_sums, int* num_partials_out,

@@ -60,3 +60,86 @@ __device__ __forceinline__ Quad gh_quad(int nlin, double mg, double vg, bool wan
   }
   return q;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Prediction side: E1, E2 exactly as gh_quad forms them (same operations in the same order) and the rule's own variance of
+// nlin(g), V = sum_h w_h (nlin(x_h) - E1)^2 >= 0.  The 20 values stay in registers (both loops fully unrolled), so each
+// node's exp() work is done once.
+struct QuadV {
+  double E1, E2, V;
+};
+
+__device__ __forceinline__ QuadV gh_quad_var(int nlin, double mg, double vg) {
+  double s[GH_POINTS];
+  QuadV q = {0, 0, 0};
+  const double sd = sqrt(2.0 * vg);
+#pragma unroll
+  for (int hh = 0; hh < GH_POINTS; hh++) {
+    const double xh = c_gh_x[hh], wh = c_gh_w[hh];
+    double ds;
+    nlin_eval(nlin, xh * sd + mg, s[hh], ds);
+    q.E1 = fma(s[hh], wh, q.E1);
+    q.E2 = fma(s[hh] * s[hh], wh, q.E2);
+  }
+#pragma unroll
+  for (int hh = 0; hh < GH_POINTS; hh++) {
+    const double d = s[hh] - q.E1;
+    q.V = fma(c_gh_w[hh], d * d, q.V);
+  }
+  return q;
+}
+
+// Moments of one frame by MOM_LANES lanes (lane l takes the sources l, l + MOM_LANES, ...), shared by mpd_moments_kernel
+// (lik.hip) and pdgpb_pred_moments_kernel (pdgp_batch.hip).  Fm / Fv: the model's 2P rows, element (row c, this frame) at
+// [c * cs + fo]; smean / svar: P rows, element (i, this frame) at [i * ld + oo]; ymean / yvar / logp: the frame's own slot;
+// yvar takes the noise variance only when add_noise.
+// Each lane writes the moments of its sources and parks a_i = E1_i m_f_i, E2_i, v_f_i + m_f_i^2 and svar_i in LDS (sm: 4 P
+// doubles of this frame); after the barrier lane 0 replays mpd_lik_kernel's sequential accumulation over i = 0..P-1 (same
+// order, same fused operations) and adds up the variances in source order.  Called by every thread of the workgroup
+// (`live` = false for the lanes of a frame beyond the end): it holds a __syncthreads().
+#define MOM_LANES 16
+__device__ __forceinline__ void mpd_moments_frame(const double* __restrict__ Fm, const double* __restrict__ Fv, int64_t cs,
+                                                  int64_t fo, bool live, int l, int P, int nlin, const double* noise, bool add_noise,
+                                                  const double* y, double* __restrict__ smean, double* __restrict__ svar,
+                                                  int64_t ld, int64_t oo, double* ymean, double* yvar, double* logp,
+                                                  double* sm) {
+  double* sa = sm;
+  double* se = sa + P;
+  double* sc = se + P;
+  double* sv = sc + P;
+  if (live) {
+    for (int i = l; i < P; i += MOM_LANES) {
+      const double mg = Fm[i * cs + fo], vg = Fv[i * cs + fo];
+      const double mf = Fm[(i + P) * cs + fo], vf = Fv[(i + P) * cs + fo];
+      const QuadV q = gh_quad_var(nlin, mg, vg);
+      const double a = q.E1 * mf;
+      const double v = fma(q.V, mf * mf, q.E2 * vf);
+      sa[i] = a;
+      se[i] = q.E2;
+      sc[i] = vf + mf * mf;
+      sv[i] = v;
+      if (smean) smean[i * ld + oo] = a;
+      if (svar) svar[i * ld + oo] = v;
+    }
+  }
+  __syncthreads();
+  if (live && l == 0 && (ymean || yvar || logp)) {
+    double A = 0.0, B = 0.0, Cpair = 0.0, S = 0.0;
+    for (int i = 0; i < P; i++) {
+      const double a = sa[i];
+      Cpair = fma(a, A, Cpair);
+      A += a;
+      B = fma(se[i], sc[i], B);
+      S += sv[i];
+    }
+    if (ymean) *ymean = A;
+    if (yvar) *yvar = add_noise ? S + noise[0] : S;
+    if (logp) {
+      const double Y = y[0], s2 = noise[0];
+      const double C = 2.0 * Cpair;
+      const double resid = Y * Y - 2.0 * Y * A + B + C;
+      const double LOG2PI = 1.8378770664093453;
+      *logp = -0.5 * ((1.0 / s2) * resid + LOG2PI + log(s2));
+    }
+  }
+}

@@ -351,3 +351,36 @@ gp_status launch_mean_source(gp_handle h, const double* fmean, int P, int n, int
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Posterior moments of the sources and of the mixture, and the expected log density (gp_mpd_predict_moments): the
+// prediction-side twin of mpd_lik_kernel, in its shape — sixteen lanes per frame, one source per lane, the frame's sums by
+// one lane in source order (mpd_moments_frame, gh_quad.h).  One pass, no gradients.  LDS: [LIK_FRAMES][4][P].
+__global__ void __launch_bounds__(LIK_THREADS) mpd_moments_kernel(const double* __restrict__ Fmu, const double* __restrict__ Fvar,
+                                                                  int64_t rs, int64_t cs, const double* __restrict__ y, int N,
+                                                                  int P, int nlin, const double* __restrict__ noise_var, int add_noise,
+                                                                  double* __restrict__ smean, double* __restrict__ svar,
+                                                                  double* __restrict__ ymean, double* __restrict__ yvar,
+                                                                  double* __restrict__ logp) {
+  extern __shared__ double lik_sm[];
+  const int fl = threadIdx.x / MOM_LANES, l = threadIdx.x % MOM_LANES;
+  const int64_t n = (int64_t)blockIdx.x * LIK_FRAMES + fl;
+  const bool live = (n < N);
+  mpd_moments_frame(Fmu, Fvar, cs, n * rs, live, l, P, nlin, noise_var, add_noise != 0, y ? y + n : nullptr, smean, svar, (int64_t)N, n,
+                    ymean ? ymean + n : nullptr, yvar ? yvar + n : nullptr, logp ? logp + n : nullptr,
+                    lik_sm + (size_t)fl * 4 * P);
+}
+
+gp_status launch_mpd_moments(gp_handle h, const double* Fmu, const double* Fvar, int64_t f_rs, int64_t f_cs, const double* y,
+                             int N, int P, int nlin, const double* noise_var, int add_noise, double* smean, double* svar,
+                             double* ymean, double* yvar, double* logp) {
+  static_assert(MOM_LANES == LIK_LANES, "the moments kernel keeps the likelihood kernel's lane-per-source shape");
+  if (N <= 0) return GP_OK;
+  GpTimerScope ts(h, GP_TIMER_LIK);
+  const size_t sh = (size_t)LIK_FRAMES * 4 * P * sizeof(double);
+  if (sh > 48 * 1024) return gp_fail(h, GP_ERR_UNSUPPORTED, "too many sources for the moments kernel's LDS staging");
+  hipLaunchKernelGGL(mpd_moments_kernel, dim3(mpd_lik_blocks(N)), dim3(LIK_THREADS), sh, h->stream, Fmu, Fvar, f_rs, f_cs, y,
+                     N, P, nlin, noise_var, add_noise, smean, svar, ymean, yvar, logp);
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}

@@ -483,4 +483,37 @@ gp_status gp_pdgp_predict_reuse(gp_pdgp_plan p, const double* params, const doub
   return pdgp_predict_impl(p, params, xnew, n, fmean, fvar, mean_source, true);
 }
 
+// the conditionals into the plan's own fmean / fvar ([2P][n], never copied out), then the moments kernel on them
+static gp_status pdgp_predict_moments_impl(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n,
+                                           const double* ynew, int32_t with_noise, double* smean, double* svar, double* ymean,
+                                           double* yvar, double* logp, bool reuse_factor) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgp_predict_moments: workspace not set");
+  if (p->subset)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_predict_moments: a GP-sharded plan holds only some of the 2P rows (assemble them and call gp_mpd_predict_moments)");
+  if (!params || !xnew || n < 1 || n > p->maxN || (logp && !ynew))
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_predict_moments: bad argument (logp needs ynew)");
+  if (reuse_factor && !p->factor_valid)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_predict_moments_reuse: no factorisation to reuse (call gp_pdgp_predict or gp_pdgp_predict_moments first)");
+  GP_CHECK(pdgp_bind(p, params, xnew, n, nullptr, p->fmean, p->fvar));
+  GP_CHECK(cond_batch_run(h, p->cb, xnew, n, p->whiten != 0, p->jitter, reuse_factor));
+  GP_CHECK(launch_mpd_moments(h, p->fmean, p->fvar, 1, n, ynew, n, p->P, p->nlin, params, with_noise != 0, smean, svar, ymean,
+                              yvar, logp));
+  gp_status st = check_not_pd(h);
+  p->factor_valid = (st == GP_OK);
+  return st;
+}
+
+gp_status gp_pdgp_predict_moments(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const double* ynew,
+                                  int32_t with_noise, double* smean, double* svar, double* ymean, double* yvar, double* logp) {
+  return pdgp_predict_moments_impl(p, params, xnew, n, ynew, with_noise, smean, svar, ymean, yvar, logp, false);
+}
+
+gp_status gp_pdgp_predict_moments_reuse(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n,
+                                        const double* ynew, int32_t with_noise, double* smean, double* svar, double* ymean,
+                                        double* yvar, double* logp) {
+  return pdgp_predict_moments_impl(p, params, xnew, n, ynew, with_noise, smean, svar, ymean, yvar, logp, true);
+}
+
 }  // extern "C"

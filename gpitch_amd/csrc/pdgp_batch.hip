@@ -758,6 +758,42 @@ __global__ void __launch_bounds__(PB_PT) pdgpb_pred_source_kernel(const PbGp* __
   src[pg.src_off + n] = s * fmean[pg.out_off + (int64_t)pg.P * pg.n + n];
 }
 
+// the moments of gp_mpd_predict_moments over the same entries, from the fmean / fvar pdgpb_pred_kernel left in the workspace:
+// the entries of a model's row 0 take the model's frame tile (every source of its PB_PT frames), the others return.  Sixteen
+// lanes per frame as lik.hip's mpd_moments_kernel (mpd_moments_frame, gh_quad.h): PB_MOM_FRAMES frames per pass, PB_PT /
+// PB_MOM_FRAMES passes.  LDS: [PB_MOM_FRAMES][4][maxP].  A frame's results come from its own model's rows only.
+#define PB_MOM_THREADS 256
+#define PB_MOM_FRAMES (PB_MOM_THREADS / MOM_LANES)
+__global__ void __launch_bounds__(PB_MOM_THREADS) pdgpb_pred_moments_kernel(const PbGp* __restrict__ gps, const PbPredGp* __restrict__ pgs,
+                                                                            const int64_t* __restrict__ tile_start, int G,
+                                                                            const double* __restrict__ params,
+                                                                            const double* __restrict__ fmean, const double* __restrict__ fvar,
+                                                                            const double* __restrict__ ynew, double* __restrict__ smean,
+                                                                            double* __restrict__ svar, double* __restrict__ ymean,
+                                                                            double* __restrict__ yvar, double* __restrict__ logp, int maxP) {
+  extern __shared__ double pb_sm[];
+  const int64_t b = blockIdx.x;
+  const int gi = pb_entry_gp(tile_start, G, b);
+  const PbGp g = gps[gi];
+  if (g.row != 0) return;
+  const PbPredGp pg = pgs[gi];
+  const int P = pg.P, fl = threadIdx.x / MOM_LANES, l = threadIdx.x % MOM_LANES;
+  const int64_t t0 = (b - tile_start[gi]) * PB_PT;
+  const double* noise = params + (g.off_theta - 1);      // the model's noise variance sits right before its first GP
+  const double* Fm = fmean + pg.out_off;                 // row 0 of the model: its 2P rows of pg.n frames follow
+  const double* Fv = fvar + pg.out_off;
+  double* sm = pb_sm + (size_t)fl * 4 * maxP;
+  for (int c0 = 0; c0 < PB_PT; c0 += PB_MOM_FRAMES) {
+    const int64_t n = t0 + c0 + fl;
+    const bool live = n < pg.n;
+    const int64_t f = pg.x_off + n;                      // the frame's slot in xnew / ynew / ymean / yvar / logp
+    mpd_moments_frame(Fm, Fv, pg.n, n, live, l, P, pg.nlin, noise, true, ynew ? ynew + f : nullptr,
+                      smean ? smean + pg.src_off : nullptr, svar ? svar + pg.src_off : nullptr, pg.n, n,
+                      ymean ? ymean + f : nullptr, yvar ? yvar + f : nullptr, logp ? logp + f : nullptr, sm);
+    __syncthreads();                                     // lane 0 has read the frame's LDS before the next pass writes it
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 static size_t pb_fwd_lds(const gp_pdgpb_plan_s* p) {
   return ((size_t)p->maxM * p->maxM + p->maxB + 2 * (size_t)p->maxM + PB_TILE_DOUBLES) * sizeof(double);
@@ -1003,15 +1039,13 @@ gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* 
   return GP_OK;
 }
 
-gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off, double* fmean,
-                           double* fvar, double* mean_source, void* workspace, size_t bytes) {
-  if (!p) return GP_ERR_BAD_ARG;
+}  // extern "C"
+
+// the call's records and tile list from xnew_off, on the host and (when there is a tile) on the device; *tiles_out = entries,
+// *latent_out = sum_k 2 P_k n_k; args_ok = 0: the caller's pointers do not allow a call with frames
+static gp_status pb_pred_records(gp_pdgpb_plan_s* p, const int64_t* xnew_off, int args_ok, int64_t* tiles_out,
+                                 int64_t* latent_out) {
   gp_handle h = p->h;
-  if (!p->predict_only || !xnew_off)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument or a training plan (create the plan with cfg->batch == NULL)");
-  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
-  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: xnew_off[0] must be 0");
   p->pgs.resize(p->G);
   p->tiles.resize(p->G + 1);
   int64_t fbase = 0, sbase = 0, tiles = 0;
@@ -1035,13 +1069,32 @@ gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* 
     sbase += (int64_t)md.P * n;
   }
   p->tiles[p->G] = tiles;
+  *tiles_out = tiles;
+  *latent_out = fbase;
   if (tiles == 0) return GP_OK;
-  if (!xnew || !fmean || !fvar) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument");
+  if (!args_ok) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument");
   if (tiles > 0x7fffffff) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: more than 2^31 - 1 frame tiles in one call");
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_pgs, p->pgs.data(), p->pgs.size() * sizeof(PbPredGp), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_tiles, p->tiles.data(), p->tiles.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   // pageable host vectors again: the next call rewrites them
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return GP_OK;
+}
+
+extern "C" {
+
+gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off, double* fmean,
+                           double* fvar, double* mean_source, void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->predict_only || !xnew_off)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument or a training plan (create the plan with cfg->batch == NULL)");
+  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
+  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: xnew_off[0] must be 0");
+  int64_t tiles = 0, latent = 0;
+  GP_CHECK(pb_pred_records(p, xnew_off, (xnew && fmean && fvar) ? 1 : 0, &tiles, &latent));
+  if (tiles == 0) return GP_OK;
   hipLaunchKernelGGL(pdgpb_pred_kernel, dim3((unsigned)tiles), dim3(PB_PRED_THREADS), pb_pred_lds(p), h->stream, p->d_gps, p->d_pgs,
                      p->d_tiles, p->G, params, p->d_G, xnew, fmean, fvar, pb_pad16(p->maxM));
   GP_HIP_CHECK(h, hipGetLastError());
@@ -1050,6 +1103,57 @@ gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* 
                        p->G, fmean, mean_source);
     GP_HIP_CHECK(h, hipGetLastError());
   }
+  return GP_OK;
+}
+
+size_t gp_pdgpb_predict_moments_workspace_bytes(gp_pdgpb_plan p, int64_t latent_frames) {
+  if (!p || !p->predict_only || latent_frames < 0) return 0;
+  return pb_pred_region_bytes(p) + 2 * gp_align_up((size_t)latent_frames * sizeof(double), 256) + 256;
+}
+
+gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
+                                   const double* ynew, double* smean, double* svar, double* ymean, double* yvar, double* logp,
+                                   void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->predict_only || !xnew_off)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: bad argument or a training plan (create the plan with cfg->batch == NULL)");
+  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
+  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: xnew_off[0] must be 0");
+  int maxP = 1;
+  bool any = false;
+  for (int k = 0; k < p->nm; k++) {
+    if (xnew_off[k + 1] < xnew_off[k]) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: xnew_off must not decrease");
+    any = any || xnew_off[k + 1] > xnew_off[k];
+    maxP = std::max(maxP, p->models[k].P);
+  }
+  if (!any) return GP_OK;
+  if (!xnew || (logp && !ynew)) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: bad argument (logp needs ynew)");
+  const size_t lds = (size_t)PB_MOM_FRAMES * 4 * maxP * sizeof(double);
+  if (lds > 48 * 1024) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_predict_moments: too many sources for the moments kernel's LDS staging");
+  int64_t latent = 0;
+  for (int k = 0; k < p->nm; k++) latent += 2 * (int64_t)p->models[k].P * (xnew_off[k + 1] - xnew_off[k]);
+  // fmean / fvar of this call: behind gp_pdgpb_predict_prepare's regions of the same workspace
+  GpArena ar(workspace, bytes);
+  ar.take<PbGp>(p->gps.size());
+  ar.take<int32_t>(p->nm);
+  ar.take<PbPredGp>(p->gps.size());
+  ar.take<int64_t>(p->gps.size() + 1);
+  ar.take<double>(p->pred_g);
+  double* fm = ar.take<double>((size_t)latent);
+  double* fv = ar.take<double>((size_t)latent);
+  if (!ar.ok || !fm || !fv)
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_moments: the workspace does not hold this call's fmean / fvar (gp_pdgpb_predict_moments_workspace_bytes)");
+  int64_t tiles = 0, lat2 = 0;
+  GP_CHECK(pb_pred_records(p, xnew_off, 1, &tiles, &lat2));
+  if (tiles == 0) return GP_OK;
+  hipLaunchKernelGGL(pdgpb_pred_kernel, dim3((unsigned)tiles), dim3(PB_PRED_THREADS), pb_pred_lds(p), h->stream, p->d_gps, p->d_pgs,
+                     p->d_tiles, p->G, params, p->d_G, xnew, fm, fv, pb_pad16(p->maxM));
+  GP_HIP_CHECK(h, hipGetLastError());
+  hipLaunchKernelGGL(pdgpb_pred_moments_kernel, dim3((unsigned)tiles), dim3(PB_MOM_THREADS), lds, h->stream, p->d_gps, p->d_pgs,
+                     p->d_tiles, p->G, params, fm, fv, ynew, smean, svar, ymean, yvar, logp, maxP);
+  GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
 

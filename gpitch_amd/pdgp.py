@@ -675,6 +675,81 @@ class Pdgp(Parameterized):
                 [col(fm, P + i) for i in range(P)], [col(fv, P + i) for i in range(P)],
                 [col(src, i) for i in range(P)])
 
+    # ------------------------------------------------------------------------------------------
+    # posterior of the sources, of the mixture, and held-out density (csrc/lik.hip mpd_moments_kernel through
+    # gp_pdgp_predict_moments: the conditionals stay on the device, only the requested arrays come back)
+    def _predict_moments(self, xnew, ynew=None, sources=False, y=False, logp=False, noise=True):
+        """(smean, svar) P x n, (ymean, yvar) n, logp n — None for what was not asked for.  Chunked by _max_batch with
+        the factorisation reused, as _predict; the prediction memo of _predict is neither read nor written."""
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim > 2 or (xnew.ndim == 2 and xnew.shape[1] != 1):
+            raise ValueError("xnew has shape %r, not (n,) or (n, 1)" % (xnew.shape,))
+        xnew = xnew.reshape(-1)
+        P, n = self.num_sources, xnew.size
+        if logp:
+            if ynew is None:
+                raise ValueError("expected_log_density needs ynew")
+            ynew = np.asarray(ynew, dtype=np.float64)
+            if ynew.ndim > 2 or (ynew.ndim == 2 and ynew.shape[1] != 1) or ynew.size != n:
+                raise ValueError("ynew has shape %r for %d inputs in xnew" % (ynew.shape, n))
+            ynew = ynew.reshape(-1)
+        if self._shard:
+            # the rows are assembled over the ranks as _predict does; the operator entry runs on the assembled rows
+            fm, fv, _ = self._predict(xnew, False)
+            return self.likelihood._moments(fm.T, fv.T, ynew, sources=sources, y=y, logp=logp, noise=noise)
+        state = (param_version(), self._adam_t)
+        reuse = self._plan is not None and getattr(self, "_pred_state", None) == state
+        if not reuse:
+            self._pack()
+        h = self._handle
+        call = h.lib.gp_pdgp_predict_moments_reuse if reuse else h.lib.gp_pdgp_predict_moments
+        sm, sv = (np.zeros((P, n)), np.zeros((P, n))) if sources else (None, None)
+        ym, yv = (np.zeros(n), np.zeros(n)) if y else (None, None)
+        lp = np.zeros(n) if logp else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        step = self._max_batch
+        for s in range(0, n, step):
+            xs = h.to_device(xnew[s:s + step])
+            c = xs.numel()
+            ys = h.to_device(ynew[s:s + step]) if logp else None
+            dsm, dsv = (h.empty(P, c), h.empty(P, c)) if sources else (None, None)
+            dym, dyv = (h.empty(c), h.empty(c)) if y else (None, None)
+            dlp = h.empty(c) if logp else None
+            h.check(call(self._plan, self._params.data_ptr(), xs.data_ptr(), c, ptr(ys), int(bool(noise)), ptr(dsm),
+                         ptr(dsv), ptr(dym), ptr(dyv), ptr(dlp)))
+            call = h.lib.gp_pdgp_predict_moments_reuse     # further chunks share the factorisation
+            for dst, src in ((sm, dsm), (sv, dsv), (ym, dym), (yv, dyv), (lp, dlp)):
+                if dst is not None:
+                    dst[..., s:s + c] = src.cpu().numpy()
+        if n:
+            self._pred_state = state
+        return sm, sv, ym, yv, lp
+
+    def predict_sources(self, xnew):
+        """posterior mean and variance under q of every source nlin(g_i) f_i at xnew: (mean_s, var_s), lists of P (n, 1)
+        arrays.  mean_s[i] = E[nlin(g_i)] E[f_i] with the nonlinearity integrated by the likelihood's 20-point rule
+        (predict_act_n_com's mean_source plugs the activation's mean in instead)."""
+        sm, sv, _, _, _ = self._predict_moments(xnew, sources=True)
+        col = lambda a, i: a[i].reshape(-1, 1).copy()
+        P = self.num_sources
+        return [col(sm, i) for i in range(P)], [col(sv, i) for i in range(P)]
+
+    def predict_y(self, xnew):
+        """GPflow Model.predict_y: mean and variance of the observed mixture at xnew, (n, 1) each; the sources are
+        independent under q, the variance includes the noise variance"""
+        _, _, ym, yv, _ = self._predict_moments(xnew, y=True)
+        return ym.reshape(-1, 1), yv.reshape(-1, 1)
+
+    def predict_mixture(self, xnew):
+        """mean and variance of the latent mixture sum_i nlin(g_i) f_i at xnew (predict_y without the noise variance)"""
+        _, _, ym, yv, _ = self._predict_moments(xnew, y=True, noise=False)
+        return ym.reshape(-1, 1), yv.reshape(-1, 1)
+
+    def expected_log_density(self, xnew, ynew):
+        """E_q[log p(ynew_n | g, f)] per frame, (n, 1): MpdLik.variational_expectations at the posterior's moments at xnew,
+        not scaled by N / B and without the KL terms — on the training data, the data term of the ELBO"""
+        return self._predict_moments(xnew, ynew, logp=True)[4].reshape(-1, 1)
+
     def __del__(self):
         try:
             if self._plan is not None and self._handle is not None and self._handle.h:

@@ -524,3 +524,140 @@ def predict_many(models, xnews):
                     [col(fm, Pk + i) for i in range(Pk)], [col(fv, Pk + i) for i in range(Pk)],
                     [col(src, i) for i in range(Pk)]))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# posterior of the sources, predictive moments of the mixture and held-out density of many models
+# (csrc/pdgp_batch.hip pdgpb_pred_moments_kernel, gp_pdgpb_predict_moments)
+def _targets(ynews, xs):
+    """ynews as flat float64 arrays, one per model, each as long as the model's inputs (ValueError otherwise)"""
+    if ynews is None:
+        return None
+    if isinstance(ynews, (list, tuple)):
+        if len(ynews) != len(xs):
+            raise ValueError("predict_sources_many: %d target arrays for %d models" % (len(ynews), len(xs)))
+        ys = list(ynews)
+    else:
+        ys = [ynews] * len(xs)
+    out = []
+    for k, (yk, x) in enumerate(zip(ys, xs)):
+        a = np.asarray(yk, dtype=np.float64)
+        if a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 1) or a.size != x.size:
+            raise ValueError("predict_sources_many: targets of model %d have shape %r for %d inputs" % (k, a.shape, x.size))
+        out.append(a.reshape(-1))
+    return out
+
+
+def predict_sources_many(models, xnews, ynews=None):
+    """Pdgp.predict_sources, predict_y and (with ynews) expected_log_density of every model at its own inputs, all models
+    together:
+
+        res = predict_sources_many(models, xnews, ynews)
+        res[k]["mean_s"], res[k]["var_s"]   # lists of P_k (n_k, 1) arrays: models[k].predict_sources(xnews[k])
+        res[k]["mean_y"], res[k]["var_y"]   # (n_k, 1): models[k].predict_y(xnews[k])
+        res[k]["logp"]                      # (n_k, 1): models[k].expected_log_density(xnews[k], ynews[k]); absent without ynews
+
+    Scope, chunking and staging are predict_many's (check_predictable, predict_chunks, page-locked buffers); the moments
+    of the 2P latent GPs stay in the device workspace.  xnews / ynews: one array per model or one array for every model;
+    ynews[k] must be as long as xnews[k].  Reads each model's current Params and changes nothing."""
+    models, xs = check_predictable(models, xnews)
+    ys = _targets(ynews, xs)
+    h = _lib.default_handle()
+    t = h.torch
+    nm = len(models)
+    P = [m.num_sources for m in models]
+    counts = [x.size for x in xs]
+    i32 = C.c_int32
+    gps = [g for m in models for g in _gps(m)]
+    keep = dict(P=(i32 * nm)(*P), nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in models]),
+                M=(i32 * len(gps))(*[g[1].size for g in gps]), kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
+                mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
+    from .pdgp import jitter
+    cfg = _lib.PdgpBatchConfig(nm, keep["P"], None, keep["nlin"], None, keep["M"], keep["kt"], keep["mp"], jitter)
+    segs, base = [], 0
+    for m in models:
+        sm, n = model_segments(m, base)
+        segs += sm
+        base += n
+    whole = predict_layout(P, counts)
+    chunks = predict_chunks(P, counts, MAX_PREDICT_FRAMES)
+    ns_all, nx_all = int(whole["src_base"][-1]), int(whole["x_off"][-1])
+    names = ("mean_s", "var_s", "mean_y", "var_y") + (("logp",) if ys is not None else ())
+    res = {"mean_s": np.zeros(ns_all), "var_s": np.zeros(ns_all)}
+    for name in names[2:]:
+        res[name] = np.zeros(nx_all)
+    plan = C.c_void_p()
+    h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
+    try:
+        if int(h.lib.gp_pdgpb_num_params(plan)) != base:
+            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
+        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
+        host = ppin.numpy()
+        for off, p in segs:
+            v = p.value.reshape(-1)
+            host[off:off + v.size] = v
+        params = ppin.to(h.device, non_blocking=True)
+        # the largest chunk's fmean / fvar live behind the factors in the one workspace
+        latent = max(int(np.dot(2 * np.asarray(P, dtype=np.int64), c[:, 1])) for c in chunks)
+        ws = h.workspace(h.lib.gp_pdgpb_predict_moments_workspace_bytes(plan, latent))
+        h.check(h.lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
+        for chunk in chunks:
+            c = chunk[:, 1]
+            if not c.any():
+                continue
+            lay = predict_layout(P, c)
+            ns, nx = int(lay["src_base"][-1]), int(lay["x_off"][-1])
+            xpin = t.empty(nx * (2 if ys is not None else 1), dtype=t.float64, pin_memory=True)
+            np.concatenate([xs[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[:nx])
+            if ys is not None:
+                np.concatenate([ys[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[nx:])
+            xd = xpin.to(h.device, non_blocking=True)
+            sizes = [ns, ns] + [nx] * (len(names) - 2)
+            starts = np.concatenate([[0], np.cumsum(sizes)])
+            buf = h.empty(int(starts[-1]))              # smean | svar | ymean | yvar [| logp]: one copy back to the host
+            part = [buf[int(a):] for a in starts[:-1]]
+            off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
+            h.check(h.lib.gp_pdgpb_predict_moments(plan, params.data_ptr(), xd.data_ptr(), off,
+                                                   xd[nx:].data_ptr() if ys is not None else None,
+                                                   part[0].data_ptr(), part[1].data_ptr(), part[2].data_ptr(),
+                                                   part[3].data_ptr(), part[4].data_ptr() if ys is not None else None,
+                                                   ws.data_ptr(), ws.numel()))
+            pin = t.empty(int(starts[-1]), dtype=t.float64, pin_memory=True)
+            pin.copy_(buf, non_blocking=True)
+            h.sync()
+            got = pin.numpy().copy()
+            del xpin, pin
+            for j, name in enumerate(names):
+                g = got[int(starts[j]):int(starts[j + 1])]
+                if len(chunks) == 1:
+                    res[name] = g
+                    continue
+                for k, (s, n) in enumerate(chunk):
+                    if n == 0:
+                        continue
+                    if j < 2:
+                        d = res[name][whole["src_base"][k]:whole["src_base"][k + 1]].reshape(P[k], counts[k])
+                        d[:, s:s + n] = g[lay["src_base"][k]:lay["src_base"][k + 1]].reshape(P[k], n)
+                    else:
+                        res[name][whole["x_off"][k] + s:whole["x_off"][k] + s + n] = g[lay["x_off"][k]:lay["x_off"][k + 1]]
+        del ppin
+        bad = (C.c_int32 * nm)()
+        h.check(h.lib.gp_pdgpb_not_pd(plan, bad, 1))
+    finally:
+        h.sync()
+        h.lib.gp_pdgpb_destroy(plan)
+    for k in range(nm):
+        if bad[k]:
+            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "predict_sources_many: model %d: Cholesky failed: %s"
+                                                % (k, _describe_not_pd(bad[k])))
+    out = []
+    for k in range(nm):
+        sb, xo = whole["src_base"], whole["x_off"]
+        item = {}
+        for name in names[:2]:
+            a = res[name][sb[k]:sb[k + 1]].reshape(P[k], counts[k])
+            item[name] = [a[i].reshape(-1, 1) for i in range(P[k])]
+        for name in names[2:]:
+            item[name] = res[name][xo[k]:xo[k + 1]].reshape(-1, 1)
+        out.append(item)
+    return out

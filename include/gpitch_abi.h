@@ -166,6 +166,21 @@ gp_status gp_gauss_kl_matrix(gp_handle h, const double* q_mu, const double* q_sq
 gp_status gp_mpd_varexp(gp_handle h, const double* Fmu, const double* Fvar, const double* y, int32_t N,
                         int32_t P, int32_t nlin, const double* noise_var, double* per_frame, double* sum_host);
 
+/* Posterior moments of the sources, of the mixture and the expected log density, from the moments of the 2P latent GPs
+ * (the prediction-side counterpart of gp_mpd_varexp; same 20-point rule, weights and nonlinearities).  With g ~ N(m_g, v_g),
+ * f ~ N(m_f, v_f) independent under q, E1 = E[nlin(g)], E2 = E[nlin(g)^2] and V = sum_h w_h (nlin(x_h) - E1)^2:
+ *   smean[i][n] = E1 m_f                      posterior mean of source i = nlin(g_i) f_i
+ *   svar[i][n]  = V m_f^2 + E2 v_f            its variance (both terms non-negative: svar >= 0 exactly)
+ *   ymean[n]    = sum_i smean[i][n]           in source order
+ *   yvar[n]     = sum_i svar[i][n] + noise    in source order; noise_var == NULL: the latent mixture, nothing added
+ *   logp[n]     = MpdLik.variational_expectations(Fmu, Fvar, y)[n]   (E_q log p(y_n | g, f); not scaled, no KL)
+ * Fmu/Fvar are N x 2P row-major as in gp_mpd_varexp; smean/svar are P x N row-major; ymean/yvar/logp hold N values.
+ * Every output may be NULL; logp needs y and noise_var.  noise_var is a device scalar.  float64; asynchronous on the
+ * handle's stream; every sum is one lane's sequential loop, so two calls give bit-identical results. */
+gp_status gp_mpd_predict_moments(gp_handle h, const double* Fmu, const double* Fvar, const double* y, int32_t N, int32_t P,
+                                 int32_t nlin, const double* noise_var, double* smean, double* svar, double* ymean,
+                                 double* yvar, double* logp);
+
 /* ---- L3 model: Pdgp (gpitch/pdgp.py:48-208) ---------------------------------------------------
  * Parameter vector layout (float64, constrained space), offsets returned by gp_pdgp_layout:
  *   [ noise_var | for g in (act_0..act_{P-1}, com_0..com_{P-1}):
@@ -323,6 +338,19 @@ gp_status gp_pdgp_predict(gp_pdgp_plan p, const double* params, const double* xn
  * between).  pdgp.py:17-44 (predict_windowed) re-factorises for every window and for act / com separately. */
 gp_status gp_pdgp_predict_reuse(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n,
                                 double* fmean, double* fvar, double* mean_source);
+
+/* gp_pdgp_predict / _reuse into the plan's workspace, then the moments of gp_mpd_predict_moments at xnew with the plan's
+ * nonlinearity and the noise variance params[0]: the 2P x n conditional moments never leave the device.  smean / svar:
+ * P x n row-major; ymean / yvar / logp: n values; every output may be NULL.  ynew (n device values, may be NULL) is needed
+ * for logp only.  with_noise = 0 leaves the noise variance out of yvar (the latent mixture sum_i nlin(g_i) f_i).  A subset
+ * (GP-sharded) plan holds only some rows: GP_ERR_BAD_ARG.  Synchronises and reports a failed factorisation as
+ * gp_pdgp_predict does; _reuse under gp_pdgp_predict_reuse's condition (either pair of entries may have made the
+ * factorisation). */
+gp_status gp_pdgp_predict_moments(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const double* ynew,
+                                  int32_t with_noise, double* smean, double* svar, double* ymean, double* yvar, double* logp);
+gp_status gp_pdgp_predict_moments_reuse(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n,
+                                        const double* ynew, int32_t with_noise, double* smean, double* svar, double* ymean,
+                                        double* yvar, double* logp);
 
 /* ---- overlap-add of per-window predictions (gpitch/window_overlap.py:19-59: merged_mean / merged_variance) ----------
  * windows: num_windows x ws (row-major, leading dimension ld) device array of per-window means (square = 0) or
@@ -540,6 +568,20 @@ size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p);
 gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* workspace, size_t bytes);
 gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
                            double* fmean, double* fvar, double* mean_source, void* workspace, size_t bytes);
+
+/* The moments of gp_mpd_predict_moments for every model of a prediction-only plan, each with its own P, nonlinearity and
+ * noise variance: pdgpb_pred_kernel leaves fmean / fvar in the workspace (they never cross to the host) and one more launch
+ * forms, model-major with 64-bit offsets: smean / svar (per model P rows of n_k frames, the layout of mean_source) and
+ * ymean / yvar / logp (per frame, concatenated as xnew).  ynew (device, concatenated as xnew; may be NULL) is needed for
+ * logp only; every output may be NULL.  The workspace is the one given to gp_pdgpb_predict_prepare, which for this entry
+ * must have gp_pdgpb_predict_moments_workspace_bytes(plan, latent_frames) bytes, latent_frames >= sum_k 2 P_k n_k of the
+ * largest call (gp_pdgpb_predict_workspace_bytes plus two arrays of that many doubles); a call that needs more returns
+ * GP_ERR_WORKSPACE.  Bit-identical between calls; a model's results depend neither on the other models of the call nor on
+ * how its frames are split between calls. */
+size_t gp_pdgpb_predict_moments_workspace_bytes(gp_pdgpb_plan p, int64_t latent_frames);
+gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
+                                   const double* ynew, double* smean, double* svar, double* ymean, double* yvar, double* logp,
+                                   void* workspace, size_t bytes);
 
 /* ---- kernel learning from an isolated-note recording (the drivers' init_kernel(train=True) branch,
  *      gpitch/transcription.py:176-195, gpitch/separation.py:185-204) -------------------------------------------------
