@@ -161,7 +161,7 @@ struct GpArena {
   T* take(size_t count) {
     size_t bytes = gp_align_up(count * sizeof(T), 256);
     if (off + bytes > size) { ok = false; return nullptr; }
-    T* r = (T*)(base + off);
+    T* r = base ? (T*)(base + off) : nullptr;     // no base: the arena only measures (`off` = bytes asked for)
     off += bytes;
     return r;
   }

@@ -998,14 +998,22 @@ gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear) 
 }
 
 // ---- prediction ----------------------------------------------------------------------------------------------------
+// gp_pdgpb_predict_prepare's regions of a workspace, in order (gp_pdgpb_predict_moments keeps fmean / fvar behind them)
+struct PbPredRegions { PbGp* gps; int32_t* status; PbPredGp* pgs; int64_t* tiles; double* G; };
+static PbPredRegions pb_pred_regions(const gp_pdgpb_plan_s* p, GpArena& ar) {
+  PbPredRegions r;
+  r.gps = ar.take<PbGp>(p->gps.size());
+  r.status = ar.take<int32_t>(p->nm);
+  r.pgs = ar.take<PbPredGp>(p->gps.size());
+  r.tiles = ar.take<int64_t>(p->gps.size() + 1);
+  r.G = ar.take<double>(p->pred_g);
+  return r;
+}
+
 static size_t pb_pred_region_bytes(const gp_pdgpb_plan_s* p) {
-  size_t b = 0;
-  b += gp_align_up(p->gps.size() * sizeof(PbGp), 256);
-  b += gp_align_up((size_t)p->nm * sizeof(int32_t), 256);
-  b += gp_align_up(p->gps.size() * sizeof(PbPredGp), 256);
-  b += gp_align_up((p->gps.size() + 1) * sizeof(int64_t), 256);
-  b += gp_align_up((size_t)p->pred_g * sizeof(double), 256);
-  return b;
+  GpArena ar(nullptr, SIZE_MAX);     // no memory behind it: measures
+  pb_pred_regions(p, ar);
+  return ar.off;
 }
 
 size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p) { return (p && p->predict_only) ? pb_pred_region_bytes(p) + 256 : 0; }
@@ -1018,12 +1026,9 @@ gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* 
   if (!workspace || bytes < gp_pdgpb_predict_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_prepare: workspace too small or not 256-byte aligned");
   GpArena ar(workspace, bytes);
-  p->d_gps = ar.take<PbGp>(p->gps.size());
-  p->d_status = ar.take<int32_t>(p->nm);
-  p->d_pgs = ar.take<PbPredGp>(p->gps.size());
-  p->d_tiles = ar.take<int64_t>(p->gps.size() + 1);
-  p->d_G = ar.take<double>(p->pred_g);
+  const PbPredRegions r = pb_pred_regions(p, ar);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_prepare: arena overflow");
+  p->d_gps = r.gps; p->d_status = r.status; p->d_pgs = r.pgs; p->d_tiles = r.tiles; p->d_G = r.G;
   p->pred_ws = nullptr;
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_gps, p->gps.data(), p->gps.size() * sizeof(PbGp), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
@@ -1041,10 +1046,23 @@ gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* 
 
 }  // extern "C"
 
-// the call's records and tile list from xnew_off, on the host and (when there is a tile) on the device; *tiles_out = entries,
-// *latent_out = sum_k 2 P_k n_k; args_ok = 0: the caller's pointers do not allow a call with frames
-static gp_status pb_pred_records(gp_pdgpb_plan_s* p, const int64_t* xnew_off, int args_ok, int64_t* tiles_out,
-                                 int64_t* latent_out) {
+// what gp_pdgpb_predict and gp_pdgpb_predict_moments (`who`, named in the messages) ask before anything else: a
+// predict-only plan, xnew_off starting at 0, and the workspace and parameters gp_pdgpb_predict_prepare was given
+static gp_status pb_pred_check(gp_pdgpb_plan_s* p, const char* who, const double* params, const int64_t* xnew_off,
+                               const void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  const std::string w(who);
+  if (!p->predict_only || !xnew_off)
+    return gp_fail(p->h, GP_ERR_BAD_ARG, (w + ": bad argument or a training plan (create the plan with cfg->batch == NULL)").c_str());
+  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
+    return gp_fail(p->h, GP_ERR_BAD_ARG, (w + ": call gp_pdgpb_predict_prepare first with the same parameters and workspace").c_str());
+  if (xnew_off[0] != 0) return gp_fail(p->h, GP_ERR_BAD_ARG, (w + ": xnew_off[0] must be 0").c_str());
+  return GP_OK;
+}
+
+// the call's records and tile list from xnew_off, on the host and (when there is a tile) on the device; *tiles_out = entries;
+// args_ok = 0: the caller's pointers do not allow a call with frames
+static gp_status pb_pred_records(gp_pdgpb_plan_s* p, const int64_t* xnew_off, int args_ok, int64_t* tiles_out) {
   gp_handle h = p->h;
   p->pgs.resize(p->G);
   p->tiles.resize(p->G + 1);
@@ -1070,7 +1088,6 @@ static gp_status pb_pred_records(gp_pdgpb_plan_s* p, const int64_t* xnew_off, in
   }
   p->tiles[p->G] = tiles;
   *tiles_out = tiles;
-  *latent_out = fbase;
   if (tiles == 0) return GP_OK;
   if (!args_ok) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument");
   if (tiles > 0x7fffffff) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: more than 2^31 - 1 frame tiles in one call");
@@ -1085,15 +1102,10 @@ extern "C" {
 
 gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off, double* fmean,
                            double* fvar, double* mean_source, void* workspace, size_t bytes) {
-  if (!p) return GP_ERR_BAD_ARG;
+  GP_CHECK(pb_pred_check(p, "gp_pdgpb_predict", params, xnew_off, workspace, bytes));
   gp_handle h = p->h;
-  if (!p->predict_only || !xnew_off)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: bad argument or a training plan (create the plan with cfg->batch == NULL)");
-  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
-  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict: xnew_off[0] must be 0");
-  int64_t tiles = 0, latent = 0;
-  GP_CHECK(pb_pred_records(p, xnew_off, (xnew && fmean && fvar) ? 1 : 0, &tiles, &latent));
+  int64_t tiles = 0;
+  GP_CHECK(pb_pred_records(p, xnew_off, (xnew && fmean && fvar) ? 1 : 0, &tiles));
   if (tiles == 0) return GP_OK;
   hipLaunchKernelGGL(pdgpb_pred_kernel, dim3((unsigned)tiles), dim3(PB_PRED_THREADS), pb_pred_lds(p), h->stream, p->d_gps, p->d_pgs,
                      p->d_tiles, p->G, params, p->d_G, xnew, fmean, fvar, pb_pad16(p->maxM));
@@ -1114,40 +1126,27 @@ size_t gp_pdgpb_predict_moments_workspace_bytes(gp_pdgpb_plan p, int64_t latent_
 gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
                                    const double* ynew, double* smean, double* svar, double* ymean, double* yvar, double* logp,
                                    void* workspace, size_t bytes) {
-  if (!p) return GP_ERR_BAD_ARG;
+  GP_CHECK(pb_pred_check(p, "gp_pdgpb_predict_moments", params, xnew_off, workspace, bytes));
   gp_handle h = p->h;
-  if (!p->predict_only || !xnew_off)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: bad argument or a training plan (create the plan with cfg->batch == NULL)");
-  if (!workspace || workspace != p->pred_ws || bytes < gp_pdgpb_predict_workspace_bytes(p) || params != p->pred_params)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: call gp_pdgpb_predict_prepare first with the same parameters and workspace");
-  if (xnew_off[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: xnew_off[0] must be 0");
   int maxP = 1;
-  bool any = false;
+  int64_t latent = 0;      // sum_k 2 P_k n_k; without frames the call is done before any pointer is looked at
   for (int k = 0; k < p->nm; k++) {
     if (xnew_off[k + 1] < xnew_off[k]) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: xnew_off must not decrease");
-    any = any || xnew_off[k + 1] > xnew_off[k];
+    latent += 2 * (int64_t)p->models[k].P * (xnew_off[k + 1] - xnew_off[k]);
     maxP = std::max(maxP, p->models[k].P);
   }
-  if (!any) return GP_OK;
+  if (latent == 0) return GP_OK;
   if (!xnew || (logp && !ynew)) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: bad argument (logp needs ynew)");
   const size_t lds = (size_t)PB_MOM_FRAMES * 4 * maxP * sizeof(double);
   if (lds > 48 * 1024) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_predict_moments: too many sources for the moments kernel's LDS staging");
-  int64_t latent = 0;
-  for (int k = 0; k < p->nm; k++) latent += 2 * (int64_t)p->models[k].P * (xnew_off[k + 1] - xnew_off[k]);
   // fmean / fvar of this call: behind gp_pdgpb_predict_prepare's regions of the same workspace
   GpArena ar(workspace, bytes);
-  ar.take<PbGp>(p->gps.size());
-  ar.take<int32_t>(p->nm);
-  ar.take<PbPredGp>(p->gps.size());
-  ar.take<int64_t>(p->gps.size() + 1);
-  ar.take<double>(p->pred_g);
-  double* fm = ar.take<double>((size_t)latent);
-  double* fv = ar.take<double>((size_t)latent);
+  pb_pred_regions(p, ar);
+  double *fm = ar.take<double>((size_t)latent), *fv = ar.take<double>((size_t)latent);
   if (!ar.ok || !fm || !fv)
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_moments: the workspace does not hold this call's fmean / fvar (gp_pdgpb_predict_moments_workspace_bytes)");
-  int64_t tiles = 0, lat2 = 0;
-  GP_CHECK(pb_pred_records(p, xnew_off, 1, &tiles, &lat2));
-  if (tiles == 0) return GP_OK;
+  int64_t tiles = 0;       // > 0: there are frames
+  GP_CHECK(pb_pred_records(p, xnew_off, 1, &tiles));
   hipLaunchKernelGGL(pdgpb_pred_kernel, dim3((unsigned)tiles), dim3(PB_PRED_THREADS), pb_pred_lds(p), h->stream, p->d_gps, p->d_pgs,
                      p->d_tiles, p->G, params, p->d_G, xnew, fm, fv, pb_pad16(p->maxM));
   GP_HIP_CHECK(h, hipGetLastError());

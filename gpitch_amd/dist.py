@@ -68,6 +68,17 @@ def require_group(world, what):
         raise RuntimeError("%s: the model is sharded over %d ranks, the process group has %d" % (what, world, dist.get_world_size()))
 
 
+def rccl_comm(handle, world):
+    """the handle's RCCL communicator when a model sharded over `world` ranks can use the library's one-call forms
+    (begin -> exchange -> end inside one call): an nccl process group of exactly that size, or no group at all for a
+    one-rank model.  None: the torch.distributed exchange between the two stages (gloo rehearsals, emulated ranks).
+    The models cache the answer."""
+    import torch.distributed as dist
+    grouped = dist.is_available() and dist.is_initialized()
+    ok = (grouped and dist.get_backend() == "nccl" and dist.get_world_size() == world) or (not grouped and world == 1)
+    return handle.comm() if ok else None
+
+
 def allreduce_max_(t):
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:

@@ -171,6 +171,20 @@ class MinibatchData(DataHolder):
         return self.rng.permutation(N)[:self.minibatch_size]
 
 
+def draw_in_lockstep(x, y, draw, times=1):
+    """`draw()` takes `times` minibatches of indices from x's generator; y's, seeded like x's so that rows stay paired
+    (pdgp.py:76-77), is advanced by the same draws: by copying x's state, or by drawing `times` minibatches of its own
+    when a generator gives no access to its state.  Returns the indices with every minibatch sorted in time order."""
+    idx = draw()
+    if y.rng is not x.rng:
+        if hasattr(x.rng, "get_state") and hasattr(y.rng, "set_state"):
+            y.rng.set_state(x.rng.get_state())
+        else:
+            for _ in range(times):
+                y.next_indices()
+    return np.sort(idx, axis=-1, kind="stable")
+
+
 class Parameterized(object):
     """Anything with Params.  `.fixed = True` fixes every Param underneath (GPflow semantics used at
     init_models.py:97-98)."""

@@ -10,10 +10,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, flatvec
+from .flatvec import col
 from .likelihoods import MpdLik
 from .methods import logistic, logistic_tf, nlin_code
-from .param import MinibatchData, Param, ParamList, Parameterized, param_version, sorted_params
+from .param import MinibatchData, Param, ParamList, Parameterized, draw_in_lockstep, param_version
 from .train import AdamOptimizer, OptimizeResult
 
 jitter = 1e-6   # gpflow settings.numerics.jitter_level (pdgp.py:14)
@@ -146,19 +147,13 @@ class Pdgp(Parameterized):
     # engine plumbing
     def _gps(self):
         """GP order of the engine: act then com of the pitches this rank holds (all of them when unsharded)"""
-        out = []
+        return flatvec.latent_gps(self, self._rows())
+
+    def _rows(self):
+        """the engine's latent GPs as rows of the model's order [g_0..g_{P-1}, f_0..f_{P-1}]"""
         if self._gp_shard is not None:
-            P = self.num_sources
-            for g in self._gp_shard:
-                i = g if g < P else g - P
-                out.append((self.kern_act[i], self.za[i], self.q_mu_act[i], self.q_sqrt_act[i]) if g < P else
-                           (self.kern_com[i], self.zc[i], self.q_mu_com[i], self.q_sqrt_com[i]))
-            return out
-        for i in self._local:
-            out.append((self.kern_act[i], self.za[i], self.q_mu_act[i], self.q_sqrt_act[i]))
-        for i in self._local:
-            out.append((self.kern_com[i], self.zc[i], self.q_mu_com[i], self.q_sqrt_com[i]))
-        return out
+            return list(self._gp_shard)
+        return self._local + [self.num_sources + i for i in self._local]
 
     def _compile(self):
         if self._plan is not None:
@@ -265,18 +260,10 @@ class Pdgp(Parameterized):
         """host Param values -> device parameter vector, free state and transform codes"""
         self._compile()
         h = self._handle
-        host = np.zeros(self._nparams)
-        tc = np.full(self._nparams, 2, dtype=np.uint8)   # padding slots: fixed
-        for off, p in self._segments():
-            v = p.value.reshape(-1)
-            host[off:off + v.size] = v
-            tc[off:off + v.size] = 2 if p.fixed else p.transform.device_code(h)
+        host, tc = flatvec.pack(self._segments(), self._nparams, h)     # padding slots: fixed
         self._params.copy_(h.torch.as_tensor(host))
         self._tcode.copy_(h.torch.as_tensor(tc))
-        # `.fixed` Params drop out of the backward pass (GPflow removes them from the free state)
-        for g, (kern, z, q_mu, q_sqrt) in enumerate(self._gps()):
-            need_theta = any(not p.fixed for p in kern.theta_params())
-            h.check(h.lib.gp_pdgp_set_grad_needs(self._plan, g, int(need_theta), int(not z.fixed)))
+        flatvec.set_grad_needs(h, h.lib.gp_pdgp_set_grad_needs, self._plan, self._gps())
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                             self._free.data_ptr()))
         self._packed_key = self._host_key()
@@ -291,10 +278,7 @@ class Pdgp(Parameterized):
         key = tuple(p.fixed for _, p in self._segments())
         memo = self.__dict__.get("_free_index_memo")
         if memo is None or memo[0] != key:
-            off = {id(p): o for o, p in self._segments()}
-            idx = [np.arange(off[id(p)], off[id(p)] + p.size) for p in sorted_params(self)
-                   if not p.fixed and id(p) in off]
-            idx = np.concatenate(idx) if idx else np.zeros(0, dtype=np.int64)
+            idx = flatvec.free_index(self, self._segments())
             memo = (key, idx, self._handle.torch.as_tensor(idx, device=self._handle.device))
             self._free_index_memo = memo
         return memo[1], memo[2]
@@ -317,15 +301,7 @@ class Pdgp(Parameterized):
             # no index upload, no gather: at 4-5 ms per step the two 32768-element permutations and the sort were 1.7 ms
             # of host time per step, as much as the rest of the step's launches (tools/host_profile.py).
             return self._x_dev, self._y_dev, n_all
-        idx = self.x.next_indices()
-        # the y generator is seeded like x's and drawn in lockstep (pdgp.py:76-77): it is advanced by copying the state
-        # instead of drawing the same indices a second time
-        if self.y.rng is not self.x.rng:
-            if hasattr(self.x.rng, "get_state") and hasattr(self.y.rng, "set_state"):
-                self.y.rng.set_state(self.x.rng.get_state())
-            else:
-                self.y.next_indices()        # a generator object without state access: draw the pair, as before
-        idx = np.sort(idx, kind="stable")
+        idx = draw_in_lockstep(self.x, self.y, self.x.next_indices)
         ti = self._upload_indices(idx)
         return self._x_dev.index_select(0, ti).contiguous(), self._y_dev.index_select(0, ti).contiguous(), idx.size
 
@@ -358,11 +334,8 @@ class Pdgp(Parameterized):
         model's world size (or no group at all for a one-rank model).  None: the torch.distributed exchange between the two
         stages (gloo rehearsals, emulated ranks)."""
         if "_comm_cache" not in self.__dict__:
-            import torch.distributed as dist
-            world = self._shard[1]
-            grouped = dist.is_available() and dist.is_initialized()
-            ok = (grouped and dist.get_backend() == "nccl" and dist.get_world_size() == world) or (not grouped and world == 1)
-            object.__setattr__(self, "_comm_cache", self._handle.comm() if ok else None)
+            from .dist import rccl_comm
+            object.__setattr__(self, "_comm_cache", rccl_comm(self._handle, self._shard[1]))
         return self._comm_cache
 
     def _elbo_one_call(self, comm, want_grad, sync, adam):
@@ -508,13 +481,7 @@ class Pdgp(Parameterized):
         h.check(h.lib.gp_transform_forward(h.h, self._free.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                            self._params.data_ptr()))
         f = self._elbo(True)
-        g = self._grad.cpu().numpy()
-        # chain rule through each Param's transform (fixed Params are not part of the free state)
-        scale = np.zeros_like(g)
-        for off, p in self._segments():
-            if not p.fixed:
-                scale[off:off + p.size] = p.transform.dforward(xf[off:off + p.size])
-        g = g * scale
+        g = flatvec.free_gradient(self._segments(), xf, self._grad.cpu().numpy())
         return -f, -g[idx]
 
     def get_free_state(self):
@@ -575,43 +542,58 @@ class Pdgp(Parameterized):
         self._unpack()
         return res
 
-    def _predict(self, xnew, want_source):
-        h = self._handle
-        xnew = np.asarray(xnew, dtype=np.float64).reshape(-1)
-        # (i) predict_act followed by predict_com at the same inputs (pdgp.py:17-44 does exactly that per window)
-        #     is one engine evaluation; (ii) while no Param changed, Kuu / its Cholesky factor / inverse of the
-        #     previous prediction are reused instead of rebuilt for every call.  `.fixed` flags do not matter here.
-        state = (param_version(), self._adam_t)
-        memo = getattr(self, "_pred_memo", None)
-        if memo is not None and memo[0] == state and memo[1].shape == xnew.shape and np.array_equal(memo[1], xnew):
-            return memo[2]
+    def _pred_key(self):
+        """what a prediction's factorisation depends on: every Param value and the Adam steps taken (`.fixed` flags do
+        not matter here)"""
+        return (param_version(), self._adam_t)
+
+    def _predict_chunks(self, xnew, entry, chunk):
+        """The loop of _predict and _predict_moments: xnew goes to the engine `_max_batch` frames at a time through
+        chunk(call, s, xs) — xs the device copy of xnew[s:s + _max_batch], call the library entry to use.  While no
+        Param changed, Kuu / its Cholesky factor / inverse of the previous prediction are reused instead of rebuilt:
+        `call` is `entry` after a fresh _pack(), its `_reuse` form when the engine still holds the factorisation of
+        these Params, and always from the second chunk on.  The factorisation is recorded only once a chunk has run
+        (an empty xnew factors nothing)."""
+        state = self._pred_key()
         reuse = self._plan is not None and getattr(self, "_pred_state", None) == state
         if not reuse:
             self._pack()
-            h = self._handle
-        predict = h.lib.gp_pdgp_predict_reuse if reuse else h.lib.gp_pdgp_predict
+        h = self._handle
+        call = getattr(h.lib, entry + "_reuse" if reuse else entry)
+        for s in range(0, xnew.size, self._max_batch):
+            chunk(call, s, h.to_device(xnew[s:s + self._max_batch]))
+            call = getattr(h.lib, entry + "_reuse")
+        if xnew.size:
+            self._pred_state = state
+
+    def _predict(self, xnew, want_source):
+        xnew = np.asarray(xnew, dtype=np.float64).reshape(-1)
+        # predict_act followed by predict_com at the same inputs (pdgp.py:17-44 does exactly that per window) is one
+        # engine evaluation
+        state = self._pred_key()
+        memo = getattr(self, "_pred_memo", None)
+        if memo is not None and memo[0] == state and memo[1].shape == xnew.shape and np.array_equal(memo[1], xnew):
+            return memo[2]
         P, n = self.num_sources, xnew.size
         loc = self._local
         gp_mode = self._gp_shard is not None
-        Pl, Gl = len(loc), (len(self._gp_shard) if gp_mode else 2 * len(loc))
+        rows = np.array(self._rows())      # engine row -> model row [g_0..g_{P-1}, f_0..f_{P-1}]
         fmean = np.zeros((2 * P, n))
         fvar = np.zeros((2 * P, n))
         src = np.zeros((P, n))
-        # engine row -> model row [g_0..g_{P-1}, f_0..f_{P-1}]
-        rows = np.array(self._gp_shard if gp_mode else loc + [P + i for i in loc])
-        step = self._max_batch
-        for s in range(0, n, step):
-            xs = h.to_device(xnew[s:s + step])
-            c = xs.numel()
-            fm, fv, ms = h.empty(Gl, c), h.empty(Gl, c), (None if gp_mode else h.empty(Pl, c))
+
+        def chunk(predict, s, xs):
+            h, c = self._handle, xs.numel()
+            fm, fv, ms = h.empty(len(rows), c), h.empty(len(rows), c), (None if gp_mode else h.empty(len(loc), c))
             h.check(predict(self._plan, self._params.data_ptr(), xs.data_ptr(), c, fm.data_ptr(), fv.data_ptr(),
                             None if gp_mode else ms.data_ptr()))
-            predict = h.lib.gp_pdgp_predict_reuse     # further chunks of the same call share the factorisation
             fmean[rows, s:s + c] = fm.cpu().numpy()
             fvar[rows, s:s + c] = fv.cpu().numpy()
             if not gp_mode:
                 src[loc, s:s + c] = ms.cpu().numpy()
-        self._pred_state = state
+
+        self._predict_chunks(xnew, "gp_pdgp_predict", chunk)
+        h = self._handle
         if self._shard:
             # rows of other ranks are zero here: a sum over ranks assembles the full prediction (emulated ranks — a test
             # driving several shards in one process — pass allow_local=True through _pred_allow_local and get their rows only)
@@ -634,9 +616,8 @@ class Pdgp(Parameterized):
         if not (self._shard and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             return
         P = self.num_sources
-        owned = self._gp_shard if self._gp_shard is not None else self._local + [P + i for i in self._local]
         mine = {}
-        for g in owned:
+        for g in self._rows():
             i, act = (g, True) if g < P else (g - P, False)
             kname = "kern_act" if act else "kern_com"
             mine[(kname, i)] = [q.value.copy() for q in getattr(self, kname)[i].theta_params()]
@@ -658,22 +639,21 @@ class Pdgp(Parameterized):
         """pdgp.py:172-179"""
         P = self.num_sources
         fm, fv, _ = self._predict(xnew, False)
-        return [fm[i].reshape(-1, 1).copy() for i in range(P)], [fv[i].reshape(-1, 1).copy() for i in range(P)]
+        return [col(fm, i).copy() for i in range(P)], [col(fv, i).copy() for i in range(P)]
 
     def predict_com(self, xnew):
         """pdgp.py:181-188"""
         P = self.num_sources
         fm, fv, _ = self._predict(xnew, False)
-        return [fm[P + i].reshape(-1, 1).copy() for i in range(P)], [fv[P + i].reshape(-1, 1).copy() for i in range(P)]
+        return [col(fm, P + i).copy() for i in range(P)], [col(fv, P + i).copy() for i in range(P)]
 
     def predict_act_n_com(self, xnew):
         """pdgp.py:190-208"""
         P = self.num_sources
         fm, fv, src = self._predict(xnew, True)
-        col = lambda a, i: a[i].reshape(-1, 1).copy()
-        return ([col(fm, i) for i in range(P)], [col(fv, i) for i in range(P)],
-                [col(fm, P + i) for i in range(P)], [col(fv, P + i) for i in range(P)],
-                [col(src, i) for i in range(P)])
+        return ([col(fm, i).copy() for i in range(P)], [col(fv, i).copy() for i in range(P)],
+                [col(fm, P + i).copy() for i in range(P)], [col(fv, P + i).copy() for i in range(P)],
+                [col(src, i).copy() for i in range(P)])
 
     # ------------------------------------------------------------------------------------------
     # posterior of the sources, of the mixture, and held-out density (csrc/lik.hip mpd_moments_kernel through
@@ -697,32 +677,24 @@ class Pdgp(Parameterized):
             # the rows are assembled over the ranks as _predict does; the operator entry runs on the assembled rows
             fm, fv, _ = self._predict(xnew, False)
             return self.likelihood._moments(fm.T, fv.T, ynew, sources=sources, y=y, logp=logp, noise=noise)
-        state = (param_version(), self._adam_t)
-        reuse = self._plan is not None and getattr(self, "_pred_state", None) == state
-        if not reuse:
-            self._pack()
-        h = self._handle
-        call = h.lib.gp_pdgp_predict_moments_reuse if reuse else h.lib.gp_pdgp_predict_moments
         sm, sv = (np.zeros((P, n)), np.zeros((P, n))) if sources else (None, None)
         ym, yv = (np.zeros(n), np.zeros(n)) if y else (None, None)
         lp = np.zeros(n) if logp else None
         ptr = lambda t: None if t is None else t.data_ptr()
-        step = self._max_batch
-        for s in range(0, n, step):
-            xs = h.to_device(xnew[s:s + step])
-            c = xs.numel()
-            ys = h.to_device(ynew[s:s + step]) if logp else None
+
+        def chunk(call, s, xs):
+            h, c = self._handle, xs.numel()
+            ys = h.to_device(ynew[s:s + c]) if logp else None
             dsm, dsv = (h.empty(P, c), h.empty(P, c)) if sources else (None, None)
             dym, dyv = (h.empty(c), h.empty(c)) if y else (None, None)
             dlp = h.empty(c) if logp else None
             h.check(call(self._plan, self._params.data_ptr(), xs.data_ptr(), c, ptr(ys), int(bool(noise)), ptr(dsm),
                          ptr(dsv), ptr(dym), ptr(dyv), ptr(dlp)))
-            call = h.lib.gp_pdgp_predict_moments_reuse     # further chunks share the factorisation
             for dst, src in ((sm, dsm), (sv, dsv), (ym, dym), (yv, dyv), (lp, dlp)):
                 if dst is not None:
                     dst[..., s:s + c] = src.cpu().numpy()
-        if n:
-            self._pred_state = state
+
+        self._predict_chunks(xnew, "gp_pdgp_predict_moments", chunk)
         return sm, sv, ym, yv, lp
 
     def predict_sources(self, xnew):
@@ -730,9 +702,8 @@ class Pdgp(Parameterized):
         arrays.  mean_s[i] = E[nlin(g_i)] E[f_i] with the nonlinearity integrated by the likelihood's 20-point rule
         (predict_act_n_com's mean_source plugs the activation's mean in instead)."""
         sm, sv, _, _, _ = self._predict_moments(xnew, sources=True)
-        col = lambda a, i: a[i].reshape(-1, 1).copy()
         P = self.num_sources
-        return [col(sm, i) for i in range(P)], [col(sv, i) for i in range(P)]
+        return [col(sm, i).copy() for i in range(P)], [col(sv, i).copy() for i in range(P)]
 
     def predict_y(self, xnew):
         """GPflow Model.predict_y: mean and variance of the observed mixture at xnew, (n, 1) each; the sources are

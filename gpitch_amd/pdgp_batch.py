@@ -15,13 +15,16 @@ replaces  [m.predict_act_n_com(x) for m, x in zip(models, xnews)]  with one fact
 one launch for every (latent GP, frame tile) pair, without building any single-model engine plan (check_predictable()
 takes the same models, without the minibatch limit).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, flatvec
+from .flatvec import col, free_index, latent_gps  # noqa: F401  (free_index: part of this module's interface)
 from .methods import nlin_code
-from .param import sorted_params
+from .param import draw_in_lockstep
+from .pdgp import Pdgp, jitter
 from .train import AdamOptimizer, OptimizeResult
 
 MAX_M = 128            # inducing points per latent GP (one factor of 128 x 128 float64 in a workgroup's LDS)
@@ -35,7 +38,6 @@ _SINGLE = "train this model on its own with Pdgp.optimize"
 def _check_models(models, entry, single, minibatch):
     """the scope both batched entries share (check_batchable, check_predictable): a list of distinct whitened float64
     unsharded Pdgp models whose latent GPs the batch's kernels take; `minibatch` adds the training minibatch limit"""
-    from .pdgp import Pdgp
     models = list(models)
     if not models:
         raise ValueError("%s needs at least one model" % entry)
@@ -77,19 +79,12 @@ def check_batchable(models, method=None, callback=None):
     return _check_models(models, "optimize_many", _SINGLE, minibatch=True)
 
 
-def _gps(m):
-    """latent GPs in the plan's order: [g_0..g_{P-1}, f_0..f_{P-1}] (Pdgp._gps of an unsharded model)"""
-    P = m.num_sources
-    return ([(m.kern_act[i], m.za[i], m.q_mu_act[i], m.q_sqrt_act[i]) for i in range(P)] +
-            [(m.kern_com[i], m.zc[i], m.q_mu_com[i], m.q_sqrt_com[i]) for i in range(P)])
-
-
 def model_segments(m, base=0):
     """[(offset, Param)] of one model's block of the batch's parameter vector (include/gpitch_abi.h gp_pdgpb_config):
     [noise | per latent GP: theta | z | q_mu | q_sqrt], starting at `base`; also returns the block's length"""
     segs = [(base, m.likelihood.variance)]
     off = base + 1
-    for kern, z, q_mu, q_sqrt in _gps(m):
+    for kern, z, q_mu, q_sqrt in latent_gps(m):
         for j, p in enumerate(kern.theta_params()):
             segs.append((off + j, p))
         off += 2 + 2 * int(kern.num_partials)
@@ -99,12 +94,32 @@ def model_segments(m, base=0):
     return segs, off - base
 
 
-def free_index(m, segs):
-    """entries of the batch vector that make up the model's GPflow free state, in GPflow's order (param.sorted_params:
-    Params by attribute name, `.fixed` ones absent) — the order of Pdgp._objective / optimize's `x` and `jac`"""
-    off = {id(p): o for o, p in segs}
-    idx = [np.arange(off[id(p)], off[id(p)] + p.size) for p in sorted_params(m) if not p.fixed and id(p) in off]
-    return np.concatenate(idx) if idx else np.zeros(0, dtype=np.int64)
+def _segments(models):
+    """model_segments of every model back to back: per model its segments and its (first, end) slots; the vector's length"""
+    segs, ranges, base = [], [], 0
+    for m in models:
+        sm, n = model_segments(m, base)
+        segs.append(sm)
+        ranges.append((base, base + n))
+        base += n
+    return segs, ranges, base
+
+
+def _config(models, train):
+    """gp_pdgpb_config of the models — a training plan's with the minibatch sizes B and the data counts N, a predict-only
+    plan's without — and the ctypes arrays it points to, which the caller keeps alive as long as the config"""
+    i32, nm = C.c_int32, len(models)
+    gps = [g for m in models for g in latent_gps(m)]
+    keep = dict(
+        P=(i32 * nm)(*[m.num_sources for m in models]),
+        B=(i32 * nm)(*[min(m.minibatch_size, m.num_data) for m in models]) if train else None,
+        nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in models]),
+        N=(C.c_double * nm)(*[float(m.num_data) for m in models]) if train else None,
+        M=(i32 * len(gps))(*[g[1].size for g in gps]),
+        kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
+        mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
+    k = keep
+    return _lib.PdgpBatchConfig(nm, k["P"], k["B"], k["nlin"], k["N"], k["M"], k["kt"], k["mp"], jitter), keep
 
 
 def draw_indices(m, steps):
@@ -115,18 +130,13 @@ def draw_indices(m, steps):
     N, B = m.num_data, m.minibatch_size
     if m.x.minibatch_size >= N and m.y.minibatch_size >= N:
         return np.tile(np.arange(N, dtype=np.int64), (steps, 1))
-    rng = m.x.rng
-    if float(m.x.minibatch_size) / float(N) < 0.5 and steps > 0:
-        idx = rng.randint(N, size=(steps, m.x.minibatch_size))
-    else:
-        idx = np.stack([m.x.next_indices() for _ in range(steps)]) if steps else np.zeros((0, B), dtype=np.int64)
-    if m.y.rng is not rng:
-        if hasattr(rng, "get_state") and hasattr(m.y.rng, "set_state"):
-            m.y.rng.set_state(rng.get_state())
-        else:
-            for _ in range(steps):
-                m.y.next_indices()
-    return np.sort(idx, axis=1, kind="stable")
+
+    def draw():
+        if float(m.x.minibatch_size) / float(N) < 0.5 and steps > 0:
+            return m.x.rng.randint(N, size=(steps, m.x.minibatch_size))
+        return np.stack([m.x.next_indices() for _ in range(steps)]) if steps else np.zeros((0, B), dtype=np.int64)
+
+    return draw_in_lockstep(m.x, m.y, draw, steps)
 
 
 def _describe_not_pd(code):
@@ -142,28 +152,10 @@ class PdgpBatch(object):
     def __init__(self, models, handle=None):
         self.models = check_batchable(models)
         h = self._handle = handle or _lib.default_handle()
-        self._segs, self._free_idx, self._range = [], [], []
-        base = 0
-        for m in self.models:
-            segs, n = model_segments(m, base)
-            self._segs.append(segs)
-            self._range.append((base, base + n))
-            base += n
-        self.num_params = base
-        i32 = C.c_int32
-        gps = [g for m in self.models for g in _gps(m)]
+        self._free_idx = []
+        self._segs, self._range, self.num_params = _segments(self.models)
         nm = len(self.models)
-        self._cfg_keep = dict(
-            P=(i32 * nm)(*[m.num_sources for m in self.models]),
-            B=(i32 * nm)(*[min(m.minibatch_size, m.num_data) for m in self.models]),
-            nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in self.models]),
-            N=(C.c_double * nm)(*[float(m.num_data) for m in self.models]),
-            M=(i32 * len(gps))(*[g[1].size for g in gps]),
-            kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
-            mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
-        k = self._cfg_keep
-        from .pdgp import jitter
-        cfg = _lib.PdgpBatchConfig(nm, k["P"], k["B"], k["nlin"], k["N"], k["M"], k["kt"], k["mp"], jitter)
+        cfg, self._cfg_keep = _config(self.models, train=True)
         plan = C.c_void_p()
         h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
         self._plan = plan
@@ -171,7 +163,6 @@ class PdgpBatch(object):
             raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
         self._ws = h.workspace(h.lib.gp_pdgpb_workspace_bytes(plan))
         h.check(h.lib.gp_pdgpb_set_workspace(plan, self._ws.data_ptr(), self._ws.numel()))
-        self._batch_off = np.concatenate([[0], np.cumsum([min(m.minibatch_size, m.num_data) for m in self.models])])
         self._data_off = np.concatenate([[0], np.cumsum([m.num_data for m in self.models])])
         self._x = h.to_device(np.concatenate([m.x._array.reshape(-1) for m in self.models]))
         self._y = h.to_device(np.concatenate([m.y._array.reshape(-1) for m in self.models]))
@@ -187,19 +178,9 @@ class PdgpBatch(object):
         gradients the backward pass skips follow the models' current `.fixed` flags"""
         h = self._handle
         self._free_idx = [free_index(m, segs) for m, segs in zip(self.models, self._segs)]
-        g = 0
-        for m in self.models:
-            for kern, z, _, _ in _gps(m):
-                need_theta = any(not p.fixed for p in kern.theta_params())
-                h.check(h.lib.gp_pdgpb_set_grad_needs(self._plan, g, int(need_theta), int(not z.fixed)))
-                g += 1
-        host = np.zeros(self.num_params)
-        tc = np.full(self.num_params, 2, dtype=np.uint8)
-        for segs in self._segs:
-            for off, p in segs:
-                v = p.value.reshape(-1)
-                host[off:off + v.size] = v
-                tc[off:off + v.size] = 2 if p.fixed else p.transform.device_code(h)
+        flatvec.set_grad_needs(h, h.lib.gp_pdgpb_set_grad_needs, self._plan,
+                               [g for m in self.models for g in latent_gps(m)])
+        host, tc = flatvec.pack([sp for segs in self._segs for sp in segs], self.num_params, h)
         self._params.copy_(h.torch.as_tensor(host))
         self._tcode.copy_(h.torch.as_tensor(tc))
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self.num_params,
@@ -226,12 +207,7 @@ class PdgpBatch(object):
 
     def _jac(self, k, free_host, grad_host):
         """-(d ELBO / d free state) of model k in GPflow's order (Pdgp._objective's chain rule)"""
-        scale = np.zeros(self.num_params)
-        for off, p in self._segs[k]:
-            if not p.fixed:
-                scale[off:off + p.size] = p.transform.dforward(free_host[off:off + p.size])
-        idx = self._free_idx[k]
-        return -(grad_host * scale)[idx]
+        return -flatvec.free_gradient(self._segs[k], free_host, grad_host)[self._free_idx[k]]
 
     def _evaluate(self, draws):
         h = self._handle
@@ -423,6 +399,94 @@ def predict_chunks(num_sources, counts, limit=MAX_PREDICT_FRAMES):
     return chunks
 
 
+@contextlib.contextmanager
+def _predict_plan(h, models):
+    """a predict-only gp_pdgpb plan of the models (no minibatch, no training state), destroyed behind the stream's work"""
+    cfg, keep = _config(models, train=False)
+    plan = C.c_void_p()
+    h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
+    try:
+        yield plan
+    finally:
+        h.sync()
+        h.lib.gp_pdgpb_destroy(plan)
+
+
+def _predict_batch(entry, models, xs, ys, blocks, ws_bytes, launch):
+    """The device work of predict_many and predict_sources_many (`entry` names the caller in messages), after the host
+    checks: one predict-only plan, every Param uploaded once, gp_pdgpb_predict_prepare, then one launch(...) per
+    MAX_PREDICT_FRAMES chunk of the inputs xs (and targets ys, or None) with one copy back each.
+
+    blocks names each output array by the predict_layout key of its per-model offsets: "out_base" (2 P_k rows of n_k
+    frames per model), "src_base" (P_k rows) or "x_off" (one row).  ws_bytes(lib, plan, latent) sizes the workspace,
+    `latent` being the largest chunk's count of latent-GP frames; launch(lib, plan, params, xd, off, yd, out, ws, nws)
+    runs one chunk, `out` holding a device pointer per block.  Returns per model one (rows, n_k) array per block."""
+    h = _lib.default_handle()
+    t = h.torch
+    nm = len(models)
+    P = [m.num_sources for m in models]
+    counts = [x.size for x in xs]
+    rows = lambda key, k: {"out_base": 2 * P[k], "src_base": P[k], "x_off": 1}[key]
+    segs, _, base = _segments(models)
+    # host results in the layout of one call over every frame: a call that fits one launch lands there directly, the
+    # chunks of a larger one are copied into it; every model's arrays are views of these buffers
+    whole = predict_layout(P, counts)
+    chunks = predict_chunks(P, counts, MAX_PREDICT_FRAMES)
+    res = [np.zeros(int(whole[key][-1])) for key in blocks]
+    with _predict_plan(h, models) as plan:
+        if int(h.lib.gp_pdgpb_num_params(plan)) != base:
+            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
+        # every Param written once into a page-locked vector, copied to the device on the stream
+        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
+        flatvec.pack([sp for sm in segs for sp in sm], base, out=ppin.numpy())
+        params = ppin.to(h.device, non_blocking=True)
+        latent = max(int(np.dot(2 * np.asarray(P, dtype=np.int64), c[:, 1])) for c in chunks)
+        ws = h.workspace(ws_bytes(h.lib, plan, latent))
+        h.check(h.lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
+        for chunk in chunks:
+            c = chunk[:, 1]
+            if not c.any():
+                continue
+            lay = predict_layout(P, c)
+            nx = int(lay["x_off"][-1])
+            # transfers go through page-locked staging buffers (torch's caching host allocator): pageable copies of
+            # tens of MB cost several times the kernels
+            xpin = t.empty(nx * (2 if ys is not None else 1), dtype=t.float64, pin_memory=True)
+            np.concatenate([xs[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[:nx])
+            if ys is not None:
+                np.concatenate([ys[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[nx:])
+            xd = xpin.to(h.device, non_blocking=True)
+            starts = np.concatenate([[0], np.cumsum([int(lay[key][-1]) for key in blocks])])
+            buf = h.empty(int(starts[-1]))              # the blocks one after another: one copy back to the host
+            off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
+            h.check(launch(h.lib, plan, params.data_ptr(), xd.data_ptr(), off,
+                           xd[nx:].data_ptr() if ys is not None else None,
+                           [buf[int(a):].data_ptr() for a in starts[:-1]], ws.data_ptr(), ws.numel()))
+            pin = t.empty(int(starts[-1]), dtype=t.float64, pin_memory=True)
+            pin.copy_(buf, non_blocking=True)
+            h.sync()
+            got = pin.numpy().copy()                    # the results live in ordinary memory; the staging goes back
+            del xpin, pin
+            for j, key in enumerate(blocks):
+                g = got[int(starts[j]):int(starts[j + 1])]
+                if len(chunks) == 1:
+                    res[j] = g
+                    continue
+                for k, (s, n) in enumerate(chunk):
+                    if n:
+                        d = res[j][whole[key][k]:whole[key][k + 1]].reshape(rows(key, k), counts[k])
+                        d[:, s:s + n] = g[lay[key][k]:lay[key][k + 1]].reshape(rows(key, k), n)
+        del ppin
+        bad = (C.c_int32 * nm)()
+        h.check(h.lib.gp_pdgpb_not_pd(plan, bad, 1))
+    for k in range(nm):
+        if bad[k]:
+            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "%s: model %d: Cholesky failed: %s"
+                                                % (entry, k, _describe_not_pd(bad[k])))
+    return [[res[j][whole[key][k]:whole[key][k + 1]].reshape(rows(key, k), counts[k]) for j, key in enumerate(blocks)]
+            for k in range(nm)]
+
+
 def predict_many(models, xnews):
     """Pdgp.predict_act_n_com of every model at its own inputs, all models together:
 
@@ -434,95 +498,15 @@ def predict_many(models, xnews):
     every latent GP's Kuu, then one launch per MAX_PREDICT_FRAMES chunk predicts every (latent GP, frame tile) pair and
     one more forms the source means.  A failed Kuu factorisation raises NotPositiveDefiniteError naming the model."""
     models, xs = check_predictable(models, xnews)
-    h = _lib.default_handle()
-    t = h.torch
-    nm = len(models)
-    P = [m.num_sources for m in models]
-    counts = [x.size for x in xs]
-    i32 = C.c_int32
-    gps = [g for m in models for g in _gps(m)]
-    keep = dict(P=(i32 * nm)(*P), nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in models]),
-                M=(i32 * len(gps))(*[g[1].size for g in gps]), kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
-                mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
-    from .pdgp import jitter
-    cfg = _lib.PdgpBatchConfig(nm, keep["P"], None, keep["nlin"], None, keep["M"], keep["kt"], keep["mp"], jitter)
-    segs, base = [], 0
-    for m in models:
-        sm, n = model_segments(m, base)
-        segs += sm
-        base += n
-    plan = C.c_void_p()
-    h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
-    try:
-        if int(h.lib.gp_pdgpb_num_params(plan)) != base:
-            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
-        # every Param written once into a page-locked vector, copied to the device on the stream
-        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
-        host = ppin.numpy()
-        for off, p in segs:
-            v = p.value.reshape(-1)
-            host[off:off + v.size] = v
-        params = ppin.to(h.device, non_blocking=True)
-        nbytes = h.lib.gp_pdgpb_predict_workspace_bytes(plan)
-        ws = h.workspace(nbytes)
-        h.check(h.lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
-        # host results in the layout of one call over every frame: a call that fits one launch lands there directly,
-        # the chunks of a larger one are copied into it; every model's arrays are views of these three buffers
-        whole = predict_layout(P, counts)
-        chunks = predict_chunks(P, counts, MAX_PREDICT_FRAMES)
-        fm_all, fv_all, src_all = (np.zeros(int(whole["out_base"][-1])), np.zeros(int(whole["out_base"][-1])),
-                                   np.zeros(int(whole["src_base"][-1])))
-        for chunk in chunks:
-            c = chunk[:, 1]
-            if not c.any():
-                continue
-            lay = predict_layout(P, c)
-            # transfers go through page-locked staging buffers (torch's caching host allocator): pageable copies of
-            # tens of MB cost several times the kernels
-            xpin = t.empty(int(lay["x_off"][-1]), dtype=t.float64, pin_memory=True)
-            np.concatenate([xs[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy())
-            xd = xpin.to(h.device, non_blocking=True)
-            nf, ns = int(lay["out_base"][-1]), int(lay["src_base"][-1])
-            buf = h.empty(2 * nf + ns)                  # fmean | fvar | mean_source: one copy back to the host
-            off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
-            h.check(h.lib.gp_pdgpb_predict(plan, params.data_ptr(), xd.data_ptr(), off, buf.data_ptr(),
-                                           buf[nf:].data_ptr(), buf[2 * nf:].data_ptr(), ws.data_ptr(), ws.numel()))
-            pin = t.empty(2 * nf + ns, dtype=t.float64, pin_memory=True)
-            pin.copy_(buf, non_blocking=True)
-            h.sync()
-            got = pin.numpy().copy()                    # the results live in ordinary memory; the staging goes back
-            del xpin, pin
-            fm_h, fv_h, src_h = got[:nf], got[nf:2 * nf], got[2 * nf:]
-            if len(chunks) == 1:
-                fm_all, fv_all, src_all = fm_h, fv_h, src_h
-                continue
-            for k, (s, n) in enumerate(chunk):
-                if n == 0:
-                    continue
-                for dst, part, key, rows in ((fm_all, fm_h, "out_base", 2 * P[k]), (fv_all, fv_h, "out_base", 2 * P[k]),
-                                             (src_all, src_h, "src_base", P[k])):
-                    d = dst[whole[key][k]:whole[key][k + 1]].reshape(rows, counts[k])
-                    d[:, s:s + n] = part[lay[key][k]:lay[key][k + 1]].reshape(rows, n)
-        del ppin
-        bad = (C.c_int32 * nm)()
-        h.check(h.lib.gp_pdgpb_not_pd(plan, bad, 1))
-    finally:
-        h.sync()
-        h.lib.gp_pdgpb_destroy(plan)
-    for k in range(nm):
-        if bad[k]:
-            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "predict_many: model %d: Cholesky failed: %s"
-                                                % (k, _describe_not_pd(bad[k])))
+    got = _predict_batch(
+        "predict_many", models, xs, None, ("out_base", "out_base", "src_base"),      # fmean | fvar | mean_source
+        lambda lib, plan, latent: lib.gp_pdgpb_predict_workspace_bytes(plan),
+        lambda lib, plan, params, xd, off, yd, out, ws, nws: lib.gp_pdgpb_predict(plan, params, xd, off, *out, ws, nws))
     out = []
-    for k in range(nm):
-        Pk, n, ob, sb = P[k], counts[k], whole["out_base"], whole["src_base"]
-        fm = fm_all[ob[k]:ob[k + 1]].reshape(2 * Pk, n)
-        fv = fv_all[ob[k]:ob[k + 1]].reshape(2 * Pk, n)
-        src = src_all[sb[k]:sb[k + 1]].reshape(Pk, n)
-        col = lambda a, i: a[i].reshape(-1, 1)
-        out.append(([col(fm, i) for i in range(Pk)], [col(fv, i) for i in range(Pk)],
-                    [col(fm, Pk + i) for i in range(Pk)], [col(fv, Pk + i) for i in range(Pk)],
-                    [col(src, i) for i in range(Pk)]))
+    for m, (fm, fv, src) in zip(models, got):
+        r = range(m.num_sources)
+        out.append(([col(fm, i) for i in r], [col(fv, i) for i in r],
+                    [col(fm, len(r) + i) for i in r], [col(fv, len(r) + i) for i in r], [col(src, i) for i in r]))
     return out
 
 
@@ -558,106 +542,23 @@ def predict_sources_many(models, xnews, ynews=None):
         res[k]["logp"]                      # (n_k, 1): models[k].expected_log_density(xnews[k], ynews[k]); absent without ynews
 
     Scope, chunking and staging are predict_many's (check_predictable, predict_chunks, page-locked buffers); the moments
-    of the 2P latent GPs stay in the device workspace.  xnews / ynews: one array per model or one array for every model;
-    ynews[k] must be as long as xnews[k].  Reads each model's current Params and changes nothing."""
+    of the 2P latent GPs stay in the device workspace: the largest chunk's fmean / fvar live behind the factors.
+    xnews / ynews: one array per model or one array for every model; ynews[k] must be as long as xnews[k].  Reads each
+    model's current Params and changes nothing."""
     models, xs = check_predictable(models, xnews)
     ys = _targets(ynews, xs)
-    h = _lib.default_handle()
-    t = h.torch
-    nm = len(models)
-    P = [m.num_sources for m in models]
-    counts = [x.size for x in xs]
-    i32 = C.c_int32
-    gps = [g for m in models for g in _gps(m)]
-    keep = dict(P=(i32 * nm)(*P), nlin=(i32 * nm)(*[nlin_code(m.nlinfun) for m in models]),
-                M=(i32 * len(gps))(*[g[1].size for g in gps]), kt=(i32 * len(gps))(*[g[0].type_code for g in gps]),
-                mp=(i32 * len(gps))(*[int(g[0].num_partials) for g in gps]))
-    from .pdgp import jitter
-    cfg = _lib.PdgpBatchConfig(nm, keep["P"], None, keep["nlin"], None, keep["M"], keep["kt"], keep["mp"], jitter)
-    segs, base = [], 0
-    for m in models:
-        sm, n = model_segments(m, base)
-        segs += sm
-        base += n
-    whole = predict_layout(P, counts)
-    chunks = predict_chunks(P, counts, MAX_PREDICT_FRAMES)
-    ns_all, nx_all = int(whole["src_base"][-1]), int(whole["x_off"][-1])
     names = ("mean_s", "var_s", "mean_y", "var_y") + (("logp",) if ys is not None else ())
-    res = {"mean_s": np.zeros(ns_all), "var_s": np.zeros(ns_all)}
-    for name in names[2:]:
-        res[name] = np.zeros(nx_all)
-    plan = C.c_void_p()
-    h.check(h.lib.gp_pdgpb_create(h.h, C.byref(cfg), C.byref(plan)))
-    try:
-        if int(h.lib.gp_pdgpb_num_params(plan)) != base:
-            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
-        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
-        host = ppin.numpy()
-        for off, p in segs:
-            v = p.value.reshape(-1)
-            host[off:off + v.size] = v
-        params = ppin.to(h.device, non_blocking=True)
-        # the largest chunk's fmean / fvar live behind the factors in the one workspace
-        latent = max(int(np.dot(2 * np.asarray(P, dtype=np.int64), c[:, 1])) for c in chunks)
-        ws = h.workspace(h.lib.gp_pdgpb_predict_moments_workspace_bytes(plan, latent))
-        h.check(h.lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
-        for chunk in chunks:
-            c = chunk[:, 1]
-            if not c.any():
-                continue
-            lay = predict_layout(P, c)
-            ns, nx = int(lay["src_base"][-1]), int(lay["x_off"][-1])
-            xpin = t.empty(nx * (2 if ys is not None else 1), dtype=t.float64, pin_memory=True)
-            np.concatenate([xs[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[:nx])
-            if ys is not None:
-                np.concatenate([ys[k][s:s + n] for k, (s, n) in enumerate(chunk)], out=xpin.numpy()[nx:])
-            xd = xpin.to(h.device, non_blocking=True)
-            sizes = [ns, ns] + [nx] * (len(names) - 2)
-            starts = np.concatenate([[0], np.cumsum(sizes)])
-            buf = h.empty(int(starts[-1]))              # smean | svar | ymean | yvar [| logp]: one copy back to the host
-            part = [buf[int(a):] for a in starts[:-1]]
-            off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
-            h.check(h.lib.gp_pdgpb_predict_moments(plan, params.data_ptr(), xd.data_ptr(), off,
-                                                   xd[nx:].data_ptr() if ys is not None else None,
-                                                   part[0].data_ptr(), part[1].data_ptr(), part[2].data_ptr(),
-                                                   part[3].data_ptr(), part[4].data_ptr() if ys is not None else None,
-                                                   ws.data_ptr(), ws.numel()))
-            pin = t.empty(int(starts[-1]), dtype=t.float64, pin_memory=True)
-            pin.copy_(buf, non_blocking=True)
-            h.sync()
-            got = pin.numpy().copy()
-            del xpin, pin
-            for j, name in enumerate(names):
-                g = got[int(starts[j]):int(starts[j + 1])]
-                if len(chunks) == 1:
-                    res[name] = g
-                    continue
-                for k, (s, n) in enumerate(chunk):
-                    if n == 0:
-                        continue
-                    if j < 2:
-                        d = res[name][whole["src_base"][k]:whole["src_base"][k + 1]].reshape(P[k], counts[k])
-                        d[:, s:s + n] = g[lay["src_base"][k]:lay["src_base"][k + 1]].reshape(P[k], n)
-                    else:
-                        res[name][whole["x_off"][k] + s:whole["x_off"][k] + s + n] = g[lay["x_off"][k]:lay["x_off"][k + 1]]
-        del ppin
-        bad = (C.c_int32 * nm)()
-        h.check(h.lib.gp_pdgpb_not_pd(plan, bad, 1))
-    finally:
-        h.sync()
-        h.lib.gp_pdgpb_destroy(plan)
-    for k in range(nm):
-        if bad[k]:
-            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "predict_sources_many: model %d: Cholesky failed: %s"
-                                                % (k, _describe_not_pd(bad[k])))
-    out = []
-    for k in range(nm):
-        sb, xo = whole["src_base"], whole["x_off"]
-        item = {}
+    got = _predict_batch(
+        "predict_sources_many", models, xs, ys, ("src_base", "src_base") + ("x_off",) * (len(names) - 2),
+        lambda lib, plan, latent: lib.gp_pdgpb_predict_moments_workspace_bytes(plan, latent),
+        lambda lib, plan, params, xd, off, yd, out, ws, nws: lib.gp_pdgpb_predict_moments(
+            plan, params, xd, off, yd, *(out + [None])[:5], ws, nws))
+    res = []
+    for m, arrays in zip(models, got):
+        item = dict(zip(names, arrays))
         for name in names[:2]:
-            a = res[name][sb[k]:sb[k + 1]].reshape(P[k], counts[k])
-            item[name] = [a[i].reshape(-1, 1) for i in range(P[k])]
+            item[name] = [col(item[name], i) for i in range(m.num_sources)]
         for name in names[2:]:
-            item[name] = res[name][xo[k]:xo[k + 1]].reshape(-1, 1)
-        out.append(item)
-    return out
+            item[name] = item[name].reshape(-1, 1)
+        res.append(item)
+    return res

@@ -448,6 +448,20 @@ def test_predictions_reuse_factorisation_and_memoise(gp_handle):
                                             fv.data_ptr(), None))
 
 
+def test_prediction_at_no_inputs_records_no_factorisation(gp_handle):
+    """predict_act at an empty xnew factors nothing, so the next prediction of the fresh model must not ask the engine
+    to reuse a factorisation: it returns what it returns on a model that never saw the empty call"""
+    from gpitch_amd.synth import make_problem
+    prob = make_problem(1200, 20, 2, num_partials=3, seed=2)
+    m, alone = pdgp_from_problem(prob, handle=gp_handle), pdgp_from_problem(prob, handle=gp_handle)
+    x = prob["x"][:300]
+    empty = m.predict_act(x[:0])
+    assert [a.shape for a in empty[0] + empty[1]] == [(0, 1)] * 4
+    for got, want in zip(m.predict_act(x), alone.predict_act(x)):
+        for a, b in zip(got, want):
+            np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize("N", [900, 4200])
 def test_blocked_kuu_factorisation_with_partial_last_panel(gp_handle, N):
     """M > 256 switches the Kuu batch to the panel-blocked Cholesky + inverse (engine.hip: cond_batch_factorize);
