@@ -162,7 +162,10 @@ gp_status gp_gauss_kl_matrix(gp_handle h, const double* q_mu, const double* q_sq
 /* MpdLik.variational_expectations(Fmu, Fvar, Y) (likelihoods.py:422-447 + hermgauss1d :33-45 +
  * log_lik_exp :47-68).  Fmu/Fvar are N x 2P row-major with columns [g_0..g_{P-1}, f_0..f_{P-1}]
  * (pdgp.py:157-164).  noise_var is a device scalar.  per_frame (N values) may be NULL; the sum over
- * frames is written to *sum_host when non-NULL (syncs). */
+ * frames is written to *sum_host when non-NULL (syncs).
+ * P <= 128: a workgroup of 16 frames stages 3 P doubles per frame in LDS (16 * 3 * P * 8 bytes <= 48 KiB); a larger P
+ * returns GP_ERR_UNSUPPORTED before any launch.  The same limit holds for the likelihood inside gp_pdgp_elbo and its
+ * sharded forms, there for the sources one plan holds. */
 gp_status gp_mpd_varexp(gp_handle h, const double* Fmu, const double* Fvar, const double* y, int32_t N,
                         int32_t P, int32_t nlin, const double* noise_var, double* per_frame, double* sum_host);
 
@@ -176,7 +179,9 @@ gp_status gp_mpd_varexp(gp_handle h, const double* Fmu, const double* Fvar, cons
  *   logp[n]     = MpdLik.variational_expectations(Fmu, Fvar, y)[n]   (E_q log p(y_n | g, f); not scaled, no KL)
  * Fmu/Fvar are N x 2P row-major as in gp_mpd_varexp; smean/svar are P x N row-major; ymean/yvar/logp hold N values.
  * Every output may be NULL; logp needs y and noise_var.  noise_var is a device scalar.  float64; asynchronous on the
- * handle's stream; every sum is one lane's sequential loop, so two calls give bit-identical results. */
+ * handle's stream; every sum is one lane's sequential loop, so two calls give bit-identical results.
+ * P <= 96: the staging is 4 P doubles per frame (svar joins the three of gp_mpd_varexp; 16 * 4 * P * 8 bytes <= 48 KiB),
+ * so this entry stops 32 sources before gp_mpd_varexp does; a larger P returns GP_ERR_UNSUPPORTED before any launch. */
 gp_status gp_mpd_predict_moments(gp_handle h, const double* Fmu, const double* Fvar, const double* y, int32_t N, int32_t P,
                                  int32_t nlin, const double* noise_var, double* smean, double* svar, double* ymean,
                                  double* yvar, double* logp);
@@ -577,7 +582,10 @@ gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* 
  * must have gp_pdgpb_predict_moments_workspace_bytes(plan, latent_frames) bytes, latent_frames >= sum_k 2 P_k n_k of the
  * largest call (gp_pdgpb_predict_workspace_bytes plus two arrays of that many doubles); a call that needs more returns
  * GP_ERR_WORKSPACE.  Bit-identical between calls; a model's results depend neither on the other models of the call nor on
- * how its frames are split between calls. */
+ * how its frames are split between calls.
+ * Every model of the plan needs P_k <= 96 (the LDS staging of gp_mpd_predict_moments, 4 P doubles per frame, strided by
+ * the plan's largest P_k); otherwise a call with frames returns GP_ERR_UNSUPPORTED before any launch.  gp_pdgpb_predict
+ * stages nothing per source and has no such limit. */
 size_t gp_pdgpb_predict_moments_workspace_bytes(gp_pdgpb_plan p, int64_t latent_frames);
 gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
                                    const double* ynew, double* smean, double* svar, double* ymean, double* yvar, double* logp,
