@@ -260,19 +260,30 @@ gp_status gp_kernel_diag(gp_handle h, const gp_kernel_desc* kern, int32_t n, dou
   return launch_kernel_diag(h, dev_kern(kern), n, out, accumulate);
 }
 
+// gp_kuu_cholesky's workspace: the factor when the caller wants only the inverse (*L null), a Mercer kernel's feature table
+static double* kuu_chol_carve(GpArena& ar, DevKern k, int M, double** L) {
+  if (!*L) *L = ar.take<double>((size_t)M * M);
+  return gp_kern_is_mercer(k.type) ? ar.take<double>(kernel_build_feat_ws_doubles(k.m, M, M)) : nullptr;
+}
+// the largest kernel a descriptor can hold, for the size functions that are not told the kernel
+static const DevKern GP_LARGEST_KERN = {GP_KERN_MERCER_MATERN12SM, 32, nullptr};
+
 size_t gp_chol_workspace_bytes(int32_t M) {
   if (M <= 0) return 256;
-  return gp_align_up((size_t)M * M * sizeof(double), 256) + gp_align_up(kernel_build_feat_ws_doubles(32, M, M) * sizeof(double), 256);
+  // M alone is known: the largest carve (own factor, 32 partials)
+  double* L = nullptr;
+  return gp_measure([&](GpArena& ar) { kuu_chol_carve(ar, GP_LARGEST_KERN, M, &L); });
 }
 
 gp_status gp_kuu_cholesky(gp_handle h, const gp_kernel_desc* kern, const double* z, int32_t M, double jitter, double* L,
                           double* Linv, void* workspace, size_t workspace_bytes) {
   if (!h) return GP_ERR_BAD_ARG;
   if (!kern_ok(kern) || !z || M <= 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_kuu_cholesky: bad argument");
+  if (!workspace || workspace_bytes < gp_chol_workspace_bytes(M)) return gp_fail(h, GP_ERR_WORKSPACE, "gp_kuu_cholesky: workspace too small");
   GpArena ar(workspace, workspace_bytes);
-  double* Lbuf = L ? L : ar.take<double>((size_t)M * M);
   DevKern k = dev_kern(kern);
-  double* feat = gp_kern_is_mercer(k.type) ? ar.take<double>(kernel_build_feat_ws_doubles(k.m, M, M)) : nullptr;
+  double* Lbuf = L;
+  double* feat = kuu_chol_carve(ar, k, M, &Lbuf);
   if (!ar.ok || !Lbuf) return gp_fail(h, GP_ERR_WORKSPACE, "gp_kuu_cholesky: workspace too small");
   GP_CHECK(launch_kernel_build(h, k, z, M, nullptr, M, Lbuf, M, 0, jitter, feat));
   if (Linv) GP_CHECK(launch_cholesky_inverse_single(h, Lbuf, Linv, M, M));   // one launch (on an LDS copy for M <= 64)
@@ -287,9 +298,29 @@ gp_status gp_cholesky_inplace(gp_handle h, double* A, int32_t M, int64_t ld) {
   return check_not_pd(h);
 }
 
+// The one-task batch of the one-shot conditionals: descriptor block, then the task's buffers.  `full`: in front of them
+// gp_conditional_full's diagonal (which the engine writes) and the descriptors of its three products.
+struct CondFullHead { double* fvar_diag; GemmProblem* probs; };
+static bool cond_op_carve(GpArena& ar, CondBatch& cb, int N, bool whiten, bool f32, CondFullHead* full = nullptr) {
+  if (full) { full->fvar_diag = ar.take<double>(N); full->probs = ar.take<GemmProblem>(3); }
+  cb.d_desc = ar.take<char>(cond_batch_desc_bytes(1));
+  return cond_task_carve(ar, cb.tasks[0], N, whiten, f32) && cb.d_desc;
+}
+// its largest carve at (N, M): 32 partials, unwhitened
+static size_t cond_op_measure(int N, int M, bool f32, bool full) {
+  CondBatch cb;
+  cb.tasks.resize(1);
+  cb.tasks[0].kern = GP_LARGEST_KERN; cb.tasks[0].M = M;
+  CondFullHead head;
+  return gp_measure([&](GpArena& ar) { cond_op_carve(ar, cb, N, false, f32, full ? &head : nullptr); });
+}
+
 size_t gp_conditional_workspace_bytes(int32_t N, int32_t M) {
   if (N <= 0 || M <= 0) return 256;
-  return cond_task_workspace_doubles(M, N, 32, false) * sizeof(double) + cond_batch_desc_bytes(1) + 4096;
+  // neither kernel, precision nor `whiten` is known here: the largest carve of gp_conditional_diag, _f32 and _f32w —
+  // float64 strips (long N) or float32 ones with their two M x M copies (short N)
+  const size_t b64 = cond_op_measure(N, M, false, false), b32 = cond_op_measure(N, M, true, false);
+  return (b64 > b32 ? b64 : b32) + GP_WS_TAIL_OP;
 }
 
 static gp_status conditional_diag_impl(gp_handle h, const gp_kernel_desc* kern, const double* xnew, int32_t N,
@@ -300,15 +331,15 @@ static gp_status conditional_diag_impl(gp_handle h, const gp_kernel_desc* kern, 
   if (!kern_ok(kern) || !xnew || !z || !q_mu || !fmean || !fvar || N < 0 || M <= 0)
     return gp_fail(h, GP_ERR_BAD_ARG, who);
   if (N == 0) return GP_OK;
+  if (!workspace || workspace_bytes < gp_conditional_workspace_bytes(N, M))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_conditional_diag: workspace too small");
   GpArena ar(workspace, workspace_bytes);
   CondBatch cb;
   cb.f32 = f32;
   cb.tasks.resize(1);
   CondTask& t = cb.tasks[0];
   t.kern = dev_kern(kern); t.z = z; t.M = M; t.q_mu = q_mu; t.q_sqrt = q_sqrt; t.fmean = fmean; t.fvar = fvar;
-  cb.desc_bytes = cond_batch_desc_bytes(1);
-  cb.d_desc = ar.take<char>(cb.desc_bytes);
-  if (!cond_task_carve(ar, t, N, whiten != 0, f32) || !cb.d_desc)
+  if (!cond_op_carve(ar, cb, N, whiten != 0, f32))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_conditional_diag: workspace too small");
   cb.N = N;
   gp_status st = cond_batch_upload(h, cb, whiten != 0, jitter);
@@ -347,8 +378,7 @@ gp_status gp_conditional_diag_f32w(gp_handle h, const gp_kernel_desc* kern, cons
 // Never used by the reference's own callers (its N is a window of frames: N^2 values); here for API parity.
 size_t gp_conditional_full_workspace_bytes(int32_t N, int32_t M) {
   if (N <= 0 || M <= 0) return 256;
-  return gp_conditional_workspace_bytes(N, M) + gp_align_up((size_t)N * sizeof(double), 256) +
-         gp_align_up(3 * sizeof(GemmProblem), 256) + 512;
+  return cond_op_measure(N, M, false, true) + GP_WS_TAIL_OP + GP_WS_TAIL_CHOL;   // a float64 operator
 }
 
 gp_status gp_conditional_full(gp_handle h, const gp_kernel_desc* kern, const double* xnew, int32_t N, const double* z,
@@ -361,16 +391,15 @@ gp_status gp_conditional_full(gp_handle h, const gp_kernel_desc* kern, const dou
   if (!workspace || workspace_bytes < gp_conditional_full_workspace_bytes(N, M) || (((uintptr_t)workspace) & 255))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_conditional_full: workspace too small or not 256-byte aligned");
   GpArena ar(workspace, workspace_bytes);
-  double* fvar_diag = ar.take<double>(N);
-  GemmProblem* d_prob = ar.take<GemmProblem>(3);
+  CondFullHead head;
   CondBatch cb;
   cb.tasks.resize(1);
   CondTask& t = cb.tasks[0];
-  t.kern = dev_kern(kern); t.z = z; t.M = M; t.q_mu = q_mu; t.q_sqrt = q_sqrt; t.fmean = fmean; t.fvar = fvar_diag;
-  cb.desc_bytes = cond_batch_desc_bytes(1);
-  cb.d_desc = ar.take<char>(cb.desc_bytes);
-  if (!cond_task_carve(ar, t, N, whiten != 0, false) || !cb.d_desc || !ar.ok)
+  t.kern = dev_kern(kern); t.z = z; t.M = M; t.q_mu = q_mu; t.q_sqrt = q_sqrt; t.fmean = fmean;
+  if (!cond_op_carve(ar, cb, N, whiten != 0, false, &head))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_conditional_full: workspace too small");
+  t.fvar = head.fvar_diag;
+  GemmProblem* d_prob = head.probs;
   cb.N = N;
   gp_status st = cond_batch_upload(h, cb, whiten != 0, jitter);
   if (st == GP_OK) st = cond_batch_run(h, cb, xnew, N, whiten != 0, jitter);     // mean, and A (A') left in the workspace
@@ -433,33 +462,47 @@ gp_status gp_mpd_predict_moments(gp_handle h, const double* Fmu, const double* F
                             yvar, logp);
 }
 
+// gauss_kl_impl's workspace; with_prior: K is given (as a kernel or a matrix), so its factor, inverse and the trace
+// term's partials are needed too
+struct GaussKlBufs { char* item; GemmProblem* prob; double* out; double* L; double* W; double* tr; void* chol_ws; size_t item_bytes; };
+static GaussKlBufs gauss_kl_carve(GpArena& ar, int M, bool with_prior) {
+  GaussKlBufs b = {};
+  b.item_bytes = kl_item_bytes() > klu_item_bytes() ? kl_item_bytes() : klu_item_bytes();
+  b.item = ar.take<char>(b.item_bytes);
+  b.prob = ar.take<GemmProblem>(1);
+  b.out = ar.take<double>(GP_KL_BLOCKS + 4);
+  if (with_prior) {
+    b.L = ar.take<double>((size_t)M * M);
+    b.W = ar.take<double>((size_t)M * M);
+    b.tr = ar.take<double>((size_t)gemm_rowblocks(M, 0) * M);
+    b.chol_ws = ar.take<char>(gp_chol_workspace_bytes(M));
+  }
+  return b;
+}
 size_t gp_gauss_kl_workspace_bytes(int32_t M, int32_t with_kernel) {
-  if (M <= 0 || !with_kernel) return 4096;
-  const size_t mm = gp_align_up((size_t)M * M * sizeof(double), 256);
-  return 4096 + 2 * mm + gp_align_up((size_t)gemm_rowblocks(M, 0) * M * sizeof(double), 256) + gp_chol_workspace_bytes(M);
+  if (M <= 0) return GP_WS_TAIL_OP;
+  return gp_measure([&](GpArena& ar) { gauss_kl_carve(ar, M, with_kernel != 0); }) + GP_WS_TAIL_OP;
 }
 
 // shared body: kern != NULL builds K = kern.K(z) + jitter I; Kmat != NULL takes the caller's K (M x M, ld = M)
 static gp_status gauss_kl_impl(gp_handle h, const double* q_mu, const double* q_sqrt, int32_t M,
                                const gp_kernel_desc* kern, const double* z, double jitter, const double* Kmat,
                                double* out_host, void* workspace, size_t workspace_bytes, const char* who) {
+  const bool with_prior = kern || Kmat;
+  if (!workspace || workspace_bytes < gp_gauss_kl_workspace_bytes(M, with_prior)) return gp_fail(h, GP_ERR_WORKSPACE, who);
   GpArena ar(workspace, workspace_bytes);
-  const size_t item_bytes = kl_item_bytes() > klu_item_bytes() ? kl_item_bytes() : klu_item_bytes();
-  char* d_item = ar.take<char>(item_bytes);
-  GemmProblem* d_prob = ar.take<GemmProblem>(1);
-  double* d_out = ar.take<double>(GP_KL_BLOCKS + 4);
-  double* d_res = d_out;
+  const GaussKlBufs b = gauss_kl_carve(ar, M, with_prior);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, who);
-  std::vector<char> item(item_bytes);
+  char* d_item = b.item;
+  GemmProblem* d_prob = b.prob;
+  double *d_out = b.out, *d_res = d_out;
+  std::vector<char> item(b.item_bytes);
   GemmProblem r;
-  if (kern || Kmat) {
+  if (with_prior) {
     // L = chol(K), W = L^-1, trace term from the column sums of (W Lq)^2
-    double* L = ar.take<double>((size_t)M * M);
-    double* W = ar.take<double>((size_t)M * M);
+    double *L = b.L, *W = b.W, *tr = b.tr;
     const int nrb = gemm_rowblocks(M, 0);
-    double* tr = ar.take<double>((size_t)nrb * M);
-    void* cw = ar.take<char>(gp_chol_workspace_bytes(M));
-    if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, who);
+    void* cw = b.chol_ws;
     if (kern) {
       GP_CHECK(gp_kuu_cholesky(h, kern, z, M, jitter, L, W, cw, gp_chol_workspace_bytes(M)));
     } else {

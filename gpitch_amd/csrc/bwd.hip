@@ -1417,17 +1417,12 @@ gp_status launch_hyper_contract_items(gp_handle h, int type, int m, const HyperI
 enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
                S_E, S_EH, S_WBAR, S_LU, S_RANK1, S_R, S_ALPHA, S_G, S_T2, S_LBAR, S_P, S_T3, S_S, S_WB_R1, S_WB_L,
                S_COUNT };
-static_assert(S_COUNT <= 24, "gp_pdgp_plan_s::off_bwd");
+static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
 
 
 gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
   (void)x;
   const int G = p->G;
-  const size_t slot_bytes = gp_align_up(G * sizeof(GemmProblem), 256);
-  size_t base = pdgp_kl_region_bytes(G);
-  for (int s = 0; s < S_COUNT; s++) p->off_bwd[s] = base + s * slot_bytes;
-  p->off_kl2 = base + 24 * slot_bytes;
-  p->off_fin_items = p->off_kl2 + pdgp_kl_region_bytes(G);
   p->h_fin_items.clear();       // the descriptor block is rewritten: force a fresh upload of the finish items
   const bool white = p->whiten != 0;
   size_t slab_off = 0;
@@ -1456,7 +1451,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       const bool kchain = (slot >= S_E);   // E, Wbar, R, alpha, Kuf_bar and the Cholesky-adjoint chain
       if (kchain && !kneed) { memset(&p->dummy_prob, 0, sizeof(p->dummy_prob)); return p->dummy_prob; }
       const int idx = kchain ? kslot : g;
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off_bwd[slot] + idx * sizeof(GemmProblem));
+      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + idx * sizeof(GemmProblem));
       memset(&r, 0, sizeof(r));
       r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
       return r;
@@ -1476,7 +1471,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       { GemmProblem& r = P(S_GQ_L); r.A = t.W; r.B = b.g_Lq_w; r.C = grad + q.off_qsqrt; }
       { GemmProblem& r = P(S_WB_R1); r.C = b.Wbar; r.v0 = b.g_qmu_w; r.v1 = qm; }
       { GemmProblem& r = P(S_WB_L); r.A = b.g_Lq_w; r.B = qs; r.C = b.Wbar; }
-      kl_item_fill(p->h_misc.data() + p->off_kl2 + g * kl_item_bytes(), b.qmu_w, b.Lq_w, M, p->kl_dummy + (size_t)g * GP_KL_BLOCKS, b.g_qmu_w,
+      kl_item_fill(p->h_misc.data() + p->off.kl2 + g * kl_item_bytes(), b.qmu_w, b.Lq_w, M, p->kl_dummy + (size_t)g * GP_KL_BLOCKS, b.g_qmu_w,
                    b.g_Lq_w);
     }
     { GemmProblem& r = P(S_E); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
@@ -1499,7 +1494,6 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
   // Kuf-side contractions, one launch per kernel family (same type and partial count): item array in kgps order inside
   // each family.  x2 stays null in the items: the frames of the batch come with the launch (their pointer may change
   // from step to step without a descriptor upload).
-  p->off_hy_items = p->off_fin_items + gp_align_up((size_t)G * hyper_finish_item_bytes(), 256);
   p->hy_fams.clear();
   for (size_t s = 0; s < p->kgps.size(); s++) {
     const int g = p->kgps[s];
@@ -1514,7 +1508,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
     if (q.M != fam.M || q.need_z || !q.need_theta) fam.batched = false;   // the per-GP path handles those
   }
   {
-    HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off_hy_items);
+    HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
     int pos = 0;
     for (auto& fam : p->hy_fams) {
       fam.first = pos; fam.count = (int)fam.gps.size();
@@ -1556,7 +1550,7 @@ gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
   if (kl_done) *kl_done = false;
   if (!(p->whiten && p->nK > 0 && n >= 4096 && p->overlap >= 2 && h->aux_stream && !h->aux_active)) return GP_OK;
   if (!h->ev_era && hipEventCreateWithFlags(&h->ev_era, hipEventDisableTiming) != hipSuccess) { h->ev_era = nullptr; return GP_OK; }
-  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off_bwd[slot]); };
+  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
   const int nK = p->nK, maxM = p->maxM;
   hipStream_t mainq = h->stream;
   h->stream = h->aux_stream;
@@ -1569,7 +1563,7 @@ gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
   if (st == GP_OK) st = launch_gemm_batched(h, D(S_R), nK, maxM, maxM, f);
   if (st == GP_OK) st = launch_matvec_batched(h, D(S_ALPHA), nK, maxM, 1);
   if (st == GP_OK && kl_done) {
-    st = launch_kl_white(h, p->d_misc + p->off_kl_items, p->G);
+    st = launch_kl_white(h, p->d_misc + p->off.kl_items, p->G);
     *kl_done = (st == GP_OK);
   }
   hipError_t e = hipEventRecord(h->ev_era, h->aux_stream);
@@ -1584,7 +1578,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   gp_handle h = p->h;
   const int G = p->G, maxM = p->maxM;
   const int n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
-  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off_bwd[slot]); };
+  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
   GemmFlags f;
   const bool white = p->whiten != 0;
   if (!white) {
@@ -1596,7 +1590,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     GP_CHECK(launch_matvec_batched(h, D(S_QW_MU), G, maxM, 0));
     f = GemmFlags(); f.triA = TRI_LOWER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
     GP_CHECK(launch_gemm_batched(h, D(S_QW_L), G, maxM, maxM, f));
-    GP_CHECK(launch_kl_white(h, p->d_misc + p->off_kl2, G));   // accumulates -dKL/dq' into (g', G')
+    GP_CHECK(launch_kl_white(h, p->d_misc + p->off.kl2, G));   // accumulates -dKL/dq' into (g', G')
   }
   const int nK = p->nK;   // latent GPs whose kernel hyper-parameters / inducing inputs are trainable
   // sum_n gv  (kdiag term)
@@ -1694,7 +1688,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       for (const auto& fam : p->hy_fams) {
         if (!fam.batched) continue;
         int np = 0;
-        GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off_hy_items) + p->G + fam.first,
+        GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + p->G + fam.first,
                                              fam.count, fam.M, fam.M, 0, &np));
         for (int g : fam.gps) np_uu[g] = np;
       }
@@ -1773,7 +1767,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
 #endif
       if (!fam.batched) { for (int g : fam.gps) GP_CHECK(kuf_contract(g)); return GP_OK; }
       int np = 0;
-      GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off_hy_items) + fam.first,
+      GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + fam.first,
                                            fam.count, fam.M, n, 0, &np, fam.mfma, x, fam.f32, 1));
       for (int g : fam.gps) np_uf[g] = np;
       return GP_OK;
@@ -1901,7 +1895,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
         items.push_back(it);
       }
       const size_t bytes = items.size() * sizeof(HyperFinishItem);
-      char* d_items = p->d_misc + p->off_fin_items;
+      char* d_items = p->d_misc + p->off.fin_items;
       if (p->h_fin_items.size() != bytes || memcmp(p->h_fin_items.data(), items.data(), bytes) != 0) {
         p->h_fin_items.assign((const char*)items.data(), (const char*)items.data() + bytes);
         GP_HIP_CHECK(h, hipMemcpyAsync(d_items, p->h_fin_items.data(), bytes, hipMemcpyHostToDevice, h->stream));

@@ -664,12 +664,20 @@ gp_status launch_tri_inverse_batched(gp_handle h, const double* const* d_L, doub
 #define CHL_NB 128
 // `count` matrices of the same size go through the SAME launch sequence (every launch batched over the matrices):
 // the N = 2001 factorisation is ~80 dependent launches of small grids, so W windows cost little more than one.
+struct ChlLargeLayout { GemmProblem* probs; double** ptrs; int* ints; double* T; size_t t_stride; int64_t ldT; int nblk; };
+static ChlLargeLayout chl_large_layout(GpArena& ar, int N, size_t C) {
+  ChlLargeLayout L;
+  L.nblk = (N + CHL_NB - 1) / CHL_NB;
+  L.probs = ar.take<GemmProblem>((size_t)4 * L.nblk * C);      // [step][kind][matrix]
+  L.ptrs = ar.take<double*>((size_t)2 * L.nblk * C);           // [step][L_kk | W_kk][matrix]
+  L.ints = ar.take<int>((size_t)(L.nblk + 1) * C);             // [step][matrix] block sizes, then the ld's
+  L.ldT = (N + 1) & ~1;
+  L.t_stride = gp_align_up((size_t)CHL_NB * L.ldT * sizeof(double), 256) / sizeof(double);
+  L.T = ar.take<double>(L.t_stride * C);     // per matrix: panel (N x 128, ld 128) or block row (128 x N, ld ldT)
+  return L;
+}
 size_t cholesky_large_batched_workspace_bytes(int N, int count) {
-  const int nblk = (N + CHL_NB - 1) / CHL_NB;
-  const size_t ldT = (size_t)((N + 1) & ~1);
-  const size_t c = (size_t)(count < 1 ? 1 : count);
-  return gp_align_up((size_t)4 * nblk * c * sizeof(GemmProblem), 256) + gp_align_up((size_t)2 * nblk * c * sizeof(double*), 256) +
-         gp_align_up((size_t)(nblk + 1) * c * sizeof(int), 256) + c * gp_align_up((size_t)CHL_NB * ldT * sizeof(double), 256) + 512;
+  return gp_measure([&](GpArena& ar) { chl_large_layout(ar, N, (size_t)(count < 1 ? 1 : count)); }) + GP_WS_TAIL_CHOL;
 }
 size_t cholesky_large_workspace_bytes(int N) { return cholesky_large_batched_workspace_bytes(N, 1); }
 
@@ -693,23 +701,17 @@ gp_status launch_cholesky_large_batched(gp_handle h, double* const* A, double* c
   if (N <= 0 || count <= 0) return GP_OK;
   if ((ld & 1) || ld < N) return gp_fail(h, GP_ERR_BAD_ARG, "launch_cholesky_large: ld must be even and >= N");
   GpArena ar(ws, ws_bytes);
-  const int nblk = (N + CHL_NB - 1) / CHL_NB;
   const size_t C = (size_t)count;
-  GemmProblem* d_probs = ar.take<GemmProblem>((size_t)4 * nblk * C);      // [step][kind][matrix]
-  double** d_ptrs = ar.take<double*>((size_t)2 * nblk * C);               // [step][L_kk | W_kk][matrix]
-  int* d_ints = ar.take<int>((size_t)(nblk + 1) * C);                     // [step][matrix] block sizes, then the ld's
-  const int64_t ldT = (N + 1) & ~1;
-  const size_t t_stride = gp_align_up((size_t)CHL_NB * ldT * sizeof(double), 256) / sizeof(double);
-  double* T0 = ar.take<double>(t_stride * C);     // per matrix: panel (N x 128, ld 128) or block row (128 x N, ld ldT)
+  const ChlLargeLayout lay = chl_large_layout(ar, N, C);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "launch_cholesky_large: workspace too small");
-  std::vector<GemmProblem> hp((size_t)4 * nblk * C);
-  std::vector<double*> hptr((size_t)2 * nblk * C);
-  std::vector<int> hint((size_t)(nblk + 1) * C);
+  std::vector<GemmProblem> hp((size_t)4 * lay.nblk * C);
+  std::vector<double*> hptr((size_t)2 * lay.nblk * C);
+  std::vector<int> hint((size_t)(lay.nblk + 1) * C);
   memset(hp.data(), 0, hp.size() * sizeof(GemmProblem));
-  for (int k = 0; k < nblk; k++) {
+  for (int k = 0; k < lay.nblk; k++) {
     const int c0 = k * CHL_NB, nb = (N - c0 < CHL_NB) ? N - c0 : CHL_NB, r0 = c0 + nb, mrem = N - r0;
     for (size_t w = 0; w < C; w++) {
-      double* Aw = A[w]; double* Ww = W[w]; double* T = T0 + w * t_stride;
+      double* Aw = A[w]; double* Ww = W[w]; double* T = lay.T + w * lay.t_stride;
       double* Wkk = Ww + (int64_t)c0 * ld + c0;
       hptr[((size_t)2 * k + 0) * C + w] = Aw + (int64_t)c0 * ld + c0;
       hptr[((size_t)2 * k + 1) * C + w] = Wkk;
@@ -719,48 +721,48 @@ gp_status launch_cholesky_large_batched(gp_handle h, double* const* A, double* c
       { GemmProblem& r = hp[((size_t)4 * k + 1) * C + w];   // A[r0:, r0:] -= P P^T
         r.A = T; r.lda = CHL_NB; r.B = T; r.ldb = CHL_NB; r.C = Aw + (int64_t)r0 * ld + r0; r.ldc = ld; r.M = mrem; r.N = mrem; r.K = nb; }
       { GemmProblem& r = hp[((size_t)4 * k + 2) * C + w];   // T = L[c0:c0+nb, :c0] W[:c0, :c0]
-        r.A = Aw + (int64_t)c0 * ld; r.lda = ld; r.B = Ww; r.ldb = ld; r.C = T; r.ldc = ldT; r.M = nb; r.N = c0; r.K = c0; }
+        r.A = Aw + (int64_t)c0 * ld; r.lda = ld; r.B = Ww; r.ldb = ld; r.C = T; r.ldc = lay.ldT; r.M = nb; r.N = c0; r.K = c0; }
       { GemmProblem& r = hp[((size_t)4 * k + 3) * C + w];   // W[c0:c0+nb, :c0] = -W_kk T
-        r.A = Wkk; r.lda = ld; r.B = T; r.ldb = ldT; r.C = Ww + (int64_t)c0 * ld; r.ldc = ld; r.M = nb; r.N = c0; r.K = nb; }
+        r.A = Wkk; r.lda = ld; r.B = T; r.ldb = lay.ldT; r.C = Ww + (int64_t)c0 * ld; r.ldc = ld; r.M = nb; r.N = c0; r.K = nb; }
     }
   }
-  for (size_t w = 0; w < C; w++) hint[(size_t)nblk * C + w] = (int)ld;
-  GP_HIP_CHECK(h, hipMemcpyAsync(d_probs, hp.data(), hp.size() * sizeof(GemmProblem), hipMemcpyHostToDevice, h->stream));
-  GP_HIP_CHECK(h, hipMemcpyAsync(d_ptrs, hptr.data(), hptr.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-  GP_HIP_CHECK(h, hipMemcpyAsync(d_ints, hint.data(), hint.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  for (size_t w = 0; w < C; w++) hint[(size_t)lay.nblk * C + w] = (int)ld;
+  GP_HIP_CHECK(h, hipMemcpyAsync(lay.probs, hp.data(), hp.size() * sizeof(GemmProblem), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(lay.ptrs, hptr.data(), hptr.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(lay.ints, hint.data(), hint.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));   // the staging vectors are stack objects
   // the W matrices start as zeros (their upper blocks are never written): step 0's W_kk pointers are their bases
-  hipLaunchKernelGGL(chl_zero_kernel, dim3(512, count), dim3(256), 0, h->stream, (double* const*)(d_ptrs + C), (int64_t)N * ld);
+  hipLaunchKernelGGL(chl_zero_kernel, dim3(512, count), dim3(256), 0, h->stream, (double* const*)(lay.ptrs + C), (int64_t)N * ld);
   GP_HIP_CHECK(h, hipGetLastError());
-  const int* d_ld = d_ints + (size_t)nblk * C;
-  for (int k = 0; k < nblk; k++) {
+  const int* d_ld = lay.ints + (size_t)lay.nblk * C;
+  for (int k = 0; k < lay.nblk; k++) {
     const int c0 = k * CHL_NB, nb = (N - c0 < CHL_NB) ? N - c0 : CHL_NB, r0 = c0 + nb, mrem = N - r0;
-    double* const* dL = d_ptrs + ((size_t)2 * k + 0) * C;
-    double* const* dW = d_ptrs + ((size_t)2 * k + 1) * C;
-    const int* dM = d_ints + (size_t)k * C;
+    double* const* dL = lay.ptrs + ((size_t)2 * k + 0) * C;
+    double* const* dW = lay.ptrs + ((size_t)2 * k + 1) * C;
+    const int* dM = lay.ints + (size_t)k * C;
     GP_CHECK(launch_cholesky_batched(h, dL, dM, d_ld, count, nb, c0));
     GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)dL, dW, dM, d_ld, count));
     if (mrem > 0) {
       GemmFlags f;
       f.transB = 1; f.triB = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, d_probs + ((size_t)4 * k + 0) * C, count, mrem, nb, f));
+      GP_CHECK(launch_gemm_batched(h, lay.probs + ((size_t)4 * k + 0) * C, count, mrem, nb, f));
       int blocks = (int)(((int64_t)mrem * nb + 255) / 256);
       if (blocks > 256) blocks = 256;
-      hipLaunchKernelGGL(chl_panel_copy_kernel, dim3(blocks, count), dim3(256), 0, h->stream, d_probs + ((size_t)4 * k + 0) * C);
+      hipLaunchKernelGGL(chl_panel_copy_kernel, dim3(blocks, count), dim3(256), 0, h->stream, lay.probs + ((size_t)4 * k + 0) * C);
       GP_HIP_CHECK(h, hipGetLastError());
       f = GemmFlags();
       f.transB = 1; f.triC = TRI_LOWER; f.alpha = -1.0; f.beta = 1.0;
-      GP_CHECK(launch_gemm_batched(h, d_probs + ((size_t)4 * k + 1) * C, count, mrem, mrem, f));
+      GP_CHECK(launch_gemm_batched(h, lay.probs + ((size_t)4 * k + 1) * C, count, mrem, mrem, f));
     }
   }
-  for (int k = 1; k < nblk; k++) {
+  for (int k = 1; k < lay.nblk; k++) {
     const int c0 = k * CHL_NB, nb = (N - c0 < CHL_NB) ? N - c0 : CHL_NB;
     GemmFlags f;
     f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, d_probs + ((size_t)4 * k + 2) * C, count, nb, c0, f));
+    GP_CHECK(launch_gemm_batched(h, lay.probs + ((size_t)4 * k + 2) * C, count, nb, c0, f));
     f = GemmFlags();
     f.triA = TRI_LOWER; f.alpha = -1.0;
-    GP_CHECK(launch_gemm_batched(h, d_probs + ((size_t)4 * k + 3) * C, count, nb, c0, f));
+    GP_CHECK(launch_gemm_batched(h, lay.probs + ((size_t)4 * k + 3) * C, count, nb, c0, f));
   }
   return GP_OK;
 }
@@ -777,19 +779,11 @@ gp_status launch_cholesky_large(gp_handle h, double* A, double* W, int N, int64_
 // 512 x 512 matrix takes 1.37 ms (the inverse is the slower half); this takes 0.9.  The descriptors are built and
 // uploaded ONCE (chol_inverse_blocked_prepare: the caller's buffers do not move), so a run is launches only and can sit
 // inside a recorded launch sequence.
-size_t chol_inverse_blocked_workspace_bytes(int M) {
-  const int nblk = (M + CHL_NB - 1) / CHL_NB;
-  const size_t ldT = (size_t)((M + 1) & ~1);
-  return gp_align_up((size_t)2 * nblk * sizeof(GemmProblem), 256) + gp_align_up((size_t)(2 * nblk + 2) * sizeof(double*), 256) +
-         gp_align_up((size_t)(2 * nblk + 2) * sizeof(int), 256) + gp_align_up((size_t)CHL_NB * ldT * sizeof(double), 256) + 512;
-}
-
 struct CholBlockedLayout {
   GemmProblem* probs; double** ptrs; int* ints; double* T; int nblk;
   // ptrs: [0] A, [1] W, [2 .. 2 + nblk) L_kk, [2 + nblk .. 2 + 2 nblk) W_kk;  ints: [0] M, [1] ld, [2 .. 2 + nblk) nb_k, then nblk x ld
 };
-static bool chol_blocked_layout(int M, void* ws, size_t ws_bytes, CholBlockedLayout* L) {
-  GpArena ar(ws, ws_bytes);
+static bool chol_blocked_layout(int M, GpArena& ar, CholBlockedLayout* L) {
   L->nblk = (M + CHL_NB - 1) / CHL_NB;
   const int64_t ldT = (M + 1) & ~1;
   L->probs = ar.take<GemmProblem>((size_t)2 * L->nblk);
@@ -798,11 +792,16 @@ static bool chol_blocked_layout(int M, void* ws, size_t ws_bytes, CholBlockedLay
   L->T = ar.take<double>((size_t)CHL_NB * ldT);
   return ar.ok;
 }
+size_t chol_inverse_blocked_workspace_bytes(int M) {
+  CholBlockedLayout L;
+  return gp_measure([&](GpArena& ar) { chol_blocked_layout(M, ar, &L); }) + GP_WS_TAIL_CHOL;
+}
 
 gp_status chol_inverse_blocked_prepare(gp_handle h, double* A, double* W, int M, int64_t ld, void* ws, size_t ws_bytes) {
   if (M <= CHL_NB || (ld & 1) || ld < M) return gp_fail(h, GP_ERR_BAD_ARG, "chol_inverse_blocked: M > 128 and an even ld >= M");
   CholBlockedLayout L;
-  if (!chol_blocked_layout(M, ws, ws_bytes, &L)) return gp_fail(h, GP_ERR_WORKSPACE, "chol_inverse_blocked: workspace too small");
+  GpArena ar(ws, ws_bytes);
+  if (!chol_blocked_layout(M, ar, &L)) return gp_fail(h, GP_ERR_WORKSPACE, "chol_inverse_blocked: workspace too small");
   const int nblk = L.nblk;
   const int64_t ldT = (M + 1) & ~1;
   std::vector<GemmProblem> hp((size_t)2 * nblk);
@@ -829,7 +828,8 @@ gp_status chol_inverse_blocked_prepare(gp_handle h, double* A, double* W, int M,
 
 gp_status chol_inverse_blocked_run(gp_handle h, int M, int64_t ld, void* ws, size_t ws_bytes) {
   CholBlockedLayout L;
-  if (!chol_blocked_layout(M, ws, ws_bytes, &L)) return gp_fail(h, GP_ERR_WORKSPACE, "chol_inverse_blocked: workspace too small");
+  GpArena ar(ws, ws_bytes);
+  if (!chol_blocked_layout(M, ar, &L)) return gp_fail(h, GP_ERR_WORKSPACE, "chol_inverse_blocked: workspace too small");
   const int nblk = L.nblk;
   GP_CHECK(launch_cholesky_batched(h, (double* const*)L.ptrs, L.ints, L.ints + 1, 1, M, 0));     // the whole factor, one workgroup
   hipLaunchKernelGGL(chl_zero_kernel, dim3(256, 1), dim3(256), 0, h->stream, (double* const*)(L.ptrs + 1), (int64_t)M * ld);

@@ -166,6 +166,21 @@ struct GpArena {
     return r;
   }
 };
+// Every caller-allocated workspace is laid out by ONE carve function (a list of take() calls); its *_workspace_bytes is
+// that same function run on an arena without memory (gp_measure), plus a trailing margin.
+template <typename Carve>
+static inline size_t gp_measure(Carve carve) { GpArena ar(nullptr, SIZE_MAX); carve(ar); return ar.off; }
+// (a descriptor block's layout function walks its regions with this: region(bytes) -> offset, `off` = total so far)
+struct GpRegions {
+  size_t off = 0;
+  size_t operator()(size_t bytes) { const size_t o = off; off += gp_align_up(bytes, 256); return o; }
+};
+// Trailing margins behind the measured carve: nobody has shown that no kernel reads a few bytes past its last buffer
+// (padded vector loads at a strip's end), so each family keeps the slack it always had.
+static const size_t GP_WS_TAIL_BATCH = 256;    // pdgp_batch.hip plans
+static const size_t GP_WS_TAIL_CHOL = 512;     // chol.hip's blocked factorisations
+static const size_t GP_WS_TAIL_OP = 4096;      // one-shot operators, the SGPR plan
+static const size_t GP_WS_TAIL_PLAN = 8192;    // Pdgp plan, window-batched SGPR plan and its source prediction
 
 // ---------------------------------------------------------------------------------------------
 // device-side kernel descriptor (passed by value in kernel args)

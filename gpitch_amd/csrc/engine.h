@@ -63,6 +63,21 @@ size_t hyper_finish_item_bytes();
 // partial records the Kuf-side contraction of an M x N strip may write (the largest over its kernel variants)
 size_t hyper_kuf_records(int N, int M);
 
+#define CB_NB 128          // panel width of the blocked Kuu factorisation
+#define CB_MAX_PANELS 8    // M <= 1024
+
+// The descriptor block of a batch of `count` conditionals whose blocked Kuu factorisation has `nblk` panels (0: not
+// blocked): every region's offset and the total, from one walk (cond_batch_desc_layout).
+struct CondDescLayout {
+  size_t chol_ptrs, w_ptrs, Ms, lds, f1, f1u, f2, finish;
+  size_t cov_uu, cov_uf, feat_zuu, feat_zuf, feat_x;     // grouped covariance builds: Kuu + Kuf items, z / x feature items
+  // blocked factorisation: per panel 2 pointer arrays, 1 size array, 4 GEMM problem arrays ...
+  size_t blk_mats[CB_MAX_PANELS], blk_w[CB_MAX_PANELS], blk_M[CB_MAX_PANELS], blk_gemm[CB_MAX_PANELS][4];
+  size_t diag_mats, diag_w, diag_M, diag_ld;             // ... and all panels' diagonal blocks as one batch
+  size_t bytes;
+};
+CondDescLayout cond_batch_desc_layout(int count, int nblk);
+
 // One latent GP inside a batch of conditionals.
 struct CondTask {
   DevKern kern;
@@ -88,11 +103,10 @@ struct CondBatch {
   std::vector<CondTask> tasks;
   int N = 0;
   int maxM = 0;
-  // device descriptor storage (inside the caller's workspace)
-  char* d_desc = nullptr; size_t desc_bytes = 0;
+  // device descriptor storage (inside the caller's workspace: cond_batch_desc_bytes(tasks.size()) bytes)
+  char* d_desc = nullptr;
   std::vector<char> h_desc;
-  // offsets of the descriptor arrays inside d_desc
-  size_t off_chol_ptrs = 0, off_w_ptrs = 0, off_Ms = 0, off_lds = 0, off_f1 = 0, off_f1u = 0, off_f2 = 0, off_finish = 0;
+  CondDescLayout off;     // offsets of the descriptor arrays inside d_desc (cond_batch_upload)
   bool uploaded = false;
   bool overlap = true;    // run the Kuu factorisation on the handle's helper stream next to the Kuf builds
   bool f32 = false;       // every task's M x N strips (Kuf, A) are float32 and the strip products run on the float32 matrix path
@@ -104,18 +118,15 @@ struct CondBatch {
   // grouped covariance builds (one launch per kernel family)
   struct Group { int type = 0, m = 0, first = 0, maxM = 0; bool f32 = false; std::vector<int> members; };
   std::vector<Group> groups;
-  size_t off_cov_uu = 0, off_cov_uf = 0, off_feat_zuu = 0, off_feat_zuf = 0, off_feat_x = 0;
   // blocked Kuu factorisation (engine.hip: cond_batch_factorize)
   bool blocked = false; int nblk = 0;
   bool diag_ready = false;   // set by a factorisation that recorded gp_handle_s::ev_diag after the diagonal blocks of W
-  size_t off_blk_mats[8] = {0}, off_blk_w[8] = {0}, off_blk_M[8] = {0}, off_blk_gemm[8][4] = {{0}};
-  size_t off_diag_mats = 0, off_diag_w = 0, off_diag_M = 0, off_diag_ld = 0;   // all panels' diagonal blocks, one batch
 };
 
 int cond_batch_uniform(const CondBatch& cb, int N);
-size_t cond_task_workspace_doubles(int M, int N, int num_partials, bool whiten, bool f32 = false);
-size_t cond_batch_desc_bytes(int count);
-// carve the per-task buffers out of the arena
+size_t cond_batch_desc_bytes(int count);     // the largest layout of `count` tasks (CB_MAX_PANELS panels)
+// carve the per-task buffers out of the arena (needs t.M and t.kern's type and partial count); on a measuring arena this
+// is the task's size
 bool cond_task_carve(GpArena& ar, CondTask& t, int N, bool whiten, bool f32 = false);
 gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitter);
 // run: Kuu -> chol -> W ; Kuf ; A = W Kuf ; (A2 = W^T A) ; Lq^T A ; reductions -> fmean, fvar

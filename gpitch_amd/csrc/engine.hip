@@ -5,27 +5,9 @@
 #include "engine.h"
 #include <string.h>
 
-#define CB_NB 128          // panel width of the blocked Kuu factorisation
-#define CB_MAX_PANELS 8    // M <= 1024
-
-size_t cond_task_workspace_doubles(int M, int N, int m, bool whiten, bool f32) {
-  const size_t strip = gp_strip_doubles((size_t)M, N, f32);
-  const int rb = (M + 63) / 64;      // partial-sum rows: one per 64-row tile (gemm_wave.hip; the 128-row forms use half of them)
-  size_t d = 0;
-  auto add = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
-  add((size_t)M * M); add((size_t)M * M);          // L, W
-  add((size_t)CB_NB * M);                          // block-row scratch of the blocked inverse
-  add(strip); add(strip);                          // Kuf, A
-  if (!whiten) add(strip);                         // A2
-  if (m > 0) { add(kernel_build_feat_ws_doubles(m, M, N)); add(kernel_build_feat_ws_doubles(m, M, M)); }
-  add((size_t)rb * N); add((size_t)rb * N); add((size_t)rb * N);  // s1, s2, dot
-  if (f32) { add(((size_t)M * M + 1) / 2); add(((size_t)M * M + 1) / 2); }   // float32 copies of W, tril(Lq)^T
-  return d;
-}
-
 bool cond_task_carve(GpArena& ar, CondTask& t, int N, bool whiten, bool f32) {
   const size_t strip = gp_strip_doubles((size_t)t.M, N, f32);
-  const int rb = (t.M + 63) / 64;
+  const int rb = (t.M + 63) / 64;      // partial-sum rows: one per 64-row tile (gemm_wave.hip; the 128-row forms use half of them)
   t.L = ar.take<double>((size_t)t.M * t.M);
   t.W = ar.take<double>((size_t)t.M * t.M);
   t.Tblk = ar.take<double>((size_t)CB_NB * t.M);
@@ -44,23 +26,39 @@ bool cond_task_carve(GpArena& ar, CondTask& t, int N, bool whiten, bool f32) {
   return ar.ok;
 }
 
-size_t cond_batch_desc_bytes(int count) {
-  size_t b = 0;
-  b += gp_align_up(count * sizeof(double*), 256) * 2;  // chol ptrs, W ptrs
-  b += gp_align_up(count * sizeof(int), 256) * 2;      // Ms, lds
-  b += gp_align_up(count * sizeof(GemmProblem), 256) * 3;
-  b += gp_align_up(count * cond_finish_item_bytes(), 256);
-  // grouped covariance builds: Kuu + Kuf items, and z (x2) / x feature items
-  b += 2 * gp_align_up(count * sizeof(CovItem), 256) + 3 * gp_align_up(count * sizeof(FeatItem), 256);
-  // blocked Cholesky + inverse (up to CB_MAX_PANELS 128-column panels): per panel 2 pointer arrays, 1 size array,
-  // 4 GEMM problem arrays
-  b += CB_MAX_PANELS * (2 * gp_align_up(count * sizeof(double*), 256) + gp_align_up(count * sizeof(int), 256) +
-                        4 * gp_align_up(count * sizeof(GemmProblem), 256));
-  // ... and the diagonal blocks of all panels as one batch (2 pointer arrays, sizes, leading dimensions)
-  b += 2 * gp_align_up((size_t)CB_MAX_PANELS * count * sizeof(double*), 256) +
-       2 * gp_align_up((size_t)CB_MAX_PANELS * count * sizeof(int), 256);
-  return b;
+CondDescLayout cond_batch_desc_layout(int count, int nblk) {
+  CondDescLayout o = {};
+  GpRegions region;
+  const size_t G = count;
+  o.chol_ptrs = region(G * sizeof(double*));
+  o.w_ptrs = region(G * sizeof(double*));
+  o.Ms = region(G * sizeof(int));
+  o.lds = region(G * sizeof(int));
+  o.f1 = region(G * sizeof(GemmProblem));
+  o.f1u = region(G * sizeof(GemmProblem));
+  o.f2 = region(G * sizeof(GemmProblem));
+  o.finish = region(G * cond_finish_item_bytes());
+  o.cov_uu = region(G * sizeof(CovItem));
+  o.cov_uf = region(G * sizeof(CovItem));
+  o.feat_zuu = region(G * sizeof(FeatItem));
+  o.feat_zuf = region(G * sizeof(FeatItem));
+  o.feat_x = region(G * sizeof(FeatItem));
+  for (int k = 0; k < nblk; k++) {
+    o.blk_mats[k] = region(G * sizeof(double*));
+    o.blk_w[k] = region(G * sizeof(double*));
+    o.blk_M[k] = region(G * sizeof(int));
+    for (int q = 0; q < 4; q++) o.blk_gemm[k][q] = region(G * sizeof(GemmProblem));
+  }
+  if (nblk > 0) {
+    o.diag_mats = region((size_t)nblk * G * sizeof(double*));
+    o.diag_w = region((size_t)nblk * G * sizeof(double*));
+    o.diag_M = region((size_t)nblk * G * sizeof(int));
+    o.diag_ld = region((size_t)nblk * G * sizeof(int));
+  }
+  o.bytes = region.off;
+  return o;
 }
+size_t cond_batch_desc_bytes(int count) { return cond_batch_desc_layout(count, CB_MAX_PANELS).bytes; }
 
 gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitter) {
   const int G = (int)cb.tasks.size();
@@ -72,29 +70,28 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
     if (cb.f32) t.f32 = true;
     if (!t.f32) { if (cb.n64 != g) return gp_fail(h, GP_ERR_UNSUPPORTED, "per-GP precision: float64 latent GPs must precede float32 ones"); cb.n64 = g + 1; }
   }
-  size_t need = cond_batch_desc_bytes(G);
-  if (cb.desc_bytes < need || !cb.d_desc) return gp_fail(h, GP_ERR_WORKSPACE, "descriptor workspace too small");
-  cb.h_desc.assign(need, 0);
-  size_t off = 0;
-  auto region = [&](size_t bytes) { size_t o = off; off += gp_align_up(bytes, 256); return o; };
-  cb.off_chol_ptrs = region(G * sizeof(double*));
-  cb.off_w_ptrs = region(G * sizeof(double*));
-  cb.off_Ms = region(G * sizeof(int));
-  cb.off_lds = region(G * sizeof(int));
-  cb.off_f1 = region(G * sizeof(GemmProblem));
-  cb.off_f1u = region(G * sizeof(GemmProblem));
-  cb.off_f2 = region(G * sizeof(GemmProblem));
-  cb.off_finish = region(G * cond_finish_item_bytes());
-  double** cp = (double**)(cb.h_desc.data() + cb.off_chol_ptrs);
-  double** wp = (double**)(cb.h_desc.data() + cb.off_w_ptrs);
-  int* Ms = (int*)(cb.h_desc.data() + cb.off_Ms);
-  int* lds = (int*)(cb.h_desc.data() + cb.off_lds);
-  GemmProblem* f1 = (GemmProblem*)(cb.h_desc.data() + cb.off_f1);
-  GemmProblem* f1u = (GemmProblem*)(cb.h_desc.data() + cb.off_f1u);
-  GemmProblem* f2 = (GemmProblem*)(cb.h_desc.data() + cb.off_f2);
-  char* fin = cb.h_desc.data() + cb.off_finish;
+  if (!cb.d_desc) return gp_fail(h, GP_ERR_WORKSPACE, "descriptor workspace not set");
   cb.maxM = 0;
   for (int g = 0; g < G; g++) if (cb.tasks[g].M > cb.maxM) cb.maxM = cb.tasks[g].M;
+  // Blocked factorisation of the Kuu batch (M > 256): 128-column panels; the diagonal blocks go to the one-workgroup
+  // kernels (batched over the GPs), the O(M^3) panel solve / trailing update / block-row inverse to the batched GEMMs.
+  // One workgroup per GP for the whole 512 x 512 factor + inverse took 1.8 ms of a 31 ms step.
+  cb.nblk = (cb.maxM + CB_NB - 1) / CB_NB;
+  // (two panels already pay off for long batches: the factor comes from one resident launch, the first row-block of
+  // A = W Kuf starts from W's diagonal blocks — cond_batch_run — and the fused factor + inverse kernel was the head's
+  // critical path: 0.46 ms at M = 256)
+  const bool blk256 = gp_switches().blocked_256 != 0;
+  cb.blocked = (cb.maxM > 256 || (blk256 && cb.maxM > 128 && cb.N >= 4096)) && cb.nblk <= CB_MAX_PANELS;
+  cb.off = cond_batch_desc_layout(G, cb.blocked ? cb.nblk : 0);
+  cb.h_desc.assign(cb.off.bytes, 0);
+  double** cp = (double**)(cb.h_desc.data() + cb.off.chol_ptrs);
+  double** wp = (double**)(cb.h_desc.data() + cb.off.w_ptrs);
+  int* Ms = (int*)(cb.h_desc.data() + cb.off.Ms);
+  int* lds = (int*)(cb.h_desc.data() + cb.off.lds);
+  GemmProblem* f1 = (GemmProblem*)(cb.h_desc.data() + cb.off.f1);
+  GemmProblem* f1u = (GemmProblem*)(cb.h_desc.data() + cb.off.f1u);
+  GemmProblem* f2 = (GemmProblem*)(cb.h_desc.data() + cb.off.f2);
+  char* fin = cb.h_desc.data() + cb.off.finish;
   // which strip products of the float64 tasks take the wave form (one partial row per 64-row tile instead of per 128)
   const int uni = cond_batch_uniform(cb, N);
   cb.wave_a = gemm_wave_takes(1, cb.maxM, N, uni);
@@ -141,16 +138,11 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
       if (gi < 0) { CondBatch::Group ng; ng.type = t.kern.type; ng.m = key_m; ng.f32 = t.f32; cb.groups.push_back(ng); gi = (int)cb.groups.size() - 1; }
       cb.groups[gi].members.push_back(g);
     }
-    cb.off_cov_uu = region(G * sizeof(CovItem));
-    cb.off_cov_uf = region(G * sizeof(CovItem));
-    cb.off_feat_zuu = region(G * sizeof(FeatItem));
-    cb.off_feat_zuf = region(G * sizeof(FeatItem));
-    cb.off_feat_x = region(G * sizeof(FeatItem));
-    CovItem* uu = (CovItem*)(cb.h_desc.data() + cb.off_cov_uu);
-    CovItem* uf = (CovItem*)(cb.h_desc.data() + cb.off_cov_uf);
-    FeatItem* fzuu = (FeatItem*)(cb.h_desc.data() + cb.off_feat_zuu);
-    FeatItem* fzuf = (FeatItem*)(cb.h_desc.data() + cb.off_feat_zuf);
-    FeatItem* fx = (FeatItem*)(cb.h_desc.data() + cb.off_feat_x);
+    CovItem* uu = (CovItem*)(cb.h_desc.data() + cb.off.cov_uu);
+    CovItem* uf = (CovItem*)(cb.h_desc.data() + cb.off.cov_uf);
+    FeatItem* fzuu = (FeatItem*)(cb.h_desc.data() + cb.off.feat_zuu);
+    FeatItem* fzuf = (FeatItem*)(cb.h_desc.data() + cb.off.feat_zuf);
+    FeatItem* fx = (FeatItem*)(cb.h_desc.data() + cb.off.feat_x);
     int pos = 0;
     for (auto& gr : cb.groups) {
       gr.first = pos; gr.maxM = 0;
@@ -167,26 +159,13 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
       }
     }
   }
-  // Blocked factorisation of the Kuu batch (M > 256): 128-column panels; the diagonal blocks go to the one-workgroup
-  // kernels (batched over the GPs), the O(M^3) panel solve / trailing update / block-row inverse to the batched GEMMs.
-  // One workgroup per GP for the whole 512 x 512 factor + inverse took 1.8 ms of a 31 ms step.
-  cb.nblk = (cb.maxM + CB_NB - 1) / CB_NB;
-  // (two panels already pay off for long batches: the factor comes from one resident launch, the first row-block of
-  // A = W Kuf starts from W's diagonal blocks — cond_batch_run — and the fused factor + inverse kernel was the head's
-  // critical path: 0.46 ms at M = 256)
-  const bool blk256 = gp_switches().blocked_256 != 0;
-  cb.blocked = (cb.maxM > 256 || (blk256 && cb.maxM > 128 && cb.N >= 4096)) && cb.nblk <= CB_MAX_PANELS;
   if (cb.blocked) {
     for (int k = 0; k < cb.nblk; k++) {
-      cb.off_blk_mats[k] = region(G * sizeof(double*));
-      cb.off_blk_w[k] = region(G * sizeof(double*));
-      cb.off_blk_M[k] = region(G * sizeof(int));
-      for (int q = 0; q < 4; q++) cb.off_blk_gemm[k][q] = region(G * sizeof(GemmProblem));
-      double** bm = (double**)(cb.h_desc.data() + cb.off_blk_mats[k]);
-      double** bw = (double**)(cb.h_desc.data() + cb.off_blk_w[k]);
-      int* bM = (int*)(cb.h_desc.data() + cb.off_blk_M[k]);
+      double** bm = (double**)(cb.h_desc.data() + cb.off.blk_mats[k]);
+      double** bw = (double**)(cb.h_desc.data() + cb.off.blk_w[k]);
+      int* bM = (int*)(cb.h_desc.data() + cb.off.blk_M[k]);
       GemmProblem* gp[4];
-      for (int q = 0; q < 4; q++) gp[q] = (GemmProblem*)(cb.h_desc.data() + cb.off_blk_gemm[k][q]);
+      for (int q = 0; q < 4; q++) gp[q] = (GemmProblem*)(cb.h_desc.data() + cb.off.blk_gemm[k][q]);
       const int c0 = k * CB_NB;
       for (int g = 0; g < G; g++) {
         const CondTask& t = cb.tasks[g];
@@ -210,15 +189,11 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
       }
     }
     // every panel's diagonal block of every GP as ONE batch (inverted in one launch after a whole-matrix factorisation)
-    cb.off_diag_mats = region((size_t)cb.nblk * G * sizeof(double*));
-    cb.off_diag_w = region((size_t)cb.nblk * G * sizeof(double*));
-    cb.off_diag_M = region((size_t)cb.nblk * G * sizeof(int));
-    cb.off_diag_ld = region((size_t)cb.nblk * G * sizeof(int));
     {
-      double** dm = (double**)(cb.h_desc.data() + cb.off_diag_mats);
-      double** dw = (double**)(cb.h_desc.data() + cb.off_diag_w);
-      int* dM = (int*)(cb.h_desc.data() + cb.off_diag_M);
-      int* dl = (int*)(cb.h_desc.data() + cb.off_diag_ld);
+      double** dm = (double**)(cb.h_desc.data() + cb.off.diag_mats);
+      double** dw = (double**)(cb.h_desc.data() + cb.off.diag_w);
+      int* dM = (int*)(cb.h_desc.data() + cb.off.diag_M);
+      int* dl = (int*)(cb.h_desc.data() + cb.off.diag_ld);
       for (int k = 0; k < cb.nblk; k++)
         for (int g = 0; g < G; g++) {
           const CondTask& t = cb.tasks[g];
@@ -228,9 +203,8 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
           dm[k * G + g] = t.L + dk; dw[k * G + g] = t.W + dk; dM[k * G + g] = nb; dl[k * G + g] = t.M;
         }
     }
-    if (off > need) return gp_fail(h, GP_ERR_WORKSPACE, "descriptor workspace too small (blocked factorisation)");
   }
-  GP_HIP_CHECK(h, hipMemcpyAsync(cb.d_desc, cb.h_desc.data(), need, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(cb.d_desc, cb.h_desc.data(), cb.off.bytes, hipMemcpyHostToDevice, h->stream));
   cb.uploaded = true;
   return GP_OK;
 }
@@ -242,10 +216,10 @@ static gp_status cond_batch_block_row_inverse(gp_handle h, CondBatch& cb) {
     const int c0 = k * CB_NB;
     GemmFlags f;
     f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off_blk_gemm[k][2]), G, CB_NB, c0, f));
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.blk_gemm[k][2]), G, CB_NB, c0, f));
     f = GemmFlags();
     f.triA = TRI_LOWER; f.alpha = -1.0;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off_blk_gemm[k][3]), G, CB_NB, c0, f));
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.blk_gemm[k][3]), G, CB_NB, c0, f));
   }
   return GP_OK;
 }
@@ -274,27 +248,27 @@ static gp_status cond_batch_factorize(gp_handle h, CondBatch& cb, bool resident)
     int minM = cb.maxM;
     const bool whole = cond_batch_cluster_shape(cb, &minM);
     gp_status st = GP_OK;
-    if (whole && launch_cholesky_cluster_batched(h, (double* const*)(cb.d_desc + cb.off_chol_ptrs), (double* const*)(cb.d_desc + cb.off_w_ptrs),
-                                                 (const int*)(cb.d_desc + cb.off_Ms), (const int*)(cb.d_desc + cb.off_lds), G, minM,
+    if (whole && launch_cholesky_cluster_batched(h, (double* const*)(cb.d_desc + cb.off.chol_ptrs), (double* const*)(cb.d_desc + cb.off.w_ptrs),
+                                                 (const int*)(cb.d_desc + cb.off.Ms), (const int*)(cb.d_desc + cb.off.lds), G, minM,
                                                  cb.maxM, &st))
       return st;
   }
   if (!cb.blocked) {
-    return launch_cholesky_inverse_batched(h, (double* const*)(cb.d_desc + cb.off_chol_ptrs),
-                                           (double* const*)(cb.d_desc + cb.off_w_ptrs),
-                                           (const int*)(cb.d_desc + cb.off_Ms), (const int*)(cb.d_desc + cb.off_lds), G,
+    return launch_cholesky_inverse_batched(h, (double* const*)(cb.d_desc + cb.off.chol_ptrs),
+                                           (double* const*)(cb.d_desc + cb.off.w_ptrs),
+                                           (const int*)(cb.d_desc + cb.off.Ms), (const int*)(cb.d_desc + cb.off.lds), G,
                                            cb.maxM);
   }
   if (resident && cb.maxM <= 512) {
-    GP_CHECK(launch_cholesky_batched(h, (double* const*)(cb.d_desc + cb.off_chol_ptrs),
-                                     (const int*)(cb.d_desc + cb.off_Ms), (const int*)(cb.d_desc + cb.off_lds), G,
+    GP_CHECK(launch_cholesky_batched(h, (double* const*)(cb.d_desc + cb.off.chol_ptrs),
+                                     (const int*)(cb.d_desc + cb.off.Ms), (const int*)(cb.d_desc + cb.off.lds), G,
                                      cb.maxM));
-    GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off_w_ptrs),
-                                              (const int*)(cb.d_desc + cb.off_Ms), (const int*)(cb.d_desc + cb.off_lds), G,
+    GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off.w_ptrs),
+                                              (const int*)(cb.d_desc + cb.off.Ms), (const int*)(cb.d_desc + cb.off.lds), G,
                                               cb.maxM, CB_NB));
-    GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)(cb.d_desc + cb.off_diag_mats),
-                                        (double* const*)(cb.d_desc + cb.off_diag_w),
-                                        (const int*)(cb.d_desc + cb.off_diag_M), (const int*)(cb.d_desc + cb.off_diag_ld),
+    GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)(cb.d_desc + cb.off.diag_mats),
+                                        (double* const*)(cb.d_desc + cb.off.diag_w),
+                                        (const int*)(cb.d_desc + cb.off.diag_M), (const int*)(cb.d_desc + cb.off.diag_ld),
                                         cb.nblk * G));
     // the first row-block of A = W Kuf needs only W's first diagonal block: cond_batch_run starts it from here, underneath
     // the six dependent launches of the block-row inverse (0.2 ms of a few workgroups each)
@@ -304,29 +278,29 @@ static gp_status cond_batch_factorize(gp_handle h, CondBatch& cb, bool resident)
     }
     return cond_batch_block_row_inverse(h, cb);
   }
-  const int* lds = (const int*)(cb.d_desc + cb.off_lds);
+  const int* lds = (const int*)(cb.d_desc + cb.off.lds);
   // zero above the block diagonal of every W in one launch (the diagonal blocks are written whole, the blocks
   // below by the block-row inverse)
-  GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off_w_ptrs),
-                                            (const int*)(cb.d_desc + cb.off_Ms), lds, G, cb.maxM, CB_NB));
+  GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off.w_ptrs),
+                                            (const int*)(cb.d_desc + cb.off.Ms), lds, G, cb.maxM, CB_NB));
   for (int k = 0; k < cb.nblk; k++) {
-    double* const* mats = (double* const*)(cb.d_desc + cb.off_blk_mats[k]);
-    double* const* ws = (double* const*)(cb.d_desc + cb.off_blk_w[k]);
-    const int* bM = (const int*)(cb.d_desc + cb.off_blk_M[k]);
+    double* const* mats = (double* const*)(cb.d_desc + cb.off.blk_mats[k]);
+    double* const* ws = (double* const*)(cb.d_desc + cb.off.blk_w[k]);
+    const int* bM = (const int*)(cb.d_desc + cb.off.blk_M[k]);
     const int c0 = k * CB_NB, rem = cb.maxM - c0 - CB_NB;
     GP_CHECK(launch_cholesky_batched(h, mats, bM, lds, G, CB_NB, c0));
     GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)mats, ws, bM, lds, G));
     if (rem > 0) {
       GemmFlags f;
       f.transB = 1; f.triB = TRI_UPPER; f.big_tiles = 1;   // 128-wide tiles: each workgroup reads exactly the rows it rewrites
-      GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off_blk_gemm[k][0]), G, rem, CB_NB, f));
+      GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.blk_gemm[k][0]), G, rem, CB_NB, f));
       f = GemmFlags();
       f.transB = 1; f.triC = TRI_LOWER; f.alpha = -1.0; f.beta = 1.0;
-      GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off_blk_gemm[k][1]), G, rem, rem, f));
+      GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.blk_gemm[k][1]), G, rem, rem, f));
     }
   }
-  GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off_chol_ptrs),
-                                            (const int*)(cb.d_desc + cb.off_Ms), lds, G, cb.maxM, CB_NB));
+  GP_CHECK(launch_zero_upper_blocks_batched(h, (double* const*)(cb.d_desc + cb.off.chol_ptrs),
+                                            (const int*)(cb.d_desc + cb.off.Ms), lds, G, cb.maxM, CB_NB));
   return cond_batch_block_row_inverse(h, cb);
 }
 
@@ -357,9 +331,9 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     for (const auto& gr : cb.groups) {
       const int cnt = (int)gr.members.size();
       if (gp_kern_is_mercer(gr.type))
-        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off_feat_zuu) + gr.first, cnt, gr.maxM,
+        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off.feat_zuu) + gr.first, cnt, gr.maxM,
                                           sm_mpad(gr.m), nullptr, 0));
-      GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off_cov_uu) + gr.first, cnt,
+      GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off.cov_uu) + gr.first, cnt,
                                          gr.maxM, gr.maxM, nullptr, 0));
     }
     return GP_OK;
@@ -370,11 +344,11 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
       const int cnt = (int)gr.members.size();
       if (gp_kern_is_mercer(gr.type)) {
         const int mp = sm_mpad(gr.m);
-        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off_feat_zuf) + gr.first, cnt, gr.maxM, mp,
+        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off.feat_zuf) + gr.first, cnt, gr.maxM, mp,
                                           nullptr, 0));
-        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off_feat_x) + gr.first, cnt, N, mp, x, N));
+        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off.feat_x) + gr.first, cnt, N, mp, x, N));
       }
-      GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off_cov_uf) + gr.first, cnt,
+      GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off.cov_uf) + gr.first, cnt,
                                          gr.maxM, N, x, N, gr.f32 ? 2 : 1));     // 2: the strips are float32
     }
     return GP_OK;
@@ -428,7 +402,7 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     auto cond_a = [&](int m0, int mcount) -> gp_status {
       GemmFlags g = f;
       g.tile_m0 = m0; g.tile_mcount = mcount;
-      return strips(cb.off_f1, g);
+      return strips(cb.off.f1, g);
     };
     if (early) {
       gp_status s1 = cond_a(0, 1);
@@ -446,7 +420,7 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     f.epilogue = EPI_STORE | EPI_COLDOT;
     // float32 strips: the same product shape as Lq^T A (op(A) = W^T upper, read row-wise), stored: role 2 of gemm_f32.hip
     GemmFlags f3 = f; f3.role = 2;
-    GP_CHECK(strips(cb.off_f1u, f, &f3));
+    GP_CHECK(strips(cb.off.f1u, f, &f3));
   }
   // 5. LTA = tril(q_sqrt)^T A  (only its column sums of squares are needed)
   bool any_qsqrt = false;
@@ -459,9 +433,9 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     f.epilogue = EPI_COLSUMSQ;
     f.uniform_aligned = whiten ? cond_batch_uniform(cb, N) : 0;
     f.rows64_ok = cb.wave_lta ? 1 : 0;
-    GP_CHECK(strips(cb.off_f2, f));
+    GP_CHECK(strips(cb.off.f2, f));
   }
   // 6. fmean / fvar
-  GP_CHECK(launch_cond_finish(h, cb.d_desc + cb.off_finish, G, N));
+  GP_CHECK(launch_cond_finish(h, cb.d_desc + cb.off.finish, G, N));
   return GP_OK;
 }

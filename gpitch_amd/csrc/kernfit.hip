@@ -205,11 +205,16 @@ __global__ __launch_bounds__(64) void kernfit_eval_kernel(const double* __restri
 
 extern "C" {
 
+// gp_segment_gram's workspace: the tile partials of every (recording, chunk), the start table padded to 16 per recording
+static double* segment_gram_carve(GpArena& ar, int B, int K, int L, int** st) {
+  double* part = ar.take<double>((size_t)B * sg_chunks(K) * sg_tiles(L) * SG_T * SG_T);
+  *st = ar.take<int>((size_t)B * sg_round_up(K, 16));
+  return part;
+}
 size_t gp_segment_gram_workspace_bytes(int32_t B, int32_t K, int32_t L) {
   if (B < 1 || K < 1 || L < 1) return 0;
-  const int64_t part = (int64_t)B * sg_chunks(K) * sg_tiles(L) * SG_T * SG_T * 8;
-  const int64_t st = (int64_t)B * sg_round_up(K, 16) * 4;
-  return (size_t)(sg_round_up(part, 256) + sg_round_up(st, 256));
+  int* st;
+  return gp_measure([&](GpArena& ar) { segment_gram_carve(ar, B, K, L, &st); });
 }
 
 gp_status gp_segment_gram(gp_handle h, const double* y, int64_t ny, const int64_t* rec_off_host, const int64_t* rec_len_host,
@@ -236,8 +241,9 @@ gp_status gp_segment_gram(gp_handle h, const double* y, int64_t ny, const int64_
   }
   const int ntiles = sg_tiles(L), nch = sg_chunks(K), ntg = (ntiles + 3) / 4;
   const int Kp = (int)sg_round_up(K, 16);
-  double* part = (double*)workspace;
-  int* st = (int*)((char*)workspace + sg_round_up((int64_t)B * nch * ntiles * SG_T * SG_T * 8, 256));
+  GpArena ar(workspace, workspace_bytes);
+  int* st;
+  double* part = segment_gram_carve(ar, B, K, L, &st);
   GP_HIP_CHECK(h, hipMemsetAsync(st, 0, (size_t)B * Kp * 4, h->stream));
   GP_HIP_CHECK(h, hipMemcpy2DAsync(st, (size_t)Kp * 4, start_host, (size_t)K * 4, (size_t)K * 4, B, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(segment_gram_kernel, dim3(B * nch * ntg), dim3(256), 0, h->stream, y, ny, st, Kp, K, ntiles, ntg, nch, part);

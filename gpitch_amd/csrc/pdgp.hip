@@ -5,29 +5,6 @@
 #include <string.h>
 
 
-static size_t pdgp_bwd_doubles(const gp_pdgp_plan_s* p) {
-  size_t d = 0;
-  auto add = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
-  for (int g = 0; g < p->G; g++) {
-    const size_t M = p->gps[g].M;
-    for (int i = 0; i < 6; i++) add(M * M);
-    add(gp_strip_doubles(M, p->maxN, p->gps[g].f32 != 0));
-    if (p->gps[g].f32) add((M * M + 1) / 2);
-    add(M); add(M); add(M); add((size_t)65 * M);
-    const size_t ns = hyper_num_sums(p->gps[g].m);
-    const size_t colblocks = (p->maxN + 255) / 256 + 1;
-    add(ns * hyper_kuf_records(p->maxN, (int)M));
-    add(ns * hyper_kuf_records((int)M, (int)M));
-    add(colblocks * M + ((M + 255) / 256 + 1) * M);
-  }
-  add(p->G + 8);
-  if (!p->whiten) {
-    for (int g = 0; g < p->G; g++) { const size_t M = p->gps[g].M; add(2 * (M + M * M) + 8); }
-    add((size_t)p->G * GP_KL_BLOCKS);
-  }
-  return d;
-}
-
 extern "C" {
 
 static gp_status pdgp_create_impl(gp_handle h, const gp_pdgp_config* cfg, const int32_t* gp_index, int32_t count,
@@ -148,44 +125,13 @@ gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t*
   return GP_OK;
 }
 
-static size_t pdgp_misc_bytes(const gp_pdgp_plan_s* p) {
-  return 2 * pdgp_kl_region_bytes(p->G) + 24 * gp_align_up(p->G * sizeof(GemmProblem), 256) +
-         gp_align_up(p->G * hyper_finish_item_bytes(), 256) + gp_align_up(2 * p->G * sizeof(HyperItem), 256);
-}
-
-size_t gp_pdgp_workspace_bytes(gp_pdgp_plan p) {
-  if (!p) return 0;
-  size_t d = 0;
-  for (int g = 0; g < p->G; g++) d += cond_task_workspace_doubles(p->gps[g].M, p->maxN, p->gps[g].m, p->whiten != 0, p->gps[g].f32 != 0);
-  auto addd = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
-  for (int i = 0; i < 4; i++) addd((size_t)p->G * p->maxN);
-  if (p->subset) for (int i = 0; i < 2; i++) addd((size_t)2 * p->P * p->maxN);
-  addd((size_t)p->G * GP_KL_BLOCKS);
-  addd(2 * (size_t)mpd_lik_blocks(p->maxN) + 8);
-  if (!p->whiten)
-    for (int g = 0; g < p->G; g++) addd((size_t)gemm_rowblocks(p->gps[g].M, 0) * p->gps[g].M);
-  {
-    d += pdgp_bwd_doubles(p);
-    int ns = gemm_nt_nsplit(p->maxM, p->maxN, p->G);
-    if (ns < 2) ns = 2;
-    size_t slab = 0;
-    for (int g = 0; g < p->G; g++) slab += gp_align_up((size_t)ns * p->gps[g].M * p->gps[g].M * sizeof(double), 256) / sizeof(double);
-    d += slab;
-  }
-  return d * sizeof(double) + cond_batch_desc_bytes(p->G) + pdgp_misc_bytes(p) + 8192;
-}
-
-gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
-  if (!p) return GP_ERR_BAD_ARG;
-  if (!workspace || bytes < gp_pdgp_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
-    return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_pdgp_set_workspace: workspace too small or not 256-byte aligned");
-  p->ws = workspace; p->ws_bytes = bytes;
-  GpArena ar(workspace, bytes);
+// Every buffer of the plan's workspace, in order, into the plan's own members.  gp_pdgp_workspace_bytes runs it on a
+// throwaway copy of the plan and a measuring arena.
+static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
   p->cb.tasks.assign(p->G, CondTask());
-  p->cb.desc_bytes = cond_batch_desc_bytes(p->G);
-  p->cb.d_desc = ar.take<char>(p->cb.desc_bytes);
-  p->misc_bytes = pdgp_misc_bytes(p);
-  p->d_misc = ar.take<char>(p->misc_bytes);
+  p->cb.d_desc = ar.take<char>(cond_batch_desc_bytes(p->G));
+  p->off = pdgp_misc_layout(p->G);
+  p->d_misc = ar.take<char>(p->off.bytes);
   p->fmean = ar.take<double>((size_t)p->G * p->maxN);
   p->fvar = ar.take<double>((size_t)p->G * p->maxN);
   p->gFmu = ar.take<double>((size_t)p->G * p->maxN);
@@ -201,7 +147,7 @@ gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
     t.M = p->gps[g].M;
     t.kern = DevKern{p->gps[g].ktype, p->gps[g].m, nullptr};
     t.f32 = p->gps[g].f32 != 0;
-    if (!cond_task_carve(ar, t, p->maxN, p->whiten != 0, t.f32)) return gp_fail(p->h, GP_ERR_WORKSPACE, "workspace carve failed");
+    cond_task_carve(ar, t, p->maxN, p->whiten != 0, t.f32);
   }
   p->bw.assign(p->G, BwdBufs());
   p->tr_part.assign(p->G, nullptr);
@@ -246,7 +192,22 @@ gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
       p->kl_dummy = ar.take<double>((size_t)p->G * GP_KL_BLOCKS);
     }
   }
-  if (!ar.ok) return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_pdgp_set_workspace: arena exhausted");
+  return ar.ok;
+}
+
+size_t gp_pdgp_workspace_bytes(gp_pdgp_plan p) {
+  if (!p) return 0;
+  gp_pdgp_plan_s dry = *p;      // a throwaway copy takes the null pointers: the plan owns nothing a destructor releases
+  return gp_measure([&](GpArena& ar) { pdgp_carve(&dry, ar); }) + GP_WS_TAIL_PLAN;
+}
+
+gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (!workspace || bytes < gp_pdgp_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
+    return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_pdgp_set_workspace: workspace too small or not 256-byte aligned");
+  GpArena ar(workspace, bytes);
+  if (!pdgp_carve(p, ar)) return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_pdgp_set_workspace: arena exhausted");
+  p->ws = workspace; p->ws_bytes = bytes;
   p->last_params = nullptr; p->last_n = -1;
   return GP_OK;
 }
@@ -279,26 +240,25 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   p->cb.N = n;
   GP_CHECK(cond_batch_upload(h, p->cb, p->whiten != 0, p->jitter));
   // KL items
-  p->h_misc.assign(p->misc_bytes, 0);
-  p->off_kl_items = 0;
+  p->h_misc.assign(p->off.bytes, 0);
   for (int g = 0; g < p->G; g++) {
     const PdgpGP& q = p->gps[g];
     const CondTask& t = p->cb.tasks[g];
     if (p->whiten) {
-      kl_item_fill(p->h_misc.data() + p->off_kl_items + g * kl_item_bytes(), params + q.off_qmu, params + q.off_qsqrt,
+      kl_item_fill(p->h_misc.data() + p->off.kl_items + g * kl_item_bytes(), params + q.off_qmu, params + q.off_qsqrt,
                    q.M, p->kl + (size_t)g * GP_KL_BLOCKS, grad ? grad + q.off_qmu : nullptr, grad ? grad + q.off_qsqrt : nullptr);
     } else {
-      klu_item_fill(p->h_misc.data() + p->off_kl_items + g * klu_item_bytes(), params + q.off_qmu, params + q.off_qsqrt,
+      klu_item_fill(p->h_misc.data() + p->off.kl_items + g * klu_item_bytes(), params + q.off_qmu, params + q.off_qsqrt,
                     t.L, t.W, p->tr_part[g], gemm_rowblocks(q.M, 0), q.M, p->kl + (size_t)g * GP_KL_BLOCKS);
       // trace term: column sums of squares of W Lq (its own descriptor slot, after the backward ones)
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + pdgp_kltr_offset(p->G) + g * sizeof(GemmProblem));
+      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.kltr + g * sizeof(GemmProblem));
       memset(&r, 0, sizeof(r));
       r.A = t.W; r.lda = q.M; r.B = params + q.off_qsqrt; r.ldb = q.M; r.M = q.M; r.N = q.M; r.K = q.M; r.ldc = q.M;
       r.o0 = p->tr_part[g];
     }
   }
   if (grad) GP_CHECK(pdgp_upload_bwd(p, params, x, n, grad));
-  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_misc, p->h_misc.data(), p->misc_bytes, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(p->d_misc, p->h_misc.data(), p->off.bytes, hipMemcpyHostToDevice, h->stream));
   p->last_params = params; p->last_x = x; p->last_n = n; p->last_grad = grad;
   return GP_OK;
 }
@@ -323,15 +283,15 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
                             nullptr, nullptr, xchg, nullptr));
   }
   if (p->whiten) {
-    if (!kl_done) GP_CHECK(launch_kl_white(h, p->d_misc + p->off_kl_items, p->G));
+    if (!kl_done) GP_CHECK(launch_kl_white(h, p->d_misc + p->off.kl_items, p->G));
   } else {
     // gauss_kl(q_mu, q_sqrt, K = Kuu + jitter I) (pdgp.py:123-129): L and W of the conditional are reused
     // (one value per GP: the other partial-sum slots of the whitened layout stay zero)
     GP_HIP_CHECK(h, hipMemsetAsync(p->kl, 0, (size_t)p->G * GP_KL_BLOCKS * sizeof(double), h->stream));
     GemmFlags f;
     f.triA = TRI_LOWER; f.triB = TRI_LOWER; f.epilogue = EPI_COLSUMSQ;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(p->d_misc + pdgp_kltr_offset(p->G)), p->G, p->maxM, p->maxM, f));
-    GP_CHECK(launch_kl_unwhite(h, p->d_misc + p->off_kl_items, p->G));
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(p->d_misc + p->off.kltr), p->G, p->maxM, p->maxM, f));
+    GP_CHECK(launch_kl_unwhite(h, p->d_misc + p->off.kl_items, p->G));
   }
   if (xchg) GP_CHECK(launch_finish_sum(h, p->kl, p->G * GP_KL_BLOCKS, 1, 1, xchg + 3 * (size_t)n, 1.0, 0));
   return GP_OK;

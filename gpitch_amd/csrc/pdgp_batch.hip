@@ -905,21 +905,27 @@ gp_status gp_pdgpb_set_grad_needs(gp_pdgpb_plan p, int32_t g, int32_t need_theta
   return GP_OK;
 }
 
-static size_t pb_region_bytes(const gp_pdgpb_plan_s* p) {
-  size_t b = 0;
-  b += gp_align_up(p->gps.size() * sizeof(PbGp), 256);
-  b += gp_align_up(p->models.size() * sizeof(PbModel), 256);
-  b += gp_align_up((size_t)p->nparams * sizeof(int32_t), 256);
-  b += gp_align_up((size_t)p->nm * sizeof(int32_t), 256);
-  b += 4 * gp_align_up((size_t)p->f_len * sizeof(double), 256);
-  b += gp_align_up((size_t)p->G * sizeof(double), 256);
-  b += gp_align_up((size_t)p->nparams * sizeof(double), 256);
-  b += gp_align_up((size_t)p->nm * sizeof(double), 256);
-  b += gp_align_up((size_t)p->scratch * sizeof(double), 256);
-  return b;
+// gp_pdgpb_set_workspace's regions of a workspace, in order
+struct PbRegions { PbGp* gps; PbModel* models; int32_t* owner; int32_t* status; double *fm, *fv, *gm, *gv, *kl, *grad, *elbo, *scr; };
+static PbRegions pb_regions(const gp_pdgpb_plan_s* p, GpArena& ar) {
+  PbRegions r;
+  r.gps = ar.take<PbGp>(p->gps.size());
+  r.models = ar.take<PbModel>(p->models.size());
+  r.owner = ar.take<int32_t>(p->nparams);
+  r.status = ar.take<int32_t>(p->nm);
+  r.fm = ar.take<double>(p->f_len); r.fv = ar.take<double>(p->f_len);
+  r.gm = ar.take<double>(p->f_len); r.gv = ar.take<double>(p->f_len);
+  r.kl = ar.take<double>(p->G);
+  r.grad = ar.take<double>(p->nparams);
+  r.elbo = ar.take<double>(p->nm);
+  r.scr = ar.take<double>(p->scratch);
+  return r;
 }
 
-size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p) { return (p && !p->predict_only) ? pb_region_bytes(p) + 256 : 0; }
+size_t gp_pdgpb_workspace_bytes(gp_pdgpb_plan p) {
+  if (!p || p->predict_only) return 0;
+  return gp_measure([&](GpArena& ar) { pb_regions(p, ar); }) + GP_WS_TAIL_BATCH;
+}
 
 gp_status gp_pdgpb_set_workspace(gp_pdgpb_plan p, void* workspace, size_t bytes) {
   if (!p) return GP_ERR_BAD_ARG;
@@ -928,17 +934,11 @@ gp_status gp_pdgpb_set_workspace(gp_pdgpb_plan p, void* workspace, size_t bytes)
   if (!workspace || bytes < gp_pdgpb_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_workspace: workspace too small or not 256-byte aligned");
   GpArena ar(workspace, bytes);
-  p->d_gps = ar.take<PbGp>(p->gps.size());
-  p->d_models = ar.take<PbModel>(p->models.size());
-  p->d_owner = ar.take<int32_t>(p->nparams);
-  p->d_status = ar.take<int32_t>(p->nm);
-  p->d_fm = ar.take<double>(p->f_len); p->d_fv = ar.take<double>(p->f_len);
-  p->d_gm = ar.take<double>(p->f_len); p->d_gv = ar.take<double>(p->f_len);
-  p->d_kl = ar.take<double>(p->G);
-  p->d_grad = ar.take<double>(p->nparams);
-  p->d_elbo = ar.take<double>(p->nm);
-  p->d_scr = ar.take<double>(p->scratch);
+  const PbRegions r = pb_regions(p, ar);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_workspace: arena overflow");
+  p->d_gps = r.gps; p->d_models = r.models; p->d_owner = r.owner; p->d_status = r.status;
+  p->d_fm = r.fm; p->d_fv = r.fv; p->d_gm = r.gm; p->d_gv = r.gv;
+  p->d_kl = r.kl; p->d_grad = r.grad; p->d_elbo = r.elbo; p->d_scr = r.scr;
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_owner, p->owner.data(), p->owner.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipMemsetAsync(p->d_status, 0, p->nm * sizeof(int32_t), h->stream));
   GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_fwd_lds(p)));
@@ -1010,13 +1010,9 @@ static PbPredRegions pb_pred_regions(const gp_pdgpb_plan_s* p, GpArena& ar) {
   return r;
 }
 
-static size_t pb_pred_region_bytes(const gp_pdgpb_plan_s* p) {
-  GpArena ar(nullptr, SIZE_MAX);     // no memory behind it: measures
-  pb_pred_regions(p, ar);
-  return ar.off;
+size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p) {
+  return (p && p->predict_only) ? gp_measure([&](GpArena& ar) { pb_pred_regions(p, ar); }) + GP_WS_TAIL_BATCH : 0;
 }
-
-size_t gp_pdgpb_predict_workspace_bytes(gp_pdgpb_plan p) { return (p && p->predict_only) ? pb_pred_region_bytes(p) + 256 : 0; }
 
 gp_status gp_pdgpb_predict_prepare(gp_pdgpb_plan p, const double* params, void* workspace, size_t bytes) {
   if (!p) return GP_ERR_BAD_ARG;
@@ -1118,9 +1114,15 @@ gp_status gp_pdgpb_predict(gp_pdgpb_plan p, const double* params, const double* 
   return GP_OK;
 }
 
+// gp_pdgpb_predict_moments' carve: gp_pdgpb_predict_prepare's regions, then this call's fmean / fvar (`latent` doubles each)
+static std::pair<double*, double*> pb_mom_regions(const gp_pdgpb_plan_s* p, GpArena& ar, int64_t latent) {
+  pb_pred_regions(p, ar);
+  double* fm = ar.take<double>((size_t)latent);
+  return {fm, ar.take<double>((size_t)latent)};
+}
 size_t gp_pdgpb_predict_moments_workspace_bytes(gp_pdgpb_plan p, int64_t latent_frames) {
   if (!p || !p->predict_only || latent_frames < 0) return 0;
-  return pb_pred_region_bytes(p) + 2 * gp_align_up((size_t)latent_frames * sizeof(double), 256) + 256;
+  return gp_measure([&](GpArena& ar) { pb_mom_regions(p, ar, latent_frames); }) + GP_WS_TAIL_BATCH;
 }
 
 gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
@@ -1139,11 +1141,9 @@ gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const 
   if (!xnew || (logp && !ynew)) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_predict_moments: bad argument (logp needs ynew)");
   const size_t lds = (size_t)PB_MOM_FRAMES * 4 * maxP * sizeof(double);
   if (lds > 48 * 1024) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_predict_moments: too many sources for the moments kernel's LDS staging");
-  // fmean / fvar of this call: behind gp_pdgpb_predict_prepare's regions of the same workspace
   GpArena ar(workspace, bytes);
-  pb_pred_regions(p, ar);
-  double *fm = ar.take<double>((size_t)latent), *fv = ar.take<double>((size_t)latent);
-  if (!ar.ok || !fm || !fv)
+  const auto [fm, fv] = pb_mom_regions(p, ar, latent);
+  if (bytes < gp_pdgpb_predict_moments_workspace_bytes(p, latent) || !ar.ok)
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_predict_moments: the workspace does not hold this call's fmean / fvar (gp_pdgpb_predict_moments_workspace_bytes)");
   int64_t tiles = 0;       // > 0: there are frames
   GP_CHECK(pb_pred_records(p, xnew_off, 1, &tiles));

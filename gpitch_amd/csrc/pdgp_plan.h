@@ -7,9 +7,23 @@ static inline size_t pdgp_kl_region_bytes(int G) {
   return gp_align_up((size_t)G * (a > b ? a : b), 256);
 }
 
-// descriptor slot (of 24) holding the trace-term problems of the unwhitened KL
-static inline size_t pdgp_kltr_offset(int G) {
-  return pdgp_kl_region_bytes(G) + 23 * gp_align_up((size_t)G * sizeof(GemmProblem), 256);
+// The plan's `misc` descriptor block: [KL items][PDGP_BWD_SLOTS arrays of G GemmProblems][KL items of the unwhitened
+// backward][G hyper-gradient finish items][2 G contraction items].  The backward pass uses the first S_COUNT slots
+// (bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
+#define PDGP_BWD_SLOTS 24
+#define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, bytes; };
+static inline PdgpMiscLayout pdgp_misc_layout(int G) {
+  PdgpMiscLayout o;
+  GpRegions region;
+  o.kl_items = region(pdgp_kl_region_bytes(G));
+  for (int s = 0; s < PDGP_BWD_SLOTS; s++) o.bwd[s] = region((size_t)G * sizeof(GemmProblem));
+  o.kltr = o.bwd[PDGP_KLTR_SLOT];
+  o.kl2 = region(pdgp_kl_region_bytes(G));
+  o.fin_items = region((size_t)G * hyper_finish_item_bytes());
+  o.hy_items = region((size_t)2 * G * sizeof(HyperItem));      // G Kuf-side items, then G Kuu-side items, same order
+  o.bytes = region.off;
+  return o;
 }
 
 struct PdgpGP {
@@ -61,17 +75,12 @@ struct gp_pdgp_plan_s {
   double* kl = nullptr;                              // [G]
   double* lik_partials = nullptr;                    // [2 * blocks]
   double* slabs = nullptr;                           // split-K slabs
-  char* d_misc = nullptr; size_t misc_bytes = 0;     // KL items + backward problem arrays
+  char* d_misc = nullptr; PdgpMiscLayout off;        // KL items + backward problem arrays: off = pdgp_misc_layout(G)
   std::vector<char> h_misc;
-  size_t off_kl_items = 0;
-  size_t off_bwd[24] = {0};
-  size_t off_fin_items = 0; std::vector<char> h_fin_items;   // batched hyper-gradient finish (bwd.hip)
-  // Kuf-side and Kuu-side contractions grouped by kernel family: one launch per family and side over an item array
-  // (bwd.hip; G Kuf-side items, then G Kuu-side items, same order)
-  size_t off_hy_items = 0;
+  std::vector<char> h_fin_items;   // batched hyper-gradient finish (bwd.hip)
+  // Kuf-side and Kuu-side contractions grouped by kernel family: one launch per family and side over an item array (bwd.hip)
   struct HyFamily { int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; std::vector<int> gps; };
   std::vector<HyFamily> hy_fams;
-  size_t off_kl2 = 0;         // unwhitened backward: KL items of the equivalent whitened state
   double* qw_block = nullptr; size_t qw_doubles = 0;   // [q' | grad q'] of all GPs, contiguous (one memset)
   double* kl_dummy = nullptr;
   int nsplit = 1;

@@ -8,7 +8,25 @@
 #include "engine.h"
 #include <string.h>
 
-struct gp_sgpr_plan_s {
+// what gp_sgpr_set_workspace carves out of the caller's memory (sgpr_carve)
+struct SgprBufs {
+  char* d_desc = nullptr;      // two descriptor blocks (training pass / prediction pass)
+  double *L = nullptr, *W = nullptr, *Kuf = nullptr, *A = nullptr, *H = nullptr, *LB = nullptr, *WB = nullptr;
+  double *feat = nullptr, *s1 = nullptr, *s2 = nullptr, *dot = nullptr, *u = nullptr, *c = nullptr, *slabs = nullptr;
+  // backward
+  double *E2 = nullptr, *T1 = nullptr, *T2 = nullptr, *Wbar = nullptr, *R = nullptr, *Binv = nullptr, *G = nullptr;
+  double *ubar = nullptr, *Lu = nullptr, *alpha = nullptr, *ones = nullptr, *hyp = nullptr, *hyp_uu = nullptr;
+  size_t hyp_stride = 0;    // doubles between the per-kernel partial record sets in hyp
+  size_t hyp_uu_stride = 0; // the same for the Kuu-side record sets in hyp_uu
+  double *upart = nullptr;  // [max(nsplit, 2)][M] row-dot partials of u = A' y, fused into the H = A' A'^T launch
+  double *red = nullptr;    // [2][SG_RED_BLOCKS] partial sums of the two N-long reductions (tr H, sum y^2)
+  double *scal = nullptr;   // [0] bound, [1] sum err^2, [2] sum colsumsq(A'), [3] kdiag total per point, [4] dF/dkd, [5] dF/ds
+  // M > 256: Kuu and B are factored by one resident launch and inverted block by block (chol.hip: chol_inverse_blocked_*),
+  // descriptors prepared when the workspace is set
+  void *chol_ws_kuu = nullptr, *chol_ws_b = nullptr; size_t chol_ws_bytes = 0; bool chol_blocked = false;
+};
+
+struct gp_sgpr_plan_s : SgprBufs {
   gp_handle h = nullptr;
   int P = 0, maxN = 0, M = 0, reg = 0;
   int f32 = 0;                 // gp_sgpr_set_precision: Kuf, A, Kuf_bar strips in float32 (gemm_f32.hip)
@@ -18,23 +36,9 @@ struct gp_sgpr_plan_s {
   int64_t nparams = 0;
   int maxm = 0;
   void* ws = nullptr; size_t ws_bytes = 0;
-  // workspace
-  double *L = nullptr, *W = nullptr, *Kuf = nullptr, *A = nullptr, *H = nullptr, *LB = nullptr, *WB = nullptr;
-  double *feat = nullptr, *s1 = nullptr, *s2 = nullptr, *dot = nullptr, *u = nullptr, *c = nullptr, *slabs = nullptr;
-  // backward
-  double *E2 = nullptr, *T1 = nullptr, *T2 = nullptr, *Wbar = nullptr, *R = nullptr, *Binv = nullptr, *G = nullptr;
-  double *ubar = nullptr, *Lu = nullptr, *alpha = nullptr, *ones = nullptr, *hyp = nullptr, *hyp_uu = nullptr;
-  size_t hyp_stride = 0;    // doubles between the per-kernel partial record sets in hyp
-  size_t hyp_uu_stride = 0; // the same for the Kuu-side record sets in hyp_uu
   std::vector<char> h_tail_fin;   // the batched gradient tail's finish items as last uploaded (sgpr_backward)
-  double *upart = nullptr;  // [max(nsplit, 2)][M] row-dot partials of u = A' y, fused into the H = A' A'^T launch
-  double *red = nullptr;    // [2][SG_RED_BLOCKS] partial sums of the two N-long reductions (tr H, sum y^2)
-  double *scal = nullptr;   // [0] bound, [1] sum err^2, [2] sum colsumsq(A'), [3] kdiag total per point, [4] dF/dkd, [5] dF/ds
-  char* d_desc = nullptr; std::vector<char> h_desc[2];   // two descriptor blocks (training pass / prediction pass)
+  std::vector<char> h_desc[2];    // host copies of the two descriptor blocks
   int nsplit = 2;
-  // M > 256: Kuu and B are factored by one resident launch and inverted block by block (chol.hip: chol_inverse_blocked_*),
-  // descriptors prepared when the workspace is set
-  void *chol_ws_kuu = nullptr, *chol_ws_b = nullptr; size_t chol_ws_bytes = 0; bool chol_blocked = false;
   // bound+gradient evaluations are launch-bound at window sizes (N ~ 2001): once the device descriptors match
   // the argument pointers the whole kernel sequence is captured into a hipGraph and replayed (L-BFGS-B calls it
   // dozens of times per window with the same buffers)
@@ -215,26 +219,39 @@ static size_t sgpr_feat_stride(const gp_sgpr_plan_s* p) {
 }
 
 static bool sgpr_chol_blocked(const gp_sgpr_plan_s* p) { return p->M > 256 && p->M <= 1024 && (p->M % 2) == 0; }
-static size_t sgpr_ws_doubles(const gp_sgpr_plan_s* p) {
-  size_t d = 0;
-  auto add = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
+// every buffer of the plan's workspace, in order
+static SgprBufs sgpr_carve(const gp_sgpr_plan_s* p, GpArena& ar) {
+  SgprBufs b;
   const size_t M = p->M, strip = gp_strip_doubles(M, p->maxN, p->f32 != 0);
-  const int rb = (p->M + 63) / 64;                   // column-partial rows: one per 64-row tile (gemm_wave.hip; the 128-row forms use half)
-  for (int i = 0; i < 5; i++) add(M * M);           // L, W, H, LB, WB
-  add(strip); add(strip);                            // Kuf, A
-  add(sgpr_feat_stride(p) * p->P);                   // one feature table per kernel of the sum
-  add((size_t)rb * p->maxN); add((size_t)rb * p->maxN); add((size_t)rb * p->maxN);
-  add(M); add(M); add(64); add((size_t)(p->nsplit > 2 ? p->nsplit : 2) * M); add(2 * SG_RED_BLOCKS);
-  add((size_t)p->nsplit * M * M);
-  for (int i = 0; i < 6; i++) add(M * M);            // E2, T1, T2, Wbar, R, Binv
-  add(strip); add(M); add(M); add(M); add(p->maxN);
+  const int rb = (p->M + 63) / 64;     // column-partial rows: one per 64-row tile (gemm_wave.hip; the 128-row forms use half)
+  b.d_desc = ar.take<char>(2 * SG_DESC_BYTES);
+  b.L = ar.take<double>(M * M); b.W = ar.take<double>(M * M); b.H = ar.take<double>(M * M);
+  b.LB = ar.take<double>(M * M); b.WB = ar.take<double>(M * M);
+  b.Kuf = ar.take<double>(strip); b.A = ar.take<double>(strip);
+  b.feat = ar.take<double>(sgpr_feat_stride(p) * p->P);        // one feature table per kernel of the sum
+  b.s1 = ar.take<double>((size_t)rb * p->maxN); b.s2 = ar.take<double>((size_t)rb * p->maxN);
+  b.dot = ar.take<double>((size_t)rb * p->maxN);
+  b.u = ar.take<double>(M); b.c = ar.take<double>(M); b.scal = ar.take<double>(64);
+  b.upart = ar.take<double>((size_t)(p->nsplit > 2 ? p->nsplit : 2) * M); b.red = ar.take<double>(2 * SG_RED_BLOCKS);
+  b.slabs = ar.take<double>((size_t)p->nsplit * M * M);
+  b.E2 = ar.take<double>(M * M); b.T1 = ar.take<double>(M * M); b.T2 = ar.take<double>(M * M);
+  b.Wbar = ar.take<double>(M * M); b.R = ar.take<double>(M * M); b.Binv = ar.take<double>(M * M);
+  b.G = ar.take<double>(strip); b.ubar = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);
+  b.ones = ar.take<double>(p->maxN);
   {
     const size_t ns = hyper_num_sums(p->maxm);
-    add(ns * hyper_kuf_records(p->maxN, (int)M) * (size_t)(p->P > 0 ? p->P : 1));     // one record set per kernel of the sum (fused contraction)
-    add(ns * hyper_kuf_records((int)M, (int)M) * (size_t)(p->P > 0 ? p->P : 1));
+    b.hyp_stride = ns * hyper_kuf_records(p->maxN, (int)M);      // one record set per kernel of the sum (fused contraction)
+    b.hyp = ar.take<double>(b.hyp_stride * (size_t)(p->P > 0 ? p->P : 1));
+    b.hyp_uu_stride = ns * hyper_kuf_records((int)M, (int)M);
+    b.hyp_uu = ar.take<double>(b.hyp_uu_stride * (size_t)(p->P > 0 ? p->P : 1));
   }
-  if (sgpr_chol_blocked(p)) { add(chol_inverse_blocked_workspace_bytes(p->M) / sizeof(double) + 1); add(chol_inverse_blocked_workspace_bytes(p->M) / sizeof(double) + 1); }
-  return d;
+  b.chol_blocked = sgpr_chol_blocked(p);
+  if (b.chol_blocked) {
+    b.chol_ws_bytes = chol_inverse_blocked_workspace_bytes(p->M);
+    b.chol_ws_kuu = ar.take<char>(b.chol_ws_bytes);
+    b.chol_ws_b = ar.take<char>(b.chol_ws_bytes);
+  }
+  return b;
 }
 
 extern "C" {
@@ -272,7 +289,10 @@ gp_status gp_sgpr_set_precision(gp_sgpr_plan p, int32_t bits) {
   return GP_OK;
 }
 int64_t gp_sgpr_num_params(gp_sgpr_plan p) { return p ? p->nparams : 0; }
-size_t gp_sgpr_workspace_bytes(gp_sgpr_plan p) { return p ? sgpr_ws_doubles(p) * sizeof(double) + 2 * SG_DESC_BYTES + 4096 : 0; }
+size_t gp_sgpr_workspace_bytes(gp_sgpr_plan p) {
+  if (!p) return 0;
+  return gp_measure([&](GpArena& ar) { sgpr_carve(p, ar); }) + GP_WS_TAIL_OP;
+}
 
 gp_status gp_sgpr_set_workspace(gp_sgpr_plan p, void* workspace, size_t bytes) {
   if (!p) return GP_ERR_BAD_ARG;
@@ -280,36 +300,9 @@ gp_status gp_sgpr_set_workspace(gp_sgpr_plan p, void* workspace, size_t bytes) {
   if (!workspace || bytes < gp_sgpr_workspace_bytes(p) || (((uintptr_t)workspace) & 255))
     return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_sgpr_set_workspace: workspace too small or not 256-byte aligned");
   GpArena ar(workspace, bytes);
-  const size_t M = p->M, strip = gp_strip_doubles(M, p->maxN, p->f32 != 0);
-  const int rb = (p->M + 63) / 64;
-  p->d_desc = ar.take<char>(2 * SG_DESC_BYTES);
-  p->L = ar.take<double>(M * M); p->W = ar.take<double>(M * M); p->H = ar.take<double>(M * M);
-  p->LB = ar.take<double>(M * M); p->WB = ar.take<double>(M * M);
-  p->Kuf = ar.take<double>(strip); p->A = ar.take<double>(strip);
-  p->feat = ar.take<double>(sgpr_feat_stride(p) * p->P);
-  p->s1 = ar.take<double>((size_t)rb * p->maxN); p->s2 = ar.take<double>((size_t)rb * p->maxN);
-  p->dot = ar.take<double>((size_t)rb * p->maxN);
-  p->u = ar.take<double>(M); p->c = ar.take<double>(M); p->scal = ar.take<double>(64);
-  p->upart = ar.take<double>((size_t)(p->nsplit > 2 ? p->nsplit : 2) * M); p->red = ar.take<double>(2 * SG_RED_BLOCKS);
-  p->slabs = ar.take<double>((size_t)p->nsplit * M * M);
-  p->E2 = ar.take<double>(M * M); p->T1 = ar.take<double>(M * M); p->T2 = ar.take<double>(M * M);
-  p->Wbar = ar.take<double>(M * M); p->R = ar.take<double>(M * M); p->Binv = ar.take<double>(M * M);
-  p->G = ar.take<double>(strip); p->ubar = ar.take<double>(M); p->Lu = ar.take<double>(M); p->alpha = ar.take<double>(M);
-  p->ones = ar.take<double>(p->maxN);
-  {
-    const size_t ns = hyper_num_sums(p->maxm);
-    p->hyp_stride = ns * hyper_kuf_records(p->maxN, (int)M);
-    p->hyp = ar.take<double>(p->hyp_stride * (size_t)(p->P > 0 ? p->P : 1));
-    p->hyp_uu_stride = ns * hyper_kuf_records((int)M, (int)M);
-    p->hyp_uu = ar.take<double>(p->hyp_uu_stride * (size_t)(p->P > 0 ? p->P : 1));
-  }
-  p->chol_blocked = sgpr_chol_blocked(p);
-  if (p->chol_blocked) {
-    p->chol_ws_bytes = chol_inverse_blocked_workspace_bytes(p->M);
-    p->chol_ws_kuu = ar.take<char>(p->chol_ws_bytes);
-    p->chol_ws_b = ar.take<char>(p->chol_ws_bytes);
-  }
+  const SgprBufs bufs = sgpr_carve(p, ar);
   if (!ar.ok) return gp_fail(p->h, GP_ERR_WORKSPACE, "gp_sgpr_set_workspace: arena exhausted");
+  *static_cast<SgprBufs*>(p) = bufs;
   p->ws = workspace; p->ws_bytes = bytes;
   if (p->chol_blocked) {
     GP_CHECK(chol_inverse_blocked_prepare(p->h, p->L, p->W, p->M, p->M, p->chol_ws_kuu, p->chol_ws_bytes));
@@ -953,18 +946,29 @@ static gp_status sgpr_predict_f_impl(gp_sgpr_plan p, const double* params, const
   return check_not_pd(h);
 }
 
+// sgpr_predict_source_impl's workspace
+struct SgprSrcBufs { char* d_desc; double *L, *W; void* chol_ws; double *Kx, *A, *feat, *s1, *dot, *V, *scal; };
+static SgprSrcBufs sgpr_src_carve(GpArena& ar, int N, int n) {
+  SgprSrcBufs b;
+  const int64_t ld = ldN64(n);
+  const int64_t ldL = ldN64(N);      // even leading dimension: 16-byte operand loads in the GEMMs
+  const int rb = gemm_rowblocks(N, 1);
+  b.d_desc = ar.take<char>(SG_DESC_BYTES);
+  b.L = ar.take<double>((size_t)N * ldL);      // K -> L
+  b.W = ar.take<double>((size_t)N * ldL);
+  b.chol_ws = ar.take<char>(cholesky_large_workspace_bytes(N));
+  b.Kx = ar.take<double>((size_t)N * ld);
+  b.A = ar.take<double>((size_t)N * ld);
+  b.feat = ar.take<double>(kernel_build_feat_ws_doubles(32, N, n > N ? n : N));   // no plan here: the largest partial count
+  b.s1 = ar.take<double>((size_t)rb * n);
+  b.dot = ar.take<double>((size_t)rb * n);
+  b.V = ar.take<double>(N);
+  b.scal = ar.take<double>(64);
+  return b;
+}
 size_t gp_sgpr_predict_source_workspace_bytes(int32_t N, int32_t n) {
   if (N < 1 || n < 1) return 256;
-  const size_t ld = ldN64(n);
-  const int rb = gemm_rowblocks(N, 1);
-  size_t d = 0;
-  auto add = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
-  add((size_t)N * ldN64(N)); add((size_t)N * ldN64(N));     // K -> L, W
-  add((size_t)N * ld); add((size_t)N * ld);   // Kx, A
-  d += cholesky_large_workspace_bytes(N) / sizeof(double) + 64;
-  add(kernel_build_feat_ws_doubles(32, N, n > N ? n : N));
-  add((size_t)rb * n); add((size_t)rb * n); add(N); add(64);
-  return d * sizeof(double) + SG_DESC_BYTES + 4096;
+  return gp_measure([&](GpArena& ar) { sgpr_src_carve(ar, N, n); }) + GP_WS_TAIL_OP + GP_WS_TAIL_CHOL;
 }
 
 static gp_status sgpr_predict_source_impl(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
@@ -997,45 +1001,34 @@ static gp_status sgpr_predict_source_impl(gp_sgpr_plan p, const double* params, 
   if (!workspace || workspace_bytes < gp_sgpr_predict_source_workspace_bytes(N, n) || (((uintptr_t)workspace) & 255))
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgpr_predict_source: workspace too small");
   GpArena ar(workspace, workspace_bytes);
-  const int64_t ld = ldN64(n);
+  const int64_t ld = ldN64(n), ldL = ldN64(N);
   const int rb = gemm_rowblocks(N, 1);
-  char* d_desc = ar.take<char>(SG_DESC_BYTES);
-  const int64_t ldL = ldN64(N);      // even leading dimension: 16-byte operand loads in the GEMMs
-  double* L = ar.take<double>((size_t)N * ldL);
-  double* W = ar.take<double>((size_t)N * ldL);
-  void* chol_ws = ar.take<char>(cholesky_large_workspace_bytes(N));
-  double* Kx = ar.take<double>((size_t)N * ld);
-  double* A = ar.take<double>((size_t)N * ld);
-  double* feat = ar.take<double>(kernel_build_feat_ws_doubles(32, N, n > N ? n : N));
-  double* s1 = ar.take<double>((size_t)rb * n);
-  double* dot = ar.take<double>((size_t)rb * n);
-  double* V = ar.take<double>(N);
-  double* scal = ar.take<double>(64);
+  const SgprSrcBufs b = sgpr_src_carve(ar, N, n);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgpr_predict_source: arena exhausted");
   // K = K_sum(X) + sigma^2 I ; L = chol(K) ; W = L^-1 ; V = W y   (sgpr_ss.py:88-90)
   for (int i = 0; i < p->P; i++)
-    GP_CHECK(launch_kernel_build(h, sg_kern(p, params, i), X, N, nullptr, N, L, ldL, i > 0, 0.0, feat));
-  hipLaunchKernelGGL(add_diag_kernel, dim3((N + 255) / 256), dim3(256), 0, h->stream, L, N, ldL, params, 1.0, 0.0);
+    GP_CHECK(launch_kernel_build(h, sg_kern(p, params, i), X, N, nullptr, N, b.L, ldL, i > 0, 0.0, b.feat));
+  hipLaunchKernelGGL(add_diag_kernel, dim3((N + 255) / 256), dim3(256), 0, h->stream, b.L, N, ldL, params, 1.0, 0.0);
   if (N > 512) {
     // N = 2001 per window: blocked over the GEMM kernels instead of one workgroup (72 ms -> a few ms)
-    GP_CHECK(launch_cholesky_large(h, L, W, N, ldL, chol_ws, cholesky_large_workspace_bytes(N)));
+    GP_CHECK(launch_cholesky_large(h, b.L, b.W, N, ldL, b.chol_ws, cholesky_large_workspace_bytes(N)));
   } else {
-    GP_CHECK(launch_cholesky_single(h, L, N, ldL));
-    GP_CHECK(launch_tri_inverse_single(h, L, W, N, ldL));
+    GP_CHECK(launch_cholesky_single(h, b.L, N, ldL));
+    GP_CHECK(launch_tri_inverse_single(h, b.L, b.W, N, ldL));
   }
   std::vector<GemmProblem> probs(2 + (cov ? p->P : 0));
   memset(probs.data(), 0, probs.size() * sizeof(GemmProblem));
-  { GemmProblem& r = probs[0]; r.A = W; r.lda = ldL; r.M = N; r.v0 = Y; r.o0 = V; }
-  { GemmProblem& r = probs[1]; r.A = W; r.lda = ldL; r.B = Kx; r.ldb = ld; r.C = A; r.ldc = ld; r.M = N; r.N = n; r.K = N;
-    r.v0 = V; r.o0 = s1; r.o1 = dot; }
+  { GemmProblem& r = probs[0]; r.A = b.W; r.lda = ldL; r.M = N; r.v0 = Y; r.o0 = b.V; }
+  { GemmProblem& r = probs[1]; r.A = b.W; r.lda = ldL; r.B = b.Kx; r.ldb = ld; r.C = b.A; r.ldc = ld; r.M = N; r.N = n; r.K = N;
+    r.v0 = b.V; r.o0 = b.s1; r.o1 = b.dot; }
   for (int i = 0; cov && i < p->P; i++) {
     GemmProblem& r = probs[2 + i];
-    r.A = A; r.lda = ld; r.B = A; r.ldb = ld; r.C = cov + (size_t)i * n * n; r.ldc = n; r.M = n; r.N = n; r.K = N;
+    r.A = b.A; r.lda = ld; r.B = b.A; r.ldb = ld; r.C = cov + (size_t)i * n * n; r.ldc = n; r.M = n; r.N = n; r.K = N;
   }
   if (probs.size() * sizeof(GemmProblem) > SG_DESC_BYTES) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_sgpr_predict_source_full: too many kernels");
-  GP_HIP_CHECK(h, hipMemcpyAsync(d_desc, probs.data(), probs.size() * sizeof(GemmProblem), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(b.d_desc, probs.data(), probs.size() * sizeof(GemmProblem), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));   // probs is a stack object
-  GemmProblem* dp = (GemmProblem*)d_desc;
+  GemmProblem* dp = (GemmProblem*)b.d_desc;
   GP_CHECK(launch_matvec_batched(h, dp + 0, 1, N, 0));
   // kd = Kdiag of the SUM kernel (sgpr_ss.py:101), computed by the bound's finish kernel formula
   {
@@ -1053,21 +1046,21 @@ static gp_status sgpr_predict_source_impl(gp_sgpr_plan p, const double* params, 
       }
       kd += v;
     }
-    GP_HIP_CHECK(h, hipMemcpyAsync(scal, &kd, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    GP_HIP_CHECK(h, hipMemcpyAsync(b.scal, &kd, sizeof(double), hipMemcpyHostToDevice, h->stream));
     GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
   for (int i = 0; i < p->P; i++) {
     // Kx = K_i(X, Xnew); A = W Kx; mean_i = A^T V; var_i = Kdiag_sum - sum A^2   (sgpr_ss.py:92-103)
-    GP_CHECK(launch_kernel_build(h, sg_kern(p, params, i), X, N, Xnew, n, Kx, ld, 0, 0.0, feat));
+    GP_CHECK(launch_kernel_build(h, sg_kern(p, params, i), X, N, Xnew, n, b.Kx, ld, 0, 0.0, b.feat));
     GemmFlags f; f.triA = TRI_LOWER; f.big_tiles = 1; f.role = 1; f.timer = GP_TIMER_COND_A;
     f.epilogue = EPI_COLSUMSQ | EPI_COLDOT | (cov ? EPI_STORE : 0);
     GP_CHECK(launch_gemm_batched(h, dp + 1, 1, N, n, f));
-    hipLaunchKernelGGL(predict_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, dot, s1,
-                       (const double*)nullptr, rb, n, scal, mean + (size_t)i * n, var + (size_t)i * n);
+    hipLaunchKernelGGL(predict_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, b.dot, b.s1,
+                       (const double*)nullptr, rb, n, b.scal, mean + (size_t)i * n, var + (size_t)i * n);
     if (cov) {     // cov_i = K_sum(Xnew) - A^T A
       double* ci = cov + (size_t)i * n * n;
       for (int q = 0; q < p->P; q++)
-        GP_CHECK(launch_kernel_build(h, sg_kern(p, params, q), Xnew, n, nullptr, n, ci, n, q > 0, 0.0, feat));
+        GP_CHECK(launch_kernel_build(h, sg_kern(p, params, q), Xnew, n, nullptr, n, ci, n, q > 0, 0.0, b.feat));
       GemmFlags g; g.transA = 1; g.alpha = -1.0; g.beta = 1.0;
       GP_CHECK(launch_gemm_batched(h, dp + 2 + i, 1, n, n, g));
     }

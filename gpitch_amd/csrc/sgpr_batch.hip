@@ -30,6 +30,57 @@ struct SgbWin {            // per-window device pointers (device array, indexed 
   int kw, pad_;              // inducing points of this window (<= M; the rest is identity padding)
 };
 
+struct SgbPredWin {        // per-window pointers of the prediction launches
+  const double* params; double* L; int64_t ldL; double* scal;
+  const double* dot; const double* s1; const double* s2; const double* kd;
+  double* mean; double* var;
+};
+
+// The plan's three descriptor blocks: each layout function walks its regions once and yields every offset and the total.
+// (item arrays are kernel-major, [p][w]; C = windows in the block, P = kernels of the sum)
+enum SgbProb { F_A = 0, F_H, F_U, Q_BINV, Q_UBAR, Q_EH, Q_WBAR, Q_LU, Q_RANK1, Q_R, Q_ALPHA, Q_G, Q_T2, Q_LBAR, Q_P, Q_T3, Q_S, Q_COUNT };
+struct SgbDescLayout {          // bound + gradient (sgb_upload)
+  size_t win, ptr_L, ptr_W, ptr_LB, ptr_WB, M, ld, feat, cov_uu, cov_uf, hy_uf, hy_uu, fin, prob[Q_COUNT], bytes;
+};
+struct SgbPredLayout { size_t feat, cov, p1, p2, win, bytes; };                                  // gp_sgprb_predict_f
+struct SgbSrcLayout { size_t fx, fn, ck, cx, pv, pa, win, pL, pW, iM, ild, bytes; };             // gp_sgprb_predict_source
+static SgbDescLayout sgb_desc_layout(size_t C, size_t P) {
+  SgbDescLayout o;
+  GpRegions region;
+  o.win = region(C * sizeof(SgbWin));
+  o.ptr_L = region(C * sizeof(double*)); o.ptr_W = region(C * sizeof(double*));
+  o.ptr_LB = region(C * sizeof(double*)); o.ptr_WB = region(C * sizeof(double*));
+  o.M = region(C * sizeof(int)); o.ld = region(C * sizeof(int));
+  o.feat = region(2 * C * P * sizeof(FeatItem));
+  o.cov_uu = region(C * P * sizeof(CovItem)); o.cov_uf = region(C * P * sizeof(CovItem));
+  o.hy_uf = region(C * P * sizeof(HyperItem)); o.hy_uu = region(C * P * sizeof(HyperItem));
+  o.fin = region(C * P * sizeof(HyperFinishItem));
+  for (int q = 0; q < Q_COUNT; q++) o.prob[q] = region(C * sizeof(GemmProblem));
+  o.bytes = region.off;
+  return o;
+}
+static SgbPredLayout sgb_pred_layout(size_t C, size_t P) {
+  SgbPredLayout o;
+  GpRegions region;
+  o.feat = region(C * P * sizeof(FeatItem)); o.cov = region(C * P * sizeof(CovItem));
+  o.p1 = region(C * sizeof(GemmProblem)); o.p2 = region(C * sizeof(GemmProblem));
+  o.win = region(C * sizeof(SgbPredWin));
+  o.bytes = region.off;
+  return o;
+}
+static SgbSrcLayout sgb_src_layout(size_t C, size_t P) {
+  SgbSrcLayout o;
+  GpRegions region;
+  o.fx = region(C * P * sizeof(FeatItem)); o.fn = region(C * P * sizeof(FeatItem));
+  o.ck = region(C * P * sizeof(CovItem)); o.cx = region(C * P * sizeof(CovItem));
+  o.pv = region(C * sizeof(GemmProblem)); o.pa = region(C * sizeof(GemmProblem));
+  o.win = region(C * sizeof(SgbPredWin));
+  o.pL = region(C * sizeof(double*)); o.pW = region(C * sizeof(double*));
+  o.iM = region(C * sizeof(int)); o.ild = region(C * sizeof(int));
+  o.bytes = region.off;
+  return o;
+}
+
 struct gp_sgprb_plan_s {
   gp_handle h = nullptr;
   int P = 0, N = 0, M = 0, W = 0, reg = 0;
@@ -46,18 +97,14 @@ struct gp_sgprb_plan_s {
   size_t feat_stride = 0;
   double* ones = nullptr;
   int* d_toff = nullptr; int* d_ktype = nullptr; int* d_km = nullptr;
-  char* d_desc = nullptr; size_t desc_bytes = 0; std::vector<char> h_desc;
-  // descriptor offsets
-  size_t off_win = 0, off_ptr_L = 0, off_ptr_W = 0, off_ptr_LB = 0, off_ptr_WB = 0, off_M = 0, off_ld = 0;
-  size_t off_feat = 0, off_cov_uu = 0, off_cov_uf = 0, off_hy_uf = 0, off_hy_uu = 0, off_fin = 0;
-  enum { F_A = 0, F_H, F_U, Q_BINV, Q_UBAR, Q_EH, Q_WBAR, Q_LU, Q_RANK1, Q_R, Q_ALPHA, Q_G, Q_T2, Q_LBAR, Q_P, Q_T3, Q_S, Q_COUNT };
-  size_t off_prob[Q_COUNT] = {0};
+  char* d_desc = nullptr; std::vector<char> h_desc;
+  SgbDescLayout off;          // = sgb_desc_layout(W, P)
   // cache: what the uploaded descriptors describe
   const double *k_params = nullptr, *k_X = nullptr, *k_Y = nullptr, *k_Z = nullptr; double *k_grad = nullptr, *k_bound = nullptr;
   bool desc_valid = false;
   hipGraphExec_t gexec = nullptr; int graphs = 1; int64_t n_eager = 0, n_captured = 0, n_replayed = 0; int graph_count = -1;
   int np_uf = 0, np_uu = 0;
-  char* d_pred_desc = nullptr; size_t pred_desc_bytes = 0;    // descriptors of gp_sgprb_predict_f (uploaded per call)
+  char* d_pred_desc = nullptr;    // descriptors of gp_sgprb_predict_f (uploaded per call)
   std::vector<int> kw;         // inducing points per window slot (all M unless gp_sgprb_set_inducing_counts said otherwise)
   bool ragged = false;         // some kw[w] < M: the pad launches run
   ~gp_sgprb_plan_s() { if (gexec) (void)hipGraphExecDestroy(gexec); }
@@ -234,21 +281,16 @@ static void sgb_layout(gp_sgprb_plan_s* p) {
   p->win_doubles = d;
 }
 
-struct SgbPredWin;
-static size_t sgb_pred_desc_bytes(const gp_sgprb_plan_s* p);
-static size_t sgb_desc_bytes(const gp_sgprb_plan_s* p) {
-  const size_t W = p->W, P = p->P;
-  size_t b = 0;
-  auto add = [&](size_t c) { b += gp_align_up(c, 256); };
-  add(W * sizeof(SgbWin));
-  for (int i = 0; i < 4; i++) add(W * sizeof(double*));
-  add(W * sizeof(int)); add(W * sizeof(int));
-  add(2 * W * P * sizeof(FeatItem));
-  add(W * P * sizeof(CovItem)); add(W * P * sizeof(CovItem));
-  add(W * P * sizeof(HyperItem)); add(W * P * sizeof(HyperItem));
-  add(W * P * sizeof(HyperFinishItem));
-  for (int q = 0; q < gp_sgprb_plan_s::Q_COUNT; q++) add(W * sizeof(GemmProblem));
-  return b;
+// gp_sgprb_set_workspace's regions of the caller's memory, in order
+struct SgbRegions { char* desc; char* pred_desc; double* ones; int *toff, *ktype, *km; double* wsd; };
+static SgbRegions sgb_regions(const gp_sgprb_plan_s* p, GpArena& ar) {
+  SgbRegions r;
+  r.desc = ar.take<char>(sgb_desc_layout(p->W, p->P).bytes);
+  r.pred_desc = ar.take<char>(sgb_pred_layout(p->W, p->P).bytes);
+  r.ones = ar.take<double>(p->N);
+  r.toff = ar.take<int>(256); r.ktype = ar.take<int>(256); r.km = ar.take<int>(256);
+  r.wsd = ar.take<double>((size_t)p->W * p->win_doubles);
+  return r;
 }
 
 extern "C" {
@@ -288,8 +330,7 @@ int32_t gp_sgprb_num_windows(gp_sgprb_plan_t p) { return p ? p->W : 0; }
 
 size_t gp_sgprb_workspace_bytes(gp_sgprb_plan_t p) {
   if (!p) return 0;
-  return (size_t)p->W * p->win_doubles * sizeof(double) + gp_align_up((size_t)p->N * sizeof(double), 256) + 3 * 1024 +
-         sgb_desc_bytes(p) + sgb_pred_desc_bytes(p) + 8192;
+  return gp_measure([&](GpArena& ar) { sgb_regions(p, ar); }) + GP_WS_TAIL_PLAN;
 }
 
 gp_status gp_sgprb_set_workspace(gp_sgprb_plan_t p, void* workspace, size_t bytes) {
@@ -299,14 +340,11 @@ gp_status gp_sgprb_set_workspace(gp_sgprb_plan_t p, void* workspace, size_t byte
     return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_set_workspace: workspace too small or not 256-byte aligned");
   if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
   GpArena ar(workspace, bytes);
-  p->desc_bytes = sgb_desc_bytes(p);
-  p->d_desc = ar.take<char>(p->desc_bytes);
-  p->pred_desc_bytes = sgb_pred_desc_bytes(p);
-  p->d_pred_desc = ar.take<char>(p->pred_desc_bytes);
-  p->ones = ar.take<double>(p->N);
-  p->d_toff = ar.take<int>(256); p->d_ktype = ar.take<int>(256); p->d_km = ar.take<int>(256);
-  p->wsd = ar.take<double>((size_t)p->W * p->win_doubles);
+  const SgbRegions r = sgb_regions(p, ar);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_set_workspace: arena exhausted");
+  p->d_desc = r.desc; p->d_pred_desc = r.pred_desc; p->ones = r.ones;
+  p->d_toff = r.toff; p->d_ktype = r.ktype; p->d_km = r.km; p->wsd = r.wsd;
+  p->off = sgb_desc_layout(p->W, p->P);
   p->ws = workspace; p->ws_bytes = bytes;
   p->desc_valid = false;
   // constants: the all-ones column scale of Kuf_bar = R A', the kernel structure tables
@@ -326,35 +364,21 @@ gp_status gp_sgprb_set_workspace(gp_sgprb_plan_t p, void* workspace, size_t byte
 // (re)build every descriptor for the given argument pointers; uploaded once per pointer set
 static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y, const double* Z,
                             double* grad) {
-  gp_handle h = p->h;
   const int W = p->W, P = p->P, M = p->M, N = p->N;
   const int64_t ld = sgb_ld(N);
-  p->h_desc.assign(p->desc_bytes, 0);
-  size_t off = 0;
-  auto region = [&](size_t bytes) { size_t o = off; off += gp_align_up(bytes, 256); return o; };
-  p->off_win = region(W * sizeof(SgbWin));
-  p->off_ptr_L = region(W * sizeof(double*)); p->off_ptr_W = region(W * sizeof(double*));
-  p->off_ptr_LB = region(W * sizeof(double*)); p->off_ptr_WB = region(W * sizeof(double*));
-  p->off_M = region(W * sizeof(int)); p->off_ld = region(W * sizeof(int));
-  p->off_feat = region(2 * (size_t)W * P * sizeof(FeatItem));
-  p->off_cov_uu = region((size_t)W * P * sizeof(CovItem)); p->off_cov_uf = region((size_t)W * P * sizeof(CovItem));
-  p->off_hy_uf = region((size_t)W * P * sizeof(HyperItem)); p->off_hy_uu = region((size_t)W * P * sizeof(HyperItem));
-  p->off_fin = region((size_t)W * P * sizeof(HyperFinishItem));
-  for (int q = 0; q < gp_sgprb_plan_s::Q_COUNT; q++) p->off_prob[q] = region(W * sizeof(GemmProblem));
-  if (off > p->desc_bytes) return gp_fail(h, GP_ERR_WORKSPACE, "sgprb: descriptor block too small");
+  p->h_desc.assign(p->off.bytes, 0);
   char* hd = p->h_desc.data();
-  SgbWin* wins = (SgbWin*)(hd + p->off_win);
-  double** pL = (double**)(hd + p->off_ptr_L); double** pW = (double**)(hd + p->off_ptr_W);
-  double** pLB = (double**)(hd + p->off_ptr_LB); double** pWB = (double**)(hd + p->off_ptr_WB);
-  int* pM = (int*)(hd + p->off_M); int* pld = (int*)(hd + p->off_ld);
+  SgbWin* wins = (SgbWin*)(hd + p->off.win);
+  double** pL = (double**)(hd + p->off.ptr_L); double** pW = (double**)(hd + p->off.ptr_W);
+  double** pLB = (double**)(hd + p->off.ptr_LB); double** pWB = (double**)(hd + p->off.ptr_WB);
+  int* pM = (int*)(hd + p->off.M); int* pld = (int*)(hd + p->off.ld);
   // item arrays are kernel-major: [p][w], so that one launch per kernel of the sum takes a contiguous run of W items
-  FeatItem* feat = (FeatItem*)(hd + p->off_feat);
-  CovItem* cuu = (CovItem*)(hd + p->off_cov_uu); CovItem* cuf = (CovItem*)(hd + p->off_cov_uf);
-  HyperItem* hyf = (HyperItem*)(hd + p->off_hy_uf); HyperItem* hyu = (HyperItem*)(hd + p->off_hy_uu);
-  HyperFinishItem* fin = (HyperFinishItem*)(hd + p->off_fin);
+  FeatItem* feat = (FeatItem*)(hd + p->off.feat);
+  CovItem* cuu = (CovItem*)(hd + p->off.cov_uu); CovItem* cuf = (CovItem*)(hd + p->off.cov_uf);
+  HyperItem* hyf = (HyperItem*)(hd + p->off.hy_uf); HyperItem* hyu = (HyperItem*)(hd + p->off.hy_uu);
+  HyperFinishItem* fin = (HyperFinishItem*)(hd + p->off.fin);
   const size_t ns = hyper_num_sums(p->maxm);
   const size_t rec_uf = hyper_kuf_records(N, M), rec_uu = hyper_kuf_records(M, M);
-  typedef gp_sgprb_plan_s PL;
   for (int w = 0; w < W; w++) {
     double* b = p->wsd + (size_t)w * p->win_doubles;
     const double* par = params + (size_t)w * p->nparams;
@@ -367,7 +391,7 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
     sw.ubar = b + p->o_ubar; sw.grad = gw; sw.L = b + p->o_L; sw.Kuf = b + p->o_Kuf; sw.kw = kw; sw.pad_ = 0;
     pL[w] = b + p->o_L; pW[w] = b + p->o_W; pLB[w] = b + p->o_LB; pWB[w] = b + p->o_WB; pM[w] = M; pld[w] = M;
     auto prob = [&](int q) -> GemmProblem& {
-      GemmProblem& r = *((GemmProblem*)(hd + p->off_prob[q]) + w);
+      GemmProblem& r = *((GemmProblem*)(hd + p->off.prob[q]) + w);
       memset(&r, 0, sizeof(r));
       r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
       return r;
@@ -376,23 +400,23 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
            *G = b + p->o_G, *E2 = b + p->o_E2, *T1 = b + p->o_T1, *T2 = b + p->o_T2, *Wbar = b + p->o_Wbar, *R = b + p->o_R,
            *Binv = b + p->o_Binv, *ubar = b + p->o_ubar, *Lu = b + p->o_Lu, *alpha = b + p->o_alpha, *u = b + p->o_u,
            *c = b + p->o_c;
-    { GemmProblem& r = prob(PL::F_A); r.A = Wm; r.B = Kuf; r.ldb = ld; r.C = A; r.ldc = ld; r.N = N; r.o0 = b + p->o_s1; }
-    { GemmProblem& r = prob(PL::F_H); r.A = A; r.lda = ld; r.B = A; r.ldb = ld; r.C = H; r.K = N; r.o2 = b + p->o_slabs; }
-    { GemmProblem& r = prob(PL::F_U); r.A = A; r.lda = ld; r.N = N; r.v0 = Yw; r.o0 = u; }
-    { GemmProblem& r = prob(PL::Q_BINV); r.A = WB; r.B = WB; r.C = Binv; }
-    { GemmProblem& r = prob(PL::Q_UBAR); r.A = WB; r.v0 = c; r.o0 = ubar; }
-    { GemmProblem& r = prob(PL::Q_EH); r.A = E2; r.B = H; r.C = T1; }
-    { GemmProblem& r = prob(PL::Q_WBAR); r.A = T1; r.B = L; r.C = Wbar; }
-    { GemmProblem& r = prob(PL::Q_LU); r.A = L; r.v0 = u; r.o0 = Lu; }
-    { GemmProblem& r = prob(PL::Q_RANK1); r.C = Wbar; r.v0 = ubar; r.v1 = Lu; }
-    { GemmProblem& r = prob(PL::Q_R); r.A = Wm; r.B = E2; r.C = R; }
-    { GemmProblem& r = prob(PL::Q_ALPHA); r.A = Wm; r.v0 = ubar; r.o0 = alpha; }
-    { GemmProblem& r = prob(PL::Q_G); r.A = R; r.B = A; r.ldb = ld; r.N = N; r.v1 = p->ones; r.C = G; r.ldc = ld; }
-    { GemmProblem& r = prob(PL::Q_T2); r.A = Wm; r.B = Wbar; r.C = T2; }
-    { GemmProblem& r = prob(PL::Q_LBAR); r.A = T2; r.B = Wm; r.C = T1; }
-    { GemmProblem& r = prob(PL::Q_P); r.A = L; r.B = T1; r.C = T2; }
-    { GemmProblem& r = prob(PL::Q_T3); r.A = Wm; r.B = T2; r.C = H; }
-    { GemmProblem& r = prob(PL::Q_S); r.A = H; r.B = Wm; r.C = E2; }
+    { GemmProblem& r = prob(F_A); r.A = Wm; r.B = Kuf; r.ldb = ld; r.C = A; r.ldc = ld; r.N = N; r.o0 = b + p->o_s1; }
+    { GemmProblem& r = prob(F_H); r.A = A; r.lda = ld; r.B = A; r.ldb = ld; r.C = H; r.K = N; r.o2 = b + p->o_slabs; }
+    { GemmProblem& r = prob(F_U); r.A = A; r.lda = ld; r.N = N; r.v0 = Yw; r.o0 = u; }
+    { GemmProblem& r = prob(Q_BINV); r.A = WB; r.B = WB; r.C = Binv; }
+    { GemmProblem& r = prob(Q_UBAR); r.A = WB; r.v0 = c; r.o0 = ubar; }
+    { GemmProblem& r = prob(Q_EH); r.A = E2; r.B = H; r.C = T1; }
+    { GemmProblem& r = prob(Q_WBAR); r.A = T1; r.B = L; r.C = Wbar; }
+    { GemmProblem& r = prob(Q_LU); r.A = L; r.v0 = u; r.o0 = Lu; }
+    { GemmProblem& r = prob(Q_RANK1); r.C = Wbar; r.v0 = ubar; r.v1 = Lu; }
+    { GemmProblem& r = prob(Q_R); r.A = Wm; r.B = E2; r.C = R; }
+    { GemmProblem& r = prob(Q_ALPHA); r.A = Wm; r.v0 = ubar; r.o0 = alpha; }
+    { GemmProblem& r = prob(Q_G); r.A = R; r.B = A; r.ldb = ld; r.N = N; r.v1 = p->ones; r.C = G; r.ldc = ld; }
+    { GemmProblem& r = prob(Q_T2); r.A = Wm; r.B = Wbar; r.C = T2; }
+    { GemmProblem& r = prob(Q_LBAR); r.A = T2; r.B = Wm; r.C = T1; }
+    { GemmProblem& r = prob(Q_P); r.A = L; r.B = T1; r.C = T2; }
+    { GemmProblem& r = prob(Q_T3); r.A = Wm; r.B = T2; r.C = H; }
+    { GemmProblem& r = prob(Q_S); r.A = H; r.B = Wm; r.C = E2; }
     for (int i = 0; i < P; i++) {
       DevKern k{p->ktype[i], p->m[i], par + p->off_theta[i]};
       double* ft = b + p->o_feat + (size_t)i * p->feat_stride;
@@ -427,12 +451,11 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
 static gp_status sgb_enqueue(gp_sgprb_plan_t p, int count, double* bound_dev, bool with_grad) {
   gp_handle h = p->h;
   const int W = count, P = p->P, M = p->M, N = p->N;
-  typedef gp_sgprb_plan_s PL;
   char* dd = p->d_desc;
-  const SgbWin* wins = (const SgbWin*)(dd + p->off_win);
-  auto D = [&](int q) { return (const GemmProblem*)(dd + p->off_prob[q]); };
-  const FeatItem* feat = (const FeatItem*)(dd + p->off_feat);
-  const CovItem* cuu = (const CovItem*)(dd + p->off_cov_uu); const CovItem* cuf = (const CovItem*)(dd + p->off_cov_uf);
+  const SgbWin* wins = (const SgbWin*)(dd + p->off.win);
+  auto D = [&](int q) { return (const GemmProblem*)(dd + p->off.prob[q]); };
+  const FeatItem* feat = (const FeatItem*)(dd + p->off.feat);
+  const CovItem* cuu = (const CovItem*)(dd + p->off.cov_uu); const CovItem* cuf = (const CovItem*)(dd + p->off.cov_uf);
   // items are kernel-major with stride p->W; a partial batch (count < W) takes the first `count` of each run
   for (int i = 0; i < P; i++) {
     if (gp_kern_is_mercer(p->ktype[i])) {
@@ -443,19 +466,19 @@ static gp_status sgb_enqueue(gp_sgprb_plan_t p, int count, double* bound_dev, bo
     GP_CHECK(launch_kernel_build_items(h, p->ktype[i], p->m[i], cuu + (size_t)i * p->W, W, M, M, nullptr, 0));
   }
   if (p->ragged) hipLaunchKernelGGL(sgb_kuu_pad_kernel, dim3(16, W), dim3(256), 0, h->stream, wins, M);
-  GP_CHECK(launch_cholesky_inverse_batched(h, (double* const*)(dd + p->off_ptr_L), (double* const*)(dd + p->off_ptr_W),
-                                           (const int*)(dd + p->off_M), (const int*)(dd + p->off_ld), W, M));
+  GP_CHECK(launch_cholesky_inverse_batched(h, (double* const*)(dd + p->off.ptr_L), (double* const*)(dd + p->off.ptr_W),
+                                           (const int*)(dd + p->off.M), (const int*)(dd + p->off.ld), W, M));
   for (int i = 0; i < P; i++)
     GP_CHECK(launch_kernel_build_items(h, p->ktype[i], p->m[i], cuf + (size_t)i * p->W, W, M, N, nullptr, 0));
   { GemmFlags f; f.triA = TRI_LOWER; f.big_tiles = (M > 64); f.role = (M > 64) ? 1 : 0; f.timer = GP_TIMER_COND_A;
     f.epilogue = EPI_STORE | EPI_COLSUMSQ;
-    GP_CHECK(launch_gemm_batched(h, D(PL::F_A), W, M, N, f)); }
+    GP_CHECK(launch_gemm_batched(h, D(F_A), W, M, N, f)); }
   hipLaunchKernelGGL(sgb_pre_kernel, dim3(W), dim3(256), 0, h->stream, wins, N, p->rb);
-  GP_CHECK(launch_gemm_nt_reduce_batched(h, D(PL::F_H), W, M, N, p->nsplit, 1, 0, 1.0));
-  GP_CHECK(launch_rowdot_batched(h, D(PL::F_U), W, M));
+  GP_CHECK(launch_gemm_nt_reduce_batched(h, D(F_H), W, M, N, p->nsplit, 1, 0, 1.0));
+  GP_CHECK(launch_rowdot_batched(h, D(F_U), W, M));
   hipLaunchKernelGGL(sgb_B_kernel, dim3(16, W), dim3(256), 0, h->stream, wins, M);
-  GP_CHECK(launch_cholesky_inverse_batched(h, (double* const*)(dd + p->off_ptr_LB), (double* const*)(dd + p->off_ptr_WB),
-                                           (const int*)(dd + p->off_M), (const int*)(dd + p->off_ld), W, M));
+  GP_CHECK(launch_cholesky_inverse_batched(h, (double* const*)(dd + p->off.ptr_LB), (double* const*)(dd + p->off.ptr_WB),
+                                           (const int*)(dd + p->off.M), (const int*)(dd + p->off.ld), W, M));
   hipLaunchKernelGGL(sgb_finish_kernel, dim3(W), dim3(256), 0, h->stream, wins, M, N, P, p->d_toff, p->d_ktype, p->d_km,
                      p->reg, bound_dev);
   GP_HIP_CHECK(h, hipGetLastError());
@@ -463,35 +486,35 @@ static gp_status sgb_enqueue(gp_sgprb_plan_t p, int count, double* bound_dev, bo
   // ---- backward (sgpr.hip: sgpr_backward, window-batched) ----
   GemmFlags f;
   f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_BINV), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(PL::Q_UBAR), W, M, 1));
+  GP_CHECK(launch_gemm_batched(h, D(Q_BINV), W, M, M, f));
+  GP_CHECK(launch_matvec_batched(h, D(Q_UBAR), W, M, 1));
   hipLaunchKernelGGL(sgb_E2_kernel, dim3(16, W), dim3(256), 0, h->stream, wins, M);
   hipLaunchKernelGGL(sgb_noise_grad_kernel, dim3(W), dim3(256), 0, h->stream, wins, M, N, p->nparams, P, p->d_toff, p->reg);
   f = GemmFlags();
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_EH), W, M, M, f));
+  GP_CHECK(launch_gemm_batched(h, D(Q_EH), W, M, M, f));
   f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_WBAR), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(PL::Q_LU), W, M, 0));
-  GP_CHECK(launch_rank1_tril_batched(h, D(PL::Q_RANK1), W, M));
+  GP_CHECK(launch_gemm_batched(h, D(Q_WBAR), W, M, M, f));
+  GP_CHECK(launch_matvec_batched(h, D(Q_LU), W, M, 0));
+  GP_CHECK(launch_rank1_tril_batched(h, D(Q_RANK1), W, M));
   f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_R), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(PL::Q_ALPHA), W, M, 1));
+  GP_CHECK(launch_gemm_batched(h, D(Q_R), W, M, M, f));
+  GP_CHECK(launch_matvec_batched(h, D(Q_ALPHA), W, M, 1));
   f = GemmFlags(); f.big_tiles = (M > 64); f.scale_mode = 1; f.timer = GP_TIMER_KUF_BAR; f.role = (M > 64) ? 3 : 0;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_G), W, M, N, f));
+  GP_CHECK(launch_gemm_batched(h, D(Q_G), W, M, N, f));
   f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_T2), W, M, M, f));
+  GP_CHECK(launch_gemm_batched(h, D(Q_T2), W, M, M, f));
   f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_LBAR), W, M, M, f));
+  GP_CHECK(launch_gemm_batched(h, D(Q_LBAR), W, M, M, f));
   f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_P), W, M, M, f));
-  GP_CHECK(launch_phi_batched(h, D(PL::Q_P), W, M));
+  GP_CHECK(launch_gemm_batched(h, D(Q_P), W, M, M, f));
+  GP_CHECK(launch_phi_batched(h, D(Q_P), W, M));
   f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_T3), W, M, M, f));
+  GP_CHECK(launch_gemm_batched(h, D(Q_T3), W, M, M, f));
   f = GemmFlags(); f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(PL::Q_S), W, M, M, f));
-  const HyperItem* hyf = (const HyperItem*)(dd + p->off_hy_uf);
-  const HyperItem* hyu = (const HyperItem*)(dd + p->off_hy_uu);
-  const HyperFinishItem* fin = (const HyperFinishItem*)(dd + p->off_fin);
+  GP_CHECK(launch_gemm_batched(h, D(Q_S), W, M, M, f));
+  const HyperItem* hyf = (const HyperItem*)(dd + p->off.hy_uf);
+  const HyperItem* hyu = (const HyperItem*)(dd + p->off.hy_uu);
+  const HyperFinishItem* fin = (const HyperFinishItem*)(dd + p->off.fin);
   int maxblocks = 0;
   for (int i = 0; i < P; i++) {
     int a = 0, b2 = 0;
@@ -562,12 +585,12 @@ gp_status gp_sgprb_bound_grad(gp_sgprb_plan_t p, const double* params, const dou
       const int wr_uf = ((int64_t)p->M * p->N >= (1 << 20)) ? 32 : 8, wr_uu = ((int64_t)p->M * p->M >= (1 << 20)) ? 32 : 8;
       p->np_uf = ((p->N + 255) / 256) * ((p->M + wr_uf - 1) / wr_uf);
       p->np_uu = ((p->M + 255) / 256) * ((p->M + wr_uu - 1) / wr_uu);
-      HyperFinishItem* fin = (HyperFinishItem*)(p->h_desc.data() + p->off_fin);
+      HyperFinishItem* fin = (HyperFinishItem*)(p->h_desc.data() + p->off.fin);
       for (size_t i = 0; i < (size_t)p->W * p->P; i++) { fin[i].np_uf = p->np_uf; fin[i].np_uu = p->np_uu; }
     }
-    GP_HIP_CHECK(h, hipMemcpyAsync(p->d_desc, p->h_desc.data(), p->desc_bytes, hipMemcpyHostToDevice, h->stream));
+    GP_HIP_CHECK(h, hipMemcpyAsync(p->d_desc, p->h_desc.data(), p->off.bytes, hipMemcpyHostToDevice, h->stream));
     if (p->ragged) {      // pad rows of the Kuf strips: zero from here on (the builds write the kw real rows only)
-      hipLaunchKernelGGL(sgb_kuf_pad_kernel, dim3(64, p->W), dim3(256), 0, h->stream, (const SgbWin*)(p->d_desc + p->off_win),
+      hipLaunchKernelGGL(sgb_kuf_pad_kernel, dim3(64, p->W), dim3(256), 0, h->stream, (const SgbWin*)(p->d_desc + p->off.win),
                          p->M, sgb_ld(p->N));
       GP_HIP_CHECK(h, hipGetLastError());
     }
@@ -622,12 +645,6 @@ gp_status gp_sgprb_bound_grad(gp_sgprb_plan_t p, const double* params, const dou
 // Same kernels and operation order per window as gp_sgpr_predict_f / gp_sgpr_predict_source (sgpr.hip); what changes is
 // that every launch carries all windows: one window's predict_s is ~100 dependent launches of small grids (7 ms, nearly
 // all latency), W windows cost the arithmetic.
-struct SgbPredWin {
-  const double* params; double* L; int64_t ldL; double* scal;
-  const double* dot; const double* s1; const double* s2; const double* kd;
-  double* mean; double* var;
-};
-
 // L[i][i] += noise variance; scal[0] = Kdiag of the SUM kernel (sgpr_ss.py:101)
 __global__ void __launch_bounds__(256) sgb_pred_prep_kernel(const SgbPredWin* __restrict__ wins, int N, int P,
                                                             const int* __restrict__ toff, const int* __restrict__ ktype,
@@ -668,12 +685,6 @@ __global__ void __launch_bounds__(256) sgb_pred_finish_kernel(const SgbPredWin* 
 }
 
 static inline int64_t sgb_ld64(int n) { return (n + 1) & ~1; }
-static size_t sgb_pred_desc_bytes(const gp_sgprb_plan_s* p) {
-  const size_t W = p->W, P = p->P;
-  return gp_align_up(W * P * sizeof(FeatItem), 256) + gp_align_up(W * P * sizeof(CovItem), 256) +
-         2 * gp_align_up(W * sizeof(GemmProblem), 256) + gp_align_up(W * sizeof(SgbPredWin), 256);
-}
-
 extern "C" {
 
 // mean, var: [count][n].  Xnew: [count][n], n <= N.  Runs the forward pass of the bound at `params` first (same descriptors
@@ -692,20 +703,13 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
   // window's G strip, which a forward-only evaluation leaves free and which the prediction overwrites afterwards.)
   GP_CHECK(gp_sgprb_bound_grad(p, params, X, Y, Z, count, p->wsd + p->o_G, nullptr));
   // descriptors of the prediction launches (host-built, uploaded per call: predictions are not in the training loop)
-  const size_t nfeat = (size_t)W * P, ncov = (size_t)W * P;
-  const size_t bytes = gp_align_up(nfeat * sizeof(FeatItem), 256) + gp_align_up(ncov * sizeof(CovItem), 256) +
-                       2 * gp_align_up((size_t)W * sizeof(GemmProblem), 256) + gp_align_up((size_t)W * sizeof(SgbPredWin), 256);
-  std::vector<char> hd(bytes, 0);
-  size_t off = 0;
-  auto region = [&](size_t b) { size_t o = off; off += gp_align_up(b, 256); return o; };
-  const size_t o_feat = region(nfeat * sizeof(FeatItem)), o_cov = region(ncov * sizeof(CovItem));
-  const size_t o_p1 = region((size_t)W * sizeof(GemmProblem)), o_p2 = region((size_t)W * sizeof(GemmProblem));
-  const size_t o_win = region((size_t)W * sizeof(SgbPredWin));
-  FeatItem* feat = (FeatItem*)(hd.data() + o_feat);
-  CovItem* cov = (CovItem*)(hd.data() + o_cov);
-  GemmProblem* p1 = (GemmProblem*)(hd.data() + o_p1);
-  GemmProblem* p2 = (GemmProblem*)(hd.data() + o_p2);
-  SgbPredWin* wins = (SgbPredWin*)(hd.data() + o_win);
+  const SgbPredLayout lay = sgb_pred_layout(W, P);      // count <= num_windows: inside the block the plan holds
+  std::vector<char> hd(lay.bytes, 0);
+  FeatItem* feat = (FeatItem*)(hd.data() + lay.feat);
+  CovItem* cov = (CovItem*)(hd.data() + lay.cov);
+  GemmProblem* p1 = (GemmProblem*)(hd.data() + lay.p1);
+  GemmProblem* p2 = (GemmProblem*)(hd.data() + lay.p2);
+  SgbPredWin* wins = (SgbPredWin*)(hd.data() + lay.win);
   for (int w = 0; w < W; w++) {
     double* b = p->wsd + (size_t)w * p->win_doubles;
     const double* par = params + (size_t)w * p->nparams;
@@ -735,12 +739,11 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
     sw.params = par; sw.dot = dot; sw.s1 = s1; sw.s2 = s2; sw.kd = b + p->o_scal + 3;
     sw.mean = mean + (size_t)w * n; sw.var = var + (size_t)w * n;
   }
-  if (bytes > p->pred_desc_bytes) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_predict_f: descriptor block too small");
   char* dd = p->d_pred_desc;
-  GP_HIP_CHECK(h, hipMemcpyAsync(dd, hd.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(dd, hd.data(), lay.bytes, hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // hd is a stack object
-  const FeatItem* dfeat = (const FeatItem*)(dd + o_feat);
-  const CovItem* dcov = (const CovItem*)(dd + o_cov);
+  const FeatItem* dfeat = (const FeatItem*)(dd + lay.feat);
+  const CovItem* dcov = (const CovItem*)(dd + lay.cov);
   for (int i = 0; i < P; i++) {
     if (gp_kern_is_mercer(p->ktype[i]))
       GP_CHECK(launch_sm_features_items(h, dfeat + (size_t)i * W, W, n, sm_mpad(p->m[i]), nullptr, 0));
@@ -748,33 +751,41 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
   }
   { GemmFlags f; f.triA = TRI_LOWER; f.big_tiles = (M > 64); f.role = (M > 64) ? 1 : 0; f.timer = GP_TIMER_COND_A;
     f.epilogue = EPI_STORE | EPI_COLSUMSQ;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(dd + o_p1), W, M, n, f)); }
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(dd + lay.p1), W, M, n, f)); }
   { GemmFlags f; f.triA = TRI_LOWER; f.big_tiles = (M > 64); f.role = (M > 64) ? 1 : 0; f.timer = GP_TIMER_COND_A;
     f.epilogue = EPI_COLSUMSQ | EPI_COLDOT;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(dd + o_p2), W, M, n, f)); }
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(dd + lay.p2), W, M, n, f)); }
   hipLaunchKernelGGL(sgb_pred_finish_kernel, dim3((n + 255) / 256, W), dim3(256), 0, h->stream,
-                     (const SgbPredWin*)(dd + o_win), rb, n, (int64_t)0);
+                     (const SgbPredWin*)(dd + lay.win), rb, n, (int64_t)0);
   GP_HIP_CHECK(h, hipGetLastError());
   // (the frame halves of the feature tables and the Kuf strips now hold Xnew's: every evaluation rebuilds them first)
   return check_not_pd(h);
 }
 
-size_t gp_sgprb_predict_source_workspace_bytes(gp_sgprb_plan_t p, int32_t count, int32_t n) {
-  if (!p || count < 1 || n < 1) return 256;
+// gp_sgprb_predict_source's workspace: descriptor block, the batched factorisation's own, then per window
+// K -> L, W = L^-1, K_p(X, Xnew), one feature table, the two [rb][n] partials, V = W y and the scalars
+struct SgbSrcWin { double *L, *W, *Kx, *feat, *s1, *dot, *V, *scal; };
+struct SgbSrcRegions { char* desc; void* chol_ws; std::vector<SgbSrcWin> win; };
+static SgbSrcRegions sgb_src_regions(const gp_sgprb_plan_s* p, GpArena& ar, int count, int n) {
+  SgbSrcRegions r;
   const int N = p->N;
   const size_t ldL = sgb_ld64(N), ld = sgb_ld64(n);
   const int rb = gemm_rowblocks(N, 1);
-  size_t d = 0;
-  auto add = [&](size_t c) { d += gp_align_up(c * sizeof(double), 256) / sizeof(double); };
-  add((size_t)N * ldL); add((size_t)N * ldL);     // K -> L, W = L^-1
-  add((size_t)N * ld);                            // K_p(X, Xnew)
-  add(kernel_build_feat_ws_doubles(p->maxm > 0 ? p->maxm : 1, N, n > N ? n : N));
-  add((size_t)rb * n); add((size_t)rb * n); add(N); add(64);
-  const size_t C = (size_t)count, P = p->P;
-  size_t desc = 2 * gp_align_up(C * P * sizeof(FeatItem), 256) + 2 * gp_align_up(C * P * sizeof(CovItem), 256) +
-                2 * gp_align_up(C * sizeof(GemmProblem), 256) + gp_align_up(C * sizeof(SgbPredWin), 256) +
-                2 * gp_align_up(C * sizeof(double*), 256) + 2 * gp_align_up(C * sizeof(int), 256);
-  return C * d * sizeof(double) + desc + cholesky_large_batched_workspace_bytes(N, count) + 8192;
+  r.desc = ar.take<char>(sgb_src_layout(count, p->P).bytes);
+  r.chol_ws = ar.take<char>(cholesky_large_batched_workspace_bytes(N, count));
+  r.win.resize(count);
+  for (SgbSrcWin& w : r.win) {
+    w.L = ar.take<double>((size_t)N * ldL); w.W = ar.take<double>((size_t)N * ldL);
+    w.Kx = ar.take<double>((size_t)N * ld);
+    w.feat = ar.take<double>(kernel_build_feat_ws_doubles(p->maxm > 0 ? p->maxm : 1, N, n > N ? n : N));
+    w.s1 = ar.take<double>((size_t)rb * n); w.dot = ar.take<double>((size_t)rb * n);
+    w.V = ar.take<double>(N); w.scal = ar.take<double>(64);
+  }
+  return r;
+}
+size_t gp_sgprb_predict_source_workspace_bytes(gp_sgprb_plan_t p, int32_t count, int32_t n) {
+  if (!p || count < 1 || n < 1) return 256;
+  return gp_measure([&](GpArena& ar) { sgb_src_regions(p, ar, count, n); }) + GP_WS_TAIL_PLAN;
 }
 
 // mean, var: [count][P][n] (window-major, then source).  Xnew: [count][n].
@@ -792,63 +803,46 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan_t p, const double* params, const
   const int64_t ldL = sgb_ld64(N), ld = sgb_ld64(n);
   const int rb = gemm_rowblocks(N, 1);
   GpArena ar(workspace, workspace_bytes);
-  const size_t C = (size_t)W;
-  // descriptor block
-  const size_t b_feat = gp_align_up(C * P * sizeof(FeatItem), 256), b_cov = gp_align_up(C * P * sizeof(CovItem), 256),
-               b_prob = gp_align_up(C * sizeof(GemmProblem), 256), b_win = gp_align_up(C * sizeof(SgbPredWin), 256),
-               b_ptr = gp_align_up(C * sizeof(double*), 256), b_int = gp_align_up(C * sizeof(int), 256);
-  const size_t desc_bytes = 2 * b_feat + 2 * b_cov + 2 * b_prob + b_win + 2 * b_ptr + 2 * b_int;
-  char* dd = ar.take<char>(desc_bytes);
-  void* chol_ws = ar.take<char>(cholesky_large_batched_workspace_bytes(N, W));
-  const size_t featd = gp_align_up(kernel_build_feat_ws_doubles(p->maxm > 0 ? p->maxm : 1, N, n > N ? n : N) * sizeof(double), 256) / sizeof(double);
-  std::vector<double*> hL(W), hW(W);
-  std::vector<double*> hKx(W), hfeat(W), hs1(W), hdot(W), hV(W), hscal(W);
-  for (int w = 0; w < W; w++) {
-    hL[w] = ar.take<double>((size_t)N * ldL); hW[w] = ar.take<double>((size_t)N * ldL);
-    hKx[w] = ar.take<double>((size_t)N * ld); hfeat[w] = ar.take<double>(featd);
-    hs1[w] = ar.take<double>((size_t)rb * n); hdot[w] = ar.take<double>((size_t)rb * n);
-    hV[w] = ar.take<double>(N); hscal[w] = ar.take<double>(64);
-  }
+  const SgbSrcRegions reg = sgb_src_regions(p, ar, W, n);
   if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_predict_source: arena exhausted");
-  std::vector<char> hd(desc_bytes, 0);
-  size_t off = 0;
-  auto region = [&](size_t b) { size_t o = off; off += b; return o; };
-  const size_t o_fx = region(b_feat), o_fn = region(b_feat), o_ck = region(b_cov), o_cx = region(b_cov),
-               o_pv = region(b_prob), o_pa = region(b_prob), o_win = region(b_win), o_pL = region(b_ptr), o_pW = region(b_ptr),
-               o_iM = region(b_int), o_ild = region(b_int);
-  FeatItem* fx = (FeatItem*)(hd.data() + o_fx); FeatItem* fn = (FeatItem*)(hd.data() + o_fn);
-  CovItem* ck = (CovItem*)(hd.data() + o_ck); CovItem* cx = (CovItem*)(hd.data() + o_cx);
-  GemmProblem* pv = (GemmProblem*)(hd.data() + o_pv); GemmProblem* pa = (GemmProblem*)(hd.data() + o_pa);
-  SgbPredWin* wins = (SgbPredWin*)(hd.data() + o_win);
-  double** pL = (double**)(hd.data() + o_pL); double** pW = (double**)(hd.data() + o_pW);
-  int* iM = (int*)(hd.data() + o_iM); int* ild = (int*)(hd.data() + o_ild);
+  std::vector<double*> hL(W), hW(W);     // host pointer arrays of the batched factorisation
+  for (int w = 0; w < W; w++) { hL[w] = reg.win[w].L; hW[w] = reg.win[w].W; }
+  const SgbSrcLayout lay = sgb_src_layout(W, P);
+  std::vector<char> hd(lay.bytes, 0);
+  FeatItem* fx = (FeatItem*)(hd.data() + lay.fx); FeatItem* fn = (FeatItem*)(hd.data() + lay.fn);
+  CovItem* ck = (CovItem*)(hd.data() + lay.ck); CovItem* cx = (CovItem*)(hd.data() + lay.cx);
+  GemmProblem* pv = (GemmProblem*)(hd.data() + lay.pv); GemmProblem* pa = (GemmProblem*)(hd.data() + lay.pa);
+  SgbPredWin* wins = (SgbPredWin*)(hd.data() + lay.win);
+  double** pL = (double**)(hd.data() + lay.pL); double** pW = (double**)(hd.data() + lay.pW);
+  int* iM = (int*)(hd.data() + lay.iM); int* ild = (int*)(hd.data() + lay.ild);
   for (int w = 0; w < W; w++) {
+    const SgbSrcWin& b = reg.win[w];
     const double* par = params + (size_t)w * p->nparams;
     const double* Xw = X + (size_t)w * N; const double* Yw = Y + (size_t)w * N; const double* Xn = Xnew + (size_t)w * n;
     for (int i = 0; i < P; i++) {
       DevKern k{p->ktype[i], p->m[i], par + p->off_theta[i]};
       const int mp = sm_mpad(k.m);
       const size_t idx = (size_t)i * W + w;
-      double* ft = hfeat[w];         // one table per window, rebuilt for every kernel of the sum (launches are ordered)
+      double* ft = b.feat;         // one table per window, rebuilt for every kernel of the sum (launches are ordered)
       fx[idx] = FeatItem{k, Xw, ft, N, 0};
       fn[idx] = FeatItem{k, Xn, ft + gp_align_up((size_t)2 * mp * N, 32), n, 0};
       cov_item_fill(&ck[idx], k, Xw, N, nullptr, N, hL[w], ldL, i > 0, 0.0, ft);
-      cov_item_fill(&cx[idx], k, Xw, N, Xn, n, hKx[w], ld, 0, 0.0, ft);
+      cov_item_fill(&cx[idx], k, Xw, N, Xn, n, b.Kx, ld, 0, 0.0, ft);
     }
-    { GemmProblem& r = pv[w]; memset(&r, 0, sizeof(r)); r.A = hW[w]; r.lda = ldL; r.M = N; r.v0 = Yw; r.o0 = hV[w]; }
+    { GemmProblem& r = pv[w]; memset(&r, 0, sizeof(r)); r.A = hW[w]; r.lda = ldL; r.M = N; r.v0 = Yw; r.o0 = b.V; }
     { GemmProblem& r = pa[w]; memset(&r, 0, sizeof(r));
-      r.A = hW[w]; r.lda = ldL; r.B = hKx[w]; r.ldb = ld; r.M = N; r.N = n; r.K = N; r.v0 = hV[w]; r.o0 = hs1[w]; r.o1 = hdot[w]; }
+      r.A = hW[w]; r.lda = ldL; r.B = b.Kx; r.ldb = ld; r.M = N; r.N = n; r.K = N; r.v0 = b.V; r.o0 = b.s1; r.o1 = b.dot; }
     SgbPredWin& sw = wins[w];
     memset(&sw, 0, sizeof(sw));
-    sw.params = par; sw.L = hL[w]; sw.ldL = ldL; sw.scal = hscal[w]; sw.dot = hdot[w]; sw.s1 = hs1[w]; sw.s2 = nullptr;
-    sw.kd = hscal[w]; sw.mean = mean + (size_t)w * P * n; sw.var = var + (size_t)w * P * n;
+    sw.params = par; sw.L = hL[w]; sw.ldL = ldL; sw.scal = b.scal; sw.dot = b.dot; sw.s1 = b.s1; sw.s2 = nullptr;
+    sw.kd = b.scal; sw.mean = mean + (size_t)w * P * n; sw.var = var + (size_t)w * P * n;
     pL[w] = hL[w]; pW[w] = hW[w]; iM[w] = N; ild[w] = (int)ldL;
   }
-  GP_HIP_CHECK(h, hipMemcpyAsync(dd, hd.data(), desc_bytes, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(reg.desc, hd.data(), lay.bytes, hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // hd is a stack object
-  const FeatItem* dfx = (const FeatItem*)(dd + o_fx); const FeatItem* dfn = (const FeatItem*)(dd + o_fn);
-  const CovItem* dck = (const CovItem*)(dd + o_ck); const CovItem* dcx = (const CovItem*)(dd + o_cx);
-  const SgbPredWin* dwins = (const SgbPredWin*)(dd + o_win);
+  const FeatItem* dfx = (const FeatItem*)(reg.desc + lay.fx); const FeatItem* dfn = (const FeatItem*)(reg.desc + lay.fn);
+  const CovItem* dck = (const CovItem*)(reg.desc + lay.ck); const CovItem* dcx = (const CovItem*)(reg.desc + lay.cx);
+  const SgbPredWin* dwins = (const SgbPredWin*)(reg.desc + lay.win);
   // K = K_sum(X) + s2 I ; L = chol(K) ; W = L^-1 ; V = W y   (sgpr_ss.py:88-90)
   for (int i = 0; i < P; i++) {
     if (gp_kern_is_mercer(p->ktype[i]))
@@ -858,13 +852,13 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan_t p, const double* params, const
   hipLaunchKernelGGL(sgb_pred_prep_kernel, dim3(W), dim3(256), 0, h->stream, dwins, N, P, p->d_toff, p->d_ktype, p->d_km);
   GP_HIP_CHECK(h, hipGetLastError());
   if (N > 512) {
-    GP_CHECK(launch_cholesky_large_batched(h, hL.data(), hW.data(), W, N, ldL, chol_ws, cholesky_large_batched_workspace_bytes(N, W)));
+    GP_CHECK(launch_cholesky_large_batched(h, hL.data(), hW.data(), W, N, ldL, reg.chol_ws, cholesky_large_batched_workspace_bytes(N, W)));
   } else {
-    GP_CHECK(launch_cholesky_batched(h, (double* const*)(dd + o_pL), (const int*)(dd + o_iM), (const int*)(dd + o_ild), W, N, 0));
-    GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)(dd + o_pL), (double* const*)(dd + o_pW), (const int*)(dd + o_iM),
-                                        (const int*)(dd + o_ild), W));
+    GP_CHECK(launch_cholesky_batched(h, (double* const*)(reg.desc + lay.pL), (const int*)(reg.desc + lay.iM), (const int*)(reg.desc + lay.ild), W, N, 0));
+    GP_CHECK(launch_tri_inverse_batched(h, (const double* const*)(reg.desc + lay.pL), (double* const*)(reg.desc + lay.pW), (const int*)(reg.desc + lay.iM),
+                                        (const int*)(reg.desc + lay.ild), W));
   }
-  GP_CHECK(launch_matvec_batched(h, (const GemmProblem*)(dd + o_pv), W, N, 0));
+  GP_CHECK(launch_matvec_batched(h, (const GemmProblem*)(reg.desc + lay.pv), W, N, 0));
   for (int i = 0; i < P; i++) {
     // Kx = K_i(X, Xnew); A = W Kx (never stored); mean_i = A^T V; var_i = Kdiag_sum - sum A^2   (sgpr_ss.py:92-103)
     if (gp_kern_is_mercer(p->ktype[i])) {
@@ -874,7 +868,7 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan_t p, const double* params, const
     GP_CHECK(launch_kernel_build_items(h, p->ktype[i], p->m[i], dcx + (size_t)i * W, W, N, n, nullptr, 0));
     GemmFlags f; f.triA = TRI_LOWER; f.big_tiles = 1; f.role = 1; f.timer = GP_TIMER_COND_A;
     f.epilogue = EPI_COLSUMSQ | EPI_COLDOT;
-    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(dd + o_pa), W, N, n, f));
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(reg.desc + lay.pa), W, N, n, f));
     hipLaunchKernelGGL(sgb_pred_finish_kernel, dim3((n + 255) / 256, W), dim3(256), 0, h->stream, dwins, rb, n, (int64_t)i * n);
     GP_HIP_CHECK(h, hipGetLastError());
   }
