@@ -342,6 +342,16 @@ gp_status launch_sm_features_items(gp_handle h, const FeatItem* d_items, int cou
 // aligned output, leading dimension gp_strip_ld) — what the lean Mercer form needs to know on the host
 gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem* d_items, int count, int max_n1,
                                     int max_n2, const double* x2_shared, int n2_shared, int engine_strips = 0);
+// predict_sparse.hip: the sparse per-source posterior (gp_sgpr_predict_source_sparse), one fused launch over
+// (frame tile, source, window).  One item per (source, window), kernel-major [P][nwin]: the window's forward state
+// (W = chol(Kuu)^-1 and WB = chol(B)^-1 with leading dimension ldw, c), its kz inducing points z with the kernel's feature
+// table fz ([2 sm_mpad(m)][kz], Mercer kernels only), the window's n new frames and the source's two output rows.
+#define SPS_MAX_M 1024
+struct SrcSparseItem {
+  DevKern k; const double* z; const double* fz; const double* W; const double* WB; const double* c;
+  const double* xnew; double* mean; double* var; int kz, ldw;
+};
+gp_status launch_sgpr_source_sparse(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n, int max_mpad);
 gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int64_t ldy, int n, int square, double* out);
 // lik.hip
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)

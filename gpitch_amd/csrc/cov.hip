@@ -11,6 +11,7 @@
 //   r2 = ((-2*(a*b)) + a*a) + b*b,  a = x/l, b = x'/l     (each op rounded separately, no FMA)
 // so that coincident inducing/data points give r = sqrt(r2 + 1e-12) exactly as TF does.
 #include "common.h"
+#include "cov_entry.h"      // the entry, feature and Kdiag arithmetic (shared with predict_sparse.hip)
 #include <type_traits>
 
 #ifndef GP_COV_NT_STORE
@@ -29,24 +30,6 @@ typedef cov_d2 __attribute__((address_space(1))) * cov_gptr2;
 typedef cov_f2 __attribute__((address_space(1))) * cov_gfptr2;
 #define COV_THREADS 256
 #define COV_ROWS 32  // rows (inducing points) handled per block
-
-__device__ __forceinline__ double stat_profile(int type, double r2, double var, const double* __restrict__ etab) {
-  // r2 is the literal expansion; the kernels below follow GPflow 0.5 Stationary subclasses
-  if (type == GP_KERN_RBF) return var * gp_exp_neg(-r2 * 0.5, etab);
-  double r = gp_sqrt_pos(__dadd_rn(r2, 1e-12));
-  if (type == GP_KERN_MATERN12) return var * gp_exp_neg(-r, etab);
-  if (type == GP_KERN_MATERN32) {
-    const double s3 = 1.7320508075688772;
-    return var * (1.0 + s3 * r) * gp_exp_neg(-s3 * r, etab);
-  }
-  // Matern52
-  const double s5 = 2.23606797749979;
-  return var * (1.0 + s5 * r + (5.0 / 3.0) * (r * r)) * gp_exp_neg(-s5 * r, etab);
-}
-
-__device__ __forceinline__ double r2_expand(double a, double aa, double b, double bb) {
-  return __dadd_rn(__dadd_rn(-2.0 * __dmul_rn(a, b), aa), bb);
-}
 
 // store CPT results of one row as float32 (the strips of a float32 plan; `off` and the leading dimension count floats)
 template <int CPT>
@@ -75,12 +58,7 @@ __global__ void __launch_bounds__(256) sm_features_kernel(DevKern k, const doubl
   if (j >= n) return;
   double c = 0.0, s = 0.0;
   if (p < k.m) {
-    const double* th = k.theta;
-    double e = th[2 + p], fr = th[2 + k.m + p];
-    double arg = __dmul_rn(__dmul_rn(6.283185307179586, fr), x[j]);
-    sincos(arg, &s, &c);
-    double se = __dsqrt_rn(e);
-    c *= se; s *= se;
+    cov_sm_feature(k.theta, k.m, p, x[j], &c, &s);
   }
   f[(size_t)p * n + j] = c;
   f[(size_t)(p + mpad) * n + j] = s;
@@ -170,13 +148,7 @@ __global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const
       double res[CPT];
 #pragma unroll
       for (int c = 0; c < CPT; c++) {
-        double r = gp_sqrt_pos(__dadd_rn(r2_expand(a, aa, b[c], bb[c]), 1e-12));
-        if (ENV == 0) {
-          res[c] = var * gp_exp_neg(-r, etab) * acc[c];
-        } else {   // GPflow Matern52.K profile
-          const double s5 = 2.23606797749979;
-          res[c] = var * ((1.0 + s5 * r + (5.0 / 3.0) * (r * r)) * gp_exp_neg(-s5 * r, etab)) * acc[c];
-        }
+        res[c] = cov_mercer_entry(ENV, var, a, aa, b[c], bb[c], acc[c], etab);
         if (self_cov && i == j0 + c) res[c] += diag_add;
       }
       if (f32out) { cov_store_f32<CPT>(gout, (size_t)i * ld + j0, n2 - j0, res, accumulate, vec_ok); continue; }
@@ -205,21 +177,8 @@ __global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const
   #pragma unroll
         for (int c = 0; c < CPT; c++) res[c] = stat_profile(MODE == 0 ? ENV : k.type, r2_expand(a, aa, b[c], bb[c]), var, etab);
       } else {
-        // Matern12sm (m12sm.py:46-56) / Matern32sm (kernels.py:232-247): r = sqrt((x - x' + 1e-12)^2)
   #pragma unroll
-        for (int c = 0; c < CPT; c++) {
-          double d = __dadd_rn(__dadd_rn(xa, -xb[c]), 1e-12);
-          double r = __dsqrt_rn(__dmul_rn(d, d));
-          double s = 0.0;
-          for (int p = 0; p < m; p++)
-            s += th[2 + p] * cos(__dmul_rn(__dmul_rn(6.283185307179586, th[2 + m + p]), r));
-          if (k.type == GP_KERN_MATERN12SM) {
-            res[c] = var * exp(-(r / ls)) * s;
-          } else {   // Matern32sm: r1 = sqrt(3) r / l, (1 + r1) exp(-r1) sum_k variance_k cos(2 pi f_k r)
-            const double r1 = 1.7320508075688772 * (r / ls);
-            res[c] = var * ((1.0 + r1) * exp(-r1)) * s;
-          }
-        }
+        for (int c = 0; c < CPT; c++) res[c] = cov_broadcast_entry(k.type, th, m, var, ls, xa, xb[c]);
       }
   #pragma unroll
       for (int c = 0; c < CPT; c++)
@@ -244,13 +203,7 @@ __global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const
 __global__ void __launch_bounds__(256) cov_diag_kernel(DevKern k, int n, double* __restrict__ out, int accumulate) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const double* th = k.theta;
-  double v = th[0];
-  if (gp_kern_kdiag_energy(k.type)) {
-    double s = th[2];
-    for (int p = 1; p < k.m; p++) s += th[2 + p];
-    v = v * s;
-  }
+  const double v = cov_kdiag(k.type, k.m, k.theta);
   out[j] = accumulate ? out[j] + v : v;
 }
 

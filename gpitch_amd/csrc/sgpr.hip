@@ -946,6 +946,38 @@ static gp_status sgpr_predict_f_impl(gp_sgpr_plan p, const double* params, const
   return check_not_pd(h);
 }
 
+// The sparse per-source posterior (predict_sparse.hip): source p under the optimal q(u) of the collapsed bound, SGPR.build_predict
+// with K_p in place of the sum.  State from sgpr_common (W, WB, c and the kernels' Z feature tables), one fused launch, no
+// workspace beyond the plan's and no limit on n.
+gp_status gp_sgpr_predict_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                        const double* Z, const double* Xnew, int32_t n, double* mean, double* var) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  sg_invalidate(p);
+  if (!params || !X || !Y || !Z || !Xnew || !mean || !var || N < 1 || N > p->maxN || n < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgpr_predict_source_sparse: bad argument");
+  if (p->M > SPS_MAX_M || (size_t)p->P * sizeof(SrcSparseItem) > SG_DESC_BYTES)
+    return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_sgpr_predict_source_sparse: M <= 1024 inducing points (and at most 186 kernels)");
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgpr_predict_source_sparse: workspace not set");
+  SgDesc d;
+  GP_CHECK(sgpr_common(p, params, X, Y, N, Z, &d));
+  std::vector<char>& hd = p->h_desc[1];
+  hd.assign(SG_DESC_BYTES, 0);
+  SrcSparseItem* items = (SrcSparseItem*)hd.data();
+  int max_mpad = 0;
+  for (int i = 0; i < p->P; i++) {
+    SrcSparseItem& it = items[i];
+    it.k = sg_kern(p, params, i); it.z = Z; it.fz = p->feat + (size_t)i * sgpr_feat_stride(p);
+    it.W = p->W; it.WB = p->WB; it.c = p->c; it.xnew = Xnew;
+    it.mean = mean + (size_t)i * n; it.var = var + (size_t)i * n; it.kz = p->M; it.ldw = p->M;
+    if (gp_kern_is_mercer(it.k.type) && sm_mpad(it.k.m) > max_mpad) max_mpad = sm_mpad(it.k.m);
+  }
+  char* dd = p->d_desc + SG_DESC_BYTES;
+  GP_HIP_CHECK(h, hipMemcpyAsync(dd, hd.data(), SG_DESC_BYTES, hipMemcpyHostToDevice, h->stream));
+  GP_CHECK(launch_sgpr_source_sparse(h, (const SrcSparseItem*)dd, p->P, 1, p->M, n, max_mpad));
+  return check_not_pd(h);
+}
+
 // sgpr_predict_source_impl's workspace
 struct SgprSrcBufs { char* d_desc; double *L, *W; void* chol_ws; double *Kx, *A, *feat, *s1, *dot, *V, *scal; };
 static SgprSrcBufs sgpr_src_carve(GpArena& ar, int N, int n) {

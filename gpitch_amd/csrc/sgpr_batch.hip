@@ -762,6 +762,46 @@ gp_status gp_sgprb_predict_f(gp_sgprb_plan_t p, const double* params, const doub
   return check_not_pd(h);
 }
 
+// The sparse per-source posterior of every window (gp_sgpr_predict_source_sparse, predict_sparse.hip): the forward pass, then ONE
+// fused launch over (frame tile, source, window).  Items are kernel-major [P][count] like gp_sgprb_predict_f's and live in its
+// descriptor block.  A slot with kw < M inducing points is carried as its own kw-point problem: the item bounds every read of
+// Z, its feature table, W, WB and c by kw (the identity pad blocks of W and WB meet zero rows only), so pad rows of Z are
+// never read.  mean, var: [count][P][n]; Xnew: [count][n], any n >= 1.
+extern "C" gp_status gp_sgprb_predict_source_sparse(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
+                                                    const double* Z, const double* Xnew, int32_t n, int32_t count, double* mean,
+                                                    double* var) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!params || !X || !Y || !Z || !Xnew || !mean || !var || count < 1 || count > p->W || n < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgprb_predict_source_sparse: bad argument (n >= 1, 1 <= count <= num_windows)");
+  const int W = count, P = p->P, M = p->M;
+  const size_t bytes = (size_t)W * P * sizeof(SrcSparseItem);
+  if (M > SPS_MAX_M || bytes > sgb_pred_layout(p->W, P).bytes)
+    return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_sgprb_predict_source_sparse: M <= 1024 inducing points");
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_predict_source_sparse: workspace not set");
+  GP_CHECK(gp_sgprb_bound_grad(p, params, X, Y, Z, count, p->wsd + p->o_G, nullptr));      // (as gp_sgprb_predict_f)
+  std::vector<char> hd(bytes, 0);
+  SrcSparseItem* items = (SrcSparseItem*)hd.data();
+  int max_mpad = 0;
+  for (int i = 0; i < P; i++) {
+    if (gp_kern_is_mercer(p->ktype[i]) && sm_mpad(p->m[i]) > max_mpad) max_mpad = sm_mpad(p->m[i]);
+    for (int w = 0; w < W; w++) {
+      double* b = p->wsd + (size_t)w * p->win_doubles;
+      SrcSparseItem& it = items[(size_t)i * W + w];
+      it.k = DevKern{p->ktype[i], p->m[i], params + (size_t)w * p->nparams + p->off_theta[i]};
+      it.z = Z + (size_t)w * M; it.fz = b + p->o_feat + (size_t)i * p->feat_stride;
+      it.W = b + p->o_W; it.WB = b + p->o_WB; it.c = b + p->o_c; it.xnew = Xnew + (size_t)w * n;
+      it.mean = mean + ((size_t)w * P + i) * n; it.var = var + ((size_t)w * P + i) * n;
+      it.kz = p->kw[w]; it.ldw = M;
+    }
+  }
+  char* dd = p->d_pred_desc;
+  GP_HIP_CHECK(h, hipMemcpyAsync(dd, hd.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // hd is a stack object
+  GP_CHECK(launch_sgpr_source_sparse(h, (const SrcSparseItem*)dd, P, W, M, n, max_mpad));
+  return check_not_pd(h);
+}
+
 // gp_sgprb_predict_source's workspace: descriptor block, the batched factorisation's own, then per window
 // K -> L, W = L^-1, K_p(X, Xnew), one feature table, the two [rb][n] partials, V = W y and the scalars
 struct SgbSrcWin { double *L, *W, *Kx, *feat, *s1, *dot, *V, *scal; };

@@ -330,6 +330,33 @@ class SGPRSS(Parameterized):
         """sgpr_ss.py:108-114"""
         return self.build_predict_source(Xnew)
 
+    def predict_s_sparse(self, Xnew):
+        """Sparse posterior of every source at Xnew: (list of P means (n, D), list of P variances (n, D)).
+
+        Source p under the optimal q(u) of the collapsed bound (gp_sgpr_predict_source_sparse): GPflow's
+        SGPR.build_predict with the one kernel K_p in place of the sum, O(M^2 n) per source and independent of N, where
+        predict_s factorises the N x N exact GP.  It approximates predict_s; the variance starts from the source's own
+        Kdiag, not the sum kernel's (sgpr_ss.py:101).  The mean function is NOT added: the sources are zero-mean GPs, and
+        sum_p smean_p + mean_function(Xnew) is predict_f's mean.  Xnew may be longer than the training window."""
+        if self._shard:
+            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        n, P = Xnew.size, len(self.kern.kern_list)
+        self._compile()
+        self._pack()
+        h = self._handle
+        xs = h.to_device(Xnew)
+        mean, var = h.empty(P, n), h.empty(P, n)
+        D = self.num_latent
+        m = np.empty((P, n, D))
+        for d in self._columns():                   # the mean is linear in the column, the variance does not see it
+            h.check(h.lib.gp_sgpr_predict_source_sparse(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                        self._Yd.data_ptr(), self.X.shape[0], self._Zd.data_ptr(),
+                                                        xs.data_ptr(), n, mean.data_ptr(), var.data_ptr()))
+            m[:, :, d] = mean.cpu().numpy()
+        v = var.cpu().numpy()
+        return [m[i] for i in range(P)], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(P)]
+
     # ---- training: GPflow Model.optimize -> scipy L-BFGS-B on the free state (transcription.py:283) ----
     def _param_list(self):
         ps = [self.likelihood.variance]

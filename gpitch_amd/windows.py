@@ -248,6 +248,21 @@ class SgprWindowBatch(object):
                                                   mean[b0:].data_ptr(), var[b0:].data_ptr(), ws.data_ptr(), ws.numel()))
         return mean.cpu().numpy(), var.cpu().numpy()
 
+    def predict_s_sparse(self, params_host, xnews=None):
+        """SGPRSS.predict_s_sparse (the sparse per-source posteriors, gp_sgprb_predict_source_sparse) of every loaded
+        window from one fused launch: (mean, var), each (count, P, n).  n may exceed N."""
+        h = self.h
+        cnt = self.count
+        xn, n = self._load_xnew(xnews, cnt)
+        P = len(self._keep[0])
+        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        mean, var = h.empty(cnt, P, n), h.empty(cnt, P, n)
+        h.check(h.lib.gp_sgprb_predict_source_sparse(self.plan, self.params.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
+                                                     self.Z.data_ptr(), xn.data_ptr(), n, cnt, mean.data_ptr(),
+                                                     var.data_ptr()))
+        return mean.cpu().numpy(), var.cpu().numpy()
+
     def close(self):
         if self.plan is not None:
             self.h.sync()
@@ -300,7 +315,8 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     params0[i] (constrained vector [noise | theta_0 | ...]) when given.  All windows must share N (see below for M).
     predict=True adds what SoSp.optimize computes after every window's optimisation (separation.py:300-313), batched the
     same way: "mean", "var" (predict_f at the window's frames, (N, 1)) and "smean", "svar" (predict_s: lists over the
-    sources of (N, 1) arrays).
+    sources of (N, 1) arrays).  predict="sparse" is the same with "smean", "svar" from the sparse per-source posterior
+    (SGPRSS.predict_s_sparse: no N x N factorisation) instead of predict_s; `merge_sources` takes either.
     Windows must share N; their inducing-point counts may differ (each window's Z from its own audio, as the drivers'
     init_liv picks it).  Windows of different counts are sorted by count and batched with their neighbours
     (`ragged_batches`), each batch on a plan sized by its largest count; plans are made when first needed and freed once no
@@ -323,6 +339,9 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     if not lbfgsb_batch.available():
         raise RuntimeError("fit_windows_batched needs scipy >= 1.15 (its reverse-communication L-BFGS-B routine); "
                            "use fit_windows")
+    if not (isinstance(predict, (bool, np.bool_)) or predict == "sparse"):
+        raise ValueError('fit_windows_batched: predict is False, True or "sparse"')
+    sparse = isinstance(predict, str)
     mine = window_assignment(len(windows), world_size, rank)
     results = [None] * len(windows)
     if not mine:
@@ -464,7 +483,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                 results[i].update(error=r.failed[q], bound=float("nan"))
         if predict:
             fm, fv = r.dev.predict_f(pfin)
-            sm, sv = r.dev.predict_s(pfin)
+            sm, sv = r.dev.predict_s_sparse(pfin) if sparse else r.dev.predict_s(pfin)
             for q, i in enumerate(r.ids):
                 if q in r.failed:           # (predicted at the starting parameters only to keep the batch whole)
                     continue
@@ -511,7 +530,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                       "variances": pv[var_idx].copy(), "noise": float(pv[0]), "params": pv, "engine": "single"}
         if predict:
             m1, v1 = model.predict_f(x)
-            ms, vs = model.predict_s(x)
+            ms, vs = model.predict_s_sparse(x) if sparse else model.predict_s(x)
             results[i].update(mean=m1, var=v1, smean=list(ms), svar=list(vs))
     model._destroy()
     return results

@@ -467,6 +467,23 @@ gp_status gp_sgpr_predict_source(gp_sgpr_plan p, const double* params, const dou
                                  int32_t N, const double* Xnew, int32_t n, double* mean, double* var,
                                  void* workspace, size_t workspace_bytes);
 
+/* Sparse per-source posterior: source p under the optimal q(u) of the collapsed bound, at O(M^2 n) per source and
+ * independent of N.  The sources are independent a priori, so cov(f_p(x*), u) = K_p(x*, Z); with L, LB, c as in
+ * sgpr_ss.py:43-53 (the plan's forward state W = L^-1, WB = LB^-1, c):
+ *   tmp1_p = W K_p(Z, Xnew),  tmp2_p = WB tmp1_p,  smean_p = tmp2_p^T c,
+ *   svar_p = Kdiag_p(Xnew) + sum_m tmp2_p^2 - sum_m tmp1_p^2
+ * i.e. GPflow 0.5 SGPR.build_predict with the one kernel K_p in place of the sum: sum_p smean_p is gp_sgpr_predict_f's mean
+ * and for one kernel both outputs are gp_sgpr_predict_f's.  It sits beside the exact posterior of sgpr_ss.py:73-114
+ * (gp_sgpr_predict_source), which it approximates; unlike sgpr_ss.py:101 the variance starts from the source's OWN Kdiag,
+ * not the sum kernel's.  mean, var: P x n row-major.  One fused float64 launch (predict_sparse.hip): no M x n array is
+ * written, no workspace beyond the plan's is used and n may exceed the plan's max_N (any n >= 1; N <= max_N as ever).
+ * Runs the forward pass at `params` first, synchronises and reports a failed factorisation like gp_sgpr_predict_f.
+ * Limits: 1 <= M <= 1024 (GP_ERR_UNSUPPORTED before any launch otherwise).  float32 plans (gp_sgpr_set_precision) are
+ * taken: the state comes from the plan's float32 forward pass, this kernel's own arithmetic is float64 regardless.
+ * Deterministic: bit-identical between calls, and a frame's result does not depend on the other frames of the call. */
+gp_status gp_sgpr_predict_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                        const double* Z, const double* Xnew, int32_t n, double* mean, double* var);
+
 /* ---- many independent SGPRSS windows per launch sequence -------------------------------------------------------
  * replaces the window loop of AMT.optimize / SoSp.optimize (gpitch/transcription.py:265-288, gpitch/separation.py:279-313):
  * for each window, reset_model then model.optimize(maxiter) = a dozen-odd evaluations of SGPRSS.build_likelihood
@@ -507,6 +524,12 @@ size_t gp_sgprb_predict_source_workspace_bytes(gp_sgprb_plan p, int32_t count, i
 gp_status gp_sgprb_predict_source(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
                                   const double* Xnew, int32_t n, int32_t count, double* mean, double* var,
                                   void* workspace, size_t workspace_bytes);
+/* gp_sgpr_predict_source_sparse of the first `count` windows from ONE fused launch over all windows and sources: Xnew
+ * [count][n] (any n >= 1), mean / var [count][P][n].  Honours gp_sgprb_set_inducing_counts: a slot with k < M points gives
+ * the k-point window's result and its pad rows of Z are never read.  Synchronises; GP_ERR_NOT_PD as gp_sgprb_predict_f. */
+gp_status gp_sgprb_predict_source_sparse(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
+                                         const double* Z, const double* Xnew, int32_t n, int32_t count, double* mean,
+                                         double* var);
 
 /* ---- many small, independent Pdgp models per launch sequence ------------------------------------------------------
  * replaces the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)  over single-pitch models trained
