@@ -34,10 +34,11 @@ ABI_SYMBOLS = [
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
     "gp_sgpr_create", "gp_sgpr_destroy", "gp_sgpr_num_params", "gp_sgpr_workspace_bytes", "gp_sgpr_set_workspace", "gp_sgpr_set_precision",
     "gp_sgpr_bound", "gp_sgpr_bound_grad", "gp_sgpr_residual_grad", "gp_sgpr_exchange_doubles", "gp_sgpr_bound_begin", "gp_sgpr_bound_end", "gp_sgpr_set_graphs", "gp_sgpr_eval_counts", "gp_sgpr_predict_f", "gp_sgpr_predict_f_full", "gp_sgpr_predict_source_full", "gp_sgpr_predict_source_workspace_bytes", "gp_sgpr_predict_source", "gp_sgpr_predict_source_sparse",
+    "gp_sgpr_sample_source_sparse", "gp_sgpr_sample_source_workspace_bytes",
     "gp_sgprb_create", "gp_sgprb_destroy", "gp_sgprb_num_params", "gp_sgprb_num_windows", "gp_sgprb_workspace_bytes",
     "gp_sgprb_set_workspace", "gp_sgprb_bound_grad", "gp_sgprb_set_graphs", "gp_sgprb_eval_counts",
     "gp_sgprb_set_inducing_counts",
-    "gp_sgprb_predict_f", "gp_sgprb_predict_source_workspace_bytes", "gp_sgprb_predict_source", "gp_sgprb_predict_source_sparse",
+    "gp_sgprb_predict_f", "gp_sgprb_predict_source_workspace_bytes", "gp_sgprb_predict_source", "gp_sgprb_predict_source_sparse", "gp_sgprb_sample_source_sparse",
     "gp_timers_enable", "gp_timers_reset", "gp_timers_read",
     "gp_comm_unique_id", "gp_comm_create", "gp_comm_destroy", "gp_comm_world", "gp_comm_rank", "gp_comm_allreduce_sum",
     "gp_pdgp_elbo_pitch_sharded", "gp_pdgp_elbo_gp_sharded", "gp_sgpr_bound_grad_sharded",
@@ -192,6 +193,8 @@ def load_library():
         "gp_sgpr_eval_counts": (i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
         "gp_sgpr_predict_f": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
         "gp_sgpr_predict_source_sparse": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+        "gp_sgpr_sample_source_sparse": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, sz]),
+        "gp_sgpr_sample_source_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
         "gp_sgpr_predict_f_full": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]),
         "gp_sgpr_predict_source_full": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz]),
         "gp_sgpr_predict_source_workspace_bytes": (sz, [i32, i32]),
@@ -208,6 +211,7 @@ def load_library():
         "gp_sgprb_set_inducing_counts": (i32, [vp, vp, i32]),
         "gp_sgprb_predict_f": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
         "gp_sgprb_predict_source_sparse": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+        "gp_sgprb_sample_source_sparse": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, sz]),
         "gp_sgprb_predict_source_workspace_bytes": (sz, [vp, i32, i32]),
         "gp_sgprb_predict_source": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz]),
         "gp_timers_enable": (i32, [vp, i32]),

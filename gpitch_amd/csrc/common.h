@@ -352,6 +352,20 @@ struct SrcSparseItem {
   const double* xnew; double* mean; double* var; int kz, ldw;
 };
 gp_status launch_sgpr_source_sparse(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n, int max_mpad);
+// sample_sparse.hip: joint posterior draws of every source under the sparse posterior's q(u) (gp_sgpr_sample_source_sparse,
+// gp_sgprb_sample_source_sparse).  The two entries describe their windows on the host — a window's forward state and inputs,
+// and per (window, source) the kernel and the plan's Z feature table (nullptr: the plan keeps none for this kernel) — check
+// every argument with sgpr_sample_check BEFORE anything is enqueued, run their forward pass, then call sgpr_sample_run.
+struct SmpWindow { const double* z; const double* W; const double* WB; const double* c; const double* xnew; int kz; };
+struct SmpSource { DevKern k; const double* fz; };
+size_t sgpr_sample_workspace_bytes(int M, int P, int C, int n, int S, int count);
+// kw: inducing points per window (nullptr: M each); order_host: [count][n + M], a slot's first n + k entries checked to be a
+// permutation of 0..n+k-1 (a bad index must never become a device address)
+gp_status sgpr_sample_check(gp_handle h, const int* ktype, const int* km, int P, int M, const int* kw, int count, int n, int S,
+                            const int32_t* order_host, const void* ws, size_t ws_bytes, int* C_out);
+gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* src, int count, int P, int M, int ldw, int n, int S,
+                          double jitter, const int32_t* order_host, const double* eps_x, const double* eps_z, const double* eps_u,
+                          double* out, void* ws, size_t ws_bytes);
 gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int64_t ldy, int n, int square, double* out);
 // lik.hip
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)

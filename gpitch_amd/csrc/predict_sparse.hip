@@ -7,7 +7,8 @@
 // A workgroup takes one (window, source, tile of T new frames):
 //   1. K_p(Z, x*) of its T frames is built straight into LDS (frame-major, M values per frame) with the entry arithmetic
 //      of cov.hip (cov_entry.h): an entry equals what launch_kernel_build writes.  The Z feature table of a Mercer kernel is
-//      the plan's (current after the forward pass); the T frames' features are computed here, once per workgroup.
+//      the plan's (current after the forward pass); the T frames' features are computed here, once per workgroup.  The
+//      build itself is sps_tile.h's, shared with sample_sparse.hip.
 //   2. tmp1 = W tile on v_mfma_f64_16x16x4_f64.  A wavefront owns 16 frames — both products act on a frame's column alone,
 //      so nothing crosses wavefronts after the build.  Row blocks run from the last to the first and overwrite the tile
 //      in place: block rb reads blocks kb <= rb only (the zero blocks above W's diagonal are skipped).
@@ -21,99 +22,25 @@
 // or WB) and in n (frames past the end repeat the last one and are not written) are handled here.
 #include "common.h"
 #include "cov_entry.h"
+#include "sps_tile.h"
 
 typedef double sps_d4 __attribute__((ext_vector_type(4)));
-#define SPS_CHUNK 32      // rows of Z staged per pass of the tile build
 
-// frames per workgroup, from the plan's M: the M x T tile (plus 4 pad doubles per frame) stays inside the 160 KiB of LDS
-int sps_tile_frames(int M) { return M <= 256 ? 64 : (M <= 512 ? 32 : 16); }
-static inline int sps_stride(int M) { return ((M + 15) & ~15) + 4; }       // doubles per frame of the tile (4 x odd: see the reads)
-static size_t sps_lds_bytes(int M, int mpad) {
-  const int T = sps_tile_frames(M), S = sps_stride(M);
-  const size_t buf = (size_t)T * (S > 2 * mpad ? S : 2 * mpad);
-  return (GP_EXP_TAB + 2 * SPS_CHUNK + (size_t)SPS_CHUNK * 2 * mpad + buf) * sizeof(double);
-}
-
-// LDS (doubles): etab[64] | rowa[32] | rowx[32] | zf[32][2 MPAD] | buf[T][S]  (buf first holds the frames' features [2 MPAD][T])
 template <int MPAD>
 __global__ void __launch_bounds__(256) sgpr_source_sparse_kernel(const SrcSparseItem* __restrict__ items, int nwin, int n,
                                                                  int T, int S) {
   extern __shared__ double sps_lds[];
-  double* etab = sps_lds;
-  double* rowa = etab + GP_EXP_TAB;
-  double* rowx = rowa + SPS_CHUNK;
-  double* zf = rowx + SPS_CHUNK;
-  double* buf = zf + SPS_CHUNK * 2 * MPAD;
+  const SpsLds lds = sps_lds_carve<MPAD>(sps_lds);
+  double* buf = lds.buf;
   const SrcSparseItem it = items[(size_t)blockIdx.y * nwin + blockIdx.z];
-  const int tid = threadIdx.x, NT = blockDim.x;           // NT = 4 T
+  const int tid = threadIdx.x;
   const int kz = it.kz, Mp = (kz + 15) & ~15, ldw = it.ldw;
   const int type = it.k.type, m = it.k.m;
   const double* __restrict__ th = it.k.theta;
-  const double var = th[0], ls = th[1];
-  const bool mercer = gp_kern_is_mercer(type), bcast = gp_kern_is_broadcast(type);
-  const int mp = mercer ? ((m + 3) / 4) * 4 : 0;          // the feature table's own padding (sm_mpad)
-  const int env = (type == GP_KERN_MERCER_MATERN12SM) ? 0 : 2;
   const int j0 = blockIdx.x * T;
-  gp_exp_tab_init(etab);
 
-  // ---- 1. the tile ------------------------------------------------------------------------------------------------
-  const int jj = tid % T, rg = tid / T;                   // this thread's frame of the tile and its row group (0..3)
-  const double xb = it.xnew[min(j0 + jj, n - 1)];
-  const double b = xb / ls, bb = __dmul_rn(b, b);
-  double fx[2 * MPAD];
-  if (mercer) {
-    for (int t = tid; t < MPAD * T; t += NT) {
-      const int q = t / T, fj = t % T;
-      double c = 0.0, s = 0.0;
-      if (q < m) cov_sm_feature(th, m, q, it.xnew[min(j0 + fj, n - 1)], &c, &s);
-      buf[q * T + fj] = c;
-      buf[(q + MPAD) * T + fj] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 2 * MPAD; q++) fx[q] = buf[q * T + jj];
-  } else {
-#pragma unroll
-    for (int q = 0; q < 2 * MPAD; q++) fx[q] = 0.0;
-  }
-  for (int r0 = 0; r0 < Mp; r0 += SPS_CHUNK) {
-    __syncthreads();                                      // the frames' features / the previous chunk's rows are read
-    if (tid < SPS_CHUNK) {
-      const int i = r0 + tid;
-      const double z = (i < kz) ? it.z[i] : 0.0;
-      rowx[tid] = z;
-      rowa[tid] = z / ls;
-    }
-    if (mercer)
-      for (int t = tid; t < SPS_CHUNK * MPAD; t += NT) {
-        const int q = t / SPS_CHUNK, ii = t % SPS_CHUNK, i = r0 + ii;
-        const bool on = (q < mp) && (i < kz);
-        zf[ii * 2 * MPAD + q] = on ? it.fz[(size_t)q * kz + i] : 0.0;
-        zf[ii * 2 * MPAD + MPAD + q] = on ? it.fz[(size_t)(mp + q) * kz + i] : 0.0;
-      }
-    __syncthreads();
-    for (int ii = rg; ii < SPS_CHUNK; ii += 4) {
-      const int i = r0 + ii;
-      if (i >= Mp) break;
-      double res = 0.0;
-      if (i < kz) {
-        const double a = rowa[ii], aa = __dmul_rn(a, a);
-        if (mercer) {
-          const double* fzr = &zf[ii * 2 * MPAD];
-          double acc = 0.0;
-#pragma unroll
-          for (int q = 0; q < 2 * MPAD; q++) acc = fma(fzr[q], fx[q], acc);
-          res = cov_mercer_entry(env, var, a, aa, b, bb, acc, etab);
-        } else if (bcast) {
-          res = cov_broadcast_entry(type, th, m, var, ls, rowx[ii], xb);
-        } else {
-          res = stat_profile(type, r2_expand(a, aa, b, bb), var, etab);
-        }
-      }
-      buf[jj * S + i] = res;
-    }
-  }
-  __syncthreads();
+  // ---- 1. the tile (sps_tile.h) -------------------------------------------------------------------------------------
+  sps_build_tile<MPAD>(lds, it.k, it.z, it.fz, kz, it.xnew, n, j0, T, S);
 
   // ---- 2.-4. the two triangular products and the per-frame sums, one wavefront per 16 frames ---------------------------
   const int lane = tid & 63, wave = tid >> 6, lc = lane & 15, kq = lane >> 4;

@@ -978,6 +978,38 @@ gp_status gp_sgpr_predict_source_sparse(gp_sgpr_plan p, const double* params, co
   return check_not_pd(h);
 }
 
+// Joint posterior draws of every source under the q(u) of gp_sgpr_predict_source_sparse (sample_sparse.hip).  Every argument,
+// the host array `order` included, is checked before the forward pass: a refused call enqueues nothing.
+gp_status gp_sgpr_sample_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                       const double* Z, const double* Xnew, int32_t n, const int32_t* order_host, int32_t S,
+                                       const double* eps_x, const double* eps_z, const double* eps_u, double* out, void* workspace,
+                                       size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  sg_invalidate(p);
+  if (!params || !X || !Y || !Z || !Xnew || !order_host || !eps_x || !eps_z || !eps_u || !out || !workspace || N < 1 ||
+      N > p->maxN || n < 1 || S < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgpr_sample_source_sparse: bad argument");
+  GP_CHECK(sgpr_sample_check(h, p->ktype.data(), p->m.data(), p->P, p->M, nullptr, 1, n, S, order_host, workspace, workspace_bytes,
+                             nullptr));
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgpr_sample_source_sparse: workspace not set");
+  SgDesc d;
+  GP_CHECK(sgpr_common(p, params, X, Y, N, Z, &d));
+  const SmpWindow win{Z, p->W, p->WB, p->c, Xnew, p->M};
+  std::vector<SmpSource> src(p->P);
+  for (int i = 0; i < p->P; i++) {
+    src[i].k = sg_kern(p, params, i);
+    src[i].fz = gp_kern_is_mercer(src[i].k.type) ? p->feat + (size_t)i * sgpr_feat_stride(p) : nullptr;
+  }
+  GP_CHECK(sgpr_sample_run(h, &win, src.data(), 1, p->P, p->M, p->M, n, S, p->jitter, order_host, eps_x, eps_z, eps_u, out, workspace,
+                           workspace_bytes));
+  return check_not_pd(h);
+}
+
+size_t gp_sgpr_sample_source_workspace_bytes(int32_t M, int32_t P, int32_t C, int32_t n, int32_t S, int32_t count) {
+  return sgpr_sample_workspace_bytes(M, P, C, n, S, count);
+}
+
 // sgpr_predict_source_impl's workspace
 struct SgprSrcBufs { char* d_desc; double *L, *W; void* chol_ws; double *Kx, *A, *feat, *s1, *dot, *V, *scal; };
 static SgprSrcBufs sgpr_src_carve(GpArena& ar, int N, int n) {

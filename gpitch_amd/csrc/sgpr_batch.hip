@@ -802,6 +802,39 @@ extern "C" gp_status gp_sgprb_predict_source_sparse(gp_sgprb_plan_t p, const dou
   return check_not_pd(h);
 }
 
+// gp_sgpr_sample_source_sparse of the first `count` windows (sample_sparse.hip): the forward pass, then one launch sequence
+// over every (window, source).  A slot with kw < M inducing points is its own kw-point problem, as in
+// gp_sgprb_predict_source_sparse.  Every argument, the host array `order` included, is checked before anything is enqueued.
+extern "C" gp_status gp_sgprb_sample_source_sparse(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
+                                                   const double* Z, const double* Xnew, int32_t n, int32_t count,
+                                                   const int32_t* order_host, int32_t S, const double* eps_x, const double* eps_z,
+                                                   const double* eps_u, double* out, void* workspace, size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!params || !X || !Y || !Z || !Xnew || !order_host || !eps_x || !eps_z || !eps_u || !out || !workspace || count < 1 ||
+      count > p->W || n < 1 || S < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_sgprb_sample_source_sparse: bad argument (n >= 1, S >= 1, 1 <= count <= num_windows)");
+  const int P = p->P, M = p->M;
+  GP_CHECK(sgpr_sample_check(h, p->ktype.data(), p->m.data(), P, M, p->kw.data(), count, n, S, order_host, workspace,
+                             workspace_bytes, nullptr));
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_sgprb_sample_source_sparse: workspace not set");
+  GP_CHECK(gp_sgprb_bound_grad(p, params, X, Y, Z, count, p->wsd + p->o_G, nullptr));      // (as gp_sgprb_predict_f)
+  std::vector<SmpWindow> win(count);
+  std::vector<SmpSource> src((size_t)count * P);
+  for (int w = 0; w < count; w++) {
+    double* b = p->wsd + (size_t)w * p->win_doubles;
+    win[w] = SmpWindow{Z + (size_t)w * M, b + p->o_W, b + p->o_WB, b + p->o_c, Xnew + (size_t)w * n, p->kw[w]};
+    for (int i = 0; i < P; i++) {
+      SmpSource& sc = src[(size_t)w * P + i];
+      sc.k = DevKern{p->ktype[i], p->m[i], params + (size_t)w * p->nparams + p->off_theta[i]};
+      sc.fz = gp_kern_is_mercer(p->ktype[i]) ? b + p->o_feat + (size_t)i * p->feat_stride : nullptr;
+    }
+  }
+  GP_CHECK(sgpr_sample_run(h, win.data(), src.data(), count, P, M, M, n, S, p->jitter, order_host, eps_x, eps_z, eps_u, out,
+                           workspace, workspace_bytes));
+  return check_not_pd(h);
+}
+
 // gp_sgprb_predict_source's workspace: descriptor block, the batched factorisation's own, then per window
 // K -> L, W = L^-1, K_p(X, Xnew), one feature table, the two [rb][n] partials, V = W y and the scalars
 struct SgbSrcWin { double *L, *W, *Kx, *feat, *s1, *dot, *V, *scal; };

@@ -22,6 +22,65 @@ class _Gaussian(Parameterized):
         self.variance = Param(1.0, transforms.positive)
 
 
+# ---- joint posterior draws of the sources (csrc/sample_sparse.hip): host-only helpers, no device work ----
+_KERN_NAMES = {_lib.KERN_MATERN12: "Matern12", _lib.KERN_MATERN32: "Matern32", _lib.KERN_MATERN52: "Matern52",
+               _lib.KERN_RBF: "RBF", _lib.KERN_MERCER_MATERN12SM: "MercerMatern12sm", _lib.KERN_MATERN12SM: "Matern12sm",
+               _lib.KERN_MATERN32SM: "Matern32sm", _lib.KERN_MERCER_MATERN52SM: "Matern52 * MercerCosMix"}
+_SAMPLE_KERNS = (_lib.KERN_MERCER_MATERN12SM, _lib.KERN_MATERN12SM, _lib.KERN_MATERN12)
+# eps=None: the standard normals of one library call stay below this many bytes (the draws are generated chunk by chunk)
+SAMPLE_EPS_BYTES = 1 << 30
+
+
+def _kern_codes(kern_list):
+    """[(type_code, num_partials)] of kernel objects (an Add, a list) or of such pairs"""
+    kl = getattr(kern_list, "kern_list", kern_list)
+    return [(int(k[0]), int(k[1])) if isinstance(k, (tuple, list)) else (int(k.type_code), int(k.num_partials)) for k in kl]
+
+
+def sample_components(kern_list):
+    """Ornstein-Uhlenbeck components per source for sample_s_sparse: 2 m for a Matern-1/2 spectral mixture of m partials
+    (a_k and b_k of every partial), 1 for Matern12.  Raises NotImplementedError, naming the kernel, for a sum that holds a
+    kernel without a Matern-1/2 envelope: only those have the exact first-order prior sampler."""
+    comps = []
+    for i, (code, m) in enumerate(_kern_codes(kern_list)):
+        if code not in _SAMPLE_KERNS:
+            raise NotImplementedError("sample_s_sparse: kernel %d of the sum is %s; joint draws need a Matern-1/2 envelope "
+                                      "(supported: %s)" % (i, _KERN_NAMES.get(code, "type %d" % code),
+                                                           ", ".join(_KERN_NAMES[c] for c in _SAMPLE_KERNS)))
+        comps.append(1 if code == _lib.KERN_MATERN12 else 2 * m)
+    return comps
+
+
+def sample_eps_shapes(kern_list, n, M, num_samples=1):
+    """shapes of the three standard-normal arrays of sample_s_sparse for one window and output column:
+    eps_x (S, C, n), eps_z (S, C, M), eps_u (S, 2, M) with C = sum of sample_components(kern_list), the sources' blocks in
+    kern_list order.  Blocks are indexed by the caller's own point order (Xnew, Z), not by the merged one."""
+    C = int(sum(sample_components(kern_list)))
+    S = int(num_samples)
+    return (S, C, int(n)), (S, C, int(M)), (S, 2, int(M))
+
+
+def merged_order(xnew, z):
+    """stable ascending argsort of t = concat(xnew, z) as int32: entry < len(xnew) is a new frame, len(xnew) + i is z[i].
+    Ties keep the caller's order (a frame that coincides with an inducing input comes first)."""
+    t = np.concatenate([np.asarray(xnew, dtype=np.float64).reshape(-1), np.asarray(z, dtype=np.float64).reshape(-1)])
+    return np.argsort(t, kind="stable").astype(np.int32)
+
+
+def _sample_chunk(num_samples, doubles_per_sample):
+    """draws per library call so that their standard normals stay below SAMPLE_EPS_BYTES"""
+    return int(max(1, min(int(num_samples), SAMPLE_EPS_BYTES // (8 * max(1, int(doubles_per_sample))))))
+
+
+def _sample_generator(h, seed):
+    g = h.torch.Generator(device=h.device)
+    if seed is None:
+        g.seed()
+    else:
+        g.manual_seed(int(seed))
+    return g
+
+
 class SGPRSS(Parameterized):
     def __init__(self, X, Y, kern, Z, mean_function=None, reg=False, handle=None, shard=None, float_type=None):
         """shard=(rank, world): ONE window spread over `world` GPUs by frames (one process each).  Every rank is
@@ -356,6 +415,58 @@ class SGPRSS(Parameterized):
             m[:, :, d] = mean.cpu().numpy()
         v = var.cpu().numpy()
         return [m[i] for i in range(P)], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(P)]
+
+    def sample_s_sparse(self, Xnew, num_samples=1, seed=None, eps=None):
+        """Joint posterior draws of every source at Xnew under the q(u) of predict_s_sparse: a list of P arrays
+        (num_samples, n, D).  A draw is joint across the n frames and across the P sources (gp_sgpr_sample_source_sparse:
+        Matheron's rule on an exact O(n) prior sampler, no n x n matrix); its mean over many draws is predict_s_sparse's
+        mean and its spread the joint posterior covariance.  Every kernel needs a Matern-1/2 envelope (MercerMatern12sm,
+        Matern12sm, Matern12); the mean function is NOT added, as in predict_s_sparse.
+
+        eps=None: the standard normals are torch.randn on the handle's device from a generator seeded by `seed`, drawn
+        SAMPLE_EPS_BYTES at a time (the same seed and chunk size give the same draws); output columns get independent ones.
+        eps=(eps_x, eps_z, eps_u) of shapes sample_eps_shapes(kern, n, M, num_samples), each with a leading D axis when
+        D > 1, supplies them: the map is affine in eps and eps = 0 returns the posterior mean."""
+        if self._shard:
+            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        kl = self.kern.kern_list
+        C = int(sum(sample_components(kl)))           # raises for an unsupported kernel, before any device work
+        Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        n, P, M, S, D = Xnew.size, len(kl), self.Z.shape[0], int(num_samples), self.num_latent
+        if n < 1 or S < 1:
+            raise ValueError("sample_s_sparse: needs at least one new point and one sample")
+        shapes = sample_eps_shapes(kl, n, M, S)
+        if eps is not None:
+            eps = [np.asarray(e, dtype=np.float64) for e in eps]
+            want = [((D,) if D > 1 else ()) + sh for sh in shapes]
+            if len(eps) != 3 or any(e.shape != w for e, w in zip(eps, want)):
+                raise ValueError("sample_s_sparse: eps must be (eps_x, eps_z, eps_u) of shapes %s" % (want,))
+            eps = [e.reshape((D,) + sh) for e, sh in zip(eps, shapes)]
+        order = np.ascontiguousarray(merged_order(Xnew, self.Z._array))
+        self._compile()
+        self._pack()
+        h = self._handle
+        xs = h.to_device(Xnew)
+        chunk = S if eps is not None else _sample_chunk(S, C * (n + M) + 2 * M)
+        ws = h.workspace(h.lib.gp_sgpr_sample_source_workspace_bytes(M, P, C, n, chunk, 1))
+        out = h.empty(P, chunk, n)
+        gen = None if eps is not None else _sample_generator(h, seed)
+        res = np.empty((P, S, n, D))
+        for d in self._columns():
+            for s0 in range(0, S, chunk):
+                sc = min(chunk, S - s0)
+                if eps is not None:
+                    ex, ez, eu = (h.to_device(e[d]) for e in eps)
+                else:
+                    ex, ez, eu = (h.torch.randn(sc, *sh[1:], dtype=h.torch.float64, device=h.device, generator=gen)
+                                  for sh in shapes)
+                h.check(h.lib.gp_sgpr_sample_source_sparse(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                           self._Yd.data_ptr(), self.X.shape[0], self._Zd.data_ptr(),
+                                                           xs.data_ptr(), n, order.ctypes.data, sc, ex.data_ptr(),
+                                                           ez.data_ptr(), eu.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                           ws.numel()))
+                res[:, s0:s0 + sc, :, d] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
+        return [res[i] for i in range(P)]
 
     # ---- training: GPflow Model.optimize -> scipy L-BFGS-B on the free state (transcription.py:283) ----
     def _param_list(self):

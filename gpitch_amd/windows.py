@@ -263,6 +263,52 @@ class SgprWindowBatch(object):
                                                      var.data_ptr()))
         return mean.cpu().numpy(), var.cpu().numpy()
 
+    def sample_s_sparse(self, params_host, xnews=None, num_samples=1, seed=None, eps=None):
+        """SGPRSS.sample_s_sparse (joint posterior draws of every source, gp_sgprb_sample_source_sparse) of every loaded
+        window from one launch sequence: (count, P, num_samples, n); ragged windows included.  eps=None: standard normals
+        from a device generator seeded by `seed`, sgpr_ss.SAMPLE_EPS_BYTES per library call; otherwise
+        eps=(eps_x (count, S, C, n), eps_z (count, S, C, M), eps_u (count, S, 2, M)) with M the plan's: rows of eps_z and
+        eps_u past a window's own inducing-point count are never read."""
+        from . import sgpr_ss
+        h = self.h
+        t = h.torch
+        cnt, S, M = self.count, int(num_samples), self.M
+        codes = list(zip(self._keep[0], self._keep[1]))
+        C = int(sum(sgpr_ss.sample_components(codes)))          # raises for an unsupported kernel, before any device work
+        xn, n = self._load_xnew(xnews, cnt)
+        if S < 1:
+            raise ValueError("sample_s_sparse: needs at least one sample")
+        P = len(codes)
+        shapes = [(cnt,) + sh for sh in sgpr_ss.sample_eps_shapes(codes, n, M, S)]
+        if eps is not None:
+            eps = [np.asarray(e, dtype=np.float64) for e in eps]
+            if len(eps) != 3 or any(e.shape != sh for e, sh in zip(eps, shapes)):
+                raise ValueError("sample_s_sparse: eps must be (eps_x, eps_z, eps_u) of shapes %s" % (shapes,))
+        xh, zh = xn.cpu().numpy(), self.Z[:cnt].cpu().numpy()
+        order = np.zeros((cnt, n + M), dtype=np.int32)
+        for w in range(cnt):
+            k = self.counts[w]
+            order[w, :n + k] = sgpr_ss.merged_order(xh[w], zh[w, :k])
+        self._p_host[:cnt].copy_(t.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        chunk = S if eps is not None else sgpr_ss._sample_chunk(S, cnt * (C * (n + M) + 2 * M))
+        ws = h.workspace(h.lib.gp_sgpr_sample_source_workspace_bytes(M, P, C, n, chunk, cnt))
+        gen = None if eps is not None else sgpr_ss._sample_generator(h, seed)
+        res = np.empty((cnt, P, S, n))
+        for s0 in range(0, S, chunk):
+            sc = min(chunk, S - s0)
+            if eps is not None:
+                ex, ez, eu = (h.to_device(e) for e in eps)
+            else:
+                ex, ez, eu = (t.randn(cnt, sc, *sh[2:], dtype=t.float64, device=h.device, generator=gen) for sh in shapes)
+            out = h.empty(cnt, P, sc, n)
+            h.check(h.lib.gp_sgprb_sample_source_sparse(self.plan, self.params.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
+                                                        self.Z.data_ptr(), xn.data_ptr(), n, cnt, order.ctypes.data, sc,
+                                                        ex.data_ptr(), ez.data_ptr(), eu.data_ptr(), out.data_ptr(),
+                                                        ws.data_ptr(), ws.numel()))
+            res[:, :, s0:s0 + sc] = out.cpu().numpy()
+        return res
+
     def close(self):
         if self.plan is not None:
             self.h.sync()

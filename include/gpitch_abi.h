@@ -484,6 +484,32 @@ gp_status gp_sgpr_predict_source(gp_sgpr_plan p, const double* params, const dou
 gp_status gp_sgpr_predict_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
                                         const double* Z, const double* Xnew, int32_t n, double* mean, double* var);
 
+/* Joint posterior draws of every source under the q(u) of gp_sgpr_predict_source_sparse, by Matheron's rule: S draws that
+ * are jointly distributed across the n frames AND across the P sources, in O((n + M) m + M n) per source and draw; no
+ * n x n matrix is formed.  Every kernel of the sum must have a Matern-1/2 envelope (GP_KERN_MERCER_MATERN12SM,
+ * GP_KERN_MATERN12SM, GP_KERN_MATERN12; anything else: GP_ERR_UNSUPPORTED): such a source is a sum of Ornstein-Uhlenbeck
+ * processes, a_k cos + b_k sin per partial (2 m components; Matern12: one), drawn exactly by a first-order recursion along
+ * sorted time.  The caller supplies the standard normals and the merge:
+ *   order_host  HOST array, n + M entries: a stable ascending argsort of t = (Xnew | Z); entry < n is a frame, n + i is z_i.
+ *               Checked on the host to be a permutation of 0..n+M-1 before anything is enqueued (GP_ERR_BAD_ARG otherwise).
+ *   eps_x [S][C][n], eps_z [S][C][M], eps_u [S][2][M] (device), C = sum_p components_p, sources in kernel order; blocks are
+ *               indexed by the caller's own point order.  The eps of a point that coincides with its predecessor is
+ *               multiplied by 0.
+ *   out [P][S][n] (device).  The map is affine in eps: with eps = 0 it returns gp_sgpr_predict_source_sparse's mean, and its
+ *               linear part T has T T^T = the joint posterior covariance, block (p, r) =
+ *               delta_pr K_p(x*, x*) - tmp1_p^T tmp1_r + tmp2_p^T tmp2_r (up to the kernels' own 1e-12 under the root).
+ * The mean function is not added.  workspace: gp_sgpr_sample_source_workspace_bytes(M, P, C, n, S, 1) bytes, 256-byte
+ * aligned (a short one: GP_ERR_BAD_ARG); n may exceed max_N; M <= 1024 (GP_ERR_UNSUPPORTED).  Runs the forward pass at
+ * `params`, synchronises and reports a failed factorisation like gp_sgpr_predict_f.  float64 throughout, float32 plans are
+ * taken as by gp_sgpr_predict_source_sparse.  Deterministic, no atomics: bit-identical between calls, and draw s depends on
+ * nothing but its own eps. */
+gp_status gp_sgpr_sample_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                       const double* Z, const double* Xnew, int32_t n, const int32_t* order_host, int32_t S,
+                                       const double* eps_x, const double* eps_z, const double* eps_u, double* out,
+                                       void* workspace, size_t workspace_bytes);
+/* handle-free, runs without a device: the one carve of the sampling operator (also the window-batched entry's), measured */
+size_t gp_sgpr_sample_source_workspace_bytes(int32_t M, int32_t P, int32_t C, int32_t n, int32_t S, int32_t count);
+
 /* ---- many independent SGPRSS windows per launch sequence -------------------------------------------------------
  * replaces the window loop of AMT.optimize / SoSp.optimize (gpitch/transcription.py:265-288, gpitch/separation.py:279-313):
  * for each window, reset_model then model.optimize(maxiter) = a dozen-odd evaluations of SGPRSS.build_likelihood
@@ -530,6 +556,16 @@ gp_status gp_sgprb_predict_source(gp_sgprb_plan p, const double* params, const d
 gp_status gp_sgprb_predict_source_sparse(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
                                          const double* Z, const double* Xnew, int32_t n, int32_t count, double* mean,
                                          double* var);
+
+/* gp_sgpr_sample_source_sparse of the first `count` windows: Xnew [count][n], order_host [count][n + M] (HOST; a slot with
+ * k <= M inducing points: its first n + k entries, a permutation of 0..n+k-1, checked before anything is enqueued),
+ * eps_x [count][S][C][n], eps_z [count][S][C][M], eps_u [count][S][2][M], out [count][P][S][n].  Honours
+ * gp_sgprb_set_inducing_counts: rows >= k of a slot's eps_z, eps_u, Z, W and WB are never read.  workspace:
+ * gp_sgpr_sample_source_workspace_bytes(M, P, C, n, S, count).  Synchronises; GP_ERR_NOT_PD as gp_sgprb_predict_f. */
+gp_status gp_sgprb_sample_source_sparse(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
+                                        const double* Z, const double* Xnew, int32_t n, int32_t count,
+                                        const int32_t* order_host, int32_t S, const double* eps_x, const double* eps_z,
+                                        const double* eps_u, double* out, void* workspace, size_t workspace_bytes);
 
 /* ---- many small, independent Pdgp models per launch sequence ------------------------------------------------------
  * replaces the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)  over single-pitch models trained
