@@ -166,40 +166,29 @@ size_t hyper_kuf_records(int N, int M) {
 // inner loop carries no guards); SM = Mercer Matern-1/2 SM kernel; GZ = also produce the inducing-input gradient.
 // KT >= 0: the (stationary) kernel type as a compile-time constant, so the row loop carries no type switch.
 template <int MPAD, bool SM, bool GZ, int KT = -1>
-__global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, const double* __restrict__ x1, int n1,
-                                                                    const double* __restrict__ x2, int n2,
-                                                                    const double* __restrict__ G, int64_t ldg,
-                                                                    const double* __restrict__ alpha,
-                                                                    const double* __restrict__ gm, int symmetric,
-                                                                    const double* __restrict__ f1,
-                                                                    const double* __restrict__ f2,
-                                                                    double* __restrict__ partials,
-                                                                    double* __restrict__ gz_part, int wg_rows, int g32,
-                                                                    const HyperItem* __restrict__ items) {
-  if (items) {     // one launch for many contractions (window-batched SGPR plans): blockIdx.z = item
-    const HyperItem it = items[blockIdx.z];
-    k = it.k; x1 = it.x1; n1 = it.n1; G = it.G; ldg = it.ldg; alpha = it.alpha; gm = it.gm;
-    if (it.x2) { x2 = it.x2; n2 = it.n2; }      // null: the launch's shared x2 / n2 (the frames of the batch)
-    symmetric = it.symmetric; f1 = it.f1; f2 = it.f2; partials = it.partials; gz_part = it.gz; g32 = it.g32;
-  }
+__global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(const HyperItem one, const HyperItem* __restrict__ items,
+                                                                    const double* __restrict__ x2s, int n2s, int wg_rows) {
+  const HyperItem it = gp_item(one, items, blockIdx.z);      // many contractions in one launch: blockIdx.z = item
+  const double* x2 = it.x2 ? it.x2 : x2s;      // x2 null: the launch's shared x2s / n2s (the frames of the batch)
+  const int n2 = it.x2 ? it.n2 : n2s;
   extern __shared__ double smem[];  // [HY_ROWS][2*MPAD] row features | omega[MPAD] | reduction scratch
-  const double* th = k.theta;
+  const double* th = it.k.theta;
   const double var = th[0], ls = th[1];
-  const int m = k.m;
+  const int m = it.k.m;
   const int j = blockIdx.x * HY_THREADS + threadIdx.x;
   const int i0 = blockIdx.y * wg_rows;             // wg_rows <= HY_ROWS rows of x1 per workgroup
-  const int iend = min(i0 + wg_rows, n1);
+  const int iend = min(i0 + wg_rows, it.n1);
   double* fzs = smem;
   __shared__ double etab[GP_EXP_TAB];  // 2^(j/64) for gp_exp_neg
   gp_exp_tab_init(etab);
   __shared__ double row_a[HY_ROWS];   // x1[i] / lengthscale, once per row
-  if (threadIdx.x < HY_ROWS) row_a[threadIdx.x] = (i0 + (int)threadIdx.x < n1) ? x1[i0 + threadIdx.x] / ls : 0.0;
+  if (threadIdx.x < HY_ROWS) row_a[threadIdx.x] = (i0 + (int)threadIdx.x < it.n1) ? it.x1[i0 + threadIdx.x] / ls : 0.0;
   double* omega = smem + (SM ? HY_ROWS * 2 * MPAD : 0);
   double* red = omega + (SM ? MPAD : 0);  // [4 waves][max(2+2m, HY_ROWS)]
   if (SM) {
     for (int t = threadIdx.x; t < HY_ROWS * 2 * MPAD; t += HY_THREADS) {
       int q = t / HY_ROWS, ii = t % HY_ROWS;
-      fzs[ii * 2 * MPAD + q] = (ii < wg_rows && i0 + ii < n1) ? f1[(size_t)q * n1 + i0 + ii] : 0.0;
+      fzs[ii * 2 * MPAD + q] = (ii < wg_rows && i0 + ii < it.n1) ? it.f1[(size_t)q * it.n1 + i0 + ii] : 0.0;
     }
     if ((int)threadIdx.x < MPAD) omega[threadIdx.x] = ((int)threadIdx.x < m) ? 6.283185307179586 * th[2 + m + threadIdx.x] : 0.0;
   }
@@ -208,13 +197,13 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, c
   const int jc = live ? j : n2 - 1;
   const double xb = x2[jc];
   const double b = xb / ls, bb = __dmul_rn(b, b);
-  const double gmj = (gm && live) ? gm[jc] : 0.0;
+  const double gmj = (it.gm && live) ? it.gm[jc] : 0.0;
   double fxc[MPAD], fxs[MPAD];  // column features (static indices only)
   double acc_e[MPAD], acc_f[MPAD];
 #pragma unroll
   for (int q = 0; q < MPAD; q++) {
-    fxc[q] = SM ? f2[(size_t)q * n2 + jc] : 0.0;
-    fxs[q] = SM ? f2[(size_t)(q + MPAD) * n2 + jc] : 0.0;
+    fxc[q] = SM ? it.f2[(size_t)q * n2 + jc] : 0.0;
+    fxs[q] = SM ? it.f2[(size_t)(q + MPAD) * n2 + jc] : 0.0;
     acc_e[q] = 0.0; acc_f[q] = 0.0;
   }
   double acc_v = 0.0, acc_l = 0.0;
@@ -222,18 +211,18 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, c
   const double inv_ls = 1.0 / ls, inv_ls2 = inv_ls * inv_ls;   // hoisted: f64 division is ~25 instructions
 
   for (int i = i0; i < iend; i++) {
-    const double xa = x1[i];
+    const double xa = it.x1[i];
     double w = 0.0;
     if (live) {
-      w = hy_ld(G, (int64_t)i * ldg + j, g32);
-      if (symmetric) w = 0.5 * (w + hy_ld(G, (int64_t)j * ldg + i, g32));
-      if (alpha) w = fma(alpha[i], gmj, w);
+      w = hy_ld(it.G, (int64_t)i * it.ldg + j, it.g32);
+      if (it.symmetric) w = 0.5 * (w + hy_ld(it.G, (int64_t)j * it.ldg + i, it.g32));
+      if (it.alpha) w = fma(it.alpha[i], gmj, w);
     }
     const double a = row_a[i - i0], aa = __dmul_rn(a, a);
     const double r2 = __dadd_rn(__dadd_rn(-2.0 * __dmul_rn(a, b), aa), bb);
     const double d = xa - xb;
     double dz = 0.0;  // w * dK/dx1
-    const int ktype = (KT >= 0) ? KT : k.type;
+    const int ktype = (KT >= 0) ? KT : it.k.type;
     if (!SM && ktype == GP_KERN_RBF) {
       const double e = gp_exp_neg(-0.5 * r2, etab);
       acc_v = fma(w, e, acc_v);
@@ -245,7 +234,7 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, c
       if (SM) {
         // envelope phi(r) and phi'(r): Matern-1/2 (MercerMatern12sm) or Matern-5/2 (Matern52 * MercerCosMix)
         double E, dE;
-        if (k.type == GP_KERN_MERCER_MATERN12SM) { E = gp_exp_neg(-r, etab); dE = -E; }
+        if (it.k.type == GP_KERN_MERCER_MATERN12SM) { E = gp_exp_neg(-r, etab); dE = -E; }
         else {
           const double s5 = 2.23606797749979, e5 = gp_exp_neg(-s5 * r, etab);
           E = (1.0 + s5 * r + (5.0 / 3.0) * r * r) * e5; dE = -(5.0 / 3.0) * r * (1.0 + s5 * r) * e5;
@@ -289,10 +278,10 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, c
   }
   if (GZ) {
     __syncthreads();
-    if ((int)threadIdx.x < wg_rows && i0 + (int)threadIdx.x < n1) {
+    if ((int)threadIdx.x < wg_rows && i0 + (int)threadIdx.x < it.n1) {
       const int t = threadIdx.x;
       double s = (red[0 * HY_ROWS + t] + red[1 * HY_ROWS + t]) + (red[2 * HY_ROWS + t] + red[3 * HY_ROWS + t]);
-      gz_part[(int64_t)blockIdx.x * n1 + i0 + t] = symmetric ? 2.0 * s : s;
+      it.gz[(int64_t)blockIdx.x * it.n1 + i0 + t] = it.symmetric ? 2.0 * s : s;
     }
     __syncthreads();
   }
@@ -316,7 +305,7 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_contract_kernel(DevKern k, c
   if ((int)threadIdx.x < ns) {
     const int t = threadIdx.x;
     const double s = (red[0 * ns + t] + red[1 * ns + t]) + (red[2 * ns + t] + red[3 * ns + t]);
-    partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ns + t] = s;
+    it.partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ns + t] = s;
   }
 }
 
@@ -493,48 +482,37 @@ __device__ __forceinline__ double hyr_swap1(double v) {      // value of the nei
   return __hiloint2double(hi, lo);
 }
 template <int NT, bool M52, bool G32>      // feature tiles (16 wide), Matern-5/2 envelope (else Matern-1/2), float32 strips
-__global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(DevKern k, const double* __restrict__ x1, int n1,
-                                                               const double* __restrict__ x2, int n2,
-                                                               const double* __restrict__ G, int64_t ldg,
-                                                               const double* __restrict__ alpha,
-                                                               const double* __restrict__ gm,
-                                                               const double* __restrict__ Kuf, int64_t ldk,
-                                                               const double* __restrict__ f1,
-                                                               const double* __restrict__ f2,
-                                                               double* __restrict__ partials, int g32, int col_seg,
-                                                               const HyperItem* __restrict__ items) {
-  if (items) {     // one launch for a whole kernel family: blockIdx.y = item (latent GP)
-    const HyperItem it = items[blockIdx.y];
-    k = it.k; x1 = it.x1; n1 = it.n1; G = it.G; ldg = it.ldg; alpha = it.alpha; gm = it.gm;
-    if (it.x2) { x2 = it.x2; n2 = it.n2; }
-    Kuf = it.kvals; ldk = it.ldk; f1 = it.f1; f2 = it.f2; partials = it.partials;
-  }
+__global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(const HyperItem one, const HyperItem* __restrict__ items,
+                                                               const double* __restrict__ x2s, int n2s, int col_seg) {
+  const HyperItem it = gp_item(one, items, blockIdx.y);      // a whole kernel family in one launch: blockIdx.y = item (latent GP)
+  const double* x2 = it.x2 ? it.x2 : x2s;      // x2 null: the launch's shared x2s / n2s (the frames of the batch)
+  const int n2 = it.x2 ? it.n2 : n2s;
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef double d2v __attribute__((ext_vector_type(2)));
   typedef float f2v __attribute__((ext_vector_type(2)));
   typedef const d2v __attribute__((address_space(1))) * pd2v;
   typedef const f2v __attribute__((address_space(1))) * pf2v;
-  const int mpad = ((k.m + 3) / 4) * 4;        // = sm_mpad(m): the feature tables hold 2 mpad rows (cos rows, sin rows)
+  const int mpad = ((it.k.m + 3) / 4) * 4;        // = sm_mpad(m): the feature tables hold 2 mpad rows (cos rows, sin rows)
   const int NF = 2 * mpad;                     // features: phi = 2 q (cos of partial q), 2 q + 1 (sin); NF <= 16 NT
-  const hy_gcptr gG = (hy_gcptr)G, gK = (hy_gcptr)Kuf, gx1 = (hy_gcptr)x1, gx2 = (hy_gcptr)x2, galpha = (hy_gcptr)alpha,
-                 ggm = (hy_gcptr)gm, gf1 = (hy_gcptr)f1, gf2 = (hy_gcptr)f2, th = (hy_gcptr)k.theta;
+  const hy_gcptr gG = (hy_gcptr)it.G, gK = (hy_gcptr)it.kvals, gx1 = (hy_gcptr)it.x1, gx2 = (hy_gcptr)x2, galpha = (hy_gcptr)it.alpha,
+                 ggm = (hy_gcptr)it.gm, gf1 = (hy_gcptr)it.f1, gf2 = (hy_gcptr)it.f2, th = (hy_gcptr)it.k.theta;
   __shared__ double etab[GP_EXP_TAB];
   __shared__ double red[4][2 + 2 * NT * 16];
   gp_exp_tab_init(etab);
   __syncthreads();
   const double var = th[0], ls = th[1];
-  const int m = k.m;
+  const int m = it.k.m;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lc = lane & 15, kq = lane >> 4;
   // a workgroup = four adjacent row tiles walking the SAME columns: the column features each wavefront streams are in
   // the L1 / L2 the other three have just filled (one tile per workgroup, columns in quarters: 1.4x the algorithmic HBM
   // fetch from feature re-reads alone)
-  if (blockIdx.x * 64 >= n1) return;           // (uniform per workgroup: the grid is sized for the largest item)
+  if (blockIdx.x * 64 >= it.n1) return;           // (uniform per workgroup: the grid is sized for the largest item)
   const int i0 = (blockIdx.x * 4 + wave) * 16;
-  const bool tile_on = (i0 < n1);              // a whole wavefront past the last row: no columns, joins the final sum
+  const bool tile_on = (i0 < it.n1);              // a whole wavefront past the last row: no columns, joins the final sum
   const int row = i0 + lc;
-  const bool rowok = (row < n1);
-  const int rowc = rowok ? row : n1 - 1;
+  const bool rowok = (row < it.n1);
+  const int rowc = rowok ? row : it.n1 - 1;
   const double zi = gx1[rowc], a = zi / ls, aa = __dmul_rn(a, a), m2a = -2.0 * a, al = galpha[rowc];
   const double inv_ls = 1.0 / ls;
   // table row of feature phi = 16 t + lc (B operand side: this lane supplies feature lc of every tile)
@@ -550,7 +528,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(DevKern k, const 
   for (int t = 0; t < NT; t++) { TE[t] = d4{0.0, 0.0, 0.0, 0.0}; TD[t] = d4{0.0, 0.0, 0.0, 0.0}; }
   double acc_v = 0.0, acc_l = 0.0;
   const int cw0 = blockIdx.z * col_seg, cw1 = tile_on ? min(n2, cw0 + col_seg) : cw0;
-  const bool vec_ok = ((n2 & 1) == 0) && ((ldg & 1) == 0) && ((ldk & 1) == 0);
+  const bool vec_ok = ((n2 & 1) == 0) && ((it.ldg & 1) == 0) && ((it.ldk & 1) == 0);
   // ---- separable envelope (cov.hip has the argument): with A / B the smallest / largest scaled row input a = z / l of
   // this workgroup's 64 rows, an entry whose column lies at least HYR_SEP below A or above B has
   //     exp(-s r) = exp(-s (a_i - A)) exp(-s (A - b_j))     or     exp(-s (B - a_i)) exp(-s (b_j - B)),   r = |a_i - b_j|
@@ -588,7 +566,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(DevKern k, const 
   // arithmetic of block b (two wavefronts per SIMD do not hide an HBM round trip per 16 columns by themselves), with
   // 16-byte loads and no column predicates; what is left (ragged ends, odd strides) goes block by block, checked.
   struct Blk { double g[4], k[4], x[4], gm[4], bf[NT][4]; };
-  const int64_t rowg = (int64_t)rowc * ldg, rowk = (int64_t)rowc * ldk;
+  const int64_t rowg = (int64_t)rowc * it.ldg, rowk = (int64_t)rowc * it.ldk;
   unsigned foff[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) foff[t] = (unsigned)frow[t] * (unsigned)n2;
@@ -721,7 +699,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(DevKern k, const 
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int ri = i0 + kq + 4 * r;
-      const double zf = (ri < n1 && fok[t]) ? gf1[(size_t)frow[t] * n1 + ri] : 0.0;
+      const double zf = (ri < it.n1 && fok[t]) ? gf1[(size_t)frow[t] * it.n1 + ri] : 0.0;
       se = fma(zf, TE[t][r], se);
       sd = fma(zf, hyr_swap1(TD[t][r]), sd);
     }
@@ -742,7 +720,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(DevKern k, const 
       const int q = tid - 2 - m;
       out = -6.283185307179586 * (tot(2 + NT * 16 + 2 * q + 1) - tot(2 + NT * 16 + 2 * q));
     }
-    partials[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * ns + tid] = out;
+    it.partials[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * ns + tid] = out;
   }
 }
 
@@ -768,31 +746,20 @@ __device__ __forceinline__ hy_gcbytes hyl_uniform(hy_gcbytes p) {
   return (hy_gcbytes)(((uint64_t)hi << 32) | lo);
 }
 template <int NT, bool G32>
-__global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(DevKern k, const double* __restrict__ x1, int n1,
-                                                                    const double* __restrict__ x2, int n2,
-                                                                    const double* __restrict__ G, int64_t ldg,
-                                                                    const double* __restrict__ alpha,
-                                                                    const double* __restrict__ gm,
-                                                                    const double* __restrict__ Kuf, int64_t ldk,
-                                                                    const double* __restrict__ f1,
-                                                                    const double* __restrict__ f2,
-                                                                    double* __restrict__ partials, int col_seg,
-                                                                    const HyperItem* __restrict__ items) {
-  if (items) {     // one launch for a whole kernel family: blockIdx.y = item (latent GP)
-    const HyperItem it = items[blockIdx.y];
-    k = it.k; x1 = it.x1; n1 = it.n1; G = it.G; ldg = it.ldg; alpha = it.alpha; gm = it.gm;
-    if (it.x2) { x2 = it.x2; n2 = it.n2; }
-    Kuf = it.kvals; ldk = it.ldk; f1 = it.f1; f2 = it.f2; partials = it.partials;
-  }
+__global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperItem one, const HyperItem* __restrict__ items,
+                                                                    const double* __restrict__ x2s, int n2s, int col_seg) {
+  const HyperItem it = gp_item(one, items, blockIdx.y);      // a whole kernel family in one launch: blockIdx.y = item (latent GP)
+  const double* x2 = it.x2 ? it.x2 : x2s;      // x2 null: the launch's shared x2s / n2s (the frames of the batch)
+  const int n2 = it.x2 ? it.n2 : n2s;
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef double d2v __attribute__((ext_vector_type(2)));
   typedef float f2v __attribute__((ext_vector_type(2)));
   typedef const d2v __attribute__((address_space(1))) * pd2v;
   typedef const f2v __attribute__((address_space(1))) * pf2v;
-  const int mpad = ((k.m + 3) / 4) * 4;
+  const int mpad = ((it.k.m + 3) / 4) * 4;
   const int NF = 2 * mpad;
-  const hy_gcptr gx1 = (hy_gcptr)x1, gx2 = (hy_gcptr)x2, galpha = (hy_gcptr)alpha, ggm = (hy_gcptr)gm, gf1 = (hy_gcptr)f1,
-                 th = (hy_gcptr)k.theta;
+  const hy_gcptr gx1 = (hy_gcptr)it.x1, gx2 = (hy_gcptr)x2, galpha = (hy_gcptr)it.alpha, ggm = (hy_gcptr)it.gm, gf1 = (hy_gcptr)it.f1,
+                 th = (hy_gcptr)it.k.theta;
   __shared__ double etab[GP_EXP_TAB];
   __shared__ double red[4][2 + 2 * NT * 16];
   __shared__ __attribute__((aligned(16))) double t_cf[HYL_CF_MAX], t_b[HYL_CF_MAX], t_gm[HYL_CF_MAX];
@@ -800,14 +767,14 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(DevKern k, c
   __shared__ double wg_lo[4], wg_hi[4];
   gp_exp_tab_init(etab);
   const double var = th[0], ls = th[1];
-  const int m = k.m;
+  const int m = it.k.m;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lc = lane & 15, kq = lane >> 4;
-  if (blockIdx.x * 64 >= n1) return;           // (uniform per workgroup: the grid is sized for the largest item)
+  if (blockIdx.x * 64 >= it.n1) return;           // (uniform per workgroup: the grid is sized for the largest item)
   const int i0 = (blockIdx.x * 4 + wave) * 16;
-  const bool tile_on = (i0 < n1);              // a whole wavefront past the last row: no columns, joins the final sum
-  const int rowc = tile_on ? i0 + lc : n1 - 1;
+  const bool tile_on = (i0 < it.n1);              // a whole wavefront past the last row: no columns, joins the final sum
+  const int rowc = tile_on ? i0 + lc : it.n1 - 1;
   const double inv_ls = 1.0 / ls;
   const double al = galpha[rowc];
   const double ab_i = gx1[rowc] * inv_ls;      // the scaled input as the covariance build forms it (x * (1 / l))
@@ -850,9 +817,9 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(DevKern k, c
   __syncthreads();
   // ---- the stream -------------------------------------------------------------------------------------------------------
   struct Blk { d2v g[2], kv[2], bf[NT][2]; };
-  const hy_gcbytes bG = (hy_gcbytes)G, bK = (hy_gcbytes)Kuf, bF = (hy_gcbytes)f2;
+  const hy_gcbytes bG = (hy_gcbytes)it.G, bK = (hy_gcbytes)it.kvals, bF = (hy_gcbytes)it.f2;
   constexpr int ES = G32 ? 4 : 8;              // strip element size
-  const uint32_t voG = (uint32_t)(((int64_t)rowc * ldg + 2 * kq) * ES), voK = (uint32_t)(((int64_t)rowc * ldk + 2 * kq) * ES);
+  const uint32_t voG = (uint32_t)(((int64_t)rowc * it.ldg + 2 * kq) * ES), voK = (uint32_t)(((int64_t)rowc * it.ldk + 2 * kq) * ES);
   uint32_t voF[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) voF[t] = (uint32_t)(((int64_t)frow[t] * n2 + 2 * kq) * 8);
@@ -948,7 +915,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(DevKern k, c
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int ri = i0 + kq + 4 * r;
-      const double zf = (ri < n1 && fok[t]) ? gf1[(size_t)frow[t] * n1 + ri] : 0.0;
+      const double zf = (ri < it.n1 && fok[t]) ? gf1[(size_t)frow[t] * it.n1 + ri] : 0.0;
       se = fma(zf, TE[t][r], se);
       sd = fma(zf, hyr_swap1(TD[t][r]), sd);
     }
@@ -970,7 +937,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(DevKern k, c
       const int q = tid - 2 - m;
       out = -6.283185307179586 * (tot(2 + NT * 16 + 2 * q + 1) - tot(2 + NT * 16 + 2 * q));
     }
-    partials[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * ns + tid] = out;
+    it.partials[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * ns + tid] = out;
   }
 }
 
@@ -1019,24 +986,15 @@ static void hyr_geometry(int n1, int n2, int count, int* col_seg, int* nseg) {
 //   phi = exp(-r / ls)  or  (1 + r1) exp(-r1), r1 = sqrt(3) r / ls.
 // Same grid and partial layout as hyper_contract_kernel; m cosines per entry, as the reference.
 template <bool GZ>
-__global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(DevKern k, const double* __restrict__ x1, int n1,
-                                                                 const double* __restrict__ x2, int n2,
-                                                                 const double* __restrict__ G, int64_t ldg,
-                                                                 const double* __restrict__ alpha,
-                                                                 const double* __restrict__ gm, int symmetric,
-                                                                 double* __restrict__ partials,
-                                                                 double* __restrict__ gz_part, int wg_rows, int g32,
-                                                                 const HyperItem* __restrict__ items) {
-  if (items) {
-    const HyperItem it = items[blockIdx.z];
-    k = it.k; x1 = it.x1; n1 = it.n1; G = it.G; ldg = it.ldg; alpha = it.alpha; gm = it.gm;
-    if (it.x2) { x2 = it.x2; n2 = it.n2; }
-    symmetric = it.symmetric; partials = it.partials; gz_part = it.gz; g32 = it.g32;
-  }
+__global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(const HyperItem one, const HyperItem* __restrict__ items,
+                                                                 const double* __restrict__ x2s, int n2s, int wg_rows) {
+  const HyperItem it = gp_item(one, items, blockIdx.z);
+  const double* x2 = it.x2 ? it.x2 : x2s;      // x2 null: the launch's shared x2s / n2s (the frames of the batch)
+  const int n2 = it.x2 ? it.n2 : n2s;
   extern __shared__ double smem[];   // e[m] | omega[m] | reduction scratch [4][max(2+2m, HY_ROWS)]
-  const double* th = k.theta;
+  const double* th = it.k.theta;
   const double var = th[0], ls = th[1];
-  const int m = k.m;
+  const int m = it.k.m;
   double* en = smem;
   double* omega = smem + m;
   double* red = smem + 2 * m;
@@ -1047,11 +1005,11 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(DevKern k, cons
   __syncthreads();
   const int j = blockIdx.x * HY_THREADS + threadIdx.x;
   const int i0 = blockIdx.y * wg_rows;             // wg_rows <= HY_ROWS rows of x1 per workgroup
-  const int iend = min(i0 + wg_rows, n1);
+  const int iend = min(i0 + wg_rows, it.n1);
   const bool live = (j < n2);
   const int jc = live ? j : n2 - 1;
   const double xb = x2[jc];
-  const double gmj = (gm && live) ? gm[jc] : 0.0;
+  const double gmj = (it.gm && live) ? it.gm[jc] : 0.0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ns = 2 + 2 * m;
   double acc_v = 0.0, acc_l = 0.0;
@@ -1061,23 +1019,23 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(DevKern k, cons
   for (int i = i0; i < iend; i++) {
     double w = 0.0;
     if (live) {
-      w = hy_ld(G, (int64_t)i * ldg + j, g32);
-      if (symmetric) w = 0.5 * (w + hy_ld(G, (int64_t)j * ldg + i, g32));
-      if (alpha) w = fma(alpha[i], gmj, w);
+      w = hy_ld(it.G, (int64_t)i * it.ldg + j, it.g32);
+      if (it.symmetric) w = 0.5 * (w + hy_ld(it.G, (int64_t)j * it.ldg + i, it.g32));
+      if (it.alpha) w = fma(it.alpha[i], gmj, w);
     }
-    const double d = __dadd_rn(__dadd_rn(x1[i], -xb), 1e-12);
+    const double d = __dadd_rn(__dadd_rn(it.x1[i], -xb), 1e-12);
     const double r = __dsqrt_rn(__dmul_rn(d, d));
     // dr/dx1 = sign(d).  On the Kuu side z_i enters K_ij as x1 and K_ji as x2: the two contributions are
     // sign(d_ij) and -sign(d_ji); they cancel on the diagonal (d_ii = +1e-12 both ways), where the generic
     // "twice the x1 derivative" shortcut of the symmetric mode would be wrong for this kinked kernel.
     double sg = d < 0.0 ? -1.0 : 1.0;
-    if (symmetric) {
-      const double dji = __dadd_rn(__dadd_rn(xb, -x1[i]), 1e-12);
+    if (it.symmetric) {
+      const double dji = __dadd_rn(__dadd_rn(xb, -it.x1[i]), 1e-12);
       sg = 0.5 * (sg - (dji < 0.0 ? -1.0 : 1.0));
     }
     // envelope phi(r; l), d phi / d r, d phi / d l
     double E, dEr, dEl;
-    if (k.type == GP_KERN_MATERN12SM) {
+    if (it.k.type == GP_KERN_MATERN12SM) {
       E = exp(-(r / ls)); dEr = -E / ls; dEl = E * r / (ls * ls);
     } else {   // Matern32sm: r1 = sqrt(3) r / l
       const double s3 = 1.7320508075688772, r1 = s3 * (r / ls), e1 = exp(-r1);
@@ -1106,10 +1064,10 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(DevKern k, cons
   }
   if (GZ) {
     __syncthreads();
-    if ((int)threadIdx.x < wg_rows && i0 + (int)threadIdx.x < n1) {
+    if ((int)threadIdx.x < wg_rows && i0 + (int)threadIdx.x < it.n1) {
       const int t = threadIdx.x;
       double s = (red[0 * HY_ROWS + t] + red[1 * HY_ROWS + t]) + (red[2 * HY_ROWS + t] + red[3 * HY_ROWS + t]);
-      gz_part[(int64_t)blockIdx.x * n1 + i0 + t] = symmetric ? 2.0 * s : s;
+      it.gz[(int64_t)blockIdx.x * it.n1 + i0 + t] = it.symmetric ? 2.0 * s : s;
     }
     __syncthreads();
   }
@@ -1130,21 +1088,82 @@ __global__ void __launch_bounds__(HY_THREADS) hyper_m12sm_kernel(DevKern k, cons
   if ((int)threadIdx.x < ns) {
     const int t = threadIdx.x;
     const double s = (red[0 * ns + t] + red[1 * ns + t]) + (red[2 * ns + t] + red[3 * ns + t]);
-    partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ns + t] = s;
+    it.partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ns + t] = s;
   }
 }
 
+// ---- host side: one record per contraction, by value for a single problem or from a device array for a family ----
+static void hyper_item_fill(HyperItem* it, DevKern k, const double* x1, int n1, const double* x2, int n2, const double* G, int64_t ldg,
+                            const double* alpha, const double* gm, int symmetric, const double* feat, double* partials, double* gz,
+                            const double* kvals, int64_t ldk, int g32) {
+  const int mp = gp_kern_is_mercer(k.type) ? sm_mpad(k.m) : 0;
+  it->k = k; it->x1 = x1; it->x2 = x2; it->G = G; it->alpha = alpha; it->gm = gm;
+  it->f1 = feat;
+  it->f2 = (x2 == x1 || !feat) ? feat : feat + gp_align_up((size_t)2 * mp * n1, 32);
+  it->partials = partials; it->gz = gz; it->kvals = kvals;
+  it->ldg = ldg; it->ldk = ldk; it->n1 = n1; it->n2 = n2; it->symmetric = symmetric; it->g32 = g32;
+}
+static void hyper_finish_item_fill(HyperFinishItem* it, DevKern k, const double* partials, int nparts, const double* gv_sum,
+                                   double* g_theta, const double* gz_partials, int ncolblocks, int n1, double* g_z) {
+  it->k = k; it->p_uf = partials; it->p_uu = nullptr; it->gv_sum = gv_sum; it->g_theta = g_theta;
+  it->gz_uf = gz_partials; it->gz_uu = nullptr; it->g_z = (g_z && gz_partials) ? g_z : nullptr;
+  it->np_uf = nparts; it->np_uu = 0; it->cb_uf = ncolblocks; it->cb_uu = 0; it->n1 = n1; it->pad = 0;
+}
+
 template <int MPAD, bool SM, int KT = -1>
-static void launch_hyper_t(gp_handle h, dim3 grid, size_t sh, DevKern k, const double* x1, int n1, const double* x2,
-                           int n2, const double* G, int64_t ldg, const double* alpha, const double* gm, int symmetric,
-                           const double* f1, const double* f2, double* partials, double* gz, int wg_rows, int g32,
-                           const HyperItem* items = nullptr) {
-  if (gz)
-    hipLaunchKernelGGL((hyper_contract_kernel<MPAD, SM, true, KT>), grid, dim3(HY_THREADS), sh, h->stream, k, x1, n1, x2,
-                       n2, G, ldg, alpha, gm, symmetric, f1, f2, partials, gz, wg_rows, g32, items);
+static void launch_hyper_t(gp_handle h, dim3 grid, size_t sh, const HyperItem& one, const HyperItem* items, const double* x2s,
+                           int n2s, int wg_rows, bool with_gz) {
+  if (with_gz)
+    hipLaunchKernelGGL((hyper_contract_kernel<MPAD, SM, true, KT>), grid, dim3(HY_THREADS), sh, h->stream, one, items, x2s, n2s, wg_rows);
   else
-    hipLaunchKernelGGL((hyper_contract_kernel<MPAD, SM, false, KT>), grid, dim3(HY_THREADS), sh, h->stream, k, x1, n1,
-                       x2, n2, G, ldg, alpha, gm, symmetric, f1, f2, partials, gz, wg_rows, g32, items);
+    hipLaunchKernelGGL((hyper_contract_kernel<MPAD, SM, false, KT>), grid, dim3(HY_THREADS), sh, h->stream, one, items, x2s, n2s, wg_rows);
+}
+// The generic (vector-pipe) contraction of `count` n1 x n2 problems of one kernel family (type, m): returns the partial
+// records each problem leaves.  x2s / n2s: the frames that items with a null x2 share.
+static int hyper_generic_dispatch(gp_handle h, int type, int m, const HyperItem& one, const HyperItem* items, int count, int n1,
+                                  int n2, const double* x2s, int n2s, bool with_gz) {
+  const int wg_rows = hy_rows_for(n1, n2);
+  dim3 grid((n2 + HY_THREADS - 1) / HY_THREADS, (n1 + wg_rows - 1) / wg_rows, count);
+  const int ns = 2 + 2 * m;
+  const int redw = ns > HY_ROWS ? ns : HY_ROWS;
+  const bool sm = gp_kern_is_mercer(type);
+  const int mp = sm ? sm_mpad(m) : 0;
+  const size_t sh = ((sm ? (size_t)HY_ROWS * 2 * mp + mp : 0) + 4 * (size_t)redw) * sizeof(double);
+  if (gp_kern_is_broadcast(type)) {
+    const size_t shb = (2 * (size_t)m + 4 * (size_t)redw) * sizeof(double);
+    if (with_gz) hipLaunchKernelGGL((hyper_m12sm_kernel<true>), grid, dim3(HY_THREADS), shb, h->stream, one, items, x2s, n2s, wg_rows);
+    else hipLaunchKernelGGL((hyper_m12sm_kernel<false>), grid, dim3(HY_THREADS), shb, h->stream, one, items, x2s, n2s, wg_rows);
+  } else if (!sm) switch (type) {
+    case GP_KERN_MATERN12: launch_hyper_t<1, false, GP_KERN_MATERN12>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case GP_KERN_MATERN32: launch_hyper_t<1, false, GP_KERN_MATERN32>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case GP_KERN_MATERN52: launch_hyper_t<1, false, GP_KERN_MATERN52>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    default: launch_hyper_t<1, false, GP_KERN_RBF>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+  }
+  else switch (mp) {
+    case 4: launch_hyper_t<4, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 8: launch_hyper_t<8, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 12: launch_hyper_t<12, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 16: launch_hyper_t<16, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 20: launch_hyper_t<20, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 24: launch_hyper_t<24, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    case 28: launch_hyper_t<28, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+    default: launch_hyper_t<32, true>(h, grid, sh, one, items, x2s, n2s, wg_rows, with_gz); break;
+  }
+  return grid.x * grid.y;
+}
+// The matrix-core (row-streaming) contraction of `count` Mercer problems, rows_form as hy_rows_form gives it (2: lean):
+// nseg column segments of col_seg columns each.  Returns the partial records each problem leaves.
+static int hyper_rows_dispatch(gp_handle h, int rows_form, int type, int m, bool g32, const HyperItem& one, const HyperItem* items,
+                               int count, int n1, const double* x2s, int n2s, int col_seg, int nseg) {
+  dim3 gridm((n1 + 63) / 64, count, nseg);
+  const int nt = (2 * sm_mpad(m) + 15) / 16;
+#define HYL_GO(NT_, G32_) hipLaunchKernelGGL((hyper_sm_rows_lean_kernel<NT_, G32_>), gridm, dim3(256), 0, h->stream, one, items, x2s, n2s, col_seg)
+#define HYR_GO(NT_, M52_, G32_) hipLaunchKernelGGL((hyper_sm_rows_kernel<NT_, M52_, G32_>), gridm, dim3(256), 0, h->stream, one, items, x2s, n2s, col_seg)
+  if (rows_form == 2) HYL_DISPATCH(HYL_GO, nt, g32);
+  else HYR_DISPATCH(HYR_GO, nt, type != GP_KERN_MERCER_MATERN12SM, g32);
+#undef HYL_GO
+#undef HYR_GO
+  return gridm.x * gridm.z;
 }
 
 gp_status launch_hyper_contract(gp_handle h, DevKern k, const double* x1, int n1, const double* x2, int n2,
@@ -1152,139 +1171,32 @@ gp_status launch_hyper_contract(gp_handle h, DevKern k, const double* x1, int n1
                                 const double* feat, double* partials, int* nparts, double* gz_partials,
                                 const double* kvals, int64_t ldk, int g32) {
   GpTimerScope ts(h, GP_TIMER_HYPER);
-  const int wg_rows = hy_rows_for(n1, n2);
-  if (gp_kern_is_broadcast(k.type)) {
-    dim3 grid((n2 + HY_THREADS - 1) / HY_THREADS, (n1 + wg_rows - 1) / wg_rows);
-    const int ns = 2 + 2 * k.m;
-    const int redw = ns > HY_ROWS ? ns : HY_ROWS;
-    const size_t sh = (2 * (size_t)k.m + 4 * (size_t)redw) * sizeof(double);
-    if (gz_partials)
-      hipLaunchKernelGGL((hyper_m12sm_kernel<true>), grid, dim3(HY_THREADS), sh, h->stream, k, x1, n1, x2, n2, G, ldg,
-                         alpha, gm, symmetric, partials, gz_partials, wg_rows, g32, (const HyperItem*)nullptr);
-    else
-      hipLaunchKernelGGL((hyper_m12sm_kernel<false>), grid, dim3(HY_THREADS), sh, h->stream, k, x1, n1, x2, n2, G, ldg,
-                         alpha, gm, symmetric, partials, gz_partials, wg_rows, g32, (const HyperItem*)nullptr);
-    GP_HIP_CHECK(h, hipGetLastError());
-    if (nparts) *nparts = grid.x * grid.y;
-    return GP_OK;
-  }
+  HyperItem one;
+  hyper_item_fill(&one, k, x1, n1, x2, n2, G, ldg, alpha, gm, symmetric, feat, partials, gz_partials, kvals, ldk, g32);
   const bool sm = gp_kern_is_mercer(k.type);
-  const int mp = sm ? sm_mpad(k.m) : 0;
-  const double* f1 = feat;
-  const double* f2 = (x2 == x1 || !feat) ? feat : feat + gp_align_up((size_t)2 * mp * n1, 32);
-  dim3 grid((n2 + HY_THREADS - 1) / HY_THREADS, (n1 + wg_rows - 1) / wg_rows);
-  const int ns = 2 + 2 * k.m;
-  const int redw = ns > HY_ROWS ? ns : HY_ROWS;
-  size_t sh = ((sm ? (size_t)HY_ROWS * 2 * mp + mp : 0) + 4 * (size_t)redw) * sizeof(double);
-  int col_seg = 0, nseg = 0;
+  int col_seg = 0, nseg = 0, np;
   if (sm) hyr_geometry(n1, n2, 1, &col_seg, &nseg);
   const bool lean_ok = sm && k.type == GP_KERN_MERCER_MATERN12SM && (n1 % 16) == 0 && (n2 % 16) == 0 && col_seg <= HYL_CF_MAX &&
-                       (ldg % 2) == 0 && (ldk % 2) == 0 && ((uintptr_t)G % 16) == 0 && ((uintptr_t)kvals % 16) == 0 && ((uintptr_t)f2 % 16) == 0;
-  const int rows_form = sm ? hy_rows_form((2 * mp + 15) / 16, lean_ok) : 0;
-  if (sm && kvals && !gz_partials && !symmetric && alpha && gm && rows_form > 0) {
-    // Kuf side with the covariance strip still in memory: the matrix-core form (hyper_sm_rows_kernel)
-    dim3 gridm((n1 + 63) / 64, 1, nseg);
-    if (rows_form == 2) {
-#define HYL_ONE(NT_, G32_) hipLaunchKernelGGL((hyper_sm_rows_lean_kernel<NT_, G32_>), gridm, dim3(256), 0, h->stream, k, x1, n1, x2, \
-                                              n2, G, ldg, alpha, gm, kvals, ldk, f1, f2, partials, col_seg, (const HyperItem*)nullptr)
-      HYL_DISPATCH(HYL_ONE, (2 * mp + 15) / 16, g32 != 0);
-#undef HYL_ONE
-      GP_HIP_CHECK(h, hipGetLastError());
-      if (nparts) *nparts = gridm.x * gridm.z;
-      return GP_OK;
-    }
-#define HY_MFMA(NT_, M52_, G32_) hipLaunchKernelGGL((hyper_sm_rows_kernel<NT_, M52_, G32_>), gridm, dim3(256), 0, h->stream, k, x1, \
-                                                  n1, x2, n2, G, ldg, alpha, gm, kvals, ldk, f1, f2, partials, g32, col_seg,    \
-                                                  (const HyperItem*)nullptr)
-    HYR_DISPATCH(HY_MFMA, (2 * mp + 15) / 16, k.type != GP_KERN_MERCER_MATERN12SM, g32 != 0);
-#undef HY_MFMA
-    GP_HIP_CHECK(h, hipGetLastError());
-    if (nparts) *nparts = gridm.x * gridm.z;
-    return GP_OK;
-  }
-#define HY_ARGS grid, sh, k, x1, n1, x2, n2, G, ldg, alpha, gm, symmetric, f1, f2, partials, gz_partials, wg_rows, g32
-  if (!sm) switch (k.type) {
-    case GP_KERN_MATERN12: launch_hyper_t<1, false, GP_KERN_MATERN12>(h, HY_ARGS); break;
-    case GP_KERN_MATERN32: launch_hyper_t<1, false, GP_KERN_MATERN32>(h, HY_ARGS); break;
-    case GP_KERN_MATERN52: launch_hyper_t<1, false, GP_KERN_MATERN52>(h, HY_ARGS); break;
-    default: launch_hyper_t<1, false, GP_KERN_RBF>(h, HY_ARGS); break;
-  }
-  else switch (mp) {
-    case 4: launch_hyper_t<4, true>(h, HY_ARGS); break;
-    case 8: launch_hyper_t<8, true>(h, HY_ARGS); break;
-    case 12: launch_hyper_t<12, true>(h, HY_ARGS); break;
-    case 16: launch_hyper_t<16, true>(h, HY_ARGS); break;
-    case 20: launch_hyper_t<20, true>(h, HY_ARGS); break;
-    case 24: launch_hyper_t<24, true>(h, HY_ARGS); break;
-    case 28: launch_hyper_t<28, true>(h, HY_ARGS); break;
-    default: launch_hyper_t<32, true>(h, HY_ARGS); break;
-  }
-#undef HY_ARGS
+                       (ldg % 2) == 0 && (ldk % 2) == 0 && ((uintptr_t)G % 16) == 0 && ((uintptr_t)kvals % 16) == 0 && ((uintptr_t)one.f2 % 16) == 0;
+  const int rows_form = sm ? hy_rows_form((2 * sm_mpad(k.m) + 15) / 16, lean_ok) : 0;
+  // Kuf side with the covariance strip still in memory: the matrix-core form (hyper_sm_rows_kernel)
+  if (sm && kvals && !gz_partials && !symmetric && alpha && gm && rows_form > 0)
+    np = hyper_rows_dispatch(h, rows_form, k.type, k.m, g32 != 0, one, nullptr, 1, n1, nullptr, 0, col_seg, nseg);
+  else
+    np = hyper_generic_dispatch(h, k.type, k.m, one, nullptr, 1, n1, n2, nullptr, 0, gz_partials != nullptr);
   GP_HIP_CHECK(h, hipGetLastError());
-  if (nparts) *nparts = grid.x * grid.y;
+  if (nparts) *nparts = np;
   return GP_OK;
 }
 
-// g_theta[s] += sum of partials (+ kdiag term); g_z[i] += sum over column blocks
-__global__ void __launch_bounds__(256) hyper_finish_kernel(DevKern k, const double* __restrict__ partials, int nparts,
-                                                           const double* __restrict__ gv_sum,
-                                                           double* __restrict__ g_theta,
-                                                           const double* __restrict__ gz_part, int ncolblocks, int n1,
-                                                           double* __restrict__ g_z) {
-  const int ns = 2 + 2 * k.m;
-  const int s = blockIdx.x;
-  if (s < ns) {
-    __shared__ double red[256];
-    double a = 0.0;
-    for (int c = threadIdx.x; c < nparts; c += 256) a += partials[(int64_t)c * ns + s];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      double v = red[0];
-      if (gv_sum) {  // d kdiag / d theta contribution: kdiag = var (stationary) or var * sum(e)
-        const double gs = gv_sum[0];
-        const bool smk = gp_kern_kdiag_energy(k.type);
-        if (s == 0) {
-          double se = 1.0;
-          if (smk) { se = 0.0; for (int q = 0; q < k.m; q++) se += k.theta[2 + q]; }
-          v += gs * se;
-        } else if (smk && s >= 2 && s < 2 + k.m) {
-          v += gs * k.theta[0];
-        }
-      }
-      g_theta[s] += v;
-    }
-  } else if (g_z && gz_part) {
-    // remaining blocks: z-gradient, 256 rows per block
-    const int i = (blockIdx.x - ns) * 256 + threadIdx.x;
-    if (i < n1) {
-      double a = 0.0;
-      for (int c = 0; c < ncolblocks; c++) a += gz_part[(int64_t)c * n1 + i];
-      g_z[i] += a;
-    }
-  }
-}
-
-gp_status launch_hyper_finish(gp_handle h, DevKern k, const double* partials, int nparts, const double* gv_sum,
-                              double* g_theta, const double* gz_partials, int ncolblocks, int n1, double* g_z) {
-  const int ns = 2 + 2 * k.m;
-  int blocks = ns + ((g_z && gz_partials) ? (n1 + 255) / 256 : 0);
-  hipLaunchKernelGGL(hyper_finish_kernel, dim3(blocks), dim3(256), 0, h->stream, k, partials, nparts, gv_sum, g_theta,
-                     gz_partials, ncolblocks, n1, g_z);
-  GP_HIP_CHECK(h, hipGetLastError());
-  return GP_OK;
-}
-
-// One launch for all latent GPs: block (s, item) adds the Kuf-side and the Kuu-side partial sums (and the Kdiag term)
-// of entry s of that GP's theta gradient; the remaining blocks do the same for its inducing-input gradient.
+// One launch for all latent GPs: block (s, item) adds the Kuf-side and the Kuu-side partial sums (and the Kdiag term, where
+// the item has a gv_sum) of entry s of that GP's theta gradient; the remaining blocks do the same for its inducing-input
+// gradient.  A single finish is the same kernel with its record by value and nothing on the Kuu side.
+//   g_theta[s] += sum of partials (+ kdiag term); g_z[i] += sum over column blocks
 size_t hyper_finish_item_bytes() { return sizeof(HyperFinishItem); }
 
-__global__ void __launch_bounds__(256) hyper_finish_items_kernel(const HyperFinishItem* __restrict__ items) {
-  const HyperFinishItem it = items[blockIdx.y];
+__global__ void __launch_bounds__(256) hyper_finish_items_kernel(const HyperFinishItem one, const HyperFinishItem* __restrict__ items) {
+  const HyperFinishItem it = gp_item(one, items, blockIdx.y);
   const int ns = 2 + 2 * it.k.m;
   const int s = blockIdx.x;
   if (s < ns) {
@@ -1300,18 +1212,21 @@ __global__ void __launch_bounds__(256) hyper_finish_items_kernel(const HyperFini
     }
     if (threadIdx.x == 0) {
       double v = red[0];
-      const double gs = it.gv_sum[0];      // d kdiag / d theta contribution: kdiag = var (stationary) or var * sum(e)
-      const bool smk = gp_kern_kdiag_energy(it.k.type);
-      if (s == 0) {
-        double se = 1.0;
-        if (smk) { se = 0.0; for (int q = 0; q < it.k.m; q++) se += it.k.theta[2 + q]; }
-        v += gs * se;
-      } else if (smk && s >= 2 && s < 2 + it.k.m) {
-        v += gs * it.k.theta[0];
+      if (it.gv_sum) {  // d kdiag / d theta contribution: kdiag = var (stationary) or var * sum(e)
+        const double gs = it.gv_sum[0];
+        const bool smk = gp_kern_kdiag_energy(it.k.type);
+        if (s == 0) {
+          double se = 1.0;
+          if (smk) { se = 0.0; for (int q = 0; q < it.k.m; q++) se += it.k.theta[2 + q]; }
+          v += gs * se;
+        } else if (smk && s >= 2 && s < 2 + it.k.m) {
+          v += gs * it.k.theta[0];
+        }
       }
       it.g_theta[s] += v;
     }
   } else if (it.g_z) {
+    // remaining blocks: z-gradient, 256 rows per block
     const int i = (blockIdx.x - ns) * 256 + threadIdx.x;
     if (i < it.n1) {
       double a = 0.0;
@@ -1322,91 +1237,39 @@ __global__ void __launch_bounds__(256) hyper_finish_items_kernel(const HyperFini
   }
 }
 
-gp_status launch_hyper_finish_items(gp_handle h, const HyperFinishItem* d_items, int count, int maxblocks) {
-  if (count <= 0) return GP_OK;
-  hipLaunchKernelGGL(hyper_finish_items_kernel, dim3(maxblocks, (unsigned)count), dim3(256), 0, h->stream, d_items);
+gp_status launch_hyper_finish(gp_handle h, DevKern k, const double* partials, int nparts, const double* gv_sum,
+                              double* g_theta, const double* gz_partials, int ncolblocks, int n1, double* g_z) {
+  HyperFinishItem one;
+  hyper_finish_item_fill(&one, k, partials, nparts, gv_sum, g_theta, gz_partials, ncolblocks, n1, g_z);
+  const int blocks = 2 + 2 * k.m + (one.g_z ? (n1 + 255) / 256 : 0);
+  hipLaunchKernelGGL(hyper_finish_items_kernel, dim3(blocks), dim3(256), 0, h->stream, one, (const HyperFinishItem*)nullptr);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
 
-// Many contractions of one kernel family (same type and partial count, same n1 x n2) in one launch: the generic
-// (vector-pipe) kernels with an item array.  *nparts = partial records each item leaves.
+gp_status launch_hyper_finish_items(gp_handle h, const HyperFinishItem* d_items, int count, int maxblocks) {
+  if (count <= 0) return GP_OK;
+  hipLaunchKernelGGL(hyper_finish_items_kernel, dim3(maxblocks, (unsigned)count), dim3(256), 0, h->stream, HyperFinishItem{}, d_items);
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
+// Many contractions of one kernel family (same type and partial count, same n1 x n2) in one launch, one item each.
+// *nparts = partial records each item leaves.
 gp_status launch_hyper_contract_items(gp_handle h, int type, int m, const HyperItem* d_items, int count, int n1, int n2,
                                       int with_gz, int* nparts, int use_mfma, const double* x2_shared, int g32_items, int lean_items) {
   if (count <= 0) return GP_OK;
   GpTimerScope ts(h, GP_TIMER_HYPER);
-  int col_seg = 0, nseg = 0;
+  int col_seg = 0, nseg = 0, np;
   if (gp_kern_is_mercer(type)) hyr_geometry(n1, n2, count, &col_seg, &nseg);
   const bool lean_ok = lean_items && type == GP_KERN_MERCER_MATERN12SM && (n1 % 16) == 0 && (n2 % 16) == 0 && col_seg <= HYL_CF_MAX;
   const int rows_form = gp_kern_is_mercer(type) ? hy_rows_form((2 * sm_mpad(m) + 15) / 16, lean_ok) : 0;
-  if (use_mfma && gp_kern_is_mercer(type) && !with_gz && rows_form > 0) {
-    dim3 gridm((n1 + 63) / 64, count, nseg);
-    DevKern k0{type, m, nullptr};
-    if (rows_form == 2) {
-#define HYL_ITEMS(NT_, G32_) hipLaunchKernelGGL((hyper_sm_rows_lean_kernel<NT_, G32_>), gridm, dim3(256), 0, h->stream, k0,        \
-                                                (const double*)nullptr, 0, x2_shared, n2, (const double*)nullptr, (int64_t)0,         \
-                                                (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0,   \
-                                                (const double*)nullptr, (const double*)nullptr, (double*)nullptr, col_seg, d_items)
-      HYL_DISPATCH(HYL_ITEMS, (2 * sm_mpad(m) + 15) / 16, g32_items != 0);
-#undef HYL_ITEMS
-      GP_HIP_CHECK(h, hipGetLastError());
-      if (nparts) *nparts = gridm.x * gridm.z;
-      return GP_OK;
-    }
-#define HYI_MFMA(NT_, M52_, G32_) hipLaunchKernelGGL((hyper_sm_rows_kernel<NT_, M52_, G32_>), gridm, dim3(256), 0, h->stream, k0, \
-                                                   (const double*)nullptr, 0, x2_shared, n2, (const double*)nullptr, (int64_t)0, \
-                                                   (const double*)nullptr, (const double*)nullptr, (const double*)nullptr,       \
-                                                   (int64_t)0, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, \
-                                                   0, col_seg, d_items)
-    HYR_DISPATCH(HYI_MFMA, (2 * sm_mpad(m) + 15) / 16, type != GP_KERN_MERCER_MATERN12SM, g32_items != 0);
-#undef HYI_MFMA
-    GP_HIP_CHECK(h, hipGetLastError());
-    if (nparts) *nparts = gridm.x * gridm.z;
-    return GP_OK;
-  }
-  const int wg_rows = hy_rows_for(n1, n2);
-  dim3 grid((n2 + HY_THREADS - 1) / HY_THREADS, (n1 + wg_rows - 1) / wg_rows, count);
-  const int ns = 2 + 2 * m;
-  const int redw = ns > HY_ROWS ? ns : HY_ROWS;
-  DevKern k0{type, m, nullptr};
-  if (gp_kern_is_broadcast(type)) {
-    const size_t sh = (2 * (size_t)m + 4 * (size_t)redw) * sizeof(double);
-    if (with_gz)
-      hipLaunchKernelGGL((hyper_m12sm_kernel<true>), grid, dim3(HY_THREADS), sh, h->stream, k0, (const double*)nullptr, 0,
-                         x2_shared, n2, (const double*)nullptr, (int64_t)0, (const double*)nullptr,
-                         (const double*)nullptr, 0, (double*)nullptr, (double*)nullptr, wg_rows, 0, d_items);
-    else
-      hipLaunchKernelGGL((hyper_m12sm_kernel<false>), grid, dim3(HY_THREADS), sh, h->stream, k0, (const double*)nullptr, 0,
-                         x2_shared, n2, (const double*)nullptr, (int64_t)0, (const double*)nullptr,
-                         (const double*)nullptr, 0, (double*)nullptr, (double*)nullptr, wg_rows, 0, d_items);
-  } else {
-    const bool sm = gp_kern_is_mercer(type);
-    const int mp = sm ? sm_mpad(m) : 0;
-    const size_t sh = ((sm ? (size_t)HY_ROWS * 2 * mp + mp : 0) + 4 * (size_t)redw) * sizeof(double);
-    double* gzflag = with_gz ? (double*)(uintptr_t)8 : nullptr;     // only its null-ness selects the kernel variant
-#define HYI_ARGS grid, sh, k0, (const double*)nullptr, 0, x2_shared, n2, (const double*)nullptr, (int64_t)0, \
-                 (const double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr,      \
-                 (double*)nullptr, gzflag, wg_rows, 0, d_items
-    if (!sm) switch (type) {
-      case GP_KERN_MATERN12: launch_hyper_t<1, false, GP_KERN_MATERN12>(h, HYI_ARGS); break;
-      case GP_KERN_MATERN32: launch_hyper_t<1, false, GP_KERN_MATERN32>(h, HYI_ARGS); break;
-      case GP_KERN_MATERN52: launch_hyper_t<1, false, GP_KERN_MATERN52>(h, HYI_ARGS); break;
-      default: launch_hyper_t<1, false, GP_KERN_RBF>(h, HYI_ARGS); break;
-    }
-    else switch (mp) {
-      case 4: launch_hyper_t<4, true>(h, HYI_ARGS); break;
-      case 8: launch_hyper_t<8, true>(h, HYI_ARGS); break;
-      case 12: launch_hyper_t<12, true>(h, HYI_ARGS); break;
-      case 16: launch_hyper_t<16, true>(h, HYI_ARGS); break;
-      case 20: launch_hyper_t<20, true>(h, HYI_ARGS); break;
-      case 24: launch_hyper_t<24, true>(h, HYI_ARGS); break;
-      case 28: launch_hyper_t<28, true>(h, HYI_ARGS); break;
-      default: launch_hyper_t<32, true>(h, HYI_ARGS); break;
-    }
-#undef HYI_ARGS
-  }
+  if (use_mfma && gp_kern_is_mercer(type) && !with_gz && rows_form > 0)
+    np = hyper_rows_dispatch(h, rows_form, type, m, g32_items != 0, HyperItem{}, d_items, count, n1, x2_shared, n2, col_seg, nseg);
+  else
+    np = hyper_generic_dispatch(h, type, m, HyperItem{}, d_items, count, n1, n2, x2_shared, n2, with_gz != 0);
   GP_HIP_CHECK(h, hipGetLastError());
-  if (nparts) *nparts = grid.x * grid.y;
+  if (nparts) *nparts = np;
   return GP_OK;
 }
 
@@ -1900,9 +1763,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
         p->h_fin_items.assign((const char*)items.data(), (const char*)items.data() + bytes);
         GP_HIP_CHECK(h, hipMemcpyAsync(d_items, p->h_fin_items.data(), bytes, hipMemcpyHostToDevice, h->stream));
       }
-      hipLaunchKernelGGL(hyper_finish_items_kernel, dim3(maxblocks, (unsigned)items.size()), dim3(256), 0, h->stream,
-                         (const HyperFinishItem*)d_items);
-      GP_HIP_CHECK(h, hipGetLastError());
+      GP_CHECK(launch_hyper_finish_items(h, (const HyperFinishItem*)d_items, (int)items.size(), maxblocks));
     }
   } else if (!white) {
     GP_CHECK(launch_matvec_batched(h, D(S_GQ_MU), G, maxM, 1));

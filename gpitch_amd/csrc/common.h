@@ -190,6 +190,16 @@ struct DevKern {
   const double* theta;  // [variance, lengthscales, e_0.., f_0..]
 };
 static inline DevKern dev_kern(const gp_kernel_desc* k) { return DevKern{k->type, k->num_partials, k->theta}; }
+// The record a kernel works on: `one` by value for a single problem, or entry `idx` of a device array for a family.
+// (A copy under a branch, not `items ? items[idx] : one`: with the select between the kernel-argument segment and global
+// memory, cov_build_kernel compiled to 5-30 more VGPRs and lost a wavefront of occupancy at most partial counts; this form
+// compiles to the register counts the kernels had with every field as an argument of its own.)
+template <typename T>
+__device__ __forceinline__ T gp_item(const T& one, const T* __restrict__ items, unsigned idx) {
+  T it = one;
+  if (items) it = items[idx];
+  return it;
+}
 
 // ---------------------------------------------------------------------------------------------
 // launchers implemented across the .hip files (all enqueue on h->stream)

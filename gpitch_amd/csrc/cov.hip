@@ -49,19 +49,20 @@ __device__ __forceinline__ void cov_store_f32(cov_gptr out, size_t off, int cols
 
 // Precompute spectral-mixture features, zero-padded to MPAD partials so the consumers can unroll without
 // guards:  f[q][j] = sqrt(e_q) cos(2 pi f_q x_j),  f[MPAD + q][j] = sqrt(e_q) sin(2 pi f_q x_j),  q < m;  0 for q >= m.
-__global__ void __launch_bounds__(256) sm_features_kernel(DevKern k, const double* __restrict__ x, int n,
-                                                          double* __restrict__ f, int mpad,
-                                                          const FeatItem* __restrict__ items) {
-  if (items) { const FeatItem it = items[blockIdx.z]; k = it.k; f = it.f; if (it.n >= 0) { x = it.x; n = it.n; } }
+__global__ void __launch_bounds__(256) sm_features_kernel(const FeatItem one, const FeatItem* __restrict__ items,
+                                                          const double* __restrict__ xs, int ns, int mpad) {
+  const FeatItem it = gp_item(one, items, blockIdx.z);
+  const double* x = (it.n >= 0) ? it.x : xs;            // n < 0: every item shares the launch's xs / ns (the frames)
+  const int n = (it.n >= 0) ? it.n : ns;
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   int p = blockIdx.y;
   if (j >= n) return;
   double c = 0.0, s = 0.0;
-  if (p < k.m) {
-    cov_sm_feature(k.theta, k.m, p, x[j], &c, &s);
+  if (p < it.k.m) {
+    cov_sm_feature(it.k.theta, it.k.m, p, x[j], &c, &s);
   }
-  f[(size_t)p * n + j] = c;
-  f[(size_t)(p + mpad) * n + j] = s;
+  it.f[(size_t)p * n + j] = c;
+  it.f[(size_t)(p + mpad) * n + j] = s;
 }
 
 // MODE 0: stationary (Matern12/32/52/RBF); MODE 1: Mercer spectral mixture (feature form) with envelope ENV
@@ -69,45 +70,37 @@ __global__ void __launch_bounds__(256) sm_features_kernel(DevKern k, const doubl
 // MODE 2: broadcast cosine form (Matern12sm, Matern32sm).  CPT = columns per thread (16-byte stores when 2).
 // MODE 0 takes the stationary kernel type as ENV, so the row loop carries no type switch.
 template <int MODE, int CPT, int MPAD, int ENV = 0>
-__global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const double* __restrict__ x1, int n1,
-                                                                const double* __restrict__ x2, int n2,
-                                                                double* __restrict__ out, int64_t ld,
-                                                                int accumulate, double diag_add,
-                                                                const double* __restrict__ f1,
-                                                                const double* __restrict__ f2, int vec_ok,
-                                                                const CovItem* __restrict__ items, int wg_rows, int f32out) {
+__global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(const CovItem one, const CovItem* __restrict__ items,
+                                                                const double* __restrict__ x2s, int n2s, int wg_rows) {
   // wg_rows: rows handled per workgroup (<= COV_ROWS; fewer for small matrices, which otherwise occupy a handful of CUs)
-  if (items) {
-    const CovItem it = items[blockIdx.z];
-    k = it.k; x1 = it.x1; n1 = it.n1; out = it.out; ld = it.ld;
-    if (it.n2 >= 0) { x2 = it.x2; n2 = it.n2; }         // n2 < 0: every item shares the launch's x2 / n2 (the frames)
-    accumulate = it.accumulate; diag_add = it.diag_add; f1 = it.f1; f2 = it.f2; vec_ok = it.vec_ok; f32out = it.f32out;
-    if ((int)(blockIdx.y * wg_rows) >= n1) return;       // the grid is sized for the largest item
-  }
-  const cov_gcptr gx1 = (cov_gcptr)x1, gx2 = (cov_gcptr)x2, gf1 = (cov_gcptr)f1, gf2 = (cov_gcptr)f2;
-  const cov_gptr gout = (cov_gptr)out;
+  const CovItem it = gp_item(one, items, blockIdx.z);
+  if ((int)(blockIdx.y * wg_rows) >= it.n1) return;      // the grid is sized for the largest item
+  const double* x2 = (it.n2 >= 0) ? it.x2 : x2s;         // n2 < 0: every item shares the launch's x2s / n2s (the frames)
+  const int n2 = (it.n2 >= 0) ? it.n2 : n2s;
+  const cov_gcptr gx1 = (cov_gcptr)it.x1, gx2 = (cov_gcptr)x2, gf1 = (cov_gcptr)it.f1, gf2 = (cov_gcptr)it.f2;
+  const cov_gptr gout = (cov_gptr)it.out;
   extern __shared__ double smem[];  // MODE 1: z-features for this block's rows [COV_ROWS][2m]
   __shared__ double row_a[COV_ROWS];  // x1[i] / lengthscale (the exact quotient, computed once per row, not per entry)
   __shared__ double etab[GP_EXP_TAB];
   gp_exp_tab_init(etab);
-  const double* th = k.theta;
+  const double* th = it.k.theta;
   const double var = th[0];
   const double ls = th[1];
-  const int m = k.m;
+  const int m = it.k.m;
   const int j0 = (blockIdx.x * COV_THREADS + threadIdx.x) * CPT;
   const int i0 = blockIdx.y * wg_rows;
-  const int iend = min(i0 + wg_rows, n1);
+  const int iend = min(i0 + wg_rows, it.n1);
   // K(x, x) + diag_add I: only the workgroups whose column range meets their row range carry the diagonal test
   const int jb0 = blockIdx.x * COV_THREADS * CPT;
-  const bool self_cov = (x2 == x1) && (diag_add != 0.0) && (jb0 < i0 + wg_rows) && (jb0 + COV_THREADS * CPT > i0);
+  const bool self_cov = (x2 == it.x1) && (it.diag_add != 0.0) && (jb0 < i0 + wg_rows) && (jb0 + COV_THREADS * CPT > i0);
 
-  if (threadIdx.x < COV_ROWS) row_a[threadIdx.x] = (i0 + (int)threadIdx.x < n1) ? gx1[i0 + threadIdx.x] / th[1] : 0.0;   // (rows beyond wg_rows unused)
+  if (threadIdx.x < COV_ROWS) row_a[threadIdx.x] = (i0 + (int)threadIdx.x < it.n1) ? gx1[i0 + threadIdx.x] / th[1] : 0.0;   // (rows beyond wg_rows unused)
   if (MODE != 1) __syncthreads();
   if (MODE == 1) {
     // stage this block's row features: smem[(i - i0) * 2*MPAD + q] = f1[q][i]
     for (int t = threadIdx.x; t < COV_ROWS * 2 * MPAD; t += COV_THREADS) {
       int q = t / COV_ROWS, ii = t % COV_ROWS;
-      smem[ii * 2 * MPAD + q] = (ii < wg_rows && i0 + ii < n1) ? gf1[(size_t)q * n1 + i0 + ii] : 0.0;
+      smem[ii * 2 * MPAD + q] = (ii < wg_rows && i0 + ii < it.n1) ? gf1[(size_t)q * it.n1 + i0 + ii] : 0.0;
     }
     __syncthreads();
   }
@@ -149,18 +142,18 @@ __global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const
 #pragma unroll
       for (int c = 0; c < CPT; c++) {
         res[c] = cov_mercer_entry(ENV, var, a, aa, b[c], bb[c], acc[c], etab);
-        if (self_cov && i == j0 + c) res[c] += diag_add;
+        if (self_cov && i == j0 + c) res[c] += it.diag_add;
       }
-      if (f32out) { cov_store_f32<CPT>(gout, (size_t)i * ld + j0, n2 - j0, res, accumulate, vec_ok); continue; }
-      const cov_gptr o = gout + (size_t)i * ld + j0;
-      if (CPT == 2 && vec_ok && j0 + 1 < n2) {
+      if (it.f32out) { cov_store_f32<CPT>(gout, (size_t)i * it.ld + j0, n2 - j0, res, it.accumulate, it.vec_ok); continue; }
+      const cov_gptr o = gout + (size_t)i * it.ld + j0;
+      if (CPT == 2 && it.vec_ok && j0 + 1 < n2) {
         cov_d2 v = cov_d2{res[0], res[CPT - 1]};
-        if (accumulate) { const cov_d2 old = *(cov_gptr2)o; v.x += old.x; v.y += old.y; }
+        if (it.accumulate) { const cov_d2 old = *(cov_gptr2)o; v.x += old.x; v.y += old.y; }
         *(cov_gptr2)o = v;
       } else {
 #pragma unroll
         for (int c = 0; c < CPT; c++)
-          if (j0 + c < n2) o[c] = accumulate ? o[c] + res[c] : res[c];
+          if (j0 + c < n2) o[c] = it.accumulate ? o[c] + res[c] : res[c];
       }
     }
     return;
@@ -175,25 +168,25 @@ __global__ void __launch_bounds__(COV_THREADS) cov_build_kernel(DevKern k, const
       if (MODE == 0) {
         double a = row_a[i - i0], aa = __dmul_rn(a, a);
   #pragma unroll
-        for (int c = 0; c < CPT; c++) res[c] = stat_profile(MODE == 0 ? ENV : k.type, r2_expand(a, aa, b[c], bb[c]), var, etab);
+        for (int c = 0; c < CPT; c++) res[c] = stat_profile(MODE == 0 ? ENV : it.k.type, r2_expand(a, aa, b[c], bb[c]), var, etab);
       } else {
   #pragma unroll
-        for (int c = 0; c < CPT; c++) res[c] = cov_broadcast_entry(k.type, th, m, var, ls, xa, xb[c]);
+        for (int c = 0; c < CPT; c++) res[c] = cov_broadcast_entry(it.k.type, th, m, var, ls, xa, xb[c]);
       }
   #pragma unroll
       for (int c = 0; c < CPT; c++)
-        if (DIAG && i == j0 + c) res[c] += diag_add;
-      if (f32out) { cov_store_f32<CPT>(gout, (size_t)i * ld + j0, n2 - j0, res, accumulate, vec_ok); continue; }
-      const cov_gptr o = gout + (size_t)i * ld + j0;
-      if (CPT == 2 && vec_ok && j0 + 1 < n2) {
+        if (DIAG && i == j0 + c) res[c] += it.diag_add;
+      if (it.f32out) { cov_store_f32<CPT>(gout, (size_t)i * it.ld + j0, n2 - j0, res, it.accumulate, it.vec_ok); continue; }
+      const cov_gptr o = gout + (size_t)i * it.ld + j0;
+      if (CPT == 2 && it.vec_ok && j0 + 1 < n2) {
         cov_d2 v = cov_d2{res[0], res[CPT - 1]};
-        if (accumulate) { const cov_d2 old = *(cov_gptr2)o; v.x += old.x; v.y += old.y; }
-        if (GP_COV_NT_STORE && !accumulate) __builtin_nontemporal_store(v, (cov_gptr2)o);
+        if (it.accumulate) { const cov_d2 old = *(cov_gptr2)o; v.x += old.x; v.y += old.y; }
+        if (GP_COV_NT_STORE && !it.accumulate) __builtin_nontemporal_store(v, (cov_gptr2)o);
         else *(cov_gptr2)o = v;
       } else {
   #pragma unroll
         for (int c = 0; c < CPT; c++)
-          if (j0 + c < n2) o[c] = accumulate ? o[c] + res[c] : res[c];
+          if (j0 + c < n2) o[c] = it.accumulate ? o[c] + res[c] : res[c];
       }
     }
   };
@@ -216,16 +209,49 @@ size_t kernel_build_feat_ws_doubles(int m, int n1, int n2) {
 }
 
 template <int MPAD>
-static void launch_mercer(gp_handle h, dim3 grid, DevKern k, const double* x1, int n1, const double* x2, int n2,
-                          double* out, int64_t ld, int accumulate, double diag_add, const double* f1, const double* f2,
-                          int vec_ok, const CovItem* items, int rows = COV_ROWS, int f32out = 0) {
+static void launch_mercer(gp_handle h, int type, dim3 grid, const CovItem& one, const CovItem* items, const double* x2s,
+                          int n2s, int rows) {
   size_t sh = (size_t)COV_ROWS * 2 * MPAD * sizeof(double);
-  if (k.type == GP_KERN_MERCER_MATERN12SM)
-    hipLaunchKernelGGL((cov_build_kernel<1, 2, MPAD, 0>), grid, dim3(COV_THREADS), sh, h->stream, k, x1, n1, x2, n2, out,
-                       ld, accumulate, diag_add, f1, f2, vec_ok, items, rows, f32out);
+  if (type == GP_KERN_MERCER_MATERN12SM)
+    hipLaunchKernelGGL((cov_build_kernel<1, 2, MPAD, 0>), grid, dim3(COV_THREADS), sh, h->stream, one, items, x2s, n2s, rows);
   else
-    hipLaunchKernelGGL((cov_build_kernel<1, 2, MPAD, 2>), grid, dim3(COV_THREADS), sh, h->stream, k, x1, n1, x2, n2, out,
-                       ld, accumulate, diag_add, f1, f2, vec_ok, items, rows, f32out);
+    hipLaunchKernelGGL((cov_build_kernel<1, 2, MPAD, 2>), grid, dim3(COV_THREADS), sh, h->stream, one, items, x2s, n2s, rows);
+}
+template <int KT>
+static void launch_stat(gp_handle h, dim3 grid, const CovItem& one, const CovItem* items, const double* x2s, int n2s, int rows) {
+  hipLaunchKernelGGL((cov_build_kernel<0, 2, 1, KT>), grid, dim3(COV_THREADS), 0, h->stream, one, items, x2s, n2s, rows);
+}
+
+// The generic build of `count` matrices of one kernel family (type, m), `rows` rows per workgroup: the record `one` by value
+// (items == nullptr, count == 1) or one record per blockIdx.z from `items`; x2s / n2s are the frames that items with
+// n2 < 0 share.  Any type that is neither Mercer nor broadcast takes the stationary kernels (callers have checked it).
+static void cov_build_dispatch(gp_handle h, int type, int m, const CovItem& one, const CovItem* items, int count, int max_n1,
+                               int max_n2, int rows, const double* x2s, int n2s) {
+  const int cpt = gp_kern_is_broadcast(type) ? 1 : 2;
+  dim3 grid((max_n2 + COV_THREADS * cpt - 1) / (COV_THREADS * cpt), (max_n1 + rows - 1) / rows, count);
+  if (gp_kern_is_mercer(type)) switch (sm_mpad(m)) {
+    case 4: launch_mercer<4>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 8: launch_mercer<8>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 12: launch_mercer<12>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 16: launch_mercer<16>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 20: launch_mercer<20>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 24: launch_mercer<24>(h, type, grid, one, items, x2s, n2s, rows); break;
+    case 28: launch_mercer<28>(h, type, grid, one, items, x2s, n2s, rows); break;
+    default: launch_mercer<32>(h, type, grid, one, items, x2s, n2s, rows); break;
+  }
+  else if (gp_kern_is_broadcast(type))
+    hipLaunchKernelGGL((cov_build_kernel<2, 1, 1>), grid, dim3(COV_THREADS), 0, h->stream, one, items, x2s, n2s, rows);
+  else switch (type) {
+    case GP_KERN_MATERN12: launch_stat<GP_KERN_MATERN12>(h, grid, one, items, x2s, n2s, rows); break;
+    case GP_KERN_MATERN32: launch_stat<GP_KERN_MATERN32>(h, grid, one, items, x2s, n2s, rows); break;
+    case GP_KERN_MATERN52: launch_stat<GP_KERN_MATERN52>(h, grid, one, items, x2s, n2s, rows); break;
+    default: launch_stat<GP_KERN_RBF>(h, grid, one, items, x2s, n2s, rows); break;
+  }
+}
+// `count` feature tables of up to max_n points each, one record by value or one per blockIdx.z
+static void sm_features_dispatch(gp_handle h, const FeatItem& one, const FeatItem* items, int count, int max_n, int mpad,
+                                 const double* xs, int ns) {
+  hipLaunchKernelGGL(sm_features_kernel, dim3((max_n + 255) / 256, mpad, count), dim3(256), 0, h->stream, one, items, xs, ns, mpad);
 }
 
 // rows per workgroup: the full COV_ROWS for strips; small matrices (window-sized problems, Kuu) get more, smaller
@@ -369,57 +395,26 @@ gp_status launch_kernel_build(gp_handle h, DevKern k, const double* x1, int n1, 
   // feat_ready: the feature tables in feat_ws (layout of launch_sm_features: x1 block, then x2 block) are current
   if (n1 <= 0 || n2 <= 0) return GP_OK;
   if (x2 == nullptr) { x2 = x1; n2 = n1; }
-  const int vec_ok = ((ld % 2) == 0) && ((((uintptr_t)out) & 15) == 0);
   if (f32out && x2 == x1 && diag_add != 0.0) return gp_fail(h, GP_ERR_UNSUPPORTED, "float32 output is for Kuf strips, not Kuu");
   const bool big = (int64_t)n1 * n2 >= (1 << 20);   // M x N strips; the small Kuu builds are booked elsewhere
   GpTimerScope ts(h, !big ? GP_TIMER_SMALL_GEMM
                           : (gp_kern_is_mercer(k.type) ? GP_TIMER_KUF_BUILD_SM : GP_TIMER_KUF_BUILD));
+  CovItem one;
+  cov_item_fill(&one, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, feat_ws, f32out);
   if (gp_kern_is_mercer(k.type)) {
     if (k.m < 1 || k.m > 32) return gp_fail(h, GP_ERR_UNSUPPORTED, "num_partials must be in [1, 32]");
     if (!feat_ws) return gp_fail(h, GP_ERR_WORKSPACE, "feature workspace missing");
     const int mp = sm_mpad(k.m);
-    double* f1 = feat_ws;
-    double* f2 = (x2 == x1) ? f1 : feat_ws + gp_align_up((size_t)2 * mp * n1, 32);
-    dim3 g1((n1 + 255) / 256, mp);
-    if (!feat_ready)
-      hipLaunchKernelGGL(sm_features_kernel, g1, dim3(256), 0, h->stream, k, x1, n1, f1, mp, (const FeatItem*)nullptr);
-    if (x2 != x1 && !feat_ready) {
-      dim3 g2((n2 + 255) / 256, mp);
-      hipLaunchKernelGGL(sm_features_kernel, g2, dim3(256), 0, h->stream, k, x2, n2, f2, mp, (const FeatItem*)nullptr);
-    }
-    const int rows = cov_rows_for(n1, n2);
-    dim3 grid((n2 + COV_THREADS * 2 - 1) / (COV_THREADS * 2), (n1 + rows - 1) / rows);
-    switch (mp) {
-      case 4: launch_mercer<4>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 8: launch_mercer<8>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 12: launch_mercer<12>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 16: launch_mercer<16>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 20: launch_mercer<20>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 24: launch_mercer<24>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      case 28: launch_mercer<28>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
-      default: launch_mercer<32>(h, grid, k, x1, n1, x2, n2, out, ld, accumulate, diag_add, f1, f2, vec_ok, (const CovItem*)nullptr, rows, f32out); break;
+    if (!feat_ready) {
+      sm_features_dispatch(h, FeatItem{k, x1, feat_ws, n1, 0}, nullptr, 1, n1, mp, nullptr, 0);
+      if (x2 != x1) sm_features_dispatch(h, FeatItem{k, x2, (double*)one.f2, n2, 0}, nullptr, 1, n2, mp, nullptr, 0);
     }
   } else if (gp_kern_is_broadcast(k.type)) {
     if (k.m < 1) return gp_fail(h, GP_ERR_BAD_ARG, "num_partials must be >= 1");
-    const int rows = cov_rows_for(n1, n2);
-    dim3 grid((n2 + COV_THREADS - 1) / COV_THREADS, (n1 + rows - 1) / rows);
-    hipLaunchKernelGGL((cov_build_kernel<2, 1, 1>), grid, dim3(COV_THREADS), 0, h->stream, k, x1, n1, x2, n2, out, ld,
-                       accumulate, diag_add, nullptr, nullptr, vec_ok, (const CovItem*)nullptr, rows, f32out);
-  } else if (k.type >= GP_KERN_MATERN12 && k.type <= GP_KERN_RBF) {
-    const int rows = cov_rows_for(n1, n2);
-    dim3 grid((n2 + COV_THREADS * 2 - 1) / (COV_THREADS * 2), (n1 + rows - 1) / rows);
-#define COV_STAT(T) hipLaunchKernelGGL((cov_build_kernel<0, 2, 1, T>), grid, dim3(COV_THREADS), 0, h->stream, k, x1, n1, \
-                                      x2, n2, out, ld, accumulate, diag_add, nullptr, nullptr, vec_ok, (const CovItem*)nullptr, rows, f32out)
-    switch (k.type) {
-      case GP_KERN_MATERN12: COV_STAT(GP_KERN_MATERN12); break;
-      case GP_KERN_MATERN32: COV_STAT(GP_KERN_MATERN32); break;
-      case GP_KERN_MATERN52: COV_STAT(GP_KERN_MATERN52); break;
-      default: COV_STAT(GP_KERN_RBF); break;
-    }
-#undef COV_STAT
-  } else {
+  } else if (!(k.type >= GP_KERN_MATERN12 && k.type <= GP_KERN_RBF)) {
     return gp_fail(h, GP_ERR_BAD_ARG, "unknown kernel type");
   }
+  cov_build_dispatch(h, k.type, k.m, one, nullptr, 1, n1, n2, cov_rows_for(n1, n2), nullptr, 0);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
@@ -840,8 +835,7 @@ void cov_item_fill(CovItem* it, DevKern k, const double* x1, int n1, const doubl
 gp_status launch_sm_features_items(gp_handle h, const FeatItem* d_items, int count, int max_n, int mpad,
                                    const double* x_shared, int n_shared) {
   if (count <= 0 || max_n <= 0) return GP_OK;
-  hipLaunchKernelGGL(sm_features_kernel, dim3((max_n + 255) / 256, mpad, count), dim3(256), 0, h->stream, DevKern{0, 0, nullptr},
-                     x_shared, n_shared, (double*)nullptr, mpad, d_items);
+  sm_features_dispatch(h, FeatItem{}, d_items, count, max_n, mpad, x_shared, n_shared);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
@@ -853,7 +847,6 @@ gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem*
   if (count <= 0 || max_n1 <= 0 || max_n2 <= 0) return GP_OK;
   const bool big = (int64_t)max_n1 * max_n2 >= (1 << 20);
   GpTimerScope ts(h, !big ? GP_TIMER_SMALL_GEMM : (gp_kern_is_mercer(type) ? GP_TIMER_KUF_BUILD_SM : GP_TIMER_KUF_BUILD));
-  DevKern k0{type, m, nullptr};
   if (gp_kern_is_mercer(type)) {
     if (m < 1 || m > 32) return gp_fail(h, GP_ERR_UNSUPPORTED, "num_partials must be in [1, 32]");
     if (x2_shared && big) {
@@ -898,37 +891,8 @@ gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem*
       GP_HIP_CHECK(h, hipGetLastError());
       return GP_OK;
     }
-    dim3 grid((max_n2 + COV_THREADS * 2 - 1) / (COV_THREADS * 2), (max_n1 + COV_ROWS - 1) / COV_ROWS, count);
-#define COV_MERCER_ITEMS(MP) launch_mercer<MP>(h, grid, k0, nullptr, 0, x2_shared, n2_shared, nullptr, 0, 0, 0.0, nullptr, nullptr, 0, d_items)
-    switch (sm_mpad(m)) {
-      case 4: COV_MERCER_ITEMS(4); break;
-      case 8: COV_MERCER_ITEMS(8); break;
-      case 12: COV_MERCER_ITEMS(12); break;
-      case 16: COV_MERCER_ITEMS(16); break;
-      case 20: COV_MERCER_ITEMS(20); break;
-      case 24: COV_MERCER_ITEMS(24); break;
-      case 28: COV_MERCER_ITEMS(28); break;
-      default: COV_MERCER_ITEMS(32); break;
-    }
-#undef COV_MERCER_ITEMS
-  } else if (gp_kern_is_broadcast(type)) {
-    dim3 grid((max_n2 + COV_THREADS - 1) / COV_THREADS, (max_n1 + COV_ROWS - 1) / COV_ROWS, count);
-    hipLaunchKernelGGL((cov_build_kernel<2, 1, 1>), grid, dim3(COV_THREADS), 0, h->stream, k0, (const double*)nullptr, 0,
-                       x2_shared, n2_shared, (double*)nullptr, (int64_t)0, 0, 0.0, (const double*)nullptr,
-                       (const double*)nullptr, 0, d_items, COV_ROWS, 0);
-  } else {
-    dim3 grid((max_n2 + COV_THREADS * 2 - 1) / (COV_THREADS * 2), (max_n1 + COV_ROWS - 1) / COV_ROWS, count);
-#define COV_STAT_ITEMS(T) hipLaunchKernelGGL((cov_build_kernel<0, 2, 1, T>), grid, dim3(COV_THREADS), 0, h->stream, k0, \
-                                            (const double*)nullptr, 0, x2_shared, n2_shared, (double*)nullptr,             \
-                                            (int64_t)0, 0, 0.0, (const double*)nullptr, (const double*)nullptr, 0, d_items, COV_ROWS, 0)
-    switch (type) {
-      case GP_KERN_MATERN12: COV_STAT_ITEMS(GP_KERN_MATERN12); break;
-      case GP_KERN_MATERN32: COV_STAT_ITEMS(GP_KERN_MATERN32); break;
-      case GP_KERN_MATERN52: COV_STAT_ITEMS(GP_KERN_MATERN52); break;
-      default: COV_STAT_ITEMS(GP_KERN_RBF); break;
-    }
-#undef COV_STAT_ITEMS
   }
+  cov_build_dispatch(h, type, m, CovItem{}, d_items, count, max_n1, max_n2, COV_ROWS, x2_shared, n2_shared);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }
@@ -937,11 +901,9 @@ gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem*
 gp_status launch_sm_features(gp_handle h, DevKern k, const double* x1, int n1, const double* x2, int n2, double* feat_ws) {
   if (!gp_kern_is_mercer(k.type)) return GP_OK;
   const int mp = sm_mpad(k.m);
-  double* f1 = feat_ws;
-  double* f2 = feat_ws + gp_align_up((size_t)2 * mp * n1, 32);
-  hipLaunchKernelGGL(sm_features_kernel, dim3((n1 + 255) / 256, mp), dim3(256), 0, h->stream, k, x1, n1, f1, mp, (const FeatItem*)nullptr);
+  sm_features_dispatch(h, FeatItem{k, x1, feat_ws, n1, 0}, nullptr, 1, n1, mp, nullptr, 0);
   if (x2 && x2 != x1)
-    hipLaunchKernelGGL(sm_features_kernel, dim3((n2 + 255) / 256, mp), dim3(256), 0, h->stream, k, x2, n2, f2, mp, (const FeatItem*)nullptr);
+    sm_features_dispatch(h, FeatItem{k, x2, feat_ws + gp_align_up((size_t)2 * mp * n1, 32), n2, 0}, nullptr, 1, n2, mp, nullptr, 0);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }

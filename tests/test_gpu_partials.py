@@ -25,7 +25,8 @@ share m.  What each case reaches:
      activations [matern32, matern12, matern32, rbf, matern52, matern32] (test_pdgp_mixed_*): more than two families,
      so the general side-stream schedule; whitened with z fixed (batched families: lean NT = 1 / 2 / 3 and
      hyper_contract_kernel<32, ..>), z trained (per-GP contractions with inducing-input gradients), unwhitened, inducing
-     counts that differ inside a family (m = [9, 20, 9] at M = [48, 64, 80]: the per-GP path, row / lean forms), and
+     counts that differ inside a family (m = [9, 20, 9] at M = [48, 64, 80]: the per-GP path, lean form; m = [9, 9] at
+     M = [72, 56], N = 2004: the per-GP path, row form), and
      all-float32 / (float64, float32) strips (the G32 variants hyper_sm_rows_lean_kernel<NT, true>).  Predictions of the
      mixed model against the oracle.
   4. sgpr_ss, mixed m per source (test_sgpr_mixed_partials): m = [1, 3, 4, 2] hyper_contract_sum_kernel<4> (the fused
@@ -258,12 +259,15 @@ def test_pdgp_mixed_unwhitened(gp_handle):
     _check_f64(gp_handle, prob, whiten=False)
 
 
-def test_pdgp_mixed_inducing_counts_inside_a_family(gp_handle):
+@pytest.mark.parametrize("N,ms,Ms", [(2048, [9, 20, 9], [48, 64, 80]), (2004, [9, 9], [72, 56])],
+                         ids=["lean_N2048", "rows_ragged_N2004"])
+def test_pdgp_mixed_inducing_counts_inside_a_family(gp_handle, N, ms, Ms):
     """m = [9, 20, 9] at M = [48, 64, 80] (activations too): the m = 9 family holds two inducing counts, so it takes the
-    per-GP path (hyper_sm_rows_lean_kernel<2, false>: M and N multiples of 16); m = 20 alone is batched (lean NT = 3)"""
-    Ms = [48, 64, 80]
-    com = [_sm("mercer_matern12sm", m, _f0(i)) for i, m in enumerate([9, 20, 9])]
-    prob = _problem(2048, 80, com, act=["matern32", "matern12", "matern32"], seed=14)
+    per-GP path (hyper_sm_rows_lean_kernel<2, false>: M and N multiples of 16); m = 20 alone is batched (lean NT = 3).
+    m = [9, 9] at M = [72, 56], N = 2004 (no multiple of 16): the per-GP path with hyper_sm_rows_kernel<2, false, false>,
+    its record passed by value"""
+    com = [_sm("mercer_matern12sm", m, _f0(i)) for i, m in enumerate(ms)]
+    prob = _problem(N, max(Ms), com, act=["matern32", "matern12", "matern32"][:len(ms)], seed=14)
     for p, M in enumerate(Ms):
         _set_inducing(prob, "act", p, M, 100 + p)
         _set_inducing(prob, "com", p, M, 200 + p)
