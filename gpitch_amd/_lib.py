@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
     "gp_pdgp_create", "gp_pdgp_destroy", "gp_pdgp_num_params", "gp_pdgp_layout", "gp_pdgp_workspace_bytes",
     "gp_pdgp_set_workspace", "gp_pdgp_set_precision", "gp_pdgp_set_gp_precision", "gp_pdgp_set_grad_needs", "gp_pdgp_set_overlap", "gp_pdgp_elbo", "gp_pdgp_elbo_begin", "gp_pdgp_elbo_end", "gp_pdgp_create_subset", "gp_pdgp_cond_begin", "gp_pdgp_cond_end", "gp_pdgp_predict", "gp_pdgp_predict_reuse",
+    "gp_pdgp_sample", "gp_pdgp_sample_reuse", "gp_pdgp_sample_workspace_bytes",
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
     "gp_sgpr_create", "gp_sgpr_destroy", "gp_sgpr_num_params", "gp_sgpr_workspace_bytes", "gp_sgpr_set_workspace", "gp_sgpr_set_precision",
     "gp_sgpr_bound", "gp_sgpr_bound_grad", "gp_sgpr_residual_grad", "gp_sgpr_exchange_doubles", "gp_sgpr_bound_begin", "gp_sgpr_bound_end", "gp_sgpr_set_graphs", "gp_sgpr_eval_counts", "gp_sgpr_predict_f", "gp_sgpr_predict_f_full", "gp_sgpr_predict_source_full", "gp_sgpr_predict_source_workspace_bytes", "gp_sgpr_predict_source", "gp_sgpr_predict_source_sparse",
@@ -167,6 +168,9 @@ def load_library():
         "gp_pdgp_cond_end": (i32, [vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, C.POINTER(dbl), vp]),
         "gp_pdgp_predict": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "gp_pdgp_predict_reuse": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "gp_pdgp_sample": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz]),
+        "gp_pdgp_sample_reuse": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz]),
+        "gp_pdgp_sample_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
         "gp_pdgp_predict_moments": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "gp_pdgp_predict_moments_reuse": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "gp_overlap_merge": (i32, [vp, vp, i32, i32, i64, i32, i32, vp]),

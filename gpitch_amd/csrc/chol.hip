@@ -352,6 +352,9 @@ __global__ void __launch_bounds__(CH_THREADS) chol_kernel(double* const* __restr
                                                           double* single_mat, int single_M, int single_ld, int panel_rows_cap,
                                                           int pivot_base) {
   const int b = blockIdx.x;
+  // an empty slot of a panel batch (engine.hip: a ragged Kuu batch gives a matrix with fewer panels size 0 in the later
+  // ones): chol_diag_block's clamped loads would start at row min(i, -1), an offset that wraps around 2^32 elements
+  if ((mats ? Ms[b] : single_M) <= 0) return;
   chol_body((ch_gptr)(mats ? mats[b] : single_mat), mats ? Ms[b] : single_M, mats ? (int64_t)lds_[b] : (int64_t)single_ld, status, b,
             panel_rows_cap, pivot_base);
 }

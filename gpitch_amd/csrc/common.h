@@ -376,6 +376,17 @@ gp_status sgpr_sample_check(gp_handle h, const int* ktype, const int* km, int P,
 gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* src, int count, int P, int M, int ldw, int n, int S,
                           double jitter, const int32_t* order_host, const double* eps_x, const double* eps_z, const double* eps_u,
                           double* out, void* ws, size_t ws_bytes);
+// sample_pdgp.hip: joint posterior draws of every latent GP and source of a Pdgp plan (gp_pdgp_sample, gp_pdgp_sample_reuse).
+// The entry describes the plan's latent GPs on the host (engine order [g_0..g_{P-1}, f_0..f_{P-1}]; z, W, q_mu, q_sqrt are
+// device pointers), checks every argument with pdgp_sample_check BEFORE anything is enqueued, factorises, then runs.
+struct PsmGP { DevKern k; const double* z; const double* W; const double* q_mu; const double* q_sqrt; int M; };
+size_t pdgp_sample_workspace_bytes(int G, int maxM, int C, int n, int S);
+// order_host: the GPs' merges back to back, GP r's n + M_r entries checked to be a permutation of 0..n+M_r-1
+gp_status pdgp_sample_check(gp_handle h, const PsmGP* gps, int G, int n, int S, const int32_t* order_host, const void* ws,
+                            size_t ws_bytes);
+gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int nlin, double jitter, const double* xnew, int n,
+                          int S, const int32_t* order_host, const double* eps_x, const double* eps_z, const double* eps_u,
+                          double* latents, double* sources, void* ws, size_t ws_bytes);
 gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int64_t ldy, int n, int square, double* out);
 // lik.hip
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)

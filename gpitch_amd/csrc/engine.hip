@@ -313,6 +313,27 @@ int cond_batch_uniform(const CondBatch& cb, int N) {
   return 1;
 }
 
+// Kuu + jitter I of every task into its L: one launch per kernel family
+static gp_status cond_batch_build_kuu(gp_handle h, CondBatch& cb) {
+  for (const auto& gr : cb.groups) {
+    const int cnt = (int)gr.members.size();
+    if (gp_kern_is_mercer(gr.type))
+      GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off.feat_zuu) + gr.first, cnt, gr.maxM,
+                                        sm_mpad(gr.m), nullptr, 0));
+    GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off.cov_uu) + gr.first, cnt,
+                                       gr.maxM, gr.maxM, nullptr, 0));
+  }
+  return GP_OK;
+}
+
+gp_status cond_batch_factor(gp_handle h, CondBatch& cb) {
+  if (cb.tasks.empty()) return GP_OK;
+  if (!cb.uploaded) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch descriptors not uploaded");
+  cb.diag_ready = false;
+  GP_CHECK(cond_batch_build_kuu(h, cb));
+  return cond_batch_factorize(h, cb, false);
+}
+
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
                          bool reuse_factor) {
   const int G = (int)cb.tasks.size();
@@ -327,17 +348,7 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
   const bool resident = (N >= 4096);   // long batch: the strip builds fill the device (independent of the overlap level)
   const bool forked = !reuse_factor && (N >= 4096) && cb.overlap && gp_aux_fork(h);
   // one launch per kernel family for the Kuu builds (helper stream when forked) ...
-  auto build_kuu = [&]() -> gp_status {
-    for (const auto& gr : cb.groups) {
-      const int cnt = (int)gr.members.size();
-      if (gp_kern_is_mercer(gr.type))
-        GP_CHECK(launch_sm_features_items(h, (const FeatItem*)(cb.d_desc + cb.off.feat_zuu) + gr.first, cnt, gr.maxM,
-                                          sm_mpad(gr.m), nullptr, 0));
-      GP_CHECK(launch_kernel_build_items(h, gr.type, gr.m, (const CovItem*)(cb.d_desc + cb.off.cov_uu) + gr.first, cnt,
-                                         gr.maxM, gr.maxM, nullptr, 0));
-    }
-    return GP_OK;
-  };
+  auto build_kuu = [&]() -> gp_status { return cond_batch_build_kuu(h, cb); };
   // ... and for the Kuf strips (main stream): every item shares the frames x
   auto build_kuf = [&]() -> gp_status {
     for (const auto& gr : cb.groups) {

@@ -476,4 +476,56 @@ gp_status gp_pdgp_predict_moments_reuse(gp_pdgp_plan p, const double* params, co
   return pdgp_predict_moments_impl(p, params, xnew, n, ynew, with_noise, smean, svar, ymean, yvar, logp, true);
 }
 
+// Joint posterior draws (sample_pdgp.hip).  Every argument, the host array `order` included, is checked before anything is
+// enqueued.  The plain form factorises every Kuu at `params` without a conditional (n is not bounded by the plan's batch:
+// the descriptors are bound for min(n, max_batch) frames, which only the factorisation's choice of path looks at).
+static gp_status pdgp_sample_impl(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,
+                                  int32_t S, const double* eps_x, const double* eps_z, const double* eps_u, double* latents,
+                                  double* sources, void* workspace, size_t workspace_bytes, bool reuse_factor) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (p->subset)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_sample: a GP-sharded plan holds only some of the 2P latent GPs");
+  if (!params || !xnew || !order_host || !eps_x || !eps_z || !eps_u || !latents || !workspace || n < 1 || S < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_sample: bad argument (n >= 1, S >= 1, no null pointers but sources)");
+  if (!p->ws) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgp_sample: workspace not set");
+  if (reuse_factor && !p->factor_valid)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgp_sample_reuse: no factorisation to reuse (call gp_pdgp_sample or gp_pdgp_predict first)");
+  std::vector<PsmGP> gps(p->G);
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    gps[g] = PsmGP{DevKern{q.ktype, q.m, params + q.off_theta}, params + q.off_z, p->cb.tasks[g].W, params + q.off_qmu,
+                   params + q.off_qsqrt, q.M};
+  }
+  GP_CHECK(pdgp_sample_check(h, gps.data(), p->G, n, S, order_host, workspace, workspace_bytes));
+  if (!reuse_factor) {
+    p->factor_valid = false;
+    GP_CHECK(pdgp_bind(p, params, xnew, n < p->maxN ? n : p->maxN, nullptr, p->fmean, p->fvar));
+    GP_CHECK(cond_batch_factor(h, p->cb));
+  }
+  GP_CHECK(pdgp_sample_run(h, gps.data(), p->P, p->whiten != 0, p->nlin, p->jitter, xnew, n, S, order_host, eps_x, eps_z, eps_u,
+                           latents, sources, workspace, workspace_bytes));
+  gp_status st = check_not_pd(h);
+  if (!reuse_factor) p->factor_valid = (st == GP_OK);
+  return st;
+}
+
+gp_status gp_pdgp_sample(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,
+                         int32_t S, const double* eps_x, const double* eps_z, const double* eps_u, double* latents,
+                         double* sources, void* workspace, size_t workspace_bytes) {
+  return pdgp_sample_impl(p, params, xnew, n, order_host, S, eps_x, eps_z, eps_u, latents, sources, workspace, workspace_bytes,
+                          false);
+}
+
+gp_status gp_pdgp_sample_reuse(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,
+                               int32_t S, const double* eps_x, const double* eps_z, const double* eps_u, double* latents,
+                               double* sources, void* workspace, size_t workspace_bytes) {
+  return pdgp_sample_impl(p, params, xnew, n, order_host, S, eps_x, eps_z, eps_u, latents, sources, workspace, workspace_bytes,
+                          true);
+}
+
+size_t gp_pdgp_sample_workspace_bytes(int32_t G, int32_t maxM, int32_t C, int32_t n, int32_t S) {
+  return pdgp_sample_workspace_bytes(G, maxM, C, n, S);
+}
+
 }  // extern "C"

@@ -14,10 +14,13 @@ from . import _lib, flatvec
 from .flatvec import col
 from .likelihoods import MpdLik
 from .methods import logistic, logistic_tf, nlin_code
+from .sgpr_ss import _sample_chunk, _sample_generator, merged_order
 from .param import MinibatchData, Param, ParamList, Parameterized, draw_in_lockstep, param_version
 from .train import AdamOptimizer, OptimizeResult
 
 jitter = 1e-6   # gpflow settings.numerics.jitter_level (pdgp.py:14)
+# sample_sources: standard normals per point of the kernels that have an exact state-space prior sampler (0: 2 m)
+_SAMPLE_COMPONENTS = {_lib.KERN_MATERN12: 1, _lib.KERN_MATERN32: 2, _lib.KERN_MERCER_MATERN12SM: 0, _lib.KERN_MATERN12SM: 0}
 
 
 def predict_windowed(model, xnew, ws=1600):
@@ -720,6 +723,108 @@ class Pdgp(Parameterized):
         """E_q[log p(ynew_n | g, f)] per frame, (n, 1): MpdLik.variational_expectations at the posterior's moments at xnew,
         not scaled by N / B and without the KL terms — on the training data, the data term of the ELBO"""
         return self._predict_moments(xnew, ynew, logp=True)[4].reshape(-1, 1)
+
+    # ------------------------------------------------------------------------------------------
+    # joint posterior draws of the latent GPs and the sources (csrc/sample_pdgp.hip through gp_pdgp_sample)
+    def _sample_components(self):
+        """standard normals per point of every latent GP, rows [g_0..g_{P-1}, f_0..f_{P-1}]: 1 for Matern12, 2 for
+        Matern32 (the state (f, f')), 2 m for a Matern-1/2 spectral mixture of m partials.  Raises NotImplementedError,
+        naming the GP and its kernel, for a kernel without an exact state-space prior sampler.  No device work."""
+        from .sgpr_ss import _KERN_NAMES
+        comps = []
+        for role, kerns in (("activation", self.kern_act), ("component", self.kern_com)):
+            for i in range(self.num_sources):
+                code, m = int(kerns[i].type_code), int(kerns[i].num_partials)
+                if code not in _SAMPLE_COMPONENTS:
+                    raise NotImplementedError(
+                        "sample_sources: the %s GP %d has kernel %s; joint draws need an exact state-space prior sampler "
+                        "(supported: %s)" % (role, i, _KERN_NAMES.get(code, "type %d" % code),
+                                             ", ".join(_KERN_NAMES[c] for c in sorted(_SAMPLE_COMPONENTS))))
+                comps.append(_SAMPLE_COMPONENTS[code] or 2 * m)
+        return comps
+
+    def sample_eps_shapes(self, n, num_samples=1):
+        """shapes of the standard normals of sample_sources at n frames: three lists (eps_x, eps_z, eps_u) of 2P shapes,
+        rows [g_0..g_{P-1}, f_0..f_{P-1}]: (S, c_r, n), (S, c_r, M_r), (S, 2, M_r).  Blocks are indexed by the caller's own
+        point order (xnew, Z_r), not by the merged one."""
+        S, n = int(num_samples), int(n)
+        comps = self._sample_components()
+        Ms = list(self.num_inducing_a) + list(self.num_inducing_c)
+        return ([(S, c, n) for c in comps], [(S, c, M) for c, M in zip(comps, Ms)], [(S, 2, M) for M in Ms])
+
+    def sample_sources(self, xnew, num_samples=1, seed=0, eps=None, return_latents=False):
+        """Joint posterior draws under q of every source nlin(g_i) f_i across all frames of xnew: `src` of shape
+        (P, num_samples, n); with return_latents=True also the draws of the activations g and components f it was formed
+        from, `(src, g, f)`, each (P, num_samples, n).  A draw is a whole path: each latent GP is drawn by Matheron's rule
+        on an exact O(n + M) state-space prior sampler along sorted time (gp_pdgp_sample; no n x n matrix), so functionals
+        of a path (an envelope, a spectrogram, an onset time) can be evaluated draw by draw.  Activation and component
+        kernels need such a sampler: Matern12, Matern32, MercerMatern12sm, Matern12sm (NotImplementedError otherwise,
+        before any device work).  Observation noise is not added.  float64 whatever the model's float_type.
+
+        eps=None: the standard normals are torch.randn on the handle's device from a generator seeded by `seed`, drawn
+        sgpr_ss.SAMPLE_EPS_BYTES at a time (the same seed and chunk size give the same draws).  eps=(eps_x, eps_z, eps_u),
+        three lists of 2P arrays of shapes sample_eps_shapes(n, num_samples), supplies them: the map is affine in eps per
+        GP, eps = 0 returns predict_act / predict_com's means and predict_act_n_com's mean_source.  All of xnew is one
+        call: a joint draw cannot be cut into frame chunks, so n is bounded by device memory, not by max_predict_batch.
+        The factorisation of a previous prediction or draw is reused while no Param changed; the prediction memo is
+        neither read nor written."""
+        if self._shard:
+            raise NotImplementedError("sample_sources of a sharded model: build the model unsharded on one GPU")
+        comps = self._sample_components()              # raises for an unsupported kernel, before any device work
+        xnew = np.asarray(xnew, dtype=np.float64)
+        if xnew.ndim > 2 or (xnew.ndim == 2 and xnew.shape[1] != 1):
+            raise ValueError("xnew has shape %r, not (n,) or (n, 1)" % (xnew.shape,))
+        xnew = xnew.reshape(-1)
+        if isinstance(num_samples, bool) or int(num_samples) != num_samples or int(num_samples) < 1:
+            raise ValueError("num_samples must be a positive integer, not %r" % (num_samples,))
+        P, n, S = self.num_sources, xnew.size, int(num_samples)
+        Ms = list(self.num_inducing_a) + list(self.num_inducing_c)
+        shapes = self.sample_eps_shapes(n, S)
+        if eps is not None:
+            if len(eps) != 3 or any(len(e) != 2 * P for e in eps):
+                raise ValueError("eps must be (eps_x, eps_z, eps_u), three lists of %d arrays" % (2 * P))
+            eps = [[np.asarray(a, dtype=np.float64) for a in e] for e in eps]
+            for name, e, sh in zip(("eps_x", "eps_z", "eps_u"), eps, shapes):
+                for r in range(2 * P):
+                    if e[r].shape != sh[r]:
+                        raise ValueError("%s[%d] has shape %r, not %r (sample_eps_shapes)" % (name, r, e[r].shape, sh[r]))
+        if n == 0:
+            out = tuple(np.zeros((P, S, 0)) for _ in range(3))
+            return out if return_latents else out[0]
+        zs = [z.value.reshape(-1) for z in list(self.za) + list(self.zc)]
+        order = np.ascontiguousarray(np.concatenate([merged_order(xnew, z) for z in zs]))
+        state = self._pred_key()
+        reuse = self._plan is not None and getattr(self, "_pred_state", None) == state
+        if not reuse:
+            self._pack()
+        h = self._handle
+        t = h.torch
+        xs = h.to_device(xnew)
+        C_all, maxM = int(sum(comps)), int(max(Ms))
+        per_draw = sum(c * (n + M) + 2 * M for c, M in zip(comps, Ms))
+        chunk = S if eps is not None else _sample_chunk(S, per_draw)
+        ws = h.workspace(h.lib.gp_pdgp_sample_workspace_bytes(2 * P, maxM, C_all, n, chunk))
+        lat, dsrc = h.empty(2 * P * chunk * n), h.empty(P * chunk * n)
+        gen = None if eps is not None else _sample_generator(h, seed)
+        src = np.empty((P, S, n))
+        g, f = (np.empty((P, S, n)), np.empty((P, S, n))) if return_latents else (None, None)
+        call = h.lib.gp_pdgp_sample_reuse if reuse else h.lib.gp_pdgp_sample
+        for s0 in range(0, S, chunk):
+            sc = min(chunk, S - s0)
+            if eps is not None:
+                ex, ez, eu = (h.to_device(np.concatenate([a.reshape(-1) for a in e])) for e in eps)
+            else:
+                ex, ez, eu = (t.randn(sc * sum(int(np.prod(sh[1:])) for sh in shs), dtype=t.float64, device=h.device,
+                                      generator=gen) for shs in shapes)
+            h.check(call(self._plan, self._params.data_ptr(), xs.data_ptr(), n, order.ctypes.data, sc, ex.data_ptr(),
+                         ez.data_ptr(), eu.data_ptr(), lat.data_ptr(), dsrc.data_ptr(), ws.data_ptr(), ws.numel()))
+            call = h.lib.gp_pdgp_sample_reuse
+            self._pred_state = state
+            src[:, s0:s0 + sc] = dsrc[:P * sc * n].reshape(P, sc, n).cpu().numpy()
+            if return_latents:
+                l = lat[:2 * P * sc * n].reshape(2 * P, sc, n).cpu().numpy()
+                g[:, s0:s0 + sc], f[:, s0:s0 + sc] = l[:P], l[P:]
+        return (src, g, f) if return_latents else src
 
     def __del__(self):
         try:

@@ -357,6 +357,40 @@ gp_status gp_pdgp_predict_moments_reuse(gp_pdgp_plan p, const double* params, co
                                         const double* ynew, int32_t with_noise, double* smean, double* svar, double* ymean,
                                         double* yvar, double* logp);
 
+/* Joint posterior draws of every latent GP and every source nlin(g_i) f_i of the model under q, by Matheron's rule: S draws
+ * that are jointly distributed across the n frames of xnew; latent GPs are independent under q.  Per latent GP r (rows as in
+ * gp_pdgp_layout, M_r inducing inputs z_r, W_r = chol(Kuu_r + jitter I)^-1 from the plan):
+ *   prior path along the merged sorted points (xnew | z_r) by an exact state-space recursion: GP_KERN_MATERN12 (1 normal per
+ *   point), GP_KERN_MATERN32 (state (f, f'), 2 normals per point), GP_KERN_MERCER_MATERN12SM / GP_KERN_MATERN12SM (a_k cos +
+ *   b_k sin per partial, 2 m normals per point); any other kernel: GP_ERR_UNSUPPORTED.  A point that coincides with its
+ *   predecessor repeats its value exactly.
+ *   u0 = prior(z_r) + sqrt(jitter) eps_u[0];  beta = W^T (q_mu + tril(q_sqrt) eps_u[1] - W u0)   (whitened plan)
+ *                                             beta = W^T W (q_mu + tril(q_sqrt) eps_u[1] - u0)   (unwhitened plan)
+ *   draw_r(x*) = prior_r(x*) + K_r(x*, z_r) beta;   source_i = nlin(draw_i) * draw_{P+i}.
+ * Arguments:
+ *   order_host  HOST array, the 2P merges back to back: GP r's n + M_r entries are a stable ascending argsort of
+ *               (xnew | z_r); entry < n is a frame, n + i is z_r[i].  Each is checked to be a permutation before anything is
+ *               enqueued (GP_ERR_BAD_ARG otherwise).
+ *   eps_x, eps_z, eps_u (device): the GPs' blocks back to back, GP r's being [S][c_r][n], [S][c_r][M_r], [S][2][M_r] with c_r
+ *               the normals per point above; blocks are indexed by the caller's own point order.
+ *   latents [2P][S][n] (device, required), sources [P][S][n] (device, may be NULL).
+ * The map is affine in eps per GP: eps = 0 gives gp_pdgp_predict's fmean and mean_source, the linear part T_r has
+ * T_r T_r^T = the full-covariance conditional of GP r.  workspace: gp_pdgp_sample_workspace_bytes(2P, max_r M_r, sum_r c_r,
+ * n, S) bytes, 256-byte aligned (a short one: GP_ERR_BAD_ARG); n is bounded by it, not by max_batch; M_r <= 1024.  A subset
+ * (GP-sharded) plan: GP_ERR_BAD_ARG.  gp_pdgp_sample factorises Kuu at `params` (without a conditional); _reuse under
+ * gp_pdgp_predict_reuse's condition.  Both synchronise and report a failed factorisation as gp_pdgp_predict does.  float64
+ * throughout whatever the plan's strip precision.  Deterministic, no atomics: bit-identical between calls, and draw s depends
+ * on nothing but its own eps. */
+gp_status gp_pdgp_sample(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,
+                         int32_t S, const double* eps_x, const double* eps_z, const double* eps_u, double* latents,
+                         double* sources, void* workspace, size_t workspace_bytes);
+gp_status gp_pdgp_sample_reuse(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,
+                               int32_t S, const double* eps_x, const double* eps_z, const double* eps_u, double* latents,
+                               double* sources, void* workspace, size_t workspace_bytes);
+/* handle-free, runs without a device: the one carve of the sampling operator, measured (0 for an empty problem).  G latent
+ * GPs of at most maxM inducing inputs, C = sum_r c_r normals per point, n frames, S draws. */
+size_t gp_pdgp_sample_workspace_bytes(int32_t G, int32_t maxM, int32_t C, int32_t n, int32_t S);
+
 /* ---- overlap-add of per-window predictions (gpitch/window_overlap.py:19-59: merged_mean / merged_variance) ----------
  * windows: num_windows x ws (row-major, leading dimension ld) device array of per-window means (square = 0) or
  * variances (square = 1: squared Hann weights); ws odd, 50 % overlap (hop (ws-1)/2); out: n = (ws-1)/2 *
