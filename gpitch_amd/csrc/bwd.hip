@@ -1372,14 +1372,24 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
   }
   {
     HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
+    KufScanItem* sitems = (KufScanItem*)(p->h_misc.data() + p->off.ks_items);
     int pos = 0;
     for (auto& fam : p->hy_fams) {
       fam.first = pos; fam.count = (int)fam.gps.size();
       fam.mfma = (gp_kern_is_mercer(fam.type) && fam.batched) ? 1 : 0;
+      fam.scan_ws = true;
       for (int g : fam.gps) {
         const PdgpGP& q = p->gps[g];
         const CondTask& t = p->cb.tasks[g];
         const BwdBufs& bb = p->bw[g];
+        {    // the same GP's record for the scan form (kuf_scan.hip), used only when pdgp_backward picks that form
+          KufScanItem& si = sitems[pos];
+          memset(&si, 0, sizeof(si));
+          si.A = t.A; si.lda = gp_strip_ld(n, q.f32 != 0); si.gv = p->gFvar + (size_t)g * n; si.gm = p->gFmu + (size_t)g * n;
+          si.R = bb.R; si.alpha = bb.alpha; si.z = params + q.off_z; si.theta = t.kern.theta;
+          si.mom = bb.ks_mom; si.near = bb.ks_near; si.partials = bb.hyp_part; si.M = q.M;
+          if (!bb.ks_mom || !bb.ks_near) fam.scan_ws = false;
+        }
         HyperItem& it = items[pos++];
         memset(&it, 0, sizeof(it));
         const int64_t ldN = gp_strip_ld(n, q.f32 != 0);
@@ -1529,6 +1539,34 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     // From here two independent chains remain: the Kuf side (the big Kuf_bar product and its contraction with
     // dK/dtheta over all frames) and the Kuu side (the Cholesky adjoint, six M x M products, and its contraction
     // over M x M).  The Kuu side is ~1.4 ms of small launches: it runs on the helper stream underneath Kuf_bar.
+    auto fam_slot0 = [&](const gp_pdgp_plan_s::HyFamily& fam) -> int {    // first slot in the compacted batch, -1 if scattered
+      int s0 = -1;
+      for (size_t s = 0; s < p->kgps.size(); s++) if (p->kgps[s] == fam.gps[0]) s0 = (int)s;
+      for (size_t i = 0; i < fam.gps.size(); i++)
+        if (s0 < 0 || s0 + (int)i >= (int)p->kgps.size() || p->kgps[s0 + i] != fam.gps[i]) return -1;
+      return s0;
+    };
+    // Which families contract Kuf_bar by the scan (kuf_scan.hip: no product at all): Matern-3/2 / Matern-5/2 over frames the
+    // caller promised ascending.  Any M, any n; fam.batched already says one M and hyper-parameter gradients only.  Matern-1/2
+    // (kink at 0) and RBF (not semiseparable) have no such form.  Like the fused form below the choice depends on shapes,
+    // types and that promise alone — never on the overlap level — and needs every family in one contiguous run of the batch.
+    const int nfam = (int)p->hy_fams.size();
+    std::vector<int> fslot(nfam, -1), ffuse(nfam, 0), fscan(nfam, 0);
+    bool contiguous = (white && nfam > 0), any_scan = false;
+    for (int fi = 0; fi < nfam; fi++) { fslot[fi] = fam_slot0(p->hy_fams[fi]); if (fslot[fi] < 0) contiguous = false; }
+    for (int fi = 0; fi < nfam && contiguous; fi++) {
+      const auto& fam = p->hy_fams[fi];
+      fscan[fi] = (gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
+                   kuf_scan_nq(fam.type) > 0 && fam.M <= 1024) ? 1 : 0;
+      any_scan |= (fscan[fi] != 0);
+    }
+    // Schedule with a scan family (switches.h scan_side; the same launches either way, so the same bits): the scan's three
+    // launches go to the side stream, beside the other families' Kuf_bar product, instead of ahead of it on the main stream
+    // (measurements: DESIGN.md 3.02).  The side stream serves ONE fork per backward pass — gp_side_begin refuses until
+    // gp_side_join — so only the first scan family gets it; a further scan family, or one that follows the spectral-mixture
+    // contraction onto the side stream (kufbar_split 1), stays on the main stream, and so do the contractions that would
+    // otherwise have gone to the side stream after it.
+    const bool scan_side = any_scan && gp_switches().scan_side != 0 && (n >= 4096) && p->overlap >= 2;
     const bool forked = (n >= 4096) && p->overlap >= 1 && gp_aux_fork(h);
     gp_status st = GP_OK;
     std::vector<int> np_uu(p->G, 0);
@@ -1586,13 +1624,6 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     // (the long one: 40 % of it matrix-core work) then runs on the side stream UNDERNEATH the second family's product
     // instead of after it, and only the stationary family's short, HBM-bound contraction is left behind the product.
     std::vector<int> np_uf(p->G, 0);
-    auto fam_slot0 = [&](const gp_pdgp_plan_s::HyFamily& fam) -> int {    // first slot in the compacted batch, -1 if scattered
-      int s0 = -1;
-      for (size_t s = 0; s < p->kgps.size(); s++) if (p->kgps[s] == fam.gps[0]) s0 = (int)s;
-      for (size_t i = 0; i < fam.gps.size(); i++)
-        if (s0 < 0 || s0 + (int)i >= (int)p->kgps.size() || p->kgps[s0 + i] != fam.gps[i]) return -1;
-      return s0;
-    };
     int kuf_uniform = ((n & 1) == 0) ? 1 : 0;        // every GP of the compacted batch M = maxM (R, A, G: arena buffers, even ld)
     for (int g : p->kgps) if (p->gps[g].M != maxM) kuf_uniform = 0;
     // (slots of the compacted batch keep the GPs' order: its float64 GPs come first, k64 of them)
@@ -1639,21 +1670,24 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     // epilogue (gemm_strip.hip role 5; float64 strips, whole 128-tiles) and neither the strip nor the separate contraction
     // exists.  The choice depends on shapes and kernel types alone — never on the overlap level, whose settings must give
     // bit-identical results — and needs every family in one contiguous run of the compacted batch.
-    const int nfam = (int)p->hy_fams.size();
-    std::vector<int> fslot(nfam, -1), ffuse(nfam, 0);
-    {
-      bool contiguous = (white && nfam > 0);
-      for (int fi = 0; fi < nfam; fi++) { fslot[fi] = fam_slot0(p->hy_fams[fi]); if (fslot[fi] < 0) contiguous = false; }
-      for (int fi = 0; fi < nfam && contiguous; fi++) {
-        const auto& fam = p->hy_fams[fi];
-        bool ok = kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM &&
-                  (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type));
-        for (int g : fam.gps) if (p->gps[g].need_z || !p->gps[g].need_theta) ok = false;
-        ffuse[fi] = ok ? 1 : 0;
-      }
+    for (int fi = 0; fi < nfam && contiguous; fi++) {
+      const auto& fam = p->hy_fams[fi];
+      bool ok = kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM && !fscan[fi] &&
+                (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type));
+      for (int g : fam.gps) if (p->gps[g].need_z || !p->gps[g].need_theta) ok = false;
+      ffuse[fi] = ok ? 1 : 0;
     }
+    auto fdone = [&](int fi) { return ffuse[fi] || fscan[fi]; };   // the family's Kuf-side partial sums come with kuf_bar_family
     auto kuf_bar_family = [&](int fi) -> gp_status {          // one family's product (contiguous slots), fused form if chosen
       const auto& fam = p->hy_fams[fi];
+      if (fscan[fi]) {
+        const bool side = scan_side && gp_side_begin(h);
+        gp_status st2 = launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, x, n);
+        if (side) { gp_status s3 = gp_side_end(h); if (st2 == GP_OK) st2 = s3; }
+        GP_CHECK(st2);
+        for (int g : fam.gps) np_uf[g] = kuf_scan_records(fam.M);
+        return GP_OK;
+      }
       if (!ffuse[fi]) return kuf_bar(fslot[fi], fam.count);
       GP_CHECK(kuf_bar(fslot[fi], fam.count, fam.type, fam.f32));
       for (int g : fam.gps) np_uf[g] = fam.f32 ? (gemm_wave_f32_takes(5, maxM, n, kuf_uniform) ? (maxM / 64) * (n / 64) : (maxM / 128) * (n / 128))
@@ -1661,7 +1695,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       return GP_OK;
     };
     bool any_fused = false;
-    for (int fi = 0; fi < nfam; fi++) any_fused |= (ffuse[fi] != 0);
+    for (int fi = 0; fi < nfam; fi++) any_fused |= (fdone(fi) != 0);
     int sm_fam = -1, other_fam = -1, sm_slot = -1, other_slot = -1;
     // (switches.h; -1 = by precision: with float32 strips the spectral-mixture family goes first — its vector-ALU contraction then runs
     // beside the other family's float32 matrix product, which leaves the vector ALU free; the float64 MFMA holds it, so there the
@@ -1682,7 +1716,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       // spectral-mixture family's product, and the long contraction has the device to itself afterwards
       const auto& fs = p->hy_fams[sm_fam];
       const auto& fo = p->hy_fams[other_fam];
-      if (ffuse[other_fam]) {
+      if (fdone(other_fam)) {
         GP_CHECK(kuf_bar_family(other_fam));
         GP_CHECK(kuf_bar(sm_slot, fs.count));
       } else {
@@ -1709,7 +1743,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       }
       GP_CHECK(kuf_bar_family(other_fam));
       if (!side) GP_CHECK(contract_family(fs));
-      if (!ffuse[other_fam]) GP_CHECK(contract_family(fo));
+      if (!fdone(other_fam)) GP_CHECK(contract_family(fo));
     } else {
       if (any_fused) { for (int fi = 0; fi < nfam; fi++) GP_CHECK(kuf_bar_family(fi)); }
       else GP_CHECK(kuf_bar(0, nK));
@@ -1722,11 +1756,11 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       const bool side = (p->hy_fams.size() > 1) && forked && p->overlap >= 2 && gp_side_begin(h);
       if (side) {
         gp_status st2 = GP_OK;
-        for (int fi = 0; fi < nfam; fi++) if (!p->hy_fams[fi].mfma && !ffuse[fi] && st2 == GP_OK) st2 = contract_family(p->hy_fams[fi]);
+        for (int fi = 0; fi < nfam; fi++) if (!p->hy_fams[fi].mfma && !fdone(fi) && st2 == GP_OK) st2 = contract_family(p->hy_fams[fi]);
         gp_status s3 = gp_side_end(h);
         GP_CHECK(st2); GP_CHECK(s3);
       }
-      for (int fi = 0; fi < nfam; fi++) if ((!side || p->hy_fams[fi].mfma) && !ffuse[fi]) GP_CHECK(contract_family(p->hy_fams[fi]));
+      for (int fi = 0; fi < nfam; fi++) if ((!side || p->hy_fams[fi].mfma) && !fdone(fi)) GP_CHECK(contract_family(p->hy_fams[fi]));
     }
     if (!white) {
       GP_CHECK(launch_matvec_batched(h, D(S_GQ_MU), G, maxM, 1));

@@ -883,6 +883,12 @@ gp_status check_not_pd(gp_handle h) {
     h->not_pd_index = st[1];
     char buf[160];
     const bool stalled = (st[0] == 2);      // chol_cluster.hip: a wavefront gave up waiting for the cluster's exchange
+    if (st[0] == 3) {                       // kuf_scan.hip: a descending pair of frames under gp_pdgp_set_frames_ascending
+      snprintf(buf, sizeof(buf), "frames not ascending: frame %d is below frame %d although gp_pdgp_set_frames_ascending promised time order", st[1] + 1, st[1]);
+      h->last_error = buf;
+      GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
+      return GP_ERR_BAD_ARG;
+    }
     if (stalled) snprintf(buf, sizeof(buf), "Cholesky failed: the workgroup cluster stalled (GPITCH_AMD_SWITCHES=chol_cluster=0 selects the one-workgroup kernels)");
     else snprintf(buf, sizeof(buf), "Cholesky failed: matrix %d is not positive definite (pivot %d)", st[2], st[1]);
     h->last_error = buf;

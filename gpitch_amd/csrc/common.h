@@ -20,7 +20,7 @@ struct gp_handle_s {
   bool own_stream = false;
   std::string last_error;
   int32_t not_pd_index = -1;
-  int32_t* d_status = nullptr;   // device int[4]: {not_pd_flag, pivot_index, gp_index, spare}
+  int32_t* d_status = nullptr;   // device int[4]: {flag (1 not PD, 2 cluster stalled, 3 frames not ascending), pivot / frame index, gp_index, spare}
   int num_cus = 256;
   GpLogisticTable logistic = {}; int num_logistic = 0;
   // helper stream for work that can overlap the main stream (the latency-bound Kuu factorisation runs on ~24 CUs

@@ -63,6 +63,21 @@ size_t hyper_finish_item_bytes();
 // partial records the Kuf-side contraction of an M x N strip may write (the largest over its kernel variants)
 size_t hyper_kuf_records(int N, int M);
 
+// kuf_scan.hip: the Kuf-side contraction of a Matern-3/2 / Matern-5/2 family by moment sums along ascending frames
+struct KufScanItem {
+  const double* A; const double* gv; const double* gm;      // M x N strip (ld lda), dELBO/dfvar, dELBO/dfmean (N each)
+  const double* R; const double* alpha; const double* z;    // M x M (ld M), M, M
+  const double* theta;                                      // [variance, lengthscale]
+  double* mom; double* near; double* partials;              // moments [chunk][side][q][M + 1], near sums [chunk][2], records
+  int64_t lda; int M, pad;
+};
+int kuf_scan_nq(int ktype);                 // moment orders a kernel type needs (3 Matern-3/2, 4 Matern-5/2; 0: not a scan type)
+int kuf_scan_chunks(int N);
+size_t kuf_scan_moment_doubles(int N, int M, int ktype);
+int kuf_scan_records(int M);                // partial records one GP leaves (never more than hyper_kuf_records gives it)
+// all `count` GPs of one family (same kernel type) over the n ascending frames x: three launches, no Kuf_bar product
+gp_status launch_kuf_scan(gp_handle h, int ktype, const KufScanItem* d_items, int count, int maxM, const double* x, int n);
+
 #define CB_NB 128          // panel width of the blocked Kuu factorisation
 #define CB_MAX_PANELS 8    // M <= 1024
 

@@ -113,6 +113,11 @@ gp_status gp_pdgp_set_overlap(gp_pdgp_plan p, int32_t level) {
   p->cb.overlap = (level >= 1);
   return GP_OK;
 }
+gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
+  if (!p) return GP_ERR_BAD_ARG;
+  p->frames_ascending = (ascending != 0);
+  return GP_OK;
+}
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
@@ -170,6 +175,14 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       b.hyp_part = ar.take<double>(ns * hyper_kuf_records(p->maxN, (int)M));
       b.hyp_part_uu = ar.take<double>(ns * hyper_kuf_records((int)M, (int)M));
       b.gz_part = ar.take<double>(colblocks * M + ((M + 255) / 256 + 1) * M);
+      // moment arrays of the scan form of the Kuf-side contraction (kuf_scan.hip), for the GPs whose shape and types admit it:
+      // 2 NQ (M + 1) doubles per chunk of 64 frames, 12.6 MB per GP at N = 32768, M = 512.  gp_pdgp_set_frames_ascending and
+      // gp_pdgp_set_grad_needs may both be called after the workspace is set, so the carve cannot wait for them: the arrays
+      // are reserved whether or not the caller goes on to make the promise.  With kuf_scan=0 nothing is reserved.
+      if (gp_switches().kuf_scan != 0 && p->whiten && !p->gps[g].f32 && kuf_scan_nq(p->gps[g].ktype) > 0) {
+        b.ks_mom = ar.take<double>(kuf_scan_moment_doubles(p->maxN, (int)M, p->gps[g].ktype));
+        b.ks_near = ar.take<double>(2 * (size_t)kuf_scan_chunks(p->maxN));
+      }
     }
     {  // sum_n gv per GP, contiguous so one launch fills all of them
       double* gvs = ar.take<double>(p->G + 8);

@@ -12,7 +12,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // (bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 24
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
-struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, bytes; };
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   PdgpMiscLayout o;
   GpRegions region;
@@ -22,6 +22,7 @@ static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   o.kl2 = region(pdgp_kl_region_bytes(G));
   o.fin_items = region((size_t)G * hyper_finish_item_bytes());
   o.hy_items = region((size_t)2 * G * sizeof(HyperItem));      // G Kuf-side items, then G Kuu-side items, same order
+  o.ks_items = region((size_t)G * sizeof(KufScanItem));       // kuf_scan.hip: one per latent GP, in the families' item order
   o.bytes = region.off;
   return o;
 }
@@ -50,6 +51,8 @@ struct BwdBufs {  // per-GP backward workspace (device)
   double* hyp_part_uu = nullptr;
   double* gz_part = nullptr;    // z-gradient partials
   double* gvsum = nullptr;      // sum_n gv
+  double* ks_mom = nullptr;     // kuf_scan.hip: chunk moments / their prefix and suffix sums (eligible GPs only)
+  double* ks_near = nullptr;    // kuf_scan.hip: [chunks][2] near-part sums
   // unwhitened model only: the equivalent whitened variational state q' = (W q_mu, W Lq) and its gradient
   double* qmu_w = nullptr; double* Lq_w = nullptr;       // M, M x M
   double* g_qmu_w = nullptr; double* g_Lq_w = nullptr;   // M, M x M
@@ -79,7 +82,7 @@ struct gp_pdgp_plan_s {
   std::vector<char> h_misc;
   std::vector<char> h_fin_items;   // batched hyper-gradient finish (bwd.hip)
   // Kuf-side and Kuu-side contractions grouped by kernel family: one launch per family and side over an item array (bwd.hip)
-  struct HyFamily { int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; std::vector<int> gps; };
+  struct HyFamily { int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; bool scan_ws = false; std::vector<int> gps; };
   std::vector<HyFamily> hy_fams;
   double* qw_block = nullptr; size_t qw_doubles = 0;   // [q' | grad q'] of all GPs, contiguous (one memset)
   double* kl_dummy = nullptr;
@@ -97,6 +100,7 @@ struct gp_pdgp_plan_s {
            double* g_noise = nullptr; bool pending = false; } fin;
   int overlap = 2;             // gp_pdgp_set_overlap: 0 one stream, 1 Kuu factorisation / Kuu-side backward on the helper
                                // stream, 2 also the H = A D A^T chain next to Kuf_bar
+  bool frames_ascending = false;   // gp_pdgp_set_frames_ascending: the caller promises time-ordered batches
   bool era_ready = false;      // pdgp_prefetch_backward ran for the current evaluation
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end

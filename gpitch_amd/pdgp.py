@@ -206,6 +206,11 @@ class Pdgp(Parameterized):
         h.check(h.lib.gp_pdgp_set_workspace(plan, self._ws.data_ptr(), self._ws.numel()))
         self._x_dev = h.to_device(self.x._array.reshape(-1))
         self._y_dev = h.to_device(self.y._array.reshape(-1))
+        # _batch() hands over the resident frames as they lie, or a subset drawn in index order: every batch is in time order
+        # exactly when the resident x is.  The engine may then contract Kuf_bar of its Matern-3/2 / 5/2 families along the
+        # sorted frames (kuf_scan.hip); it re-checks neighbouring pairs on the device.
+        xh = self.x._array.reshape(-1)
+        h.check(h.lib.gp_pdgp_set_frames_ascending(plan, int(bool(np.all(xh[1:] >= xh[:-1])))))
         self._xchg = h.zeros(3 * self._max_batch + 1) if (self._shard and self._gp_shard is None) else None
         if self._gp_shard is not None:
             from .dist import gp_exchange_layout

@@ -245,6 +245,14 @@ gp_status gp_pdgp_set_grad_needs(gp_pdgp_plan p, int32_t g, int32_t need_theta, 
  * Batches below 4096 frames always run on one stream. */
 gp_status gp_pdgp_set_overlap(gp_pdgp_plan p, int32_t level);
 
+/* A promise about every batch handed to gp_pdgp_elbo from now on: ascending != 0 says its frames x are in ascending order
+ * (equal neighbours allowed).  A whitened plan then contracts Kuf_bar of a Matern-3/2 / Matern-5/2 family whose inducing
+ * inputs are fixed (need_theta, no need_z) by exponentially weighted moment sums along the sorted frames instead of forming
+ * the product (kuf_scan.hip; gradients agree to ~1e-11 relative).  The kernel that streams the frames checks neighbouring
+ * pairs: a descending pair raises the handle's device status word, and the next gp_check_not_pd / host-scalar call returns
+ * GP_ERR_BAD_ARG ("frames not ascending") and clears it.  Default 0: today's path. */
+gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending);
+
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the
  * summed KL term (Pdgp.build_prior_kl, pdgp.py:113-131).  When
