@@ -362,7 +362,7 @@ struct SrcSparseItem {
   const double* xnew; double* mean; double* var; int kz, ldw;
 };
 gp_status launch_sgpr_source_sparse(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n, int max_mpad);
-// sample_sparse.hip: joint posterior draws of every source under the sparse posterior's q(u) (gp_sgpr_sample_source_sparse,
+// sample.hip, SGPRSS section: joint posterior draws of every source under the sparse posterior's q(u) (gp_sgpr_sample_source_sparse,
 // gp_sgprb_sample_source_sparse).  The two entries describe their windows on the host — a window's forward state and inputs,
 // and per (window, source) the kernel and the plan's Z feature table (nullptr: the plan keeps none for this kernel) — check
 // every argument with sgpr_sample_check BEFORE anything is enqueued, run their forward pass, then call sgpr_sample_run.
@@ -376,7 +376,7 @@ gp_status sgpr_sample_check(gp_handle h, const int* ktype, const int* km, int P,
 gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* src, int count, int P, int M, int ldw, int n, int S,
                           double jitter, const int32_t* order_host, const double* eps_x, const double* eps_z, const double* eps_u,
                           double* out, void* ws, size_t ws_bytes);
-// sample_pdgp.hip: joint posterior draws of every latent GP and source of a Pdgp plan (gp_pdgp_sample, gp_pdgp_sample_reuse).
+// sample.hip, Pdgp section: joint posterior draws of every latent GP and source of a Pdgp plan (gp_pdgp_sample, gp_pdgp_sample_reuse).
 // The entry describes the plan's latent GPs on the host (engine order [g_0..g_{P-1}, f_0..f_{P-1}]; z, W, q_mu, q_sqrt are
 // device pointers), checks every argument with pdgp_sample_check BEFORE anything is enqueued, factorises, then runs.
 struct PsmGP { DevKern k; const double* z; const double* W; const double* q_mu; const double* q_sqrt; int M; };

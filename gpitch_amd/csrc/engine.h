@@ -148,5 +148,5 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
                          bool reuse_factor = false);
 // steps 1-2 of cond_batch_run alone, on the current stream: Kuu + jitter I -> L, W of every task (the uploaded descriptors'),
-// for a caller that needs the factorisation and no conditional (sample_pdgp.hip)
+// for a caller that needs the factorisation and no conditional (sample.hip)
 gp_status cond_batch_factor(gp_handle h, CondBatch& cb);

@@ -489,7 +489,7 @@ gp_status gp_pdgp_predict_moments_reuse(gp_pdgp_plan p, const double* params, co
   return pdgp_predict_moments_impl(p, params, xnew, n, ynew, with_noise, smean, svar, ymean, yvar, logp, true);
 }
 
-// Joint posterior draws (sample_pdgp.hip).  Every argument, the host array `order` included, is checked before anything is
+// Joint posterior draws (sample.hip).  Every argument, the host array `order` included, is checked before anything is
 // enqueued.  The plain form factorises every Kuu at `params` without a conditional (n is not bounded by the plan's batch:
 // the descriptors are bound for min(n, max_batch) frames, which only the factorisation's choice of path looks at).
 static gp_status pdgp_sample_impl(gp_pdgp_plan p, const double* params, const double* xnew, int32_t n, const int32_t* order_host,

@@ -8,7 +8,7 @@
 //   1. K_p(Z, x*) of its T frames is built straight into LDS (frame-major, M values per frame) with the entry arithmetic
 //      of cov.hip (cov_entry.h): an entry equals what launch_kernel_build writes.  The Z feature table of a Mercer kernel is
 //      the plan's (current after the forward pass); the T frames' features are computed here, once per workgroup.  The
-//      build itself is sps_tile.h's, shared with sample_sparse.hip.
+//      build itself is sps_tile.h's, shared with sample.hip.
 //   2. tmp1 = W tile on v_mfma_f64_16x16x4_f64.  A wavefront owns 16 frames — both products act on a frame's column alone,
 //      so nothing crosses wavefronts after the build.  Row blocks run from the last to the first and overwrite the tile
 //      in place: block rb reads blocks kb <= rb only (the zero blocks above W's diagonal are skipped).
@@ -105,33 +105,20 @@ __global__ void __launch_bounds__(256) sgpr_source_sparse_kernel(const SrcSparse
   }
 }
 
-template <int MPAD>
-static gp_status sps_launch(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n) {
-  const int T = sps_tile_frames(M), S = sps_stride(M);
-  const size_t lds = sps_lds_bytes(M, MPAD);
-  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)sgpr_source_sparse_kernel<MPAD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-  hipLaunchKernelGGL((sgpr_source_sparse_kernel<MPAD>), dim3((n + T - 1) / T, P, nwin), dim3(4 * T), lds, h->stream, d_items,
-                     nwin, n, T, S);
-  GP_HIP_CHECK(h, hipGetLastError());
-  return GP_OK;
-}
-
 // d_items: device array [P][nwin] (kernel-major); every item's kz <= M (the plan's inducing-point count, <= SPS_MAX_M);
 // max_mpad: the largest sm_mpad() among the Mercer kernels of the launch (0: none)
 gp_status launch_sgpr_source_sparse(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n, int max_mpad) {
   if (M < 1 || M > SPS_MAX_M) return gp_fail(h, GP_ERR_UNSUPPORTED, "sparse source posterior: M must be in [1, 1024]");
   if (P < 1 || P > 65535 || nwin < 1 || nwin > 65535 || n < 1) return gp_fail(h, GP_ERR_BAD_ARG, "sparse source posterior: bad launch shape");
   GpTimerScope ts(h, GP_TIMER_COND_A);
-  switch (max_mpad <= 4 ? 4 : max_mpad) {
-    case 4: return sps_launch<4>(h, d_items, P, nwin, M, n);
-    case 8: return sps_launch<8>(h, d_items, P, nwin, M, n);
-    case 12: return sps_launch<12>(h, d_items, P, nwin, M, n);
-    case 16: return sps_launch<16>(h, d_items, P, nwin, M, n);
-    case 20: return sps_launch<20>(h, d_items, P, nwin, M, n);
-    case 24: return sps_launch<24>(h, d_items, P, nwin, M, n);
-    case 28: return sps_launch<28>(h, d_items, P, nwin, M, n);
-    case 32: return sps_launch<32>(h, d_items, P, nwin, M, n);
-    default: return gp_fail(h, GP_ERR_UNSUPPORTED, "sparse source posterior: num_partials must be in [1, 32]");
-  }
+  return sps_dispatch_mpad(h, max_mpad, "sparse source posterior: num_partials must be in [1, 32]", [&](auto mpad) -> gp_status {
+    const int T = sps_tile_frames(M), S = sps_stride(M);
+    const size_t lds = sps_lds_bytes(M, decltype(mpad)::value);
+    GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)sgpr_source_sparse_kernel<decltype(mpad)::value>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((sgpr_source_sparse_kernel<decltype(mpad)::value>), dim3((n + T - 1) / T, P, nwin), dim3(4 * T), lds, h->stream,
+                       d_items, nwin, n, T, S);
+    GP_HIP_CHECK(h, hipGetLastError());
+    return GP_OK;
+  });
 }

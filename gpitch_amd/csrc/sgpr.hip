@@ -978,7 +978,7 @@ gp_status gp_sgpr_predict_source_sparse(gp_sgpr_plan p, const double* params, co
   return check_not_pd(h);
 }
 
-// Joint posterior draws of every source under the q(u) of gp_sgpr_predict_source_sparse (sample_sparse.hip).  Every argument,
+// Joint posterior draws of every source under the q(u) of gp_sgpr_predict_source_sparse (sample.hip).  Every argument,
 // the host array `order` included, is checked before the forward pass: a refused call enqueues nothing.
 gp_status gp_sgpr_sample_source_sparse(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
                                        const double* Z, const double* Xnew, int32_t n, const int32_t* order_host, int32_t S,

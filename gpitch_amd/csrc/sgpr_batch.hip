@@ -802,7 +802,7 @@ extern "C" gp_status gp_sgprb_predict_source_sparse(gp_sgprb_plan_t p, const dou
   return check_not_pd(h);
 }
 
-// gp_sgpr_sample_source_sparse of the first `count` windows (sample_sparse.hip): the forward pass, then one launch sequence
+// gp_sgpr_sample_source_sparse of the first `count` windows (sample.hip): the forward pass, then one launch sequence
 // over every (window, source).  A slot with kw < M inducing points is its own kw-point problem, as in
 // gp_sgprb_predict_source_sparse.  Every argument, the host array `order` included, is checked before anything is enqueued.
 extern "C" gp_status gp_sgprb_sample_source_sparse(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,

@@ -1,10 +1,12 @@
 // sps_tile.h — the K_p(Z, x*) tile of the sparse per-source kernels, built straight into LDS: shared by predict_sparse.hip
-// (posterior mean and variance of each source) and sample_sparse.hip (joint posterior draws), so both see the entries the
+// (posterior mean and variance of each source) and sample.hip (joint posterior draws), so both see the entries the
 // sparse predictor always built.  A workgroup of 4 T threads takes T new frames; the tile is frame-major, sps_stride(M)
 // doubles per frame (M rounded up to 16, plus 4: 4 x odd, so the 16 frames a wavefront reads sit on different LDS banks).
 // Tails: rows in [kz, Mp) are zero and never read from Z; frames past n repeat the last one.  Device-only apart from the
-// three host-side size functions; include after common.h.
+// host-side size functions and the MPAD dispatch; include after common.h.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "cov_entry.h"
 
@@ -17,6 +19,23 @@ static inline size_t sps_lds_bytes(int M, int mpad) {
   const int T = sps_tile_frames(M), S = sps_stride(M);
   const size_t buf = (size_t)T * (S > 2 * mpad ? S : 2 * mpad);
   return (GP_EXP_TAB + 2 * SPS_CHUNK + (size_t)SPS_CHUNK * 2 * mpad + buf) * sizeof(double);
+}
+
+// The kernels on this tile are templates over MPAD, the largest sm_mpad() of a launch (0: no spectral-mixture kernel, served
+// by MPAD = 4).  Calls f(std::integral_constant<int, MPAD>()) and returns its status, or fails with the caller's message.
+template <typename F>
+static inline gp_status sps_dispatch_mpad(gp_handle h, int max_mpad, const char* unsupported, F f) {
+  switch (max_mpad <= 4 ? 4 : max_mpad) {
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 12: return f(std::integral_constant<int, 12>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 20: return f(std::integral_constant<int, 20>());
+    case 24: return f(std::integral_constant<int, 24>());
+    case 28: return f(std::integral_constant<int, 28>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return gp_fail(h, GP_ERR_UNSUPPORTED, unsupported);
+  }
 }
 
 // LDS (doubles): etab[64] | rowa[32] | rowx[32] | zf[32][2 MPAD] | buf[T][S]  (buf first holds the frames' features [2 MPAD][T])

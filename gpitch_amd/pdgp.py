@@ -730,7 +730,7 @@ class Pdgp(Parameterized):
         return self._predict_moments(xnew, ynew, logp=True)[4].reshape(-1, 1)
 
     # ------------------------------------------------------------------------------------------
-    # joint posterior draws of the latent GPs and the sources (csrc/sample_pdgp.hip through gp_pdgp_sample)
+    # joint posterior draws of the latent GPs and the sources (csrc/sample.hip through gp_pdgp_sample)
     def _sample_components(self):
         """standard normals per point of every latent GP, rows [g_0..g_{P-1}, f_0..f_{P-1}]: 1 for Matern12, 2 for
         Matern32 (the state (f, f')), 2 m for a Matern-1/2 spectral mixture of m partials.  Raises NotImplementedError,

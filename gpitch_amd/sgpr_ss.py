@@ -22,7 +22,7 @@ class _Gaussian(Parameterized):
         self.variance = Param(1.0, transforms.positive)
 
 
-# ---- joint posterior draws of the sources (csrc/sample_sparse.hip): host-only helpers, no device work ----
+# ---- joint posterior draws of the sources (csrc/sample.hip): host-only helpers, no device work ----
 _KERN_NAMES = {_lib.KERN_MATERN12: "Matern12", _lib.KERN_MATERN32: "Matern32", _lib.KERN_MATERN52: "Matern52",
                _lib.KERN_RBF: "RBF", _lib.KERN_MERCER_MATERN12SM: "MercerMatern12sm", _lib.KERN_MATERN12SM: "Matern12sm",
                _lib.KERN_MATERN32SM: "Matern32sm", _lib.KERN_MERCER_MATERN52SM: "Matern52 * MercerCosMix"}

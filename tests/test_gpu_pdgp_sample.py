@@ -1,4 +1,4 @@
-"""Joint posterior draws of every Pdgp source on the GPU (Pdgp.sample_sources, csrc/sample_pdgp.hip through gp_pdgp_sample)
+"""Joint posterior draws of every Pdgp source on the GPU (Pdgp.sample_sources, csrc/sample.hip through gp_pdgp_sample)
 against the numpy restatement on the same eps (tests/pdgp_sample_ref.py), the oracle's full-covariance conditionals, the
 model's own predictions, and itself.  Tolerance against the restatement: the project's rule, absolute 1e-8 max(|ref|, 1e-3);
 the inputs are conditioned for it (test_pdgp_sample_cpu.py::test_gpu_shapes_are_well_conditioned)."""

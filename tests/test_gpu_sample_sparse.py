@@ -194,6 +194,62 @@ def test_ragged_windows_match_their_own_size(gp_handle):
     tmpl._destroy()
 
 
+def _ragged_mixed_windows(counts, N):
+    """every window the mixed sum (partials padded to 4, 20 and 4, and a Matern12 with no table) at its own variances and
+    lengthscales"""
+    wins = []
+    for i, (X, Y, Z, _) in enumerate(_windows(counts, N, 2, seed0=5)):
+        kl = _mixed_kernels()
+        for p, d in enumerate(kl):
+            d["variance"] *= 1.0 + 0.1 * ((i + p) % 3)
+            d["lengthscales"] *= 1.0 + 0.2 * ((2 * i + p) % 3)
+        wins.append((X, Y, Z, kl))
+    return wins
+
+
+def test_ragged_windows_with_a_mixed_kernel_sum(gp_handle):
+    """test_ragged_windows_match_their_own_size with counts [16, 9, 1] on an M = 16 plan, n = 70 (a 64-frame tile and a partial
+    one), S = 17 (a 16-draw block and one draw) and the mixed sum: the strides of a process record where they all differ: a
+    source's component offset inside C = 47, the eps_z row stride M = 16 against the feature-table stride k = 9 or 1, a
+    Matern12 source without a table beside sources padded to 20 partials in one launch.  The inputs are conditioned for the 1e-8 rule
+    (tests/test_sample_sparse_cpu.py::test_ragged_mixed_gpu_shape_is_well_conditioned: two host routes differ by 1.8e-15)."""
+    from gpitch_amd.windows import SgprWindowBatch
+    counts, N, P, M, S, n = [16, 9, 1], 300, 4, 16, 17, 70
+    wins = _ragged_mixed_windows(counts, N)
+    assert ref.eps_shapes(wins[0][3], n, M, S) == ((S, 47, n), (S, 47, M), (S, 2, M))
+    tmpl = _model(*wins[0][:3], wins[0][3], 0.3, gp_handle)
+    dev = SgprWindowBatch(tmpl, 3, N, M, handle=gp_handle)
+    dev.load([w[0] for w in wins], [w[1] for w in wins], [w[2] for w in wins])
+    zpad = np.full((3, M), np.nan)
+    for i, w in enumerate(wins):
+        zpad[i, :counts[i]] = w[2].reshape(-1)
+    dev.Z.copy_(gp_handle.torch.as_tensor(zpad))
+    noises = [0.2 + 0.05 * i for i in range(3)]
+    pv = np.stack([_params_vector(nz, w[3]) for nz, w in zip(noises, wins)])
+    xnews = [np.linspace(w[0].min(), w[0].max(), n).reshape(-1, 1) for w in wins]
+    per = [_random_eps(w[3], n, M, S, 80 + i) for i, w in enumerate(wins)]
+    for i, k in enumerate(counts):
+        per[i][1][:, :, k:] = np.nan
+        per[i][2][:, :, k:] = np.nan
+    eps = [np.stack([e[q] for e in per]) for q in range(3)]
+    got = dev.sample_s_sparse(pv, xnews, num_samples=S, eps=eps)
+    assert got.shape == (3, P, S, n) and np.isfinite(got).all()
+    for i, w in enumerate(wins):
+        k = counts[i]
+        one = _model(w[0], w[1], w[2], w[3], noises[i], gp_handle)
+        own = [per[i][0], per[i][1][:, :, :k], per[i][2][:, :, :k]]
+        want = one.sample_s_sparse(xnews[i], num_samples=S, eps=own)
+        rest = ref.sample_sources(xnews[i], w[0], w[1], w[2], w[3], noises[i], *own)
+        for q in range(P):
+            print("slot %d source %d: |batch - one window| %.3e, |batch - restatement| %.3e at |ref| %.3e" % (
+                i, q, np.abs(got[i, q] - want[q][:, :, 0]).max(), np.abs(got[i, q] - rest[q]).max(), np.abs(rest[q]).max()))
+            _close(got[i, q], want[q][:, :, 0], 1e-8)
+            _close(got[i, q], rest[q], 1e-8)
+        one._destroy()
+    dev.close()
+    tmpl._destroy()
+
+
 # ---- 7. eps=None: the device generator ---------------------------------------------------------------------------------------
 def test_seeded_draws_and_their_mean(gp_handle):
     X, Y, Z, kl, noise, Xs = ref.smallest_problem()

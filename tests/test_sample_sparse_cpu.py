@@ -34,6 +34,39 @@ def test_restatement_reproduces_the_joint_posterior_covariance():
         assert np.abs(mean0[p] - sm[p][:, 0]).max() <= 1e-12
 
 
+def test_ragged_mixed_gpu_shape_is_well_conditioned():
+    """The inputs of tests/test_gpu_sample_sparse.py::test_ragged_windows_with_a_mixed_kernel_sum: two host routes of the same
+    map (the restatement's triangular solves; products with the explicit W = L^-1, WB = LB^-1 the device holds) agree to a
+    tenth of the 1e-8 rule in every slot, as tests/test_pdgp_sample_cpu.py asks of the Pdgp shapes."""
+    from scipy.linalg import solve_triangular
+    from oracle import gpflow05 as orc
+    from test_gpu_sample_sparse import _ragged_mixed_windows, _random_eps
+    counts, N, M, S, n = [16, 9, 1], 300, 16, 17, 70
+    for i, ((X, Y, Z, kl), k) in enumerate(zip(_ragged_mixed_windows(counts, N), counts)):
+        noise = 0.2 + 0.05 * i
+        Xs = np.linspace(X.min(), X.max(), n).reshape(-1, 1)
+        ex, ez, eu = _random_eps(kl, n, M, S, 80 + i)
+        ez, eu = ez[:, :, :k], eu[:, :, :k]
+        a = ref.sample_sources(Xs, X, Y, Z, kl, noise, ex, ez, eu)
+        err, Kdg, L, A, AAT, LB, c = orc.sgpr_common(X, Y, Z, kl, noise)
+        W, WB = solve_triangular(L, np.eye(k), lower=True), solve_triangular(LB, np.eye(k), lower=True)
+        t, order = np.concatenate([Xs.ravel(), Z.ravel()]), ref.merged_order(Xs, Z)
+        u0, off, prior_x = np.sqrt(ref.JITTER) * eu[:, 0, :], 0, []
+        for kp in kl:
+            cp = ref.components(kp)
+            pr = ref.prior_paths(kp, t, order, np.concatenate([ex[:, off:off + cp], ez[:, off:off + cp]], axis=2))
+            prior_x.append(pr[:, :n])
+            u0 = u0 + pr[:, n:]
+            off += cp
+        beta = W.T.dot(WB.T.dot((c.reshape(1, k) + eu[:, 1, :]).T) - W.dot(u0.T))
+        for p, kp in enumerate(kl):
+            b = prior_x[p] + orc.K(kp, Z, Xs).T.dot(beta).T
+            bar = 1e-8 * max(np.abs(a[p]).max(), 1e-3)
+            d = np.abs(a[p] - b).max()
+            print("slot %d source %d: host routes differ by %.2e, a tenth of the bar is %.2e" % (i, p, d, 0.1 * bar))
+            assert d <= 0.1 * bar, (i, p, d, bar)
+
+
 def test_merged_order():
     from gpitch_amd import merged_order
     z = np.array([0.1, 0.3, 0.5])
