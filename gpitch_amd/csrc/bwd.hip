@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(256) rank1_tril_kernel(const GemmProblem* __re
   }
 }
 
-// o0 = op(A) v0, A is M x M (lda); trans: o0[j] = sum_i A[i][j] v0[i].   grid (M, batch), one block per output
+// o0 = op(A) v0, A is M x M (lda); trans: o0[j] = sum_i A[i][j] v0[i]; if o1: o1 += that.   grid (M, batch), one block per output
 __global__ void __launch_bounds__(64) matvec_kernel(const GemmProblem* __restrict__ probs, int trans) {
   const GemmProblem p = probs[blockIdx.y];
   const int r = blockIdx.x;
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(64) matvec_kernel(const GemmProblem* __restric
   if (!trans) for (int k = threadIdx.x; k < p.M; k += 64) acc = fma(p.A[(int64_t)r * p.lda + k], p.v0[k], acc);
   else        for (int k = threadIdx.x; k < p.M; k += 64) acc = fma(p.A[(int64_t)k * p.lda + r], p.v0[k], acc);
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if (threadIdx.x == 0) p.o0[r] = acc;
+  if (threadIdx.x == 0) { p.o0[r] = acc; if (p.o1) p.o1[r] += acc; }
 }
 
 // out[g] = sum_n v[g * stride + n]   (one block per row; fixed reduction order)
@@ -745,7 +745,9 @@ __device__ __forceinline__ hy_gcbytes hyl_uniform(hy_gcbytes p) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
   return (hy_gcbytes)(((uint64_t)hi << 32) | lo);
 }
-template <int NT, bool G32>
+// SC: the items' G strips want their columns scaled by 2 gscale[j] on the way in (the Q route: Kuf_bar = G diag(2 gv) is never
+// formed in memory) — one more column table and one multiply per entry.
+template <int NT, bool G32, bool SC = false>
 __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperItem one, const HyperItem* __restrict__ items,
                                                                     const double* __restrict__ x2s, int n2s, int col_seg) {
   const HyperItem it = gp_item(one, items, blockIdx.y);      // a whole kernel family in one launch: blockIdx.y = item (latent GP)
@@ -762,7 +764,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperI
                  th = (hy_gcptr)it.k.theta;
   __shared__ double etab[GP_EXP_TAB];
   __shared__ double red[4][2 + 2 * NT * 16];
-  __shared__ __attribute__((aligned(16))) double t_cf[HYL_CF_MAX], t_b[HYL_CF_MAX], t_gm[HYL_CF_MAX];
+  __shared__ __attribute__((aligned(16))) double t_cf[HYL_CF_MAX], t_b[HYL_CF_MAX], t_gm[HYL_CF_MAX], t_sc[SC ? HYL_CF_MAX : 2];
   __shared__ unsigned char t_side[HYL_CF_MAX], t_cls[HYL_CF_MAX / 16];
   __shared__ double wg_lo[4], wg_hi[4];
   gp_exp_tab_init(etab);
@@ -805,6 +807,7 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperI
     if (A - b >= HYR_SEP) { v = gp_exp_neg(-(A - b), etab); side = 0; }
     else if (b - B >= HYR_SEP) { v = gp_exp_neg(-(b - B), etab); side = 1; }
     t_cf[j] = v; t_b[j] = b; t_gm[j] = ggm[cw0 + j]; t_side[j] = side;
+    if (SC) t_sc[j] = 2.0 * ((hy_gcptr)it.gscale)[cw0 + j];
   }
   __syncthreads();
   for (int blk = tid; blk * 16 < nseg_cols; blk += 256) {
@@ -858,7 +861,12 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperI
     const d2v gm0 = *reinterpret_cast<const d2v*>(t_gm + cl), gm1 = *reinterpret_cast<const d2v*>(t_gm + cl + 8);
     const double cfv[4] = {cf0.x, cf0.y, cf1.x, cf1.y}, bsv[4] = {bs0.x, bs0.y, bs1.x, bs1.y},
                  gmv[4] = {gm0.x, gm0.y, gm1.x, gm1.y};
-    const double gv[4] = {b.g[0].x, b.g[0].y, b.g[1].x, b.g[1].y}, kv[4] = {b.kv[0].x, b.kv[0].y, b.kv[1].x, b.kv[1].y};
+    double gv[4] = {b.g[0].x, b.g[0].y, b.g[1].x, b.g[1].y};
+    const double kv[4] = {b.kv[0].x, b.kv[0].y, b.kv[1].x, b.kv[1].y};
+    if (SC) {
+      const d2v sc0 = *reinterpret_cast<const d2v*>(t_sc + cl), sc1 = *reinterpret_cast<const d2v*>(t_sc + cl + 8);
+      gv[0] *= sc0.x; gv[1] *= sc0.y; gv[2] *= sc1.x; gv[3] *= sc1.y;
+    }
     double wvE[4], wd[4];
     if (cls != 2) {
       const double rf = cls ? rfn : rfp;
@@ -1101,7 +1109,7 @@ static void hyper_item_fill(HyperItem* it, DevKern k, const double* x1, int n1, 
   it->f1 = feat;
   it->f2 = (x2 == x1 || !feat) ? feat : feat + gp_align_up((size_t)2 * mp * n1, 32);
   it->partials = partials; it->gz = gz; it->kvals = kvals;
-  it->ldg = ldg; it->ldk = ldk; it->n1 = n1; it->n2 = n2; it->symmetric = symmetric; it->g32 = g32;
+  it->ldg = ldg; it->ldk = ldk; it->n1 = n1; it->n2 = n2; it->symmetric = symmetric; it->g32 = g32; it->gscale = nullptr;
 }
 static void hyper_finish_item_fill(HyperFinishItem* it, DevKern k, const double* partials, int nparts, const double* gv_sum,
                                    double* g_theta, const double* gz_partials, int ncolblocks, int n1, double* g_z) {
@@ -1154,13 +1162,16 @@ static int hyper_generic_dispatch(gp_handle h, int type, int m, const HyperItem&
 // The matrix-core (row-streaming) contraction of `count` Mercer problems, rows_form as hy_rows_form gives it (2: lean):
 // nseg column segments of col_seg columns each.  Returns the partial records each problem leaves.
 static int hyper_rows_dispatch(gp_handle h, int rows_form, int type, int m, bool g32, const HyperItem& one, const HyperItem* items,
-                               int count, int n1, const double* x2s, int n2s, int col_seg, int nseg) {
+                               int count, int n1, const double* x2s, int n2s, int col_seg, int nseg, bool gscale = false) {
   dim3 gridm((n1 + 63) / 64, count, nseg);
   const int nt = (2 * sm_mpad(m) + 15) / 16;
 #define HYL_GO(NT_, G32_) hipLaunchKernelGGL((hyper_sm_rows_lean_kernel<NT_, G32_>), gridm, dim3(256), 0, h->stream, one, items, x2s, n2s, col_seg)
 #define HYR_GO(NT_, M52_, G32_) hipLaunchKernelGGL((hyper_sm_rows_kernel<NT_, M52_, G32_>), gridm, dim3(256), 0, h->stream, one, items, x2s, n2s, col_seg)
-  if (rows_form == 2) HYL_DISPATCH(HYL_GO, nt, g32);
+#define HYL_GO_SC(NT_) hipLaunchKernelGGL((hyper_sm_rows_lean_kernel<NT_, false, true>), gridm, dim3(256), 0, h->stream, one, items, x2s, n2s, col_seg)
+  if (rows_form == 2 && gscale) { if (nt == 1) HYL_GO_SC(1); else if (nt == 2) HYL_GO_SC(2); else HYL_GO_SC(3); }
+  else if (rows_form == 2) HYL_DISPATCH(HYL_GO, nt, g32);
   else HYR_DISPATCH(HYR_GO, nt, type != GP_KERN_MERCER_MATERN12SM, g32);
+#undef HYL_GO_SC
 #undef HYL_GO
 #undef HYR_GO
   return gridm.x * gridm.z;
@@ -1257,20 +1268,30 @@ gp_status launch_hyper_finish_items(gp_handle h, const HyperFinishItem* d_items,
 // Many contractions of one kernel family (same type and partial count, same n1 x n2) in one launch, one item each.
 // *nparts = partial records each item leaves.
 gp_status launch_hyper_contract_items(gp_handle h, int type, int m, const HyperItem* d_items, int count, int n1, int n2,
-                                      int with_gz, int* nparts, int use_mfma, const double* x2_shared, int g32_items, int lean_items) {
+                                      int with_gz, int* nparts, int use_mfma, const double* x2_shared, int g32_items, int lean_items,
+                                      int gscale_items) {
   if (count <= 0) return GP_OK;
+  if (gscale_items && !(use_mfma && lean_items && !g32_items && !with_gz && hyper_lean_takes(type, m, n1, n2, count)))
+    return gp_fail(h, GP_ERR_UNSUPPORTED, "Kuf-side contraction: no kernel applies a column scale to this family");
   GpTimerScope ts(h, GP_TIMER_HYPER);
   int col_seg = 0, nseg = 0, np;
   if (gp_kern_is_mercer(type)) hyr_geometry(n1, n2, count, &col_seg, &nseg);
   const bool lean_ok = lean_items && type == GP_KERN_MERCER_MATERN12SM && (n1 % 16) == 0 && (n2 % 16) == 0 && col_seg <= HYL_CF_MAX;
   const int rows_form = gp_kern_is_mercer(type) ? hy_rows_form((2 * sm_mpad(m) + 15) / 16, lean_ok) : 0;
   if (use_mfma && gp_kern_is_mercer(type) && !with_gz && rows_form > 0)
-    np = hyper_rows_dispatch(h, rows_form, type, m, g32_items != 0, HyperItem{}, d_items, count, n1, x2_shared, n2, col_seg, nseg);
+    np = hyper_rows_dispatch(h, rows_form, type, m, g32_items != 0, HyperItem{}, d_items, count, n1, x2_shared, n2, col_seg, nseg,
+                             gscale_items != 0);
   else
     np = hyper_generic_dispatch(h, type, m, HyperItem{}, d_items, count, n1, n2, x2_shared, n2, with_gz != 0);
   GP_HIP_CHECK(h, hipGetLastError());
   if (nparts) *nparts = np;
   return GP_OK;
+}
+bool hyper_lean_takes(int type, int m, int n1, int n2, int count) {
+  if (type != GP_KERN_MERCER_MATERN12SM || count <= 0 || (n1 % 16) || (n2 % 16)) return false;
+  int col_seg = 0, nseg = 0;
+  hyr_geometry(n1, n2, count, &col_seg, &nseg);
+  return col_seg <= HYL_CF_MAX && hy_rows_form((2 * sm_mpad(m) + 15) / 16, true) == 2;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1279,9 +1300,140 @@ gp_status launch_hyper_contract_items(gp_handle h, int type, int m, const HyperI
 // S_QW_* / S_GQ_* / S_WB_*: unwhitened model only (see pdgp_backward).
 enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
                S_E, S_EH, S_WBAR, S_LU, S_RANK1, S_R, S_ALPHA, S_G, S_T2, S_LBAR, S_P, S_T3, S_S, S_WB_R1, S_WB_L,
+               // Q route, entry i = latent GP q0 + i: E, R, beta and Q = R W of the forward pass (filled whether or
+               // not a gradient is asked), then T = W Qbar, H = T W^T and u = W v of the backward pass
+               S_QE, S_QR, S_QALPHA, S_QQ, S_QT, S_QHH, S_QU,
                S_COUNT };
 static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
 
+
+// ---- Q route --------------------------------------------------------------------------------------------------------
+// With E = Lq Lq^T - I, Q = W^T E W and beta = W^T q_mu the whitened conditional is
+//   fmean = Kuf^T beta,  fvar = kdiag + colsum(Kuf o G),  G = Q Kuf                      (one dense strip product)
+// and its reverse pass
+//   Kuf_bar = G diag(2 gv) + beta gm^T        (no product: the contraction reads G and scales its columns)
+//   Qbar = Kuf diag(2 gv) Kuf^T, v = Kuf gm   (the split-K product on Kuf);  H = W Qbar W^T, u = W v: the chain's H and u.
+// Which latent GPs take it at n frames (p->q0, p->nq, p->qk0): shapes, types, the gradient needs and gp_pdgp_set_qform alone,
+// never the overlap level.  All MercerMatern12sm GPs of a whitened plan, when they are float64, train their hyper-parameters
+// over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
+// batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
+void pdgp_qform_select(gp_pdgp_plan p, int n) {
+  p->q0 = p->nq = p->qk0 = 0;
+  if (!gp_switches().qform || !p->qform || !p->whiten) return;
+  int first = -1, last = -1, cnt = 0, m = -1;
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    if (q.ktype != GP_KERN_MERCER_MATERN12SM) continue;
+    if (q.f32 || !q.need_theta || q.need_z || !p->bw[g].Q || (m >= 0 && q.m != m)) return;
+    m = q.m;
+    if (first < 0) first = g;
+    last = g; cnt++;
+  }
+  if (cnt == 0 || last - first + 1 != cnt) return;
+  struct Key { int type, m, f32; };
+  std::vector<Key> seen;
+  int qk0 = 0;
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    if (!(q.need_theta || q.need_z)) continue;
+    if (g < first) qk0++;
+    const Key k{q.ktype, gp_kern_has_partials(q.ktype) ? q.m : 0, q.f32};
+    const bool same = !seen.empty() && seen.back().type == k.type && seen.back().m == k.m && seen.back().f32 == k.f32;
+    if (same) continue;
+    for (const Key& s : seen) if (s.type == k.type && s.m == k.m && s.f32 == k.f32) return;
+    seen.push_back(k);
+  }
+  if (!cond_batch_uniform(p->cb, n) || !gemm_wave_takes(6, p->maxM, n, 1) || !hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, p->maxM, n, cnt)) return;
+  p->q0 = first; p->nq = cnt; p->qk0 = qk0;
+}
+
+// the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
+void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
+  for (int i = 0; i < p->nq; i++) {
+    const int g = p->q0 + i;
+    const PdgpGP& q = p->gps[g];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& b = p->bw[g];
+    const int M = q.M;
+    auto P = [&](int slot) -> GemmProblem& {
+      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + i * sizeof(GemmProblem));
+      memset(&r, 0, sizeof(r));
+      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+      return r;
+    };
+    const double* q_sqrt = params + q.off_qsqrt;
+    { GemmProblem& r = P(S_QE); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
+    { GemmProblem& r = P(S_QR); r.A = t.W; r.B = b.E; r.C = b.R; }
+    { GemmProblem& r = P(S_QALPHA); r.A = t.W; r.v0 = params + q.off_qmu; r.o0 = b.alpha; }
+    // (the guard reads L through v0: qform_guard_kernel)
+    { GemmProblem& r = P(S_QQ); r.A = b.R; r.B = t.W; r.C = b.Q; r.v0 = t.L; }
+  }
+}
+
+// Guard of the Q route: Q inverts Kuu + jitter I explicitly, so its error grows with cond_2 of that matrix (not its root), and
+// the lengthscale is trained on the device.  c = ||L||_F^2 ||W||_F^2 = tr(K) tr(K^-1) >= cond_2(K); above GP_QFORM_COND_MAX M^2
+// (switches.h; or not finite) the handle's status word is raised, as the scan's frame check does, and the next host-scalar call fails.
+__global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __restrict__ probs, int g0, double cmax, int32_t* status) {
+  const GemmProblem p = probs[blockIdx.x];
+  const double* L = p.v0;
+  const double* W = p.B;
+  double sl = 0.0, sw = 0.0;
+  for (int idx = threadIdx.x; idx < p.M * p.M; idx += 256)      // (the lower triangles: above them L still holds Kuu)
+    if (idx % p.M <= idx / p.M) { sl = fma(L[idx], L[idx], sl); sw = fma(W[idx], W[idx], sw); }
+  __shared__ double red[2][4];
+  for (int o = 32; o > 0; o >>= 1) { sl += __shfl_down(sl, o, 64); sw += __shfl_down(sw, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sl; red[1][threadIdx.x >> 6] = sw; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double c = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+    if (!(c <= cmax * (double)p.M * (double)p.M)) { status[0] = 4; status[1] = 0; status[2] = g0 + (int)blockIdx.x; }
+  }
+}
+
+// E, R, beta, Q and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
+// (behind the factorisation it has just run, beside the other GPs' strip products), else in line; h->stream waits either way.
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n) {
+  gp_handle h = p->h;
+  const int nq = p->nq, maxM = p->maxM;
+  if (nq <= 0) return GP_OK;
+  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
+  bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
+  if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
+  hipStream_t mainq = h->stream;
+  if (aux) h->stream = h->aux_stream;
+  gp_status st = GP_OK;
+  GemmFlags f;
+  f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+  st = launch_gemm_batched(h, D(S_QE), nq, maxM, maxM, f);
+  if (st == GP_OK) st = launch_sub_identity_batched(h, D(S_QE), nq, maxM);
+  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
+  if (st == GP_OK) st = launch_gemm_batched(h, D(S_QR), nq, maxM, maxM, f);
+  if (st == GP_OK) st = launch_matvec_batched(h, D(S_QALPHA), nq, maxM, 1);
+  f = GemmFlags(); f.triB = TRI_LOWER;
+  if (st == GP_OK) st = launch_gemm_batched(h, D(S_QQ), nq, maxM, maxM, f);
+  if (st == GP_OK) {
+    hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, D(S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
+    if (hipGetLastError() != hipSuccess) st = gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
+  }
+  hipError_t e = hipSuccess;
+  if (aux) {
+    e = hipEventRecord(h->ev_q, h->aux_stream);
+    h->stream = mainq;
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_q, 0);
+  }
+  GP_CHECK(st);
+  if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
+  return GP_OK;
+}
+
+// f(first slot, count) over the compacted batch without the Q run, whose E, R and beta the forward pass has left
+template <typename F>
+static gp_status pdgp_non_q_slots(gp_pdgp_plan p, F f) {
+  if (p->nq <= 0) return f(0, p->nK);
+  if (p->qk0 > 0) GP_CHECK(f(0, p->qk0));
+  if (p->qk0 + p->nq < p->nK) GP_CHECK(f(p->qk0 + p->nq, p->nK - p->qk0 - p->nq));
+  return GP_OK;
+}
 
 gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
   (void)x;
@@ -1322,7 +1474,20 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
     { GemmProblem& r = P(S_H); r.A = t.A; r.lda = ldN; r.B = t.A; r.ldb = ldN; r.K = n; r.v1 = gv; r.C = b.H;
       r.o2 = p->slabs + slab_off; slab_off += gp_align_up((size_t)p->nsplit * M * M * sizeof(double), 256) / sizeof(double);
       // fused u = A gm: partials per K-slice in o1, result in o0 and accumulated into grad q_mu (xa)
-      r.v2 = gm; r.o1 = b.upart; r.o0 = b.u; r.xa = g_mu; }
+      r.v2 = gm; r.o1 = b.upart; r.o0 = b.u; r.xa = g_mu;
+      // Q route: the same product on Kuf gives Qbar (into T2) and v = Kuf gm (into Lu); H and u follow from S_QT / S_QHH / S_QU
+      if (g >= p->q0 && g < p->q0 + p->nq) { r.A = t.Kuf; r.B = t.Kuf; r.C = b.T2; r.o0 = b.Lu; r.xa = nullptr; } }
+    if (g >= p->q0 && g < p->q0 + p->nq) {
+      auto PQ = [&](int slot) -> GemmProblem& {
+        GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + (g - p->q0) * sizeof(GemmProblem));
+        memset(&r, 0, sizeof(r));
+        r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+        return r;
+      };
+      { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
+      { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
+      { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
+    }
     { GemmProblem& r = P(S_U); r.A = t.A; r.lda = ldN; r.N = n; r.v0 = gm; r.o0 = b.u; r.o1 = g_mu; r.a_f32 = q.f32; }
     { GemmProblem& r = P(S_HLQ); r.A = b.H; r.B = q_sqrt; r.C = g_sqrt; }
     if (!white) {
@@ -1396,6 +1561,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
         it.k = t.kern; it.x1 = params + q.off_z; it.n1 = q.M; it.x2 = nullptr; it.n2 = n; it.G = bb.G; it.ldg = ldN;
         it.alpha = bb.alpha; it.gm = p->gFmu + (size_t)g * n; it.symmetric = 0; it.partials = bb.hyp_part; it.gz = nullptr;
         it.kvals = t.Kuf; it.ldk = ldN; it.g32 = q.f32;
+        if (g >= p->q0 && g < p->q0 + p->nq) { it.G = t.A; it.gscale = p->gFvar + (size_t)g * n; }     // Q route: G = Q Kuf, in A's strip
         if (gp_kern_is_mercer(q.ktype) && t.feat) {
           it.f1 = t.feat;
           it.f2 = t.feat + gp_align_up((size_t)2 * sm_mpad(q.m) * q.M, 32);
@@ -1424,17 +1590,19 @@ gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
   if (!(p->whiten && p->nK > 0 && n >= 4096 && p->overlap >= 2 && h->aux_stream && !h->aux_active)) return GP_OK;
   if (!h->ev_era && hipEventCreateWithFlags(&h->ev_era, hipEventDisableTiming) != hipSuccess) { h->ev_era = nullptr; return GP_OK; }
   auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
-  const int nK = p->nK, maxM = p->maxM;
+  const int maxM = p->maxM;
   hipStream_t mainq = h->stream;
   h->stream = h->aux_stream;
   gp_status st = GP_OK;
-  GemmFlags f;
-  f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-  st = launch_gemm_batched(h, D(S_E), nK, maxM, maxM, f);
-  if (st == GP_OK) st = launch_sub_identity_batched(h, D(S_E), nK, maxM);
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  if (st == GP_OK) st = launch_gemm_batched(h, D(S_R), nK, maxM, maxM, f);
-  if (st == GP_OK) st = launch_matvec_batched(h, D(S_ALPHA), nK, maxM, 1);
+  st = pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
+    GemmFlags f;
+    f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+    GP_CHECK(launch_gemm_batched(h, D(S_E) + s0, cnt, maxM, maxM, f));
+    GP_CHECK(launch_sub_identity_batched(h, D(S_E) + s0, cnt, maxM));
+    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
+    GP_CHECK(launch_gemm_batched(h, D(S_R) + s0, cnt, maxM, maxM, f));
+    return launch_matvec_batched(h, D(S_ALPHA) + s0, cnt, maxM, 1);
+  });
   if (st == GP_OK && kl_done) {
     st = launch_kl_white(h, p->d_misc + p->off.kl_items, p->G);
     *kl_done = (st == GP_OK);
@@ -1495,6 +1663,13 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, D(S_H), n64, maxM, n, p->nsplit, 1, 1, 2.0, uni));
       if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, D(S_H) + n64, G - n64, maxM, n, p->nsplit, 1, 1, 2.0, uni));
     }
+    if (p->nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
+      f = GemmFlags(); f.triA = TRI_LOWER;
+      GP_CHECK(launch_gemm_batched(h, D(S_QT), p->nq, maxM, maxM, f));
+      f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER;
+      GP_CHECK(launch_gemm_batched(h, D(S_QHH), p->nq, maxM, maxM, f));
+      GP_CHECK(launch_matvec_batched(h, D(S_QU), p->nq, maxM, 0));
+    }
     // grad q_sqrt += tril(H Lq)
     f = GemmFlags(); f.triB = TRI_LOWER; f.triC = TRI_LOWER; f.beta = 1.0;
     GP_CHECK(launch_gemm_batched(h, D(S_HLQ), G, maxM, maxM, f));
@@ -1525,16 +1700,22 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));
     } else {
       // E = Lq Lq^T - I
-      f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, D(S_E), nK, maxM, maxM, f));
-      GP_CHECK(launch_sub_identity_batched(h, D(S_E), nK, maxM));
+      GP_CHECK(pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
+        GemmFlags f;
+        f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+        GP_CHECK(launch_gemm_batched(h, D(S_E) + s0, cnt, maxM, maxM, f));
+        return launch_sub_identity_batched(h, D(S_E) + s0, cnt, maxM);
+      }));
     }
     if (!early_fork) GP_CHECK(wbar_chain());
     if (!pre) {
       // R = W^T E ; alpha = W^T mu
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, D(S_R), nK, maxM, maxM, f));
-      GP_CHECK(launch_matvec_batched(h, D(S_ALPHA), nK, maxM, 1));
+      GP_CHECK(pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
+        GemmFlags f;
+        f.transA = 1; f.triA = TRI_UPPER;
+        GP_CHECK(launch_gemm_batched(h, D(S_R) + s0, cnt, maxM, maxM, f));
+        return launch_matvec_batched(h, D(S_ALPHA) + s0, cnt, maxM, 1);
+      }));
     }
     // From here two independent chains remain: the Kuf side (the big Kuf_bar product and its contraction with
     // dK/dtheta over all frames) and the Kuu side (the Cholesky adjoint, six M x M products, and its contraction
@@ -1551,9 +1732,12 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     // (kink at 0) and RBF (not semiseparable) have no such form.  Like the fused form below the choice depends on shapes,
     // types and that promise alone — never on the overlap level — and needs every family in one contiguous run of the batch.
     const int nfam = (int)p->hy_fams.size();
-    std::vector<int> fslot(nfam, -1), ffuse(nfam, 0), fscan(nfam, 0);
+    std::vector<int> fslot(nfam, -1), ffuse(nfam, 0), fscan(nfam, 0), fq(nfam, 0);     // fq: the Q route's family (pdgp_qform_select)
     bool contiguous = (white && nfam > 0), any_scan = false;
-    for (int fi = 0; fi < nfam; fi++) { fslot[fi] = fam_slot0(p->hy_fams[fi]); if (fslot[fi] < 0) contiguous = false; }
+    for (int fi = 0; fi < nfam; fi++) {
+      fslot[fi] = fam_slot0(p->hy_fams[fi]); if (fslot[fi] < 0) contiguous = false;
+      fq[fi] = (p->nq > 0 && p->hy_fams[fi].gps[0] == p->q0) ? 1 : 0;
+    }
     for (int fi = 0; fi < nfam && contiguous; fi++) {
       const auto& fam = p->hy_fams[fi];
       fscan[fi] = (gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
@@ -1662,7 +1846,8 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       if (!fam.batched) { for (int g : fam.gps) GP_CHECK(kuf_contract(g)); return GP_OK; }
       int np = 0;
       GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + fam.first,
-                                           fam.count, fam.M, n, 0, &np, fam.mfma, x, fam.f32, 1));
+                                           fam.count, fam.M, n, 0, &np, fam.mfma, x, fam.f32, 1,
+                                           (p->nq > 0 && fam.gps[0] == p->q0) ? 1 : 0));
       for (int g : fam.gps) np_uf[g] = np;
       return GP_OK;
     };
@@ -1672,7 +1857,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     // bit-identical results — and needs every family in one contiguous run of the compacted batch.
     for (int fi = 0; fi < nfam && contiguous; fi++) {
       const auto& fam = p->hy_fams[fi];
-      bool ok = kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM && !fscan[fi] &&
+      bool ok = kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM && !fscan[fi] && !fq[fi] &&
                 (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type));
       for (int g : fam.gps) if (p->gps[g].need_z || !p->gps[g].need_theta) ok = false;
       ffuse[fi] = ok ? 1 : 0;
@@ -1680,6 +1865,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
     auto fdone = [&](int fi) { return ffuse[fi] || fscan[fi]; };   // the family's Kuf-side partial sums come with kuf_bar_family
     auto kuf_bar_family = [&](int fi) -> gp_status {          // one family's product (contiguous slots), fused form if chosen
       const auto& fam = p->hy_fams[fi];
+      if (fq[fi]) return GP_OK;      // Q route: Kuf_bar = G diag(2 gv) + beta gm^T needs no product (contract_family scales G's columns)
       if (fscan[fi]) {
         const bool side = scan_side && gp_side_begin(h);
         gp_status st2 = launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, x, n);
@@ -1695,7 +1881,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       return GP_OK;
     };
     bool any_fused = false;
-    for (int fi = 0; fi < nfam; fi++) any_fused |= (fdone(fi) != 0);
+    for (int fi = 0; fi < nfam; fi++) any_fused |= (fdone(fi) != 0 || fq[fi] != 0);
     int sm_fam = -1, other_fam = -1, sm_slot = -1, other_slot = -1;
     // (switches.h; -1 = by precision: with float32 strips the spectral-mixture family goes first — its vector-ALU contraction then runs
     // beside the other family's float32 matrix product, which leaves the vector ALU free; the float64 MFMA holds it, so there the
@@ -1718,7 +1904,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       const auto& fo = p->hy_fams[other_fam];
       if (fdone(other_fam)) {
         GP_CHECK(kuf_bar_family(other_fam));
-        GP_CHECK(kuf_bar(sm_slot, fs.count));
+        GP_CHECK(kuf_bar_family(sm_fam));
       } else {
         GP_CHECK(kuf_bar(other_slot, fo.count));
         const bool side = gp_side_begin(h);
@@ -1727,14 +1913,14 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
           gp_status s3 = gp_side_end(h);
           GP_CHECK(st2); GP_CHECK(s3);
         }
-        GP_CHECK(kuf_bar(sm_slot, fs.count));
+        GP_CHECK(kuf_bar_family(sm_fam));
         if (!side) GP_CHECK(contract_family(fo));
       }
       GP_CHECK(contract_family(fs));
     } else if (sm_slot >= 0 && other_slot >= 0) {
       const auto& fs = p->hy_fams[sm_fam];
       const auto& fo = p->hy_fams[other_fam];
-      GP_CHECK(kuf_bar(sm_slot, fs.count));
+      GP_CHECK(kuf_bar_family(sm_fam));
       const bool side = gp_side_begin(h);              // the side stream picks up once that product is through
       if (side) {
         gp_status st2 = contract_family(fs);

@@ -881,13 +881,19 @@ gp_status check_not_pd(gp_handle h) {
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   if (st[0] != 0) {
     h->not_pd_index = st[1];
-    char buf[160];
+    char buf[256];
     const bool stalled = (st[0] == 2);      // chol_cluster.hip: a wavefront gave up waiting for the cluster's exchange
     if (st[0] == 3) {                       // kuf_scan.hip: a descending pair of frames under gp_pdgp_set_frames_ascending
       snprintf(buf, sizeof(buf), "frames not ascending: frame %d is below frame %d although gp_pdgp_set_frames_ascending promised time order", st[1] + 1, st[1]);
       h->last_error = buf;
       GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
       return GP_ERR_BAD_ARG;
+    }
+    if (st[0] == 4) {                       // bwd.hip: the Q route's guard on ||L||_F^2 ||W||_F^2 >= cond_2(Kuu + jitter I)
+      snprintf(buf, sizeof(buf), "qform: Kuu of latent GP %d is too ill-conditioned for the Q route (tr(K) tr(K^-1) > GP_QFORM_COND_MAX M^2); gp_pdgp_set_qform(plan, 0) or GPITCH_AMD_SWITCHES=qform=0 selects the Cholesky route", st[2]);
+      h->last_error = buf;
+      GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
+      return GP_ERR_UNSUPPORTED;
     }
     if (stalled) snprintf(buf, sizeof(buf), "Cholesky failed: the workgroup cluster stalled (GPITCH_AMD_SWITCHES=chol_cluster=0 selects the one-workgroup kernels)");
     else snprintf(buf, sizeof(buf), "Cholesky failed: matrix %d is not positive definite (pivot %d)", st[2], st[1]);

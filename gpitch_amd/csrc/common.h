@@ -20,12 +20,12 @@ struct gp_handle_s {
   bool own_stream = false;
   std::string last_error;
   int32_t not_pd_index = -1;
-  int32_t* d_status = nullptr;   // device int[4]: {flag (1 not PD, 2 cluster stalled, 3 frames not ascending), pivot / frame index, gp_index, spare}
+  int32_t* d_status = nullptr;   // device int[4]: {flag (1 not PD, 2 cluster stalled, 3 frames not ascending, 4 qform guard), pivot / frame index, gp_index, spare}
   int num_cus = 256;
   GpLogisticTable logistic = {}; int num_logistic = 0;
   // helper stream for work that can overlap the main stream (the latency-bound Kuu factorisation runs on ~24 CUs
   // while the Kuf builds stream over the rest): created on first use, joined through events
-  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr;
+  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr, ev_q = nullptr;
   hipStream_t main_stream_saved = nullptr; bool aux_active = false, aux_pending = false;
   // second helper stream ("side"): one more independent piece of a step (the spectral-mixture Kuf-side contractions
   // underneath the second half of the Kuf_bar product); gp_side_begin / _end / _join
@@ -270,7 +270,7 @@ struct GemmFlags {
   int epilogue = 1;      // bitmask of GemmEpi
   int scale_mode = 0;    // 0 none; 1: opB(B)(k,n) *= v1[n]; 2: opB(B)(k,n) *= v1[k]
   int timer = GP_TIMER_SMALL_GEMM;
-  int role = 0;          // 1 cond_A, 2 cond_LTA (needs transA), 3 kuf_bar: dedicated 128x128 instantiations
+  int role = 0;          // 1 cond_A, 2 cond_LTA (needs transA), 3 kuf_bar: dedicated 128x128 instantiations; 6 G = Q Kuf (gemm_wave.hip only)
   int tile_m0 = 0, tile_mcount = 0;   // strip products (big tiles, no split-K): only row-blocks [m0, m0 + mcount) (0 = all)
   const double* aux_x = nullptr;      // role 5 (gemm_strip.hip): the frames x of the batch; aux_ktype: the stationary kernel type
   int aux_ktype = -1;

@@ -2,6 +2,7 @@
 // C-ABI operators.  Host-side orchestration only; all arithmetic is in the .hip kernels.
 #pragma once
 #include "common.h"
+#include <functional>
 
 // lik.hip helpers
 size_t cond_finish_item_bytes();
@@ -42,6 +43,7 @@ struct HyperItem {
   const double* f1; const double* f2; double* partials; double* gz;
   const double* kvals;            // the covariance strip itself (Mercer Kuf side, matrix-core form), or null
   int64_t ldg, ldk; int n1, n2, symmetric, g32;
+  const double* gscale;           // Q route: G's columns are still to be scaled by 2 gscale[j] (Kuf_bar = G diag(2 gv)); else null
 };
 struct HyperFinishItem {
   DevKern k;
@@ -53,7 +55,9 @@ struct HyperFinishItem {
 // (g32_items: the items' strips are float32 — all of them, as their g32 fields say)
 gp_status launch_hyper_contract_items(gp_handle h, int type, int m, const HyperItem* d_items, int count, int n1, int n2,
                                       int with_gz, int* nparts, int use_mfma = 0, const double* x2_shared = nullptr,
-                                      int g32_items = 0, int lean_items = 0);
+                                      int g32_items = 0, int lean_items = 0, int gscale_items = 0);
+// would that launch (use_mfma, lean_items, float64 strips) take hyper_sm_rows_lean_kernel, the form that applies gscale?
+bool hyper_lean_takes(int type, int m, int n1, int n2, int count);
 // one pass over G for the P MercerMatern12sm kernels of a sum (bwd.hip; true = taken)
 bool launch_hyper_contract_sum(gp_handle h, const DevKern* kernels, double* const* feats, double* const* partials, int P,
                                const double* x1, int n1, const double* x2, int n2, const double* G, int64_t ldg,
@@ -85,13 +89,14 @@ gp_status launch_kuf_scan(gp_handle h, int ktype, const KufScanItem* d_items, in
 // blocked): every region's offset and the total, from one walk (cond_batch_desc_layout).
 struct CondDescLayout {
   size_t chol_ptrs, w_ptrs, Ms, lds, f1, f1u, f2, finish;
+  size_t fq, finish_q;                                   // the Q route's product and finish items (CondBatch::q_desc; else f1's and finish's offsets)
   size_t cov_uu, cov_uf, feat_zuu, feat_zuf, feat_x;     // grouped covariance builds: Kuu + Kuf items, z / x feature items
   // blocked factorisation: per panel 2 pointer arrays, 1 size array, 4 GEMM problem arrays ...
   size_t blk_mats[CB_MAX_PANELS], blk_w[CB_MAX_PANELS], blk_M[CB_MAX_PANELS], blk_gemm[CB_MAX_PANELS][4];
   size_t diag_mats, diag_w, diag_M, diag_ld;             // ... and all panels' diagonal blocks as one batch
   size_t bytes;
 };
-CondDescLayout cond_batch_desc_layout(int count, int nblk);
+CondDescLayout cond_batch_desc_layout(int count, int nblk, bool q_desc = false);
 
 // One latent GP inside a batch of conditionals.
 struct CondTask {
@@ -112,6 +117,8 @@ struct CondTask {
   double* s1 = nullptr; double* s2 = nullptr; double* dot = nullptr;  // [rowblocks][N] partials
   double* fmean = nullptr; double* fvar = nullptr;                    // N each
   bool f32 = false;       // this GP's M x N strips (Kuf, A, A2) are float32 (per-GP precision: CondBatch::n64)
+  // Q route (CondBatch::nq): Q = W^T (Lq Lq^T - I) W (M x M) and beta = W^T q_mu, which the caller's hook fills
+  const double* Qm = nullptr; const double* beta = nullptr;
 };
 
 struct CondBatch {
@@ -135,18 +142,25 @@ struct CondBatch {
   std::vector<Group> groups;
   // blocked Kuu factorisation (engine.hip: cond_batch_factorize)
   bool blocked = false; int nblk = 0;
+  // Q route: the tasks [q0, q0 + nq) — float64, whitened, Qm and beta set — form G = Q Kuf into their A strip
+  // instead of A = W Kuf and Lq^T A when cond_batch_run is given a hook; set before cond_batch_upload
+  int q0 = 0, nq = 0;
+  bool q_desc = false;    // the descriptor block was sized with the Q route's regions (cond_batch_desc_bytes(count, true))
   bool diag_ready = false;   // set by a factorisation that recorded gp_handle_s::ev_diag after the diagonal blocks of W
 };
 
 int cond_batch_uniform(const CondBatch& cb, int N);
-size_t cond_batch_desc_bytes(int count);     // the largest layout of `count` tasks (CB_MAX_PANELS panels)
+size_t cond_batch_desc_bytes(int count, bool q_desc = false);     // the largest layout of `count` tasks (CB_MAX_PANELS panels)
 // carve the per-task buffers out of the arena (needs t.M and t.kern's type and partial count); on a measuring arena this
 // is the task's size
 bool cond_task_carve(GpArena& ar, CondTask& t, int N, bool whiten, bool f32 = false);
 gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitter);
 // run: Kuu -> chol -> W ; Kuf ; A = W Kuf ; (A2 = W^T A) ; Lq^T A ; reductions -> fmean, fvar
+// q_prepare: take the Q route for the tasks [q0, q0 + nq).  The hook is called once the factorisation is enqueued and the other
+// tasks' strip products are; it enqueues what fills Qm and beta and makes h->stream wait for it.  Null: every task takes
+// the Cholesky route (predictions always do).
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
-                         bool reuse_factor = false);
+                         bool reuse_factor = false, const std::function<gp_status()>* q_prepare = nullptr);
 // steps 1-2 of cond_batch_run alone, on the current stream: Kuu + jitter I -> L, W of every task (the uploaded descriptors'),
 // for a caller that needs the factorisation and no conditional (sample.hip)
 gp_status cond_batch_factor(gp_handle h, CondBatch& cb);

@@ -26,7 +26,7 @@ bool cond_task_carve(GpArena& ar, CondTask& t, int N, bool whiten, bool f32) {
   return ar.ok;
 }
 
-CondDescLayout cond_batch_desc_layout(int count, int nblk) {
+CondDescLayout cond_batch_desc_layout(int count, int nblk, bool q_desc) {
   CondDescLayout o = {};
   GpRegions region;
   const size_t G = count;
@@ -38,6 +38,8 @@ CondDescLayout cond_batch_desc_layout(int count, int nblk) {
   o.f1u = region(G * sizeof(GemmProblem));
   o.f2 = region(G * sizeof(GemmProblem));
   o.finish = region(G * cond_finish_item_bytes());
+  o.fq = q_desc ? region(G * sizeof(GemmProblem)) : o.f1;
+  o.finish_q = q_desc ? region(G * cond_finish_item_bytes()) : o.finish;
   o.cov_uu = region(G * sizeof(CovItem));
   o.cov_uf = region(G * sizeof(CovItem));
   o.feat_zuu = region(G * sizeof(FeatItem));
@@ -58,7 +60,7 @@ CondDescLayout cond_batch_desc_layout(int count, int nblk) {
   o.bytes = region.off;
   return o;
 }
-size_t cond_batch_desc_bytes(int count) { return cond_batch_desc_layout(count, CB_MAX_PANELS).bytes; }
+size_t cond_batch_desc_bytes(int count, bool q_desc) { return cond_batch_desc_layout(count, CB_MAX_PANELS, q_desc).bytes; }
 
 gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitter) {
   const int G = (int)cb.tasks.size();
@@ -82,7 +84,8 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
   // critical path: 0.46 ms at M = 256)
   const bool blk256 = gp_switches().blocked_256 != 0;
   cb.blocked = (cb.maxM > 256 || (blk256 && cb.maxM > 128 && cb.N >= 4096)) && cb.nblk <= CB_MAX_PANELS;
-  cb.off = cond_batch_desc_layout(G, cb.blocked ? cb.nblk : 0);
+  cb.off = cond_batch_desc_layout(G, cb.blocked ? cb.nblk : 0, cb.q_desc);
+  if (cb.nq > 0 && !cb.q_desc) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a Q run without its descriptor regions");
   cb.h_desc.assign(cb.off.bytes, 0);
   double** cp = (double**)(cb.h_desc.data() + cb.off.chol_ptrs);
   double** wp = (double**)(cb.h_desc.data() + cb.off.w_ptrs);
@@ -92,6 +95,8 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
   GemmProblem* f1u = (GemmProblem*)(cb.h_desc.data() + cb.off.f1u);
   GemmProblem* f2 = (GemmProblem*)(cb.h_desc.data() + cb.off.f2);
   char* fin = cb.h_desc.data() + cb.off.finish;
+  GemmProblem* fq = (GemmProblem*)(cb.h_desc.data() + cb.off.fq);
+  char* fin_q = cb.h_desc.data() + cb.off.finish_q;
   // which strip products of the float64 tasks take the wave form (one partial row per 64-row tile instead of per 128)
   const int uni = cond_batch_uniform(cb, N);
   cb.wave_a = gemm_wave_takes(1, cb.maxM, N, uni);
@@ -122,6 +127,17 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
     const int rb_a = (t.f32 ? cb.wave_a32 : cb.wave_a) ? rb64 : rb, rb_lta = (t.f32 ? cb.wave_lta32 : cb.wave_lta) ? rb64 : rb;
     cond_finish_fill(fin + g * cond_finish_item_bytes(), t.s1, rb_a, t.s2, t.q_sqrt ? rb_lta : 0, t.dot,
                      whiten ? rb_a : rb, t.kern, t.fmean, t.fvar);
+    // Q route: G = Q Kuf into the A strip; the partial rows of colsum(Kuf o G) take s2's place (fvar = (kdiag - 0) + that),
+    // those of Kuf^T beta the dot rows'.  Every other task's records repeat the Cholesky route's.
+    if (!cb.q_desc) continue;
+    fq[g] = f1[g];
+    memcpy(fin_q + g * cond_finish_item_bytes(), fin + g * cond_finish_item_bytes(), cond_finish_item_bytes());
+    if (g >= cb.q0 && g < cb.q0 + cb.nq) {
+      if (!whiten || t.f32 || !t.Qm || !t.beta || !t.q_sqrt || !gemm_wave_takes(6, cb.maxM, N, uni))
+        return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a task of the Q run does not qualify");
+      fq[g].A = t.Qm; fq[g].v0 = t.beta; fq[g].o0 = t.s2; fq[g].xb = nullptr;
+      cond_finish_fill(fin_q + g * cond_finish_item_bytes(), t.s1, 0, t.s2, rb64, t.dot, rb64, t.kern, t.fmean, t.fvar);
+    }
   }
   // Grouped covariance builds: the latent GPs are sorted into kernel families (type, padded partial count); each
   // family's Kuu (and Kuf) matrices are built by ONE launch (48 + 36 launches per step at P = 12 otherwise, which
@@ -335,7 +351,7 @@ gp_status cond_batch_factor(gp_handle h, CondBatch& cb) {
 }
 
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
-                         bool reuse_factor) {
+                         bool reuse_factor, const std::function<gp_status()>* q_prepare) {
   const int G = (int)cb.tasks.size();
   if (G == 0 || N <= 0) return GP_OK;
   if (!cb.uploaded || cb.N != N) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch descriptors not uploaded");
@@ -366,10 +382,15 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
   };
   // a strip product over the batch: the float64 tasks [0, n64) on the float64 kernels, the float32 tasks behind them on the
   // float32 ones (f32flags: the flags of the float32 launch where they differ)
+  // Q route: the run [q0, q0 + nq) of float64 tasks is left out of these products (one launch on either side of it)
+  const int q0 = (q_prepare && cb.nq > 0) ? cb.q0 : 0, q1 = (q_prepare && cb.nq > 0) ? cb.q0 + cb.nq : 0;
   auto strips = [&](size_t off, const GemmFlags& f, const GemmFlags* f32flags = nullptr) -> gp_status {
     const GemmProblem* d = (const GemmProblem*)(cb.d_desc + off);
     const int n64 = (cb.n64 < 0) ? (cb.f32 ? 0 : G) : cb.n64;
-    if (n64 > 0) GP_CHECK(launch_gemm_batched(h, d, n64, cb.maxM, N, f));
+    if (q1 > q0) {
+      if (q0 > 0) GP_CHECK(launch_gemm_batched(h, d, q0, cb.maxM, N, f));
+      if (q1 < n64) GP_CHECK(launch_gemm_batched(h, d + q1, n64 - q1, cb.maxM, N, f));
+    } else if (n64 > 0) GP_CHECK(launch_gemm_batched(h, d, n64, cb.maxM, N, f));
     if (n64 < G) {
       GemmFlags g32 = f32flags ? *f32flags : f;
       // (float32 tasks: their own wave form — scratch for the float32 copy of the M x M operand is in xb; partial rows per 64-row tile)
@@ -446,7 +467,16 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     f.rows64_ok = cb.wave_lta ? 1 : 0;
     GP_CHECK(strips(cb.off.f2, f));
   }
+  // 4q. the Q run, behind the Cholesky-route tasks so that it never makes them wait for Q:  G = Q Kuf, colsum(Kuf o G), Kuf^T beta
+  if (q1 > q0) {
+    GP_CHECK((*q_prepare)());
+    GemmFlags f;
+    f.timer = GP_TIMER_COND_A; f.role = 6; f.big_tiles = 1;
+    f.epilogue = EPI_STORE | EPI_COLSUMSQ | EPI_COLDOT;
+    f.uniform_aligned = cond_batch_uniform(cb, N);
+    GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.fq) + q0, q1 - q0, cb.maxM, N, f));
+  }
   // 6. fmean / fvar
-  GP_CHECK(launch_cond_finish(h, cb.d_desc + cb.off.finish, G, N));
+  GP_CHECK(launch_cond_finish(h, cb.d_desc + ((q1 > q0) ? cb.off.finish_q : cb.off.finish), G, N));
   return GP_OK;
 }

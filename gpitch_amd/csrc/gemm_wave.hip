@@ -4,6 +4,8 @@
 //   role 1  A   = W Kuf      tf.matrix_triangular_solve(Lm, Kmn) + reduce_sum(A^2), A^T q_mu   (GPflow conditional,
 //   role 2  LTA = Lq^T A     tf.matmul(Lq^T, A) -> reduce_sum(LTA^2) only                        gpitch/pdgp.py:147-155)
 //   role 3  G   = R (A D)    backward: Kuf_bar (TF reverse mode of the same lines)
+//   role 6  G   = Q Kuf      Q = W^T (Lq Lq^T - I) W: a whitened Matern-1/2 spectral-mixture family's whole forward strip work
+//                            (DESIGN.md 3.03): fvar = kdiag + colsum(Kuf o G), fmean = Kuf^T beta, Kuf_bar = G diag(2 gv) + beta gm^T
 //
 // Why a third form.  gemm_strip.hip's tiles (128 x 128 per workgroup, operands staged through LDS, one barrier per K-tile,
 // two workgroups per CU) run the dense product at 0.83 of the matrix peak but the triangular ones at 0.65-0.75
@@ -63,13 +65,14 @@ struct WaveFlags {
 
 // One 64 x 64 tile: rows [i0, i0 + 64) of op(A) x columns [j0, j0 + 64) of B over k in [kbeg, kend) (multiples of 8).
 // TAG 1: op(A) = A lower triangular (k < i0 + 64; zeros above the diagonal are IN the matrix).  TAG 2: op(A) = A^T with A
-// lower triangular (k >= i0), walked downwards.  TAG 3: dense.  TAG 5 (KT = a stationary kernel type): TAG 3's product with the
+// lower triangular (k >= i0), walked downwards.  TAG 3: dense.  TAG 6: dense, no column scale; its column sums run over Kuf o C and Kuf o v0 (the
+// tile's own rows of the B strip, read again in the epilogue: they left the K loop's registers chunks ago).  TAG 5 (KT = a stationary kernel type): TAG 3's product with the
 // Kuf-side hyper-gradient contraction of that kernel as its epilogue (gemm_strip.hip role 5; bwd.hip hyper_contract_kernel:
 // sum_ij (Kuf_bar_ij + alpha_i gm_j) dK_ij / d(variance, lengthscale)), nothing stored: one partial record per wavefront tile.
 template <int TAG, int KT = -1>
 __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f, const int i0, const int j0, const int lane,
                                         double* etab = nullptr) {
-  constexpr bool DENSE = (TAG == 3 || TAG == 5);
+  constexpr bool DENSE = (TAG == 3 || TAG == 5 || TAG == 6);
   constexpr bool TA = (TAG == 2);
   constexpr bool KDOWN = (TAG == 2);
   const int lc = lane & 15, kq = lane >> 4;
@@ -208,7 +211,7 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
   // ---- epilogue -------------------------------------------------------------------------------------------------------
   // acc[a][b][r] = C(i0 + ROW(a, r), j0 + 32 (b >> 1) + 2 lc + (b & 1)),  ROW = 16 a + 4 r + kq  (TA: the row permutation
   // is irrelevant — role 2 stores nothing and its column sums run over all 64 rows)
-  if (DENSE) {
+  if (TAG == 3 || TAG == 5) {
     const gcptr2 gs = (gcptr2)((gcbytes)p.v1 + (int64_t)(j0 + 2 * lc) * 8);
     const dbl2 s0 = gs[0], s1 = gs[16];
     const double sc[4] = {f.alpha * s0.x, f.alpha * s0.y, f.alpha * s1.x, f.alpha * s1.y};
@@ -280,7 +283,7 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
   if (f.epi & (EPI_COLSUMSQ | EPI_COLDOT)) {
     // per-column sums over this tile's 64 rows, one partial row per 64-row tile: o0 / o1 [i0 / 64][N]
     double v0r[16];
-    if (f.epi & EPI_COLDOT) {
+    if (TAG != 6 && (f.epi & EPI_COLDOT)) {
       const gcptr gv0 = (gcptr)p.v0 + i0 + kq;
 #pragma unroll
       for (int a = 0; a < 4; a++)
@@ -288,16 +291,48 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
         for (int r = 0; r < 4; r++) v0r[4 * a + r] = gv0[16 * a + 4 * r];
     }
 #pragma unroll
-    for (int hh = 0; hh < 2; hh++) {
-      s2[hh] = dbl2{0.0, 0.0}; sd[hh] = dbl2{0.0, 0.0};
+    for (int hh = 0; hh < 2; hh++) { s2[hh] = dbl2{0.0, 0.0}; sd[hh] = dbl2{0.0, 0.0}; }
+    if (TAG == 6) {
+      // Kuf(i0 + 16 a + 4 r + kq, j0 + 32 hh + 2 lc + {0, 1}): the addressing of the C store below, on the B strip; one row
+      // tile's eight loads (and four entries of v0) at a time, fenced: hoisted together they spill
+      const int voffK = (int)(((int64_t)kq * p.ldb + 2 * lc) * 8);
+      const gcptr gv0 = (gcptr)p.v0 + i0 + kq;
 #pragma unroll
-      for (int a = 0; a < 4; a++)
+      for (int a = 0; a < 4; a++) {
+        GW_SB;
+        dbl2 kf[4][2];
+        double vb[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) vb[r] = gv0[16 * a + 4 * r];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-          const double x0 = acc[a][2 * hh][r], x1 = acc[a][2 * hh + 1][r];
-          s2[hh].x = fma(x0, x0, s2[hh].x); s2[hh].y = fma(x1, x1, s2[hh].y);
-          if (f.epi & EPI_COLDOT) { sd[hh].x = fma(x0, v0r[4 * a + r], sd[hh].x); sd[hh].y = fma(x1, v0r[4 * a + r], sd[hh].y); }
+          const int soK = (int)(((int64_t)(i0 + 16 * a + 4 * r) * p.ldb + j0) * 8);      // (scalar)
+#pragma unroll
+          for (int hh = 0; hh < 2; hh++)
+            kf[r][hh] = __builtin_bit_cast(dbl2, __builtin_amdgcn_raw_buffer_load_b128(rB, voffK + hh * 256, soK, 0));
         }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+          for (int hh = 0; hh < 2; hh++) {
+            s2[hh].x = fma(kf[r][hh].x, acc[a][2 * hh][r], s2[hh].x); s2[hh].y = fma(kf[r][hh].y, acc[a][2 * hh + 1][r], s2[hh].y);
+            sd[hh].x = fma(kf[r][hh].x, vb[r], sd[hh].x); sd[hh].y = fma(kf[r][hh].y, vb[r], sd[hh].y);
+          }
+      }
+      GW_SB;
+    }
+#pragma unroll
+    for (int hh = 0; hh < 2; hh++) {
+      if (TAG != 6) {
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const double x0 = acc[a][2 * hh][r], x1 = acc[a][2 * hh + 1][r];
+            s2[hh].x = fma(x0, x0, s2[hh].x); s2[hh].y = fma(x1, x1, s2[hh].y);
+            if (f.epi & EPI_COLDOT) { sd[hh].x = fma(x0, v0r[4 * a + r], sd[hh].x); sd[hh].y = fma(x1, v0r[4 * a + r], sd[hh].y); }
+          }
+      }
       s2[hh].x += __shfl_xor(s2[hh].x, 16, 64); s2[hh].x += __shfl_xor(s2[hh].x, 32, 64);
       s2[hh].y += __shfl_xor(s2[hh].y, 16, 64); s2[hh].y += __shfl_xor(s2[hh].y, 32, 64);
       if (f.epi & EPI_COLDOT) {
@@ -381,7 +416,7 @@ __global__ void __launch_bounds__(256, 2) gemm_wave_kernel(const GemmProblem* __
   const int cg = bid / f.nunits;
   const int u = (bid % f.nunits + cg) % f.nunits;
   const int j0 = cg * 256 + wv * GW_T;
-  if (TAG == 3 || TAG == 5) {
+  if (TAG == 3 || TAG == 5 || TAG == 6) {
     gw_tile<TAG, KT>(p, f, (f.t0 + u) * GW_T, j0, lane, etabs + ((TAG == 5) ? 64 * wv : 0));
   } else {
     // pair (t0 + u, t1 - 1 - u): the longer K range first (every pair starts on the strip's common end: k = 0 for the
@@ -400,7 +435,8 @@ static int gw_roles() { return gp_switches().strip_wave_roles; }      // bitmask
 
 // would a launch of that role and shape take the wave form?  (engine.hip sizes the partial-sum rows by it: 64-row tiles)
 bool gemm_wave_takes(int role, int maxM, int maxN, int uniform_aligned) {
-  if (!gw_enabled() || !uniform_aligned || role < 1 || (role > 3 && role != 5) || !((gw_roles() >> role) & 1)) return false;
+  // (role 6 has no other form, so strip_wave_roles does not list it: its caller keeps the Cholesky route when this says no)
+  if (!gw_enabled() || !uniform_aligned || role < 1 || (role > 3 && role != 5 && role != 6) || (role != 6 && !((gw_roles() >> role) & 1))) return false;
   return maxM > 0 && (maxM % GW_T) == 0 && (maxN % 256) == 0 && gp_strip_below_2gib(maxM, maxN, false);
 }
 
@@ -415,7 +451,7 @@ static gp_status gw_launch(gp_handle h, const GemmProblem* d_probs, int batch, i
     if (f.tile_mcount > 0 && 2 * (f.tile_m0 + f.tile_mcount) < tiles) wf.t1 = 2 * (f.tile_m0 + f.tile_mcount);
   }
   const int nt = wf.t1 - wf.t0;
-  wf.nunits = (TAG == 3 || TAG == 5) ? nt : (nt + 1) / 2;
+  wf.nunits = (TAG == 3 || TAG == 5 || TAG == 6) ? nt : (nt + 1) / 2;
   wf.epi = f.epilogue; wf.alpha = f.alpha; wf.N = N; wf.pad_ = 0; wf.xcols = f.aux_x;
   dim3 grid(wf.nunits * (N / 256), 1, batch);
   hipLaunchKernelGGL((gemm_wave_kernel<TAG, KT>), grid, dim3(256), 0, h->stream, d_probs, wf);
@@ -428,6 +464,11 @@ static gp_status gw_launch(gp_handle h, const GemmProblem* d_probs, int batch, i
 bool launch_gemm_wave(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxN, const GemmFlags& f, gp_status* st) {
   if (!gp_strip_below_2gib(maxM, maxN, false) || !gemm_wave_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
   if (f.beta != 0.0 || f.triC != TRI_NONE) return false;
+  if (f.role == 6) {
+    if (f.alpha != 1.0 || f.scale_mode != 0 || f.tile_m0 || f.tile_mcount) return false;
+    *st = gw_launch<6>(h, d_probs, batch, maxM, maxN, f);
+    return true;
+  }
   if (f.role >= 3 ? !(f.scale_mode == 1 && (f.alpha == 1.0 || f.alpha == 2.0 || f.alpha == 0.5 || f.alpha == 4.0)) : (f.alpha != 1.0)) return false;
   if (f.role == 5) {       // (the caller has asked gemm_fused_contraction_records first: it cannot fall back from here)
     if (!f.aux_x || f.tile_m0 || f.tile_mcount) { *st = gp_fail(h, GP_ERR_BAD_ARG, "fused Kuf_bar contraction: bad launch"); return true; }

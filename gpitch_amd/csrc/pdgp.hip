@@ -118,6 +118,11 @@ gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
   p->frames_ascending = (ascending != 0);
   return GP_OK;
 }
+gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (p->qform != (enable != 0)) { p->qform = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
+  return GP_OK;
+}
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
@@ -134,7 +139,9 @@ gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t*
 // throwaway copy of the plan and a measuring arena.
 static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
   p->cb.tasks.assign(p->G, CondTask());
-  p->cb.d_desc = ar.take<char>(cond_batch_desc_bytes(p->G));
+  p->cb.q_desc = false;      // (the Q route's descriptor regions: only where a latent GP could take it — as b.Q below)
+  for (const PdgpGP& q : p->gps) if (gp_switches().qform != 0 && p->whiten && !q.f32 && q.ktype == GP_KERN_MERCER_MATERN12SM) p->cb.q_desc = true;
+  p->cb.d_desc = ar.take<char>(cond_batch_desc_bytes(p->G, p->cb.q_desc));
   p->off = pdgp_misc_layout(p->G);
   p->d_misc = ar.take<char>(p->off.bytes);
   p->fmean = ar.take<double>((size_t)p->G * p->maxN);
@@ -167,6 +174,8 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       b.H = ar.take<double>(M * M); b.E = ar.take<double>(M * M); b.T1 = ar.take<double>(M * M);
       b.T2 = ar.take<double>(M * M); b.Wbar = ar.take<double>(M * M); b.R = ar.take<double>(M * M);
       b.G = ar.take<double>(gp_strip_doubles(M, p->maxN, p->gps[g].f32 != 0));
+      // (Q route, bwd.hip pdgp_qform_select: like the scan's arrays below, reserved before its setters have spoken)
+      if (gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM) b.Q = ar.take<double>(M * M);
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;
       b.u = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);
       b.upart = ar.take<double>((size_t)p->nsplit * M);
@@ -230,6 +239,9 @@ gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
 gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);  // bwd.hip
 gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done);
 gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);
+void pdgp_qform_select(gp_pdgp_plan p, int n);
+void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n);
 
 // (re)bind the parameter vector / batch to the device descriptors
 static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad,
@@ -251,6 +263,14 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
     t.fvar = fvar + (size_t)g * n;
   }
   p->cb.N = n;
+  p->cb.maxM = p->maxM;
+  pdgp_qform_select(p, n);
+  p->cb.q0 = p->q0; p->cb.nq = p->nq;
+  for (int g = 0; g < p->G; g++) {
+    const bool q = (g >= p->q0 && g < p->q0 + p->nq);
+    p->cb.tasks[g].Qm = q ? p->bw[g].Q : nullptr;
+    p->cb.tasks[g].beta = q ? p->bw[g].alpha : nullptr;
+  }
   GP_CHECK(cond_batch_upload(h, p->cb, p->whiten != 0, p->jitter));
   // KL items
   p->h_misc.assign(p->off.bytes, 0);
@@ -270,6 +290,7 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
       r.o0 = p->tr_part[g];
     }
   }
+  pdgp_upload_qform(p, params);
   if (grad) GP_CHECK(pdgp_upload_bwd(p, params, x, n, grad));
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_misc, p->h_misc.data(), p->off.bytes, hipMemcpyHostToDevice, h->stream));
   p->last_params = params; p->last_x = x; p->last_n = n; p->last_grad = grad;
@@ -287,7 +308,9 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
   p->factor_valid = false;   // an optimiser step normally follows: predictions must re-factorise
   GP_CHECK(pdgp_bind(p, params, x, n, grad, fmean ? fmean : p->fmean, fvar ? fvar : p->fvar));
   if (grad) GP_HIP_CHECK(h, hipMemsetAsync(grad, 0, (size_t)p->nparams * sizeof(double), h->stream));
-  GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter));
+  // (an ELBO takes the Q route with or without a gradient, so a step's ELBO is one number; predictions never do)
+  const std::function<gp_status()> q_prepare = [&]() -> gp_status { return pdgp_qform_prepare(p, n); };
+  GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr));
   bool kl_done = false;   // the whitened KL kernel went to the helper stream with the backward prefetch
   if (grad) GP_CHECK(pdgp_prefetch_backward(p, n, &kl_done));
   if (kl_done) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));   // behind the forward strips: no stall

@@ -10,7 +10,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // The plan's `misc` descriptor block: [KL items][PDGP_BWD_SLOTS arrays of G GemmProblems][KL items of the unwhitened
 // backward][G hyper-gradient finish items][2 G contraction items].  The backward pass uses the first S_COUNT slots
 // (bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
-#define PDGP_BWD_SLOTS 24
+#define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
 struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
@@ -41,6 +41,7 @@ struct BwdBufs {  // per-GP backward workspace (device)
   double* T2 = nullptr;     // M x M   scratch
   double* Wbar = nullptr;   // M x M
   double* R = nullptr;      // M x M   W^T E
+  double* Q = nullptr;      // M x M   R W = W^T E W: the Q route's forward operand (MercerMatern12sm GPs of a whitened float64 plan only)
   double* R32 = nullptr;    // float32 strips only: M * M floats, the float32 copy of R (gemm_wave_f32.hip)
   double* G = nullptr;      // M x N   K̄uf (dense part R (A D))
   double* u = nullptr;      // M       A gm
@@ -102,6 +103,10 @@ struct gp_pdgp_plan_s {
                                // stream, 2 also the H = A D A^T chain next to Kuf_bar
   bool frames_ascending = false;   // gp_pdgp_set_frames_ascending: the caller promises time-ordered batches
   bool era_ready = false;      // pdgp_prefetch_backward ran for the current evaluation
+  // Q route (bwd.hip pdgp_qform_select): gp_pdgp_set_qform's permission, and the run of latent GPs
+  // [q0, q0 + nq) that takes it at the bound batch size (nq = 0: none); qk0 = the run's first slot in the compacted batch
+  bool qform = false;
+  int q0 = 0, nq = 0, qk0 = 0;
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

@@ -22,11 +22,19 @@
 //   gemm_tile32       320    generic M x M products with fewer 64 x 64 tiles than this in the launch take 32 x 32 tiles (0: never)
 //   nt_cover          0      split-K product: workgroups the K-slices are chosen to cover (0: 1024 below 128 output tiles in the launch, else 2048)
 //   scan_side         1      a kuf_scan family's three launches go to the side stream, beside the other families' Kuf_bar product (0: ahead of it on the main stream)
+//   qform             1      a whitened MercerMatern12sm family with fixed inducing inputs forms G = Q Kuf, Q = W^T (Lq Lq^T - I) W, instead of A, Lq^T A and the Kuf_bar product
+//                            (gemm_wave.hip role 6; the caller enables it per plan, gp_pdgp_set_qform).  Q inverts Kuu explicitly: a guard on ||L||_F^2 ||W||_F^2
+//                            >= cond_2(Kuu + jitter I) raises the handle's status word above GP_QFORM_COND_MAX M^2 (below; DESIGN.md 3.03 has the ladder behind the value) (0: the Cholesky route)
 //
 // Unknown names are reported once on stderr and ignored.
 #pragma once
 struct GpSwitches {
   int strip_wave = 1, strip_wave_f32 = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 5), strip_wave_roles = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 5), strip_lean = 1, hyper_fuse = 1, kufbar_split = -1,
-      cond_a_early = 1, blocked_256 = 1, cov_sum = 1, hyper_sum = 1, chol_cluster = 1, aux_priority = 1, gemm_tile32 = 320, nt_cover = 0, kuf_scan = 1, scan_side = 1;
+      cond_a_early = 1, blocked_256 = 1, cov_sum = 1, hyper_sum = 1, chol_cluster = 1, aux_priority = 1, gemm_tile32 = 320, nt_cover = 0, kuf_scan = 1, scan_side = 1, qform = 1;
 };
+// qform guard: the Q route is admitted while c = ||L||_F^2 ||W||_F^2 = tr(K) tr(K^-1) <= GP_QFORM_COND_MAX * M^2 for K = Kuu + jitter I.
+// cond_2(K) <= c, and c / M^2 is (mean eigenvalue) x (mean inverse eigenvalue), so for one spectrum c grows with M^2 and the bound with
+// it.  Ladder (tests/test_qform_cpu.py): up to c / M^2 = 4 (cond_2 ~ 100-160) the Q route's deviation from a long-double
+// restatement stays within 5 x the Cholesky route's and below 1e-14 of scale; the benchmark's components sit at 1.1 - 2.7.
+#define GP_QFORM_COND_MAX 4.0
 const GpSwitches& gp_switches();     // abi.hip

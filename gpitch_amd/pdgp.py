@@ -272,9 +272,40 @@ class Pdgp(Parameterized):
         self._params.copy_(h.torch.as_tensor(host))
         self._tcode.copy_(h.torch.as_tensor(tc))
         flatvec.set_grad_needs(h, h.lib.gp_pdgp_set_grad_needs, self._plan, self._gps())
+        h.check(h.lib.gp_pdgp_set_qform(self._plan, int(self._qform_admissible())))
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                             self._free.data_ptr()))
         self._packed_key = self._host_key()
+
+    def _qform_admissible(self):
+        """May the engine take its Q route (one dense product where the Cholesky route needs three) for the
+        MercerMatern12sm latent GPs?  The route inverts Kuu explicitly, so it wants Kuu + jitter I well conditioned.  A Matern-1/2
+        envelope keeps it so when its lengthscale is near the inducing spacing (cond(Kuu) is bounded by the Ornstein-Uhlenbeck
+        matrix's, whatever the cosine mixture) — the transcription model's components, not every model's: so the engine's own
+        measure, tr(K) tr(K^-1) / M^2 >= cond(K) / M^2, is taken here from the values being packed, and the route is allowed at
+        three quarters of the bound the engine's device-side guard enforces at every evaluation (switches.h GP_QFORM_COND_MAX
+        = 4; the benchmark's twelve components sit at 1.1 - 2.7), which leaves training some room to move the lengthscale.  The engine checks shapes, types and gradient needs itself."""
+        if not self.whiten:
+            return False
+        found = False
+        for kern, z in zip(list(self.kern_act) + list(self.kern_com), list(self.za) + list(self.zc)):
+            if int(kern.type_code) != _lib.KERN_MERCER_MATERN12SM:
+                continue
+            found = True
+            zz = np.asarray(z.value, dtype=np.float64).reshape(-1)
+            M = zz.shape[0]
+            r = np.abs(zz[:, None] - zz[None, :])
+            mix = sum(float(np.ravel(e.value)[0]) * np.cos(2.0 * np.pi * float(np.ravel(f.value)[0]) * r)
+                      for e, f in zip(kern.energy, kern.frequency))
+            K = float(np.ravel(kern.variance.value)[0]) * np.exp(-r / float(np.ravel(kern.lengthscales.value)[0])) * mix
+            K[np.diag_indices(M)] += jitter
+            try:
+                bound = np.trace(K) * np.trace(np.linalg.inv(K))
+            except np.linalg.LinAlgError:
+                return False
+            if not (bound <= 3.0 * M * M):
+                return False
+        return found
 
     def _host_key(self):
         """what the packed device copy depends on: every Param value (param_version) and the `.fixed` flags"""

@@ -253,6 +253,18 @@ gp_status gp_pdgp_set_overlap(gp_pdgp_plan p, int32_t level);
  * GP_ERR_BAD_ARG ("frames not ascending") and clears it.  Default 0: today's path. */
 gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending);
 
+/* Permission for the Q route, from a caller that knows the plan's MercerMatern12sm kernels are what they are
+ * in the transcription model: a Matern-1/2 envelope whose lengthscale stays near the inducing spacing, so that Kuu + jitter I
+ * is well conditioned.  enable != 0: when ALL MercerMatern12sm latent GPs of a whitened plan have float64 strips, the same M
+ * (a multiple of 64) and partial count, fixed inducing inputs (need_theta, no need_z), sit in one run of the batch, and the
+ * batch is a multiple of 256 frames, gp_pdgp_elbo and its staged forms evaluate them through Q = W^T (Lq Lq^T - I) W: one
+ * dense product G = Q Kuf replaces A = W Kuf, Lq^T A and the Kuf_bar product (5 -> 3 M^2 N products per GP; results agree with
+ * the Cholesky route to ~1e-13 of scale).  Q inverts Kuu explicitly, so every evaluation checks ||L||_F^2 ||W||_F^2
+ * (>= cond_2(Kuu + jitter I)) per GP on the device: above 4 M^2 the handle's status word is raised and the next
+ * gp_check_not_pd / host-scalar call returns GP_ERR_UNSUPPORTED ("qform: ...") and clears it.  Predictions, samples and every
+ * other family keep the Cholesky route.  Default 0: today's path; GPITCH_AMD_SWITCHES=qform=0 overrides an enable. */
+gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable);
+
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the
  * summed KL term (Pdgp.build_prior_kl, pdgp.py:113-131).  When
@@ -724,7 +736,7 @@ gp_status gp_kernfit_eval(gp_handle h, int32_t W, const double* x, const double*
  * HIP-event timing of the dominant kernels on the handle's own stream.  Returns the accumulated time of
  * kernel class `which` since the last reset and the number of launches. */
 enum { GP_TIMER_KUF_BUILD = 0,   /* cov_build_kernel<0,2>: stationary Kuf assembly (HBM-bound)                 */
-       GP_TIMER_COND_A = 1,      /* gemm_f64_kernel<..,1>: A = L^-1 Kuf (tri-aware, M^2 N flops per GP)        */
+       GP_TIMER_COND_A = 1,      /* gemm_f64_kernel<..,1>: A = L^-1 Kuf (tri-aware, M^2 N flops per GP); Q route: G = Q Kuf (2 M^2 N) */
        GP_TIMER_COND_LTA = 2,    /* gemm_f64_kernel<..,2>: Lq^T A column sums (tri-aware, M^2 N)               */
        GP_TIMER_NT_GEMM = 3,     /* gemm_f64_kernel<..,4>: H = A D A^T split-K over frames (M^2 N, symmetric)  */
        GP_TIMER_KUF_BAR = 4,     /* gemm_f64_kernel<..,3>: Kuf_bar = R (A D) (dense, 2 M^2 N)                  */
