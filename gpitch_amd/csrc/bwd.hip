@@ -97,6 +97,12 @@ __global__ void __launch_bounds__(256) batched_sum_kernel(const double* __restri
   if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+gp_status launch_batched_sum(gp_handle h, const double* v, int64_t stride, int n, int rows, double* out) {
+  hipLaunchKernelGGL(batched_sum_kernel, dim3(rows), dim3(256), 0, h->stream, v, stride, n, out);
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
 static int ew_grid(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b > 512 ? 512 : (b < 1 ? 1 : b)); }
 
 gp_status launch_rowdot_batched(gp_handle h, const GemmProblem* d, int batch, int maxM) {
@@ -131,7 +137,6 @@ gp_status launch_matvec_batched(gp_handle h, const GemmProblem* d, int batch, in
 //   Gw[i][j] = (G[i][j] + G[j][i]) / 2                     (Kuu side, symmetric = 1, x2 == x1)
 // layout of the sums: [d_variance, d_lengthscales, d_energy_0.., d_frequency_0..]  (2 + 2m)
 // gz_part[colblock][i] = sum_{j in block} Gw[i][j] * dK[i][j]/dx1_i
-#define HY_THREADS 256
 #define HY_ROWS 32
 // element `idx` of a strip that is float64 or (g32, a float32 plan) float32
 __device__ __forceinline__ double hy_ld(const double* __restrict__ p, int64_t idx, int g32) {
@@ -1292,703 +1297,4 @@ bool hyper_lean_takes(int type, int m, int n1, int n2, int count) {
   int col_seg = 0, nseg = 0;
   hyr_geometry(n1, n2, count, &col_seg, &nseg);
   return col_seg <= HYL_CF_MAX && hy_rows_form((2 * sm_mpad(m) + 15) / 16, true) == 2;
-}
-
-// ---------------------------------------------------------------------------------------------
-// orchestration
-// slots below S_E are batched over all latent GPs, slots from S_E on over the GPs whose kernel gradients are needed.
-// S_QW_* / S_GQ_* / S_WB_*: unwhitened model only (see pdgp_backward).
-enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
-               S_E, S_EH, S_WBAR, S_LU, S_RANK1, S_R, S_ALPHA, S_G, S_T2, S_LBAR, S_P, S_T3, S_S, S_WB_R1, S_WB_L,
-               // Q route, entry i = latent GP q0 + i: E, R, beta and Q = R W of the forward pass (filled whether or
-               // not a gradient is asked), then T = W Qbar, H = T W^T and u = W v of the backward pass
-               S_QE, S_QR, S_QALPHA, S_QQ, S_QT, S_QHH, S_QU,
-               S_COUNT };
-static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
-
-
-// ---- Q route --------------------------------------------------------------------------------------------------------
-// With E = Lq Lq^T - I, Q = W^T E W and beta = W^T q_mu the whitened conditional is
-//   fmean = Kuf^T beta,  fvar = kdiag + colsum(Kuf o G),  G = Q Kuf                      (one dense strip product)
-// and its reverse pass
-//   Kuf_bar = G diag(2 gv) + beta gm^T        (no product: the contraction reads G and scales its columns)
-//   Qbar = Kuf diag(2 gv) Kuf^T, v = Kuf gm   (the split-K product on Kuf);  H = W Qbar W^T, u = W v: the chain's H and u.
-// Which latent GPs take it at n frames (p->q0, p->nq, p->qk0): shapes, types, the gradient needs and gp_pdgp_set_qform alone,
-// never the overlap level.  All MercerMatern12sm GPs of a whitened plan, when they are float64, train their hyper-parameters
-// over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
-// batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
-void pdgp_qform_select(gp_pdgp_plan p, int n) {
-  p->q0 = p->nq = p->qk0 = 0;
-  if (!gp_switches().qform || !p->qform || !p->whiten) return;
-  int first = -1, last = -1, cnt = 0, m = -1;
-  for (int g = 0; g < p->G; g++) {
-    const PdgpGP& q = p->gps[g];
-    if (q.ktype != GP_KERN_MERCER_MATERN12SM) continue;
-    if (q.f32 || !q.need_theta || q.need_z || !p->bw[g].Q || (m >= 0 && q.m != m)) return;
-    m = q.m;
-    if (first < 0) first = g;
-    last = g; cnt++;
-  }
-  if (cnt == 0 || last - first + 1 != cnt) return;
-  struct Key { int type, m, f32; };
-  std::vector<Key> seen;
-  int qk0 = 0;
-  for (int g = 0; g < p->G; g++) {
-    const PdgpGP& q = p->gps[g];
-    if (!(q.need_theta || q.need_z)) continue;
-    if (g < first) qk0++;
-    const Key k{q.ktype, gp_kern_has_partials(q.ktype) ? q.m : 0, q.f32};
-    const bool same = !seen.empty() && seen.back().type == k.type && seen.back().m == k.m && seen.back().f32 == k.f32;
-    if (same) continue;
-    for (const Key& s : seen) if (s.type == k.type && s.m == k.m && s.f32 == k.f32) return;
-    seen.push_back(k);
-  }
-  if (!cond_batch_uniform(p->cb, n) || !gemm_wave_takes(6, p->maxM, n, 1) || !hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, p->maxM, n, cnt)) return;
-  p->q0 = first; p->nq = cnt; p->qk0 = qk0;
-}
-
-// the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
-void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
-  for (int i = 0; i < p->nq; i++) {
-    const int g = p->q0 + i;
-    const PdgpGP& q = p->gps[g];
-    const CondTask& t = p->cb.tasks[g];
-    const BwdBufs& b = p->bw[g];
-    const int M = q.M;
-    auto P = [&](int slot) -> GemmProblem& {
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + i * sizeof(GemmProblem));
-      memset(&r, 0, sizeof(r));
-      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-      return r;
-    };
-    const double* q_sqrt = params + q.off_qsqrt;
-    { GemmProblem& r = P(S_QE); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
-    { GemmProblem& r = P(S_QR); r.A = t.W; r.B = b.E; r.C = b.R; }
-    { GemmProblem& r = P(S_QALPHA); r.A = t.W; r.v0 = params + q.off_qmu; r.o0 = b.alpha; }
-    // (the guard reads L through v0: qform_guard_kernel)
-    { GemmProblem& r = P(S_QQ); r.A = b.R; r.B = t.W; r.C = b.Q; r.v0 = t.L; }
-  }
-}
-
-// Guard of the Q route: Q inverts Kuu + jitter I explicitly, so its error grows with cond_2 of that matrix (not its root), and
-// the lengthscale is trained on the device.  c = ||L||_F^2 ||W||_F^2 = tr(K) tr(K^-1) >= cond_2(K); above GP_QFORM_COND_MAX M^2
-// (switches.h; or not finite) the handle's status word is raised, as the scan's frame check does, and the next host-scalar call fails.
-__global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __restrict__ probs, int g0, double cmax, int32_t* status) {
-  const GemmProblem p = probs[blockIdx.x];
-  const double* L = p.v0;
-  const double* W = p.B;
-  double sl = 0.0, sw = 0.0;
-  for (int idx = threadIdx.x; idx < p.M * p.M; idx += 256)      // (the lower triangles: above them L still holds Kuu)
-    if (idx % p.M <= idx / p.M) { sl = fma(L[idx], L[idx], sl); sw = fma(W[idx], W[idx], sw); }
-  __shared__ double red[2][4];
-  for (int o = 32; o > 0; o >>= 1) { sl += __shfl_down(sl, o, 64); sw += __shfl_down(sw, o, 64); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sl; red[1][threadIdx.x >> 6] = sw; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double c = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
-    if (!(c <= cmax * (double)p.M * (double)p.M)) { status[0] = 4; status[1] = 0; status[2] = g0 + (int)blockIdx.x; }
-  }
-}
-
-// E, R, beta, Q and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
-// (behind the factorisation it has just run, beside the other GPs' strip products), else in line; h->stream waits either way.
-gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n) {
-  gp_handle h = p->h;
-  const int nq = p->nq, maxM = p->maxM;
-  if (nq <= 0) return GP_OK;
-  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
-  bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
-  if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
-  hipStream_t mainq = h->stream;
-  if (aux) h->stream = h->aux_stream;
-  gp_status st = GP_OK;
-  GemmFlags f;
-  f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-  st = launch_gemm_batched(h, D(S_QE), nq, maxM, maxM, f);
-  if (st == GP_OK) st = launch_sub_identity_batched(h, D(S_QE), nq, maxM);
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  if (st == GP_OK) st = launch_gemm_batched(h, D(S_QR), nq, maxM, maxM, f);
-  if (st == GP_OK) st = launch_matvec_batched(h, D(S_QALPHA), nq, maxM, 1);
-  f = GemmFlags(); f.triB = TRI_LOWER;
-  if (st == GP_OK) st = launch_gemm_batched(h, D(S_QQ), nq, maxM, maxM, f);
-  if (st == GP_OK) {
-    hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, D(S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
-    if (hipGetLastError() != hipSuccess) st = gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
-  }
-  hipError_t e = hipSuccess;
-  if (aux) {
-    e = hipEventRecord(h->ev_q, h->aux_stream);
-    h->stream = mainq;
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_q, 0);
-  }
-  GP_CHECK(st);
-  if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
-  return GP_OK;
-}
-
-// f(first slot, count) over the compacted batch without the Q run, whose E, R and beta the forward pass has left
-template <typename F>
-static gp_status pdgp_non_q_slots(gp_pdgp_plan p, F f) {
-  if (p->nq <= 0) return f(0, p->nK);
-  if (p->qk0 > 0) GP_CHECK(f(0, p->qk0));
-  if (p->qk0 + p->nq < p->nK) GP_CHECK(f(p->qk0 + p->nq, p->nK - p->qk0 - p->nq));
-  return GP_OK;
-}
-
-gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
-  (void)x;
-  const int G = p->G;
-  p->h_fin_items.clear();       // the descriptor block is rewritten: force a fresh upload of the finish items
-  const bool white = p->whiten != 0;
-  size_t slab_off = 0;
-  p->kgps.clear();
-  for (int g = 0; g < G; g++)
-    if (p->gps[g].need_theta || p->gps[g].need_z) p->kgps.push_back(g);
-  p->nK = (int)p->kgps.size();
-  int kslot = 0;
-  for (int g = 0; g < G; g++) {
-    const PdgpGP& q = p->gps[g];
-    const CondTask& t = p->cb.tasks[g];
-    const BwdBufs& b = p->bw[g];
-    const int M = q.M;
-    const int64_t ldN = gp_strip_ld(n, q.f32 != 0);     // this GP's strips: float64 or float32 (per-GP precision)
-    // unwhitened model: the chain runs on the equivalent whitened state q' = (W q_mu, W Lq) and its gradient
-    // buffers; pdgp_backward maps the result back (see there)
-    const double* q_mu = white ? params + q.off_qmu : b.qmu_w;
-    const double* q_sqrt = white ? params + q.off_qsqrt : b.Lq_w;
-    double* g_mu = white ? grad + q.off_qmu : b.g_qmu_w;
-    double* g_sqrt = white ? grad + q.off_qsqrt : b.g_Lq_w;
-    const double* gm = p->gFmu + (size_t)g * n;
-    const double* gv = p->gFvar + (size_t)g * n;
-    const bool kneed = (q.need_theta || q.need_z);
-    auto P = [&](int slot) -> GemmProblem& {
-      // the kernel-gradient chain (slots S_R..S_S) is batched over the GPs that need it only
-      const bool kchain = (slot >= S_E);   // E, Wbar, R, alpha, Kuf_bar and the Cholesky-adjoint chain
-      if (kchain && !kneed) { memset(&p->dummy_prob, 0, sizeof(p->dummy_prob)); return p->dummy_prob; }
-      const int idx = kchain ? kslot : g;
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + idx * sizeof(GemmProblem));
-      memset(&r, 0, sizeof(r));
-      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-      return r;
-    };
-    { GemmProblem& r = P(S_H); r.A = t.A; r.lda = ldN; r.B = t.A; r.ldb = ldN; r.K = n; r.v1 = gv; r.C = b.H;
-      r.o2 = p->slabs + slab_off; slab_off += gp_align_up((size_t)p->nsplit * M * M * sizeof(double), 256) / sizeof(double);
-      // fused u = A gm: partials per K-slice in o1, result in o0 and accumulated into grad q_mu (xa)
-      r.v2 = gm; r.o1 = b.upart; r.o0 = b.u; r.xa = g_mu;
-      // Q route: the same product on Kuf gives Qbar (into T2) and v = Kuf gm (into Lu); H and u follow from S_QT / S_QHH / S_QU
-      if (g >= p->q0 && g < p->q0 + p->nq) { r.A = t.Kuf; r.B = t.Kuf; r.C = b.T2; r.o0 = b.Lu; r.xa = nullptr; } }
-    if (g >= p->q0 && g < p->q0 + p->nq) {
-      auto PQ = [&](int slot) -> GemmProblem& {
-        GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + (g - p->q0) * sizeof(GemmProblem));
-        memset(&r, 0, sizeof(r));
-        r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-        return r;
-      };
-      { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
-      { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
-      { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
-    }
-    { GemmProblem& r = P(S_U); r.A = t.A; r.lda = ldN; r.N = n; r.v0 = gm; r.o0 = b.u; r.o1 = g_mu; r.a_f32 = q.f32; }
-    { GemmProblem& r = P(S_HLQ); r.A = b.H; r.B = q_sqrt; r.C = g_sqrt; }
-    if (!white) {
-      const double* qm = params + q.off_qmu;
-      const double* qs = params + q.off_qsqrt;
-      { GemmProblem& r = P(S_QW_MU); r.A = t.W; r.v0 = qm; r.o0 = b.qmu_w; }
-      { GemmProblem& r = P(S_QW_L); r.A = t.W; r.B = qs; r.C = b.Lq_w; }
-      { GemmProblem& r = P(S_GQ_MU); r.A = t.W; r.v0 = b.g_qmu_w; r.o0 = grad + q.off_qmu; }
-      { GemmProblem& r = P(S_GQ_L); r.A = t.W; r.B = b.g_Lq_w; r.C = grad + q.off_qsqrt; }
-      { GemmProblem& r = P(S_WB_R1); r.C = b.Wbar; r.v0 = b.g_qmu_w; r.v1 = qm; }
-      { GemmProblem& r = P(S_WB_L); r.A = b.g_Lq_w; r.B = qs; r.C = b.Wbar; }
-      kl_item_fill(p->h_misc.data() + p->off.kl2 + g * kl_item_bytes(), b.qmu_w, b.Lq_w, M, p->kl_dummy + (size_t)g * GP_KL_BLOCKS, b.g_qmu_w,
-                   b.g_Lq_w);
-    }
-    { GemmProblem& r = P(S_E); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
-    { GemmProblem& r = P(S_EH); r.A = b.E; r.B = b.H; r.C = b.T1; }
-    { GemmProblem& r = P(S_WBAR); r.A = b.T1; r.B = t.L; r.C = b.Wbar; }
-    { GemmProblem& r = P(S_LU); r.A = t.L; r.v0 = b.u; r.o0 = b.Lu; }
-    { GemmProblem& r = P(S_RANK1); r.C = b.Wbar; r.v0 = q_mu; r.v1 = b.Lu; }
-    { GemmProblem& r = P(S_R); r.A = t.W; r.B = b.E; r.C = b.R; }
-    { GemmProblem& r = P(S_ALPHA); r.A = t.W; r.v0 = q_mu; r.o0 = b.alpha; }
-    { GemmProblem& r = P(S_G); r.A = b.R; r.B = t.A; r.ldb = ldN; r.N = n; r.v1 = gv; r.C = b.G; r.ldc = ldN; r.xb = b.R32;
-      // (read only by the form that contracts Kuf_bar with dK/dtheta in its epilogue — gemm_strip.hip role 5)
-      r.kern = t.kern; r.xa = params + q.off_z; r.v0 = b.alpha; r.v2 = gm; r.o0 = b.hyp_part; }
-    { GemmProblem& r = P(S_T2); r.A = t.W; r.B = b.Wbar; r.C = b.T2; }
-    { GemmProblem& r = P(S_LBAR); r.A = b.T2; r.B = t.W; r.C = b.T1; }
-    { GemmProblem& r = P(S_P); r.A = t.L; r.B = b.T1; r.C = b.T2; }
-    { GemmProblem& r = P(S_T3); r.A = t.W; r.B = b.T2; r.C = b.H; }
-    { GemmProblem& r = P(S_S); r.A = b.H; r.B = t.W; r.C = b.E; }
-    if (kneed) kslot++;
-  }
-  // Kuf-side contractions, one launch per kernel family (same type and partial count): item array in kgps order inside
-  // each family.  x2 stays null in the items: the frames of the batch come with the launch (their pointer may change
-  // from step to step without a descriptor upload).
-  p->hy_fams.clear();
-  for (size_t s = 0; s < p->kgps.size(); s++) {
-    const int g = p->kgps[s];
-    const PdgpGP& q = p->gps[g];
-    const int key_m = gp_kern_has_partials(q.ktype) ? q.m : 0;
-    int fi = -1;
-    for (size_t f = 0; f < p->hy_fams.size(); f++)
-      if (p->hy_fams[f].type == q.ktype && p->hy_fams[f].m == key_m && p->hy_fams[f].f32 == q.f32) fi = (int)f;
-    if (fi < 0) { gp_pdgp_plan_s::HyFamily nf; nf.type = q.ktype; nf.m = key_m; nf.M = q.M; nf.f32 = q.f32; nf.batched = true; p->hy_fams.push_back(nf); fi = (int)p->hy_fams.size() - 1; }
-    gp_pdgp_plan_s::HyFamily& fam = p->hy_fams[fi];
-    fam.gps.push_back(g);
-    if (q.M != fam.M || q.need_z || !q.need_theta) fam.batched = false;   // the per-GP path handles those
-  }
-  {
-    HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
-    KufScanItem* sitems = (KufScanItem*)(p->h_misc.data() + p->off.ks_items);
-    int pos = 0;
-    for (auto& fam : p->hy_fams) {
-      fam.first = pos; fam.count = (int)fam.gps.size();
-      fam.mfma = (gp_kern_is_mercer(fam.type) && fam.batched) ? 1 : 0;
-      fam.scan_ws = true;
-      for (int g : fam.gps) {
-        const PdgpGP& q = p->gps[g];
-        const CondTask& t = p->cb.tasks[g];
-        const BwdBufs& bb = p->bw[g];
-        {    // the same GP's record for the scan form (kuf_scan.hip), used only when pdgp_backward picks that form
-          KufScanItem& si = sitems[pos];
-          memset(&si, 0, sizeof(si));
-          si.A = t.A; si.lda = gp_strip_ld(n, q.f32 != 0); si.gv = p->gFvar + (size_t)g * n; si.gm = p->gFmu + (size_t)g * n;
-          si.R = bb.R; si.alpha = bb.alpha; si.z = params + q.off_z; si.theta = t.kern.theta;
-          si.mom = bb.ks_mom; si.near = bb.ks_near; si.partials = bb.hyp_part; si.M = q.M;
-          if (!bb.ks_mom || !bb.ks_near) fam.scan_ws = false;
-        }
-        HyperItem& it = items[pos++];
-        memset(&it, 0, sizeof(it));
-        const int64_t ldN = gp_strip_ld(n, q.f32 != 0);
-        it.k = t.kern; it.x1 = params + q.off_z; it.n1 = q.M; it.x2 = nullptr; it.n2 = n; it.G = bb.G; it.ldg = ldN;
-        it.alpha = bb.alpha; it.gm = p->gFmu + (size_t)g * n; it.symmetric = 0; it.partials = bb.hyp_part; it.gz = nullptr;
-        it.kvals = t.Kuf; it.ldk = ldN; it.g32 = q.f32;
-        if (g >= p->q0 && g < p->q0 + p->nq) { it.G = t.A; it.gscale = p->gFvar + (size_t)g * n; }     // Q route: G = Q Kuf, in A's strip
-        if (gp_kern_is_mercer(q.ktype) && t.feat) {
-          it.f1 = t.feat;
-          it.f2 = t.feat + gp_align_up((size_t)2 * sm_mpad(q.m) * q.M, 32);
-        }
-        // its Kuu-side twin (contraction of Kuu_bar = E with dK(z, z)): G entries further on
-        HyperItem& iu = items[G + pos - 1];
-        memset(&iu, 0, sizeof(iu));
-        iu.k = t.kern; iu.x1 = params + q.off_z; iu.n1 = q.M; iu.x2 = iu.x1; iu.n2 = q.M; iu.G = bb.E; iu.ldg = q.M;
-        iu.symmetric = 1; iu.partials = bb.hyp_part_uu;
-        if (gp_kern_is_mercer(q.ktype) && t.feat) { iu.f1 = t.feat; iu.f2 = t.feat; }
-      }
-    }
-  }
-  return GP_OK;
-}
-
-// R = W^T (Lq Lq^T - I) and alpha = W^T q_mu depend on the parameters and on W only: when the helper stream exists they
-// are enqueued on it during the FORWARD pass, right behind the Kuu factorisation it has just run (no wait on the main
-// stream, which is busy with the forward GEMM strips), and the backward pass finds them ready.
-// The whitened KL terms (parameters only) ride along: on the main stream they were one of five tiny kernels between
-// the last forward strip product and the first backward one, with the device idle around them.
-gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
-  gp_handle h = p->h;
-  p->era_ready = false;
-  if (kl_done) *kl_done = false;
-  if (!(p->whiten && p->nK > 0 && n >= 4096 && p->overlap >= 2 && h->aux_stream && !h->aux_active)) return GP_OK;
-  if (!h->ev_era && hipEventCreateWithFlags(&h->ev_era, hipEventDisableTiming) != hipSuccess) { h->ev_era = nullptr; return GP_OK; }
-  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
-  const int maxM = p->maxM;
-  hipStream_t mainq = h->stream;
-  h->stream = h->aux_stream;
-  gp_status st = GP_OK;
-  st = pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
-    GemmFlags f;
-    f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-    GP_CHECK(launch_gemm_batched(h, D(S_E) + s0, cnt, maxM, maxM, f));
-    GP_CHECK(launch_sub_identity_batched(h, D(S_E) + s0, cnt, maxM));
-    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-    GP_CHECK(launch_gemm_batched(h, D(S_R) + s0, cnt, maxM, maxM, f));
-    return launch_matvec_batched(h, D(S_ALPHA) + s0, cnt, maxM, 1);
-  });
-  if (st == GP_OK && kl_done) {
-    st = launch_kl_white(h, p->d_misc + p->off.kl_items, p->G);
-    *kl_done = (st == GP_OK);
-  }
-  hipError_t e = hipEventRecord(h->ev_era, h->aux_stream);
-  h->stream = mainq;
-  GP_CHECK(st);
-  if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "hipEventRecord on the helper stream failed");
-  p->era_ready = true;
-  return GP_OK;
-}
-
-gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
-  gp_handle h = p->h;
-  const int G = p->G, maxM = p->maxM;
-  const int n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
-  auto D = [&](int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); };
-  GemmFlags f;
-  const bool white = p->whiten != 0;
-  if (!white) {
-    // conditional(whiten=False) + gauss_kl(q_mu, q_sqrt, K) (pdgp.py:123-129, 147-155) is the whitened model at
-    //   q_mu' = W q_mu,  Lq' = W Lq      (W = chol(Kuu + jitter I)^-1),
-    // so the whitened chain below runs on (q_mu', Lq') with gradient buffers (g', G'), and afterwards
-    //   grad q_mu = W^T g',  grad q_sqrt = tril(W^T G'),  Wbar += tril(g' q_mu^T + G' Lq^T).
-    GP_HIP_CHECK(h, hipMemsetAsync(p->qw_block, 0, p->qw_doubles * sizeof(double), h->stream));
-    GP_CHECK(launch_matvec_batched(h, D(S_QW_MU), G, maxM, 0));
-    f = GemmFlags(); f.triA = TRI_LOWER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D(S_QW_L), G, maxM, maxM, f));
-    GP_CHECK(launch_kl_white(h, p->d_misc + p->off.kl2, G));   // accumulates -dKL/dq' into (g', G')
-  }
-  const int nK = p->nK;   // latent GPs whose kernel hyper-parameters / inducing inputs are trainable
-  // sum_n gv  (kdiag term)
-  // sum_n gv and the ELBO's final reduction (pdgp.hip: pdgp_finish) are wanted only when the step ends: they go to the end
-  // of the helper stream's chain when there is one, and run here otherwise
-  bool sums_done = false;
-  auto late_sums = [&]() -> gp_status {
-    if (sums_done) return GP_OK;
-    sums_done = true;
-    hipLaunchKernelGGL(batched_sum_kernel, dim3(G), dim3(256), 0, h->stream, p->gFvar, (int64_t)n, n, p->bw[0].gvsum);
-    GP_HIP_CHECK(h, hipGetLastError());
-    if (p->fin.pending) {
-      p->fin.pending = false;
-      GP_CHECK(launch_elbo_finish(h, p->fin.lik_partials, p->fin.nb, p->fin.kl, p->fin.nkl, p->fin.elbo, p->fin.g_noise));
-    }
-    return GP_OK;
-  };
-  // Everything that hangs off H = A diag(2 gv) A^T — grad q_sqrt, Wbar, the whole Kuu side — is independent of the
-  // Kuf_bar product, which needs only R = W^T (Lq Lq^T - I) and alpha = W^T q_mu.  With early_fork the H chain
-  // (the split-K product included) goes to the helper stream and the main stream starts Kuf_bar right away.
-  const bool early_fork = white && nK > 0 && n >= 4096 && p->overlap >= 2;
-  if (!early_fork) GP_CHECK(late_sums());
-  auto h_chain_head = [&]() -> gp_status {
-    GemmFlags f;
-    // H = A diag(2 gv) A^T  (symmetric, split-K over the frames); u = A gm and grad q_mu += u are fused into it
-    {
-      int uni = ((n & 3) == 0) ? 1 : 0;
-      for (int g = 0; g < G; g++) if (p->gps[g].M != maxM) uni = 0;
-      if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, D(S_H), n64, maxM, n, p->nsplit, 1, 1, 2.0, uni));
-      if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, D(S_H) + n64, G - n64, maxM, n, p->nsplit, 1, 1, 2.0, uni));
-    }
-    if (p->nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
-      f = GemmFlags(); f.triA = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_QT), p->nq, maxM, maxM, f));
-      f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, D(S_QHH), p->nq, maxM, maxM, f));
-      GP_CHECK(launch_matvec_batched(h, D(S_QU), p->nq, maxM, 0));
-    }
-    // grad q_sqrt += tril(H Lq)
-    f = GemmFlags(); f.triB = TRI_LOWER; f.triC = TRI_LOWER; f.beta = 1.0;
-    GP_CHECK(launch_gemm_batched(h, D(S_HLQ), G, maxM, maxM, f));
-    return GP_OK;
-  };
-  auto wbar_chain = [&]() -> gp_status {
-    GemmFlags f;
-    // T1 = E H
-    f = GemmFlags();
-    GP_CHECK(launch_gemm_batched(h, D(S_EH), nK, maxM, maxM, f));
-    // Wbar = tril(T1 L^T) + tril(mu (L u)^T)
-    f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D(S_WBAR), nK, maxM, maxM, f));
-    GP_CHECK(launch_matvec_batched(h, D(S_LU), nK, maxM, 0));
-    GP_CHECK(launch_rank1_tril_batched(h, D(S_RANK1), nK, maxM));
-    if (!white) {
-      GP_CHECK(launch_rank1_tril_batched(h, D(S_WB_R1), nK, maxM));
-      f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.beta = 1.0;
-      GP_CHECK(launch_gemm_batched(h, D(S_WB_L), nK, maxM, maxM, f));
-    }
-    return GP_OK;
-  };
-  if (!early_fork) GP_CHECK(h_chain_head());
-  if (nK > 0) {
-    const bool pre = p->era_ready;   // E, R, alpha were computed on the helper stream during the forward pass
-    p->era_ready = false;
-    if (pre) {
-      GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));
-    } else {
-      // E = Lq Lq^T - I
-      GP_CHECK(pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
-        GemmFlags f;
-        f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-        GP_CHECK(launch_gemm_batched(h, D(S_E) + s0, cnt, maxM, maxM, f));
-        return launch_sub_identity_batched(h, D(S_E) + s0, cnt, maxM);
-      }));
-    }
-    if (!early_fork) GP_CHECK(wbar_chain());
-    if (!pre) {
-      // R = W^T E ; alpha = W^T mu
-      GP_CHECK(pdgp_non_q_slots(p, [&](int s0, int cnt) -> gp_status {
-        GemmFlags f;
-        f.transA = 1; f.triA = TRI_UPPER;
-        GP_CHECK(launch_gemm_batched(h, D(S_R) + s0, cnt, maxM, maxM, f));
-        return launch_matvec_batched(h, D(S_ALPHA) + s0, cnt, maxM, 1);
-      }));
-    }
-    // From here two independent chains remain: the Kuf side (the big Kuf_bar product and its contraction with
-    // dK/dtheta over all frames) and the Kuu side (the Cholesky adjoint, six M x M products, and its contraction
-    // over M x M).  The Kuu side is ~1.4 ms of small launches: it runs on the helper stream underneath Kuf_bar.
-    auto fam_slot0 = [&](const gp_pdgp_plan_s::HyFamily& fam) -> int {    // first slot in the compacted batch, -1 if scattered
-      int s0 = -1;
-      for (size_t s = 0; s < p->kgps.size(); s++) if (p->kgps[s] == fam.gps[0]) s0 = (int)s;
-      for (size_t i = 0; i < fam.gps.size(); i++)
-        if (s0 < 0 || s0 + (int)i >= (int)p->kgps.size() || p->kgps[s0 + i] != fam.gps[i]) return -1;
-      return s0;
-    };
-    // Which families contract Kuf_bar by the scan (kuf_scan.hip: no product at all): Matern-3/2 / Matern-5/2 over frames the
-    // caller promised ascending.  Any M, any n; fam.batched already says one M and hyper-parameter gradients only.  Matern-1/2
-    // (kink at 0) and RBF (not semiseparable) have no such form.  Like the fused form below the choice depends on shapes,
-    // types and that promise alone — never on the overlap level — and needs every family in one contiguous run of the batch.
-    const int nfam = (int)p->hy_fams.size();
-    std::vector<int> fslot(nfam, -1), ffuse(nfam, 0), fscan(nfam, 0), fq(nfam, 0);     // fq: the Q route's family (pdgp_qform_select)
-    bool contiguous = (white && nfam > 0), any_scan = false;
-    for (int fi = 0; fi < nfam; fi++) {
-      fslot[fi] = fam_slot0(p->hy_fams[fi]); if (fslot[fi] < 0) contiguous = false;
-      fq[fi] = (p->nq > 0 && p->hy_fams[fi].gps[0] == p->q0) ? 1 : 0;
-    }
-    for (int fi = 0; fi < nfam && contiguous; fi++) {
-      const auto& fam = p->hy_fams[fi];
-      fscan[fi] = (gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
-                   kuf_scan_nq(fam.type) > 0 && fam.M <= 1024) ? 1 : 0;
-      any_scan |= (fscan[fi] != 0);
-    }
-    // Schedule with a scan family (switches.h scan_side; the same launches either way, so the same bits): the scan's three
-    // launches go to the side stream, beside the other families' Kuf_bar product, instead of ahead of it on the main stream
-    // (measurements: DESIGN.md 3.02).  The side stream serves ONE fork per backward pass — gp_side_begin refuses until
-    // gp_side_join — so only the first scan family gets it; a further scan family, or one that follows the spectral-mixture
-    // contraction onto the side stream (kufbar_split 1), stays on the main stream, and so do the contractions that would
-    // otherwise have gone to the side stream after it.
-    const bool scan_side = any_scan && gp_switches().scan_side != 0 && (n >= 4096) && p->overlap >= 2;
-    const bool forked = (n >= 4096) && p->overlap >= 1 && gp_aux_fork(h);
-    gp_status st = GP_OK;
-    std::vector<int> np_uu(p->G, 0);
-    auto kuu_side = [&]() -> gp_status {
-      GemmFlags f;
-      // Lbar = -tril(W^T Wbar W^T); P = Phi(L^T Lbar); S = W^T P W
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_T2), nK, maxM, maxM, f));
-      f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
-      GP_CHECK(launch_gemm_batched(h, D(S_LBAR), nK, maxM, maxM, f));
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_P), nK, maxM, maxM, f));
-      GP_CHECK(launch_phi_batched(h, D(S_P), nK, maxM));
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_T3), nK, maxM, maxM, f));
-      f = GemmFlags(); f.triB = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_S), nK, maxM, maxM, f));
-      // contraction of Kuu_bar with dK(z, z)/d(theta, z), partial sums only: one launch per kernel family (24 launches of
-      // a few workgroups each otherwise: 2.6 ms at the end of the helper stream's chain), per GP where a family is mixed
-      for (const auto& fam : p->hy_fams) {
-        if (!fam.batched) continue;
-        int np = 0;
-        GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + p->G + fam.first,
-                                             fam.count, fam.M, fam.M, 0, &np));
-        for (int g : fam.gps) np_uu[g] = np;
-      }
-      for (int g : p->kgps) {
-        bool in_batch = false;
-        for (const auto& fam : p->hy_fams) if (fam.batched) for (int gg : fam.gps) if (gg == g) in_batch = true;
-        if (in_batch) continue;
-        const PdgpGP& q = p->gps[g];
-        const CondTask& t = p->cb.tasks[g];
-        const BwdBufs& bb = p->bw[g];
-        const double* z = params + q.off_z;
-        const int cb_uf = (n + HY_THREADS - 1) / HY_THREADS;
-        double* gz_uu = q.need_z ? bb.gz_part + (size_t)cb_uf * q.M : nullptr;
-        GP_CHECK(launch_hyper_contract(h, t.kern, z, q.M, z, q.M, bb.E, q.M, nullptr, nullptr, 1, t.feat, bb.hyp_part_uu,
-                                       &np_uu[g], gz_uu));
-      }
-      return GP_OK;
-    };
-    if (!forked) GP_CHECK(late_sums());
-    if (forked) {            // helper stream: [the late sums and the H chain when forked early,] Kuu side
-      if (early_fork) { st = h_chain_head(); if (st == GP_OK) st = wbar_chain(); }
-      if (st == GP_OK) st = kuu_side();
-      if (st == GP_OK) st = late_sums();      // (at the END of the chain: ahead of the split-K product they delayed it)
-      gp_status s2 = gp_aux_end(h);
-      if (st == GP_OK) st = s2;
-      GP_CHECK(st);
-    }
-    // Kuf_bar (dense part) = R (A diag(2 gv)), and its contraction with dK/dtheta over all frames.
-    // The contractions are one launch per kernel family (item arrays built at bind time).  With exactly two families —
-    // the transcription model: stationary activations, spectral-mixture components — whose GPs sit in contiguous runs
-    // of the compacted batch, the product is issued family by family, the spectral-mixture family first: its contraction
-    // (the long one: 40 % of it matrix-core work) then runs on the side stream UNDERNEATH the second family's product
-    // instead of after it, and only the stationary family's short, HBM-bound contraction is left behind the product.
-    std::vector<int> np_uf(p->G, 0);
-    int kuf_uniform = ((n & 1) == 0) ? 1 : 0;        // every GP of the compacted batch M = maxM (R, A, G: arena buffers, even ld)
-    for (int g : p->kgps) if (p->gps[g].M != maxM) kuf_uniform = 0;
-    // (slots of the compacted batch keep the GPs' order: its float64 GPs come first, k64 of them)
-    int k64 = 0;
-    for (int g : p->kgps) if (!p->gps[g].f32) k64++;
-    auto kuf_bar = [&](int slot0, int count, int fused_ktype = -1, int fused_f32 = 0) -> gp_status {
-      GemmFlags f;
-      f.big_tiles = 1; f.scale_mode = 1; f.alpha = 2.0; f.timer = GP_TIMER_KUF_BAR; f.role = 3;
-      f.uniform_aligned = kuf_uniform;
-      f.a32_ok = 1;          // (float32 GPs: b.R32 is in every problem's xb)
-      if (fused_ktype >= 0) {      // the family's Kuf-side contraction as the product's epilogue, nothing stored (one precision per family)
-        f.role = 5; f.epilogue = 0; f.aux_x = x; f.aux_ktype = fused_ktype;
-        if (fused_f32) return launch_gemm_f32_role(h, D(S_G) + slot0, count, maxM, n, f);
-        return launch_gemm_batched(h, D(S_G) + slot0, count, maxM, n, f);
-      }
-      const int c64 = (slot0 < k64) ? ((slot0 + count <= k64) ? count : k64 - slot0) : 0;
-      if (c64 > 0) GP_CHECK(launch_gemm_batched(h, D(S_G) + slot0, c64, maxM, n, f));
-      if (c64 < count) GP_CHECK(launch_gemm_f32_role(h, D(S_G) + slot0 + c64, count - c64, maxM, n, f));
-      return GP_OK;
-    };
-    auto kuf_contract = [&](int g) -> gp_status {      // one GP (inducing-input gradients, mixed sizes)
-      const PdgpGP& q = p->gps[g];
-      const CondTask& t = p->cb.tasks[g];
-      const BwdBufs& bb = p->bw[g];
-      const double* z = params + q.off_z;
-      const double* gm = p->gFmu + (size_t)g * n;
-      double* gz_uf = q.need_z ? bb.gz_part : nullptr;
-      const int64_t ldN = gp_strip_ld(n, q.f32 != 0);
-      return launch_hyper_contract(h, t.kern, z, q.M, x, n, bb.G, ldN, bb.alpha, gm, 0, t.feat, bb.hyp_part, &np_uf[g], gz_uf,
-                                   t.Kuf, ldN, q.f32);
-    };
-    auto contract_family = [&](const gp_pdgp_plan_s::HyFamily& fam) -> gp_status {
-#ifdef GP_EXP_SKIP_STAT
-      if (!fam.mfma) return GP_OK;     // timing experiment only (wrong gradients): the stationary family's contraction left out
-#endif
-      if (!fam.batched) { for (int g : fam.gps) GP_CHECK(kuf_contract(g)); return GP_OK; }
-      int np = 0;
-      GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + fam.first,
-                                           fam.count, fam.M, n, 0, &np, fam.mfma, x, fam.f32, 1,
-                                           (p->nq > 0 && fam.gps[0] == p->q0) ? 1 : 0));
-      for (int g : fam.gps) np_uf[g] = np;
-      return GP_OK;
-    };
-    // A stationary family with fixed inducing inputs wants Kuf_bar for two sums per GP only: they come out of the product's
-    // epilogue (gemm_strip.hip role 5; float64 strips, whole 128-tiles) and neither the strip nor the separate contraction
-    // exists.  The choice depends on shapes and kernel types alone — never on the overlap level, whose settings must give
-    // bit-identical results — and needs every family in one contiguous run of the compacted batch.
-    for (int fi = 0; fi < nfam && contiguous; fi++) {
-      const auto& fam = p->hy_fams[fi];
-      bool ok = kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM && !fscan[fi] && !fq[fi] &&
-                (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type));
-      for (int g : fam.gps) if (p->gps[g].need_z || !p->gps[g].need_theta) ok = false;
-      ffuse[fi] = ok ? 1 : 0;
-    }
-    auto fdone = [&](int fi) { return ffuse[fi] || fscan[fi]; };   // the family's Kuf-side partial sums come with kuf_bar_family
-    auto kuf_bar_family = [&](int fi) -> gp_status {          // one family's product (contiguous slots), fused form if chosen
-      const auto& fam = p->hy_fams[fi];
-      if (fq[fi]) return GP_OK;      // Q route: Kuf_bar = G diag(2 gv) + beta gm^T needs no product (contract_family scales G's columns)
-      if (fscan[fi]) {
-        const bool side = scan_side && gp_side_begin(h);
-        gp_status st2 = launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, x, n);
-        if (side) { gp_status s3 = gp_side_end(h); if (st2 == GP_OK) st2 = s3; }
-        GP_CHECK(st2);
-        for (int g : fam.gps) np_uf[g] = kuf_scan_records(fam.M);
-        return GP_OK;
-      }
-      if (!ffuse[fi]) return kuf_bar(fslot[fi], fam.count);
-      GP_CHECK(kuf_bar(fslot[fi], fam.count, fam.type, fam.f32));
-      for (int g : fam.gps) np_uf[g] = fam.f32 ? (gemm_wave_f32_takes(5, maxM, n, kuf_uniform) ? (maxM / 64) * (n / 64) : (maxM / 128) * (n / 128))
-                                                : gemm_fused_contraction_records(maxM, n, fam.type);
-      return GP_OK;
-    };
-    bool any_fused = false;
-    for (int fi = 0; fi < nfam; fi++) any_fused |= (fdone(fi) != 0 || fq[fi] != 0);
-    int sm_fam = -1, other_fam = -1, sm_slot = -1, other_slot = -1;
-    // (switches.h; -1 = by precision: with float32 strips the spectral-mixture family goes first — its vector-ALU contraction then runs
-    // beside the other family's float32 matrix product, which leaves the vector ALU free; the float64 MFMA holds it, so there the
-    // stationary family goes first.  cfg3 3.90 -> 3.80 ms, headline 19.47 / 19.56 the other way round)
-    int split_mode = gp_switches().kufbar_split;
-    if (split_mode < 0) {
-      split_mode = 2;
-      for (const auto& fam : p->hy_fams) if (fam.mfma && fam.f32) split_mode = 1;
-    }
-    if (split_mode >= 1 && p->hy_fams.size() == 2 && forked && p->overlap >= 2) {
-      for (int fi = 0; fi < 2; fi++) {
-        if (p->hy_fams[fi].mfma) sm_fam = fi; else other_fam = fi;
-      }
-      if (sm_fam >= 0 && other_fam >= 0) { sm_slot = fam_slot0(p->hy_fams[sm_fam]); other_slot = fam_slot0(p->hy_fams[other_fam]); }
-    }
-    if (sm_slot >= 0 && other_slot >= 0 && split_mode == 2) {
-      // the stationary family first: its contraction (an HBM read, next to no arithmetic) goes underneath the
-      // spectral-mixture family's product, and the long contraction has the device to itself afterwards
-      const auto& fs = p->hy_fams[sm_fam];
-      const auto& fo = p->hy_fams[other_fam];
-      if (fdone(other_fam)) {
-        GP_CHECK(kuf_bar_family(other_fam));
-        GP_CHECK(kuf_bar_family(sm_fam));
-      } else {
-        GP_CHECK(kuf_bar(other_slot, fo.count));
-        const bool side = gp_side_begin(h);
-        if (side) {
-          gp_status st2 = contract_family(fo);
-          gp_status s3 = gp_side_end(h);
-          GP_CHECK(st2); GP_CHECK(s3);
-        }
-        GP_CHECK(kuf_bar_family(sm_fam));
-        if (!side) GP_CHECK(contract_family(fo));
-      }
-      GP_CHECK(contract_family(fs));
-    } else if (sm_slot >= 0 && other_slot >= 0) {
-      const auto& fs = p->hy_fams[sm_fam];
-      const auto& fo = p->hy_fams[other_fam];
-      GP_CHECK(kuf_bar_family(sm_fam));
-      const bool side = gp_side_begin(h);              // the side stream picks up once that product is through
-      if (side) {
-        gp_status st2 = contract_family(fs);
-        gp_status s3 = gp_side_end(h);
-        GP_CHECK(st2); GP_CHECK(s3);
-      }
-      GP_CHECK(kuf_bar_family(other_fam));
-      if (!side) GP_CHECK(contract_family(fs));
-      if (!fdone(other_fam)) GP_CHECK(contract_family(fo));
-    } else {
-      if (any_fused) { for (int fi = 0; fi < nfam; fi++) GP_CHECK(kuf_bar_family(fi)); }
-      else GP_CHECK(kuf_bar(0, nK));
-      if (!forked) {
-        if (early_fork) { GP_CHECK(h_chain_head()); GP_CHECK(wbar_chain()); }   // (no helper stream to be had)
-        GP_CHECK(kuu_side());
-      }
-      // the families' contractions side by side: the matrix-core ones on this stream, the others (short, HBM-bound) on
-      // the side stream
-      const bool side = (p->hy_fams.size() > 1) && forked && p->overlap >= 2 && gp_side_begin(h);
-      if (side) {
-        gp_status st2 = GP_OK;
-        for (int fi = 0; fi < nfam; fi++) if (!p->hy_fams[fi].mfma && !fdone(fi) && st2 == GP_OK) st2 = contract_family(p->hy_fams[fi]);
-        gp_status s3 = gp_side_end(h);
-        GP_CHECK(st2); GP_CHECK(s3);
-      }
-      for (int fi = 0; fi < nfam; fi++) if ((!side || p->hy_fams[fi].mfma) && !fdone(fi)) GP_CHECK(contract_family(p->hy_fams[fi]));
-    }
-    if (!white) {
-      GP_CHECK(launch_matvec_batched(h, D(S_GQ_MU), G, maxM, 1));
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
-      GP_CHECK(launch_gemm_batched(h, D(S_GQ_L), G, maxM, maxM, f));
-    }
-    GP_CHECK(gp_side_join(h));
-    GP_CHECK(gp_aux_join(h));
-    // all partial sums (Kuf side, Kuu side) are in: ONE finish launch adds them into the gradient vector (48 tiny
-    // launches at the end of every step otherwise).  The item array is re-uploaded only when it changes.
-    {
-      std::vector<HyperFinishItem> items;
-      int maxblocks = 0;
-      for (int g : p->kgps) {
-        const PdgpGP& q = p->gps[g];
-        const CondTask& t = p->cb.tasks[g];
-        const BwdBufs& bb = p->bw[g];
-        const int cb_uf = (n + HY_THREADS - 1) / HY_THREADS, cb_uu = (q.M + HY_THREADS - 1) / HY_THREADS;
-        HyperFinishItem it;
-        memset(&it, 0, sizeof(it));
-        it.k = t.kern; it.p_uf = bb.hyp_part; it.np_uf = np_uf[g]; it.p_uu = bb.hyp_part_uu; it.np_uu = np_uu[g];
-        it.gv_sum = bb.gvsum; it.g_theta = grad + q.off_theta; it.n1 = q.M;
-        if (q.need_z) {
-          it.gz_uf = bb.gz_part; it.cb_uf = cb_uf; it.gz_uu = bb.gz_part + (size_t)cb_uf * q.M; it.cb_uu = cb_uu;
-          it.g_z = grad + q.off_z;
-        }
-        const int blocks = 2 + 2 * t.kern.m + (q.need_z ? (q.M + 255) / 256 : 0);
-        if (blocks > maxblocks) maxblocks = blocks;
-        items.push_back(it);
-      }
-      const size_t bytes = items.size() * sizeof(HyperFinishItem);
-      char* d_items = p->d_misc + p->off.fin_items;
-      if (p->h_fin_items.size() != bytes || memcmp(p->h_fin_items.data(), items.data(), bytes) != 0) {
-        p->h_fin_items.assign((const char*)items.data(), (const char*)items.data() + bytes);
-        GP_HIP_CHECK(h, hipMemcpyAsync(d_items, p->h_fin_items.data(), bytes, hipMemcpyHostToDevice, h->stream));
-      }
-      GP_CHECK(launch_hyper_finish_items(h, (const HyperFinishItem*)d_items, (int)items.size(), maxblocks));
-    }
-  } else if (!white) {
-    GP_CHECK(launch_matvec_batched(h, D(S_GQ_MU), G, maxM, 1));
-    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D(S_GQ_L), G, maxM, maxM, f));
-  }
-  return GP_OK;
 }

@@ -889,7 +889,7 @@ gp_status check_not_pd(gp_handle h) {
       GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
       return GP_ERR_BAD_ARG;
     }
-    if (st[0] == 4) {                       // bwd.hip: the Q route's guard on ||L||_F^2 ||W||_F^2 >= cond_2(Kuu + jitter I)
+    if (st[0] == 4) {                       // pdgp_bwd.hip: the Q route's guard on ||L||_F^2 ||W||_F^2 >= cond_2(Kuu + jitter I)
       snprintf(buf, sizeof(buf), "qform: Kuu of latent GP %d is too ill-conditioned for the Q route (tr(K) tr(K^-1) > GP_QFORM_COND_MAX M^2); gp_pdgp_set_qform(plan, 0) or GPITCH_AMD_SWITCHES=qform=0 selects the Cholesky route", st[2]);
       h->last_error = buf;
       GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));

@@ -140,6 +140,27 @@ gp_status gp_aux_join(gp_handle h);
 bool gp_side_begin(gp_handle h);
 gp_status gp_side_end(gp_handle h);
 gp_status gp_side_join(gp_handle h);
+// body() with the launchers on the side stream, when `want` and the stream is to be had: *taken says whether it ran there.
+// Where it did not, nothing was enqueued and the caller runs the work in line, there or later.  Returns body's status,
+// or else gp_side_end's.
+template <typename Body>
+static inline gp_status gp_on_side(gp_handle h, bool want, bool* taken, Body body) {
+  *taken = want && gp_side_begin(h);
+  if (!*taken) return GP_OK;
+  const gp_status st = body();
+  const gp_status se = gp_side_end(h);
+  return st != GP_OK ? st : se;
+}
+// The launchers target `s` (null: where they are) while this object lives, and h->stream is restored on every path out.  For
+// work handed to the helper stream by an event of the caller's own, outside a gp_aux_fork / gp_aux_end pair.
+struct GpStreamScope {
+  gp_handle h;
+  hipStream_t saved;
+  GpStreamScope(gp_handle h_, hipStream_t s) : h(h_), saved(h_->stream) { if (s) h->stream = s; }
+  ~GpStreamScope() { h->stream = saved; }
+  GpStreamScope(const GpStreamScope&) = delete;
+  GpStreamScope& operator=(const GpStreamScope&) = delete;
+};
 
 struct GpTimerScope {
   gp_handle h;

@@ -27,6 +27,7 @@ gp_status launch_sub_identity_batched(gp_handle h, const GemmProblem* d_probs, i
 gp_status launch_phi_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_rank1_tril_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_matvec_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int trans);
+gp_status launch_batched_sum(gp_handle h, const double* v, int64_t stride, int n, int rows, double* out);   // out[r] = sum_n v[r * stride + n]
 gp_status launch_addvec_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_tril_add_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_hyper_contract(gp_handle h, DevKern k, const double* x1, int n1, const double* x2, int n2,
@@ -36,6 +37,7 @@ gp_status launch_hyper_contract(gp_handle h, DevKern k, const double* x1, int n1
 gp_status launch_hyper_finish(gp_handle h, DevKern k, const double* partials, int nparts, const double* gv_sum,
                               double* g_theta, const double* gz_partials, int ncolblocks, int n1, double* g_z);
 int hyper_num_sums(int m);
+#define HY_THREADS 256      // frames per workgroup of the generic contraction: one inducing-input partial record per such block
 // item forms (one launch for many contractions / finishes: the window-batched SGPR plan)
 struct HyperItem {
   DevKern k;

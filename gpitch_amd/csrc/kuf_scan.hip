@@ -1,6 +1,6 @@
 // kuf_scan.hip — the Kuf-side hyper-parameter contraction of a Matern-3/2 / Matern-5/2 family WITHOUT the Kuf_bar product.
 //
-// bwd.hip forms Kuf_bar = R (A D) + alpha gm^T (2 M^2 N flops per latent GP) for one purpose when the inducing inputs are
+// pdgp_bwd.hip forms Kuf_bar = R (A D) + alpha gm^T (2 M^2 N flops per latent GP) for one purpose when the inducing inputs are
 // fixed: the two sums  sum_ij Kuf_bar_ij dK_ij/d(variance, lengthscale).  A Matern kernel of half-integer order is
 // semiseparable along sorted inputs: with u = c |z_i - x_j| / l (c = sqrt 3, sqrt 5) every derivative is a polynomial in u
 // times e^-u, and on either side of z_i   u^p e^-u   is a sum of (function of i) x (function of j).  So with

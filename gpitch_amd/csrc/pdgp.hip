@@ -115,7 +115,7 @@ gp_status gp_pdgp_set_overlap(gp_pdgp_plan p, int32_t level) {
 }
 gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
   if (!p) return GP_ERR_BAD_ARG;
-  p->frames_ascending = (ascending != 0);
+  if (p->frames_ascending != (ascending != 0)) { p->frames_ascending = (ascending != 0); p->last_params = nullptr; }   // the routes depend on the promise
   return GP_OK;
 }
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
@@ -174,7 +174,7 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       b.H = ar.take<double>(M * M); b.E = ar.take<double>(M * M); b.T1 = ar.take<double>(M * M);
       b.T2 = ar.take<double>(M * M); b.Wbar = ar.take<double>(M * M); b.R = ar.take<double>(M * M);
       b.G = ar.take<double>(gp_strip_doubles(M, p->maxN, p->gps[g].f32 != 0));
-      // (Q route, bwd.hip pdgp_qform_select: like the scan's arrays below, reserved before its setters have spoken)
+      // (Q route, pdgp_bwd.hip pdgp_qform_select: like the scan's arrays below, reserved before its setters have spoken)
       if (gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM) b.Q = ar.take<double>(M * M);
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;
       b.u = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);
@@ -236,7 +236,7 @@ gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
 
 }  // extern "C"
 
-gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);  // bwd.hip
+gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);  // pdgp_bwd.hip
 gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done);
 gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);
 void pdgp_qform_select(gp_pdgp_plan p, int n);
@@ -267,7 +267,7 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   pdgp_qform_select(p, n);
   p->cb.q0 = p->q0; p->cb.nq = p->nq;
   for (int g = 0; g < p->G; g++) {
-    const bool q = (g >= p->q0 && g < p->q0 + p->nq);
+    const bool q = pdgp_on_q_route(p, g);
     p->cb.tasks[g].Qm = q ? p->bw[g].Q : nullptr;
     p->cb.tasks[g].beta = q ? p->bw[g].alpha : nullptr;
   }

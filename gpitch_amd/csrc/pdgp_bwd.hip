@@ -1,0 +1,679 @@
+// pdgp_bwd.hip — host orchestration of the Pdgp ELBO's reverse pass: descriptor slots, the Q route's host code and guard
+// kernel, the bind-time descriptor upload and the backward schedule.  The algebra, the element-wise helpers and the
+// contraction kernels it launches are in bwd.hip.
+#include "pdgp_plan.h"
+#include <string.h>
+#include <stdlib.h>
+
+// ---------------------------------------------------------------------------------------------
+// orchestration
+// slots below S_E are batched over all latent GPs, slots from S_E on over the GPs whose kernel gradients are needed.
+// S_QW_* / S_GQ_* / S_WB_*: unwhitened model only (see pdgp_backward).
+enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
+               S_E, S_EH, S_WBAR, S_LU, S_RANK1, S_R, S_ALPHA, S_G, S_T2, S_LBAR, S_P, S_T3, S_S, S_WB_R1, S_WB_L,
+               // Q route, entry i = latent GP q0 + i: E, R, beta and Q = R W of the forward pass (filled whether or
+               // not a gradient is asked), then T = W Qbar, H = T W^T and u = W v of the backward pass
+               S_QE, S_QR, S_QALPHA, S_QQ, S_QT, S_QHH, S_QU,
+               S_COUNT };
+static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
+static inline const GemmProblem* slot_probs(gp_pdgp_plan p, int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); }
+
+// ---- Q route --------------------------------------------------------------------------------------------------------
+// With E = Lq Lq^T - I, Q = W^T E W and beta = W^T q_mu the whitened conditional is
+//   fmean = Kuf^T beta,  fvar = kdiag + colsum(Kuf o G),  G = Q Kuf                      (one dense strip product)
+// and its reverse pass
+//   Kuf_bar = G diag(2 gv) + beta gm^T        (no product: the contraction reads G and scales its columns)
+//   Qbar = Kuf diag(2 gv) Kuf^T, v = Kuf gm   (the split-K product on Kuf);  H = W Qbar W^T, u = W v: the chain's H and u.
+// Which latent GPs take it at n frames (p->q0, p->nq, p->qk0): shapes, types, the gradient needs and gp_pdgp_set_qform alone,
+// never the overlap level.  All MercerMatern12sm GPs of a whitened plan, when they are float64, train their hyper-parameters
+// over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
+// batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
+void pdgp_qform_select(gp_pdgp_plan p, int n) {
+  p->q0 = p->nq = p->qk0 = 0;
+  if (!gp_switches().qform || !p->qform || !p->whiten) return;
+  int first = -1, last = -1, cnt = 0, m = -1;
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    if (q.ktype != GP_KERN_MERCER_MATERN12SM) continue;
+    if (q.f32 || !q.need_theta || q.need_z || !p->bw[g].Q || (m >= 0 && q.m != m)) return;
+    m = q.m;
+    if (first < 0) first = g;
+    last = g; cnt++;
+  }
+  if (cnt == 0 || last - first + 1 != cnt) return;
+  struct Key { int type, m, f32; };
+  std::vector<Key> seen;
+  int qk0 = 0;
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    if (!(q.need_theta || q.need_z)) continue;
+    if (g < first) qk0++;
+    const Key k{q.ktype, gp_kern_has_partials(q.ktype) ? q.m : 0, q.f32};
+    const bool same = !seen.empty() && seen.back().type == k.type && seen.back().m == k.m && seen.back().f32 == k.f32;
+    if (same) continue;
+    for (const Key& s : seen) if (s.type == k.type && s.m == k.m && s.f32 == k.f32) return;
+    seen.push_back(k);
+  }
+  if (!cond_batch_uniform(p->cb, n) || !gemm_wave_takes(6, p->maxM, n, 1) || !hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, p->maxM, n, cnt)) return;
+  p->q0 = first; p->nq = cnt; p->qk0 = qk0;
+}
+
+// the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
+void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
+  for (int i = 0; i < p->nq; i++) {
+    const int g = p->q0 + i;
+    const PdgpGP& q = p->gps[g];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& b = p->bw[g];
+    const int M = q.M;
+    auto P = [&](int slot) -> GemmProblem& {
+      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + i * sizeof(GemmProblem));
+      memset(&r, 0, sizeof(r));
+      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+      return r;
+    };
+    const double* q_sqrt = params + q.off_qsqrt;
+    { GemmProblem& r = P(S_QE); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
+    { GemmProblem& r = P(S_QR); r.A = t.W; r.B = b.E; r.C = b.R; }
+    { GemmProblem& r = P(S_QALPHA); r.A = t.W; r.v0 = params + q.off_qmu; r.o0 = b.alpha; }
+    // (the guard reads L through v0: qform_guard_kernel)
+    { GemmProblem& r = P(S_QQ); r.A = b.R; r.B = t.W; r.C = b.Q; r.v0 = t.L; }
+  }
+}
+
+// Guard of the Q route: Q inverts Kuu + jitter I explicitly, so its error grows with cond_2 of that matrix (not its root), and
+// the lengthscale is trained on the device.  c = ||L||_F^2 ||W||_F^2 = tr(K) tr(K^-1) >= cond_2(K); above GP_QFORM_COND_MAX M^2
+// (switches.h; or not finite) the handle's status word is raised, as the scan's frame check does, and the next host-scalar call fails.
+__global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __restrict__ probs, int g0, double cmax, int32_t* status) {
+  const GemmProblem p = probs[blockIdx.x];
+  const double* L = p.v0;
+  const double* W = p.B;
+  double sl = 0.0, sw = 0.0;
+  for (int idx = threadIdx.x; idx < p.M * p.M; idx += 256)      // (the lower triangles: above them L still holds Kuu)
+    if (idx % p.M <= idx / p.M) { sl = fma(L[idx], L[idx], sl); sw = fma(W[idx], W[idx], sw); }
+  __shared__ double red[2][4];
+  for (int o = 32; o > 0; o >>= 1) { sl += __shfl_down(sl, o, 64); sw += __shfl_down(sw, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sl; red[1][threadIdx.x >> 6] = sw; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double c = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+    if (!(c <= cmax * (double)p.M * (double)p.M)) { status[0] = 4; status[1] = 0; status[2] = g0 + (int)blockIdx.x; }
+  }
+}
+
+static gp_status qform_chain(gp_pdgp_plan p) {
+  gp_handle h = p->h;
+  const int nq = p->nq, maxM = p->maxM;
+  GemmFlags f;
+  f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QE), nq, maxM, maxM, f));
+  GP_CHECK(launch_sub_identity_batched(h, slot_probs(p, S_QE), nq, maxM));
+  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QR), nq, maxM, maxM, f));
+  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QALPHA), nq, maxM, 1));
+  f = GemmFlags(); f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QQ), nq, maxM, maxM, f));
+  hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
+  if (hipGetLastError() != hipSuccess) return gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
+  return GP_OK;
+}
+
+// E, R, beta, Q and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
+// (behind the factorisation it has just run, beside the other GPs' strip products), else in line; h->stream waits either way.
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n) {
+  gp_handle h = p->h;
+  if (p->nq <= 0) return GP_OK;
+  bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
+  if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
+  gp_status st;
+  { GpStreamScope on(h, aux ? h->aux_stream : nullptr); st = qform_chain(p); }
+  hipError_t e = hipSuccess;
+  if (aux) {
+    e = hipEventRecord(h->ev_q, h->aux_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_q, 0);
+  }
+  GP_CHECK(st);
+  if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
+  return GP_OK;
+}
+
+// E = Lq Lq^T - I (ERA_E) and R = W^T E, alpha = W^T q_mu (ERA_R) over the compacted batch without the Q run, whose E, R and
+// beta the forward pass has left: the slots before the run, then those behind it (no run: qk0 = nq = 0, the whole batch)
+enum { ERA_E = 1, ERA_R = 2 };
+static gp_status pdgp_era(gp_pdgp_plan p, int parts) {
+  gp_handle h = p->h;
+  const int maxM = p->maxM, behind = p->qk0 + p->nq;
+  const int s0[2] = {0, behind}, cnt[2] = {p->qk0, p->nK - behind};
+  for (int r = 0; r < 2; r++) {
+    if (cnt[r] <= 0) continue;
+    GemmFlags f;
+    if (parts & ERA_E) {
+      f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+      GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM, maxM, f));
+      GP_CHECK(launch_sub_identity_batched(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM));
+    }
+    if (parts & ERA_R) {
+      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
+      GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_R) + s0[r], cnt[r], maxM, maxM, f));
+      GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_ALPHA) + s0[r], cnt[r], maxM, 1));
+    }
+  }
+  return GP_OK;
+}
+
+// The Kuf route of every family and the shape facts the launches share, once per bind.  Priority: the Q
+// route (pdgp_qform_select's run, taken as it is), the scan, the fused epilogue, else the stored product.  The scan and the
+// fused form need every family in one run of the compacted batch, since Kuf_bar is then issued family by family; fam.batched
+// says one M, hyper-parameter gradients of every GP, no inducing-input gradient.
+//   scan : Matern-3/2 / Matern-5/2 over frames the caller promised ascending (kuf_scan.hip), float64 strips, M <= 1024.
+//          Matern-1/2 (kink at 0) and RBF (not semiseparable) have no such form.
+//   fused: a stationary family that wants Kuf_bar for two sums per GP only: they come out of the product's epilogue
+//          (gemm_strip.hip role 5; whole tiles) and neither the strip nor the separate contraction exists.
+// The overlap level and the schedule's switches (scan_side, kufbar_split) have no say here: every level must give the same bits.
+static void pdgp_select_routes(gp_pdgp_plan p, int n) {
+  const int maxM = p->maxM;
+  p->nt_uniform = ((n & 3) == 0) ? 1 : 0;
+  for (const PdgpGP& q : p->gps) if (q.M != maxM) p->nt_uniform = 0;
+  p->kuf_uniform = ((n & 1) == 0) ? 1 : 0;
+  p->k64 = 0;             // (slots of the compacted batch keep the GPs' order: its float64 GPs come first)
+  for (int g : p->kgps) {
+    if (p->gps[g].M != maxM) p->kuf_uniform = 0;
+    if (!p->gps[g].f32) p->k64++;
+  }
+  p->contiguous = p->whiten && !p->hy_fams.empty();
+  for (auto& fam : p->hy_fams) {
+    int s0 = -1;
+    for (size_t s = 0; s < p->kgps.size(); s++) if (p->kgps[s] == fam.gps[0]) s0 = (int)s;
+    for (size_t i = 0; i < fam.gps.size(); i++)
+      if (s0 < 0 || s0 + (int)i >= (int)p->kgps.size() || p->kgps[s0 + i] != fam.gps[i]) { s0 = -1; break; }
+    fam.slot0 = s0;
+    if (s0 < 0) p->contiguous = false;
+  }
+  p->any_scan = p->any_routed = false;
+  for (auto& fam : p->hy_fams) {
+    fam.route = KUF_PRODUCT; fam.np_uf = fam.np_uu = 0;
+    if (p->nq > 0 && fam.gps[0] == p->q0) {
+      fam.route = KUF_QFORM;
+    } else if (p->contiguous && gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
+               kuf_scan_nq(fam.type) > 0 && fam.M <= 1024) {
+      fam.route = KUF_SCAN; fam.np_uf = kuf_scan_records(fam.M);
+      p->any_scan = true;
+    } else if (p->contiguous && p->kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM &&
+               (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type))) {
+      fam.route = KUF_FUSED;
+      fam.np_uf = !fam.f32 ? gemm_fused_contraction_records(maxM, n, fam.type)
+                           : gemm_wave_f32_takes(5, maxM, n, p->kuf_uniform) ? (maxM / 64) * (n / 64) : (maxM / 128) * (n / 128);
+    }
+    if (fam.route != KUF_PRODUCT) p->any_routed = true;
+  }
+}
+// do the family's Kuf-side partial sums come with its Kuf_bar step (no contraction launch of its own)?
+static inline bool kuf_sums_with_step(const gp_pdgp_plan_s::HyFamily& fam) { return fam.route == KUF_FUSED || fam.route == KUF_SCAN; }
+
+gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
+  (void)x;
+  const int G = p->G;
+  p->h_fin_items.clear();       // the descriptor block is rewritten: force a fresh upload of the finish items
+  const bool white = p->whiten != 0;
+  size_t slab_off = 0;
+  p->kgps.clear();
+  for (int g = 0; g < G; g++)
+    if (p->gps[g].need_theta || p->gps[g].need_z) p->kgps.push_back(g);
+  p->nK = (int)p->kgps.size();
+  int kslot = 0;
+  for (int g = 0; g < G; g++) {
+    const PdgpGP& q = p->gps[g];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& b = p->bw[g];
+    const int M = q.M;
+    const int64_t ldN = gp_strip_ld(n, q.f32 != 0);     // this GP's strips: float64 or float32 (per-GP precision)
+    // unwhitened model: the chain runs on the equivalent whitened state q' = (W q_mu, W Lq) and its gradient
+    // buffers; pdgp_backward maps the result back (see there)
+    const double* q_mu = white ? params + q.off_qmu : b.qmu_w;
+    const double* q_sqrt = white ? params + q.off_qsqrt : b.Lq_w;
+    double* g_mu = white ? grad + q.off_qmu : b.g_qmu_w;
+    double* g_sqrt = white ? grad + q.off_qsqrt : b.g_Lq_w;
+    const double* gm = p->gFmu + (size_t)g * n;
+    const double* gv = p->gFvar + (size_t)g * n;
+    const bool kneed = (q.need_theta || q.need_z);
+    auto P = [&](int slot) -> GemmProblem& {
+      // the kernel-gradient chain (slots S_R..S_S) is batched over the GPs that need it only
+      const bool kchain = (slot >= S_E);   // E, Wbar, R, alpha, Kuf_bar and the Cholesky-adjoint chain
+      if (kchain && !kneed) { memset(&p->dummy_prob, 0, sizeof(p->dummy_prob)); return p->dummy_prob; }
+      const int idx = kchain ? kslot : g;
+      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + idx * sizeof(GemmProblem));
+      memset(&r, 0, sizeof(r));
+      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+      return r;
+    };
+    { GemmProblem& r = P(S_H); r.A = t.A; r.lda = ldN; r.B = t.A; r.ldb = ldN; r.K = n; r.v1 = gv; r.C = b.H;
+      r.o2 = p->slabs + slab_off; slab_off += gp_align_up((size_t)p->nsplit * M * M * sizeof(double), 256) / sizeof(double);
+      // fused u = A gm: partials per K-slice in o1, result in o0 and accumulated into grad q_mu (xa)
+      r.v2 = gm; r.o1 = b.upart; r.o0 = b.u; r.xa = g_mu;
+      // Q route: the same product on Kuf gives Qbar (into T2) and v = Kuf gm (into Lu); H and u follow from S_QT / S_QHH / S_QU
+      if (pdgp_on_q_route(p, g)) { r.A = t.Kuf; r.B = t.Kuf; r.C = b.T2; r.o0 = b.Lu; r.xa = nullptr; } }
+    if (pdgp_on_q_route(p, g)) {
+      auto PQ = [&](int slot) -> GemmProblem& {
+        GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + (g - p->q0) * sizeof(GemmProblem));
+        memset(&r, 0, sizeof(r));
+        r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+        return r;
+      };
+      { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
+      { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
+      { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
+    }
+    { GemmProblem& r = P(S_U); r.A = t.A; r.lda = ldN; r.N = n; r.v0 = gm; r.o0 = b.u; r.o1 = g_mu; r.a_f32 = q.f32; }
+    { GemmProblem& r = P(S_HLQ); r.A = b.H; r.B = q_sqrt; r.C = g_sqrt; }
+    if (!white) {
+      const double* qm = params + q.off_qmu;
+      const double* qs = params + q.off_qsqrt;
+      { GemmProblem& r = P(S_QW_MU); r.A = t.W; r.v0 = qm; r.o0 = b.qmu_w; }
+      { GemmProblem& r = P(S_QW_L); r.A = t.W; r.B = qs; r.C = b.Lq_w; }
+      { GemmProblem& r = P(S_GQ_MU); r.A = t.W; r.v0 = b.g_qmu_w; r.o0 = grad + q.off_qmu; }
+      { GemmProblem& r = P(S_GQ_L); r.A = t.W; r.B = b.g_Lq_w; r.C = grad + q.off_qsqrt; }
+      { GemmProblem& r = P(S_WB_R1); r.C = b.Wbar; r.v0 = b.g_qmu_w; r.v1 = qm; }
+      { GemmProblem& r = P(S_WB_L); r.A = b.g_Lq_w; r.B = qs; r.C = b.Wbar; }
+      kl_item_fill(p->h_misc.data() + p->off.kl2 + g * kl_item_bytes(), b.qmu_w, b.Lq_w, M, p->kl_dummy + (size_t)g * GP_KL_BLOCKS, b.g_qmu_w,
+                   b.g_Lq_w);
+    }
+    { GemmProblem& r = P(S_E); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
+    { GemmProblem& r = P(S_EH); r.A = b.E; r.B = b.H; r.C = b.T1; }
+    { GemmProblem& r = P(S_WBAR); r.A = b.T1; r.B = t.L; r.C = b.Wbar; }
+    { GemmProblem& r = P(S_LU); r.A = t.L; r.v0 = b.u; r.o0 = b.Lu; }
+    { GemmProblem& r = P(S_RANK1); r.C = b.Wbar; r.v0 = q_mu; r.v1 = b.Lu; }
+    { GemmProblem& r = P(S_R); r.A = t.W; r.B = b.E; r.C = b.R; }
+    { GemmProblem& r = P(S_ALPHA); r.A = t.W; r.v0 = q_mu; r.o0 = b.alpha; }
+    { GemmProblem& r = P(S_G); r.A = b.R; r.B = t.A; r.ldb = ldN; r.N = n; r.v1 = gv; r.C = b.G; r.ldc = ldN; r.xb = b.R32;
+      // (read only by the form that contracts Kuf_bar with dK/dtheta in its epilogue — gemm_strip.hip role 5)
+      r.kern = t.kern; r.xa = params + q.off_z; r.v0 = b.alpha; r.v2 = gm; r.o0 = b.hyp_part; }
+    { GemmProblem& r = P(S_T2); r.A = t.W; r.B = b.Wbar; r.C = b.T2; }
+    { GemmProblem& r = P(S_LBAR); r.A = b.T2; r.B = t.W; r.C = b.T1; }
+    { GemmProblem& r = P(S_P); r.A = t.L; r.B = b.T1; r.C = b.T2; }
+    { GemmProblem& r = P(S_T3); r.A = t.W; r.B = b.T2; r.C = b.H; }
+    { GemmProblem& r = P(S_S); r.A = b.H; r.B = t.W; r.C = b.E; }
+    if (kneed) kslot++;
+  }
+  // Kuf-side contractions, one launch per kernel family (same type and partial count): item array in kgps order inside
+  // each family.  x2 stays null in the items: the frames of the batch come with the launch (their pointer may change
+  // from step to step without a descriptor upload).
+  p->hy_fams.clear();
+  for (auto& q : p->gps) q.fam = -1;
+  for (size_t s = 0; s < p->kgps.size(); s++) {
+    const int g = p->kgps[s];
+    const PdgpGP& q = p->gps[g];
+    const int key_m = gp_kern_has_partials(q.ktype) ? q.m : 0;
+    int fi = -1;
+    for (size_t f = 0; f < p->hy_fams.size(); f++)
+      if (p->hy_fams[f].type == q.ktype && p->hy_fams[f].m == key_m && p->hy_fams[f].f32 == q.f32) fi = (int)f;
+    if (fi < 0) { gp_pdgp_plan_s::HyFamily nf; nf.type = q.ktype; nf.m = key_m; nf.M = q.M; nf.f32 = q.f32; nf.batched = true; p->hy_fams.push_back(nf); fi = (int)p->hy_fams.size() - 1; }
+    gp_pdgp_plan_s::HyFamily& fam = p->hy_fams[fi];
+    fam.gps.push_back(g);
+    p->gps[g].fam = fi;
+    if (q.M != fam.M || q.need_z || !q.need_theta) fam.batched = false;   // the per-GP path handles those
+  }
+  int nitems = 0;
+  for (auto& fam : p->hy_fams) {
+    fam.first = nitems; fam.count = (int)fam.gps.size(); nitems += fam.count;
+    fam.mfma = (gp_kern_is_mercer(fam.type) && fam.batched) ? 1 : 0;
+    fam.scan_ws = true;
+    for (int g : fam.gps) if (!p->bw[g].ks_mom || !p->bw[g].ks_near) fam.scan_ws = false;
+  }
+  pdgp_select_routes(p, n);
+  {
+    HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
+    KufScanItem* sitems = (KufScanItem*)(p->h_misc.data() + p->off.ks_items);
+    for (auto& fam : p->hy_fams) {
+      int pos = fam.first;
+      for (int g : fam.gps) {
+        const PdgpGP& q = p->gps[g];
+        const CondTask& t = p->cb.tasks[g];
+        const BwdBufs& bb = p->bw[g];
+        {    // the same GP's record for the scan form (kuf_scan.hip), used only on that route
+          KufScanItem& si = sitems[pos];
+          memset(&si, 0, sizeof(si));
+          si.A = t.A; si.lda = gp_strip_ld(n, q.f32 != 0); si.gv = p->gFvar + (size_t)g * n; si.gm = p->gFmu + (size_t)g * n;
+          si.R = bb.R; si.alpha = bb.alpha; si.z = params + q.off_z; si.theta = t.kern.theta;
+          si.mom = bb.ks_mom; si.near = bb.ks_near; si.partials = bb.hyp_part; si.M = q.M;
+        }
+        HyperItem& it = items[pos++];
+        memset(&it, 0, sizeof(it));
+        const int64_t ldN = gp_strip_ld(n, q.f32 != 0);
+        it.k = t.kern; it.x1 = params + q.off_z; it.n1 = q.M; it.x2 = nullptr; it.n2 = n; it.G = bb.G; it.ldg = ldN;
+        it.alpha = bb.alpha; it.gm = p->gFmu + (size_t)g * n; it.symmetric = 0; it.partials = bb.hyp_part; it.gz = nullptr;
+        it.kvals = t.Kuf; it.ldk = ldN; it.g32 = q.f32;
+        if (fam.route == KUF_QFORM) { it.G = t.A; it.gscale = p->gFvar + (size_t)g * n; }     // Q route: G = Q Kuf, in A's strip
+        if (gp_kern_is_mercer(q.ktype) && t.feat) {
+          it.f1 = t.feat;
+          it.f2 = t.feat + gp_align_up((size_t)2 * sm_mpad(q.m) * q.M, 32);
+        }
+        // its Kuu-side twin (contraction of Kuu_bar = E with dK(z, z)): G entries further on
+        HyperItem& iu = items[G + pos - 1];
+        memset(&iu, 0, sizeof(iu));
+        iu.k = t.kern; iu.x1 = params + q.off_z; iu.n1 = q.M; iu.x2 = iu.x1; iu.n2 = q.M; iu.G = bb.E; iu.ldg = q.M;
+        iu.symmetric = 1; iu.partials = bb.hyp_part_uu;
+        if (gp_kern_is_mercer(q.ktype) && t.feat) { iu.f1 = t.feat; iu.f2 = t.feat; }
+      }
+    }
+  }
+  return GP_OK;
+}
+
+// R = W^T (Lq Lq^T - I) and alpha = W^T q_mu depend on the parameters and on W only: when the helper stream exists they
+// are enqueued on it during the FORWARD pass, right behind the Kuu factorisation it has just run (no wait on the main
+// stream, which is busy with the forward GEMM strips), and the backward pass finds them ready.
+// The whitened KL terms (parameters only) ride along: on the main stream they were one of five tiny kernels between
+// the last forward strip product and the first backward one, with the device idle around them.
+gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
+  gp_handle h = p->h;
+  p->era_ready = false;
+  if (kl_done) *kl_done = false;
+  if (!(p->whiten && p->nK > 0 && n >= 4096 && p->overlap >= 2 && h->aux_stream && !h->aux_active)) return GP_OK;
+  if (!h->ev_era && hipEventCreateWithFlags(&h->ev_era, hipEventDisableTiming) != hipSuccess) { h->ev_era = nullptr; return GP_OK; }
+  gp_status st;
+  {
+    GpStreamScope on(h, h->aux_stream);
+    st = pdgp_era(p, ERA_E | ERA_R);
+    if (st == GP_OK && kl_done) {
+      st = launch_kl_white(h, p->d_misc + p->off.kl_items, p->G);
+      *kl_done = (st == GP_OK);
+    }
+  }
+  hipError_t e = hipEventRecord(h->ev_era, h->aux_stream);
+  GP_CHECK(st);
+  if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "hipEventRecord on the helper stream failed");
+  p->era_ready = true;
+  return GP_OK;
+}
+
+// ---- the backward pass's steps: each enqueues on h->stream, wherever the schedule (pdgp_backward) has pointed it ----------
+struct BwdCall { gp_pdgp_plan p; const double* params; const double* x; int n; double* grad; };
+typedef gp_pdgp_plan_s::HyFamily HyFamily;
+
+// conditional(whiten=False) + gauss_kl(q_mu, q_sqrt, K) (pdgp.py:123-129, 147-155) is the whitened model at
+//   q_mu' = W q_mu,  Lq' = W Lq      (W = chol(Kuu + jitter I)^-1),
+// so the whitened chain runs on (q_mu', Lq') with gradient buffers (g', G'), and afterwards
+//   grad q_mu = W^T g',  grad q_sqrt = tril(W^T G'),  Wbar += tril(g' q_mu^T + G' Lq^T).
+static gp_status bwd_unwhitened_head(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  GP_HIP_CHECK(h, hipMemsetAsync(p->qw_block, 0, p->qw_doubles * sizeof(double), h->stream));
+  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QW_MU), p->G, p->maxM, 0));
+  GemmFlags f; f.triA = TRI_LOWER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QW_L), p->G, p->maxM, p->maxM, f));
+  return launch_kl_white(h, p->d_misc + p->off.kl2, p->G);   // accumulates -dKL/dq' into (g', G')
+}
+static gp_status bwd_unwhitened_tail(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_GQ_MU), p->G, p->maxM, 1));
+  GemmFlags f; f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER; f.triC = TRI_LOWER;
+  return launch_gemm_batched(h, slot_probs(p, S_GQ_L), p->G, p->maxM, p->maxM, f);
+}
+
+// sum_n gv (the kdiag term) and the ELBO's final reduction (pdgp.hip: pdgp_finish): wanted only when the step ends
+static gp_status bwd_late_sums(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  GP_CHECK(launch_batched_sum(h, p->gFvar, (int64_t)c.n, c.n, p->G, p->bw[0].gvsum));
+  if (p->fin.pending) {
+    p->fin.pending = false;
+    GP_CHECK(launch_elbo_finish(h, p->fin.lik_partials, p->fin.nb, p->fin.kl, p->fin.nkl, p->fin.elbo, p->fin.g_noise));
+  }
+  return GP_OK;
+}
+
+// H = A diag(2 gv) A^T (symmetric, split-K over the frames; u = A gm and grad q_mu += u are fused into it), grad q_sqrt
+static gp_status bwd_h_chain(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  const int G = p->G, maxM = p->maxM, n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
+  GemmFlags f;
+  if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H), n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+  if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, slot_probs(p, S_H) + n64, G - n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+  if (p->nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
+    f = GemmFlags(); f.triA = TRI_LOWER;
+    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QT), p->nq, maxM, maxM, f));
+    f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER;
+    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QHH), p->nq, maxM, maxM, f));
+    GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QU), p->nq, maxM, 0));
+  }
+  // grad q_sqrt += tril(H Lq)
+  f = GemmFlags(); f.triB = TRI_LOWER; f.triC = TRI_LOWER; f.beta = 1.0;
+  return launch_gemm_batched(h, slot_probs(p, S_HLQ), G, maxM, maxM, f);
+}
+
+// T1 = E H;  Wbar = tril(T1 L^T) + tril(mu (L u)^T)
+static gp_status bwd_wbar_chain(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  const int nK = p->nK, maxM = p->maxM;
+  GemmFlags f;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_EH), nK, maxM, maxM, f));
+  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_WBAR), nK, maxM, maxM, f));
+  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_LU), nK, maxM, 0));
+  GP_CHECK(launch_rank1_tril_batched(h, slot_probs(p, S_RANK1), nK, maxM));
+  if (!p->whiten) {
+    GP_CHECK(launch_rank1_tril_batched(h, slot_probs(p, S_WB_R1), nK, maxM));
+    f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.beta = 1.0;
+    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_WB_L), nK, maxM, maxM, f));
+  }
+  return GP_OK;
+}
+
+// The Kuu side: Lbar = -tril(W^T Wbar W^T); P = Phi(L^T Lbar); S = W^T P W, and the contraction of Kuu_bar with
+// dK(z, z)/d(theta, z), partial sums only: one launch per kernel family (24 launches of a few workgroups each otherwise:
+// 2.6 ms at the end of the helper stream's chain), per GP where a family is mixed
+static gp_status bwd_kuu_side(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  const int nK = p->nK, maxM = p->maxM;
+  GemmFlags f;
+  f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_T2), nK, maxM, maxM, f));
+  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_LBAR), nK, maxM, maxM, f));
+  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_P), nK, maxM, maxM, f));
+  GP_CHECK(launch_phi_batched(h, slot_probs(p, S_P), nK, maxM));
+  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_T3), nK, maxM, maxM, f));
+  f = GemmFlags(); f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_S), nK, maxM, maxM, f));
+  for (auto& fam : p->hy_fams)
+    if (fam.batched)
+      GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + p->G + fam.first,
+                                           fam.count, fam.M, fam.M, 0, &fam.np_uu));
+  for (int g : p->kgps) {
+    PdgpGP& q = p->gps[g];
+    if (p->hy_fams[q.fam].batched) continue;
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& bb = p->bw[g];
+    const double* z = c.params + q.off_z;
+    const int cb_uf = (c.n + HY_THREADS - 1) / HY_THREADS;
+    double* gz_uu = q.need_z ? bb.gz_part + (size_t)cb_uf * q.M : nullptr;
+    GP_CHECK(launch_hyper_contract(h, t.kern, z, q.M, z, q.M, bb.E, q.M, nullptr, nullptr, 1, t.feat, bb.hyp_part_uu, &q.np_uu, gz_uu));
+  }
+  return GP_OK;
+}
+
+// Kuf_bar (dense part) = R (A diag(2 gv)) of `count` slots of the compacted batch from slot0 on.  `fused`: they are that
+// family's, and its Kuf-side contraction is the product's epilogue, nothing stored (one precision per family).
+static gp_status bwd_kuf_product(const BwdCall& c, int slot0, int count, const HyFamily* fused = nullptr) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  const int maxM = p->maxM, k64 = p->k64;
+  GemmFlags f;
+  f.big_tiles = 1; f.scale_mode = 1; f.alpha = 2.0; f.timer = GP_TIMER_KUF_BAR; f.role = 3;
+  f.uniform_aligned = p->kuf_uniform;
+  f.a32_ok = 1;          // (float32 GPs: b.R32 is in every problem's xb)
+  if (fused) {
+    f.role = 5; f.epilogue = 0; f.aux_x = c.x; f.aux_ktype = fused->type;
+    if (fused->f32) return launch_gemm_f32_role(h, slot_probs(p, S_G) + slot0, count, maxM, c.n, f);
+    return launch_gemm_batched(h, slot_probs(p, S_G) + slot0, count, maxM, c.n, f);
+  }
+  const int c64 = (slot0 < k64) ? ((slot0 + count <= k64) ? count : k64 - slot0) : 0;
+  if (c64 > 0) GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_G) + slot0, c64, maxM, c.n, f));
+  if (c64 < count) GP_CHECK(launch_gemm_f32_role(h, slot_probs(p, S_G) + slot0 + c64, count - c64, maxM, c.n, f));
+  return GP_OK;
+}
+
+// One family's Kuf_bar step, by its route.  scan_to_side: the scan's three launches go to the side stream if it is to be had.
+static gp_status bwd_kuf_bar_step(const BwdCall& c, const HyFamily& fam, bool scan_to_side) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  switch (fam.route) {
+    case KUF_QFORM: return GP_OK;      // Kuf_bar = G diag(2 gv) + beta gm^T needs no product: the contraction scales G's columns
+    case KUF_SCAN: {
+      auto scan = [&]() { return launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, c.x, c.n); };
+      bool side;
+      GP_CHECK(gp_on_side(h, scan_to_side, &side, scan));
+      return side ? GP_OK : scan();
+    }
+    case KUF_FUSED: return bwd_kuf_product(c, fam.slot0, fam.count, &fam);
+    case KUF_PRODUCT: break;
+  }
+  return bwd_kuf_product(c, fam.slot0, fam.count);
+}
+
+// One family's Kuf-side contraction of Kuf_bar with dK/dtheta over all frames: one launch over its item array (built at
+// bind), or GP by GP where the family is mixed (inducing-input gradients, several sizes)
+static gp_status bwd_contract(const BwdCall& c, HyFamily& fam) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  if (fam.batched)
+    return launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + fam.first, fam.count,
+                                       fam.M, c.n, 0, &fam.np_uf, fam.mfma, c.x, fam.f32, 1, fam.route == KUF_QFORM ? 1 : 0);
+  for (int g : fam.gps) {
+    PdgpGP& q = p->gps[g];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& bb = p->bw[g];
+    const int64_t ldN = gp_strip_ld(c.n, q.f32 != 0);
+    GP_CHECK(launch_hyper_contract(h, t.kern, c.params + q.off_z, q.M, c.x, c.n, bb.G, ldN, bb.alpha, p->gFmu + (size_t)g * c.n, 0, t.feat,
+                                   bb.hyp_part, &q.np_uf, q.need_z ? bb.gz_part : nullptr, t.Kuf, ldN, q.f32));
+  }
+  return GP_OK;
+}
+
+// All partial sums (Kuf side, Kuu side) are in: ONE finish launch adds them into the gradient vector (48 tiny launches at
+// the end of every step otherwise).  The item array is re-uploaded only when it changes.
+static gp_status bwd_finish(const BwdCall& c) {
+  gp_pdgp_plan p = c.p; gp_handle h = p->h;
+  std::vector<HyperFinishItem> items;
+  int maxblocks = 0;
+  for (int g : p->kgps) {
+    const PdgpGP& q = p->gps[g];
+    const HyFamily& fam = p->hy_fams[q.fam];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& bb = p->bw[g];
+    const int cb_uf = (c.n + HY_THREADS - 1) / HY_THREADS, cb_uu = (q.M + HY_THREADS - 1) / HY_THREADS;
+    HyperFinishItem it;
+    memset(&it, 0, sizeof(it));
+    it.k = t.kern; it.p_uf = bb.hyp_part; it.p_uu = bb.hyp_part_uu;
+    it.np_uf = fam.batched ? fam.np_uf : q.np_uf; it.np_uu = fam.batched ? fam.np_uu : q.np_uu;
+    it.gv_sum = bb.gvsum; it.g_theta = c.grad + q.off_theta; it.n1 = q.M;
+    if (q.need_z) {
+      it.gz_uf = bb.gz_part; it.cb_uf = cb_uf; it.gz_uu = bb.gz_part + (size_t)cb_uf * q.M; it.cb_uu = cb_uu;
+      it.g_z = c.grad + q.off_z;
+    }
+    const int blocks = 2 + 2 * t.kern.m + (q.need_z ? (q.M + 255) / 256 : 0);
+    if (blocks > maxblocks) maxblocks = blocks;
+    items.push_back(it);
+  }
+  const size_t bytes = items.size() * sizeof(HyperFinishItem);
+  char* d_items = p->d_misc + p->off.fin_items;
+  if (p->h_fin_items.size() != bytes || memcmp(p->h_fin_items.data(), items.data(), bytes) != 0) {
+    p->h_fin_items.assign((const char*)items.data(), (const char*)items.data() + bytes);
+    GP_HIP_CHECK(h, hipMemcpyAsync(d_items, p->h_fin_items.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  return launch_hyper_finish_items(h, (const HyperFinishItem*)d_items, (int)items.size(), maxblocks);
+}
+
+// The helper stream's chain: [the H chain when forked early,] the Kuu side [, the late sums: at the END of the chain — ahead
+// of the split-K product they delayed it]
+static gp_status bwd_helper_chain(const BwdCall& c, bool early_fork) {
+  if (early_fork) { GP_CHECK(bwd_h_chain(c)); GP_CHECK(bwd_wbar_chain(c)); }
+  GP_CHECK(bwd_kuu_side(c));
+  return early_fork ? bwd_late_sums(c) : GP_OK;
+}
+
+// With exactly two families — the transcription model: stationary activations, spectral-mixture components — in
+// contiguous runs of the compacted batch, Kuf_bar is issued family by family and the first family's contraction runs on the
+// side stream UNDERNEATH the second family's product instead of after it.  Which goes first (switches.h kufbar_split;
+// -1 = by precision): with float64 strips the stationary family — its contraction (an HBM read, next to no arithmetic)
+// goes underneath the spectral-mixture product, whose float64 MFMA holds the vector ALU, and the long contraction has the
+// device to itself afterwards; with float32 strips the spectral-mixture family — its vector-ALU contraction then runs
+// beside the other family's float32 matrix product, which leaves the vector ALU free (cfg3 3.90 -> 3.80 ms, headline
+// 19.47 / 19.56 the other way round).  False: no such pair, or the switch says no.
+static bool bwd_two_family_order(gp_pdgp_plan p, HyFamily** first, HyFamily** second) {
+  if (p->hy_fams.size() != 2 || p->hy_fams[0].mfma == p->hy_fams[1].mfma) return false;
+  HyFamily* sm = &p->hy_fams[p->hy_fams[0].mfma ? 0 : 1];
+  HyFamily* other = &p->hy_fams[p->hy_fams[0].mfma ? 1 : 0];
+  if (sm->slot0 < 0 || other->slot0 < 0) return false;
+  int mode = gp_switches().kufbar_split;
+  if (mode < 0) mode = sm->f32 ? 1 : 2;
+  if (mode < 1) return false;
+  *first = (mode == 2) ? other : sm;
+  *second = (mode == 2) ? sm : other;
+  return true;
+}
+
+// The schedule: which step goes to the helper stream (gp_aux_fork .. gp_aux_end), which to the side stream (gp_on_side), and in
+// which order.  The routes were chosen at bind; overlap, scan_side and kufbar_split move launches between streams and
+// reorder independent ones, never add or drop one that changes a bit.
+gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
+  gp_handle h = p->h;
+  const BwdCall c{p, params, x, n, grad};
+  const bool white = p->whiten != 0;
+  if (!white) GP_CHECK(bwd_unwhitened_head(c));
+  // Everything that hangs off H = A diag(2 gv) A^T — grad q_sqrt, Wbar, the whole Kuu side — is independent of the
+  // Kuf_bar product, which needs only R = W^T (Lq Lq^T - I) and alpha = W^T q_mu.  With early_fork the H chain
+  // (the split-K product included) goes to the helper stream and the main stream starts Kuf_bar right away; the late sums
+  // go to the end of the helper stream's chain when there is one, and run up front otherwise.
+  const bool early_fork = white && p->nK > 0 && n >= 4096 && p->overlap >= 2;
+  if (!early_fork) { GP_CHECK(bwd_late_sums(c)); GP_CHECK(bwd_h_chain(c)); }
+  if (p->nK == 0) return white ? GP_OK : bwd_unwhitened_tail(c);
+
+  const bool pre = p->era_ready;   // E, R, alpha were computed on the helper stream during the forward pass
+  p->era_ready = false;
+  if (pre) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));
+  else GP_CHECK(pdgp_era(p, ERA_E));
+  if (!early_fork) GP_CHECK(bwd_wbar_chain(c));
+  if (!pre) GP_CHECK(pdgp_era(p, ERA_R));
+  // From here two independent chains remain: the Kuf side (the big Kuf_bar product and its contraction with dK/dtheta over
+  // all frames) and the Kuu side (the Cholesky adjoint, six M x M products, and its contraction over M x M).  The Kuu side
+  // is ~1.4 ms of small launches: it runs on the helper stream underneath Kuf_bar.
+  // With a scan family (switches.h scan_side; measurements: DESIGN.md 3.02) the scan's launches go to the side stream, beside
+  // the other families' Kuf_bar product.  The side stream serves ONE fork per backward pass — gp_side_begin refuses until
+  // gp_side_join — so only the first taker gets it: a further scan family, or a contraction that asks after it, stays in line.
+  const bool scan_side = p->any_scan && gp_switches().scan_side != 0 && n >= 4096 && p->overlap >= 2;
+  const bool forked = n >= 4096 && p->overlap >= 1 && gp_aux_fork(h);
+  if (forked) {
+    const gp_status st = bwd_helper_chain(c, early_fork);
+    const gp_status se = gp_aux_end(h);
+    GP_CHECK(st); GP_CHECK(se);
+  } else if (early_fork) {
+    GP_CHECK(bwd_late_sums(c));
+  }
+  HyFamily *first = nullptr, *second = nullptr;
+  if (forked && p->overlap >= 2 && bwd_two_family_order(p, &first, &second)) {
+    const bool pending = !kuf_sums_with_step(*first);     // first's contraction is still to run once its step is through
+    bool side = false;
+    GP_CHECK(bwd_kuf_bar_step(c, *first, scan_side));
+    if (pending) GP_CHECK(gp_on_side(h, true, &side, [&]() { return bwd_contract(c, *first); }));
+    GP_CHECK(bwd_kuf_bar_step(c, *second, scan_side));
+    if (pending && !side) GP_CHECK(bwd_contract(c, *first));
+    if (!kuf_sums_with_step(*second)) GP_CHECK(bwd_contract(c, *second));
+  } else {
+    // one product over the whole batch, or family by family when some family has a route of its own; then the families'
+    // contractions side by side: the matrix-core ones on this stream, the others (short, HBM-bound) on the side stream
+    if (p->any_routed) { for (const auto& fam : p->hy_fams) GP_CHECK(bwd_kuf_bar_step(c, fam, scan_side)); }
+    else GP_CHECK(bwd_kuf_product(c, 0, p->nK));
+    if (!forked) {       // (no helper stream to be had)
+      if (early_fork) { GP_CHECK(bwd_h_chain(c)); GP_CHECK(bwd_wbar_chain(c)); }
+      GP_CHECK(bwd_kuu_side(c));
+    }
+    bool side = false;
+    GP_CHECK(gp_on_side(h, p->hy_fams.size() > 1 && forked && p->overlap >= 2, &side, [&]() -> gp_status {
+      for (auto& fam : p->hy_fams) if (!fam.mfma && !kuf_sums_with_step(fam)) GP_CHECK(bwd_contract(c, fam));
+      return GP_OK;
+    }));
+    for (auto& fam : p->hy_fams) if ((!side || fam.mfma) && !kuf_sums_with_step(fam)) GP_CHECK(bwd_contract(c, fam));
+  }
+  if (!white) GP_CHECK(bwd_unwhitened_tail(c));
+  GP_CHECK(gp_side_join(h));
+  GP_CHECK(gp_aux_join(h));
+  return bwd_finish(c);
+}

@@ -1,4 +1,4 @@
-// pdgp_plan.h — Pdgp plan object shared by pdgp.hip (forward) and bwd.hip (backward).
+// pdgp_plan.h — Pdgp plan object shared by pdgp.hip (forward, bind) and pdgp_bwd.hip (backward descriptors, routes, schedule).
 #pragma once
 #include "engine.h"
 
@@ -9,7 +9,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 
 // The plan's `misc` descriptor block: [KL items][PDGP_BWD_SLOTS arrays of G GemmProblems][KL items of the unwhitened
 // backward][G hyper-gradient finish items][2 G contraction items].  The backward pass uses the first S_COUNT slots
-// (bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
+// (pdgp_bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
 struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, bytes; };
@@ -32,6 +32,17 @@ struct PdgpGP {
   int need_theta = 1, need_z = 1;   // gp_pdgp_set_grad_needs
   int f32 = 0;                      // this GP's M x N strips are float32 (gp_pdgp_set_precision / gp_pdgp_set_gp_precision)
   int64_t off_theta = 0, off_z = 0, off_qmu = 0, off_qsqrt = 0;
+  int fam = -1;                     // its family in hy_fams (pdgp_upload_bwd; -1: no kernel gradient asked)
+  int np_uf = 0, np_uu = 0;         // GPs of an unbatched family: partial records its own contractions left this step
+};
+
+// How a kernel family gets its Kuf-side hyper-gradient sums.  Decided at bind (pdgp_bwd.hip: pdgp_select_routes),
+// from shapes, kernel types, precision, the gradient needs, the switches and the two setters — never from the overlap level.
+enum KufRoute {
+  KUF_PRODUCT,   // Kuf_bar = R (A diag(2 gv)) stored, then the family's contraction
+  KUF_FUSED,     // the contraction as that product's epilogue (gemm_strip.hip role 5): no strip, no contraction launch
+  KUF_SCAN,      // moment sums along ascending frames (kuf_scan.hip): no product
+  KUF_QFORM      // Kuf_bar = G diag(2 gv) + beta gm^T: no product, the contraction scales G's columns
 };
 
 struct BwdBufs {  // per-GP backward workspace (device)
@@ -81,10 +92,24 @@ struct gp_pdgp_plan_s {
   double* slabs = nullptr;                           // split-K slabs
   char* d_misc = nullptr; PdgpMiscLayout off;        // KL items + backward problem arrays: off = pdgp_misc_layout(G)
   std::vector<char> h_misc;
-  std::vector<char> h_fin_items;   // batched hyper-gradient finish (bwd.hip)
-  // Kuf-side and Kuu-side contractions grouped by kernel family: one launch per family and side over an item array (bwd.hip)
-  struct HyFamily { int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; bool scan_ws = false; std::vector<int> gps; };
+  std::vector<char> h_fin_items;   // batched hyper-gradient finish (pdgp_bwd.hip)
+  // Kuf-side and Kuu-side contractions grouped by kernel family: one launch per family and side over an item array (pdgp_bwd.hip)
+  struct HyFamily {
+    int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; bool scan_ws = false;
+    int slot0 = -1;                  // its first slot in the compacted batch; -1: its GPs do not sit in one run of it
+    KufRoute route = KUF_PRODUCT;
+    int np_uf = 0, np_uu = 0;        // batched family: partial records per GP.  np_uf is fixed at bind by the fused and scan routes;
+                                     // the contractions report the others at launch
+    std::vector<int> gps;
+  };
   std::vector<HyFamily> hy_fams;
+  // shape facts of the bound batch the routes and the launches share (pdgp_select_routes)
+  bool contiguous = false;     // whitened, and every family sits in one run of the compacted batch
+  bool any_scan = false;       // some family takes KUF_SCAN
+  bool any_routed = false;     // some family's route is not KUF_PRODUCT: Kuf_bar is then issued family by family
+  int kuf_uniform = 0;         // even n and every GP of the compacted batch M = maxM (R, A, G: arena buffers, even ld)
+  int nt_uniform = 0;          // the split-K product: n a multiple of 4 and every latent GP M = maxM
+  int k64 = 0;                 // float64 GPs of the compacted batch (they come first)
   double* qw_block = nullptr; size_t qw_doubles = 0;   // [q' | grad q'] of all GPs, contiguous (one memset)
   double* kl_dummy = nullptr;
   int nsplit = 1;
@@ -96,14 +121,14 @@ struct gp_pdgp_plan_s {
   GemmProblem dummy_prob;      // sink for descriptor slots a GP does not need (pdgp_upload_bwd)
   // the ELBO's final reduction (and the noise-variance gradient it produces), handed to the backward pass: neither is
   // needed before the step ends, so it runs at the head of the helper stream's chain instead of between the last forward
-  // product and Kuf_bar (bwd.hip: pdgp_backward)
+  // product and Kuf_bar (pdgp_bwd.hip: pdgp_backward)
   struct { const double* lik_partials = nullptr; int nb = 0; const double* kl = nullptr; int nkl = 0; double* elbo = nullptr;
            double* g_noise = nullptr; bool pending = false; } fin;
   int overlap = 2;             // gp_pdgp_set_overlap: 0 one stream, 1 Kuu factorisation / Kuu-side backward on the helper
                                // stream, 2 also the H = A D A^T chain next to Kuf_bar
   bool frames_ascending = false;   // gp_pdgp_set_frames_ascending: the caller promises time-ordered batches
   bool era_ready = false;      // pdgp_prefetch_backward ran for the current evaluation
-  // Q route (bwd.hip pdgp_qform_select): gp_pdgp_set_qform's permission, and the run of latent GPs
+  // Q route (pdgp_bwd.hip pdgp_qform_select): gp_pdgp_set_qform's permission, and the run of latent GPs
   // [q0, q0 + nq) that takes it at the bound batch size (nq = 0: none); qk0 = the run's first slot in the compacted batch
   bool qform = false;
   int q0 = 0, nq = 0, qk0 = 0;
@@ -116,4 +141,7 @@ struct gp_pdgp_plan_s {
   std::vector<int> grow;
   double* gF_full_mu = nullptr; double* gF_full_var = nullptr;   // [2 P][maxN]: d varexp / d fmean, fvar of every latent GP
 };
+
+// is latent GP g in the run that takes the Q route at the bound batch size?  (A family asks its route field instead.)
+static inline bool pdgp_on_q_route(const gp_pdgp_plan_s* p, int g) { return g >= p->q0 && g < p->q0 + p->nq; }
 

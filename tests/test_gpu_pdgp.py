@@ -517,32 +517,66 @@ def test_headline_M512_blocked_factorisation_gradient_vs_autograd(gp_handle):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("N,M,P", [(4096, 48, 2), (4200, 300, 1)])
-def test_overlap_levels_give_identical_results(gp_handle, N, M, P):
+# The cases beyond the first two walk other orders of the backward schedule at the smallest forking batch (N = 4096, M = 64):
+#   mixed: float64 activations, float32 components (the benchmark's `mixed` line); zc: trainable component inducing inputs, a
+#   family contracted GP by GP; two_act: Matern-3/2 and Matern-1/2 activations, three families, the schedule without the
+#   two-family split.
+# Not here: float32 strips (P = 2) and whiten=False (P = 1).  Their bits agree at every level, their kuf_bar launch counts
+# do not: no family of theirs takes a route of its own, so levels 0 and 1 form Kuf_bar in ONE launch over the whole batch
+# and level 2, which issues it family by family, in two.
+OVERLAP_CASES = [
+    pytest.param(4096, 48, 2, None, id="4096-48-2"),
+    pytest.param(4200, 300, 1, None, id="4200-300-1"),
+    pytest.param(4096, 64, 2, "mixed", id="4096-64-2-mixed"),
+    pytest.param(4096, 64, 2, "zc", id="4096-64-2-zc"),
+    pytest.param(4096, 64, 2, "two_act", id="4096-64-2-two_act"),
+]
+
+
+@pytest.mark.parametrize("N,M,P,case", OVERLAP_CASES)
+def test_overlap_levels_give_identical_results(gp_handle, N, M, P, case):
     """gp_pdgp_set_overlap changes only the schedule (helper-stream fork / join points); the ELBO and every gradient
     entry must come out bit for bit the same at every level (batches of >= 4096 frames are the ones that fork;
-    M = 300 takes the resident-factor + blocked-inverse route, chosen by N and M alone)."""
+    M = 300 takes the resident-factor + blocked-inverse route, chosen by N and M alone), and so must the number of
+    launches charged to the kuf_bar, nt_gemm and hyper timers: the level moves launches between streams, it neither
+    adds nor drops one."""
     from gpitch_amd.synth import make_problem
     prob = make_problem(N, M, P, num_partials=3, seed=13)
-    ref = None
+    kw = {}
+    if case == "mixed":
+        kw = dict(float_type=(np.float64, np.float32))
+    elif case == "two_act":
+        prob["kern_act"][0]["type"], prob["kern_act"][1]["type"] = "matern32", "matern12"
+    h = gp_handle
+    ref = ref_counts = None
     for level in (0, 1, 2, 1, 0):
-        m = pdgp_from_problem(prob, handle=gp_handle)
+        m = pdgp_from_problem(prob, handle=h, **kw)
         m.za.fixed = True
-        m.zc.fixed = True
+        m.zc.fixed = (case != "zc")
         m._pack()
-        gp_handle.check(gp_handle.lib.gp_pdgp_set_overlap(m._plan, level))
+        h.check(h.lib.gp_pdgp_set_overlap(m._plan, level))
         vals = []
         for _ in range(2):                      # the second evaluation (a fresh frame permutation, identically seeded in
             f = m._elbo(True)                   # every model) reuses descriptors and streams
             vals.append((f, m._grad.cpu().numpy().copy()))
+        h.check(h.lib.gp_timers_enable(h.h, 1))
+        h.check(h.lib.gp_timers_reset(h.h))
+        try:
+            m._elbo(True)
+            h.sync()
+            counts = {k: h.timers()[k][1] for k in ("kuf_bar", "nt_gemm", "hyper")}
+        finally:
+            h.check(h.lib.gp_timers_enable(h.h, 0))
+        print("%s level %d: ELBO %r launches %r" % (case, level, vals[0][0], counts))
         if ref is None:
-            ref = vals
+            ref, ref_counts = vals, counts
         else:
             for a, b in zip(vals, ref):
                 assert a[0] == b[0], level
                 assert np.array_equal(a[1], b[1]), level
+            assert counts == ref_counts, (level, counts, ref_counts)
     with pytest.raises(Exception):
-        gp_handle.check(gp_handle.lib.gp_pdgp_set_overlap(m._plan, 3))
+        h.check(h.lib.gp_pdgp_set_overlap(m._plan, 3))
 
 
 def test_adam_stops_at_a_failed_cholesky_and_leaves_the_state_alone(gp_handle):
