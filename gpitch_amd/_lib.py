@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
     "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
     "gp_pdgpb_predict_moments_workspace_bytes", "gp_pdgpb_predict_moments",
+    "gp_pdgpb_sample_workspace_bytes", "gp_pdgpb_sample",
 ]
 
 
@@ -252,6 +253,8 @@ def load_library():
         "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),
         "gp_pdgpb_predict_moments_workspace_bytes": (sz, [vp, i64]),
         "gp_pdgpb_predict_moments": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, sz]),
+        "gp_pdgpb_sample_workspace_bytes": (sz, [vp, C.POINTER(i64), i32]),
+        "gp_pdgpb_sample": (i32, [vp, vp, vp, C.POINTER(i64), vp, i32, vp, vp, vp, vp, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol

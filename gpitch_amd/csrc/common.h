@@ -383,6 +383,48 @@ struct SrcSparseItem {
   const double* xnew; double* mean; double* var; int kz, ldw;
 };
 gp_status launch_sgpr_source_sparse(gp_handle h, const SrcSparseItem* d_items, int P, int nwin, int M, int n, int max_mpad);
+// sample.hip, core: the state-space sampler of a list of independent processes (prior walk along the merged points, update
+// draw(x*) = prior(x*) + K(x*, z) beta), shared by the operators below and by pdgp_batch.hip's gp_pdgpb_sample.  One record per
+// sampled process: everything the prior and update kernels read.
+struct SsmProc {
+  DevKern k;
+  const double* z; const double* xnew;
+  const double* fz; const double* fx;     // sqrt(e) cos / sin tables of z ([2 mp][kz]) and of xnew ([2 mp][n]); SM kernels only
+  const int* order;                       // the process's merged order, n + kz entries (validated on the host)
+  const double* eps_x; const double* eps_z;   // draw 0 of this process's component block: [S][cs][n] and [S][cs][ezs]
+  const double* beta;                     // [kz][S]
+  double* out;                            // [S][n]
+  double* pz;                             // prior(z): [kz][S]
+  int n;                                  // the process's own frame count
+  int kz, mp;                             // mp: sm_mpad(m) of an SM kernel, else 0
+  int cs, ezs;                            // components between two draws; points between two components of eps_z
+};
+// the owner of entry b of a work list: the last g with start[g] <= b (start ascending, count + 1 items, the last the total)
+__device__ __forceinline__ int gp_entry_owner(const int64_t* __restrict__ start, int count, int64_t b) {
+  int lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+int ssm_components(int type, int m);      // standard normals per point: 1 Matern12, 2 Matern32, 2 m a Matern-1/2 spectral mixture
+int ssm_mpad(DevKern k);                  // sm_mpad(m) of a spectral-mixture kernel, else 0
+// A call's descriptor block: procs | the operator's own records | feature items (at most two per process) | GEMM problems |
+// the update's tile list (nproc + 1 items)
+struct SsmDesc { size_t procs, recs, feat, probs, tiles, bytes; };
+SsmDesc ssm_desc_layout(size_t nproc, size_t rec_bytes, size_t nprob);
+// fills the tile list of the host block hd from the processes' n and kz (T = the update's frames per tile at maxM); returns the entries
+int64_t ssm_fill_tiles(const SsmDesc& lay, std::vector<char>& hd, int count, int maxM);
+struct SsmSpan { size_t off; int len; };  // `order` becomes device addresses: every span's entries must be a permutation of 0..len-1
+gp_status ssm_check_orders(gp_handle h, const int32_t* order_host, const std::vector<SsmSpan>& spans, const char* not_a_permutation);
+// Uploads the block (hd: its host copy, the first nfeat feature items filled in any order) and `order`, then builds the feature tables
+gp_status ssm_upload(gp_handle h, const SsmDesc& lay, std::vector<char>& hd, char* d_desc, int nfeat, const int32_t* order_host,
+                     int* d_order, size_t norder, int max_n);
+// d_procs: count <= 32767 processes, none with more than maxM inducing inputs; max_mpad: the largest mp among them
+gp_status ssm_launch_prior(gp_handle h, const SsmProc* d_procs, int count, int S, int max_mpad, const char* unsupported);
+gp_status ssm_launch_update(gp_handle h, const SsmDesc& lay, const char* d_desc, int count, int64_t entries, int maxM, int S,
+                            int max_mpad, const char* unsupported);
 // sample.hip, SGPRSS section: joint posterior draws of every source under the sparse posterior's q(u) (gp_sgpr_sample_source_sparse,
 // gp_sgprb_sample_source_sparse).  The two entries describe their windows on the host — a window's forward state and inputs,
 // and per (window, source) the kernel and the plan's Z feature table (nullptr: the plan keeps none for this kernel) — check

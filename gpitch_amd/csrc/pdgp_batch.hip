@@ -14,6 +14,7 @@
 // Every reduction is one thread's sequential loop or a fixed tree: two runs give bit-identical results.
 #include "common.h"
 #include "gh_quad.h"
+#include "sps_tile.h"
 #include <algorithm>
 
 #define PB_THREADS 256
@@ -676,12 +677,7 @@ __device__ __forceinline__ void pb_pred_products(const double* __restrict__ Gt, 
 
 // the latent GP of entry b: the last g with tile_start[g] <= b (tile_start ascending, G + 1 entries)
 __device__ __forceinline__ int pb_entry_gp(const int64_t* __restrict__ tile_start, int G, int64_t b) {
-  int lo = 0, hi = G;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_start[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
+  return gp_entry_owner(tile_start, G, b);
 }
 
 // LDS: [maxMp x PB_PT Kuf tile | PB_PT frames | maxMp z | maxMp q_mu]; eight wavefronts, two workgroups per CU
@@ -791,6 +787,110 @@ __global__ void __launch_bounds__(PB_MOM_THREADS) pdgpb_pred_moments_kernel(cons
                       smean ? smean + pg.src_off : nullptr, svar ? svar + pg.src_off : nullptr, pg.n, n,
                       ymean ? ymean + f : nullptr, yvar ? yvar + f : nullptr, logp ? logp + f : nullptr, sm);
     __syncthreads();                                     // lane 0 has read the frame's LDS before the next pass writes it
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// joint posterior draws of many models (gp_pdgpb_sample): the state-space core of sample.hip over every latent GP of every
+// model with frames (a process each, with its own frame count), and between its prior walk and its update the inducing
+// side of all of them in ONE launch, from the G^T blocks pdgpb_pred_prep_kernel left:
+//   u0 = prior(z) + sqrt(jitter) eps_u[0];  rhs = q_mu + tril(q_sqrt) eps_u[1] - W u0;  beta = W^T rhs      (whitened)
+// One record per sampled latent GP, in process order.
+struct PbSmpGp {
+  const double* Gt;                       // the GP's prepared block: W[i][k] = Gt[k 2 Mp + i]
+  const double* eps_u;                    // [S][2][M]
+  const double* q_mu; const double* q_sqrt;
+  const double* pz;                       // prior(z): [M][S]
+  double* beta;                           // [M][S]
+  const double* lat_g; const double* lat_f;   // activation rows: the draws of g_i and of f_i, [S][n] each
+  double* src;                            // activation rows when sources are wanted: nlin(g_i) f_i, [S][n]; else null
+  int64_t n;
+  int M, nlin;
+};
+#define PB_SMP_DRAWS 16                   // draws per workgroup of the inducing kernel
+__host__ __device__ inline int64_t pb_smp_tri(int M) { return (int64_t)M * (M + 1) / 2; }
+static size_t pb_smp_lds(int maxM) { return (size_t)(pb_smp_tri(maxM) + 2 * (int64_t)maxM * PB_SMP_DRAWS) * sizeof(double); }
+
+// One workgroup per (latent GP, block of PB_SMP_DRAWS draws).  LDS: the lower triangle of W packed by rows (W[i][k] at
+// i (i + 1) / 2 + k: 66 KiB at M = 128, and rows i .. i + 3, which a wavefront reads together, start i + 1, i + 2, .. doubles
+// apart, on different banks) | u0 [M][16] | eps_u[1], then rhs [M][16].  A thread owns draw tid % 16 and the rows
+// tid / 16 + 16 p: the 16 lanes of a row read one W entry (a broadcast) and 16 consecutive doubles of u0 / rhs.  Every sum is one
+// thread's loop in ascending index, so a draw depends on its own eps alone: not on S, not on its block, not on the launch.
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_sample_inducing_kernel(const PbSmpGp* __restrict__ recs, int S, double sqrt_jitter,
+                                                                           int maxM) {
+  extern __shared__ double pb_sm[];
+  const PbSmpGp g = recs[blockIdx.x];
+  const int M = g.M, Mp = pb_pad16(M), tid = threadIdx.x;
+  constexpr int DB = PB_SMP_DRAWS;
+  double* Wl = pb_sm;
+  double* u0 = Wl + pb_smp_tri(maxM);
+  double* rh = u0 + (int64_t)maxM * DB;
+  const int s0 = blockIdx.y * DB;
+  for (int e = tid; e < M * Mp; e += PB_THREADS) {
+    const int k = e / Mp, i = e % Mp;
+    if (i < M && i >= k) Wl[pb_smp_tri(i) + k] = g.Gt[(int64_t)k * 2 * Mp + i];
+  }
+  for (int e = tid; e < M * DB; e += PB_THREADS) {
+    const int i = e / DB, s = s0 + e % DB;
+    double u = 0.0, e1 = 0.0;
+    if (s < S) {
+      const double* __restrict__ eu = g.eps_u + (int64_t)s * 2 * M;
+      u = g.pz[(int64_t)i * S + s] + sqrt_jitter * eu[i];
+      e1 = eu[M + i];
+    }
+    u0[e] = u;
+    rh[e] = e1;
+  }
+  __syncthreads();
+  const int sl = tid % DB, row = tid / DB;
+  double tv[PB_MAX_M / (PB_THREADS / DB)];
+#pragma unroll
+  for (int p = 0; p < PB_MAX_M / (PB_THREADS / DB); p++) {
+    const int i = row + (PB_THREADS / DB) * p;
+    tv[p] = 0.0;
+    if (i < M) {
+      const double* __restrict__ lq = g.q_sqrt + (int64_t)i * M;   // row i of q_sqrt: the columns j <= i are tril(q_sqrt)'s
+      const double* wr = Wl + pb_smp_tri(i);
+      double r = g.q_mu[i], a = 0.0;
+      for (int j = 0; j <= i; j++) r = fma(lq[j], rh[j * DB + sl], r);
+      for (int k = 0; k <= i; k++) a = fma(wr[k], u0[k * DB + sl], a);
+      tv[p] = r - a;
+    }
+  }
+  __syncthreads();                                                 // eps_u[1] has been read: rhs takes its place
+#pragma unroll
+  for (int p = 0; p < PB_MAX_M / (PB_THREADS / DB); p++) {
+    const int i = row + (PB_THREADS / DB) * p;
+    if (i < M) rh[i * DB + sl] = tv[p];
+  }
+  __syncthreads();
+  const int s = s0 + sl;
+  for (int k = row; k < M; k += PB_THREADS / DB) {
+    double a = 0.0;
+    for (int i = k; i < M; i++) a = fma(Wl[pb_smp_tri(i) + k], rh[i * DB + sl], a);
+    if (s < S) g.beta[(int64_t)k * S + s] = a;
+  }
+}
+
+// src = nlin_k(g) f over the update's (process, frame tile) entries: the activation rows' entries take their frames of every
+// draw (grid y strides the draws), the others return.  One thread per frame of the update's tile: the entries are laid out by
+// ssm_fill_tiles at the plan's largest M, and every M the batch takes has the 64-frame tile
+#define PB_SMP_TILE 64
+static_assert(sps_tile_frames(PB_MAX_M) == PB_SMP_TILE && sps_tile_frames(1) == PB_SMP_TILE,
+              "pdgpb_sample_source_kernel walks the update's (process, frame tile) entries with one thread per frame");
+__global__ void __launch_bounds__(PB_SMP_TILE) pdgpb_sample_source_kernel(const PbSmpGp* __restrict__ recs, const int64_t* __restrict__ tile_start,
+                                                                 int count, int S) {
+  const int64_t b = blockIdx.x;
+  const int gi = gp_entry_owner(tile_start, count, b);
+  const PbSmpGp g = recs[gi];
+  if (!g.src) return;
+  const int64_t t = (b - tile_start[gi]) * blockDim.x + threadIdx.x;
+  if (t >= g.n) return;
+  for (int s = blockIdx.y; s < S; s += gridDim.y) {
+    const int64_t o = (int64_t)s * g.n + t;
+    double sg, ds;
+    nlin_eval(g.nlin, g.lat_g[o], sg, ds);
+    g.src[o] = sg * g.lat_f[o];
   }
 }
 
@@ -1153,6 +1253,160 @@ gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const 
   hipLaunchKernelGGL(pdgpb_pred_moments_kernel, dim3((unsigned)tiles), dim3(PB_MOM_THREADS), lds, h->stream, p->d_gps, p->d_pgs,
                      p->d_tiles, p->G, params, fm, fv, ynew, smean, svar, ymean, yvar, logp, maxP);
   GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
+}  // extern "C"
+
+// ---- joint posterior draws ------------------------------------------------------------------------------------------
+static inline bool pb_smp_kernel_ok(int t) { return t == GP_KERN_MATERN12 || t == GP_KERN_MATERN32 || t == GP_KERN_MERCER_MATERN12SM; }
+static inline DevKern pb_smp_kern(const PbGp& g, const double* params) { return DevKern{g.type, g.m, params + g.off_theta}; }
+// gp_pdgpb_sample's carve: gp_pdgpb_predict_prepare's regions, then the call's descriptor block, merged orders, feature
+// tables of the frames and of z (spectral-mixture GPs), prior(z) and beta.  Only models with frames are sampled.
+struct PbSmpBufs { char* desc; int* order; double *fx, *fz, *pz, *beta; size_t nproc; };
+static PbSmpBufs pb_smp_carve(const gp_pdgpb_plan_s* p, GpArena& ar, const int64_t* xnew_off, int64_t S) {
+  pb_pred_regions(p, ar);
+  size_t nproc = 0, norder = 0, fx = 0, fz = 0, ms = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int64_t n = xnew_off[k + 1] - xnew_off[k];
+    const PbModel& md = p->models[k];
+    for (int r = 0; r < 2 * md.P; r++) {
+      const PbGp& g = p->gps[md.g0 + r];
+      norder += (size_t)(n > 0 ? n : 0) + g.M;               // every model's orders are uploaded, as the caller lays them out
+      if (n <= 0) continue;
+      const size_t mp = g.type == GP_KERN_MERCER_MATERN12SM ? sm_mpad(g.m) : 0;
+      nproc++;
+      fx += 2 * mp * (size_t)n;
+      fz += 2 * mp * g.M;
+      ms += (size_t)g.M * S;
+    }
+  }
+  PbSmpBufs b;
+  b.nproc = nproc;
+  b.desc = ar.take<char>(ssm_desc_layout(nproc, nproc * sizeof(PbSmpGp), 0).bytes);
+  b.order = ar.take<int>(norder);
+  b.fx = ar.take<double>(fx);
+  b.fz = ar.take<double>(fz);
+  b.pz = ar.take<double>(ms);
+  b.beta = ar.take<double>(ms);
+  return b;
+}
+
+extern "C" {
+
+size_t gp_pdgpb_sample_workspace_bytes(gp_pdgpb_plan p, const int64_t* xnew_off, int32_t S) {
+  if (!p || !p->predict_only || !xnew_off || S < 1) return 0;
+  return gp_measure([&](GpArena& ar) { pb_smp_carve(p, ar, xnew_off, S); }) + GP_WS_TAIL_BATCH;
+}
+
+gp_status gp_pdgpb_sample(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
+                          const int32_t* order_host, int32_t S, const double* eps_x, const double* eps_z, const double* eps_u,
+                          double* latents, double* sources, void* workspace, size_t bytes) {
+  GP_CHECK(pb_pred_check(p, "gp_pdgpb_sample", params, xnew_off, workspace, bytes));
+  gp_handle h = p->h;
+  if (S < 1) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_sample: S >= 1 draws");
+  if (S > 65535 * PB_SMP_DRAWS) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_sample: at most 1048560 draws per call");
+  int64_t frames = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int64_t n = xnew_off[k + 1] - xnew_off[k];
+    if (n < 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_sample: xnew_off must not decrease");
+    if (n + PB_MAX_M > INT32_MAX / 2) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_sample: a model has too many frames");
+    frames += n;
+  }
+  if (!xnew || !order_host || !eps_x || !eps_z || !eps_u || !latents)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_sample: bad argument (no null pointers but sources)");
+  for (const PbGp& g : p->gps)
+    if (!pb_smp_kernel_ok(g.type))
+      return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_sample: every latent GP needs a kernel with an exact state-space prior sampler "
+                                            "that the batch takes (Matern12, Matern32, MercerMatern12sm)");
+  if (bytes < gp_pdgpb_sample_workspace_bytes(p, xnew_off, S))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_sample: the workspace does not hold this call's buffers (gp_pdgpb_sample_workspace_bytes)");
+  GpArena ar(workspace, bytes);
+  const PbSmpBufs b = pb_smp_carve(p, ar, xnew_off, S);
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_sample: arena overflow");
+  if (b.nproc > 32767) return gp_fail(h, GP_ERR_UNSUPPORTED, "gp_pdgpb_sample: at most 32767 latent GPs with frames per call");
+  std::vector<SsmSpan> spans;                 // every latent GP's n_k + M_r entries back to back, empty models included
+  size_t norder = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int64_t n = xnew_off[k + 1] - xnew_off[k];
+    for (int r = 0; r < 2 * p->models[k].P; r++) {
+      const int len = (int)n + p->gps[p->models[k].g0 + r].M;
+      spans.push_back(SsmSpan{norder, len});
+      norder += len;
+    }
+  }
+  GP_CHECK(ssm_check_orders(h, order_host, spans, "gp_pdgpb_sample: order is not a permutation of a latent GP's n + M points"));
+  if (frames == 0) return GP_OK;
+
+  const int count = (int)b.nproc;
+  const SsmDesc lay = ssm_desc_layout(b.nproc, b.nproc * sizeof(PbSmpGp), 0);
+  std::vector<char> hd(lay.bytes, 0);
+  SsmProc* procs = (SsmProc*)(hd.data() + lay.procs);
+  PbSmpGp* recs = (PbSmpGp*)(hd.data() + lay.recs);
+  FeatItem* feats = (FeatItem*)(hd.data() + lay.feat);
+  int nfeat = 0, at = 0, max_mpad = 0, max_n = p->maxM;
+  size_t off_x = 0, off_z = 0, off_u = 0, off_o = 0, off_lat = 0, off_src = 0, off_fx = 0, off_fz = 0, off_ms = 0;
+  for (int k = 0; k < p->nm; k++) {
+    const int64_t n = xnew_off[k + 1] - xnew_off[k];
+    const PbModel& md = p->models[k];
+    for (int r = 0; r < 2 * md.P; r++) {
+      const PbGp& g = p->gps[md.g0 + r];
+      const DevKern kern = pb_smp_kern(g, params);
+      const int c = ssm_components(g.type, g.m), M = g.M, mp = ssm_mpad(kern);
+      if (n > 0) {
+        SsmProc& it = procs[at];
+        it.k = kern; it.z = params + g.off_z; it.xnew = xnew + xnew_off[k];
+        if (mp) {
+          double* tx = b.fx + off_fx;
+          double* tz = b.fz + off_fz;
+          feats[nfeat++] = FeatItem{kern, it.xnew, tx, (int)n, 0};
+          feats[nfeat++] = FeatItem{kern, it.z, tz, M, 0};
+          it.fx = tx; it.fz = tz;
+          off_fx += 2 * (size_t)mp * n; off_fz += 2 * (size_t)mp * M;
+        }
+        it.order = b.order + off_o;
+        it.eps_x = eps_x + off_x; it.eps_z = eps_z + off_z;
+        it.beta = b.beta + off_ms;
+        it.out = latents + off_lat + (size_t)r * S * n;
+        it.pz = b.pz + off_ms;
+        it.n = (int)n; it.kz = M; it.mp = mp; it.cs = c; it.ezs = M;
+        PbSmpGp& rc = recs[at];
+        rc.Gt = p->d_G + g.ws; rc.eps_u = eps_u + off_u;
+        rc.q_mu = params + g.off_qmu; rc.q_sqrt = params + g.off_qsq;
+        rc.pz = it.pz; rc.beta = b.beta + off_ms;
+        rc.n = n; rc.M = M; rc.nlin = md.nlin;
+        if (r < md.P) {
+          rc.lat_g = it.out;
+          rc.lat_f = latents + off_lat + (size_t)(md.P + r) * S * n;
+          rc.src = sources ? sources + off_src + (size_t)r * S * n : nullptr;
+        }
+        off_ms += (size_t)M * S;
+        if (mp > max_mpad) max_mpad = mp;
+        if (n > max_n) max_n = (int)n;
+        at++;
+      }
+      off_x += (size_t)S * c * n; off_z += (size_t)S * c * M; off_u += (size_t)S * 2 * M; off_o += (size_t)n + M;
+    }
+    off_lat += 2 * (size_t)md.P * S * n;
+    off_src += (size_t)md.P * S * n;
+  }
+  static const char* const PARTIALS = "gp_pdgpb_sample: num_partials must be in [1, 32]";
+  const int64_t entries = ssm_fill_tiles(lay, hd, count, p->maxM);
+  GP_CHECK(ssm_upload(h, lay, hd, b.desc, nfeat, order_host, b.order, norder, max_n));
+  // (process, draw) pairs packed densely into wavefronts were measured and lost to this grid: DESIGN 3h
+  GP_CHECK(ssm_launch_prior(h, (const SsmProc*)(b.desc + lay.procs), count, S, max_mpad, PARTIALS));
+  const PbSmpGp* d_recs = (const PbSmpGp*)(b.desc + lay.recs);
+  GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_sample_inducing_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)pb_smp_lds(p->maxM)));
+  hipLaunchKernelGGL(pdgpb_sample_inducing_kernel, dim3(count, (S + PB_SMP_DRAWS - 1) / PB_SMP_DRAWS), dim3(PB_THREADS),
+                     pb_smp_lds(p->maxM), h->stream, d_recs, S, sqrt(p->jitter), p->maxM);
+  GP_HIP_CHECK(h, hipGetLastError());
+  GP_CHECK(ssm_launch_update(h, lay, b.desc, count, entries, p->maxM, S, max_mpad, PARTIALS));
+  if (sources) {
+    hipLaunchKernelGGL(pdgpb_sample_source_kernel, dim3((unsigned)entries, std::min(S, 64)), dim3(PB_SMP_TILE), 0, h->stream, d_recs,
+                       (const int64_t*)(b.desc + lay.tiles), count, S);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
   return GP_OK;
 }
 

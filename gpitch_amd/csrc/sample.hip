@@ -21,8 +21,8 @@
 //          At D = 0 the transition is the identity and Q = 0 exactly.
 //      prior(x*) goes to the output, prior(z) to the workspace.
 //   2. inducing side: the operator's own u0 kernel and batched small GEMMs leave beta [kz][S] (below)
-//   3. update   draw(x*) = prior(x*) + K(x*, z) beta   (ssm_update_kernel: the K(Z, tile) build of the sparse predictor in
-//      LDS (sps_tile.h), then the float64 MFMA)
+//   3. update   draw(x*) = prior(x*) + K(x*, z) beta   (ssm_update_kernel, one workgroup per (process, frame tile) entry:
+//      the K(Z, tile) build of the sparse predictor in LDS (sps_tile.h), then the float64 MFMA)
 // The map is affine in eps and its linear part T has T T^T = the joint posterior covariance under q.
 //
 // SGPRSS (sgpr_sample_*): a process is a (source, window) pair.  State: W = L^-1, WB = LB^-1 and c of the plan's forward
@@ -42,6 +42,9 @@
 //   4. sources  src_i = nlin(draw_i) * draw_{P + i}                      (pdgp_sample_source_kernel)
 //   eps layout: the GPs' blocks back to back, GP r's being eps_x [S][c_r][n], eps_z [S][c_r][M_r], eps_u [S][2][M_r], in the
 //   caller's own point order.
+// Many Pdgp models (pdgp_batch.hip, gp_pdgpb_sample): every latent GP of every model with frames is a process of this core with
+//   its own frame count (SsmProc::n); the update's grid is the list of (process, frame tile) entries, so ragged models share
+//   its launch.  Steps 2 and 4 are that file's own kernels, on the G^T blocks its predict-only plan prepared.
 // Determinism: no atomics; every sum has a fixed order; draw s depends on nothing but its own eps (a thread owns a draw in
 // step 1 and in Pdgp's u0 kernel, a GEMM / MFMA column in steps 2 and 3), so it is bit-identical whatever S and whatever
 // else shares the launch.
@@ -57,23 +60,11 @@
 // ==== core: the state-space sampler of one process =======================================================================
 typedef double ssm_d4 __attribute__((ext_vector_type(4)));
 
-// one per sampled process: everything the prior and update kernels read
-struct SsmProc {
-  DevKern k;
-  const double* z; const double* xnew;
-  const double* fz; const double* fx;     // sqrt(e) cos / sin tables of z ([2 mp][kz]) and of xnew ([2 mp][n]); SM kernels only
-  const int* order;                       // the process's merged order, n + kz entries (validated on the host)
-  const double* eps_x; const double* eps_z;   // draw 0 of this process's component block: [S][cs][n] and [S][cs][ezs]
-  const double* beta;                     // [kz][S]
-  double* out;                            // [S][n]
-  double* pz;                             // prior(z): [kz][S]
-  int kz, mp;                             // mp: sm_mpad(m) of an SM kernel, else 0
-  int cs, ezs;                            // components between two draws; points between two components of eps_z
-};
+// (SsmProc, one per sampled process, is in common.h: pdgp_batch.hip builds the same records)
 
 __host__ __device__ static inline bool ssm_kernel_sm(int type) { return type == GP_KERN_MERCER_MATERN12SM || type == GP_KERN_MATERN12SM; }
-static inline int ssm_components(int type, int m) { return type == GP_KERN_MATERN12 ? 1 : (type == GP_KERN_MATERN32 ? 2 : 2 * m); }
-static inline int ssm_mpad(DevKern k) { return ssm_kernel_sm(k.type) ? sm_mpad(k.m) : 0; }
+int ssm_components(int type, int m) { return type == GP_KERN_MATERN12 ? 1 : (type == GP_KERN_MATERN32 ? 2 : 2 * m); }
+int ssm_mpad(DevKern k) { return ssm_kernel_sm(k.type) ? sm_mpad(k.m) : 0; }
 
 // g(x) = 1 - exp(-x)(1 + x + x^2 / 2) for x >= 0, e2 = exp(-x).  Below x = 1: exp(-x) x^3 / 6 (1 + x/4 (1 + x/5 (... (1 + x/20))))
 // (the tail beyond k = 20 is below 3e-18 of the sum); from 1 on the closed form loses at most four bits.
@@ -90,8 +81,8 @@ __device__ __forceinline__ double psm_m32_g(double x, double e2) {
 // (the walk is compiled once per family, M32 = the two-state step or not: one loop that held both kept the Matern-3/2
 // step's registers live across the partials' and cost the Matern-1/2 families a wavefront of occupancy at MPAD 4)
 template <int MPAD, bool M32>
-__device__ __forceinline__ void ssm_prior_walk(const SsmProc& it, int n, int S, int s) {
-  const int m = it.k.m, kz = it.kz;
+__device__ __forceinline__ void ssm_prior_walk(const SsmProc& it, int S, int s) {
+  const int m = it.k.m, kz = it.kz, n = it.n;
   const bool sm = ssm_kernel_sm(it.k.type);
   const double var = it.k.theta[0], ls = it.k.theta[1];
   const double sv = sqrt(var);
@@ -162,12 +153,12 @@ __device__ __forceinline__ void ssm_prior_walk(const SsmProc& it, int n, int S, 
   }
 }
 template <int MPAD>
-__global__ void __launch_bounds__(64) ssm_prior_kernel(const SsmProc* __restrict__ procs, int n, int S) {
+__global__ void __launch_bounds__(64) ssm_prior_kernel(const SsmProc* __restrict__ procs, int S) {
   const SsmProc it = procs[blockIdx.y];
   const int s = blockIdx.x * 64 + threadIdx.x;
   if (s >= S) return;
-  if (it.k.type == GP_KERN_MATERN32) ssm_prior_walk<MPAD, true>(it, n, S, s);
-  else ssm_prior_walk<MPAD, false>(it, n, S, s);
+  if (it.k.type == GP_KERN_MATERN32) ssm_prior_walk<MPAD, true>(it, S, s);
+  else ssm_prior_walk<MPAD, false>(it, S, s);
 }
 
 // ---- 3. out[s][frame] += sum_i K(z_i, x*_frame) beta[i][s]: one workgroup per (frame tile, process) -------------------------
@@ -176,14 +167,19 @@ __global__ void __launch_bounds__(64) ssm_prior_kernel(const SsmProc* __restrict
 // B[k][j = frame] = the tile in LDS (the sparse predictor's own read pattern), D[draw = kq + 4 r][frame = lc].  S is padded
 // to 16 here only: pad columns of beta are not read and pad draws not written.  T and the tile's stride come from the largest
 // M of the launch; a process with fewer inducing inputs fills the first kz rows (rounded up to 16) of each frame's column.
+// The grid is the list of (process, frame tile) entries, process-major: tile_start[p] is process p's first entry (count + 1
+// items), so processes with different frame counts share the launch without a rectangle over the longest.
 template <int MPAD>
-__global__ void __launch_bounds__(256) ssm_update_kernel(const SsmProc* __restrict__ procs, int n, int S_draws, int T, int S) {
+__global__ void __launch_bounds__(256) ssm_update_kernel(const SsmProc* __restrict__ procs, const int64_t* __restrict__ tile_start,
+                                                         int count, int S_draws, int T, int S) {
   extern __shared__ double ssm_lds[];
   const SpsLds lds = sps_lds_carve<MPAD>(ssm_lds);
-  const SsmProc it = procs[blockIdx.y];
+  const int64_t b = blockIdx.x;
+  const int pi = gp_entry_owner(tile_start, count, b);
+  const SsmProc it = procs[pi];
   const int tid = threadIdx.x;
-  const int kz = it.kz, Mp = (kz + 15) & ~15;
-  const int j0 = blockIdx.x * T;
+  const int kz = it.kz, Mp = (kz + 15) & ~15, n = it.n;
+  const int j0 = (int)(b - tile_start[pi]) * T;
   sps_build_tile<MPAD>(lds, it.k, it.z, it.fz, kz, it.xnew, n, j0, T, S);
 
   const int lane = tid & 63, wave = tid >> 6, lc = lane & 15, kq = lane >> 4;
@@ -214,31 +210,44 @@ __global__ void __launch_bounds__(256) ssm_update_kernel(const SsmProc* __restri
 
 // ---- core, host side ------------------------------------------------------------------------------------------------------
 // d_procs: count <= 32767 processes, none with more than maxM inducing inputs; max_mpad: the largest mp among them
-static gp_status ssm_launch_prior(gp_handle h, const SsmProc* d_procs, int count, int n, int S, int max_mpad, const char* unsupported) {
+gp_status ssm_launch_prior(gp_handle h, const SsmProc* d_procs, int count, int S, int max_mpad, const char* unsupported) {
   return sps_dispatch_mpad(h, max_mpad, unsupported, [&](auto mpad) -> gp_status {
-    hipLaunchKernelGGL((ssm_prior_kernel<decltype(mpad)::value>), dim3((S + 63) / 64, count), dim3(64), 0, h->stream, d_procs, n, S);
+    hipLaunchKernelGGL((ssm_prior_kernel<decltype(mpad)::value>), dim3((S + 63) / 64, count), dim3(64), 0, h->stream, d_procs, S);
     GP_HIP_CHECK(h, hipGetLastError());
     return GP_OK;
   });
 }
-static gp_status ssm_launch_update(gp_handle h, const SsmProc* d_procs, int count, int maxM, int n, int S, int max_mpad,
-                                   const char* unsupported) {
+int64_t ssm_fill_tiles(const SsmDesc& lay, std::vector<char>& hd, int count, int maxM) {
+  const SsmProc* procs = (const SsmProc*)(hd.data() + lay.procs);
+  int64_t* tiles = (int64_t*)(hd.data() + lay.tiles);
+  const int T = sps_tile_frames(maxM);
+  int64_t at = 0;
+  for (int r = 0; r < count; r++) {
+    tiles[r] = at;
+    at += (procs[r].n + T - 1) / T;
+  }
+  tiles[count] = at;
+  return at;
+}
+gp_status ssm_launch_update(gp_handle h, const SsmDesc& lay, const char* d_desc, int count, int64_t entries, int maxM, int S,
+                            int max_mpad, const char* unsupported) {
+  if (entries <= 0) return GP_OK;
+  if (entries > 0x7fffffff) return gp_fail(h, GP_ERR_UNSUPPORTED, "sampling: more than 2^31 - 1 frame tiles in one call");
   GpTimerScope ts(h, GP_TIMER_COND_A);
   return sps_dispatch_mpad(h, max_mpad, unsupported, [&](auto mpad) -> gp_status {
     const int T = sps_tile_frames(maxM);
     const size_t lds = sps_lds_bytes(maxM, decltype(mpad)::value);
     GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)ssm_update_kernel<decltype(mpad)::value>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lds));
-    hipLaunchKernelGGL((ssm_update_kernel<decltype(mpad)::value>), dim3((n + T - 1) / T, count), dim3(4 * T), lds, h->stream, d_procs, n, S,
-                       T, sps_stride(maxM));
+    hipLaunchKernelGGL((ssm_update_kernel<decltype(mpad)::value>), dim3((unsigned)entries), dim3(4 * T), lds, h->stream,
+                       (const SsmProc*)(d_desc + lay.procs), (const int64_t*)(d_desc + lay.tiles), count, S, T, sps_stride(maxM));
     GP_HIP_CHECK(h, hipGetLastError());
     return GP_OK;
   });
 }
 
 // `order` becomes device addresses: every span's entries must be a permutation of 0..len-1
-struct SsmSpan { size_t off; int len; };
-static gp_status ssm_check_orders(gp_handle h, const int32_t* order_host, const std::vector<SsmSpan>& spans, const char* not_a_permutation) {
+gp_status ssm_check_orders(gp_handle h, const int32_t* order_host, const std::vector<SsmSpan>& spans, const char* not_a_permutation) {
   std::vector<char> seen;
   for (const SsmSpan& sp : spans) {
     const int32_t* o = order_host + sp.off;
@@ -251,21 +260,21 @@ static gp_status ssm_check_orders(gp_handle h, const int32_t* order_host, const 
   return GP_OK;
 }
 
-// A call's descriptor block: procs | the operator's u0 records | feature items (at most two per process) | GEMM problems
-struct SsmDesc { size_t procs, recs, feat, probs, bytes; };
-static SsmDesc ssm_desc_layout(size_t nproc, size_t rec_bytes, size_t nprob) {
+// A call's descriptor block (SsmDesc, common.h)
+SsmDesc ssm_desc_layout(size_t nproc, size_t rec_bytes, size_t nprob) {
   SsmDesc o;
   GpRegions region;
   o.procs = region(nproc * sizeof(SsmProc));
   o.recs = region(rec_bytes);
   o.feat = region(2 * nproc * sizeof(FeatItem));
   o.probs = region(nprob * sizeof(GemmProblem));
+  o.tiles = region((nproc + 1) * sizeof(int64_t));
   o.bytes = region.off;
   return o;
 }
 // Uploads the block (hd: its host copy, the first nfeat feature items filled in any order) and `order`, then builds the feature
 // tables: the items are grouped by table padding, one launch of the shared feature kernel per distinct sm_mpad.
-static gp_status ssm_upload(gp_handle h, const SsmDesc& lay, std::vector<char>& hd, char* d_desc, int nfeat, const int32_t* order_host,
+gp_status ssm_upload(gp_handle h, const SsmDesc& lay, std::vector<char>& hd, char* d_desc, int nfeat, const int32_t* order_host,
                             int* d_order, size_t norder, int max_n) {
   FeatItem* feats = (FeatItem*)(hd.data() + lay.feat);
   std::stable_sort(feats, feats + nfeat, [](const FeatItem& a, const FeatItem& b) { return sm_mpad(a.k.m) < sm_mpad(b.k.m); });
@@ -410,7 +419,7 @@ gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* sr
       it.beta = u0;
       it.out = out + ((size_t)w * P + i) * S * n;
       it.pz = b.pz + ((size_t)w * P + i) * M * S;
-      it.kz = sw.kz; it.mp = mpad[i]; it.cs = C; it.ezs = M;
+      it.n = n; it.kz = sw.kz; it.mp = mpad[i]; it.cs = C; it.ezs = M;
     }
     // t1 = W u0;  t1 = WB^T rhs - t1;  beta (over u0) = W^T t1     — [kz][S] row-major, the slot's own kz-point problem
     GemmProblem g;
@@ -420,10 +429,11 @@ gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* sr
     g.A = sw.WB; g.B = rhs; g.C = t1; probs[1 * (size_t)count + w] = g;
     g.A = sw.W; g.B = t1; g.C = u0; probs[2 * (size_t)count + w] = g;
   }
+  const int64_t entries = ssm_fill_tiles(lay, hd, P * count, M);
   GP_CHECK(ssm_upload(h, lay, hd, b.desc, nfeat, order_host, b.order, (size_t)count * (n + M), n > M ? n : M));
   const SsmProc* d_procs = (const SsmProc*)(b.desc + lay.procs);
   const GemmProblem* d_probs = (const GemmProblem*)(b.desc + lay.probs);
-  GP_CHECK(ssm_launch_prior(h, d_procs, P * count, n, S, max_mpad, SMP_PARTIALS));
+  GP_CHECK(ssm_launch_prior(h, d_procs, P * count, S, max_mpad, SMP_PARTIALS));
   hipLaunchKernelGGL(sgpr_sample_u0_kernel, dim3((unsigned)(((size_t)M * S + 255) / 256), count), dim3(256), 0, h->stream, d_procs,
                      (const SmpU0*)(b.desc + lay.recs), count, P, M, S, sqrt(jitter));
   GP_HIP_CHECK(h, hipGetLastError());
@@ -433,7 +443,7 @@ gp_status sgpr_sample_run(gp_handle h, const SmpWindow* win, const SmpSource* sr
     GP_CHECK(launch_gemm_batched(h, d_probs + count, count, M, S, f)); }
   { GemmFlags f; f.transA = 1; f.triA = TRI_UPPER;
     GP_CHECK(launch_gemm_batched(h, d_probs + 2 * (size_t)count, count, M, S, f)); }
-  return ssm_launch_update(h, d_procs, P * count, M, n, S, max_mpad, SMP_PARTIALS);
+  return ssm_launch_update(h, lay, b.desc, P * count, entries, M, S, max_mpad, SMP_PARTIALS);
 }
 
 // ==== Pdgp ===================================================================================================================
@@ -568,7 +578,7 @@ gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int
     it.beta = t1;
     it.out = latents + (size_t)r * S * n;               // row block r of `latents`
     it.pz = b.pz + (size_t)r * maxM * S;
-    it.kz = M; it.mp = mp; it.cs = c; it.ezs = M;
+    it.n = n; it.kz = M; it.mp = mp; it.cs = c; it.ezs = M;
     off_x += (size_t)S * c * n; off_z += (size_t)S * c * M; off_u += (size_t)S * 2 * M; off_o += (size_t)n + M;
     frow += 2 * (size_t)mp;
     // [M][S] row-major.  whitened: rhs <- rhs - W u0, beta = W^T rhs;  unwhitened (rhs holds q - u0): u0 <- W rhs, beta = W^T u0
@@ -578,10 +588,11 @@ gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int
     p.B = whiten ? u0 : rhs; p.C = whiten ? rhs : u0; probs[r] = p;
     p.B = whiten ? rhs : u0; p.C = t1; probs[(size_t)G + r] = p;
   }
+  const int64_t entries = ssm_fill_tiles(lay, hd, G, maxM);
   GP_CHECK(ssm_upload(h, lay, hd, b.desc, nfeat, order_host, b.order, off_o, n > maxM ? n : maxM));
   const SsmProc* d_procs = (const SsmProc*)(b.desc + lay.procs);
   const GemmProblem* d_probs = (const GemmProblem*)(b.desc + lay.probs);
-  GP_CHECK(ssm_launch_prior(h, d_procs, G, n, S, max_mpad, PSM_PARTIALS));
+  GP_CHECK(ssm_launch_prior(h, d_procs, G, S, max_mpad, PSM_PARTIALS));
   hipLaunchKernelGGL(pdgp_sample_u0_kernel, dim3((unsigned)(((size_t)maxM * S + 255) / 256), G), dim3(256), 0, h->stream, d_procs,
                      (const PsmU0*)(b.desc + lay.recs), S, sqrt(jitter), whiten ? 1 : 0);
   GP_HIP_CHECK(h, hipGetLastError());
@@ -590,7 +601,7 @@ gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int
     GP_CHECK(launch_gemm_batched(h, d_probs, G, maxM, S, f)); }
   { GemmFlags f; f.transA = 1; f.triA = TRI_UPPER;
     GP_CHECK(launch_gemm_batched(h, d_probs + G, G, maxM, S, f)); }
-  GP_CHECK(ssm_launch_update(h, d_procs, G, maxM, n, S, max_mpad, PSM_PARTIALS));
+  GP_CHECK(ssm_launch_update(h, lay, b.desc, G, entries, maxM, S, max_mpad, PSM_PARTIALS));
   if (sources) {
     const size_t count = (size_t)P * S * n;
     hipLaunchKernelGGL(pdgp_sample_source_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, latents, sources,

@@ -13,7 +13,7 @@
 #define SPS_CHUNK 32      // rows of Z staged per pass of the tile build
 
 // frames per workgroup, from the plan's M: the M x T tile (plus 4 pad doubles per frame) stays inside the 160 KiB of LDS
-static inline int sps_tile_frames(int M) { return M <= 256 ? 64 : (M <= 512 ? 32 : 16); }
+static constexpr int sps_tile_frames(int M) { return M <= 256 ? 64 : (M <= 512 ? 32 : 16); }
 static inline int sps_stride(int M) { return ((M + 15) & ~15) + 4; }       // doubles per frame of the tile (4 x odd: see the reads)
 static inline size_t sps_lds_bytes(int M, int mpad) {
   const int T = sps_tile_frames(M), S = sps_stride(M);

@@ -14,6 +14,11 @@ everything else is refused by check_batchable() before any device work.
 replaces  [m.predict_act_n_com(x) for m, x in zip(models, xnews)]  with one factorisation launch for every latent GP and
 one launch for every (latent GP, frame tile) pair, without building any single-model engine plan (check_predictable()
 takes the same models, without the minibatch limit).
+
+    draws = sample_sources_many(models, xnews, num_samples=16, seed=0)
+
+replaces  [m.sample_sources(x, 16) for m, x in zip(models, xnews)]  — joint posterior draws of every source of every model
+(csrc/pdgp_batch.hip gp_pdgpb_sample over the state-space core of csrc/sample.hip; check_sampleable()).
 """
 import contextlib
 import ctypes as C
@@ -25,6 +30,7 @@ from .flatvec import col, free_index, latent_gps  # noqa: F401  (free_index: par
 from .methods import nlin_code
 from .param import draw_in_lockstep
 from .pdgp import Pdgp, jitter
+from .sgpr_ss import _KERN_NAMES, _sample_generator, merged_order
 from .train import AdamOptimizer, OptimizeResult
 
 MAX_M = 128            # inducing points per latent GP (one factor of 128 x 128 float64 in a workgroup's LDS)
@@ -562,3 +568,260 @@ def predict_sources_many(models, xnews, ynews=None):
             item[name] = item[name].reshape(-1, 1)
         res.append(item)
     return res
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# joint posterior draws of the sources of many models (csrc/pdgp_batch.hip gp_pdgpb_sample)
+MAX_SAMPLE_BYTES = 1 << 30     # device bytes of one gp_pdgpb_sample call's normals and draws (beside sgpr_ss.SAMPLE_EPS_BYTES)
+SAMPLE_DRAW_BLOCK = 16         # draws per block of a model's seeded stream; draw chunks are whole blocks
+MAX_SAMPLE_GPS = 32767         # latent GPs per gp_pdgpb_sample call
+_SINGLE_SAMPLE = "sample this model on its own with Pdgp.sample_sources"
+_SAMPLERS = {_lib.KERN_MATERN12: 1, _lib.KERN_MATERN32: 2, _lib.KERN_MERCER_MATERN12SM: 0}   # normals per point (0: 2 m)
+
+
+def _sample_comps(m, k):
+    """normals per point of model k's latent GPs, rows [g_0..g_{P-1}, f_0..f_{P-1}]; NotImplementedError, naming model, role,
+    GP and kernel, for a batched kernel without an exact state-space prior sampler"""
+    comps = []
+    for role, kerns in (("activation", m.kern_act), ("component", m.kern_com)):
+        for i in range(m.num_sources):
+            code = int(kerns[i].type_code)
+            if code not in _SAMPLERS:
+                raise NotImplementedError(
+                    "sample_sources_many: model %d: the %s GP %d has kernel %s; joint draws need an exact state-space prior "
+                    "sampler (supported: %s)" % (k, role, i, _KERN_NAMES.get(code, "type %d" % code),
+                                                 ", ".join(_KERN_NAMES[c] for c in sorted(_SAMPLERS))))
+            comps.append(_SAMPLERS[code] or 2 * int(kerns[i].num_partials))
+    return comps
+
+
+def check_sampleable(models, xnews):
+    """Host-only scope check of sample_sources_many, in the style of check_predictable: everything that one refuses, and every
+    latent GP needs a kernel that both the batch and the state-space sampler take (Matern12, Matern32, MercerMatern12sm).
+    NotImplementedError names the model, the GP's role and index and its kernel (Matern52, RBF, Matern32sm: batched, no
+    sampler) or Pdgp.sample_sources as the single-model path (Matern12sm: sampled, not batched).  No device work.  Returns
+    the models and their inputs as flat float64 arrays."""
+    models = _check_models(models, "sample_sources_many", _SINGLE_SAMPLE, minibatch=False)
+    for k, m in enumerate(models):
+        _sample_comps(m, k)
+    if isinstance(xnews, (list, tuple)):
+        if len(xnews) != len(models):
+            raise ValueError("sample_sources_many: %d input arrays for %d models" % (len(xnews), len(models)))
+        xs = [_sample_frames(x, k) for k, x in enumerate(xnews)]
+    else:
+        xs = [_sample_frames(xnews, 0)] * len(models)
+    return models, xs
+
+
+def _sample_frames(x, k):
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 1):
+        raise ValueError("sample_sources_many: inputs of model %d have shape %r, not (n,) or (n, 1)" % (k, a.shape))
+    return a.reshape(-1)
+
+
+def sample_layout(num_sources, counts, Ms, comps):
+    """Offsets of one gp_pdgpb_sample call at ONE draw, host only (include/gpitch_abi.h).  num_sources, counts: per model
+    P_k and n_k; Ms, comps: per latent GP (models in order, rows [g_0..g_{P-1}, f_0..f_{P-1}]) M_r and its normals per point
+    c_r.  Returns a dict of int64 arrays, each ending with its total:
+      order [G + 1]                  each GP's first entry of order_host (n_k + M_r entries; does not grow with the draws)
+      eps_x, eps_z, eps_u [G + 1]    each GP's first double per draw: c_r n_k, c_r M_r, 2 M_r per draw (S draws: times S)
+      latents, sources [num_models + 1]   each model's first double per draw: 2 P_k n_k and P_k n_k (S draws: times S)
+      x_off [num_models + 1]         the call's xnew_off"""
+    P = np.asarray(num_sources, dtype=np.int64)
+    n = np.asarray(counts, dtype=np.int64)
+    M = np.asarray(Ms, dtype=np.int64)
+    c = np.asarray(comps, dtype=np.int64)
+    assert P.shape == n.shape and M.shape == c.shape and M.size == 2 * P.sum() and np.all(n >= 0)
+    cum = lambda a: np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
+    owner = np.repeat(np.arange(P.size), 2 * P)
+    ng = n[owner]
+    return dict(order=cum(ng + M), eps_x=cum(c * ng), eps_z=cum(c * M), eps_u=cum(2 * M),
+                latents=cum(2 * P * n), sources=cum(P * n), x_off=cum(n))
+
+
+def sample_bytes_per_draw(models, xs):
+    """device bytes of ONE draw of each model at its inputs xs[k] (flat arrays): its normals (eps_x, eps_z, eps_u) and its
+    draws (2 P latent rows and P source rows of n_k frames) — what sample_split weighs against the budget"""
+    out = []
+    for m, x in zip(models, xs):
+        shapes = m.sample_eps_shapes(x.size, 1)
+        out.append(8 * (sum(int(np.prod(sh)) for part in shapes for sh in part) + 3 * m.num_sources * x.size))
+    return out
+
+
+def sample_split(per_draw, gps, num_samples, budget, block=SAMPLE_DRAW_BLOCK, max_gps=MAX_SAMPLE_GPS):
+    """The calls of one sample_sources_many: [(first model, end model, [(first draw, draws), ...])], host only.  per_draw:
+    device bytes of one draw of each model (normals and draws); gps: its latent GPs.  A joint draw cannot be cut along
+    frames, so the models are cut first: consecutive models share a group while one block of min(num_samples, block) draws of
+    all of them stays within `budget` bytes and their latent GPs within max_gps; a model too large for that goes alone.
+    Each group's draws then go in chunks of whole blocks, as many as the budget holds (at least one): chunk borders are
+    multiples of `block`, the unit of the seeded streams.  Every (model, draw) is covered once, in order."""
+    S, nb = int(num_samples), min(int(num_samples), block)
+    groups, k0, used, ng = [], 0, 0, 0
+    for k, (b, g) in enumerate(zip(per_draw, gps)):
+        if k > k0 and ((used + int(b)) * nb > budget or ng + g > max_gps):
+            groups.append((k0, k, used))
+            k0, used, ng = k, 0, 0
+        used, ng = used + int(b), ng + g
+    groups.append((k0, len(per_draw), used))
+    out = []
+    for k0, k1, used in groups:
+        chunk = S if S <= block else max(1, int(budget // max(1, used * block))) * block
+        out.append((k0, k1, [(s0, min(chunk, S - s0)) for s0 in range(0, S, chunk)]))
+    return out
+
+
+def _sample_eps(eps, shapes):
+    """caller-supplied eps as float64 arrays, checked against each model's sample_eps_shapes (ValueError otherwise)"""
+    if eps is None:
+        return None
+    if not isinstance(eps, (list, tuple)) or len(eps) != len(shapes):
+        raise ValueError("sample_sources_many: eps must be a list with one (eps_x, eps_z, eps_u) triple per model (%d)" % len(shapes))
+    out = []
+    for k, (e, shs) in enumerate(zip(eps, shapes)):
+        G = len(shs[0])
+        if not isinstance(e, (list, tuple)) or len(e) != 3 or any(len(a) != G for a in e):
+            raise ValueError("sample_sources_many: eps of model %d must be (eps_x, eps_z, eps_u), three lists of %d arrays" % (k, G))
+        e = [[np.asarray(a, dtype=np.float64) for a in part] for part in e]
+        for name, part, sh in zip(("eps_x", "eps_z", "eps_u"), e, shs):
+            for r in range(G):
+                if part[r].shape != sh[r]:
+                    raise ValueError("sample_sources_many: model %d: %s[%d] has shape %r, not %r (sample_eps_shapes)"
+                                     % (k, name, r, part[r].shape, sh[r]))
+        out.append(e)
+    return out
+
+
+def _sample_group(h, models, xs, first, chunks, eps, gens, out):
+    """one group of sample_split on the device: a predict-only plan, every Param uploaded once, gp_pdgpb_predict_prepare with
+    the largest chunk's workspace, then per chunk of draws the normals (staged from the caller's eps or drawn block by block
+    from each model's generator), gp_pdgpb_sample and one copy back.  out[k] = [src, g, f] (g, f None when not wanted)"""
+    t, lib, nm = h.torch, h.lib, len(models)
+    P = [m.num_sources for m in models]
+    gps = [g for m in models for g in latent_gps(m)]
+    lay = sample_layout(P, [x.size for x in xs], [g[1].size for g in gps],
+                        [c for k, m in enumerate(models) for c in _sample_comps(m, first + k)])
+    keys = ("eps_x", "eps_z", "eps_u")
+    want_lat = out[first][1] is not None
+    segs, _, base = _segments(models)
+    order = np.ascontiguousarray(np.concatenate(
+        [merged_order(xs[k], z.value.reshape(-1)) for k, m in enumerate(models) for _, z, _, _ in latent_gps(m)]))
+    assert order.size == lay["order"][-1]
+    # the GPs of each model: [first, end) among the group's
+    gp0 = np.concatenate([[0], np.cumsum([2 * p for p in P])])
+    with _predict_plan(h, models) as plan:
+        if int(lib.gp_pdgpb_num_params(plan)) != base:
+            raise RuntimeError("gp_pdgpb layout disagrees with the host layout")
+        ppin = t.empty(base, dtype=t.float64, pin_memory=True)
+        flatvec.pack([sp for sm in segs for sp in sm], base, out=ppin.numpy())
+        params = ppin.to(h.device, non_blocking=True)
+        nx = int(lay["x_off"][-1])
+        xpin = t.empty(nx, dtype=t.float64, pin_memory=True)
+        np.concatenate(xs, out=xpin.numpy())
+        xd = xpin.to(h.device, non_blocking=True)
+        off = (C.c_int64 * (nm + 1))(*[int(v) for v in lay["x_off"]])
+        ws = h.workspace(lib.gp_pdgpb_sample_workspace_bytes(plan, off, max(sc for _, sc in chunks)))
+        h.check(lib.gp_pdgpb_predict_prepare(plan, params.data_ptr(), ws.data_ptr(), ws.numel()))
+        # page-locked staging, allocated once at the largest chunk: the caller's eps going in, the results coming back
+        most = max(sc for _, sc in chunks)
+        nback = int(lay["sources"][-1]) + (int(lay["latents"][-1]) if want_lat else 0)
+        pin = t.empty(most * nback, dtype=t.float64, pin_memory=True)
+        epin = None if eps is None else t.empty(most * sum(int(lay[key][-1]) for key in keys), dtype=t.float64, pin_memory=True)
+        for s0, sc in chunks:
+            tot = [sc * int(lay[key][-1]) for key in keys]
+            if eps is not None:
+                # the caller's arrays cut to the chunk's draws, in the call's layout (the previous chunk's copy is done: it
+                # was synchronised with its results)
+                np.concatenate([eps[k][a][r][s0:s0 + sc].reshape(-1) for a in range(3) for k in range(nm)
+                                for r in range(2 * P[k])], out=epin.numpy()[:sum(tot)])
+                ed = epin[:sum(tot)].to(h.device, non_blocking=True)
+                bufs = [ed[sum(tot[:a]):sum(tot[:a + 1])] for a in range(3)]
+            else:
+                bufs = [h.empty(v) for v in tot]
+                for k in range(nm):
+                    for b0 in range(s0, s0 + sc, SAMPLE_DRAW_BLOCK):
+                        nb = min(SAMPLE_DRAW_BLOCK, s0 + sc - b0)
+                        for key, buf in zip(keys, bufs):
+                            o = lay[key]
+                            m0, m1 = int(o[gp0[k]]), int(o[gp0[k + 1]])
+                            if nb == sc:          # the chunk is this block: the stream lands in the call's layout as it is
+                                buf[sc * m0:sc * m1].normal_(generator=gens[first + k])
+                                continue
+                            blk = h.empty(nb * (m1 - m0)).normal_(generator=gens[first + k])
+                            for r in range(gp0[k], gp0[k + 1]):
+                                a0, a1 = int(o[r]), int(o[r + 1])
+                                if a1 > a0:
+                                    buf[sc * a0:sc * a1].view(sc, a1 - a0)[b0 - s0:b0 - s0 + nb] = \
+                                        blk[nb * (a0 - m0):nb * (a1 - m0)].view(nb, a1 - a0)
+            nlat, nsrc = sc * int(lay["latents"][-1]), sc * int(lay["sources"][-1])
+            res = h.empty(nsrc + nlat)                  # sources | latents: one copy back (the sources alone without latents)
+            h.check(lib.gp_pdgpb_sample(plan, params.data_ptr(), xd.data_ptr(), off, order.ctypes.data, sc,
+                                        bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), res[nsrc:].data_ptr(),
+                                        res.data_ptr(), ws.data_ptr(), ws.numel()))
+            ncopy = sc * nback
+            pin[:ncopy].copy_(res[:ncopy], non_blocking=True)
+            h.sync()
+            got = pin.numpy()[:ncopy]
+            for k in range(nm):
+                n = xs[k].size
+                if n == 0:
+                    continue
+                src, g, f = out[first + k]
+                src[:, s0:s0 + sc] = got[sc * lay["sources"][k]:sc * lay["sources"][k + 1]].reshape(P[k], sc, n)
+                if want_lat:
+                    l = got[nsrc + sc * lay["latents"][k]:nsrc + sc * lay["latents"][k + 1]].reshape(2 * P[k], sc, n)
+                    g[:, s0:s0 + sc], f[:, s0:s0 + sc] = l[:P[k]], l[P[k]:]
+            del bufs
+        del ppin, xpin, pin, epin
+        bad = (C.c_int32 * nm)()
+        h.check(lib.gp_pdgpb_not_pd(plan, bad, 1))
+    for k in range(nm):
+        if bad[k]:
+            raise _lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, "sample_sources_many: model %d: Cholesky failed: %s"
+                                                % (first + k, _describe_not_pd(bad[k])))
+
+
+def sample_sources_many(models, xnews, num_samples=1, seed=0, eps=None, return_latents=False):
+    """Pdgp.sample_sources of every model at its own inputs, all models together: joint posterior draws under q of every
+    source nlin(g_i) f_i across all frames of a model's inputs.
+
+        draws = sample_sources_many(models, xnews, num_samples=S)
+        draws[k]   # src (P_k, S, n_k); with return_latents=True (src, g, f), each (P_k, S, n_k)
+
+    xnews: one array per model or one array for every model; a model without frames returns (P_k, S, 0) arrays, and a call
+    without any frame does no device work.  eps: None, or one (eps_x, eps_z, eps_u) triple per model with exactly the shapes
+    of models[k].sample_eps_shapes(n_k, S), in the caller's own point order: with the same eps the draws are those of
+    models[k].sample_sources(xnews[k], S, eps=eps[k]) to rounding, and eps = 0 gives predict_many's means and mean_source.
+    seed: one int (or None) per model, or one int s standing for [s + k].  Model k's normals come from its own torch generator
+    on the handle's device, drawn SAMPLE_DRAW_BLOCK draws at a time: they depend on seeds[k], the model's shapes and
+    num_samples only — not on the other models, their order, or how the call is split.  A seeded batch draw is its OWN
+    stream, not that of Pdgp.sample_sources(seed=...), whose chunks are sized per model: only caller-supplied eps
+    reproduces the single-model call.
+    Scope: check_sampleable (raises before any device work).  Reads each model's current Params and changes nothing (no
+    Param, flag, generator, Adam state, single-model plan or prediction memo).  A failed Kuu factorisation raises
+    NotPositiveDefiniteError naming the model.  A call whose normals and draws pass MAX_SAMPLE_BYTES on the device is split
+    into groups of models, then into chunks of draws (sample_split); the draws are bit-identical however it is split, and
+    draw s of model k whatever num_samples and whatever else is in the list."""
+    models, xs = check_sampleable(models, xnews)
+    if isinstance(num_samples, bool) or int(num_samples) != num_samples or int(num_samples) < 1:
+        raise ValueError("sample_sources_many: num_samples must be a positive integer, not %r" % (num_samples,))
+    S, nm = int(num_samples), len(models)
+    if isinstance(seed, (list, tuple, np.ndarray)):
+        if len(seed) != nm:
+            raise ValueError("sample_sources_many: %d seeds for %d models" % (len(seed), nm))
+        seeds = list(seed)
+    else:
+        seeds = [None if seed is None else int(seed) + k for k in range(nm)]
+    shapes = [m.sample_eps_shapes(x.size, S) for m, x in zip(models, xs)]
+    eps = _sample_eps(eps, shapes)
+    out = [[np.zeros((m.num_sources, S, x.size))] +
+           [np.zeros((m.num_sources, S, x.size)) if return_latents else None for _ in range(2)] for m, x in zip(models, xs)]
+    if any(x.size for x in xs):
+        h = _lib.default_handle()
+        gens = None if eps is not None else [_sample_generator(h, sd) for sd in seeds]
+        per_draw = sample_bytes_per_draw(models, xs)
+        for k0, k1, chunks in sample_split(per_draw, [2 * m.num_sources for m in models], S, MAX_SAMPLE_BYTES):
+            if any(x.size for x in xs[k0:k1]):
+                _sample_group(h, models[k0:k1], xs[k0:k1], k0, chunks, None if eps is None else eps[k0:k1], gens, out)
+    return [tuple(o) if return_latents else o[0] for o in out]

@@ -704,6 +704,41 @@ gp_status gp_pdgpb_predict_moments(gp_pdgpb_plan p, const double* params, const 
                                    const double* ynew, double* smean, double* svar, double* ymean, double* yvar, double* logp,
                                    void* workspace, size_t bytes);
 
+/* Joint posterior draws of every latent GP and every source nlin(g_i) f_i of every model of a prediction-only plan
+ * (Pdgp.sample_sources of each model, gpitch/pdgp.py:146-155 for the conditional the draws follow): gp_pdgp_sample's map per
+ * latent GP, whitened, for all models in one launch sequence.  Per latent GP r of model k (rows [g_0..g_{P-1}, f_0..f_{P-1}],
+ * M_r inducing inputs z_r, W_r = chol(Kuu_r + jitter I)^-1 as gp_pdgpb_predict_prepare left it):
+ *   prior path along the merged sorted points (xnew_k | z_r) by the exact state-space recursion of gp_pdgp_sample
+ *   (GP_KERN_MATERN12: 1 normal per point, GP_KERN_MATERN32: 2, GP_KERN_MERCER_MATERN12SM: 2 m);
+ *   u0 = prior(z_r) + sqrt(jitter) eps_u[0];  beta = W^T (q_mu + tril(q_sqrt) eps_u[1] - W u0);
+ *   draw_r(x*) = prior_r(x*) + K_r(x*, z_r) beta;   source_i = nlin_k(draw_i) * draw_{P+i}.
+ * Call order: gp_pdgpb_create with cfg->batch == NULL, gp_pdgpb_predict_prepare, then this entry with the same parameters
+ * and workspace as often as wanted; its buffers live behind the factors, so the workspace given to prepare must have
+ * gp_pdgpb_sample_workspace_bytes(plan, xnew_off, S) bytes (the measured carve; 0 for a bad argument) for the largest call.
+ * Arguments (everything model-major, offsets 64-bit):
+ *   xnew, xnew_off  as gp_pdgpb_predict: model k has n_k = xnew_off[k + 1] - xnew_off[k] frames; empty models are allowed and
+ *               only take their (M_r-entry) orders and eps_z / eps_u blocks; a call without frames launches nothing.
+ *   order_host  HOST array, the merges of every latent GP back to back, models in order, rows as above: GP r of model k has
+ *               n_k + M_r entries, a stable ascending argsort of (xnew_k | z_r); entry < n_k is a frame, n_k + i is z_r[i].
+ *               Each is checked to be a permutation before anything is enqueued (GP_ERR_BAD_ARG, "permutation" in
+ *               gp_last_error, otherwise): a bad entry never becomes a device address.
+ *   eps_x, eps_z, eps_u (device): the GPs' blocks back to back in the same order, [S][c_r][n_k], [S][c_r][M_r], [S][2][M_r],
+ *               indexed by the caller's own point order.
+ *   latents     (device, required) per model 2 P_k rows of [S][n_k];  sources (device, may be NULL) per model P_k rows of
+ *               [S][n_k], each model with its own nonlinearity.
+ * Refusals, all before anything is enqueued: a training plan, a plan never prepared (or prepared with other parameters or
+ * another workspace), a null pointer other than sources, S < 1: GP_ERR_BAD_ARG; a latent GP whose kernel has no sampler here
+ * (GP_KERN_MATERN52, GP_KERN_RBF, GP_KERN_MATERN32SM), more than 32767 latent GPs with frames: GP_ERR_UNSUPPORTED; a workspace
+ * shorter than gp_pdgpb_sample_workspace_bytes: GP_ERR_WORKSPACE.  A failed factorisation is in gp_pdgpb_not_pd's status.
+ * The entry waits until its descriptors are on the device; the kernels run asynchronously on the handle's stream.
+ * Determinism: no atomics, every sum has a fixed order.  Draw s of model k depends on its own eps and its own model only: it is
+ * bit-identical whatever S, whatever other models share the call, and however the caller splits models and draws between
+ * calls. */
+size_t gp_pdgpb_sample_workspace_bytes(gp_pdgpb_plan p, const int64_t* xnew_off, int32_t S);
+gp_status gp_pdgpb_sample(gp_pdgpb_plan p, const double* params, const double* xnew, const int64_t* xnew_off,
+                          const int32_t* order_host, int32_t S, const double* eps_x, const double* eps_z, const double* eps_u,
+                          double* latents, double* sources, void* workspace, size_t bytes);
+
 /* ---- kernel learning from an isolated-note recording (the drivers' init_kernel(train=True) branch,
  *      gpitch/transcription.py:176-195, gpitch/separation.py:185-204) -------------------------------------------------
  * gp_segment_gram replaces samplecov.get_samples + comatrix (samplecov.py:5-53: one tf.matmul session call per segment):
