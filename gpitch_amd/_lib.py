@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "gp_pdgp_set_workspace", "gp_pdgp_set_precision", "gp_pdgp_set_gp_precision", "gp_pdgp_set_grad_needs", "gp_pdgp_set_overlap", "gp_pdgp_set_frames_ascending", "gp_pdgp_set_qform", "gp_pdgp_elbo", "gp_pdgp_elbo_begin", "gp_pdgp_elbo_end", "gp_pdgp_create_subset", "gp_pdgp_cond_begin", "gp_pdgp_cond_end", "gp_pdgp_predict", "gp_pdgp_predict_reuse",
     "gp_pdgp_sample", "gp_pdgp_sample_reuse", "gp_pdgp_sample_workspace_bytes",
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
+    "gp_pdgp_natgrad_workspace_bytes", "gp_pdgp_natgrad_step",
     "gp_sgpr_create", "gp_sgpr_destroy", "gp_sgpr_num_params", "gp_sgpr_workspace_bytes", "gp_sgpr_set_workspace", "gp_sgpr_set_precision",
     "gp_sgpr_bound", "gp_sgpr_bound_grad", "gp_sgpr_residual_grad", "gp_sgpr_exchange_doubles", "gp_sgpr_bound_begin", "gp_sgpr_bound_end", "gp_sgpr_set_graphs", "gp_sgpr_eval_counts", "gp_sgpr_predict_f", "gp_sgpr_predict_f_full", "gp_sgpr_predict_source_full", "gp_sgpr_predict_source_workspace_bytes", "gp_sgpr_predict_source", "gp_sgpr_predict_source_sparse",
     "gp_sgpr_sample_source_sparse", "gp_sgpr_sample_source_workspace_bytes",
@@ -184,6 +185,8 @@ def load_library():
         "gp_check_not_pd": (i32, [vp]),
         "gp_take_not_pd": (i32, [vp, vp]),
         "gp_adam_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, dbl, dbl, dbl, dbl]),
+        "gp_pdgp_natgrad_workspace_bytes": (sz, [vp]),
+        "gp_pdgp_natgrad_step": (i32, [vp, vp, vp, vp, dbl, vp, vp, sz]),
         "gp_sgpr_create": (i32, [vp, C.POINTER(SgprConfig), C.POINTER(vp)]),
         "gp_sgpr_destroy": (i32, [vp]),
         "gp_sgpr_num_params": (i64, [vp]),

@@ -16,7 +16,7 @@ from .likelihoods import MpdLik
 from .methods import logistic, logistic_tf, nlin_code
 from .sgpr_ss import _sample_chunk, _sample_generator, merged_order
 from .param import MinibatchData, Param, ParamList, Parameterized, draw_in_lockstep, param_version
-from .train import AdamOptimizer, OptimizeResult
+from .train import AdamOptimizer, NatGradAdam, OptimizeResult
 
 jitter = 1e-6   # gpflow settings.numerics.jitter_level (pdgp.py:14)
 # sample_sources: standard normals per point of the kernels that have an exact state-space prior sampler (0: 2 m)
@@ -529,16 +529,36 @@ class Pdgp(Parameterized):
         return self._free.index_select(0, self._free_index()[1]).cpu().numpy()
 
     def optimize(self, method='L-BFGS-B', tol=None, callback=None, maxiter=1000, disp=False, **kw):
-        """GPflow Model.optimize.  `method` is an AdamOptimizer token (demo-modgp.py:44-45) or a
-        scipy.optimize.minimize method name."""
+        """GPflow Model.optimize.  `method` is an AdamOptimizer token (demo-modgp.py:44-45), a NatGradAdam token
+        (natural-gradient steps on q(u) of every latent GP whose q_mu and q_sqrt are free, Adam on the rest: train.py)
+        or a scipy.optimize.minimize method name."""
+        natgrad = isinstance(method, NatGradAdam)
+        if natgrad:
+            step_gps = self._natgrad_gps(method)        # refusals come before any device work
         self._pack()
         h = self._handle
-        if isinstance(method, AdamOptimizer):
+        if natgrad:
+            step_gps = (C.c_int32 * len(step_gps))(*step_gps)
+            if self.__dict__.get("_ng_ws") is None:
+                self._ng_ws = h.workspace(h.lib.gp_pdgp_natgrad_workspace_bytes(self._plan))
+        if natgrad or isinstance(method, AdamOptimizer):
             flag = C.c_int32(0)
-            one_call = bool(self._shard) and self._sharded_comm() is not None
+            one_call = not natgrad and bool(self._shard) and self._sharded_comm() is not None
             for it in range(maxiter):
                 self._adam_t += 1
-                if one_call:
+                if natgrad:
+                    # the same evaluation an Adam iteration makes; the step on q(u) reads its blocks of the gradient and
+                    # zeroes them, so that Adam behind it (zero gradient, zero moments: an update of exactly 0) moves
+                    # the noise variance, the kernels and the inducing inputs only
+                    self._elbo(True, sync=False)
+                    h.check(h.lib.gp_pdgp_natgrad_step(self._plan, self._params.data_ptr(), self._free.data_ptr(),
+                                                       self._grad.data_ptr(), method.gamma, step_gps,
+                                                       self._ng_ws.data_ptr(), self._ng_ws.numel()))
+                    h.check(h.lib.gp_adam_step(h.h, self._free.data_ptr(), self._params.data_ptr(), self._grad.data_ptr(),
+                                               self._tcode.data_ptr(), self._adam_m.data_ptr(), self._adam_v.data_ptr(),
+                                               self._nparams, self._adam_t, method.learning_rate, method.beta1,
+                                               method.beta2, method.epsilon))
+                elif one_call:
                     # a sharded model on an RCCL group: conditionals -> exchange -> likelihood + backward -> Adam, one call
                     aa = _lib.AdamArgs(self._free.data_ptr(), self._tcode.data_ptr(), self._adam_m.data_ptr(),
                                        self._adam_v.data_ptr(), self._nparams, self._adam_t, method.learning_rate,
@@ -554,10 +574,10 @@ class Pdgp(Parameterized):
                 # the next poll that has seen the flag — no host synchronisation per step
                 h.check(h.lib.gp_poll_not_pd(h.h, C.byref(flag)))
                 if flag.value:
-                    h.check(h.lib.gp_check_not_pd(h.h))     # raises NotPositiveDefiniteError with the pivot index
+                    self._check_not_pd(method)              # raises NotPositiveDefiniteError with the pivot index
                 if callback is not None:
                     callback(self._free.index_select(0, self._free_index()[1]).cpu().numpy())
-            h.check(h.lib.gp_check_not_pd(h.h))             # a failure in the last few steps, not polled yet
+            self._check_not_pd(method)                      # a failure in the last few steps, not polled yet
             # GPflow evaluates the returned `fun`/`jac` on a fresh minibatch (demo_modgp.ipynb:140-146)
             x_final = self._free.index_select(0, self._free_index()[1]).cpu().numpy()
             f, g = self._objective(x_final)
@@ -580,6 +600,43 @@ class Pdgp(Parameterized):
                                            self._params.data_ptr()))
         self._unpack()
         return res
+
+    def _natgrad_gps(self, method):
+        """one flag per latent GP in the engine's order [g_0..g_{P-1}, f_0..f_{P-1}]: does NatGradAdam step its q(u)?
+        Both of q_mu and q_sqrt free: yes; both fixed: no; one of the two fixed has no natural-gradient step (ValueError
+        naming the GP).  No device work."""
+        if not (0.0 < method.gamma <= 1.0):
+            raise ValueError("NatGradAdam: gamma must be a number in (0, 1], not %r" % (method.gamma,))
+        if self._shard:
+            raise NotImplementedError("NatGradAdam on a sharded model: build the model unsharded on one GPU "
+                                      "(a sharded Pdgp is trained with AdamOptimizer)")
+        flags = []
+        for role, q_mu, q_sqrt in (("activation", self.q_mu_act, self.q_sqrt_act), ("component", self.q_mu_com, self.q_sqrt_com)):
+            for i in range(self.num_sources):
+                fm, fs = bool(q_mu[i].fixed), bool(q_sqrt[i].fixed)
+                if fm != fs:
+                    raise ValueError("NatGradAdam: the %s GP %d has %s fixed and %s free; a natural-gradient step moves both, "
+                                     "fix both or neither" % ((role, i) + (("q_mu", "q_sqrt") if fm else ("q_sqrt", "q_mu"))))
+                flags.append(int(not fm))
+        return flags
+
+    def _check_not_pd(self, method):
+        """gp_check_not_pd; a refusal that a NatGradAdam step raised itself (its I - 2 gamma P was not positive definite:
+        natgrad.hip leaves the GP in the first words of its workspace) is reported as such"""
+        h = self._handle
+        try:
+            h.check(h.lib.gp_check_not_pd(h.h))
+        except _lib.NotPositiveDefiniteError as e:
+            if not isinstance(method, NatGradAdam):
+                raise
+            rep = self._ng_ws[:16].view(h.torch.int32).cpu().numpy()
+            if int(rep[0]) != 1:
+                raise
+            g, P = int(rep[1]), self.num_sources
+            raise _lib.NotPositiveDefiniteError(
+                e.status, "NatGradAdam: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) is "
+                          "not positive definite (pivot %d) at gamma = %g; no parameter was changed, take a smaller gamma"
+                          % ("activation" if g < P else "component", g if g < P else g - P, g, int(rep[2]), method.gamma))
 
     def _pred_key(self):
         """what a prediction's factorisation depends on: every Param value and the Adam steps taken (`.fixed` flags do

@@ -447,6 +447,33 @@ gp_status gp_adam_step(gp_handle h, double* free_state, double* params, const do
                        const uint8_t* tcode, double* m, double* v, int64_t n, int64_t t, double lr,
                        double beta1, double beta2, double eps);
 
+/* One natural-gradient step on the variational posteriors q(u_r) = N(q_mu_r, tril(q_sqrt_r) tril(q_sqrt_r)^T) of a Pdgp plan,
+ * from the gradient gp_pdgp_elbo has just written into `grad` (natgrad.hip; the GPflow releases after 0.5 have it as
+ * NatGradOptimizer, the reference moves q entry by entry with Adam: demo-modgp.py:44-45).  A natural gradient does not change
+ * under a linear change of the Gaussian's variable, so the same map serves whitened and unwhitened plans.  Per latent GP r with
+ * Lq = tril(q_sqrt), g = grad's q_mu block, G_L = tril(grad's q_sqrt block):
+ *   Phi = tril(Lq^T G_L),  P = (Phi + Phi^T - diag(Phi)) / 2   ( = Lq^T (d ELBO / d S) Lq, symmetric ),   B = I - 2 gamma P
+ *   B = U U^T, U upper triangular (the Cholesky factor of the index-reversed matrix: J B J = C C^T, U = J C J)
+ *   Lq' = Lq U^-T   (lower triangular; S' = Lq' Lq'^T has S'^-1 = S^-1 - 2 gamma d ELBO / d S)
+ *   q_mu' = q_mu + gamma Lq' (Lq'^T g)
+ * i.e. theta_1 += gamma (g - 2 G^ q_mu), theta_2 += gamma G^ in the natural parameters (G^ = d ELBO / d S).  Lq is never
+ * inverted.  tril(q_sqrt) receives Lq', the strict upper triangle of the stored block is left as it is; the values go to
+ * `params` and to `free_state` (both Params have the identity transform), and the q_mu / q_sqrt blocks of `grad` are zeroed,
+ * so that a gp_adam_step behind this call on the same gradient moves every other parameter and leaves these alone.
+ * step_gp_host (HOST array, one flag per latent GP in gp_pdgp_layout's order, NULL = all): the GPs that take the step.
+ * Refusal: every B is factored before anything is written.  If one is not positive definite (the step was too long) the
+ * handle's status word is raised exactly as by a failed Kuu factorisation, NO GP's state is written and the gradient stays, and
+ * gp_adam_step freezes; gp_poll_not_pd / gp_check_not_pd report GP_ERR_NOT_PD.  The workspace's first four int32 then read
+ * {1, latent GP index, pivot, 1}; they read {0, ...} after a step that was taken, and are left alone by a call that finds the
+ * status word already raised.  Three launches on the handle's stream, float64 whatever the plan's strip precision, no atomics,
+ * every sum in a fixed order (bit-identical between calls); no host synchronisation.  M <= 4096 per latent GP
+ * (GP_ERR_UNSUPPORTED); a subset (GP-sharded) plan: GP_ERR_BAD_ARG.
+ * workspace: gp_pdgp_natgrad_workspace_bytes(plan) bytes, 256-byte aligned — per latent GP the reversed B (then its factor),
+ * the factor's inverse and Lq^T g, sized by the same carve that lays it out. */
+size_t gp_pdgp_natgrad_workspace_bytes(gp_pdgp_plan p);
+gp_status gp_pdgp_natgrad_step(gp_pdgp_plan p, double* params, double* free_state, double* grad, double gamma,
+                               const int32_t* step_gp_host, void* workspace, size_t workspace_bytes);
+
 /* ---- L3 model: SGPRSS (gpitch/sgpr_ss.py:10-114) ---------------------------------------------- */
 typedef struct {
   int32_t num_kernels;          /* P kernels in the GPflow Add (kern.kern_list) */
