@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "gp_segment_gram_workspace_bytes", "gp_segment_gram", "gp_autocorr", "gp_kernfit_eval",
     "gp_pdgpb_create", "gp_pdgpb_destroy", "gp_pdgpb_num_params", "gp_pdgpb_layout", "gp_pdgpb_set_grad_needs",
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
+    "gp_pdgpb_natgrad_workspace_bytes", "gp_pdgpb_natgrad", "gp_pdgpb_natgrad_refused",
     "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
     "gp_pdgpb_predict_moments_workspace_bytes", "gp_pdgpb_predict_moments",
     "gp_pdgpb_sample_workspace_bytes", "gp_pdgpb_sample",
@@ -251,6 +252,9 @@ def load_library():
         "gp_pdgpb_objective": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "gp_pdgpb_adam": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl]),
         "gp_pdgpb_not_pd": (i32, [vp, C.POINTER(i32), i32]),
+        "gp_pdgpb_natgrad_workspace_bytes": (sz, [vp]),
+        "gp_pdgpb_natgrad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl, dbl, vp, vp, sz]),
+        "gp_pdgpb_natgrad_refused": (i32, [vp, C.POINTER(i32), i32]),
         "gp_pdgpb_predict_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_predict_prepare": (i32, [vp, vp, vp, sz]),
         "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),

@@ -10,6 +10,8 @@
 //   pdgpb_lik_kernel   one workgroup per model: Gauss-Hermite expectations, d/dfmean, d/dfvar, d/dnoise, the ELBO
 //   pdgpb_bwd_kernel   one workgroup per latent GP: gradients of q_mu, tril(Lq), the hyper-parameters and z
 //   pdgpb_adam_kernel  the TF-1.2 Adam update over the concatenated free state, frozen per model after a failed Cholesky
+// With a NatGradAdam token (gp_pdgpb_natgrad) two more launches sit between the backward and the Adam kernel:
+//   pdgpb_ng_form_kernel, pdgpb_ng_apply_kernel   the natural-gradient step on q(u) of every stepped latent GP (further down)
 // and, for  [m.predict_act_n_com(x) for m, x in zip(models, xnews)], the prediction kernels pdgpb_pred_* further down.
 // Every reduction is one thread's sequential loop or a fixed tree: two runs give bit-identical results.
 #include "common.h"
@@ -48,6 +50,12 @@ struct PbPredGp {
   int32_t P, nlin;
 };
 
+// natural-gradient step (gp_pdgpb_natgrad): one record per stepped latent GP of the call
+struct PbNgGp {
+  int32_t g, pad_;     // its index in the plan
+  int64_t ws;          // its [C^-1 (M x M) | w (M)] block, doubles from the first block of the step's workspace
+};
+
 struct gp_pdgpb_plan_s {
   gp_handle h = nullptr;
   bool predict_only = false;     // created with cfg->batch == NULL
@@ -62,6 +70,13 @@ struct gp_pdgpb_plan_s {
   double *d_fm = nullptr, *d_fv = nullptr, *d_gm = nullptr, *d_gv = nullptr, *d_kl = nullptr, *d_grad = nullptr,
          *d_elbo = nullptr, *d_scr = nullptr;
   bool ready = false;
+  // gp_pdgpb_natgrad: every latent GP's block offset in the step's workspace (doubles) and their total; the workspace the
+  // plan has seen last (its refusal words were zeroed then) and the list of stepped GPs of the call in flight
+  std::vector<int64_t> ng_off;
+  int64_t ng_blocks = 0;
+  const void* ng_ws = nullptr;
+  int32_t* d_refused = nullptr;
+  std::vector<PbNgGp> ng_list;
   // prediction-only plans: G blocks (doubles; PbGp::ws is a GP's offset among them), the per-call records, and the
   // workspace / parameters of the last gp_pdgpb_predict_prepare
   int64_t pred_g = 0;
@@ -248,20 +263,14 @@ __device__ inline PbScr pb_scr(double* base, int M, int B) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Kuu + jitter I of one latent GP factored and inverted in LDS by the whole workgroup (pdgpb_fwd_kernel and
-// pdgpb_pred_prep_kernel): on return Ls (M x M, row-major ld = M) holds W = L^-1, lower, zeros above the diagonal; L
-// itself is copied to Lcopy (global) when COPY_L.  zs: the z of the GP in LDS; tmp: M doubles of LDS.
+// A symmetric M x M matrix in LDS (Ls, row-major ld = M, written and synchronised by the caller) factored and inverted in
+// place by the whole workgroup: on return Ls holds the inverse of its lower Cholesky factor L, zeros above the diagonal; L
+// itself is copied to Lcopy (global) when COPY_L.  tmp: M doubles of LDS.  Shared by Kuu + jitter I (pb_factor_invert) and
+// the natural-gradient step's reversed B (pdgpb_ng_form_kernel); `word` is the model's word for this kind of failure.
 template <bool COPY_L>
-__device__ __forceinline__ void pb_factor_invert(int type, int m, const double* __restrict__ th, const double* zs, int M,
-                                                 double jitter, double* Ls, double* tmp, int& bad_pivot,
-                                                 int32_t* __restrict__ status, int model, int row, double* Lcopy) {
+__device__ __forceinline__ void pb_chol_invert(int M, double* Ls, double* tmp, int& bad_pivot, int32_t* __restrict__ word,
+                                               int row, double* Lcopy) {
   const int tid = threadIdx.x;
-  // Kuu + jitter I (pdgp.py:126-129 / GPflow conditional), full matrix, row-major ld = M
-  for (int e = tid; e < M * M; e += PB_THREADS) {
-    const int i = e / M, j = e % M;
-    Ls[e] = pb_kern(type, m, th, zs[i], zs[j]) + (i == j ? jitter : 0.0);
-  }
-  __syncthreads();
   // right-looking Cholesky in place (lower); a non-positive pivot is recorded and replaced by 1 so that the rest of the
   // pass stays finite (the model is frozen by the Adam kernel and reported to the host)
   for (int k = 0; k < M; k++) {
@@ -288,7 +297,7 @@ __device__ __forceinline__ void pb_factor_invert(int type, int m, const double* 
   __syncthreads();
   // status word of the model: 0, or INT_MAX - (128 row + pivot); the maximum keeps the failure with the smallest
   // (row, pivot) whatever order the model's workgroups finish in
-  if (tid == 0 && bad_pivot >= 0) atomicMax(&status[model], 0x7fffffff - (PB_MAX_M * row + bad_pivot));
+  if (tid == 0 && bad_pivot >= 0) atomicMax(word, 0x7fffffff - (PB_MAX_M * row + bad_pivot));
   if (COPY_L)
     for (int e = tid; e < M * M; e += PB_THREADS) Lcopy[e] = Ls[e];
   __syncthreads();
@@ -306,6 +315,22 @@ __device__ __forceinline__ void pb_factor_invert(int type, int m, const double* 
     if (tid == 0) Ls[j * M + j] = -ajj;
     __syncthreads();
   }
+}
+
+// Kuu + jitter I of one latent GP factored and inverted in LDS by the whole workgroup (pdgpb_fwd_kernel and
+// pdgpb_pred_prep_kernel): on return Ls holds W = L^-1.  zs: the z of the GP in LDS.
+template <bool COPY_L>
+__device__ __forceinline__ void pb_factor_invert(int type, int m, const double* __restrict__ th, const double* zs, int M,
+                                                 double jitter, double* Ls, double* tmp, int& bad_pivot,
+                                                 int32_t* __restrict__ status, int model, int row, double* Lcopy) {
+  const int tid = threadIdx.x;
+  // Kuu + jitter I (pdgp.py:126-129 / GPflow conditional), full matrix, row-major ld = M
+  for (int e = tid; e < M * M; e += PB_THREADS) {
+    const int i = e / M, j = e % M;
+    Ls[e] = pb_kern(type, m, th, zs[i], zs[j]) + (i == j ? jitter : 0.0);
+  }
+  __syncthreads();
+  pb_chol_invert<COPY_L>(M, Ls, tmp, bad_pivot, &status[model], row, Lcopy);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -561,12 +586,14 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
                                                          const double* __restrict__ grad, const uint8_t* __restrict__ tc,
                                                          double* __restrict__ m, double* __restrict__ v,
                                                          const int32_t* __restrict__ owner, const int32_t* __restrict__ status,
+                                                         const int32_t* __restrict__ refused,
                                                          const double* __restrict__ lr_t, int64_t n, double b1, double b2,
                                                          double eps, GpLogisticTable T) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint8_t t = tc[i];
     const int k = owner[i];
-    if (t == 2 || status[k] != 0) continue;
+    // frozen: a failed Kuu, or (gp_pdgpb_natgrad; null on the Adam-only path) a refused natural-gradient step
+    if (t == 2 || status[k] != 0 || (refused && refused[k] != 0)) continue;
     double x = fs[i];
     double g = -grad[i];
     if (t == 1) g *= 1.0 / (1.0 + exp(-x));
@@ -579,6 +606,174 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
     params[i] = (t == 1) ? pb_softplus_pos(x)
                          : (t >= 3 ? T.a[t - 3] + (T.b[t - 3] - T.a[t - 3]) / (1.0 + exp(-x)) : x);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// natural-gradient step on q(u) of many models (gp_pdgpb_natgrad; the map of natgrad.hip's header): per stepped
+// latent GP, with Lq = tril(q_sqrt), g = d ELBO / d q_mu, G_L = tril(d ELBO / d q_sqrt),
+//   Phi = tril(Lq^T G_L),  B = I - gamma (Phi + Phi^T - diag Phi),  J B J = C C^T,  Lq' = Lq U^-T (U^-T = J C^-T J),
+//   q_mu' = q_mu + gamma Lq' (Lq'^T g).
+// Two launches between pdgpb_bwd_kernel and pdgpb_adam_kernel whatever the number of models, over the uploaded list of
+// stepped GPs:
+//   pdgpb_ng_form_kernel   one workgroup per stepped GP: the reversed B formed in LDS on v_mfma_f64_16x16x4_f64 from params /
+//                          grad in place, w = Lq^T g, then B factored and inverted where it lies (pb_chol_invert); C^-1 and w
+//                          go to the step's workspace.  A non-positive pivot raises the model's refusal word (not the Kuu word)
+//   pdgpb_ng_apply_kernel  one workgroup per (stepped GP, block of 32 rows): nothing when the model's Kuu word or refusal word is
+//                          set (every B of the model was factored by the launch before: none of a refused model's GPs moves);
+//                          else Lq' = Lq U^-T on the MFMA in place, q_mu', both to params and free_state, their gradient blocks
+//                          zeroed so that Adam behind it leaves them alone.
+// Lq is never inverted.  Every sum is one thread's ordered loop, the MFMA's fixed k order or a fixed butterfly.
+typedef double pb_d4 __attribute__((ext_vector_type(4)));
+#define PB_NG_TILE 32
+
+// LDS: [maxM^2 reversed B -> C -> C^-1 | maxM tmp].  Phi_ij = sum_{k >= max(i, j)} Lq_ki G_kj over 16 x 16 sub-tiles (ti, tj <=
+// ti) of the lower triangle, dealt to the four wavefronts in turn; the k loop starts at the sub-tile's first row, and the masks
+// k >= i, k >= j are the two tril()s: the stored strict upper triangle of q_sqrt may hold anything.
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_form_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                                   const double* __restrict__ params, const double* __restrict__ grad,
+                                                                   double gamma, double* __restrict__ blocks,
+                                                                   int32_t* __restrict__ refused, int maxM) {
+  extern __shared__ double pb_sm[];
+  __shared__ int bad_pivot;
+  const PbNgGp e = list[blockIdx.x];
+  const PbGp g = gps[e.g];
+  const int M = g.M, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* Bs = pb_sm;
+  double* tmp = Bs + (int64_t)maxM * maxM;
+  const double* __restrict__ Lq = params + g.off_qsq;
+  const double* __restrict__ GL = grad + g.off_qsq;
+  double* __restrict__ Cinv = blocks + e.ws;
+  if (tid == 0) bad_pivot = -1;
+  const int kq = lane >> 4, lc = lane & 15, T = (M + 15) >> 4;
+  int s = 0;
+  for (int ti = 0; ti < T; ti++)
+    for (int tj = 0; tj <= ti; tj++, s++) {
+      if ((s & 3) != wave) continue;                         // wave-uniform
+      const int i0 = 16 * ti, j0 = 16 * tj;
+      const int ia = i0 + lc, jb = j0 + lc;
+      pb_d4 acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = i0; kk < M; kk += 4) {
+        const int k = kk + kq;
+        const bool kin = k < M;
+        const double av = (kin && ia < M && k >= ia) ? Lq[(int64_t)k * M + ia] : 0.0;    // A(i, k) = Lq(k, i)
+        const double bv = (kin && jb < M && k >= jb) ? GL[(int64_t)k * M + jb] : 0.0;    // B(k, j) = G_L(k, j)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int i = i0 + kq + 4 * q, j = j0 + lc;
+        if (i < M && j <= i) {
+          const double v = (i == j ? 1.0 : 0.0) - gamma * acc[q];
+          const int ri = M - 1 - i, rj = M - 1 - j;          // rj >= ri: (rj, ri) is in the lower triangle of the reversed matrix
+          Bs[rj * M + ri] = v;
+          Bs[ri * M + rj] = v;
+        }
+      }
+    }
+  // w_i = sum_{k >= i} Lq_ki g_k: thread i, k ascending
+  if (tid < M) {
+    const double* __restrict__ gq = grad + g.off_qmu;
+    double a = 0.0;
+    for (int k = tid; k < M; k++) a = fma(Lq[(int64_t)k * M + tid], gq[k], a);
+    Cinv[(int64_t)M * M + tid] = a;
+  }
+  __syncthreads();
+  // the pivot replaced by 1 keeps every loop's trip count and the pass finite whatever the gradient held (a model whose Kuu
+  // failed in this evaluation hands over garbage; its Kuu word, raised by the forward launch, is what the host reports)
+  pb_chol_invert<false>(M, Bs, tmp, bad_pivot, &refused[g.model], g.row, nullptr);
+  for (int i = tid; i < M * M; i += PB_THREADS) Cinv[i] = Bs[i];
+}
+
+// Lq' = Lq V, V = U^-T (V_kj = Cinv(M-1-j, M-1-k), lower);  q_mu' = q_mu + gamma Lq' t, t = V^T w.  Row i of Lq' needs row i of
+// Lq and nothing else of it, so the update runs in place: column tiles ascend, tile tj reads Lq(i, k) for k >= 32 tj only and
+// overwrites columns [32 tj, 32 tj + 32) after a barrier, so no wavefront reads what another has replaced.
+// LDS: [t (maxM, padded to even) | 32 x 33 row shares]
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_apply_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                                    double* __restrict__ params, double* __restrict__ fs,
+                                                                    double* __restrict__ grad, double gamma,
+                                                                    const double* __restrict__ blocks,
+                                                                    const int32_t* __restrict__ status,
+                                                                    const int32_t* __restrict__ refused) {
+  extern __shared__ double pb_sm[];
+  const PbNgGp e = list[blockIdx.x];
+  const PbGp g = gps[e.g];
+  const int M = g.M, ti = blockIdx.y, row0 = ti * PB_NG_TILE;
+  if (row0 >= M || status[g.model] != 0 || refused[g.model] != 0) return;       // (uniform over the workgroup)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int iend = min(M, row0 + PB_NG_TILE);
+  double* __restrict__ Lq = params + g.off_qsq;
+  const double* __restrict__ Cinv = blocks + e.ws;
+  const double* __restrict__ w = Cinv + (int64_t)M * M;
+  double* tv = pb_sm;                                    // t_j, j < iend
+  double (*red)[PB_NG_TILE + 1] = reinterpret_cast<double (*)[PB_NG_TILE + 1]>(pb_sm + ((M + 1) & ~1));
+
+  // t_j = sum_{k >= j} V_kj w_k = sum_{c = 0}^{M-1-j} Cinv(M-1-j, c) w_{M-1-c}: a wavefront per j, lanes over c, one butterfly
+  for (int j = wave; j < iend; j += PB_THREADS / 64) {
+    const int R = M - 1 - j;
+    const double* __restrict__ row = Cinv + (int64_t)R * M;
+    double s = 0.0;
+    for (int c = lane; c <= R; c += 64) s = fma(row[c], w[M - 1 - c], s);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    if (lane == 0) tv[j] = s;
+  }
+  __syncthreads();
+
+  const int kq = lane >> 4, lc = lane & 15;
+  const int rh = wave >> 1, ch = wave & 1;
+  const int i0 = row0 + rh * 16;
+  const int ia = i0 + lc;
+  double rs[4] = {0.0, 0.0, 0.0, 0.0};                   // this lane's share of (Lq' t) for rows i0 + kq + 4 q
+  for (int tj = 0; tj <= ti; tj++) {
+    const int j0 = tj * PB_NG_TILE + ch * 16;
+    const bool live = (j0 <= i0) && (i0 < M);            // wave-uniform
+    pb_d4 acc = {0.0, 0.0, 0.0, 0.0};
+    if (live) {
+      const int jb = j0 + lc;
+      const int kend = min(M, i0 + 16);
+      const double* __restrict__ crow = Cinv + (int64_t)(M - 1 - min(jb, M - 1)) * M;
+      for (int kk = j0; kk < kend; kk += 4) {
+        const int k = kk + kq;
+        const bool kin = k < M;
+        const double av = (kin && ia < M && k <= ia) ? Lq[(int64_t)ia * M + k] : 0.0;   // A(i, k) = Lq(i, k)
+        const double bv = (kin && jb < M && k >= jb) ? crow[M - 1 - k] : 0.0;           // B(k, j) = V(k, j)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+      }
+    }
+    __syncthreads();                                     // every wavefront has read this tile's operands
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int i = i0 + kq + 4 * q, j = j0 + lc;
+        if (i < M && j <= i) {
+          Lq[(int64_t)i * M + j] = acc[q];
+          fs[g.off_qsq + (int64_t)i * M + j] = acc[q];
+          rs[q] = fma(acc[q], tv[j], rs[q]);
+        }
+      }
+    }
+  }
+  // (Lq' t)_i: the 32 column shares of a row, added in column order
+#pragma unroll
+  for (int q = 0; q < 4; q++) red[rh * 16 + kq + 4 * q][ch * 16 + lc] = rs[q];
+  __syncthreads();
+  if (tid < PB_NG_TILE) {
+    const int i = row0 + tid;
+    if (i < M) {
+      double sum = red[tid][0];
+      for (int c = 1; c < PB_NG_TILE; c++) sum += red[tid][c];
+      const double v = params[g.off_qmu + i] + gamma * sum;
+      params[g.off_qmu + i] = v;
+      fs[g.off_qmu + i] = v;
+      grad[g.off_qmu + i] = 0.0;
+    }
+  }
+  // this step has used the gradient of these rows: what the Adam kernel sees of them is zero
+  double* __restrict__ GLrows = grad + g.off_qsq + (int64_t)row0 * M;
+  const int cnt = (iend - row0) * M;
+  for (int idx = tid; idx < cnt; idx += PB_THREADS) GLrows[idx] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -597,7 +792,6 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
 #define PB_PT 64      // frames per (latent GP, frame tile) entry: four column groups of 16
 #define PB_PRED_THREADS 512
 
-typedef double pb_d4 __attribute__((ext_vector_type(4)));
 typedef double pb_d2 __attribute__((ext_vector_type(2)));
 
 __host__ __device__ inline int pb_pad16(int M) { return (M + 15) & ~15; }
@@ -963,7 +1157,10 @@ gp_status gp_pdgpb_create(gp_handle h, const gp_pdgpb_config* cfg, gp_pdgpb_plan
       gp.off_qmu = off; off += M;
       gp.off_qsq = off; off += (int64_t)M * M;
       if (pred) { gp.ws = p->pred_g; p->pred_g += gp_align_up(pb_pred_g_doubles(M), 32); }
-      else { gp.ws = scr; scr += gp_align_up(pb_gp_scratch(M, B), 32); }
+      else {
+        gp.ws = scr; scr += gp_align_up(pb_gp_scratch(M, B), 32);
+        p->ng_off.push_back(p->ng_blocks); p->ng_blocks += gp_align_up((size_t)M * M + M, 32);
+      }
       gp.f_off = f + (int64_t)r * B;
       gp.batch_off = bo;
       p->gps.push_back(gp);
@@ -1079,9 +1276,94 @@ gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, con
   for (int s = 0; s < steps; s++) {
     GP_CHECK(pb_eval(p, params, x, y, idx + (int64_t)s * p->sumB, p->d_elbo, p->d_grad));
     hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
-                       p->d_owner, p->d_status, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps, h->logistic);
+                       p->d_owner, p->d_status, (const int32_t*)nullptr, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps,
+                       h->logistic);
     GP_HIP_CHECK(h, hipGetLastError());
   }
+  return GP_OK;
+}
+
+// gp_pdgpb_natgrad's regions of its own workspace, in order
+struct PbNgRegions { int32_t* refused; PbNgGp* list; double* blocks; };
+static PbNgRegions pb_ng_regions(const gp_pdgpb_plan_s* p, GpArena& ar) {
+  PbNgRegions r;
+  r.refused = ar.take<int32_t>(p->nm);
+  r.list = ar.take<PbNgGp>(p->gps.size());
+  r.blocks = ar.take<double>((size_t)p->ng_blocks);
+  return r;
+}
+static size_t pb_ng_form_lds(const gp_pdgpb_plan_s* p) { return ((size_t)p->maxM * p->maxM + p->maxM) * sizeof(double); }
+static size_t pb_ng_apply_lds(const gp_pdgpb_plan_s* p) {
+  return ((size_t)((p->maxM + 1) & ~1) + (size_t)PB_NG_TILE * (PB_NG_TILE + 1)) * sizeof(double);
+}
+
+size_t gp_pdgpb_natgrad_workspace_bytes(gp_pdgpb_plan p) {
+  if (!p || p->predict_only) return 0;
+  return gp_measure([&](GpArena& ar) { pb_ng_regions(p, ar); }) + GP_WS_TAIL_BATCH;
+}
+
+gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
+                           const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
+                           double beta1, double beta2, double eps, double gamma, const int32_t* step_gp_host,
+                           void* workspace, size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!free_state || !params || !tcode || !m || !v || !x || !y || !idx || !lr_t || !workspace || steps < 0 || p->predict_only)
+    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: bad argument or a prediction-only plan");
+  if (!(gamma > 0.0 && gamma <= 1.0)) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: gamma must lie in (0, 1]");
+  if (((uintptr_t)workspace & 255) != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: workspace not 256-byte aligned");
+  if (workspace_bytes < gp_pdgpb_natgrad_workspace_bytes(p))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad: workspace too small (gp_pdgpb_natgrad_workspace_bytes)");
+  GpArena ar(workspace, workspace_bytes);
+  const PbNgRegions r = pb_ng_regions(p, ar);
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad: arena overflow");
+  GP_CHECK(pb_upload(p));
+  if (workspace != p->ng_ws) {          // a workspace the plan has not seen: no model is refused yet
+    GP_HIP_CHECK(h, hipMemsetAsync(r.refused, 0, p->nm * sizeof(int32_t), h->stream));
+    p->ng_ws = workspace;
+    p->d_refused = r.refused;
+  }
+  p->ng_list.clear();
+  for (int g = 0; g < p->G; g++)
+    if (!step_gp_host || step_gp_host[g]) p->ng_list.push_back(PbNgGp{g, 0, p->ng_off[g]});
+  const int nstep = (int)p->ng_list.size();
+  if (nstep > 0) {
+    GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_ng_form_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_ng_form_lds(p)));
+    GP_HIP_CHECK(h, hipMemcpyAsync(r.list, p->ng_list.data(), nstep * sizeof(PbNgGp), hipMemcpyHostToDevice, h->stream));
+    // pageable host memory: the list may be rebuilt by the next call
+    GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  }
+  const int64_t n = p->nparams;
+  const int blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n + 255) / 256));
+  const int row_blocks = (p->maxM + PB_NG_TILE - 1) / PB_NG_TILE;
+  for (int s = 0; s < steps; s++) {
+    GP_CHECK(pb_eval(p, params, x, y, idx + (int64_t)s * p->sumB, p->d_elbo, p->d_grad));
+    if (nstep > 0) {
+      hipLaunchKernelGGL(pdgpb_ng_form_kernel, dim3(nstep), dim3(PB_THREADS), pb_ng_form_lds(p), h->stream, p->d_gps, r.list,
+                         (const double*)params, (const double*)p->d_grad, gamma, r.blocks, r.refused, p->maxM);
+      GP_HIP_CHECK(h, hipGetLastError());
+      hipLaunchKernelGGL(pdgpb_ng_apply_kernel, dim3(nstep, row_blocks), dim3(PB_THREADS), pb_ng_apply_lds(p), h->stream,
+                         p->d_gps, r.list, params, free_state, p->d_grad, gamma, (const double*)r.blocks,
+                         (const int32_t*)p->d_status, (const int32_t*)r.refused);
+      GP_HIP_CHECK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
+                       p->d_owner, p->d_status, (const int32_t*)r.refused, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps,
+                       h->logistic);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_natgrad_refused(gp_pdgpb_plan p, int32_t* host_status, int32_t clear) {
+  if (!p || !host_status) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->d_refused) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad_refused: no gp_pdgpb_natgrad call yet");
+  GP_HIP_CHECK(h, hipMemcpyAsync(host_status, p->d_refused, p->nm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k < p->nm; k++)
+    if (host_status[k] != 0) host_status[k] = 1 + (0x7fffffff - host_status[k]);
+  if (clear) GP_HIP_CHECK(h, hipMemsetAsync(p->d_refused, 0, p->nm * sizeof(int32_t), h->stream));
   return GP_OK;
 }
 

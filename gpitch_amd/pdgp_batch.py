@@ -6,8 +6,16 @@
 replaces  for m in models: m.optimize(method=AdamOptimizer(0.0025), maxiter=1000)  — the per-note training behind
 init_kernel_with_trained_models (gpitch/init_models.py:74-121) and the segments of a long recording — and leaves every
 model as that loop would: parameters, Adam step count and moments, and the minibatch generators advanced by the same
-draws (GPflow's final fresh-minibatch fun / jac evaluation included).  Whitened float64 unsharded models, Adam only;
-everything else is refused by check_batchable() before any device work.
+draws (GPflow's final fresh-minibatch fun / jac evaluation included).  Whitened float64 unsharded models; everything
+else is refused by check_batchable() before any device work.
+
+    results = optimize_many(models, method=NatGradAdam(0.1, 0.0025), maxiter=1000)
+
+replaces the same loop with the second optimiser token: per iteration a natural-gradient step on q(u) of every latent GP
+whose q_mu and q_sqrt are both free, Adam on the rest, two more launches per iteration whatever the number of models
+(gp_pdgpb_natgrad; check_batchable_natgrad() is its host check).  A model whose step is too long (I - 2 gamma P of one
+of its GPs not positive definite) is refused on its own: it is left as it was and its result carries the error, the
+others go on.
 
     preds = predict_many(models, xnews)
 
@@ -31,7 +39,7 @@ from .methods import nlin_code
 from .param import draw_in_lockstep
 from .pdgp import Pdgp, jitter
 from .sgpr_ss import _KERN_NAMES, _sample_generator, merged_order
-from .train import AdamOptimizer, OptimizeResult
+from .train import AdamOptimizer, NatGradAdam, OptimizeResult
 
 MAX_M = 128            # inducing points per latent GP (one factor of 128 x 128 float64 in a workgroup's LDS)
 MAX_MINIBATCH = 1024   # frames per model and step
@@ -83,6 +91,33 @@ def check_batchable(models, method=None, callback=None):
     if callback is not None:
         raise NotImplementedError("optimize_many takes no callback; %s" % _SINGLE)
     return _check_models(models, "optimize_many", _SINGLE, minibatch=True)
+
+
+def check_batchable_natgrad(models, method, callback=None):
+    """Host-only scope check of optimize_many / PdgpBatch.optimize with a NatGradAdam token (check_batchable stays the
+    Adam path's): the models' scope as there, no callback, and per model Pdgp._natgrad_gps(method) — gamma outside
+    (0, 1] on a token changed after construction, or one of a q_mu / q_sqrt pair fixed, is a ValueError that names the
+    model; a GP with both fixed is skipped.  Returns the models and one list of flags per model, rows
+    [g_0..g_{P-1}, f_0..f_{P-1}]: does the step move that GP's q(u)?  No device work."""
+    if not isinstance(method, NatGradAdam):
+        raise NotImplementedError("check_batchable_natgrad takes a NatGradAdam token (got %r)" % (method,))
+    if callback is not None:
+        raise NotImplementedError("optimize_many takes no callback; %s" % _SINGLE)
+    models = _check_models(models, "optimize_many", _SINGLE, minibatch=True)
+    flags = []
+    for k, m in enumerate(models):
+        try:
+            flags.append(m._natgrad_gps(method))
+        except ValueError as e:
+            raise ValueError("model %d: %s" % (k, e))
+    return models, flags
+
+
+def _check_for(models, method, callback=None):
+    """the host check of the token's type: (models, NatGradAdam's per-model flags or None)"""
+    if isinstance(method, NatGradAdam):
+        return check_batchable_natgrad(models, method, callback)
+    return check_batchable(models, method, callback), None
 
 
 def model_segments(m, base=0):
@@ -151,6 +186,14 @@ def _describe_not_pd(code):
     return "latent GP row %d of [g_0..g_{P-1}, f_0..f_{P-1}], pivot %d" % (row, pivot)
 
 
+def _describe_refused(k, code, P, gamma):
+    """gp_pdgpb_natgrad_refused's word of model k (the same 1 + 128 row + pivot) as the refusal's message"""
+    row, pivot = divmod(int(code) - 1, MAX_M)
+    return ("NatGradAdam: model %d: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) "
+            "is not positive definite (pivot %d) at gamma = %g; the model was left as it was, take a smaller gamma"
+            % (k, "activation" if row < P else "component", row if row < P else row - P, row, pivot, gamma))
+
+
 class PdgpBatch(object):
     """The plan behind optimize_many: every model's parameters in one device vector, one gp_pdgpb plan sized by the
     batch's own shapes (no single-model engine plan is built)."""
@@ -177,6 +220,7 @@ class PdgpBatch(object):
         self._adam_m, self._adam_v = h.zeros(n), h.zeros(n)
         self._elbo = h.zeros(nm)
         self._tcode = h.torch.zeros(n, dtype=h.torch.uint8, device=h.device)
+        self._ng_ws = None             # gp_pdgpb_natgrad's workspace, from the first NatGradAdam call on
 
     # ------------------------------------------------------------------------------------------
     def _pack(self):
@@ -229,6 +273,16 @@ class PdgpBatch(object):
         h.check(h.lib.gp_pdgpb_not_pd(self._plan, out, int(bool(clear))))
         return np.array(out[:], dtype=np.int64)
 
+    def refused(self, clear=True):
+        """per model: 0, or 1 + 128 row + pivot of its refused natural-gradient step with the smallest (latent GP row,
+        pivot); all 0 before the first NatGradAdam call"""
+        if self._ng_ws is None:
+            return np.zeros(len(self.models), dtype=np.int64)
+        out = (C.c_int32 * len(self.models))()
+        h = self._handle
+        h.check(h.lib.gp_pdgpb_natgrad_refused(self._plan, out, int(bool(clear))))
+        return np.array(out[:], dtype=np.int64)
+
     def objective_many(self):
         """every model's (-ELBO, -gradient over its free state) on a fresh minibatch of its own, as Pdgp._objective at
         the models' current Params (same draws, same free-state order)"""
@@ -246,13 +300,21 @@ class PdgpBatch(object):
         return out
 
     def optimize(self, method, maxiter=1000, chunk=64):
-        """`maxiter` Adam steps of every model (see optimize_many)"""
-        check_batchable(self.models, method)
+        """`maxiter` iterations of every model with an AdamOptimizer or a NatGradAdam token (see optimize_many)"""
+        _, flags = _check_for(self.models, method)
+        natgrad = flags is not None
         h = self._handle
         self._pack()
         self._load_moments()
         self.not_pd(clear=True)
         nm = len(self.models)
+        if natgrad:
+            step_gps = [f for fl in flags for f in fl]
+            step_gps = (C.c_int32 * len(step_gps))(*step_gps)
+            if self._ng_ws is None:
+                self._ng_ws = h.workspace(h.lib.gp_pdgpb_natgrad_workspace_bytes(self._plan))
+            else:
+                self.refused(clear=True)
         rng_keep = [(m.x.rng.get_state() if hasattr(m.x.rng, "get_state") else None,
                      m.y.rng.get_state() if hasattr(m.y.rng, "get_state") else None) for m in self.models]
         t0 = [m._adam_t for m in self.models]
@@ -268,12 +330,20 @@ class PdgpBatch(object):
                     lr[s, j] = method.learning_rate * np.sqrt(1. - method.beta2 ** t) / (1. - method.beta1 ** t)
             lr_dev = h.torch.as_tensor(lr.reshape(-1)).to(h.device)
             keep.append((idx, lr_dev))
-            h.check(h.lib.gp_pdgpb_adam(self._plan, self._free.data_ptr(), self._params.data_ptr(), self._tcode.data_ptr(),
-                                        self._adam_m.data_ptr(), self._adam_v.data_ptr(), self._x.data_ptr(),
-                                        self._y.data_ptr(), idx.data_ptr(), k, lr_dev.data_ptr(), method.beta1,
-                                        method.beta2, method.epsilon))
+            args = (self._plan, self._free.data_ptr(), self._params.data_ptr(), self._tcode.data_ptr(),
+                    self._adam_m.data_ptr(), self._adam_v.data_ptr(), self._x.data_ptr(), self._y.data_ptr(),
+                    idx.data_ptr(), k, lr_dev.data_ptr(), method.beta1, method.beta2, method.epsilon)
+            if natgrad:
+                # the same evaluation; the step on q(u) reads its blocks of the gradient and zeroes them, so that Adam
+                # behind it (zero gradient, zero moments: an update of exactly 0) moves everything else only
+                h.check(h.lib.gp_pdgpb_natgrad(*(args + (method.gamma, step_gps, self._ng_ws.data_ptr(),
+                                                         self._ng_ws.numel()))))
+            else:
+                h.check(h.lib.gp_pdgpb_adam(*args))
             done += k
         bad = self.not_pd(clear=True)
+        # a model whose Kuu failed is reported as that (its garbage gradient may have raised the refusal word as well)
+        refused = self.refused(clear=True) if natgrad else np.zeros(nm, dtype=np.int64)
         # GPflow evaluates the returned fun / jac on a fresh minibatch (Pdgp.optimize)
         draws = [draw_indices(m, 1) for m in self.models]
         elbo, grad = self._evaluate(draws)
@@ -286,14 +356,17 @@ class PdgpBatch(object):
         mom_m, mom_v = self._adam_m.cpu().numpy(), self._adam_v.cpu().numpy()
         results = []
         for k, m in enumerate(self.models):
-            if bad[k]:
+            if bad[k] or refused[k]:
                 # frozen since its failed step: the model keeps its Params, Adam state and generators
                 xs, ys = rng_keep[k]
                 if xs is not None:
                     m.x.rng.set_state(xs)
                 if ys is not None:
                     m.y.rng.set_state(ys)
-                msg = "Cholesky failed: %s" % _describe_not_pd(bad[k])
+                if bad[k]:
+                    msg = "Cholesky failed: %s" % _describe_not_pd(bad[k])
+                else:
+                    msg = _describe_refused(k, refused[k], m.num_sources, method.gamma)
                 results.append(OptimizeResult(fun=None, jac=None, x=None, success=False, status="error", message=msg,
                                               error=_lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, msg)))
                 continue
@@ -320,9 +393,19 @@ class PdgpBatch(object):
 def optimize_many(models, method=None, maxiter=1000, callback=None):
     """Train every model in `models` (ordinary Pdgp objects) as  m.optimize(method=method, maxiter=maxiter)  would, all
     of them together: one OptimizeResult per model.  A model whose Cholesky fails is frozen and its result carries
-    `error`; the others go on.  method: an AdamOptimizer token shared by all models (default AdamOptimizer())."""
+    `error`; the others go on.  method: an AdamOptimizer or a NatGradAdam token shared by all models (default
+    AdamOptimizer()).
+
+    NatGradAdam(gamma, learning_rate, ...): per iteration the Adam branch's evaluation, a natural-gradient step on q(u)
+    of every latent GP whose q_mu and q_sqrt are both free (both fixed: skipped; one of the two: ValueError), then Adam
+    on the rest (train.NatGradAdam).  A model whose step is too long — I - 2 gamma P of one of its GPs is
+    not positive definite — is refused on its own: none of its GPs is stepped, it is frozen from that iteration on and
+    ends as a model with a failed Cholesky does (Params, Adam state, _adam_t and generators as before the call,
+    success=False, error a NotPositiveDefiniteError naming NatGradAdam, the model, the GP, the pivot and gamma).  The
+    Moments that an earlier AdamOptimizer run left on q_mu / q_sqrt are not cleared: Adam then keeps coasting on them
+    beside the step, as in Pdgp.optimize.  Start NatGradAdam on fresh models, or accept that."""
     method = AdamOptimizer() if method is None else method
-    models = check_batchable(models, method, callback)
+    models, _ = _check_for(models, method, callback)
     return PdgpBatch(models).optimize(method, maxiter)
 
 

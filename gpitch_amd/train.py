@@ -18,8 +18,10 @@ class NatGradAdam(object):
     AdamOptimizer's) on the noise variance, the kernels' Params and the inducing inputs, from the same ELBO evaluation.
     With everything else fixed, gamma = 1 puts q(u) of a component GP on its optimum in one step (the data term is
     linear in its expectation parameters); the activations' likelihood is not conjugate, and a step whose I - 2 gamma P
-    is not positive definite is refused with NotPositiveDefiniteError: take a smaller gamma.  Not an AdamOptimizer:
-    optimize_many and sharded models do not take it."""
+    is not positive definite is refused with NotPositiveDefiniteError: take a smaller gamma.  optimize_many /
+    PdgpBatch.optimize take the token too (gp_pdgpb_natgrad, csrc/pdgp_batch.hip) and refuse such a step per model: the
+    refused model is left as it was, the others go on.  Not an AdamOptimizer: check_batchable (the Adam path's scope
+    check) and sharded models do not take it."""
 
     def __init__(self, gamma=0.1, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8):
         if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not (0.0 < float(gamma) <= 1.0):

@@ -696,6 +696,30 @@ gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, con
  * status was last cleared (TF's InvalidArgumentError in the reference); synchronises the stream.  clear != 0 resets the
  * status afterwards. */
 gp_status gp_pdgpb_not_pd(gp_pdgpb_plan p, int32_t* host_status, int32_t clear);
+/* `steps` iterations of  m.optimize(method=NatGradAdam(gamma, ...))  of every model: gp_pdgpb_adam's evaluation, then the
+ * natural-gradient step of gp_pdgp_natgrad_step (same map, same masks: the stored strict upper triangle of q_sqrt is neither
+ * read nor written) on every latent GP flagged in step_gp_host (HOST, one int32 per latent GP of the plan in gp_pdgpb_layout's
+ * order; NULL = all), then gp_pdgpb_adam's update on a gradient whose stepped q_mu / q_sqrt blocks read 0.  Two more launches
+ * per iteration whatever the number of models (none when no GP is flagged); the list of stepped GPs is uploaded once per
+ * call, and nothing synchronises between the iterations.  float64, no float atomics, bit-identical between calls; a model's
+ * result does not depend on the other models.
+ * Refusal, per model: when I - 2 gamma P of one of its GPs is not positive definite, none of that model's GPs is stepped and
+ * its Adam update is frozen from that iteration on, exactly as after a failed Kuu; the other models go on.  The model's
+ * refusal word — separate from the Kuu word of gp_pdgpb_not_pd, which a failed Kuu of the same evaluation raises as well —
+ * lives in the workspace and is read by gp_pdgpb_natgrad_refused: per model 0, or 1 + 128 row + pivot of the refused GP with
+ * the smallest (row, pivot); clear != 0 resets the words afterwards.  The words are zeroed when the plan is handed a workspace
+ * it has not seen in the previous call and otherwise persist from call to call (a refused model stays frozen) until cleared;
+ * gp_pdgpb_natgrad_refused before any gp_pdgpb_natgrad: GP_ERR_WORKSPACE.
+ * workspace: gp_pdgpb_natgrad_workspace_bytes(plan) bytes (0 for a null or prediction-only plan), 256-byte aligned: the
+ * refusal words, the list, and per latent GP the inverse factor of its reversed B and Lq^T g; measured by its own carve.
+ * gp_pdgpb_workspace_bytes does not change.  Null pointer, gamma outside (0, 1], misaligned workspace, prediction-only plan:
+ * GP_ERR_BAD_ARG; workspace too small: GP_ERR_WORKSPACE; nothing is enqueued then. */
+size_t gp_pdgpb_natgrad_workspace_bytes(gp_pdgpb_plan p);
+gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
+                           const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
+                           double beta1, double beta2, double eps, double gamma, const int32_t* step_gp_host,
+                           void* workspace, size_t workspace_bytes);
+gp_status gp_pdgpb_natgrad_refused(gp_pdgpb_plan p, int32_t* host_status, int32_t clear);
 /* ---- prediction of many models: Pdgp.predict_act_n_com (pdgp.py:190-208) of every model at its own inputs --------------
  * A prediction-only plan is created by gp_pdgpb_create with cfg->batch == NULL (num_data is then ignored).  It has the
  * parameter layout of a training plan (gp_pdgpb_layout) and no training workspace: gp_pdgpb_workspace_bytes returns 0,

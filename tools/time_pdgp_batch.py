@@ -6,6 +6,12 @@ inducing points, Matern32 + MercerMatern12sm with 5 partials, minibatch 100, z f
 time, warm-up steps excluded; one JSON line per W on stdout.
 
     python tools/time_pdgp_batch.py [--models 1 12 88] [--steps 200] [--warmup 20] [--seq-steps 100]
+
+    python tools/time_pdgp_batch.py --natgrad GAMMA [--models 12 88] [--steps 100] [--seq-steps 20] [--repeats 5]
+
+times optimize_many with NatGradAdam(GAMMA, 0.0025) per step, optimize_many with AdamOptimizer(0.0025) on the same
+batch (the figure of the Adam path) and the loop of m.optimize(method=NatGradAdam(GAMMA, 0.0025)) over twin models,
+in the same process: medians of --repeats windows each, the three alternating, with their ranges.
 """
 import argparse
 import json
@@ -37,13 +43,62 @@ def demo_model():
     return m
 
 
+def natgrad_main(a):
+    """three figures per model count, medians of a.repeats device-synchronised windows"""
+    import copy
+    import torch
+    import gpitch_amd
+    from gpitch_amd.pdgp_batch import PdgpBatch
+    ng = gpitch_amd.train.NatGradAdam(a.natgrad, 0.0025)
+    adam = gpitch_amd.train.AdamOptimizer(0.0025)
+    base = demo_model()
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for W in a.models:
+        bn = PdgpBatch([copy.deepcopy(base) for _ in range(W)])
+        ba = PdgpBatch([copy.deepcopy(base) for _ in range(W)])
+        seq = [copy.deepcopy(base) for _ in range(W)]
+        bn.optimize(ng, a.warmup)
+        ba.optimize(adam, a.warmup)
+        for m in seq:
+            m.optimize(method=ng, maxiter=a.warmup)
+        t = {"natgrad": [], "adam": [], "loop": []}
+        ok = True
+        for _ in range(a.repeats):
+            res = []
+            t["natgrad"].append(1e3 * window(lambda: res.extend(bn.optimize(ng, a.steps))) / a.steps)
+            ok = ok and all(r.success for r in res)
+            t["adam"].append(1e3 * window(lambda: ba.optimize(adam, a.steps)) / a.steps)
+            t["loop"].append(1e3 * window(lambda: [m.optimize(method=ng, maxiter=a.seq_steps) for m in seq])
+                             / (W * a.seq_steps))
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"models": W, "gamma": a.natgrad, "steps": a.steps, "repeats": a.repeats, "every_model_succeeded": ok,
+                          "batched_natgrad_ms_per_step": med["natgrad"], "batched_natgrad_range": [min(t["natgrad"]), max(t["natgrad"])],
+                          "batched_adam_ms_per_step": med["adam"], "batched_adam_range": [min(t["adam"]), max(t["adam"])],
+                          "loop_natgrad_ms_per_model_step": med["loop"], "loop_natgrad_range": [min(t["loop"]), max(t["loop"])],
+                          "natgrad_over_adam": med["natgrad"] / med["adam"],
+                          "batched_natgrad_model_steps_per_s": 1e3 * W / med["natgrad"],
+                          "loop_natgrad_model_steps_per_s": 1e3 / med["loop"],
+                          "speedup_over_loop": W * med["loop"] / med["natgrad"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", type=int, nargs="+", default=[1, 12, 88])
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--seq-steps", type=int, default=100, help="Adam steps per model on the one-after-another path")
+    ap.add_argument("--natgrad", type=float, default=None, metavar="GAMMA",
+                    help="time NatGradAdam(GAMMA, 0.0025): batched, the batched Adam step, and the single-model loop")
+    ap.add_argument("--repeats", type=int, default=5, help="windows per figure with --natgrad (the median is reported)")
     a = ap.parse_args()
+    if a.natgrad is not None:
+        return natgrad_main(a)
     import copy
     import torch
     import gpitch_amd
