@@ -169,6 +169,7 @@ gp_status gp_destroy(gp_handle h) {
   if (h->ev_era) (void)hipEventDestroy(h->ev_era);
   if (h->ev_kuu) (void)hipEventDestroy(h->ev_kuu);
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
+  if (h->ev_feat) (void)hipEventDestroy(h->ev_feat);
   if (h->ev_diag) (void)hipEventDestroy(h->ev_diag);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -645,7 +646,7 @@ const GpSwitches& gp_switches() {
     struct { const char* name; int* slot; } table[] = {
         {"strip_wave", &w.strip_wave}, {"strip_wave_f32", &w.strip_wave_f32}, {"strip_wave_roles", &w.strip_wave_roles}, {"strip_lean", &w.strip_lean},
         {"hyper_fuse", &w.hyper_fuse}, {"kufbar_split", &w.kufbar_split}, {"cond_a_early", &w.cond_a_early},
-        {"blocked_256", &w.blocked_256}, {"cov_sum", &w.cov_sum}, {"hyper_sum", &w.hyper_sum}, {"chol_cluster", &w.chol_cluster}, {"aux_priority", &w.aux_priority}, {"gemm_tile32", &w.gemm_tile32}, {"nt_cover", &w.nt_cover}, {"kuf_scan", &w.kuf_scan}, {"scan_side", &w.scan_side}, {"qform", &w.qform}};
+        {"blocked_256", &w.blocked_256}, {"cov_sum", &w.cov_sum}, {"hyper_sum", &w.hyper_sum}, {"chol_cluster", &w.chol_cluster}, {"aux_priority", &w.aux_priority}, {"gemm_tile32", &w.gemm_tile32}, {"nt_cover", &w.nt_cover}, {"kuf_scan", &w.kuf_scan}, {"scan_side", &w.scan_side}, {"qform", &w.qform}, {"qform_far", &w.qform_far}};
     std::string all(e);
     size_t pos = 0;
     while (pos < all.size()) {

@@ -25,7 +25,7 @@ struct gp_handle_s {
   GpLogisticTable logistic = {}; int num_logistic = 0;
   // helper stream for work that can overlap the main stream (the latency-bound Kuu factorisation runs on ~24 CUs
   // while the Kuf builds stream over the rest): created on first use, joined through events
-  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr, ev_q = nullptr;
+  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr, ev_q = nullptr, ev_feat = nullptr;
   hipStream_t main_stream_saved = nullptr; bool aux_active = false, aux_pending = false;
   // second helper stream ("side"): one more independent piece of a step (the spectral-mixture Kuf-side contractions
   // underneath the second half of the Kuf_bar product); gp_side_begin / _end / _join
@@ -291,10 +291,11 @@ struct GemmFlags {
   int epilogue = 1;      // bitmask of GemmEpi
   int scale_mode = 0;    // 0 none; 1: opB(B)(k,n) *= v1[n]; 2: opB(B)(k,n) *= v1[k]
   int timer = GP_TIMER_SMALL_GEMM;
-  int role = 0;          // 1 cond_A, 2 cond_LTA (needs transA), 3 kuf_bar: dedicated 128x128 instantiations; 6 G = Q Kuf (gemm_wave.hip only)
+  int role = 0;          // 1 cond_A, 2 cond_LTA (needs transA), 3 kuf_bar: dedicated 128x128 instantiations; 6 G = Q Kuf, 7 the same from near rows + far field (gemm_wave.hip only)
   int tile_m0 = 0, tile_mcount = 0;   // strip products (big tiles, no split-K): only row-blocks [m0, m0 + mcount) (0 = all)
   const double* aux_x = nullptr;      // role 5 (gemm_strip.hip): the frames x of the batch; aux_ktype: the stationary kernel type
   int aux_ktype = -1;
+  int aux_nf = 0;                     // role 7 (gemm_wave.hip): features per point of the far field, 2 sm_mpad(m)
   int uniform_aligned = 0;            // the caller vouches: every problem has M = maxM (= K structure), N = maxN, 16-byte
                                       // aligned operands with even leading dimensions (gemm_strip.hip's lean form)
   int a32_ok = 0;                     // float32 strips (gemm_wave_f32.hip): every problem's xb = M * M floats of scratch for the M x M operand

@@ -438,7 +438,8 @@ gp_status launch_kernel_build(gp_handle h, DevKern k, const double* x1, int n1, 
 #ifndef CVM_CT
 #define CVM_CT 2                     // 16-column tiles per wavefront (see the kernel)
 #endif
-#define CVM_SEP 1.0                  // separable envelope: |z - x| / lengthscale at least this for every entry of a tile
+static_assert(16 * CVM_CT == CVM_SEP_COLS, "cov_entry.h: the separable predicate is stated per builder wavefront");
+// (CVM_SEP and the predicate that decides which tiles take the separable envelope: cov_entry.h, shared with qfar.hip)
 // Measured on MI355X (profiles/r02): direct stores 0.82 ms per 12-GP launch; LDS-transposed 512-byte row stores 0.78;
 // address-space-1 pointers (the descriptor's pointers are generic, so the stores were FLAT and every LDS wait of the
 // row loop waited for them) 0.62.  What is left is arithmetic: the float64 MFMA and the float64 vector pipe do not
@@ -519,7 +520,7 @@ __global__ void __launch_bounds__(1024 / CT, CT == 2 ? 2 : 2) cov_mercer_mfma_ke
     bmin_w = lo; bmax_w = hi;
   }
   constexpr double SENV = (ENV == 0) ? 1.0 : 2.23606797749979;
-  const bool sep_ok = (SENV * (bmax_w - bmin_w) < 300.0);       // column factors stay normal numbers
+  const bool sep_ok = cov_sep_cols_ok(SENV, bmin_w, bmax_w);       // column factors stay normal numbers
   __syncthreads();                                                 // etab is ready
   double cfp[CT], cfn[CT];                                         // var * exp(-s (bmax - b)),  var * exp(-s (b - bmin))
 #pragma unroll
@@ -554,7 +555,7 @@ __global__ void __launch_bounds__(1024 / CT, CT == 2 ? 2 : 2) cov_mercer_mfma_ke
         for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bfr[ct][s], acc[ct], 0, 0, 0);
       }
       // envelope; element r of acc[ct]: row 16 rt + kq + 4 r, column 16 ct + lc of this wavefront's strip
-      const bool above = sep_ok && (tile_lo[rt] - bmax_w >= CVM_SEP), below = sep_ok && (bmin_w - tile_hi[rt] >= CVM_SEP);
+      const bool above = cov_sep_above(sep_ok, tile_lo[rt], bmax_w), below = cov_sep_below(sep_ok, bmin_w, tile_hi[rt]);
       if (above || below) {                 // (wavefront-uniform)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -679,7 +680,7 @@ __global__ void __launch_bounds__(64 * NWV, 2) cov_mercer_mfma_lean_kernel(const
     bmin_w = lo; bmax_w = hi;
   }
   constexpr double SENV = (ENV == 0) ? 1.0 : 2.23606797749979;
-  const bool sep_ok = (SENV * (bmax_w - bmin_w) < 300.0);
+  const bool sep_ok = cov_sep_cols_ok(SENV, bmin_w, bmax_w);
   __syncthreads();                                                 // etab and a_t are ready (the only workgroup barrier)
   double cfp[CT], cfn[CT];                                         // var * exp(-s (bmax - b)),  var * exp(-s (b - bmin))
 #pragma unroll
@@ -799,8 +800,8 @@ __global__ void __launch_bounds__(64 * NWV, 2) cov_mercer_mfma_lean_kernel(const
       double lo = a_t[t * 16], hi = lo;
 #pragma unroll
       for (int q = 1; q < 16; q++) { const double v = a_t[t * 16 + q]; lo = fmin(lo, v); hi = fmax(hi, v); }
-      amask = __ballot(sep_ok && (lo - bmax_w >= CVM_SEP));
-      bmask = __ballot(sep_ok && (bmin_w - hi >= CVM_SEP));
+      amask = __ballot(cov_sep_above(sep_ok, lo, bmax_w));
+      bmask = __ballot(cov_sep_below(sep_ok, bmin_w, hi));
     }
     const int tend = min(ntile, tg + 64);
     int t = tg;

@@ -65,3 +65,14 @@ __device__ __forceinline__ double cov_kdiag(int type, int m, const double* __res
   }
   return v;
 }
+
+// ---- separable envelope: which 16-row tiles of a Mercer Kuf strip are written in product form ----------------------------
+// With a = z / l of a tile's rows in [tile_lo, tile_hi] and b = x / l of a wavefront's CVM_SEP_COLS columns in [bmin, bmax],
+// the tile is separable when every a lies at least CVM_SEP above every b, or below (cov.hip has the argument and the error
+// bound).  One definition for the builders (cov.hip) and for the range rule of the Q route's far field (qfar.hip), which must
+// call an entry far only where the builder wrote it as a product.
+#define CVM_SEP 1.0                  // |z - x| / lengthscale at least this for every entry of a tile
+#define CVM_SEP_COLS 32              // columns of one builder wavefront (16 * CVM_CT of cov.hip)
+__device__ __forceinline__ bool cov_sep_cols_ok(double senv, double bmin, double bmax) { return senv * (bmax - bmin) < 300.0; }
+__device__ __forceinline__ bool cov_sep_above(bool cols_ok, double tile_lo, double bmax) { return cols_ok && (tile_lo - bmax >= CVM_SEP); }
+__device__ __forceinline__ bool cov_sep_below(bool cols_ok, double bmin, double tile_hi) { return cols_ok && (bmin - tile_hi >= CVM_SEP); }

@@ -84,6 +84,19 @@ int kuf_scan_records(int M);                // partial records one GP leaves (ne
 // all `count` GPs of one family (same kernel type) over the n ascending frames x: three launches, no Kuf_bar product
 gp_status launch_kuf_scan(gp_handle h, int ktype, const KufScanItem* d_items, int count, int maxM, const double* x, int n);
 
+// qfar.hip: the tables of the Q route's far field, one item per latent GP of the run
+struct QfarItem {
+  const double* z; const double* theta; const double* fz; const double* fx; const double* Q;   // z features [nf][M], x features [nf][N]
+  int* rng; double* ref; double* T; double* Psi;     // [groups][2] near range, [groups][2] reference points, T, Psi (CondTask)
+  int M, pad;
+};
+#define QFAR_GROUP 256       // frames per column group: the wave product's workgroup
+struct QfarSizes { size_t rng, ref, T, Psi; };       // doubles
+QfarSizes qfar_sizes(int M, int N, int m);
+bool qfar_takes(int M, int N, int m);
+// count GPs of one family (M, m) over the n ascending frames x: two launches on h->stream
+gp_status launch_qfar_tables(gp_handle h, const QfarItem* d_items, int count, int M, int m, const double* x, int n);
+
 #define CB_NB 128          // panel width of the blocked Kuu factorisation
 #define CB_MAX_PANELS 8    // M <= 1024
 
@@ -121,6 +134,9 @@ struct CondTask {
   bool f32 = false;       // this GP's M x N strips (Kuf, A, A2) are float32 (per-GP precision: CondBatch::n64)
   // Q route (CondBatch::nq): Q = W^T (Lq Lq^T - I) W (M x M) and beta = W^T q_mu, which the caller's hook fills
   const double* Qm = nullptr; const double* beta = nullptr;
+  // ... and, when the run takes the far-field form (CondBatch::q_far), qfar.hip's tables: two ints per
+  // 256-frame group [kbeg, kend), T [group][M][2 nf], Psi [2 nf][N]
+  const int* far_rng = nullptr; const double* far_T = nullptr; const double* far_Psi = nullptr;
 };
 
 struct CondBatch {
@@ -147,7 +163,9 @@ struct CondBatch {
   // Q route: the tasks [q0, q0 + nq) — float64, whitened, Qm and beta set — form G = Q Kuf into their A strip
   // instead of A = W Kuf and Lq^T A when cond_batch_run is given a hook; set before cond_batch_upload
   int q0 = 0, nq = 0;
+  bool q_far = false;     // the run's product is role 7 (near rows + far field) instead of role 6; the hook fills the tables too
   bool q_desc = false;    // the descriptor block was sized with the Q route's regions (cond_batch_desc_bytes(count, true))
+  bool feat_ready = false;   // q_far: gp_handle_s::ev_feat was recorded behind the Kuf builds (their feature tables)
   bool diag_ready = false;   // set by a factorisation that recorded gp_handle_s::ev_diag after the diagonal blocks of W
 };
 

@@ -136,6 +136,10 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
       if (!whiten || t.f32 || !t.Qm || !t.beta || !t.q_sqrt || !gemm_wave_takes(6, cb.maxM, N, uni))
         return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a task of the Q run does not qualify");
       fq[g].A = t.Qm; fq[g].v0 = t.beta; fq[g].o0 = t.s2; fq[g].xb = nullptr;
+      if (cb.q_far) {
+        if (!t.far_rng || !t.far_T || !t.far_Psi) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: the Q run's far field without its tables");
+        fq[g].xa = (const double*)t.far_rng; fq[g].v1 = t.far_T; fq[g].v2 = t.far_Psi;
+      }
       cond_finish_fill(fin_q + g * cond_finish_item_bytes(), t.s1, 0, t.s2, rb64, t.dot, rb64, t.kern, t.fmean, t.fvar);
     }
   }
@@ -420,6 +424,12 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
   GP_CHECK(st);
   // 3. Kuf
   GP_CHECK(build_kuf());
+  // (the far field's tables read the feature tables just enqueued; the hook may build them on the helper stream)
+  cb.feat_ready = false;
+  if (q1 > q0 && cb.q_far) {
+    if (!h->ev_feat && hipEventCreateWithFlags(&h->ev_feat, hipEventDisableTiming) != hipSuccess) h->ev_feat = nullptr;
+    if (h->ev_feat && hipEventRecord(h->ev_feat, h->stream) == hipSuccess) cb.feat_ready = true;
+  }
   // 4. A = W Kuf (+ column reductions).  When the factorisation left an event behind the diagonal blocks of W, the first
   // row-block goes ahead of the join (it reads W[0:128, 0:128] only) and the rest follows it.
   {
@@ -471,7 +481,8 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
   if (q1 > q0) {
     GP_CHECK((*q_prepare)());
     GemmFlags f;
-    f.timer = GP_TIMER_COND_A; f.role = 6; f.big_tiles = 1;
+    f.timer = GP_TIMER_COND_A; f.role = cb.q_far ? 7 : 6; f.big_tiles = 1;
+    f.aux_nf = cb.q_far ? 2 * sm_mpad(cb.tasks[q0].kern.m) : 0;
     f.epilogue = EPI_STORE | EPI_COLSUMSQ | EPI_COLDOT;
     f.uniform_aligned = cond_batch_uniform(cb, N);
     GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.fq) + q0, q1 - q0, cb.maxM, N, f));

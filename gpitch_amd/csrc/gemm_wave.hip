@@ -6,6 +6,8 @@
 //   role 3  G   = R (A D)    backward: Kuf_bar (TF reverse mode of the same lines)
 //   role 6  G   = Q Kuf      Q = W^T (Lq Lq^T - I) W: a whitened Matern-1/2 spectral-mixture family's whole forward strip work
 //                            (DESIGN.md 3.03): fvar = kdiag + colsum(Kuf o G), fmean = Kuf^T beta, Kuf_bar = G diag(2 gv) + beta gm^T
+//   role 7  G   = Q Kuf      the same strip from the rows near each 256-frame group plus a far field of rank 4 mpad:
+//                            G[:, S] = Q[:, near(S)] Kuf[near(S), S] + T(S) Psi[:, S], tables by qfar.hip; role 6's epilogue
 //
 // Why a third form.  gemm_strip.hip's tiles (128 x 128 per workgroup, operands staged through LDS, one barrier per K-tile,
 // two workgroups per CU) run the dense product at 0.83 of the matrix peak but the triangular ones at 0.65-0.75
@@ -59,27 +61,35 @@ struct WaveFlags {
   int epi;            // EPI_* bitmask
   double alpha;       // role 3: a power of two, folded into the column scales
   int N;              // frames (row stride of the partial-sum arrays)
-  int pad_;
+  int nf;             // role 7: features per point, 2 sm_mpad(m) (a multiple of 8)
   const double* xcols; // role 5: the frames x (the B strip's columns; not part of any descriptor: pdgp.hip pdgp_bind)
 };
 
 // One 64 x 64 tile: rows [i0, i0 + 64) of op(A) x columns [j0, j0 + 64) of B over k in [kbeg, kend) (multiples of 8).
 // TAG 1: op(A) = A lower triangular (k < i0 + 64; zeros above the diagonal are IN the matrix).  TAG 2: op(A) = A^T with A
 // lower triangular (k >= i0), walked downwards.  TAG 3: dense.  TAG 6: dense, no column scale; its column sums run over Kuf o C and Kuf o v0 (the
-// tile's own rows of the B strip, read again in the epilogue: they left the K loop's registers chunks ago).  TAG 5 (KT = a stationary kernel type): TAG 3's product with the
+// tile's own rows of the B strip, read again in the epilogue: they left the K loop's registers chunks ago).  TAG 7: TAG 6 over
+// the near rows [kbeg, kend) of the tile's 256-column group (p.xa: two ints per group), then a second K loop into the same
+// accumulators over the far field: op(A) = T(S) (p.v1: [group][M][2 nf], k-contiguous like W), B = Psi (p.v2: [2 nf][N], frames
+// contiguous like the strip), columns [0, nf) the rows below the group, [nf, 2 nf) those above; a side without rows is skipped.  TAG 5 (KT = a stationary kernel type): TAG 3's product with the
 // Kuf-side hyper-gradient contraction of that kernel as its epilogue (gemm_strip.hip role 5; bwd.hip hyper_contract_kernel:
 // sum_ij (Kuf_bar_ij + alpha_i gm_j) dK_ij / d(variance, lengthscale)), nothing stored: one partial record per wavefront tile.
 template <int TAG, int KT = -1>
 __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f, const int i0, const int j0, const int lane,
                                         double* etab = nullptr) {
-  constexpr bool DENSE = (TAG == 3 || TAG == 5 || TAG == 6);
+  constexpr bool DENSE = (TAG == 3 || TAG == 5 || TAG == 6 || TAG == 7);
+  constexpr bool QF = (TAG == 6 || TAG == 7);      // role 6's epilogue
   constexpr bool TA = (TAG == 2);
   constexpr bool KDOWN = (TAG == 2);
   const int lc = lane & 15, kq = lane >> 4;
   int kbeg = 0, kend = p.K;
   if (TAG == 1) kend = i0 + GW_T;
   if (TAG == 2) kbeg = i0;
-  const int nch = (kend - kbeg) / GW_CH;
+  if (TAG == 7) {     // (wave-uniform: the group's range, whole 16-row tiles)
+    const int* rng = (const int*)p.xa + 2 * (j0 / 256);
+    kbeg = __builtin_amdgcn_readfirstlane(rng[0]); kend = __builtin_amdgcn_readfirstlane(rng[1]);
+  }
+  int nch = (kend - kbeg) / GW_CH;
   const int kfirst = KDOWN ? kend - GW_CH : kbeg;
 
   // ---- operand addresses: BUFFER loads — resource descriptor (SGPRs) + one constant 32-bit lane offset (VGPR) + a scalar
@@ -87,8 +97,8 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
   // v_lshl_add_u64 per distinct scalar base, and next to float64 MFMAs every vector instruction costs matrix time)
   // !TA: soff[a] -> row i0 + 16 a, column kfirst; lane offset (lc * lda + 2 kq) * 8; a chunk further = +- 64 bytes
   //  TA: soff[2 s + a'] -> row kfirst + s, column i0 + 32 a'; lane offset (2 kq * lda + 2 lc) * 8; a chunk = +- 8 lda * 8
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0x7fffffff, 0x00020000);
   int soA[4], soB[2];
   int voffA, stepA;
   if (!TA) {
@@ -105,8 +115,8 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
   // B: soff[s] -> row kfirst + s, column j0; lane offset (2 kq * ldb + 2 lc) * 8; column half h = + 256 bytes (immediate)
 #pragma unroll
   for (int s = 0; s < 2; s++) soB[s] = (int)(((int64_t)(kfirst + s) * p.ldb + j0) * 8);
-  const int voffB = (int)(((int64_t)2 * kq * p.ldb + 2 * lc) * 8);
-  const int stepB = (KDOWN ? -1 : 1) * GW_CH * (int)p.ldb * 8;
+  int voffB = (int)(((int64_t)2 * kq * p.ldb + 2 * lc) * 8);
+  int stepB = (KDOWN ? -1 : 1) * GW_CH * (int)p.ldb * 8;
 
   int nlA = 0, nlB = 0;                       // chunks requested so far (scalar)
   // raw loads only: nothing here consumes a loaded value.  A request past the last chunk re-reads the last one (L1 hit).
@@ -184,16 +194,50 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
 #define GW_WAIT(N) do { GW_SB; __builtin_amdgcn_s_waitcnt(0x0F70 | (N)); GW_SB; } while (0)
 
   dbl2 A0[4], A1[4], B0[4], B1[4], B2[4], B3[4];
-  load_B(B0); load_B(B1); load_A(A0); load_B(B2);
-  GW_WAIT(4);
-  const int nplain = DENSE ? nch : nch - 8;          // chunks outside the diagonal block: a multiple of 8 (of 4: dense)
-  for (int c = 0; c < nplain; c += 4) {
-    GW_CHUNK(A0, B0, c0, c4, (load_A(A1), load_B(B3)));
-    GW_CHUNK(A1, B1, c0, c4, (load_A(A0), load_B(B0)));
-    GW_CHUNK(A0, B2, c0, c4, (load_A(A1), load_B(B1)));
-    GW_CHUNK(A1, B3, c0, c4, (load_A(A0), load_B(B2)));
-    GW_WAIT(4);
+  // the K loop over the nch chunks the operand addresses stand at.  TAG 7 runs it twice and over any chunk count (the others:
+  // once, a multiple of 4 outside the diagonal block): up to three chunks are left behind the last whole trip, and a range
+  // without chunks requests nothing
+#define GW_KLOOP() do { \
+  if (TAG != 7 || nch > 0) { \
+    load_B(B0); load_B(B1); load_A(A0); load_B(B2); \
+    GW_WAIT(4); \
+    const int nplain = DENSE ? nch : nch - 8;          /* chunks outside the diagonal block: a multiple of 8 (of 4: dense) */ \
+    int c = 0; \
+    for (; (TAG == 7) ? (c + 4 <= nplain) : (c < nplain); c += 4) { \
+      GW_CHUNK(A0, B0, c0, c4, (load_A(A1), load_B(B3))); \
+      GW_CHUNK(A1, B1, c0, c4, (load_A(A0), load_B(B0))); \
+      GW_CHUNK(A0, B2, c0, c4, (load_A(A1), load_B(B1))); \
+      GW_CHUNK(A1, B3, c0, c4, (load_A(A0), load_B(B2))); \
+      GW_WAIT(4); \
+    } \
+    if (TAG == 7) { \
+      const int rem = nplain - c;                      /* (scalar) 0 .. 3: their operands are requested already, or next */ \
+      if (rem >= 1) GW_CHUNK(A0, B0, c0, c4, (load_A(A1))); \
+      if (rem >= 2) GW_CHUNK(A1, B1, c0, c4, (load_A(A0))); \
+      if (rem >= 3) GW_CHUNK(A0, B2, c0, c4, (void)0); \
+    } \
+  } } while (0)
+  GW_KLOOP();
+  if (TAG == 7) {
+    // far field: columns [f0, f1) of T(S) against rows [f0, f1) of Psi, into the same accumulators
+    const int nf = f.nf, M = p.K, cgi = j0 / 256;
+    const int fbeg = (kbeg > 0) ? 0 : nf, fend = (kend < M) ? 2 * nf : nf;
+    rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.v1, 0, 0x7fffffff, 0x00020000);
+    rB = __builtin_amdgcn_make_buffer_rsrc((void*)p.v2, 0, 0x7fffffff, 0x00020000);
+    const int64_t ldt = 2 * nf, ldp = f.N;
+#pragma unroll
+    for (int a = 0; a < 4; a++) soA[a] = (int)((((int64_t)cgi * M + i0 + 16 * a) * ldt + fbeg) * 8);
+    voffA = (int)(((int64_t)lc * ldt + 2 * kq) * 8);
+    stepA = GW_CH * 8;
+#pragma unroll
+    for (int s = 0; s < 2; s++) soB[s] = (int)(((int64_t)(fbeg + s) * ldp + j0) * 8);
+    voffB = (int)(((int64_t)2 * kq * ldp + 2 * lc) * 8);
+    stepB = GW_CH * (int)ldp * 8;
+    nlA = 0; nlB = 0;
+    nch = (fend - fbeg) / GW_CH;
+    GW_KLOOP();
   }
+#undef GW_KLOOP
   if (!DENSE) {
     GW_DIAG(A0, B0, 0, (load_A(A1), load_B(B3)));
     GW_DIAG(A1, B1, 1, (load_A(A0), load_B(B0)));
@@ -283,7 +327,7 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
   if (f.epi & (EPI_COLSUMSQ | EPI_COLDOT)) {
     // per-column sums over this tile's 64 rows, one partial row per 64-row tile: o0 / o1 [i0 / 64][N]
     double v0r[16];
-    if (TAG != 6 && (f.epi & EPI_COLDOT)) {
+    if (!QF && (f.epi & EPI_COLDOT)) {
       const gcptr gv0 = (gcptr)p.v0 + i0 + kq;
 #pragma unroll
       for (int a = 0; a < 4; a++)
@@ -292,10 +336,11 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
     }
 #pragma unroll
     for (int hh = 0; hh < 2; hh++) { s2[hh] = dbl2{0.0, 0.0}; sd[hh] = dbl2{0.0, 0.0}; }
-    if (TAG == 6) {
+    if (QF) {
       // Kuf(i0 + 16 a + 4 r + kq, j0 + 32 hh + 2 lc + {0, 1}): the addressing of the C store below, on the B strip; one row
       // tile's eight loads (and four entries of v0) at a time, fenced: hoisted together they spill
       const int voffK = (int)(((int64_t)kq * p.ldb + 2 * lc) * 8);
+      if (TAG == 7) rB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0x7fffffff, 0x00020000);      // (the strip again)
       const gcptr gv0 = (gcptr)p.v0 + i0 + kq;
 #pragma unroll
       for (int a = 0; a < 4; a++) {
@@ -323,7 +368,7 @@ __device__ __forceinline__ void gw_tile(const GemmProblem& p, const WaveFlags& f
     }
 #pragma unroll
     for (int hh = 0; hh < 2; hh++) {
-      if (TAG != 6) {
+      if (!QF) {
 #pragma unroll
         for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -416,7 +461,7 @@ __global__ void __launch_bounds__(256, 2) gemm_wave_kernel(const GemmProblem* __
   const int cg = bid / f.nunits;
   const int u = (bid % f.nunits + cg) % f.nunits;
   const int j0 = cg * 256 + wv * GW_T;
-  if (TAG == 3 || TAG == 5 || TAG == 6) {
+  if (TAG == 3 || TAG == 5 || TAG == 6 || TAG == 7) {
     gw_tile<TAG, KT>(p, f, (f.t0 + u) * GW_T, j0, lane, etabs + ((TAG == 5) ? 64 * wv : 0));
   } else {
     // pair (t0 + u, t1 - 1 - u): the longer K range first (every pair starts on the strip's common end: k = 0 for the
@@ -435,8 +480,8 @@ static int gw_roles() { return gp_switches().strip_wave_roles; }      // bitmask
 
 // would a launch of that role and shape take the wave form?  (engine.hip sizes the partial-sum rows by it: 64-row tiles)
 bool gemm_wave_takes(int role, int maxM, int maxN, int uniform_aligned) {
-  // (role 6 has no other form, so strip_wave_roles does not list it: its caller keeps the Cholesky route when this says no)
-  if (!gw_enabled() || !uniform_aligned || role < 1 || (role > 3 && role != 5 && role != 6) || (role != 6 && !((gw_roles() >> role) & 1))) return false;
+  // (roles 6 and 7 have no other form, so strip_wave_roles does not list it: its caller keeps the Cholesky route when this says no)
+  if (!gw_enabled() || !uniform_aligned || role < 1 || (role > 3 && role != 5 && role != 6 && role != 7) || (role != 6 && role != 7 && !((gw_roles() >> role) & 1))) return false;
   return maxM > 0 && (maxM % GW_T) == 0 && (maxN % 256) == 0 && gp_strip_below_2gib(maxM, maxN, false);
 }
 
@@ -451,8 +496,8 @@ static gp_status gw_launch(gp_handle h, const GemmProblem* d_probs, int batch, i
     if (f.tile_mcount > 0 && 2 * (f.tile_m0 + f.tile_mcount) < tiles) wf.t1 = 2 * (f.tile_m0 + f.tile_mcount);
   }
   const int nt = wf.t1 - wf.t0;
-  wf.nunits = (TAG == 3 || TAG == 5 || TAG == 6) ? nt : (nt + 1) / 2;
-  wf.epi = f.epilogue; wf.alpha = f.alpha; wf.N = N; wf.pad_ = 0; wf.xcols = f.aux_x;
+  wf.nunits = (TAG == 3 || TAG == 5 || TAG == 6 || TAG == 7) ? nt : (nt + 1) / 2;
+  wf.epi = f.epilogue; wf.alpha = f.alpha; wf.N = N; wf.nf = (TAG == 7) ? f.aux_nf : 0; wf.xcols = f.aux_x;
   dim3 grid(wf.nunits * (N / 256), 1, batch);
   hipLaunchKernelGGL((gemm_wave_kernel<TAG, KT>), grid, dim3(256), 0, h->stream, d_probs, wf);
   GP_HIP_CHECK(h, hipGetLastError());
@@ -464,9 +509,10 @@ static gp_status gw_launch(gp_handle h, const GemmProblem* d_probs, int batch, i
 bool launch_gemm_wave(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxN, const GemmFlags& f, gp_status* st) {
   if (!gp_strip_below_2gib(maxM, maxN, false) || !gemm_wave_takes(f.role, maxM, maxN, f.uniform_aligned)) return false;
   if (f.beta != 0.0 || f.triC != TRI_NONE) return false;
-  if (f.role == 6) {
+  if (f.role == 6 || f.role == 7) {
     if (f.alpha != 1.0 || f.scale_mode != 0 || f.tile_m0 || f.tile_mcount) return false;
-    *st = gw_launch<6>(h, d_probs, batch, maxM, maxN, f);
+    if (f.role == 7 && (f.aux_nf <= 0 || (f.aux_nf % GW_CH) != 0)) return false;
+    *st = (f.role == 7) ? gw_launch<7>(h, d_probs, batch, maxM, maxN, f) : gw_launch<6>(h, d_probs, batch, maxM, maxN, f);
     return true;
   }
   if (f.role >= 3 ? !(f.scale_mode == 1 && (f.alpha == 1.0 || f.alpha == 2.0 || f.alpha == 0.5 || f.alpha == 4.0)) : (f.alpha != 1.0)) return false;

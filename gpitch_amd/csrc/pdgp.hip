@@ -120,9 +120,12 @@ gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
 }
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
   if (!p) return GP_ERR_BAD_ARG;
-  if (p->qform != (enable != 0)) { p->qform = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
+  // bit 0: the Q route is allowed; bit 1: every MercerMatern12sm GP's inducing inputs ascend (the far field of its product)
+  const bool on = (enable & 1) != 0, zasc = on && (enable & 2) != 0;
+  if (p->qform != on || p->q_zasc != zasc) { p->qform = on; p->q_zasc = zasc; p->last_params = nullptr; }   // the descriptors depend on the route
   return GP_OK;
 }
+int32_t gp_pdgp_far_field(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far) ? 1 : 0; }
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
@@ -175,7 +178,17 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       b.T2 = ar.take<double>(M * M); b.Wbar = ar.take<double>(M * M); b.R = ar.take<double>(M * M);
       b.G = ar.take<double>(gp_strip_doubles(M, p->maxN, p->gps[g].f32 != 0));
       // (Q route, pdgp_bwd.hip pdgp_qform_select: like the scan's arrays below, reserved before its setters have spoken)
-      if (gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM) b.Q = ar.take<double>(M * M);
+      if (gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM) {
+        b.Q = ar.take<double>(M * M);
+        // (its far field's tables, where the shape admits them: T and Psi are 4 mpad (N / 256 + N / M) rows of M doubles.  They
+        // would fit the b.G strip a Q-route GP never uses only while 4 mpad (1 / 256 + 1 / M) <= 1 — not at M = 64 — so they
+        // have a home of their own at every shape)
+        if (gp_switches().qform_far != 0 && qfar_takes((int)M, p->maxN, p->gps[g].m)) {
+          const QfarSizes qs = qfar_sizes((int)M, p->maxN, p->gps[g].m);
+          b.qf_rng = (int*)ar.take<double>(qs.rng); b.qf_ref = ar.take<double>(qs.ref);
+          b.qf_T = ar.take<double>(qs.T); b.qf_Psi = ar.take<double>(qs.Psi);
+        }
+      }
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;
       b.u = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);
       b.upart = ar.take<double>((size_t)p->nsplit * M);
@@ -241,7 +254,7 @@ gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done);
 gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);
 void pdgp_qform_select(gp_pdgp_plan p, int n);
 void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
-gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n);
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n);
 
 // (re)bind the parameter vector / batch to the device descriptors
 static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad,
@@ -265,11 +278,15 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   p->cb.N = n;
   p->cb.maxM = p->maxM;
   pdgp_qform_select(p, n);
-  p->cb.q0 = p->q0; p->cb.nq = p->nq;
+  p->cb.q0 = p->q0; p->cb.nq = p->nq; p->cb.q_far = p->q_far;
   for (int g = 0; g < p->G; g++) {
     const bool q = pdgp_on_q_route(p, g);
-    p->cb.tasks[g].Qm = q ? p->bw[g].Q : nullptr;
-    p->cb.tasks[g].beta = q ? p->bw[g].alpha : nullptr;
+    CondTask& t = p->cb.tasks[g];
+    t.Qm = q ? p->bw[g].Q : nullptr;
+    t.beta = q ? p->bw[g].alpha : nullptr;
+    t.far_rng = (q && p->q_far) ? p->bw[g].qf_rng : nullptr;
+    t.far_T = (q && p->q_far) ? p->bw[g].qf_T : nullptr;
+    t.far_Psi = (q && p->q_far) ? p->bw[g].qf_Psi : nullptr;
   }
   GP_CHECK(cond_batch_upload(h, p->cb, p->whiten != 0, p->jitter));
   // KL items
@@ -309,7 +326,7 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
   GP_CHECK(pdgp_bind(p, params, x, n, grad, fmean ? fmean : p->fmean, fvar ? fvar : p->fvar));
   if (grad) GP_HIP_CHECK(h, hipMemsetAsync(grad, 0, (size_t)p->nparams * sizeof(double), h->stream));
   // (an ELBO takes the Q route with or without a gradient, so a step's ELBO is one number; predictions never do)
-  const std::function<gp_status()> q_prepare = [&]() -> gp_status { return pdgp_qform_prepare(p, n); };
+  const std::function<gp_status()> q_prepare = [&]() -> gp_status { return pdgp_qform_prepare(p, x, n); };
   GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr));
   bool kl_done = false;   // the whitened KL kernel went to the helper stream with the backward prefetch
   if (grad) GP_CHECK(pdgp_prefetch_backward(p, n, &kl_done));

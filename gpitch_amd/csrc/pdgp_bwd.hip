@@ -29,7 +29,7 @@ static inline const GemmProblem* slot_probs(gp_pdgp_plan p, int slot) { return (
 // over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
 // batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
 void pdgp_qform_select(gp_pdgp_plan p, int n) {
-  p->q0 = p->nq = p->qk0 = 0;
+  p->q0 = p->nq = p->qk0 = 0; p->q_far = false;
   if (!gp_switches().qform || !p->qform || !p->whiten) return;
   int first = -1, last = -1, cnt = 0, m = -1;
   for (int g = 0; g < p->G; g++) {
@@ -56,6 +56,10 @@ void pdgp_qform_select(gp_pdgp_plan p, int n) {
   }
   if (!cond_batch_uniform(p->cb, n) || !gemm_wave_takes(6, p->maxM, n, 1) || !hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, p->maxM, n, cnt)) return;
   p->q0 = first; p->nq = cnt; p->qk0 = qk0;
+  // the product's far field: frames and inducing inputs both promised ascending, the switch, the shape, the tables
+  bool far = gp_switches().qform_far != 0 && p->frames_ascending && p->q_zasc && gemm_wave_takes(7, p->maxM, n, 1) && qfar_takes(p->maxM, n, m);
+  for (int g = first; g <= last; g++) far = far && p->bw[g].qf_T && p->gps[g].M == p->maxM;
+  p->q_far = far;
 }
 
 // the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
@@ -78,6 +82,11 @@ void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
     { GemmProblem& r = P(S_QALPHA); r.A = t.W; r.v0 = params + q.off_qmu; r.o0 = b.alpha; }
     // (the guard reads L through v0: qform_guard_kernel)
     { GemmProblem& r = P(S_QQ); r.A = b.R; r.B = t.W; r.C = b.Q; r.v0 = t.L; }
+    if (p->q_far) {     // (feature tables: cov_item_fill's layout of t.feat — z first, then the frames)
+      QfarItem& it = *(QfarItem*)(p->h_misc.data() + p->off.qf_items + i * sizeof(QfarItem));
+      const size_t nfz = gp_align_up((size_t)2 * sm_mpad(q.m) * M, 32);
+      it = QfarItem{t.z, t.kern.theta, t.feat, t.feat + nfz, b.Q, b.qf_rng, b.qf_ref, b.qf_T, b.qf_Psi, M, 0};
+    }
   }
 }
 
@@ -101,7 +110,11 @@ __global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __r
   }
 }
 
-static gp_status qform_chain(gp_pdgp_plan p) {
+// far_wait: the far field's tables (qfar.hip) follow Q and precede the guard — the guard is one workgroup per GP and, beside
+// the other GPs' strip products, the longest link of this chain, while the tables are what the product waits for.  They read
+// the feature tables of the Kuf builds, which the main stream has enqueued: on the helper stream (far_wait) they first wait
+// for the event cond_batch_run left behind those builds.
+static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wait) {
   gp_handle h = p->h;
   const int nq = p->nq, maxM = p->maxM;
   GemmFlags f;
@@ -113,20 +126,25 @@ static gp_status qform_chain(gp_pdgp_plan p) {
   GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QALPHA), nq, maxM, 1));
   f = GemmFlags(); f.triB = TRI_LOWER;
   GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QQ), nq, maxM, maxM, f));
+  if (p->q_far) {
+    if (far_wait && hipStreamWaitEvent(h->stream, h->ev_feat, 0) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
+    GP_CHECK(launch_qfar_tables(h, (const QfarItem*)(p->d_misc + p->off.qf_items), nq, maxM, p->gps[p->q0].m, x, n));
+  }
   hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
   if (hipGetLastError() != hipSuccess) return gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
   return GP_OK;
 }
 
-// E, R, beta, Q and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
+// E, R, beta, Q, the far field's tables and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
 // (behind the factorisation it has just run, beside the other GPs' strip products), else in line; h->stream waits either way.
-gp_status pdgp_qform_prepare(gp_pdgp_plan p, int n) {
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n) {
   gp_handle h = p->h;
   if (p->nq <= 0) return GP_OK;
   bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
+  if (aux && p->q_far && !p->cb.feat_ready) aux = false;
   if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
   gp_status st;
-  { GpStreamScope on(h, aux ? h->aux_stream : nullptr); st = qform_chain(p); }
+  { GpStreamScope on(h, aux ? h->aux_stream : nullptr); st = qform_chain(p, x, n, aux); }
   hipError_t e = hipSuccess;
   if (aux) {
     e = hipEventRecord(h->ev_q, h->aux_stream);

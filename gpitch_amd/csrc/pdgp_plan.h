@@ -12,7 +12,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // (pdgp_bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
-struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, bytes; };
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   PdgpMiscLayout o;
   GpRegions region;
@@ -23,6 +23,7 @@ static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   o.fin_items = region((size_t)G * hyper_finish_item_bytes());
   o.hy_items = region((size_t)2 * G * sizeof(HyperItem));      // G Kuf-side items, then G Kuu-side items, same order
   o.ks_items = region((size_t)G * sizeof(KufScanItem));       // kuf_scan.hip: one per latent GP, in the families' item order
+  o.qf_items = region((size_t)G * sizeof(QfarItem));          // qfar.hip: one per latent GP of the Q run
   o.bytes = region.off;
   return o;
 }
@@ -53,6 +54,8 @@ struct BwdBufs {  // per-GP backward workspace (device)
   double* Wbar = nullptr;   // M x M
   double* R = nullptr;      // M x M   W^T E
   double* Q = nullptr;      // M x M   R W = W^T E W: the Q route's forward operand (MercerMatern12sm GPs of a whitened float64 plan only)
+  // the Q route's far field (qfar.hip): near ranges, reference points, T and Psi — carved with Q, in the plan's own arena
+  int* qf_rng = nullptr; double* qf_ref = nullptr; double* qf_T = nullptr; double* qf_Psi = nullptr;
   double* R32 = nullptr;    // float32 strips only: M * M floats, the float32 copy of R (gemm_wave_f32.hip)
   double* G = nullptr;      // M x N   K̄uf (dense part R (A D))
   double* u = nullptr;      // M       A gm
@@ -132,6 +135,9 @@ struct gp_pdgp_plan_s {
   // [q0, q0 + nq) that takes it at the bound batch size (nq = 0: none); qk0 = the run's first slot in the compacted batch
   bool qform = false;
   int q0 = 0, nq = 0, qk0 = 0;
+  // far field of the run's product: gp_pdgp_set_qform's second bit — the caller vouches that the inducing inputs
+  // of every MercerMatern12sm GP ascend (they are fixed on this route) — and whether the bound run takes it
+  bool q_zasc = false, q_far = false;
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

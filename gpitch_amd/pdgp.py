@@ -272,7 +272,9 @@ class Pdgp(Parameterized):
         self._params.copy_(h.torch.as_tensor(host))
         self._tcode.copy_(h.torch.as_tensor(tc))
         flatvec.set_grad_needs(h, h.lib.gp_pdgp_set_grad_needs, self._plan, self._gps())
-        h.check(h.lib.gp_pdgp_set_qform(self._plan, int(self._qform_admissible())))
+        # bit 0: the Q route is allowed; bit 1: its inducing inputs ascend, so the product may take its far-field form
+        allow = int(self._qform_admissible())
+        h.check(h.lib.gp_pdgp_set_qform(self._plan, allow | (2 if allow and self._qform_z_ascending() else 0)))
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                             self._free.data_ptr()))
         self._packed_key = self._host_key()
@@ -306,6 +308,18 @@ class Pdgp(Parameterized):
             if not (bound <= 3.0 * M * M):
                 return False
         return found
+
+    def _qform_z_ascending(self):
+        """Do the inducing inputs of every MercerMatern12sm latent GP ascend?  Checked beside the conditioning measure, from the
+        values being packed: the Q route fixes them, and the far-field form of its product walks them in
+        order."""
+        for kern, z in zip(list(self.kern_act) + list(self.kern_com), list(self.za) + list(self.zc)):
+            if int(kern.type_code) != _lib.KERN_MERCER_MATERN12SM:
+                continue
+            zz = np.asarray(z.value, dtype=np.float64).reshape(-1)
+            if not np.all(zz[1:] >= zz[:-1]):
+                return False
+        return True
 
     def _host_key(self):
         """what the packed device copy depends on: every Param value (param_version) and the `.fixed` flags"""

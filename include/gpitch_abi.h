@@ -262,8 +262,15 @@ gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending);
  * the Cholesky route to ~1e-13 of scale).  Q inverts Kuu explicitly, so every evaluation checks ||L||_F^2 ||W||_F^2
  * (>= cond_2(Kuu + jitter I)) per GP on the device: above 4 M^2 the handle's status word is raised and the next
  * gp_check_not_pd / host-scalar call returns GP_ERR_UNSUPPORTED ("qform: ...") and clears it.  Predictions, samples and every
- * other family keep the Cholesky route.  Default 0: today's path; GPITCH_AMD_SWITCHES=qform=0 overrides an enable. */
+ * other family keep the Cholesky route.  Default 0: today's path; GPITCH_AMD_SWITCHES=qform=0 overrides an enable.
+ * enable is a bit mask.  Bit 0 is the permission above.  Bit 1 (with bit 0): the caller vouches that the inducing inputs of every
+ * MercerMatern12sm latent GP ascend.  With frames promised ascending as well (gp_pdgp_set_frames_ascending) and M <= 1024 the
+ * product then contracts, per group of 256 frames, only the rows of Kuf within a lengthscale of the group, and adds the rows
+ * beyond through two tables of rank 2 * partials (padded to a multiple of 4) each: the same G to rounding, bit-identical when
+ * every row is near.  GPITCH_AMD_SWITCHES=qform_far=0 overrides bit 1. */
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable);
+/* 1 when the batch last bound by gp_pdgp_elbo (or its staged forms) took that near-rows-plus-far-field product, else 0 */
+int32_t gp_pdgp_far_field(gp_pdgp_plan p);
 
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the
