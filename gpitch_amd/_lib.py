@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "gp_pdgp_sample", "gp_pdgp_sample_reuse", "gp_pdgp_sample_workspace_bytes",
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
     "gp_pdgp_natgrad_workspace_bytes", "gp_pdgp_natgrad_step",
+    "gp_pdgp_natgrad_adaptive_workspace_bytes", "gp_pdgp_natgrad_step_adaptive", "gp_pdgp_natgrad_counts",
     "gp_sgpr_create", "gp_sgpr_destroy", "gp_sgpr_num_params", "gp_sgpr_workspace_bytes", "gp_sgpr_set_workspace", "gp_sgpr_set_precision",
     "gp_sgpr_bound", "gp_sgpr_bound_grad", "gp_sgpr_residual_grad", "gp_sgpr_exchange_doubles", "gp_sgpr_bound_begin", "gp_sgpr_bound_end", "gp_sgpr_set_graphs", "gp_sgpr_eval_counts", "gp_sgpr_predict_f", "gp_sgpr_predict_f_full", "gp_sgpr_predict_source_full", "gp_sgpr_predict_source_workspace_bytes", "gp_sgpr_predict_source", "gp_sgpr_predict_source_sparse",
     "gp_sgpr_sample_source_sparse", "gp_sgpr_sample_source_workspace_bytes",
@@ -48,6 +49,7 @@ ABI_SYMBOLS = [
     "gp_pdgpb_create", "gp_pdgpb_destroy", "gp_pdgpb_num_params", "gp_pdgpb_layout", "gp_pdgpb_set_grad_needs",
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
     "gp_pdgpb_natgrad_workspace_bytes", "gp_pdgpb_natgrad", "gp_pdgpb_natgrad_refused",
+    "gp_pdgpb_natgrad_adaptive_workspace_bytes", "gp_pdgpb_natgrad_adaptive", "gp_pdgpb_natgrad_counts",
     "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
     "gp_pdgpb_predict_moments_workspace_bytes", "gp_pdgpb_predict_moments",
     "gp_pdgpb_sample_workspace_bytes", "gp_pdgpb_sample",
@@ -189,6 +191,9 @@ def load_library():
         "gp_adam_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, dbl, dbl, dbl, dbl]),
         "gp_pdgp_natgrad_workspace_bytes": (sz, [vp]),
         "gp_pdgp_natgrad_step": (i32, [vp, vp, vp, vp, dbl, vp, vp, sz]),
+        "gp_pdgp_natgrad_adaptive_workspace_bytes": (sz, [vp]),
+        "gp_pdgp_natgrad_step_adaptive": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, sz]),
+        "gp_pdgp_natgrad_counts": (i32, [vp, vp, vp, vp, i32]),
         "gp_sgpr_create": (i32, [vp, C.POINTER(SgprConfig), C.POINTER(vp)]),
         "gp_sgpr_destroy": (i32, [vp]),
         "gp_sgpr_num_params": (i64, [vp]),
@@ -256,6 +261,9 @@ def load_library():
         "gp_pdgpb_natgrad_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_natgrad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl, dbl, vp, vp, sz]),
         "gp_pdgpb_natgrad_refused": (i32, [vp, C.POINTER(i32), i32]),
+        "gp_pdgpb_natgrad_adaptive_workspace_bytes": (sz, [vp]),
+        "gp_pdgpb_natgrad_adaptive": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl, vp, i32, vp, vp, sz]),
+        "gp_pdgpb_natgrad_counts": (i32, [vp, vp, vp, i32]),
         "gp_pdgpb_predict_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_predict_prepare": (i32, [vp, vp, vp, sz]),
         "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),

@@ -114,7 +114,7 @@ __device__ __noinline__ void chol_tile_slow(PT A, unsigned ldu, int M, int nb, i
 }
 
 // Cholesky of one matrix by one workgroup (body shared by chol_kernel and chol_inverse_kernel)
-template <typename PT>
+template <typename PT, bool PER_MATRIX = false>
 __device__ __forceinline__ void chol_body(PT A, const int M, const int64_t ld, int* __restrict__ status,
                                           const int b, const int panel_rows_cap, const int pivot_base) {
   typedef typename ChBytes<PT>::type BT;
@@ -148,7 +148,7 @@ __device__ __forceinline__ void chol_body(PT A, const int M, const int64_t ld, i
     while (mi * (mi + 1) / 2 > t) mi--;
     tile_tab[t] = (unsigned)mi | ((unsigned)(t - mi * (mi + 1) / 2) << 16);
   }
-  if (wave == 0) chol_diag_block(A, ld, M, 0, lane, D[0], status, b, pivot_base);
+  if (wave == 0) chol_diag_block<PT, PER_MATRIX>(A, ld, M, 0, lane, D[0], status, b, pivot_base);
   __syncthreads();
 
   int pb = 0;
@@ -268,7 +268,7 @@ __device__ __forceinline__ void chol_body(PT A, const int M, const int64_t ld, i
     auto after_tile0 = [&]() {     // the wavefront that has just updated the next diagonal block factorises it
       __threadfence_block();  // this wave's own updates of the block it is about to read back
       if (lane == 0) CH_STAMP(k0 / CH_NB, 3);
-      chol_diag_block(A, ld, M, r0, lane, D[pb ^ 1], status, b, pivot_base);
+      chol_diag_block<PT, PER_MATRIX>(A, ld, M, r0, lane, D[pb ^ 1], status, b, pivot_base);
       if (lane == 0) CH_STAMP(k0 / CH_NB, 4);
     };
     CH_PH_DECL;
@@ -486,21 +486,44 @@ __global__ void __launch_bounds__(CH_THREADS) tri_inverse_kernel(const double* c
 // Factor and invert in ONE launch: the workgroup of a matrix stays resident from the first pivot to the last block of
 // W.  Used when device-filling kernels (the Kuf strip builds) run beside the factorisation: a 512-thread,
 // 256-VGPR workgroup needs an empty CU, which a second launch would not get until those kernels have drained.
+// PER_MATRIX (the natural-gradient step's rounds, natgrad.hip): `status` is the batch's outcome array, status[b] = 0 or
+// 1 + the first bad pivot of matrix b, and the handle's word is left alone; an empty slot (M = 0) returns at once, as in
+// chol_kernel.  The form every other caller uses is the instantiation without it: the code it was (no caller hands it an
+// empty slot, and the guard would cost the LDS-resident form two VGPRs).
+template <bool PER_MATRIX>
+__device__ __forceinline__ void chol_inverse_entry(double* const* __restrict__ mats, double* const* __restrict__ Ws,
+                                                   const int* __restrict__ Ms, const int* __restrict__ lds_,
+                                                   int* __restrict__ status, int panel_rows_cap, double* single_mat,
+                                                   double* single_W, int single_M, int single_ld) {
+  const int b = blockIdx.x;
+  double* A = mats ? mats[b] : single_mat;
+  double* W = mats ? Ws[b] : single_W;
+  const int M = mats ? Ms[b] : single_M;
+  const int64_t ld = mats ? (int64_t)lds_[b] : (int64_t)single_ld;
+  if (PER_MATRIX && M <= 0) return;    // an empty slot: a GP whose length is already settled (natgrad.hip)
+  if (PER_MATRIX) {
+    if (threadIdx.x == 0) atomicExch(&status[b], 0);
+    __syncthreads();
+  }
+  chol_body<ch_gptr, PER_MATRIX>((ch_gptr)A, M, ld, status, b, panel_rows_cap, 0);
+  __threadfence();
+  __syncthreads();
+  tri_inverse_body((ch_gcptr)A, (ch_gptr)W, M, ld);
+}
 __global__ void __launch_bounds__(CH_THREADS) chol_inverse_kernel(double* const* __restrict__ mats,
                                                                   double* const* __restrict__ Ws,
                                                                   const int* __restrict__ Ms, const int* __restrict__ lds_,
                                                                   int* __restrict__ status, int panel_rows_cap,
                                                                   double* single_mat, double* single_W, int single_M,
                                                                   int single_ld) {
-  const int b = blockIdx.x;
-  double* A = mats ? mats[b] : single_mat;
-  double* W = mats ? Ws[b] : single_W;
-  const int M = mats ? Ms[b] : single_M;
-  const int64_t ld = mats ? (int64_t)lds_[b] : (int64_t)single_ld;
-  chol_body((ch_gptr)A, M, ld, status, b, panel_rows_cap, 0);
-  __threadfence();
-  __syncthreads();
-  tri_inverse_body((ch_gcptr)A, (ch_gptr)W, M, ld);
+  chol_inverse_entry<false>(mats, Ws, Ms, lds_, status, panel_rows_cap, single_mat, single_W, single_M, single_ld);
+}
+__global__ void __launch_bounds__(CH_THREADS) chol_inverse_outcome_kernel(double* const* __restrict__ mats,
+                                                                          double* const* __restrict__ Ws,
+                                                                          const int* __restrict__ Ms,
+                                                                          const int* __restrict__ lds_,
+                                                                          int* __restrict__ outcome, int panel_rows_cap) {
+  chol_inverse_entry<true>(mats, Ws, Ms, lds_, outcome, panel_rows_cap, nullptr, nullptr, 0, 0);
 }
 
 // Matrices of at most 64 rows (the window-sized SGPR problems, small inducing sets): the whole factor + inverse runs on
@@ -511,25 +534,27 @@ __global__ void __launch_bounds__(CH_THREADS) chol_inverse_kernel(double* const*
 #define CHS_LD (CHS_M + 1)
 #define CHS_OFF (2 * CH_NB * CH_LDP + (CHS_M - CH_NB) * CH_LDP)     // chol_body's own D | P region
 #define CHS_DOUBLES (CHS_OFF + 2 * CHS_M * CHS_LD)
-__global__ void __launch_bounds__(CH_THREADS) chol_inverse_lds_kernel(double* const* __restrict__ mats,
-                                                                      double* const* __restrict__ Ws,
-                                                                      const int* __restrict__ Ms, const int* __restrict__ lds_,
-                                                                      int* __restrict__ status, double* single_mat,
-                                                                      double* single_W, int single_M, int single_ld) {
+template <bool PER_MATRIX>
+__device__ __forceinline__ void chol_inverse_lds_entry(double* const* __restrict__ mats, double* const* __restrict__ Ws,
+                                                       const int* __restrict__ Ms, const int* __restrict__ lds_,
+                                                       int* __restrict__ status, double* single_mat, double* single_W,
+                                                       int single_M, int single_ld) {
   extern __shared__ __attribute__((aligned(16))) double chol_smem[];
   const int b = blockIdx.x;
   double* A = mats ? mats[b] : single_mat;
   double* W = mats ? Ws[b] : single_W;
   const int M = mats ? Ms[b] : single_M;
   const int64_t ld = mats ? (int64_t)lds_[b] : (int64_t)single_ld;
+  if (PER_MATRIX && M <= 0) return;    // an empty slot: a GP whose length is already settled (natgrad.hip)
   double* Al = chol_smem + CHS_OFF;
   double* Wl = Al + CHS_M * CHS_LD;
+  if (PER_MATRIX && threadIdx.x == 0) atomicExch(&status[b], 0);
   for (int idx = threadIdx.x; idx < M * M; idx += CH_THREADS) {
     const int i = idx / M, j = idx % M;
     Al[i * CHS_LD + j] = A[(int64_t)i * ld + j];
   }
   __syncthreads();
-  chol_body(Al, M, CHS_LD, status, b, CHS_M - CH_NB, 0);
+  chol_body<double*, PER_MATRIX>(Al, M, CHS_LD, status, b, CHS_M - CH_NB, 0);
   __threadfence_block();
   __syncthreads();
   tri_inverse_body((const double*)Al, Wl, M, CHS_LD);
@@ -540,6 +565,20 @@ __global__ void __launch_bounds__(CH_THREADS) chol_inverse_lds_kernel(double* co
     A[(int64_t)i * ld + j] = Al[i * CHS_LD + j];
     W[(int64_t)i * ld + j] = Wl[i * CHS_LD + j];
   }
+}
+__global__ void __launch_bounds__(CH_THREADS) chol_inverse_lds_kernel(double* const* __restrict__ mats,
+                                                                      double* const* __restrict__ Ws,
+                                                                      const int* __restrict__ Ms, const int* __restrict__ lds_,
+                                                                      int* __restrict__ status, double* single_mat,
+                                                                      double* single_W, int single_M, int single_ld) {
+  chol_inverse_lds_entry<false>(mats, Ws, Ms, lds_, status, single_mat, single_W, single_M, single_ld);
+}
+__global__ void __launch_bounds__(CH_THREADS) chol_inverse_lds_outcome_kernel(double* const* __restrict__ mats,
+                                                                              double* const* __restrict__ Ws,
+                                                                              const int* __restrict__ Ms,
+                                                                              const int* __restrict__ lds_,
+                                                                              int* __restrict__ outcome) {
+  chol_inverse_lds_entry<true>(mats, Ws, Ms, lds_, outcome, nullptr, nullptr, 0, 0);
 }
 
 static size_t chol_smem_bytes(int maxM, int* cap) {
@@ -582,6 +621,9 @@ static gp_status chol_inverse_set_attr(gp_handle h) {
     GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)chol_inverse_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)(CHS_DOUBLES * sizeof(double))));
     GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)chol_inverse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)chol_inverse_lds_outcome_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(CHS_DOUBLES * sizeof(double))));
+    GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)chol_inverse_outcome_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     done.fetch_or(bit, std::memory_order_release);
   }
   return GP_OK;
@@ -600,6 +642,25 @@ gp_status launch_cholesky_inverse_batched(gp_handle h, double* const* d_mats, do
   else
     hipLaunchKernelGGL(chol_inverse_kernel, dim3(batch), dim3(CH_THREADS), sh, h->stream, d_mats, d_W, d_M, d_ld, h->d_status,
                        cap, (double*)nullptr, (double*)nullptr, 0, 0);
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
+// the same batch with a per-matrix outcome: d_outcome[b] = 0 or 1 + the first bad pivot of matrix b, for every slot of size > 0
+// (a slot of size 0 is skipped and its word kept); the handle's status word is not written
+gp_status launch_cholesky_inverse_batched_outcome(gp_handle h, double* const* d_mats, double* const* d_W, const int* d_M,
+                                                  const int* d_ld, int batch, int maxM, int32_t* d_outcome) {
+  if (batch <= 0) return GP_OK;
+  GpTimerScope ts(h, GP_TIMER_CHOL);
+  int cap = 0;
+  size_t sh = chol_smem_bytes(maxM, &cap);
+  GP_CHECK(chol_inverse_set_attr(h));
+  if (maxM <= CHS_M)
+    hipLaunchKernelGGL(chol_inverse_lds_outcome_kernel, dim3(batch), dim3(CH_THREADS), CHS_DOUBLES * sizeof(double), h->stream,
+                       d_mats, d_W, d_M, d_ld, (int*)d_outcome);
+  else
+    hipLaunchKernelGGL(chol_inverse_outcome_kernel, dim3(batch), dim3(CH_THREADS), sh, h->stream, d_mats, d_W, d_M, d_ld,
+                       (int*)d_outcome, cap);
   GP_HIP_CHECK(h, hipGetLastError());
   return GP_OK;
 }

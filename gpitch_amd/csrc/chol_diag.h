@@ -43,7 +43,9 @@ __device__ __forceinline__ void pivot_sqrt_recip(double x, double& s, double& ri
 // for the matrix loads / stores in flight.
 typedef double __attribute__((address_space(1))) * ch_gptr;
 typedef const double __attribute__((address_space(1))) * ch_gcptr;
-template <typename PT>
+// PER_MATRIX: `status` is an outcome array with one word per matrix of the batch instead of the handle's word: the first bad
+// pivot of matrix b leaves 1 + pivot in status[b] (the caller has cleared it), and the handle's word is not touched.
+template <typename PT, bool PER_MATRIX = false>
 __device__ __noinline__ void chol_diag_block(PT A, int64_t ld, int M, int k0, int lane,
                                                 double (*Dinv)[CH_LDP], int* __restrict__ status, int b, int pbase) {
   // Factor and inverse in ONE pass over the pivots, the two halves of the wavefront doing one each:
@@ -98,7 +100,8 @@ __device__ __noinline__ void chol_diag_block(PT A, int64_t ld, int M, int k0, in
 #endif
   }
   if (bad >= 0 && lane == 0) {
-    if (atomicCAS(&status[0], 0, 1) == 0) { status[1] = pbase + k0 + bad; status[2] = b; }
+    if (PER_MATRIX) atomicCAS(&status[b], 0, 1 + pbase + k0 + bad);
+    else if (atomicCAS(&status[0], 0, 1) == 0) { status[1] = pbase + k0 + bad; status[2] = b; }
   }
   // pin v[] here: otherwise the arithmetic is sunk into the lane-conditional stores below while its (convergent) lane
   // broadcasts stay outside, hundreds of them live at once and spilled

@@ -255,6 +255,9 @@ gp_status launch_tri_inverse_single(gp_handle h, const double* L, double* Linv, 
 // Cholesky factor (in place) and its inverse in one launch, one resident workgroup per matrix
 gp_status launch_cholesky_inverse_batched(gp_handle h, double* const* d_mats, double* const* d_W, const int* d_M,
                                           const int* d_ld, int batch, int maxM);
+// ... with d_outcome[b] = 0 or 1 + first bad pivot per matrix instead of the handle's status word; slots of size 0 are skipped
+gp_status launch_cholesky_inverse_batched_outcome(gp_handle h, double* const* d_mats, double* const* d_W, const int* d_M,
+                                                  const int* d_ld, int batch, int maxM, int32_t* d_outcome);
 gp_status launch_cholesky_inverse_single(gp_handle h, double* A, double* W, int M, int64_t ld);
 gp_status launch_zero_upper_blocks_batched(gp_handle h, double* const* d_mats, const int* d_M, const int* d_ld, int batch,
                                            int maxM, int nb);

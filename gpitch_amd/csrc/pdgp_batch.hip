@@ -77,6 +77,9 @@ struct gp_pdgpb_plan_s {
   const void* ng_ws = nullptr;
   int32_t* d_refused = nullptr;
   std::vector<PbNgGp> ng_list;
+  // gp_pdgpb_natgrad_adaptive: the workspace whose counters the plan has cleared, and their place
+  const void* nga_ws = nullptr;
+  int64_t* d_ng_halv = nullptr; double* d_ng_short = nullptr;
   // prediction-only plans: G blocks (doubles; PbGp::ws is a GP's offset among them), the per-call records, and the
   // workspace / parameters of the last gp_pdgpb_predict_prepare
   int64_t pred_g = 0;
@@ -267,7 +270,8 @@ __device__ inline PbScr pb_scr(double* base, int M, int B) {
 // place by the whole workgroup: on return Ls holds the inverse of its lower Cholesky factor L, zeros above the diagonal; L
 // itself is copied to Lcopy (global) when COPY_L.  tmp: M doubles of LDS.  Shared by Kuu + jitter I (pb_factor_invert) and
 // the natural-gradient step's reversed B (pdgpb_ng_form_kernel); `word` is the model's word for this kind of failure.
-template <bool COPY_L>
+// RAISE = false (the adaptive natural-gradient step, which factors again at half the length): the word is left to the caller.
+template <bool COPY_L, bool RAISE = true>
 __device__ __forceinline__ void pb_chol_invert(int M, double* Ls, double* tmp, int& bad_pivot, int32_t* __restrict__ word,
                                                int row, double* Lcopy) {
   const int tid = threadIdx.x;
@@ -297,7 +301,7 @@ __device__ __forceinline__ void pb_chol_invert(int M, double* Ls, double* tmp, i
   __syncthreads();
   // status word of the model: 0, or INT_MAX - (128 row + pivot); the maximum keeps the failure with the smallest
   // (row, pivot) whatever order the model's workgroups finish in
-  if (tid == 0 && bad_pivot >= 0) atomicMax(word, 0x7fffffff - (PB_MAX_M * row + bad_pivot));
+  if (RAISE && tid == 0 && bad_pivot >= 0) atomicMax(word, 0x7fffffff - (PB_MAX_M * row + bad_pivot));
   if (COPY_L)
     for (int e = tid; e < M * M; e += PB_THREADS) Lcopy[e] = Ls[e];
   __syncthreads();
@@ -629,10 +633,24 @@ typedef double pb_d4 __attribute__((ext_vector_type(4)));
 // LDS: [maxM^2 reversed B -> C -> C^-1 | maxM tmp].  Phi_ij = sum_{k >= max(i, j)} Lq_ki G_kj over 16 x 16 sub-tiles (ti, tj <=
 // ti) of the lower triangle, dealt to the four wavefronts in turn; the k loop starts at the sub-tile's first row, and the masks
 // k >= i, k >= j are the two tril()s: the stored strict upper triangle of q_sqrt may hold anything.
-__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_form_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
-                                                                   const double* __restrict__ params, const double* __restrict__ grad,
-                                                                   double gamma, double* __restrict__ blocks,
-                                                                   int32_t* __restrict__ refused, int maxM) {
+// ADAPT (gp_pdgpb_natgrad_adaptive): the length is the GP's own, ad.gamma[g], and a recorded non-positive pivot
+// with halvings left forms B again at half the length (there is no room for a second copy at M = 128; Phi is recomputed from
+// params / grad, which this kernel does not write).  The branch is uniform over the workgroup.  The accepted length and j go to
+// ad.len / ad.j; the refusal word is raised only when the last length fails.
+struct PbNgAdapt {
+  const double* gamma;   // per latent GP of the plan: gamma_r
+  double* len;           // the length its B was accepted at (the last tried, if none was)
+  int32_t* j;            // its halvings of this iteration
+  int64_t* halv;         // the call's counters: sum of j over the iterations of steps taken,
+  double* shortest;      //   and the smallest length taken
+  int halvings;
+};
+struct PbNgNone {};
+template <bool ADAPT, typename AD>
+__device__ __forceinline__ void pb_ng_form_body(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                const double* __restrict__ params, const double* __restrict__ grad,
+                                                double gamma, double* __restrict__ blocks, int32_t* __restrict__ refused,
+                                                int maxM, const AD& ad) {
   extern __shared__ double pb_sm[];
   __shared__ int bad_pivot;
   const PbNgGp e = list[blockIdx.x];
@@ -646,60 +664,102 @@ __global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_form_kernel(const PbGp* _
   double* __restrict__ Cinv = blocks + e.ws;
   if (tid == 0) bad_pivot = -1;
   const int kq = lane >> 4, lc = lane & 15, T = (M + 15) >> 4;
-  int s = 0;
-  for (int ti = 0; ti < T; ti++)
-    for (int tj = 0; tj <= ti; tj++, s++) {
-      if ((s & 3) != wave) continue;                         // wave-uniform
-      const int i0 = 16 * ti, j0 = 16 * tj;
-      const int ia = i0 + lc, jb = j0 + lc;
-      pb_d4 acc = {0.0, 0.0, 0.0, 0.0};
-      for (int kk = i0; kk < M; kk += 4) {
-        const int k = kk + kq;
-        const bool kin = k < M;
-        const double av = (kin && ia < M && k >= ia) ? Lq[(int64_t)k * M + ia] : 0.0;    // A(i, k) = Lq(k, i)
-        const double bv = (kin && jb < M && k >= jb) ? GL[(int64_t)k * M + jb] : 0.0;    // B(k, j) = G_L(k, j)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-      }
+  double gamma0 = gamma;
+  if constexpr (ADAPT) gamma0 = ad.gamma[e.g];
+  for (int jh = 0;; jh++) {
+    if constexpr (ADAPT) gamma = scalbn(gamma0, -jh);       // an exact scaling; jh = 0 is gamma_r itself
+    int s = 0;
+    for (int ti = 0; ti < T; ti++)
+      for (int tj = 0; tj <= ti; tj++, s++) {
+        if ((s & 3) != wave) continue;                         // wave-uniform
+        const int i0 = 16 * ti, j0 = 16 * tj;
+        const int ia = i0 + lc, jb = j0 + lc;
+        pb_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int kk = i0; kk < M; kk += 4) {
+          const int k = kk + kq;
+          const bool kin = k < M;
+          const double av = (kin && ia < M && k >= ia) ? Lq[(int64_t)k * M + ia] : 0.0;    // A(i, k) = Lq(k, i)
+          const double bv = (kin && jb < M && k >= jb) ? GL[(int64_t)k * M + jb] : 0.0;    // B(k, j) = G_L(k, j)
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        }
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int i = i0 + kq + 4 * q, j = j0 + lc;
-        if (i < M && j <= i) {
-          const double v = (i == j ? 1.0 : 0.0) - gamma * acc[q];
-          const int ri = M - 1 - i, rj = M - 1 - j;          // rj >= ri: (rj, ri) is in the lower triangle of the reversed matrix
-          Bs[rj * M + ri] = v;
-          Bs[ri * M + rj] = v;
+        for (int q = 0; q < 4; q++) {
+          const int i = i0 + kq + 4 * q, j = j0 + lc;
+          if (i < M && j <= i) {
+            const double v = (i == j ? 1.0 : 0.0) - gamma * acc[q];
+            const int ri = M - 1 - i, rj = M - 1 - j;          // rj >= ri: (rj, ri) is in the lower triangle of the reversed matrix
+            Bs[rj * M + ri] = v;
+            Bs[ri * M + rj] = v;
+          }
         }
       }
+    // w_i = sum_{k >= i} Lq_ki g_k: thread i, k ascending
+    if (jh == 0 && tid < M) {
+      const double* __restrict__ gq = grad + g.off_qmu;
+      double a = 0.0;
+      for (int k = tid; k < M; k++) a = fma(Lq[(int64_t)k * M + tid], gq[k], a);
+      Cinv[(int64_t)M * M + tid] = a;
     }
-  // w_i = sum_{k >= i} Lq_ki g_k: thread i, k ascending
-  if (tid < M) {
-    const double* __restrict__ gq = grad + g.off_qmu;
-    double a = 0.0;
-    for (int k = tid; k < M; k++) a = fma(Lq[(int64_t)k * M + tid], gq[k], a);
-    Cinv[(int64_t)M * M + tid] = a;
+    __syncthreads();
+    // the pivot replaced by 1 keeps every loop's trip count and the pass finite whatever the gradient held (a model whose Kuu
+    // failed in this evaluation hands over garbage; its Kuu word, raised by the forward launch, is what the host reports)
+    pb_chol_invert<false, !ADAPT>(M, Bs, tmp, bad_pivot, &refused[g.model], g.row, nullptr);
+    if constexpr (!ADAPT) break;
+    else {
+      const int bp = bad_pivot;                                // (pb_chol_invert ends behind a barrier)
+      __syncthreads();
+      if (bp < 0 || jh == ad.halvings) {
+        if (tid == 0) {
+          if (bp >= 0) atomicMax(&refused[g.model], 0x7fffffff - (PB_MAX_M * g.row + bp));
+          ad.len[e.g] = gamma;
+          ad.j[e.g] = jh;
+        }
+        break;
+      }
+      if (tid == 0) bad_pivot = -1;
+      __syncthreads();
+    }
   }
-  __syncthreads();
-  // the pivot replaced by 1 keeps every loop's trip count and the pass finite whatever the gradient held (a model whose Kuu
-  // failed in this evaluation hands over garbage; its Kuu word, raised by the forward launch, is what the host reports)
-  pb_chol_invert<false>(M, Bs, tmp, bad_pivot, &refused[g.model], g.row, nullptr);
   for (int i = tid; i < M * M; i += PB_THREADS) Cinv[i] = Bs[i];
+}
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_form_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                                   const double* __restrict__ params, const double* __restrict__ grad,
+                                                                   double gamma, double* __restrict__ blocks,
+                                                                   int32_t* __restrict__ refused, int maxM) {
+  pb_ng_form_body<false>(gps, list, params, grad, gamma, blocks, refused, maxM, PbNgNone{});
+}
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_form_adaptive_kernel(const PbGp* __restrict__ gps,
+                                                                            const PbNgGp* __restrict__ list,
+                                                                            const double* __restrict__ params,
+                                                                            const double* __restrict__ grad, const PbNgAdapt ad,
+                                                                            double* __restrict__ blocks,
+                                                                            int32_t* __restrict__ refused, int maxM) {
+  pb_ng_form_body<true>(gps, list, params, grad, 0.0, blocks, refused, maxM, ad);
 }
 
 // Lq' = Lq V, V = U^-T (V_kj = Cinv(M-1-j, M-1-k), lower);  q_mu' = q_mu + gamma Lq' t, t = V^T w.  Row i of Lq' needs row i of
 // Lq and nothing else of it, so the update runs in place: column tiles ascend, tile tj reads Lq(i, k) for k >= 32 tj only and
 // overwrites columns [32 tj, 32 tj + 32) after a barrier, so no wavefront reads what another has replaced.
 // LDS: [t (maxM, padded to even) | 32 x 33 row shares]
-__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_apply_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
-                                                                    double* __restrict__ params, double* __restrict__ fs,
-                                                                    double* __restrict__ grad, double gamma,
-                                                                    const double* __restrict__ blocks,
-                                                                    const int32_t* __restrict__ status,
-                                                                    const int32_t* __restrict__ refused) {
+template <bool ADAPT, typename AD>
+__device__ __forceinline__ void pb_ng_apply_body(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                 double* __restrict__ params, double* __restrict__ fs, double* __restrict__ grad,
+                                                 double gamma, const double* __restrict__ blocks,
+                                                 const int32_t* __restrict__ status, const int32_t* __restrict__ refused,
+                                                 const AD& ad) {
   extern __shared__ double pb_sm[];
   const PbNgGp e = list[blockIdx.x];
   const PbGp g = gps[e.g];
   const int M = g.M, ti = blockIdx.y, row0 = ti * PB_NG_TILE;
   if (row0 >= M || status[g.model] != 0 || refused[g.model] != 0) return;       // (uniform over the workgroup)
+  if constexpr (ADAPT) {
+    // the length this GP's B was accepted at; the call's counters, once per GP and step taken
+    gamma = ad.len[e.g];
+    if (ti == 0 && threadIdx.x == 0) {
+      ad.halv[e.g] += ad.j[e.g];
+      ad.shortest[e.g] = fmin(ad.shortest[e.g], gamma);
+    }
+  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int iend = min(M, row0 + PB_NG_TILE);
@@ -774,6 +834,23 @@ __global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_apply_kernel(const PbGp* 
   double* __restrict__ GLrows = grad + g.off_qsq + (int64_t)row0 * M;
   const int cnt = (iend - row0) * M;
   for (int idx = tid; idx < cnt; idx += PB_THREADS) GLrows[idx] = 0.0;
+}
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_apply_kernel(const PbGp* __restrict__ gps, const PbNgGp* __restrict__ list,
+                                                                    double* __restrict__ params, double* __restrict__ fs,
+                                                                    double* __restrict__ grad, double gamma,
+                                                                    const double* __restrict__ blocks,
+                                                                    const int32_t* __restrict__ status,
+                                                                    const int32_t* __restrict__ refused) {
+  pb_ng_apply_body<false>(gps, list, params, fs, grad, gamma, blocks, status, refused, PbNgNone{});
+}
+__global__ void __launch_bounds__(PB_THREADS) pdgpb_ng_apply_adaptive_kernel(const PbGp* __restrict__ gps,
+                                                                             const PbNgGp* __restrict__ list,
+                                                                             double* __restrict__ params, double* __restrict__ fs,
+                                                                             double* __restrict__ grad, const PbNgAdapt ad,
+                                                                             const double* __restrict__ blocks,
+                                                                             const int32_t* __restrict__ status,
+                                                                             const int32_t* __restrict__ refused) {
+  pb_ng_apply_body<true>(gps, list, params, fs, grad, 0.0, blocks, status, refused, ad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1302,43 +1379,82 @@ size_t gp_pdgpb_natgrad_workspace_bytes(gp_pdgpb_plan p) {
   return gp_measure([&](GpArena& ar) { pb_ng_regions(p, ar); }) + GP_WS_TAIL_BATCH;
 }
 
-gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
-                           const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
-                           double beta1, double beta2, double eps, double gamma, const int32_t* step_gp_host,
-                           void* workspace, size_t workspace_bytes) {
+// the adaptive step's workspace: gp_pdgpb_natgrad's regions, then per latent GP of the plan [gamma_r | accepted length | j |
+// counters]
+struct PbNgaRegions { PbNgRegions r; double* gamma; double* len; int32_t* j; int64_t* halv; double* shortest; };
+static PbNgaRegions pb_nga_regions(const gp_pdgpb_plan_s* p, GpArena& ar) {
+  PbNgaRegions a;
+  a.r = pb_ng_regions(p, ar);
+  const size_t G = p->gps.size();
+  a.gamma = ar.take<double>(G);
+  a.len = ar.take<double>(G);
+  a.j = ar.take<int32_t>(G);
+  a.halv = ar.take<int64_t>(G);
+  a.shortest = ar.take<double>(G);
+  return a;
+}
+#define PB_NG_SHORT_CLEAR_BYTE 0x7f    // a cleared `shortest` counter: every byte 0x7f, a double far above any gamma; read back as +inf
+
+// gp_pdgpb_natgrad (gamma_gp_host null: one length, `gamma`) and gp_pdgpb_natgrad_adaptive
+static gp_status pb_natgrad_run(gp_pdgpb_plan p, const char* name, double* free_state, double* params, const uint8_t* tcode,
+                                double* m, double* v, const double* x, const double* y, const int32_t* idx, int32_t steps,
+                                const double* lr_t, double beta1, double beta2, double eps, double gamma,
+                                const double* gamma_gp_host, int32_t halvings, const int32_t* step_gp_host, void* workspace,
+                                size_t workspace_bytes) {
   if (!p) return GP_ERR_BAD_ARG;
   gp_handle h = p->h;
+  const bool adapt = gamma_gp_host != nullptr;
+  const std::string nm(name);
   if (!free_state || !params || !tcode || !m || !v || !x || !y || !idx || !lr_t || !workspace || steps < 0 || p->predict_only)
-    return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: bad argument or a prediction-only plan");
-  if (!(gamma > 0.0 && gamma <= 1.0)) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: gamma must lie in (0, 1]");
-  if (((uintptr_t)workspace & 255) != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad: workspace not 256-byte aligned");
-  if (workspace_bytes < gp_pdgpb_natgrad_workspace_bytes(p))
-    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad: workspace too small (gp_pdgpb_natgrad_workspace_bytes)");
+    return gp_fail(h, GP_ERR_BAD_ARG, (nm + ": bad argument or a prediction-only plan").c_str());
+  if (adapt) {
+    for (int g = 0; g < p->G; g++)
+      if (!(gamma_gp_host[g] > 0.0 && gamma_gp_host[g] <= 1.0))
+        return gp_fail(h, GP_ERR_BAD_ARG, (nm + ": every gamma must lie in (0, 1]").c_str());
+    if (halvings < 0 || halvings > 10) return gp_fail(h, GP_ERR_BAD_ARG, (nm + ": halvings must lie in 0..10").c_str());
+  } else if (!(gamma > 0.0 && gamma <= 1.0)) {
+    return gp_fail(h, GP_ERR_BAD_ARG, (nm + ": gamma must lie in (0, 1]").c_str());
+  }
+  if (((uintptr_t)workspace & 255) != 0) return gp_fail(h, GP_ERR_BAD_ARG, (nm + ": workspace not 256-byte aligned").c_str());
+  if (workspace_bytes < (adapt ? gp_pdgpb_natgrad_adaptive_workspace_bytes(p) : gp_pdgpb_natgrad_workspace_bytes(p)))
+    return gp_fail(h, GP_ERR_WORKSPACE, (nm + ": workspace too small (" + nm + "_workspace_bytes)").c_str());
   GpArena ar(workspace, workspace_bytes);
-  const PbNgRegions r = pb_ng_regions(p, ar);
-  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad: arena overflow");
+  PbNgaRegions a = {};
+  if (adapt) a = pb_nga_regions(p, ar); else a.r = pb_ng_regions(p, ar);
+  const PbNgRegions r = a.r;
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, (nm + ": arena overflow").c_str());
   GP_CHECK(pb_upload(p));
   if (workspace != p->ng_ws) {          // a workspace the plan has not seen: no model is refused yet
     GP_HIP_CHECK(h, hipMemsetAsync(r.refused, 0, p->nm * sizeof(int32_t), h->stream));
     p->ng_ws = workspace;
     p->d_refused = r.refused;
   }
+  if (adapt && workspace != p->nga_ws) {   // ... and its counters start cleared
+    GP_HIP_CHECK(h, hipMemsetAsync(a.halv, 0, p->gps.size() * sizeof(int64_t), h->stream));
+    GP_HIP_CHECK(h, hipMemsetAsync(a.shortest, PB_NG_SHORT_CLEAR_BYTE, p->gps.size() * sizeof(double), h->stream));
+    p->nga_ws = workspace;
+    p->d_ng_halv = a.halv; p->d_ng_short = a.shortest;
+  }
   p->ng_list.clear();
   for (int g = 0; g < p->G; g++)
     if (!step_gp_host || step_gp_host[g]) p->ng_list.push_back(PbNgGp{g, 0, p->ng_off[g]});
   const int nstep = (int)p->ng_list.size();
   if (nstep > 0) {
-    GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_ng_form_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_ng_form_lds(p)));
+    if (adapt) GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_ng_form_adaptive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_ng_form_lds(p)));
+    else GP_HIP_CHECK(h, hipFuncSetAttribute((const void*)pdgpb_ng_form_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pb_ng_form_lds(p)));
     GP_HIP_CHECK(h, hipMemcpyAsync(r.list, p->ng_list.data(), nstep * sizeof(PbNgGp), hipMemcpyHostToDevice, h->stream));
-    // pageable host memory: the list may be rebuilt by the next call
+    if (adapt)
+      GP_HIP_CHECK(h, hipMemcpyAsync(a.gamma, gamma_gp_host, p->G * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // pageable host memory: the list may be rebuilt by the next call, the caller's lengths may go away
     GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   }
+  const PbNgAdapt ad = {a.gamma, a.len, a.j, a.halv, a.shortest, (int)halvings};
   const int64_t n = p->nparams;
   const int blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n + 255) / 256));
   const int row_blocks = (p->maxM + PB_NG_TILE - 1) / PB_NG_TILE;
   for (int s = 0; s < steps; s++) {
     GP_CHECK(pb_eval(p, params, x, y, idx + (int64_t)s * p->sumB, p->d_elbo, p->d_grad));
-    if (nstep > 0) {
+    if (nstep > 0 && !adapt) {
       hipLaunchKernelGGL(pdgpb_ng_form_kernel, dim3(nstep), dim3(PB_THREADS), pb_ng_form_lds(p), h->stream, p->d_gps, r.list,
                          (const double*)params, (const double*)p->d_grad, gamma, r.blocks, r.refused, p->maxM);
       GP_HIP_CHECK(h, hipGetLastError());
@@ -1346,11 +1462,60 @@ gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, 
                          p->d_gps, r.list, params, free_state, p->d_grad, gamma, (const double*)r.blocks,
                          (const int32_t*)p->d_status, (const int32_t*)r.refused);
       GP_HIP_CHECK(h, hipGetLastError());
+    } else if (nstep > 0) {
+      hipLaunchKernelGGL(pdgpb_ng_form_adaptive_kernel, dim3(nstep), dim3(PB_THREADS), pb_ng_form_lds(p), h->stream, p->d_gps,
+                         r.list, (const double*)params, (const double*)p->d_grad, ad, r.blocks, r.refused, p->maxM);
+      GP_HIP_CHECK(h, hipGetLastError());
+      hipLaunchKernelGGL(pdgpb_ng_apply_adaptive_kernel, dim3(nstep, row_blocks), dim3(PB_THREADS), pb_ng_apply_lds(p), h->stream,
+                         p->d_gps, r.list, params, free_state, p->d_grad, ad, (const double*)r.blocks,
+                         (const int32_t*)p->d_status, (const int32_t*)r.refused);
+      GP_HIP_CHECK(h, hipGetLastError());
     }
     hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
                        p->d_owner, p->d_status, (const int32_t*)r.refused, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps,
                        h->logistic);
     GP_HIP_CHECK(h, hipGetLastError());
+  }
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m, double* v,
+                           const double* x, const double* y, const int32_t* idx, int32_t steps, const double* lr_t,
+                           double beta1, double beta2, double eps, double gamma, const int32_t* step_gp_host,
+                           void* workspace, size_t workspace_bytes) {
+  return pb_natgrad_run(p, "gp_pdgpb_natgrad", free_state, params, tcode, m, v, x, y, idx, steps, lr_t, beta1, beta2, eps, gamma,
+                        nullptr, 0, step_gp_host, workspace, workspace_bytes);
+}
+
+size_t gp_pdgpb_natgrad_adaptive_workspace_bytes(gp_pdgpb_plan p) {
+  if (!p || p->predict_only) return 0;
+  return gp_measure([&](GpArena& ar) { pb_nga_regions(p, ar); }) + GP_WS_TAIL_BATCH;
+}
+
+gp_status gp_pdgpb_natgrad_adaptive(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m,
+                                    double* v, const double* x, const double* y, const int32_t* idx, int32_t steps,
+                                    const double* lr_t, double beta1, double beta2, double eps, const double* gamma_gp_host,
+                                    int32_t halvings, const int32_t* step_gp_host, void* workspace, size_t workspace_bytes) {
+  if (p && !gamma_gp_host) return gp_fail(p->h, GP_ERR_BAD_ARG, "gp_pdgpb_natgrad_adaptive: bad argument or a prediction-only plan");
+  return pb_natgrad_run(p, "gp_pdgpb_natgrad_adaptive", free_state, params, tcode, m, v, x, y, idx, steps, lr_t, beta1, beta2, eps,
+                        0.0, gamma_gp_host, halvings, step_gp_host, workspace, workspace_bytes);
+}
+
+gp_status gp_pdgpb_natgrad_counts(gp_pdgpb_plan p, int64_t* halvings_host, double* shortest_host, int32_t clear) {
+  if (!p || (!halvings_host != !shortest_host)) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->d_ng_halv) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_natgrad_counts: no gp_pdgpb_natgrad_adaptive call yet");
+  const size_t G = p->gps.size();
+  if (halvings_host) {
+    GP_HIP_CHECK(h, hipMemcpyAsync(halvings_host, p->d_ng_halv, G * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    GP_HIP_CHECK(h, hipMemcpyAsync(shortest_host, p->d_ng_short, G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    for (size_t g = 0; g < G; g++)
+      if (!(shortest_host[g] <= 1.0)) shortest_host[g] = HUGE_VAL;   // no step since the reset
+  }
+  if (clear) {
+    GP_HIP_CHECK(h, hipMemsetAsync(p->d_ng_halv, 0, G * sizeof(int64_t), h->stream));
+    GP_HIP_CHECK(h, hipMemsetAsync(p->d_ng_short, PB_NG_SHORT_CLEAR_BYTE, G * sizeof(double), h->stream));
   }
   return GP_OK;
 }

@@ -551,9 +551,17 @@ class Pdgp(Parameterized):
             step_gps = self._natgrad_gps(method)        # refusals come before any device work
         self._pack()
         h = self._handle
+        adaptive = natgrad and method.adaptive()     # per-role lengths / halving: gp_pdgp_natgrad_step_adaptive
         if natgrad:
             step_gps = (C.c_int32 * len(step_gps))(*step_gps)
-            if self.__dict__.get("_ng_ws") is None:
+            if adaptive:
+                gammas = method.role_gammas(self.num_sources)
+                gammas = (C.c_double * len(gammas))(*gammas)
+                if self.__dict__.get("_nga_ws") is None:
+                    self._nga_ws = h.workspace(h.lib.gp_pdgp_natgrad_adaptive_workspace_bytes(self._plan))
+                # the call's counters start from zero; they are read once, after the last iteration
+                h.check(h.lib.gp_pdgp_natgrad_counts(self._plan, self._nga_ws.data_ptr(), None, None, 1))
+            elif self.__dict__.get("_ng_ws") is None:
                 self._ng_ws = h.workspace(h.lib.gp_pdgp_natgrad_workspace_bytes(self._plan))
         if natgrad or isinstance(method, AdamOptimizer):
             flag = C.c_int32(0)
@@ -565,9 +573,14 @@ class Pdgp(Parameterized):
                     # zeroes them, so that Adam behind it (zero gradient, zero moments: an update of exactly 0) moves
                     # the noise variance, the kernels and the inducing inputs only
                     self._elbo(True, sync=False)
-                    h.check(h.lib.gp_pdgp_natgrad_step(self._plan, self._params.data_ptr(), self._free.data_ptr(),
-                                                       self._grad.data_ptr(), method.gamma, step_gps,
-                                                       self._ng_ws.data_ptr(), self._ng_ws.numel()))
+                    if adaptive:
+                        h.check(h.lib.gp_pdgp_natgrad_step_adaptive(
+                            self._plan, self._params.data_ptr(), self._free.data_ptr(), self._grad.data_ptr(), gammas,
+                            method.halvings, step_gps, self._nga_ws.data_ptr(), self._nga_ws.numel()))
+                    else:
+                        h.check(h.lib.gp_pdgp_natgrad_step(self._plan, self._params.data_ptr(), self._free.data_ptr(),
+                                                           self._grad.data_ptr(), method.gamma, step_gps,
+                                                           self._ng_ws.data_ptr(), self._ng_ws.numel()))
                     h.check(h.lib.gp_adam_step(h.h, self._free.data_ptr(), self._params.data_ptr(), self._grad.data_ptr(),
                                                self._tcode.data_ptr(), self._adam_m.data_ptr(), self._adam_v.data_ptr(),
                                                self._nparams, self._adam_t, method.learning_rate, method.beta1,
@@ -598,8 +611,11 @@ class Pdgp(Parameterized):
             self._unpack()
             if self._shard:
                 self.sync_params()
-            return OptimizeResult(fun=f, jac=g, x=x_final, message='Finished iterations.', status='Finished iterations.',
-                                  success=True)
+            res = OptimizeResult(fun=f, jac=g, x=x_final, message='Finished iterations.', status='Finished iterations.',
+                                 success=True)
+            if adaptive:
+                res["natgrad"] = self._natgrad_counts(method)
+            return res
         if self._shard:
             # each rank owns a different slice of the free state: only element-wise update rules (Adam) stay
             # consistent across ranks without exchanging it
@@ -621,6 +637,9 @@ class Pdgp(Parameterized):
         naming the GP).  No device work."""
         if not (0.0 < method.gamma <= 1.0):
             raise ValueError("NatGradAdam: gamma must be a number in (0, 1], not %r" % (method.gamma,))
+        if getattr(method, "gamma_com", None) is not None:       # (a token changed after it was made)
+            method.check_gamma("gamma_com", method.gamma_com)
+        method.check_halvings(getattr(method, "halvings", 0))
         if self._shard:
             raise NotImplementedError("NatGradAdam on a sharded model: build the model unsharded on one GPU "
                                       "(a sharded Pdgp is trained with AdamOptimizer)")
@@ -634,6 +653,15 @@ class Pdgp(Parameterized):
                 flags.append(int(not fm))
         return flags
 
+    def _natgrad_counts(self, method):
+        """the adaptive step's counters of this optimize() call, rows [g_0..g_{P-1}, f_0..f_{P-1}] (one read, after the loop);
+        the shortest length starts at the GP's own gamma_r (the device reports +inf for a GP that took no step)"""
+        h, G = self._handle, 2 * self.num_sources
+        hv, sg = (C.c_int64 * G)(), (C.c_double * G)()
+        h.check(h.lib.gp_pdgp_natgrad_counts(self._plan, self._nga_ws.data_ptr(), hv, sg, 0))
+        return {"halvings": [int(v) for v in hv],
+                "shortest_gamma": [min(float(v), g) for v, g in zip(sg, method.role_gammas(self.num_sources))]}
+
     def _check_not_pd(self, method):
         """gp_check_not_pd; a refusal that a NatGradAdam step raised itself (its I - 2 gamma P was not positive definite:
         natgrad.hip leaves the GP in the first words of its workspace) is reported as such"""
@@ -643,10 +671,19 @@ class Pdgp(Parameterized):
         except _lib.NotPositiveDefiniteError as e:
             if not isinstance(method, NatGradAdam):
                 raise
-            rep = self._ng_ws[:16].view(h.torch.int32).cpu().numpy()
+            adaptive = method.adaptive()
+            rep = (self._nga_ws if adaptive else self._ng_ws)[:16].view(h.torch.int32).cpu().numpy()
             if int(rep[0]) != 1:
                 raise
             g, P = int(rep[1]), self.num_sources
+            if adaptive:
+                last = method.role_gammas(P)[g] * 2.0 ** -method.halvings
+                raise _lib.NotPositiveDefiniteError(
+                    e.status, "NatGradAdam: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) "
+                              "is not positive definite (pivot %d) at gamma = %g, the last length tried after halvings = %d; no "
+                              "parameter was changed, take a smaller gamma or more halvings"
+                              % ("activation" if g < P else "component", g if g < P else g - P, g, int(rep[2]), last,
+                                 method.halvings))
             raise _lib.NotPositiveDefiniteError(
                 e.status, "NatGradAdam: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) is "
                           "not positive definite (pivot %d) at gamma = %g; no parameter was changed, take a smaller gamma"

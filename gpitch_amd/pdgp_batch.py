@@ -186,9 +186,17 @@ def _describe_not_pd(code):
     return "latent GP row %d of [g_0..g_{P-1}, f_0..f_{P-1}], pivot %d" % (row, pivot)
 
 
-def _describe_refused(k, code, P, gamma):
-    """gp_pdgpb_natgrad_refused's word of model k (the same 1 + 128 row + pivot) as the refusal's message"""
+def _describe_refused(k, code, P, gamma, method=None):
+    """gp_pdgpb_natgrad_refused's word of model k (the same 1 + 128 row + pivot) as the refusal's message; `method`: the
+    token of a call through gp_pdgpb_natgrad_adaptive, whose message names the last length tried and the halvings"""
     row, pivot = divmod(int(code) - 1, MAX_M)
+    if method is not None:
+        last = method.role_gammas(P)[row] * 2.0 ** -method.halvings
+        return ("NatGradAdam: model %d: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) "
+                "is not positive definite (pivot %d) at gamma = %g, the last length tried after halvings = %d; the model was "
+                "left as it was, take a smaller gamma or more halvings"
+                % (k, "activation" if row < P else "component", row if row < P else row - P, row, pivot, last,
+                   method.halvings))
     return ("NatGradAdam: model %d: the natural-gradient step was too long: I - 2 gamma P of the %s GP %d (latent GP %d) "
             "is not positive definite (pivot %d) at gamma = %g; the model was left as it was, take a smaller gamma"
             % (k, "activation" if row < P else "component", row if row < P else row - P, row, pivot, gamma))
@@ -221,6 +229,8 @@ class PdgpBatch(object):
         self._elbo = h.zeros(nm)
         self._tcode = h.torch.zeros(n, dtype=h.torch.uint8, device=h.device)
         self._ng_ws = None             # gp_pdgpb_natgrad's workspace, from the first NatGradAdam call on
+        self._nga_ws = None            # gp_pdgpb_natgrad_adaptive's (per-role lengths / halving), likewise
+        self._ng_last = None           # the one of the two the plan has seen last (its refusal words)
 
     # ------------------------------------------------------------------------------------------
     def _pack(self):
@@ -276,7 +286,7 @@ class PdgpBatch(object):
     def refused(self, clear=True):
         """per model: 0, or 1 + 128 row + pivot of its refused natural-gradient step with the smallest (latent GP row,
         pivot); all 0 before the first NatGradAdam call"""
-        if self._ng_ws is None:
+        if self._ng_last is None:
             return np.zeros(len(self.models), dtype=np.int64)
         out = (C.c_int32 * len(self.models))()
         h = self._handle
@@ -308,13 +318,22 @@ class PdgpBatch(object):
         self._load_moments()
         self.not_pd(clear=True)
         nm = len(self.models)
+        adaptive = natgrad and method.adaptive()     # per-role lengths / halving: gp_pdgpb_natgrad_adaptive
         if natgrad:
             step_gps = [f for fl in flags for f in fl]
             step_gps = (C.c_int32 * len(step_gps))(*step_gps)
-            if self._ng_ws is None:
-                self._ng_ws = h.workspace(h.lib.gp_pdgpb_natgrad_workspace_bytes(self._plan))
-            else:
+            if self._ng_last is not None:
                 self.refused(clear=True)
+            if adaptive:
+                gammas = [g for m in self.models for g in method.role_gammas(m.num_sources)]
+                gammas = (C.c_double * len(gammas))(*gammas)
+                if self._nga_ws is None:
+                    self._nga_ws = h.workspace(h.lib.gp_pdgpb_natgrad_adaptive_workspace_bytes(self._plan))
+                else:                                # the call's counters start from zero
+                    h.check(h.lib.gp_pdgpb_natgrad_counts(self._plan, None, None, 1))
+            elif self._ng_ws is None:
+                self._ng_ws = h.workspace(h.lib.gp_pdgpb_natgrad_workspace_bytes(self._plan))
+            self._ng_last = self._nga_ws if adaptive else self._ng_ws
         rng_keep = [(m.x.rng.get_state() if hasattr(m.x.rng, "get_state") else None,
                      m.y.rng.get_state() if hasattr(m.y.rng, "get_state") else None) for m in self.models]
         t0 = [m._adam_t for m in self.models]
@@ -333,7 +352,10 @@ class PdgpBatch(object):
             args = (self._plan, self._free.data_ptr(), self._params.data_ptr(), self._tcode.data_ptr(),
                     self._adam_m.data_ptr(), self._adam_v.data_ptr(), self._x.data_ptr(), self._y.data_ptr(),
                     idx.data_ptr(), k, lr_dev.data_ptr(), method.beta1, method.beta2, method.epsilon)
-            if natgrad:
+            if adaptive:
+                h.check(h.lib.gp_pdgpb_natgrad_adaptive(*(args + (gammas, method.halvings, step_gps,
+                                                                  self._nga_ws.data_ptr(), self._nga_ws.numel()))))
+            elif natgrad:
                 # the same evaluation; the step on q(u) reads its blocks of the gradient and zeroes them, so that Adam
                 # behind it (zero gradient, zero moments: an update of exactly 0) moves everything else only
                 h.check(h.lib.gp_pdgpb_natgrad(*(args + (method.gamma, step_gps, self._ng_ws.data_ptr(),
@@ -344,6 +366,7 @@ class PdgpBatch(object):
         bad = self.not_pd(clear=True)
         # a model whose Kuu failed is reported as that (its garbage gradient may have raised the refusal word as well)
         refused = self.refused(clear=True) if natgrad else np.zeros(nm, dtype=np.int64)
+        counts = self._natgrad_counts(method) if adaptive else None      # one read, after the last iteration
         # GPflow evaluates the returned fun / jac on a fresh minibatch (Pdgp.optimize)
         draws = [draw_indices(m, 1) for m in self.models]
         elbo, grad = self._evaluate(draws)
@@ -366,9 +389,11 @@ class PdgpBatch(object):
                 if bad[k]:
                     msg = "Cholesky failed: %s" % _describe_not_pd(bad[k])
                 else:
-                    msg = _describe_refused(k, refused[k], m.num_sources, method.gamma)
+                    msg = _describe_refused(k, refused[k], m.num_sources, method.gamma, method if adaptive else None)
                 results.append(OptimizeResult(fun=None, jac=None, x=None, success=False, status="error", message=msg,
                                               error=_lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, msg)))
+                if adaptive:                         # what it had accumulated up to the refusing iteration
+                    results[-1]["natgrad"] = counts[k]
                 continue
             idx = self._free_idx[k]
             for off, p in self._segs[k]:
@@ -379,7 +404,24 @@ class PdgpBatch(object):
             m._invalidate_device_state()
             results.append(OptimizeResult(fun=-float(elbo[k]), jac=self._jac(k, free, grad), x=free[idx].copy(),
                                           message='Finished iterations.', status='Finished iterations.', success=True))
+            if adaptive:
+                results[-1]["natgrad"] = counts[k]
         return results
+
+    def _natgrad_counts(self, method):
+        """per model the adaptive step's counters of this call, rows [g_0..g_{P-1}, f_0..f_{P-1}]; the shortest length starts
+        at the GP's own gamma_r (the device reports +inf for a GP that took no step)"""
+        h = self._handle
+        G = sum(2 * m.num_sources for m in self.models)
+        hv, sg = (C.c_int64 * G)(), (C.c_double * G)()
+        h.check(h.lib.gp_pdgpb_natgrad_counts(self._plan, hv, sg, 0))
+        out, g0 = [], 0
+        for m in self.models:
+            n = 2 * m.num_sources
+            out.append({"halvings": [int(v) for v in hv[g0:g0 + n]],
+                        "shortest_gamma": [min(float(v), g) for v, g in zip(sg[g0:g0 + n], method.role_gammas(m.num_sources))]})
+            g0 += n
+        return out
 
     def __del__(self):
         try:

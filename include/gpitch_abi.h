@@ -480,6 +480,35 @@ gp_status gp_adam_step(gp_handle h, double* free_state, double* params, const do
 size_t gp_pdgp_natgrad_workspace_bytes(gp_pdgp_plan p);
 gp_status gp_pdgp_natgrad_step(gp_pdgp_plan p, double* params, double* free_state, double* grad, double gamma,
                                const int32_t* step_gp_host, void* workspace, size_t workspace_bytes);
+/* The same step with one length per latent GP and automatic halving.  gamma_gp_host (HOST, one double in
+ * (0, 1] per latent GP of the plan in gp_pdgp_layout's order, read for every GP whether stepped or not) gives gamma_r;
+ * halvings in 0..10.  GP r takes the map above at gamma_r 2^-j_r, in B and in q_mu', where j_r is the smallest j in
+ * 0..halvings for which I - 2 gamma_r 2^-j P_r factors with every pivot positive (the factorisation's own test, nothing
+ * stricter).  gamma 2^-j is an exact scaling, and at j = 0 the arithmetic is gp_pdgp_natgrad_step's: with nothing to halve the
+ * two entries write the same bits.  Every length is decided before anything is written, the GPs decide independently, and the
+ * next call starts from gamma_r again.  Launches: per round j = 0..halvings a form launch per 64 GPs (only GPs still pending
+ * are formed; a round with none pending returns after reading one word), one factorisation launch with a per-matrix outcome
+ * (size 0 for the GPs already accepted: their factor and inverse stay) and a one-workgroup launch that settles the outcomes;
+ * then the apply launch.  No host synchronisation.
+ * Refusal: a GP with no acceptable j <= halvings refuses the step of every GP exactly as above — the apply launch raises the
+ * handle's status word {1, pivot, slot} itself, nothing is written, gp_adam_step freezes, the first four int32 of the
+ * workspace read {1, latent GP index, pivot at the last length tried (gamma_r 2^-halvings), 1}; of several exhausted GPs the
+ * first in the plan's order is named.
+ * Counters, per latent GP of the plan, kept in the workspace: the sum of j_r over the calls and the smallest length taken.
+ * gp_pdgp_natgrad_counts copies them to the host (both arrays, one entry per latent GP; synchronises the stream) and, with
+ * clear != 0, resets them afterwards; both host pointers NULL with clear != 0 only resets.  A fresh workspace must be reset
+ * once before its first step.  A GP that took no step since the reset reports 0 and +infinity (the caller knows gamma_r).  A
+ * refused step counts nothing.
+ * Argument errors, alignment, GP_ERR_WORKSPACE, the subset-plan refusal and M <= 4096 as in gp_pdgp_natgrad_step; a gamma
+ * outside (0, 1] or halvings outside 0..10: GP_ERR_BAD_ARG.
+ * workspace: gp_pdgp_natgrad_adaptive_workspace_bytes(plan) bytes (0 for a null plan), 256-byte aligned: the plain step's
+ * carve, then the accepted j and the round's outcome per GP, the control words and the counters. */
+size_t gp_pdgp_natgrad_adaptive_workspace_bytes(gp_pdgp_plan p);
+gp_status gp_pdgp_natgrad_step_adaptive(gp_pdgp_plan p, double* params, double* free_state, double* grad,
+                                        const double* gamma_gp_host, int32_t halvings, const int32_t* step_gp_host,
+                                        void* workspace, size_t workspace_bytes);
+gp_status gp_pdgp_natgrad_counts(gp_pdgp_plan p, const void* workspace, int64_t* halvings_host, double* shortest_host,
+                                 int32_t clear);
 
 /* ---- L3 model: SGPRSS (gpitch/sgpr_ss.py:10-114) ---------------------------------------------- */
 typedef struct {
@@ -727,6 +756,29 @@ gp_status gp_pdgpb_natgrad(gp_pdgpb_plan p, double* free_state, double* params, 
                            double beta1, double beta2, double eps, double gamma, const int32_t* step_gp_host,
                            void* workspace, size_t workspace_bytes);
 gp_status gp_pdgpb_natgrad_refused(gp_pdgpb_plan p, int32_t* host_status, int32_t clear);
+/* gp_pdgpb_natgrad with one length per latent GP and automatic halving (the rule of gp_pdgp_natgrad_step_adaptive, DESIGN.md
+ * 3k): gamma_gp_host (HOST, one double in (0, 1] per latent GP of the plan in gp_pdgpb_layout's order) replaces `gamma`, and
+ * halvings is in 0..10.  The same two launches per iteration: the form launch's workgroup of a GP forms B at gamma_r 2^-j,
+ * factors it, and on a recorded non-positive pivot with j < halvings forms it again at half the length (Phi recomputed from
+ * params / grad); the accepted length goes to the workspace and the apply launch reads it.  The model's refusal word
+ * (gp_pdgpb_natgrad_refused, unchanged) is raised only when a GP's last length fails; the pivot in it is that length's.  At
+ * j = 0 the arithmetic is gp_pdgpb_natgrad's: with nothing to halve the two entries write the same bits.  GPs and models decide
+ * independently; every iteration starts from gamma_r again.
+ * Counters per latent GP of the plan, in the workspace: the sum of j over the iterations whose step the GP took, and the
+ * smallest length taken; a model frozen by a refusal or a failed Kuu counts nothing from then on.  They are cleared when the
+ * plan is handed an adaptive workspace it has not seen in the previous adaptive call and otherwise persist from call to call.
+ * gp_pdgpb_natgrad_counts copies them to the host (both arrays, one entry per latent GP, or both NULL; synchronises the stream)
+ * and with clear != 0 resets them afterwards; a GP that took no step since the reset reports 0 and +infinity (the caller knows
+ * gamma_r).  Before any gp_pdgpb_natgrad_adaptive: GP_ERR_WORKSPACE.
+ * workspace: gp_pdgpb_natgrad_adaptive_workspace_bytes(plan) bytes (0 for a null or prediction-only plan): gp_pdgpb_natgrad's
+ * regions, then per latent GP gamma_r, the accepted length, j and the counters.  Argument errors as gp_pdgpb_natgrad's; a
+ * gamma outside (0, 1], a NULL gamma_gp_host or halvings outside 0..10: GP_ERR_BAD_ARG. */
+size_t gp_pdgpb_natgrad_adaptive_workspace_bytes(gp_pdgpb_plan p);
+gp_status gp_pdgpb_natgrad_adaptive(gp_pdgpb_plan p, double* free_state, double* params, const uint8_t* tcode, double* m,
+                                    double* v, const double* x, const double* y, const int32_t* idx, int32_t steps,
+                                    const double* lr_t, double beta1, double beta2, double eps, const double* gamma_gp_host,
+                                    int32_t halvings, const int32_t* step_gp_host, void* workspace, size_t workspace_bytes);
+gp_status gp_pdgpb_natgrad_counts(gp_pdgpb_plan p, int64_t* halvings_host, double* shortest_host, int32_t clear);
 /* ---- prediction of many models: Pdgp.predict_act_n_com (pdgp.py:190-208) of every model at its own inputs --------------
  * A prediction-only plan is created by gp_pdgpb_create with cfg->batch == NULL (num_data is then ignored).  It has the
  * parameter layout of a training plan (gp_pdgpb_layout) and no training workspace: gp_pdgpb_workspace_bytes returns 0,

@@ -11,7 +11,18 @@
         the real-audio anchor model (oracle/demo_anchor.py's configuration: tests/golden/init_liv_real_audio.npz, minibatch 100):
         the full-data ELBO every --every iterations for AdamOptimizer(0.0025) and NatGradAdam(gamma, 0.0025), gamma in 0.05, 0.1,
         0.5, and the iteration count at which each first passes the ELBO that Adam reaches at the end.
-Writes natgrad_time.json / natgrad_progress.json into --out (default profiles/natgrad/)."""
+    python tools/time_natgrad.py adaptive-time [--out DIR] [--iters 200] [--reps 5] [--gamma-com G] [--halvings 4]
+        the token with a length per role / a halving budget on twin models, windows alternating in one process:
+        the plain token NatGradAdam(0.01, 0.0025) against NatGradAdam(0.01, 0.0025, gamma_com=G, halvings=H) with nothing to
+        halve (the idle rounds), at the demo and headline sizes; then, on tests/natgrad_adaptive_ref.py's 6e-6 problem, one step
+        from gamma = 1 (two real halvings) against one from gamma = 1/4 (none) and the plain entry at 1/4, state and gradient
+        restored before every call.  With GPITCH_AMD_LIB naming another build of the library and --plain-only: the plain token
+        alone (the figure to set beside this build's).
+    python tools/time_natgrad.py adaptive-progress [--out DIR] [--iters 2000] [--every 100]
+        the progress protocol above with AdamOptimizer(0.0025), NatGradAdam(0.1, 0.0025), NatGradAdam(0.5, 0.0025, gamma_com=1,
+        halvings=4) and NatGradAdam(1, 0.0025, halvings=6), and the halvings each window took.
+Writes natgrad_time.json / natgrad_progress.json / adaptive_time.json / adaptive_progress.json into --out (default
+profiles/natgrad/)."""
 import argparse
 import ctypes as C
 import json
@@ -129,6 +140,116 @@ def time_model(name, build, iters, reps, gamma=0.01):
     return res
 
 
+def adaptive_time_model(name, build, iters, reps, gamma_com, halvings, plain_only, gamma=0.01):
+    """twin models, plain token and adaptive token, windows alternating (time_model's long-minus-short windows)"""
+    from gpitch_amd.train import NatGradAdam
+    runs = [("plain", NatGradAdam(gamma, 0.0025), build())]
+    if not plain_only:
+        runs.append(("adaptive", NatGradAdam(gamma, 0.0025, gamma_com=gamma_com, halvings=halvings), build()))
+    for _, method, m in runs:
+        window(m, method, max(iters // 4, 3))
+    t = {k: [] for k, _, _ in runs}
+    halv = None
+    for _ in range(reps):
+        for k, method, m in runs:
+            t1 = window(m, method, iters) * iters
+            t3 = window(m, method, 3 * iters) * 3 * iters
+            t[k].append((t3 - t1) / (2 * iters))
+    if not plain_only:
+        halv = runs[1][2].optimize(method=runs[1][1], maxiter=iters).natgrad["halvings"]
+    res = {"model": name, "library": os.environ.get("GPITCH_AMD_LIB", "product"), "gamma": gamma, "gamma_com": gamma_com,
+           "halvings": halvings, "iters_per_window": iters, "windows": reps, "halvings_taken_in_a_last_window": halv}
+    for k, v in t.items():
+        res[k + "_token_ms_per_iteration"] = {"median": float(np.median(v)), "min": min(v), "max": max(v)}
+    if not plain_only:
+        res["adaptive_over_plain"] = res["adaptive_token_ms_per_iteration"]["median"] / res["plain_token_ms_per_iteration"]["median"]
+    print(json.dumps(res))
+    return res
+
+
+def real_halvings(iters, reps):
+    """the 6e-6 problem: device time of one step that halves twice, one that does not, and the plain entry, alternating; params,
+    free state and gradient are restored by three device copies before every call (in all three)"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import natgrad_adaptive_ref as nga
+    from gpitch_amd.synth import pdgp_from_problem
+    m = pdgp_from_problem(nga.halving_problem(6e-6), whiten=True)
+    m._pack()
+    m._elbo(True)
+    h = m._handle
+    keep = [t.clone() for t in (m._params, m._free, m._grad)]
+    G = len(m._layout)
+    ws = h.workspace(h.lib.gp_pdgp_natgrad_workspace_bytes(m._plan))
+    wsa = h.workspace(h.lib.gp_pdgp_natgrad_adaptive_workspace_bytes(m._plan))
+    h.check(h.lib.gp_pdgp_natgrad_counts(m._plan, wsa.data_ptr(), None, None, 1))
+    ptrs = (m._plan, m._params.data_ptr(), m._free.data_ptr(), m._grad.data_ptr())
+
+    def restore():
+        for dst, src in zip((m._params, m._free, m._grad), keep):
+            dst.copy_(src)
+    one, quarter = (C.c_double * G)(1.0, 1.0), (C.c_double * G)(0.25, 1.0)
+    calls = {"adaptive from 1 (two halvings)": lambda: h.lib.gp_pdgp_natgrad_step_adaptive(*(ptrs + (one, 4, None, wsa.data_ptr(), wsa.numel()))),
+             "adaptive from 1/4 (none), halvings=4": lambda: h.lib.gp_pdgp_natgrad_step_adaptive(*(ptrs + (quarter, 4, None, wsa.data_ptr(), wsa.numel()))),
+             "adaptive from 1/4, halvings=0": lambda: h.lib.gp_pdgp_natgrad_step_adaptive(*(ptrs + (quarter, 0, None, wsa.data_ptr(), wsa.numel()))),
+             "plain entry at 1/4": lambda: h.lib.gp_pdgp_natgrad_step(*(ptrs + (0.25, None, ws.data_ptr(), ws.numel())))}
+    t = {k: [] for k in calls}
+    for _ in range(reps + 1):                       # (the first round is the warm-up)
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                restore()
+                h.check(fn())
+            e1.record()
+            torch.cuda.synchronize()
+            t[k].append(e0.elapsed_time(e1) / iters)
+    hv, sg = (C.c_int64 * G)(), (C.c_double * G)()
+    h.check(h.lib.gp_pdgp_natgrad_counts(m._plan, wsa.data_ptr(), hv, sg, 0))
+    h.check(h.lib.gp_check_not_pd(h.h))
+    res = {"model": "tests/natgrad_adaptive_ref.py halving_problem(6e-6): M = 12 / 10", "calls_per_window": iters, "windows": reps,
+           "ms_per_call_with_three_restoring_copies": {k: {"median": float(np.median(v[1:])), "min": min(v[1:]), "max": max(v[1:])}
+                                                       for k, v in t.items()},
+           "halvings_counted": list(hv), "shortest_gamma": list(sg)}
+    print(json.dumps(res))
+    return res
+
+
+def adaptive_progress(iters, every):
+    from gpitch_amd import _lib
+    from gpitch_amd.train import AdamOptimizer, NatGradAdam
+    evalm = anchor_model(None)
+    runs = [("AdamOptimizer(0.0025)", AdamOptimizer(0.0025)), ("NatGradAdam(0.1, 0.0025)", NatGradAdam(0.1, 0.0025)),
+            ("NatGradAdam(0.5, 0.0025, gamma_com=1.0, halvings=4)", NatGradAdam(0.5, 0.0025, gamma_com=1.0, halvings=4)),
+            ("NatGradAdam(1.0, 0.0025, halvings=6)", NatGradAdam(1.0, 0.0025, halvings=6))]
+    out = {"model": "real-audio anchor (tests/golden/init_liv_real_audio.npz), minibatch 100", "every": every, "runs": []}
+    for name, method in runs:
+        m = anchor_model(100)
+        trace, note, halv, shortest = [full_elbo(evalm, m)], None, [], []
+        for it in range(every, iters + 1, every):
+            try:
+                res = m.optimize(method=method, maxiter=every)
+            except _lib.NotPositiveDefiniteError as e:
+                note = "refused between iterations %d and %d: %s" % (it - every, it, e)
+                break
+            if "natgrad" in res:
+                halv.append(res.natgrad["halvings"])
+                shortest.append(res.natgrad["shortest_gamma"])
+            trace.append(full_elbo(evalm, m))
+        out["runs"].append({"method": name, "full_data_elbo": trace, "note": note, "halvings_per_window": halv,
+                            "shortest_gamma_per_window": shortest})
+        print(name, "ELBO at 0 / %d / %d: %.3f / %.3f / %.3f %s" % (every, every * (len(trace) - 1), trace[0], trace[min(1, len(trace) - 1)],
+                                                                  trace[-1], note or ""), "halvings", [sum(h) for h in halv])
+    target = out["runs"][0]["full_data_elbo"][-1]
+    out["adam_elbo_at_end"] = target
+    for r in out["runs"]:
+        hit = [i * every for i, v in enumerate(r["full_data_elbo"]) if v >= target]
+        r["first_iteration_at_or_above_adam_end"] = hit[0] if hit else None
+        print("%-52s first at or above Adam's final ELBO %.3f: %s" % (r["method"], target, hit[0] if hit else "never"))
+    return out
+
+
 def full_elbo(evalm, m):
     for dst, src in zip(evalm._param_order(), m._param_order()):
         dst.value = src.value
@@ -166,7 +287,11 @@ def progress(iters, every):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["time", "progress"])
+    ap.add_argument("what", choices=["time", "progress", "adaptive-time", "adaptive-progress"])
+    ap.add_argument("--gamma-com", type=float, default=None)
+    ap.add_argument("--halvings", type=int, default=4)
+    ap.add_argument("--plain-only", action="store_true", help="adaptive-time: the plain token alone (another build of the library)")
+    ap.add_argument("--name", default=None, help="adaptive-time: file name instead of adaptive_time.json")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "natgrad"))
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--reps", type=int, default=5)
@@ -178,6 +303,18 @@ def main():
                time_model("headline (N = 32768, M = 512, P = 12, m = 20, float64, full batch)", headline_model,
                           max((args.iters or 200) // 10, 5), args.reps)]
         path = os.path.join(args.out, "natgrad_time.json")
+    elif args.what == "adaptive-time":
+        it = args.iters or 200
+        res = [adaptive_time_model("demo (N = 16000, minibatch 100, P = 1)", demo_model, it, args.reps, args.gamma_com, args.halvings,
+                                   args.plain_only),
+               adaptive_time_model("headline (N = 32768, M = 512, P = 12, m = 20, float64, full batch)", headline_model,
+                                   max(it // 10, 5), args.reps, args.gamma_com, args.halvings, args.plain_only)]
+        if not args.plain_only:
+            res.append(real_halvings(it, args.reps))
+        path = os.path.join(args.out, args.name or "adaptive_time.json")
+    elif args.what == "adaptive-progress":
+        res = adaptive_progress(args.iters or 2000, args.every)
+        path = os.path.join(args.out, "adaptive_progress.json")
     else:
         res = progress(args.iters or 2000, args.every)
         path = os.path.join(args.out, "natgrad_progress.json")

@@ -12,6 +12,12 @@ time, warm-up steps excluded; one JSON line per W on stdout.
 times optimize_many with NatGradAdam(GAMMA, 0.0025) per step, optimize_many with AdamOptimizer(0.0025) on the same
 batch (the figure of the Adam path) and the loop of m.optimize(method=NatGradAdam(GAMMA, 0.0025)) over twin models,
 in the same process: medians of --repeats windows each, the three alternating, with their ranges.
+
+    python tools/time_pdgp_batch.py --natgrad GAMMA [--gamma-com G] --halvings H [--models 12 88] [--steps 100] [--repeats 5]
+
+times optimize_many with the plain token NatGradAdam(GAMMA, 0.0025) against the token with gamma_com = G and / or
+halvings = H (gp_pdgpb_natgrad_adaptive) on twin batches, the two alternating: the cost of the loop around the
+form kernel when nothing is halved.  The halving counts of the last window are printed with it.
 """
 import argparse
 import json
@@ -87,6 +93,45 @@ def natgrad_main(a):
                           "speedup_over_loop": W * med["loop"] / med["natgrad"]}), flush=True)
 
 
+def adaptive_main(a):
+    """plain token against the per-role / halving token on twin batches, alternating windows"""
+    import copy
+    import torch
+    import gpitch_amd
+    from gpitch_amd.pdgp_batch import PdgpBatch
+    plain = gpitch_amd.train.NatGradAdam(a.natgrad, 0.0025)
+    adapt = gpitch_amd.train.NatGradAdam(a.natgrad, 0.0025, gamma_com=a.gamma_com, halvings=a.halvings)
+    base = demo_model()
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for W in a.models:
+        bp = PdgpBatch([copy.deepcopy(base) for _ in range(W)])
+        bq = PdgpBatch([copy.deepcopy(base) for _ in range(W)])
+        bp.optimize(plain, a.warmup)
+        bq.optimize(adapt, a.warmup)
+        t = {"plain": [], "adaptive": []}
+        ok, halv = True, 0
+        for _ in range(a.repeats):
+            rp, rq = [], []
+            t["plain"].append(1e3 * window(lambda: rp.extend(bp.optimize(plain, a.steps))) / a.steps)
+            t["adaptive"].append(1e3 * window(lambda: rq.extend(bq.optimize(adapt, a.steps))) / a.steps)
+            ok = ok and all(r.success for r in rp + rq)
+            halv = sum(sum(r.natgrad["halvings"]) for r in rq if r.success)
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"models": W, "gamma": a.natgrad, "gamma_com": a.gamma_com, "halvings": a.halvings, "steps": a.steps,
+                          "repeats": a.repeats, "every_model_succeeded": ok, "halvings_taken_in_the_last_window": halv,
+                          "library": os.environ.get("GPITCH_AMD_LIB", "product"),
+                          "plain_token_ms_per_step": med["plain"], "plain_token_range": [min(t["plain"]), max(t["plain"])],
+                          "adaptive_token_ms_per_step": med["adaptive"],
+                          "adaptive_token_range": [min(t["adaptive"]), max(t["adaptive"])],
+                          "adaptive_over_plain": med["adaptive"] / med["plain"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", type=int, nargs="+", default=[1, 12, 88])
@@ -96,7 +141,11 @@ def main():
     ap.add_argument("--natgrad", type=float, default=None, metavar="GAMMA",
                     help="time NatGradAdam(GAMMA, 0.0025): batched, the batched Adam step, and the single-model loop")
     ap.add_argument("--repeats", type=int, default=5, help="windows per figure with --natgrad (the median is reported)")
+    ap.add_argument("--gamma-com", type=float, default=None, help="with --natgrad: the component GPs' own step length")
+    ap.add_argument("--halvings", type=int, default=0, help="with --natgrad: the halving budget (0..10)")
     a = ap.parse_args()
+    if a.natgrad is not None and (a.gamma_com is not None or a.halvings):
+        return adaptive_main(a)
     if a.natgrad is not None:
         return natgrad_main(a)
     import copy
