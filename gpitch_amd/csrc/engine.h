@@ -97,6 +97,26 @@ bool qfar_takes(int M, int N, int m);
 // count GPs of one family (M, m) over the n ascending frames x: two launches on h->stream
 gp_status launch_qfar_tables(gp_handle h, const QfarItem* d_items, int count, int M, int m, const double* x, int n);
 
+// qbar.hip: the Q route's backward products Qbar = Kuf diag(2 gv) Kuf^T and v = Kuf gm from the same far field,
+// one item per latent GP of the run: the stored strip, the likelihood's two rows, qfar.hip's tables of this step, the workspace
+struct QbarItem {
+  const double* Kuf; int64_t ldk; const double* gv; const double* gm;
+  const double* z; const double* theta; const double* fz;           // z features [nf][M]
+  const int* rng; const double* ref; const double* Psi;             // qfar.hip's ranges, reference points, Psi
+  int* rng2; int* tS;                                               // the ranges widened to monotone; per 16-row tile S0, then Sa
+  double* CnF; double* CFF; double* cn; double* cF;                 // per group: near x far [M][2 nf], far x far [2 nf][2 nf], B gm
+  double* Um; double* Vp; double* Wv;                               // [M][nf], [M][nf], [M / 16][M][nf]
+  double* Qbar; double* v;                                          // out: M x M (full, symmetric), M
+  int M, pad;
+};
+#define QBAR_MAX_TILES 64    // 16-row tiles: M <= 1024
+#define QBAR_MAX_NF 64       // features per point: m <= 32
+struct QbarSizes { size_t rng2, tS, CnF, CFF, cn, cF, Um, Wv; };   // doubles (Vp as Um)
+QbarSizes qbar_sizes(int M, int N, int m);
+bool qbar_takes(int M, int N, int m);
+// count GPs of one family (M, m) over n frames, behind the tables and the likelihood's gv / gm: four launches on h->stream
+gp_status launch_qbar(gp_handle h, const QbarItem* d_items, int count, int M, int m, int n);
+
 #define CB_NB 128          // panel width of the blocked Kuu factorisation
 #define CB_MAX_PANELS 8    // M <= 1024
 

@@ -120,12 +120,14 @@ gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
 }
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
   if (!p) return GP_ERR_BAD_ARG;
-  // bit 0: the Q route is allowed; bit 1: every MercerMatern12sm GP's inducing inputs ascend (the far field of its product)
-  const bool on = (enable & 1) != 0, zasc = on && (enable & 2) != 0;
-  if (p->qform != on || p->q_zasc != zasc) { p->qform = on; p->q_zasc = zasc; p->last_params = nullptr; }   // the descriptors depend on the route
+  // bit 0: the Q route is allowed; bit 1: every MercerMatern12sm GP's inducing inputs ascend (the far field of its product);
+  // bit 2: the backward pass may form Qbar and v from that far field too
+  const bool on = (enable & 1) != 0, zasc = on && (enable & 2) != 0, bar = zasc && (enable & 4) != 0;
+  if (p->qform != on || p->q_zasc != zasc || p->q_bar_ok != bar) { p->qform = on; p->q_zasc = zasc; p->q_bar_ok = bar; p->last_params = nullptr; }   // the descriptors depend on the route
   return GP_OK;
 }
 int32_t gp_pdgp_far_field(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far) ? 1 : 0; }
+int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far && p->q_bar) ? 1 : 0; }
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
@@ -187,6 +189,15 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
           const QfarSizes qs = qfar_sizes((int)M, p->maxN, p->gps[g].m);
           b.qf_rng = (int*)ar.take<double>(qs.rng); b.qf_ref = ar.take<double>(qs.ref);
           b.qf_T = ar.take<double>(qs.T); b.qf_Psi = ar.take<double>(qs.Psi);
+          // (the backward pass's use of the same far field, DESIGN.md 3.06: sized for every range — the lengthscale is trained on
+          // the device.  At M = 512, N = 32768, m = 20 it is 0.41 of the b.G strip; like the tables it has a home of its own)
+          if (gp_switches().qform_qbar != 0 && qbar_takes((int)M, p->maxN, p->gps[g].m)) {
+            const QbarSizes bs = qbar_sizes((int)M, p->maxN, p->gps[g].m);
+            b.qb_rng2 = (int*)ar.take<double>(bs.rng2); b.qb_tS = (int*)ar.take<double>(bs.tS);
+            b.qb_CnF = ar.take<double>(bs.CnF); b.qb_CFF = ar.take<double>(bs.CFF); b.qb_cn = ar.take<double>(bs.cn);
+            b.qb_cF = ar.take<double>(bs.cF); b.qb_Um = ar.take<double>(bs.Um); b.qb_Vp = ar.take<double>(bs.Um);
+            b.qb_Wv = ar.take<double>(bs.Wv);
+          }
         }
       }
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;

@@ -29,7 +29,7 @@ static inline const GemmProblem* slot_probs(gp_pdgp_plan p, int slot) { return (
 // over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
 // batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
 void pdgp_qform_select(gp_pdgp_plan p, int n) {
-  p->q0 = p->nq = p->qk0 = 0; p->q_far = false;
+  p->q0 = p->nq = p->qk0 = 0; p->q_far = p->q_bar = false;
   if (!gp_switches().qform || !p->qform || !p->whiten) return;
   int first = -1, last = -1, cnt = 0, m = -1;
   for (int g = 0; g < p->G; g++) {
@@ -60,6 +60,12 @@ void pdgp_qform_select(gp_pdgp_plan p, int n) {
   bool far = gp_switches().qform_far != 0 && p->frames_ascending && p->q_zasc && gemm_wave_takes(7, p->maxM, n, 1) && qfar_takes(p->maxM, n, m);
   for (int g = first; g <= last; g++) far = far && p->bw[g].qf_T && p->gps[g].M == p->maxM;
   p->q_far = far;
+  // the backward pass's Qbar and v from the same far field: the switch, the caller's bit, the shape, the workspace
+  // — and the latent GPs left to the split-K product are one non-empty run of its float64 problems, so it stays one launch
+  bool bar = far && gp_switches().qform_qbar != 0 && p->q_bar_ok && qbar_takes(p->maxM, n, m) &&
+             (first == 0 || last + 1 == p->n64) && p->n64 > cnt;
+  for (int g = first; g <= last; g++) bar = bar && p->bw[g].qb_Wv;
+  p->q_bar = bar;
 }
 
 // the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
@@ -280,6 +286,11 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
       { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
       { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
+      if (p->q_bar) {   // Qbar and v from the far field (qbar.hip) into the same T2 and Lu; the split-K launch skips this GP
+        QbarItem& it = *(QbarItem*)(p->h_misc.data() + p->off.qb_items + (g - p->q0) * sizeof(QbarItem));
+        it = QbarItem{t.Kuf, ldN, gv, gm, t.z, t.kern.theta, t.feat, b.qf_rng, b.qf_ref, b.qf_Psi, b.qb_rng2, b.qb_tS,
+                      b.qb_CnF, b.qb_CFF, b.qb_cn, b.qb_cF, b.qb_Um, b.qb_Vp, b.qb_Wv, b.T2, b.Lu, M, 0};
+      }
     }
     { GemmProblem& r = P(S_U); r.A = t.A; r.lda = ldN; r.N = n; r.v0 = gm; r.o0 = b.u; r.o1 = g_mu; r.a_f32 = q.f32; }
     { GemmProblem& r = P(S_HLQ); r.A = b.H; r.B = q_sqrt; r.C = g_sqrt; }
@@ -438,12 +449,23 @@ static gp_status bwd_late_sums(const BwdCall& c) {
   return GP_OK;
 }
 
+static gp_status bwd_qbar(const BwdCall& c) {
+  gp_pdgp_plan p = c.p;
+  return launch_qbar(p->h, (const QbarItem*)(p->d_misc + p->off.qb_items), p->nq, p->maxM, p->gps[p->q0].m, c.n);
+}
+
 // H = A diag(2 gv) A^T (symmetric, split-K over the frames; u = A gm and grad q_mu += u are fused into it), grad q_sqrt
 static gp_status bwd_h_chain(const BwdCall& c) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
   const int G = p->G, maxM = p->maxM, n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
   GemmFlags f;
-  if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H), n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+  if (p->q_bar) {       // the Q run's Qbar and v from its far field (four launches, no timer class); the product on the other run
+    const int rest0 = (p->q0 == 0) ? p->nq : 0;
+    if (!p->qbar_ahead) GP_CHECK(bwd_qbar(c));
+    GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + rest0, n64 - p->nq, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+    // (pdgp_backward put them on the main stream, beside this product: S_QT waits for them here)
+    if (p->qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
+  } else if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H), n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
   if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, slot_probs(p, S_H) + n64, G - n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
   if (p->nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
     f = GemmFlags(); f.triA = TRI_LOWER;
@@ -635,6 +657,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   gp_handle h = p->h;
   const BwdCall c{p, params, x, n, grad};
   const bool white = p->whiten != 0;
+  p->qbar_ahead = false;
   if (!white) GP_CHECK(bwd_unwhitened_head(c));
   // Everything that hangs off H = A diag(2 gv) A^T — grad q_sqrt, Wbar, the whole Kuu side — is independent of the
   // Kuf_bar product, which needs only R = W^T (Lq Lq^T - I) and alpha = W^T q_mu.  With early_fork the H chain
@@ -658,6 +681,27 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   // gp_side_join — so only the first taker gets it: a further scan family, or a contraction that asks after it, stays in line.
   const bool scan_side = p->any_scan && gp_switches().scan_side != 0 && n >= 4096 && p->overlap >= 2;
   const bool forked = n >= 4096 && p->overlap >= 1 && gp_aux_fork(h);
+  HyFamily *first = nullptr, *second = nullptr;
+  const bool two = forked && p->overlap >= 2 && bwd_two_family_order(p, &first, &second);
+  // When the H chain goes to the helper stream, the far-field Qbar runs on the MAIN stream, beside the other
+  // GPs' split-K product instead of in front of it, and the helper stream picks it up by an event before S_QT; a first
+  // family that contracts by the scan is issued ahead of it, so that the side stream starts at once.  qform_qbar = 2 keeps
+  // the launches on the helper stream.  The same launches either way, the same bits.
+  bool first_issued = false;
+  if (forked && early_fork && p->q_bar && gp_switches().qform_qbar != 2 &&
+      (h->ev_q || hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) == hipSuccess)) {
+    hipStream_t helper = h->stream;       // (not a GpStreamScope: the main stream may be the null stream, which it reads as "stay")
+    h->stream = h->main_stream_saved;
+    gp_status st = GP_OK;
+    if (two && first->route == KUF_SCAN) { st = bwd_kuf_bar_step(c, *first, scan_side); first_issued = true; }
+    if (st == GP_OK) st = bwd_qbar(c);
+    h->stream = helper;
+    if (st != GP_OK || hipEventRecord(h->ev_q, h->main_stream_saved) != hipSuccess) {
+      (void)gp_aux_end(h);
+      return st != GP_OK ? st : gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
+    }
+    p->qbar_ahead = true;
+  }
   if (forked) {
     const gp_status st = bwd_helper_chain(c, early_fork);
     const gp_status se = gp_aux_end(h);
@@ -665,11 +709,10 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   } else if (early_fork) {
     GP_CHECK(bwd_late_sums(c));
   }
-  HyFamily *first = nullptr, *second = nullptr;
-  if (forked && p->overlap >= 2 && bwd_two_family_order(p, &first, &second)) {
+  if (two) {
     const bool pending = !kuf_sums_with_step(*first);     // first's contraction is still to run once its step is through
     bool side = false;
-    GP_CHECK(bwd_kuf_bar_step(c, *first, scan_side));
+    if (!first_issued) GP_CHECK(bwd_kuf_bar_step(c, *first, scan_side));
     if (pending) GP_CHECK(gp_on_side(h, true, &side, [&]() { return bwd_contract(c, *first); }));
     GP_CHECK(bwd_kuf_bar_step(c, *second, scan_side));
     if (pending && !side) GP_CHECK(bwd_contract(c, *first));

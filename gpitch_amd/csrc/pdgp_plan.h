@@ -12,7 +12,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // (pdgp_bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
-struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, bytes; };
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, qb_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   PdgpMiscLayout o;
   GpRegions region;
@@ -24,6 +24,7 @@ static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   o.hy_items = region((size_t)2 * G * sizeof(HyperItem));      // G Kuf-side items, then G Kuu-side items, same order
   o.ks_items = region((size_t)G * sizeof(KufScanItem));       // kuf_scan.hip: one per latent GP, in the families' item order
   o.qf_items = region((size_t)G * sizeof(QfarItem));          // qfar.hip: one per latent GP of the Q run
+  o.qb_items = region((size_t)G * sizeof(QbarItem));          // qbar.hip: one per latent GP of the Q run
   o.bytes = region.off;
   return o;
 }
@@ -56,6 +57,10 @@ struct BwdBufs {  // per-GP backward workspace (device)
   double* Q = nullptr;      // M x M   R W = W^T E W: the Q route's forward operand (MercerMatern12sm GPs of a whitened float64 plan only)
   // the Q route's far field (qfar.hip): near ranges, reference points, T and Psi — carved with Q, in the plan's own arena
   int* qf_rng = nullptr; double* qf_ref = nullptr; double* qf_T = nullptr; double* qf_Psi = nullptr;
+  // the same far field in the backward pass (qbar.hip): widened ranges, tile tables, per-group Gram blocks and
+  // vectors, the recurrences' results — carved behind the tables
+  int* qb_rng2 = nullptr; int* qb_tS = nullptr; double* qb_CnF = nullptr; double* qb_CFF = nullptr; double* qb_cn = nullptr;
+  double* qb_cF = nullptr; double* qb_Um = nullptr; double* qb_Vp = nullptr; double* qb_Wv = nullptr;
   double* R32 = nullptr;    // float32 strips only: M * M floats, the float32 copy of R (gemm_wave_f32.hip)
   double* G = nullptr;      // M x N   K̄uf (dense part R (A D))
   double* u = nullptr;      // M       A gm
@@ -138,6 +143,10 @@ struct gp_pdgp_plan_s {
   // far field of the run's product: gp_pdgp_set_qform's second bit — the caller vouches that the inducing inputs
   // of every MercerMatern12sm GP ascend (they are fixed on this route) — and whether the bound run takes it
   bool q_zasc = false, q_far = false;
+  // Qbar and v of the run from the far field as well: gp_pdgp_set_qform's third bit allows it, q_bar says
+  // the bound run takes it — its problems then leave the split-K launch, which covers the other latent GPs
+  bool q_bar_ok = false, q_bar = false;
+  bool qbar_ahead = false;     // this backward pass has put those launches on the main stream (pdgp_backward)
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

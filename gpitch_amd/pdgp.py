@@ -272,9 +272,10 @@ class Pdgp(Parameterized):
         self._params.copy_(h.torch.as_tensor(host))
         self._tcode.copy_(h.torch.as_tensor(tc))
         flatvec.set_grad_needs(h, h.lib.gp_pdgp_set_grad_needs, self._plan, self._gps())
-        # bit 0: the Q route is allowed; bit 1: its inducing inputs ascend, so the product may take its far-field form
+        # bit 0: the Q route is allowed; bit 1: its inducing inputs ascend, so the product may take its far-field form; bit 2: so
+        # may the backward pass's Kuf diag(2 gv) Kuf^T and Kuf gm
         allow = int(self._qform_admissible())
-        h.check(h.lib.gp_pdgp_set_qform(self._plan, allow | (2 if allow and self._qform_z_ascending() else 0)))
+        h.check(h.lib.gp_pdgp_set_qform(self._plan, allow | (6 if allow and self._qform_z_ascending() else 0)))
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                             self._free.data_ptr()))
         self._packed_key = self._host_key()

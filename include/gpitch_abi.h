@@ -267,10 +267,15 @@ gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending);
  * MercerMatern12sm latent GP ascend.  With frames promised ascending as well (gp_pdgp_set_frames_ascending) and M <= 1024 the
  * product then contracts, per group of 256 frames, only the rows of Kuf within a lengthscale of the group, and adds the rows
  * beyond through two tables of rank 2 * partials (padded to a multiple of 4) each: the same G to rounding, bit-identical when
- * every row is near.  GPITCH_AMD_SWITCHES=qform_far=0 overrides bit 1. */
+ * every row is near.  GPITCH_AMD_SWITCHES=qform_far=0 overrides bit 1.  Bit 2 (with bits 0 and 1): the backward pass may form
+ * Kuf diag(2 gv) Kuf^T and Kuf gm of those GPs from the same near rows and far field instead of the dense split-K product, which
+ * then covers the other latent GPs (taken when those are one run of the batch; the same gradient to rounding, ~1e-12 of a
+ * block's scale).  GPITCH_AMD_SWITCHES=qform_qbar=0 overrides bit 2. */
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable);
 /* 1 when the batch last bound by gp_pdgp_elbo (or its staged forms) took that near-rows-plus-far-field product, else 0 */
 int32_t gp_pdgp_far_field(gp_pdgp_plan p);
+/* 1 when that batch's backward pass takes the far field too (bit 2 above), else 0 */
+int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p);
 
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the
