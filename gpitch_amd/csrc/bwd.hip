@@ -518,8 +518,10 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_kernel(const HyperItem o
   const int row = i0 + lc;
   const bool rowok = (row < it.n1);
   const int rowc = rowok ? row : it.n1 - 1;
-  const double zi = gx1[rowc], a = zi / ls, aa = __dmul_rn(a, a), m2a = -2.0 * a, al = galpha[rowc];
   const double inv_ls = 1.0 / ls;
+  // (a in the form the entry arithmetic below gives b, x * (1 / l): an inducing input equal to a frame must give r2 = 0 exactly,
+  // which the quotient on one side and the product on the other do not — see hyper_sm_rows_lean_kernel)
+  const double zi = gx1[rowc], a = zi * inv_ls, aa = __dmul_rn(a, a), m2a = -2.0 * a, al = galpha[rowc];
   // table row of feature phi = 16 t + lc (B operand side: this lane supplies feature lc of every tile)
   int frow[NT]; bool fok[NT];
 #pragma unroll
@@ -784,8 +786,12 @@ __global__ void __launch_bounds__(256, 2) hyper_sm_rows_lean_kernel(const HyperI
   const int rowc = tile_on ? i0 + lc : it.n1 - 1;
   const double inv_ls = 1.0 / ls;
   const double al = galpha[rowc];
-  const double ab_i = gx1[rowc] * inv_ls;      // the scaled input as the covariance build forms it (x * (1 / l))
-  const double a_ = gx1[rowc] / ls, aa = __dmul_rn(a_, a_), m2a = -2.0 * a_;    // (entry-by-entry form: cov.hip's arithmetic)
+  const double ab_i = gx1[rowc] * inv_ls;      // the scaled input as the column table forms it (x * (1 / l))
+  // (entry-by-entry form: cov.hip's expanded square, on the SAME form of the scaled inputs as t_b.  With the quotient x / l on
+  // this side and the product on the other, an inducing input that coincides with a frame more than ~70 lengthscales from
+  // the origin got a != b by an ulp, the expansion -2 a b + a a + b b then lands anywhere within 2 ulp of a^2 around zero —
+  // below -1e-12 from there on — and the root under it is NaN: equal inputs must give r2 = 0 exactly, as in cov.hip)
+  const double a_ = ab_i, aa = __dmul_rn(a_, a_), m2a = -2.0 * a_;
   int frow[NT]; bool fok[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) {

@@ -128,6 +128,27 @@ gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
 }
 int32_t gp_pdgp_far_field(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far) ? 1 : 0; }
 int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far && p->q_bar) ? 1 : 0; }
+// debug: the device's own ranges of the last evaluation, copied to the host (tests compare them with the numpy rule)
+int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref,
+                                 int32_t* rng2, int32_t* s0, int32_t* sa) {
+  if (!p || !p->ws || p->nq <= 0 || !p->q_far || i < 0 || i >= p->nq || p->last_n <= 0 || !rng || !ref) return 0;
+  const int ng = p->last_n / QFAR_GROUP, g = p->q0 + i, nt = p->gps[g].M / 16;
+  const BwdBufs& b = p->bw[g];
+  if (ng <= 0 || ng > cap_groups || !b.qf_rng || !b.qf_ref) return 0;
+  gp_handle h = p->h;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  if (h->aux_stream && hipStreamSynchronize(h->aux_stream) != hipSuccess) return 0;
+  if (h->side_stream && hipStreamSynchronize(h->side_stream) != hipSuccess) return 0;
+  if (hipMemcpy(rng, b.qf_rng, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (hipMemcpy(ref, b.qf_ref, (size_t)2 * ng * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (p->q_bar && rng2 && s0 && sa && b.qb_rng2 && b.qb_tS) {
+    if (hipMemcpy(rng2, b.qb_rng2, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (hipMemcpy(s0, b.qb_tS, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (hipMemcpy(sa, b.qb_tS + QBAR_MAX_TILES, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  }
+  if (gp_index) *gp_index = g;
+  return ng;
+}
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,

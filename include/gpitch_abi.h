@@ -276,6 +276,14 @@ gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable);
 int32_t gp_pdgp_far_field(gp_pdgp_plan p);
 /* 1 when that batch's backward pass takes the far field too (bit 2 above), else 0 */
 int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p);
+/* Debug, read-only: what the device made of the far field for latent GP number `i` of the run that took it (0 <= i < run length)
+ * at the batch last bound and evaluated.  Waits for the handle's streams, then copies to HOST buffers: rng [2 groups] (kbeg, kend
+ * per group of 256 frames) and ref [2 groups] (bmin, bmax); and, when the backward pass took the far field too and the three
+ * pointers are given, rng2 [2 groups] (the ranges widened to monotone) and the tile tables s0 / sa [M / 16 each].  gp_index
+ * (may be NULL) receives the GP's index in the plan.  Returns the number of groups written; 0 when the batch did not take the
+ * far field, i is outside the run, or the run has more than cap_groups groups (nothing is written then).  Launches nothing. */
+int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref,
+                                 int32_t* rng2, int32_t* s0, int32_t* sa);
 
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the

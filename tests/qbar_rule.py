@@ -26,7 +26,8 @@ def is_monotone(rng):
 
 def monotone(rng):
     """near ranges widened until kbeg and kend never decrease (qbar_plan_kernel): a near row is always exact, so widening is
-    free; with ascending z and x the rule's own ranges already are monotone and this changes nothing"""
+    free; with ascending z and x the rule's own ranges already are monotone and this changes nothing — unless a 32-column strip
+    spans 300 lengthscales (a gap in the frame times): its group is all near between narrower neighbours"""
     kb, ke = [r[0] for r in rng], [r[1] for r in rng]
     for s in range(len(rng) - 2, -1, -1):
         kb[s] = min(kb[s], kb[s + 1])

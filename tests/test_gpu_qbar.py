@@ -2,7 +2,8 @@
 each 256-frame group plus the far tables, qbar.hip) against the dense split-K product in the same process: bit 2 of the plan's
 permission switches between them.  pdgp.py sets 7; a plan given 3 (or 1) runs the backward pass that existed before, which a
 child process with GPITCH_AMD_SWITCHES=qform_qbar=0 — a library that never takes the new path — confirms bit for bit.
-Shapes and models: test_gpu_qfar.py's eight cases."""
+Shapes and models: test_gpu_qfar.py's cases; every evaluation also compares the device's ranges, widened ranges and tile tables
+with the numpy rules (test_gpu_qfar.assert_device_ranges).  One test keeps a plan while the lengthscale moves, as training does."""
 import os
 import subprocess
 import sys
@@ -46,13 +47,17 @@ def _evaluate(prob, h, qform=None, overlap=None, count=False):
     finally:
         if count:
             h.check(h.lib.gp_timers_enable(h.h, 0))
-    return (f, model._grad.cpu().numpy().copy(), model_grad_dict(model), launches, int(h.lib.gp_pdgp_far_field(model._plan)),
-            int(h.lib.gp_pdgp_far_field_backward(model._plan)))
+    far, bar = int(h.lib.gp_pdgp_far_field(model._plan)), int(h.lib.gp_pdgp_far_field_backward(model._plan))
+    tq.assert_device_ranges(h, model, prob, far, bar)      # the device's ranges, widened ranges and tile tables: the numpy rules'
+    return f, model._grad.cpu().numpy().copy(), model_grad_dict(model), launches, far, bar
 
 
 def test_ranges_of_the_cases_are_monotone():
+    """... of every latent GP, but for the cases with a gap in the frame times, which are there because theirs are not"""
     for name, c in CASES.items():
-        assert qb.is_monotone(tq._ranges(tq._problem(**c))), name
+        prob = tq._problem(**c)
+        for p in range(c["P"]):
+            assert qb.is_monotone(tq._ranges(prob, p)) == (not c.get("nonmonotone")), (name, p)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -93,6 +98,73 @@ def test_all_near_ranges_stay_within_the_bar(gp_handle):
     worst = max(np.abs(g1[k] - g0[k]).max() / max(np.abs(g0[k]).max(), 1e-12) for k in g0)
     print("all near: far field vs split-K, worst %.2e of a block's scale" % worst)
     assert worst <= FAR_VS_DENSE, worst
+
+
+MOVING_LS = (25, 4, 25, 8)      # inducing spacings, in this order on one plan
+
+
+def _free_model(prob, h):
+    model = pdgp_from_problem(prob, handle=h)
+    model.za.fixed = True
+    model.zc.fixed = True
+    return model
+
+
+def _objective(model, x_free, h, prob):
+    """one evaluation through the model's own free-state entry: (ELBO, free gradient, gradient by name, far, bar, range lists)"""
+    f, g = model._objective(x_free)
+    h.sync()
+    far, bar = int(h.lib.gp_pdgp_far_field(model._plan)), int(h.lib.gp_pdgp_far_field_backward(model._plan))
+    return -f, -np.asarray(g), model_grad_dict(model), far, bar, tq.assert_device_ranges(h, model, prob, far, bar)
+
+
+def test_one_plan_while_the_lengthscale_moves(gp_handle):
+    """Training keeps one plan, its workspace and the device-side transform while the lengthscale moves, so ranges, tile tables and
+    the blocks written only where a run ends (Um, Vp, Wv, CnF) live on from a step with other ranges.  Four evaluations through
+    Pdgp._objective on one model, packed once, at 25, 4, 25 and 8 spacings: after each the device's tables are the numpy
+    rule's at that lengthscale, each agrees bit for bit with a fresh model evaluated once at that lengthscale through the same
+    entry, and the first and third agree bit for bit.  The same walk on plans with permission 3 (split-K backward) and 1
+    (dense product) stays within the bars between forms at every step."""
+    h = gp_handle
+    c = CASES["128x1024x1_l8"]
+    fresh = {}
+    for ls in sorted(set(MOVING_LS)):
+        prob = tq._problem(**dict(c, ls=ls))
+        model = _free_model(prob, h)
+        x = model.get_free_state()
+        fresh[ls] = (x,) + _objective(model, x, h, prob)
+        assert fresh[ls][4:6] == (1, 1), ls
+    xs = [fresh[ls][0] for ls in sorted(fresh)]
+    assert all(int((xs[0] != x).sum()) == 1 for x in xs[1:])             # the states differ in the lengthscale alone
+    prob = tq._problem(**c)
+    model = _free_model(prob, h)
+    packs, pack = [], model._pack
+    object.__setattr__(model, "_pack", lambda: (packs.append(1), pack())[1])
+    walk = []
+    for ls in MOVING_LS:
+        step = _objective(model, fresh[ls][0], h, prob)
+        want = fresh[ls]
+        assert step[3:5] == (1, 1), ls
+        assert step[5] == want[6], ls                                    # (both already equal the numpy rule at the device's lengthscale)
+        assert step[0] == want[1] and np.array_equal(step[1], want[2]), (ls, step[0], want[1])
+        walk.append(step)
+    assert len(packs) == 1
+    assert all(a[5] != b[5] for a, b in zip(walk, walk[1:]))             # the ranges moved at every step
+    assert walk[0][0] == walk[2][0] and np.array_equal(walk[0][1], walk[2][1])
+    for perm, flags in ((3, (1, 0)), (1, (0, 0))):
+        other = _free_model(prob, h)
+        other._pack()
+        h.check(h.lib.gp_pdgp_set_qform(other._plan, perm))
+        for k, ls in enumerate(MOVING_LS):
+            f0, _, g0, far, bar, _ = _objective(other, fresh[ls][0], h, prob)
+            assert (far, bar) == flags, (perm, ls)
+            f1, g1 = walk[k][0], walk[k][2]
+            dev = abs(f1 - f0) / abs(f0)
+            worst = max(np.abs(g1[n] - g0[n]).max() / max(np.abs(g0[n]).max(), 1e-12) for n in g0)
+            print("step %d (l = %d spacings) against permission %d: ELBO %.2e relative, gradient blocks worst %.2e" % (k, ls, perm, dev, worst))
+            if perm == 3:
+                assert f1 == f0, (f1, f0)                                # the forward pass is the same
+            assert dev <= tq.FAR_VS_DENSE_ELBO and worst <= FAR_VS_DENSE, (perm, ls, dev, worst)
 
 
 def _child(path):

@@ -17,8 +17,9 @@ Q_VS_CHOL = 1e-9            # x block scale: the project's bar for two float64 f
 # M x N x P.  The components are the benchmark's in proportion: 20 partials and a lengthscale of 25 inducing spacings (0.25 ms
 # at these sizes), which keeps tr(K) tr(K^-1) at 1.2 M^2 (the benchmark's 1.4).  With 3 partials the mixture decorrelates
 # nothing at this spacing and only a lengthscale of 2 spacings is as well conditioned — and then x / l reaches M / 2, the
-# rounding of the expanded squared distance (x / l)^2 2e-16 reaches the 1e-12 under the root, and engine and oracle disagree
-# about r at every frame that coincides with an inducing point: com0.lengthscales 3e-6 apart, on either route.
+# rounding of the expanded squared distance (x / l)^2 2e-16 reaches the 1e-12 under the root, and autograd's lengthscale gradient
+# is rounding noise at every frame that coincides with an inducing point: com0.lengthscales 3e-6 apart, on either route
+# (test_inducing_inputs_on_frames_far_from_the_origin_against_oracle takes such a shape, against finite differences).
 SHAPES = {
     "64x256x1": dict(N=256, M=64, P=1),          # one tile, one column group
     "128x512x2": dict(N=512, M=128, P=2),        # two row tiles, two families in one batch
@@ -119,6 +120,58 @@ def test_q_route_against_oracle(gp_handle, oracle_refs, shape):
             rg = np.tril(rg[:, :, 0])[:, :, None]
         scale = max(np.abs(rg).max(), 1e-12)
         np.testing.assert_allclose(g[name].reshape(rg.shape), rg, rtol=0, atol=ORACLE_TOL * scale, err_msg=name)
+
+
+def test_inducing_inputs_on_frames_far_from_the_origin_against_oracle(gp_handle):
+    """M = 256 inducing inputs on every fourth of 1024 frames, a lengthscale of one spacing: x / l reaches 256 and one ulp of its
+    square 7e-12, seven times the 1e-12 under the root of r = sqrt((a - b)^2 + 1e-12).  The covariance build, the oracle and
+    TensorFlow scale both inputs the same way, so a frame that coincides with an inducing input has a = b to the bit, the expanded
+    square is 0 and r is 1e-6.  The matrix-core contractions (bwd.hip) scaled one side by x / l and the other by x * (1 / l):
+    an ulp apart at 26 of these 256 pairs, the square then -7e-12 ... 0 instead of 0 — below -1e-12 at six of them, where the
+    root is NaN and with it the lengthscale's gradient (found by test_gpu_qfar.py's M = 1024 case, on every route).
+    Both routes at the bars of this file: against autograd for every block but that lengthscale.  Autograd differentiates the three
+    terms of -2 a b + a a + b b one by one, so at a coincident pair its d r2 / d l is the rounding of three terms of size
+    4 a^2 / l, not 0, and d r / d l = that / 2e-6: 2e-5 of the block's scale here, different on every BLAS.  The reference for
+    the lengthscale is the central difference of the oracle's ELBO (numpy, four points, Richardson), whose own error the test
+    bounds by taking it at two step sizes (measured: 1e-10 apart; the engine 9e-11 from it, autograd 1.8e-5)."""
+    import copy
+    from helpers import oracle_elbo
+    prob = _problem(N=1024, M=256, P=1, ls_com=0.00025)
+
+    def central(rel):
+        def F(scale):
+            p = copy.deepcopy(prob)
+            p["kern_com"][0]["lengthscales"] = prob["kern_com"][0]["lengthscales"] * scale
+            return float(oracle_elbo(p))
+        d1, d2 = (F(1 + rel) - F(1 - rel)) / (2 * rel), (F(1 + 2 * rel) - F(1 - 2 * rel)) / (4 * rel)
+        return (4 * d1 - d2) / 3 / prob["kern_com"][0]["lengthscales"]
+    fd, fd_b = central(3e-3), central(1e-3)
+    print("d ELBO / d l by central differences: %.10e and %.10e, %.2e apart" % (fd, fd_b, abs(fd - fd_b) / abs(fd)))
+    assert abs(fd - fd_b) <= 0.1 * ORACLE_TOL * abs(fd)
+    z, x, ls = np.ravel(prob["zc"][0]), np.ravel(prob["x"]), float(prob["kern_com"][0]["lengthscales"])
+    on = np.isin(z, x)
+    a, b = z[on] / ls, z[on] * (1.0 / ls)
+    r2 = ((-2.0 * a) * b + a * a) + b * b
+    assert on.all() and (r2 < -1e-12).any()                 # the mixed form has no root here; either form alone gives 0
+    ref_f, ref_g = oracle_elbo_and_grads(prob)
+    for qform in (None, 0):
+        f, v, g, _ = _evaluate(prob, gp_handle, qform=qform)
+        assert np.all(np.isfinite(v)), [n for n in g if not np.all(np.isfinite(g[n]))]
+        print("qform %s: ELBO %.2e relative to the oracle" % (qform, abs(f - ref_f) / abs(ref_f)))
+        worst = {}
+        for name, rg in ref_g.items():
+            if name.startswith("za") or name.startswith("zc"):
+                continue
+            if name.startswith("q_sqrt"):
+                rg = np.tril(rg[:, :, 0])[:, :, None]
+            if name == "com0.lengthscales":
+                print("qform %s: %s against autograd %.2e" % (qform, name, abs(float(g[name][0]) - float(rg)) / abs(float(rg))))
+                rg = np.array(fd)
+            worst[name] = np.abs(g[name].reshape(rg.shape) - rg).max() / max(np.abs(rg).max(), 1e-12)
+        top = sorted(worst, key=worst.get)[-3:]
+        print("qform %s: gradient blocks against autograd, worst %s" % (qform, ["%s %.2e" % (n, worst[n]) for n in top]))
+        assert abs(f - ref_f) <= ELBO_RTOL * abs(ref_f), (f, ref_f)
+        assert all(d <= ORACLE_TOL for d in worst.values()), {n: d for n, d in worst.items() if not d <= ORACLE_TOL}
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))

@@ -4,7 +4,7 @@ written (64 KiB guard bands of a fixed byte on both sides), (b) the results equa
 its fill byte).  The models allocate through Handle.workspace, which is replaced here by an allocator that hands out
 the 256-byte aligned interior of a filled tensor with numel() == the requested size.
 
-Covered: Pdgp (whitened / unwhitened x float64 / float32 / mixed, and a gp_pdgp_create_subset plan), SGPR (M = 64 and the
+Covered: Pdgp (whitened / unwhitened x float64 / float32 / mixed, a Q-route plan with its far field, and a gp_pdgp_create_subset plan), SGPR (M = 64 and the
 blocked factorisation at M = 320, float64 / float32, predict_source), the window batch (ragged counts, predict_f,
 predict_source in chunks of 2), a PdgpBatch training plan, and the handle-free conditionals / KL / Kuu factorisation with a
 32-partial Mercer kernel at N = 8 and 300, and a prediction-only PdgpBatch plan (predict, predict_moments)."""
@@ -88,6 +88,26 @@ def test_pdgp_workspace(gp_handle, monkeypatch, whiten, float_type):
         m = pdgp_from_problem(prob, whiten=whiten, handle=gp_handle, float_type=float_type)
         m._pack()
         return {"elbo": m._elbo(True), "grad": m._grad.cpu().numpy().copy()}
+    _check(gp_handle, monkeypatch, run, exact_keys=("elbo",))
+
+
+def test_pdgp_q_route_far_field_workspace(gp_handle, monkeypatch):
+    """a plan whose components take the Q route with its far field forward and backward: the carve of T, Psi,
+    CnF, CFF, cn, cF, Um / Vp, Wv, rng2 and tS between the guard bands and at its exact size, with ranges that differ per GP"""
+    import test_gpu_qfar as tq
+    from helpers import pdgp_from_problem
+    prob = tq._problem(N=1024, M=128, P=2, ls=[8, 25])
+    assert [r[:2] for r in tq._ranges(prob, 0)] != [r[:2] for r in tq._ranges(prob, 1)]
+
+    def run():
+        m = pdgp_from_problem(prob, handle=gp_handle)
+        m.za.fixed = True
+        m.zc.fixed = True
+        m._pack()
+        out = {"elbo": m._elbo(True), "grad": m._grad.cpu().numpy().copy()}
+        assert int(gp_handle.lib.gp_pdgp_far_field(m._plan)) == 1 and int(gp_handle.lib.gp_pdgp_far_field_backward(m._plan)) == 1
+        tq.assert_device_ranges(gp_handle, m, prob, 1, 1)
+        return out
     _check(gp_handle, monkeypatch, run, exact_keys=("elbo",))
 
 

@@ -12,6 +12,7 @@ import qbar_rule as qb
 M, N = 128, 2048
 FS = 16000.0
 SPACING = (N // M) / FS
+GAP_N0, GAP_LS = 3 * 256 + 5 * 32 + 11, 8
 
 # layout -> (inducing inputs, one spacing of theirs in seconds)
 def _z(layout):
@@ -20,6 +21,14 @@ def _z(layout):
         return x, x[::N // M].copy(), SPACING
     if layout == "off_grid":
         return x, x[::N // M] + 0.37 / FS, SPACING
+    if layout == "frame_gap":
+        # test_gpu_qfar.py's frame_gap layout (two excerpts joined): off-grid z, and every frame from GAP_N0 on — inside the sixth
+        # strip of the fourth group — with every inducing input behind it shifted by 400 lengthscales of GAP_LS spacings
+        z = x[::N // M] + 0.37 / FS
+        t0, shift = x[GAP_N0], 400.0 * GAP_LS * SPACING
+        x[GAP_N0:] += shift
+        z[z >= t0] += shift
+        return x, z, SPACING
     # test_gpu_qfar.py's clustered and gap layouts over eight groups: several inducing inputs per group, groups with none
     step, per = {"clustered": (5.8, [44, 42, 0, 42, 0, 0, 0, 0]), "gap": (5.2, [48, 32, 0, 0, 48, 0, 0, 0])}[layout]
     z = np.concatenate([(g * 256 + 0.37 + step * np.arange(k)) / FS for g, k in enumerate(per)])
@@ -30,6 +39,7 @@ def _z(layout):
 CASES = [(lay, ls, 20) for lay in ("on_grid", "off_grid", "clustered", "gap") for ls in (4, 8, 25)]
 CASES += [(lay, 2, 3) for lay in ("on_grid", "off_grid", "clustered", "gap")]
 CASES += [("on_grid", 10000, 20), ("gap", 10000, 3)]
+CASES += [("frame_gap", GAP_LS, 20)]         # ranges that are not monotone: the widening changes them
 
 
 @pytest.mark.parametrize("layout,ls_spacings,m", CASES)
@@ -43,7 +53,12 @@ def test_far_form_within_ten_times_the_dense_form(layout, ls_spacings, m):
     K = qf.kuf_builder(z, x, var, ls, fz, fx)
     d, gm = rs.standard_normal(N), rs.standard_normal(N)            # mixed sign
     Q, v, rng = qb.qbar_far(K, d, gm, z, x, var, ls, fz, fx)
-    assert qb.is_monotone(rng), [(kb, ke) for kb, ke, _, _ in rng]
+    if layout == "frame_gap":
+        # the group with the gap is all near between narrower neighbours: widened, kb = 0 up to it and ke = M from it on
+        assert not qb.is_monotone(rng), [(kb, ke) for kb, ke, _, _ in rng]
+        assert qb.monotone(rng) == ([0, 0, 0, 0, 48, 64, 80, 96], [32, 48, 64, 128, 128, 128, 128, 128])
+    else:
+        assert qb.is_monotone(rng), [(kb, ke) for kb, ke, _, _ in rng]
     if layout == "gap":
         assert ls_spacings == 10000 or any(kb == ke for kb, ke, _, _ in rng)
     if ls_spacings == 10000:

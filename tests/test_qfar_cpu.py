@@ -11,6 +11,8 @@ M, N, NPART = 128, 2048, 20
 FS = 16000.0
 SPACING = (N // M) / FS                  # one inducing spacing on the grid: 16 frames
 LS_SPACINGS = (4, 8, 25, 10000)
+GAP_N0, GAP_LS = 3 * 256 + 5 * 32 + 11, 8
+LAYOUTS = [(case, s) for s in LS_SPACINGS for case in ("on_grid", "off_grid", "clustered", "both_ends")] + [("frame_gap", GAP_LS)]
 
 
 def _z(case):
@@ -25,6 +27,13 @@ def _z(case):
         z = np.sort((starts[:, None] + (np.arange(16) * 1.3 / FS)[None, :]).reshape(-1))
     elif case == "both_ends":
         z = np.concatenate([x[:4 * 64:4], x[N - 4 * 64::4]])
+    elif case == "frame_gap":
+        # test_gpu_qfar.py's frame_gap layout (two excerpts joined): off-grid z, and every frame from GAP_N0 on — inside the sixth
+        # strip of the fourth group — with every inducing input behind it shifted by 400 lengthscales of GAP_LS spacings
+        z = x[::N // M] + 0.37 / FS
+        t0, shift = x[GAP_N0], 400.0 * GAP_LS * SPACING
+        x[GAP_N0:] += shift
+        z[z >= t0] += shift
     else:
         raise ValueError(case)
     assert z.shape == (M,) and np.all(z[1:] >= z[:-1])
@@ -49,11 +58,14 @@ def side_counts():
     return {}
 
 
-@pytest.mark.parametrize("ls_spacings", LS_SPACINGS)
-@pytest.mark.parametrize("case", ["on_grid", "off_grid", "clustered", "both_ends"])
+@pytest.mark.parametrize("case,ls_spacings", LAYOUTS)
 def test_far_form_within_ten_times_the_dense_form(case, ls_spacings, side_counts):
     x, z, var, ls, fz, fx, Q, K = _case(case, ls_spacings)
     rng, T, Psi = qf.tables(Q, z, x, var, ls, fz, fx)
+    if case == "frame_gap":
+        # the strip with the gap spans more than 300 lengthscales: its group is all near between narrower neighbours, so the
+        # running maxima of the T recurrence (qfar_t_kernel's) hold rows that group's own range does not call far
+        assert [(kb, ke) for kb, ke, _, _ in rng] == [(0, 32), (0, 48), (16, 64), (0, 128), (48, 96), (64, 112), (80, 128), (96, 128)]
     side_counts[(case, ls_spacings)] = qf.sides(rng, M)
     g_new, g_dense = qf.g_far(Q, K, rng, T, Psi), qf.g_dense(Q, K)
     ref = Q.astype(np.longdouble) @ K.astype(np.longdouble)
