@@ -117,6 +117,23 @@ bool qbar_takes(int M, int N, int m);
 // count GPs of one family (M, m) over n frames, behind the tables and the likelihood's gv / gm: four launches on h->stream
 gp_status launch_qbar(gp_handle h, const QbarItem* d_items, int count, int M, int m, int n);
 
+// afar.hip: the activations' A = W Kuf and colsum((Lq^T A)^2) from near rows plus an exact rank-4 far field,
+// one item per latent GP of the run: the conditional's operands and outputs, C = tril(Lq)^T W, and the tables of this step
+// W, C, T, q_mu are read through the constant address space (scalar loads at wave-uniform addresses): none of them may alias
+// A, s1, s2 or dot, and nothing may write them while afar_prod_kernel runs — they are left by earlier launches of the stream.
+struct AfarItem {
+  const double* z; const double* theta; const double* W; const double* C; const double* Kuf; const double* q_mu;
+  double* A; double* s1; double* s2; double* dot;    // the stored strip; ONE partial row each of colsum(A^2), colsum((C Kuf)^2), A^T q_mu
+  int* rng; double* ref; double* T; double* Psi;     // [groups][2] near range, [groups][2] xmin / xmax, T [groups][M][8], Psi [4][N]
+  int64_t ld; int M, pad;
+};
+#define AFAR_GROUP 256       // frames per column group: one workgroup of the product
+struct AfarSizes { size_t rng, ref, T, Psi, C; };    // doubles
+AfarSizes afar_sizes(int M, int N);
+bool afar_takes(int M, int N);
+// count GPs of one family (M) over the n ascending frames x, behind C: the tables' two launches and the product's one on h->stream
+gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, const double* x, int n);
+
 #define CB_NB 128          // panel width of the blocked Kuu factorisation
 #define CB_MAX_PANELS 8    // M <= 1024
 
@@ -184,7 +201,10 @@ struct CondBatch {
   // instead of A = W Kuf and Lq^T A when cond_batch_run is given a hook; set before cond_batch_upload
   int q0 = 0, nq = 0;
   bool q_far = false;     // the run's product is role 7 (near rows + far field) instead of role 6; the hook fills the tables too
-  bool q_desc = false;    // the descriptor block was sized with the Q route's regions (cond_batch_desc_bytes(count, true))
+  // activation far field: the tasks [a0, a0 + na) — float64, whitened, Matern-3/2 — leave A = W Kuf and Lq^T A
+  // to the caller's hook (afar.hip), which fills the A strip and one partial row each of s1, s2 and dot; set before cond_batch_upload
+  int a0 = 0, na = 0;
+  bool q_desc = false;    // the descriptor block was sized with the routes' regions (cond_batch_desc_bytes(count, true))
   bool feat_ready = false;   // q_far: gp_handle_s::ev_feat was recorded behind the Kuf builds (their feature tables)
   bool diag_ready = false;   // set by a factorisation that recorded gp_handle_s::ev_diag after the diagonal blocks of W
 };
@@ -199,8 +219,11 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
 // q_prepare: take the Q route for the tasks [q0, q0 + nq).  The hook is called once the factorisation is enqueued and the other
 // tasks' strip products are; it enqueues what fills Qm and beta and makes h->stream wait for it.  Null: every task takes
 // the Cholesky route (predictions always do).
+// a_run: the tasks [a0, a0 + na) take the activation far field.  The hook is called once the factorisation has joined the main
+// stream and enqueues their A strips and partial rows there.  Null: those tasks take the dense products.
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
-                         bool reuse_factor = false, const std::function<gp_status()>* q_prepare = nullptr);
+                         bool reuse_factor = false, const std::function<gp_status()>* q_prepare = nullptr,
+                         const std::function<gp_status()>* a_run = nullptr);
 // steps 1-2 of cond_batch_run alone, on the current stream: Kuu + jitter I -> L, W of every task (the uploaded descriptors'),
 // for a caller that needs the factorisation and no conditional (sample.hip)
 gp_status cond_batch_factor(gp_handle h, CondBatch& cb);

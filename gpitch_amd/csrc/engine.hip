@@ -85,7 +85,7 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
   const bool blk256 = gp_switches().blocked_256 != 0;
   cb.blocked = (cb.maxM > 256 || (blk256 && cb.maxM > 128 && cb.N >= 4096)) && cb.nblk <= CB_MAX_PANELS;
   cb.off = cond_batch_desc_layout(G, cb.blocked ? cb.nblk : 0, cb.q_desc);
-  if (cb.nq > 0 && !cb.q_desc) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a Q run without its descriptor regions");
+  if ((cb.nq > 0 || cb.na > 0) && !cb.q_desc) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a Q run or a far-field run without its descriptor regions");
   cb.h_desc.assign(cb.off.bytes, 0);
   double** cp = (double**)(cb.h_desc.data() + cb.off.chol_ptrs);
   double** wp = (double**)(cb.h_desc.data() + cb.off.w_ptrs);
@@ -141,6 +141,12 @@ gp_status cond_batch_upload(gp_handle h, CondBatch& cb, bool whiten, double jitt
         fq[g].xa = (const double*)t.far_rng; fq[g].v1 = t.far_T; fq[g].v2 = t.far_Psi;
       }
       cond_finish_fill(fin_q + g * cond_finish_item_bytes(), t.s1, 0, t.s2, rb64, t.dot, rb64, t.kern, t.fmean, t.fvar);
+    }
+    // activation far field (afar.hip): the product leaves the complete column sums, one partial row each
+    if (g >= cb.a0 && g < cb.a0 + cb.na) {
+      if (!whiten || t.f32 || !t.q_sqrt || (g >= cb.q0 && g < cb.q0 + cb.nq))
+        return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: a task of the far-field run does not qualify");
+      cond_finish_fill(fin_q + g * cond_finish_item_bytes(), t.s1, 1, t.s2, 1, t.dot, 1, t.kern, t.fmean, t.fvar);
     }
   }
   // Grouped covariance builds: the latent GPs are sorted into kernel families (type, padded partial count); each
@@ -355,7 +361,7 @@ gp_status cond_batch_factor(gp_handle h, CondBatch& cb) {
 }
 
 gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, bool whiten, double jitter,
-                         bool reuse_factor, const std::function<gp_status()>* q_prepare) {
+                         bool reuse_factor, const std::function<gp_status()>* q_prepare, const std::function<gp_status()>* a_run) {
   const int G = (int)cb.tasks.size();
   if (G == 0 || N <= 0) return GP_OK;
   if (!cb.uploaded || cb.N != N) return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch descriptors not uploaded");
@@ -387,14 +393,25 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
   // a strip product over the batch: the float64 tasks [0, n64) on the float64 kernels, the float32 tasks behind them on the
   // float32 ones (f32flags: the flags of the float32 launch where they differ)
   // Q route: the run [q0, q0 + nq) of float64 tasks is left out of these products (one launch on either side of it)
+  // activation far field: so is the run [a0, a0 + na), which the caller's hook covers
   const int q0 = (q_prepare && cb.nq > 0) ? cb.q0 : 0, q1 = (q_prepare && cb.nq > 0) ? cb.q0 + cb.nq : 0;
+  const int a0 = (a_run && cb.na > 0) ? cb.a0 : 0, a1 = (a_run && cb.na > 0) ? cb.a0 + cb.na : 0;
+  const bool routed = (q1 > q0) || (a1 > a0);
+  // (the routes' finish records are one array: an evaluation takes every route the descriptors were bound for, or none)
+  if (routed && ((cb.nq > 0) != (q1 > q0) || (cb.na > 0) != (a1 > a0)))
+    return gp_fail(h, GP_ERR_BAD_ARG, "conditional batch: the bound routes and the hooks given do not match");
   auto strips = [&](size_t off, const GemmFlags& f, const GemmFlags* f32flags = nullptr) -> gp_status {
     const GemmProblem* d = (const GemmProblem*)(cb.d_desc + off);
     const int n64 = (cb.n64 < 0) ? (cb.f32 ? 0 : G) : cb.n64;
-    if (q1 > q0) {
-      if (q0 > 0) GP_CHECK(launch_gemm_batched(h, d, q0, cb.maxM, N, f));
-      if (q1 < n64) GP_CHECK(launch_gemm_batched(h, d + q1, n64 - q1, cb.maxM, N, f));
-    } else if (n64 > 0) GP_CHECK(launch_gemm_batched(h, d, n64, cb.maxM, N, f));
+    // (the float64 tasks without the two runs, in order: one launch per stretch that is left)
+    const int cut[2][2] = {{q0 <= a0 ? q0 : a0, q0 <= a0 ? q1 : a1}, {q0 <= a0 ? a0 : q0, q0 <= a0 ? a1 : q1}};
+    int pos = 0;
+    for (int c = 0; c < 2; c++) {
+      if (cut[c][1] <= cut[c][0]) continue;
+      if (cut[c][0] > pos) GP_CHECK(launch_gemm_batched(h, d + pos, cut[c][0] - pos, cb.maxM, N, f));
+      if (cut[c][1] > pos) pos = cut[c][1];
+    }
+    if (pos < n64) GP_CHECK(launch_gemm_batched(h, d + pos, n64 - pos, cb.maxM, N, f));
     if (n64 < G) {
       GemmFlags g32 = f32flags ? *f32flags : f;
       // (float32 tasks: their own wave form — scratch for the float32 copy of the M x M operand is in xb; partial rows per 64-row tile)
@@ -456,6 +473,8 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
       GP_CHECK(cond_a(0, 0));
     }
   }
+  // 4a. the far-field run's A strips and partial rows (afar.hip): W is whole behind the join
+  if (a1 > a0) GP_CHECK((*a_run)());
   if (!whiten) {
     GemmFlags f;
     f.transA = 1; f.triA = TRI_UPPER; f.big_tiles = 1; f.timer = GP_TIMER_COND_A;
@@ -488,6 +507,6 @@ gp_status cond_batch_run(gp_handle h, CondBatch& cb, const double* x, int N, boo
     GP_CHECK(launch_gemm_batched(h, (const GemmProblem*)(cb.d_desc + cb.off.fq) + q0, q1 - q0, cb.maxM, N, f));
   }
   // 6. fmean / fvar
-  GP_CHECK(launch_cond_finish(h, cb.d_desc + ((q1 > q0) ? cb.off.finish_q : cb.off.finish), G, N));
+  GP_CHECK(launch_cond_finish(h, cb.d_desc + (routed ? cb.off.finish_q : cb.off.finish), G, N));
   return GP_OK;
 }

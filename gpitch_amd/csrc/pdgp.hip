@@ -149,6 +149,27 @@ int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, 
   if (gp_index) *gp_index = g;
   return ng;
 }
+gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (p->afar_ok != (enable != 0)) { p->afar_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
+  return GP_OK;
+}
+int32_t gp_pdgp_far_field_act(gp_pdgp_plan p) { return (p && p->na > 0) ? 1 : 0; }
+// debug: the device's own ranges and reference points of the last evaluation's activation far field, copied to the host
+int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref) {
+  if (!p || !p->ws || p->na <= 0 || i < 0 || i >= p->na || p->last_n <= 0 || !rng || !ref) return 0;
+  const int ng = p->last_n / AFAR_GROUP, g = p->a0 + i;
+  const BwdBufs& b = p->bw[g];
+  if (ng <= 0 || ng > cap_groups || !b.af_rng || !b.af_ref) return 0;
+  gp_handle h = p->h;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  if (h->aux_stream && hipStreamSynchronize(h->aux_stream) != hipSuccess) return 0;
+  if (h->side_stream && hipStreamSynchronize(h->side_stream) != hipSuccess) return 0;
+  if (hipMemcpy(rng, b.af_rng, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (hipMemcpy(ref, b.af_ref, (size_t)2 * ng * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (gp_index) *gp_index = g;
+  return ng;
+}
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
 gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t* off_z, int64_t* off_qmu,
@@ -167,6 +188,8 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
   p->cb.tasks.assign(p->G, CondTask());
   p->cb.q_desc = false;      // (the Q route's descriptor regions: only where a latent GP could take it — as b.Q below)
   for (const PdgpGP& q : p->gps) if (gp_switches().qform != 0 && p->whiten && !q.f32 && q.ktype == GP_KERN_MERCER_MATERN12SM) p->cb.q_desc = true;
+  // (so do the activation far field's finish records, pdgp_afar_select)
+  for (const PdgpGP& q : p->gps) if (gp_switches().act_far != 0 && p->whiten && !q.f32 && q.ktype == GP_KERN_MATERN32 && afar_takes(q.M, p->maxN)) p->cb.q_desc = true;
   p->cb.d_desc = ar.take<char>(cond_batch_desc_bytes(p->G, p->cb.q_desc));
   p->off = pdgp_misc_layout(p->G);
   p->d_misc = ar.take<char>(p->off.bytes);
@@ -220,6 +243,13 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
             b.qb_Wv = ar.take<double>(bs.Wv);
           }
         }
+      }
+      // (activation far field, pdgp_bwd.hip pdgp_afar_select: reserved before its setters have spoken, for the plan's largest
+      // batch — at M = 512, N = 32768: 4 MB of T, 1 MB of Psi, 2 MB of C per GP beside two 134 MB strips)
+      if (gp_switches().act_far != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MATERN32 && afar_takes((int)M, p->maxN)) {
+        const AfarSizes as = afar_sizes((int)M, p->maxN);
+        b.af_rng = (int*)ar.take<double>(as.rng); b.af_ref = ar.take<double>(as.ref);
+        b.af_T = ar.take<double>(as.T); b.af_Psi = ar.take<double>(as.Psi); b.af_C = ar.take<double>(as.C);
       }
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;
       b.u = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);
@@ -287,6 +317,9 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
 void pdgp_qform_select(gp_pdgp_plan p, int n);
 void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
 gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n);
+void pdgp_afar_select(gp_pdgp_plan p, int n);
+void pdgp_upload_afar(gp_pdgp_plan p, const double* params);
+gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n);
 
 // (re)bind the parameter vector / batch to the device descriptors
 static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad,
@@ -311,6 +344,8 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   p->cb.maxM = p->maxM;
   pdgp_qform_select(p, n);
   p->cb.q0 = p->q0; p->cb.nq = p->nq; p->cb.q_far = p->q_far;
+  pdgp_afar_select(p, n);
+  p->cb.a0 = p->a0; p->cb.na = p->na;
   for (int g = 0; g < p->G; g++) {
     const bool q = pdgp_on_q_route(p, g);
     CondTask& t = p->cb.tasks[g];
@@ -340,6 +375,7 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
     }
   }
   pdgp_upload_qform(p, params);
+  pdgp_upload_afar(p, params);
   if (grad) GP_CHECK(pdgp_upload_bwd(p, params, x, n, grad));
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_misc, p->h_misc.data(), p->off.bytes, hipMemcpyHostToDevice, h->stream));
   p->last_params = params; p->last_x = x; p->last_n = n; p->last_grad = grad;
@@ -359,7 +395,9 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
   if (grad) GP_HIP_CHECK(h, hipMemsetAsync(grad, 0, (size_t)p->nparams * sizeof(double), h->stream));
   // (an ELBO takes the Q route with or without a gradient, so a step's ELBO is one number; predictions never do)
   const std::function<gp_status()> q_prepare = [&]() -> gp_status { return pdgp_qform_prepare(p, x, n); };
-  GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr));
+  // (so does the activations' far field: predictions keep the dense products)
+  const std::function<gp_status()> a_run = [&]() -> gp_status { return pdgp_afar_run(p, x, n); };
+  GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr, p->na > 0 ? &a_run : nullptr));
   bool kl_done = false;   // the whitened KL kernel went to the helper stream with the backward prefetch
   if (grad) GP_CHECK(pdgp_prefetch_backward(p, n, &kl_done));
   if (kl_done) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));   // behind the forward strips: no stall

@@ -14,6 +14,8 @@ enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
                // Q route, entry i = latent GP q0 + i: E, R, beta and Q = R W of the forward pass (filled whether or
                // not a gradient is asked), then T = W Qbar, H = T W^T and u = W v of the backward pass
                S_QE, S_QR, S_QALPHA, S_QQ, S_QT, S_QHH, S_QU,
+               // activation far field, entry i = latent GP a0 + i: C = tril(Lq)^T W of the forward pass
+               S_AC,
                S_COUNT };
 static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
 static inline const GemmProblem* slot_probs(gp_pdgp_plan p, int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); }
@@ -159,6 +161,56 @@ gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n) {
   GP_CHECK(st);
   if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
   return GP_OK;
+}
+
+// ---- activation far field ---------------------------------------------------------------------------
+// A Matern-3/2 Kuf is exactly semiseparable along sorted inputs, so A = W Kuf and Lq^T A = (Lq^T W) Kuf need, per 256-frame
+// group, only the rows of Kuf near the group plus two M x 2 tables per factor (afar.hip).  Nothing is inverted that the Cholesky
+// route does not invert, and the backward pass reads the same A strip.  Which latent GPs take it at n frames (p->a0, p->na):
+// the switch, gp_pdgp_set_far_act, shapes, types, the gradient needs and the frames' promise — never the overlap level.  All
+// Matern-3/2 GPs of a whitened plan, when they are float64, over fixed inducing inputs, of the batch's one M, in one run.
+void pdgp_afar_select(gp_pdgp_plan p, int n) {
+  p->a0 = p->na = 0;
+  if (!gp_switches().act_far || !p->afar_ok || !p->whiten || !p->frames_ascending) return;
+  int first = -1, last = -1, cnt = 0;
+  for (int g = 0; g < p->G; g++) {
+    const PdgpGP& q = p->gps[g];
+    if (q.ktype != GP_KERN_MATERN32) continue;
+    if (q.f32 || q.need_z || q.M != p->maxM || !p->bw[g].af_T || pdgp_on_q_route(p, g)) return;
+    if (first < 0) first = g;
+    last = g; cnt++;
+  }
+  if (cnt == 0 || last - first + 1 != cnt) return;
+  if (!cond_batch_uniform(p->cb, n) || !afar_takes(p->maxM, n)) return;
+  p->a0 = first; p->na = cnt;
+}
+
+// the forward pass's descriptors of that run (pdgp_bind, with or without a gradient)
+void pdgp_upload_afar(gp_pdgp_plan p, const double* params) {
+  for (int i = 0; i < p->na; i++) {
+    const int g = p->a0 + i;
+    const PdgpGP& q = p->gps[g];
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& b = p->bw[g];
+    const int M = q.M;
+    GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[S_AC] + i * sizeof(GemmProblem));
+    memset(&r, 0, sizeof(r));
+    r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+    r.A = params + q.off_qsqrt; r.B = t.W; r.C = b.af_C;
+    AfarItem& it = *(AfarItem*)(p->h_misc.data() + p->off.af_items + i * sizeof(AfarItem));
+    it = AfarItem{t.z, t.kern.theta, t.W, b.af_C, t.Kuf, t.q_mu, t.A, t.s1, t.s2, t.dot,
+                  b.af_rng, b.af_ref, b.af_T, b.af_Psi, gp_strip_ld(p->cb.N, false), M, 0};
+  }
+}
+
+// C = tril(Lq)^T W, the tables and the product of the run: cond_batch_run's hook (pdgp.hip), on the main stream behind W
+gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n) {
+  gp_handle h = p->h;
+  if (p->na <= 0) return GP_OK;
+  GemmFlags f;
+  f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_AC), p->na, p->maxM, p->maxM, f));
+  return launch_afar(h, (const AfarItem*)(p->d_misc + p->off.af_items), p->na, p->maxM, x, n);
 }
 
 // E = Lq Lq^T - I (ERA_E) and R = W^T E, alpha = W^T q_mu (ERA_R) over the compacted batch without the Q run, whose E, R and

@@ -12,7 +12,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // (pdgp_bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
-struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, qb_items, bytes; };
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, qb_items, af_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   PdgpMiscLayout o;
   GpRegions region;
@@ -25,6 +25,7 @@ static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   o.ks_items = region((size_t)G * sizeof(KufScanItem));       // kuf_scan.hip: one per latent GP, in the families' item order
   o.qf_items = region((size_t)G * sizeof(QfarItem));          // qfar.hip: one per latent GP of the Q run
   o.qb_items = region((size_t)G * sizeof(QbarItem));          // qbar.hip: one per latent GP of the Q run
+  o.af_items = region((size_t)G * sizeof(AfarItem));          // afar.hip: one per latent GP of the activation far-field run
   o.bytes = region.off;
   return o;
 }
@@ -61,6 +62,9 @@ struct BwdBufs {  // per-GP backward workspace (device)
   // vectors, the recurrences' results — carved behind the tables
   int* qb_rng2 = nullptr; int* qb_tS = nullptr; double* qb_CnF = nullptr; double* qb_CFF = nullptr; double* qb_cn = nullptr;
   double* qb_cF = nullptr; double* qb_Um = nullptr; double* qb_Vp = nullptr; double* qb_Wv = nullptr;
+  // the activations' far field (afar.hip): near ranges, xmin / xmax, T, Psi and C = tril(Lq)^T W — Matern-3/2 GPs
+  // of a whitened float64 plan whose shape admits it
+  int* af_rng = nullptr; double* af_ref = nullptr; double* af_T = nullptr; double* af_Psi = nullptr; double* af_C = nullptr;
   double* R32 = nullptr;    // float32 strips only: M * M floats, the float32 copy of R (gemm_wave_f32.hip)
   double* G = nullptr;      // M x N   K̄uf (dense part R (A D))
   double* u = nullptr;      // M       A gm
@@ -147,6 +151,10 @@ struct gp_pdgp_plan_s {
   // the bound run takes it — its problems then leave the split-K launch, which covers the other latent GPs
   bool q_bar_ok = false, q_bar = false;
   bool qbar_ahead = false;     // this backward pass has put those launches on the main stream (pdgp_backward)
+  // activation far field (pdgp_bwd.hip pdgp_afar_select): gp_pdgp_set_far_act's permission — the caller vouches
+  // that the inducing inputs of every Matern-3/2 GP ascend — and the run [a0, a0 + na) that takes it at the bound batch size
+  bool afar_ok = false;
+  int a0 = 0, na = 0;
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

@@ -276,9 +276,39 @@ class Pdgp(Parameterized):
         # may the backward pass's Kuf diag(2 gv) Kuf^T and Kuf gm
         allow = int(self._qform_admissible())
         h.check(h.lib.gp_pdgp_set_qform(self._plan, allow | (6 if allow and self._qform_z_ascending() else 0)))
+        # the activations' far field: whitened, ascending inducing inputs, a lengthscale of at most
+        # FAR_ACT_MAX_SPACINGS inducing spacings
+        h.check(h.lib.gp_pdgp_set_far_act(self._plan, int(self._far_act_admissible())))
         h.check(h.lib.gp_transform_backward(h.h, self._params.data_ptr(), self._tcode.data_ptr(), self._nparams,
                                             self._free.data_ptr()))
         self._packed_key = self._host_key()
+
+    # The far-field form of A = W Kuf and Lq^T A rounds the far entries of Kuf another way than the strip builder does, and W
+    # carries the difference into the gradient in proportion to cond(Kuu).  Measured against the dense products:
+    # 4.6e-10 of the lengthscale gradient at 250 inducing spacings, 5.2e-9 at 1000 — about the 1.75th power.  The project's bar
+    # for two float64 forms of one gradient is 1e-9 of a block's scale, which that law meets at some 390 spacings; 300 leaves a
+    # margin.  Beyond it the dense products stay.
+    FAR_ACT_MAX_SPACINGS = 300.0
+
+    def _far_act_admissible(self):
+        """May the engine form A = W Kuf and Lq^T A of the Matern-3/2 latent GPs from near rows plus the exact far field
+        ?  From the values being packed: the model is whitened, the inducing inputs of every such GP ascend (the
+        route takes them fixed and walks them in order), and its lengthscale is at most FAR_ACT_MAX_SPACINGS times their median
+        spacing.  The engine checks shapes, types and gradient needs itself."""
+        if not self.whiten:
+            return False
+        found = False
+        for kern, z in zip(list(self.kern_act) + list(self.kern_com), list(self.za) + list(self.zc)):
+            if int(kern.type_code) != _lib.KERN_MATERN32:
+                continue
+            found = True
+            zz = np.asarray(z.value, dtype=np.float64).reshape(-1)
+            if zz.shape[0] < 2 or not np.all(zz[1:] >= zz[:-1]):
+                return False
+            spacing = float(np.median(np.diff(zz)))
+            if not (float(np.ravel(kern.lengthscales.value)[0]) <= self.FAR_ACT_MAX_SPACINGS * spacing):
+                return False
+        return found
 
     def _qform_admissible(self):
         """May the engine take its Q route (one dense product where the Cholesky route needs three) for the

@@ -285,6 +285,23 @@ int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p);
 int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref,
                                  int32_t* rng2, int32_t* s0, int32_t* sa);
 
+/* Permission for the activations' far field, from a caller that knows the inducing inputs of every Matern-3/2
+ * latent GP of the plan ascend.  enable != 0: when ALL Matern-3/2 latent GPs of a whitened plan have float64 strips, the batch's
+ * one M (a multiple of 16, at most 1024), fixed inducing inputs (no need_z), sit in one run of the batch, the frames are promised
+ * ascending (gp_pdgp_set_frames_ascending), the batch is a multiple of 256 frames and a strip has 2^20 entries or more,
+ * gp_pdgp_elbo and its staged forms form their A = W Kuf and the column sums of (Lq^T A)^2 per group of 256 frames from the rows
+ * of Kuf whose inducing inputs lie inside the group's span, and add the rows beyond through two exact M x 2 tables per side
+ * (a Matern-3/2 Kuf is semiseparable along sorted inputs): the same A to rounding.  Nothing is inverted that the dense route
+ * does not invert.  Predictions, samples and every other family keep the dense products.  Default 0: the dense products;
+ * GPITCH_AMD_SWITCHES=act_far=0 overrides an enable. */
+gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable);
+/* 1 when the batch last bound qualifies for that route, else 0.  It speaks of ELBO evaluations (gp_pdgp_elbo and its staged
+ * forms), which take the route when it is 1; a prediction binds the batch too and always runs the dense products. */
+int32_t gp_pdgp_far_field_act(gp_pdgp_plan p);
+/* Debug, read-only: as gp_debug_pdgp_far_ranges for latent GP number `i` of the activation far field's run — rng [2 groups]
+ * (kbeg, kend per group of 256 frames), ref [2 groups] (the group's smallest and largest frame time).  Returns the groups written. */
+int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref);
+
 /* Pdgp.build_likelihood (pdgp.py:133-170) on the batch (x, y) of n frames:
  *   elbo = (num_data / n) * sum_n varexp_n - KL.   elbo_dev points to TWO device doubles: [0] the ELBO, [1] the
  * summed KL term (Pdgp.build_prior_kl, pdgp.py:113-131).  When
