@@ -14,6 +14,7 @@ from . import param, kernels, matern12_spectral_mixture, likelihoods, conditiona
 from . import samplecov, kernelfit, pdgp_batch  # noqa: E402,F401
 from .pdgp_batch import optimize_many, predict_many, predict_sources_many, PdgpBatch  # noqa: E402,F401
 from .pdgp_batch import sample_sources_many, check_sampleable  # noqa: E402,F401
+from .pdgp_batch import tie_groups, check_tied  # noqa: E402,F401
 from .sgpr_ss import merged_order, sample_eps_shapes, sample_components  # noqa: E402,F401
 from .init_models import init_liv, init_iv  # noqa: E402,F401
 from .window_overlap import segmented, windowed, merged_mean, merged_variance  # noqa: E402,F401

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "gp_pdgpb_workspace_bytes", "gp_pdgpb_set_workspace", "gp_pdgpb_objective", "gp_pdgpb_adam", "gp_pdgpb_not_pd",
     "gp_pdgpb_natgrad_workspace_bytes", "gp_pdgpb_natgrad", "gp_pdgpb_natgrad_refused",
     "gp_pdgpb_natgrad_adaptive_workspace_bytes", "gp_pdgpb_natgrad_adaptive", "gp_pdgpb_natgrad_counts",
+    "gp_pdgpb_ties_workspace_bytes", "gp_pdgpb_set_ties", "gp_pdgpb_ties_frozen",
     "gp_pdgpb_predict_workspace_bytes", "gp_pdgpb_predict_prepare", "gp_pdgpb_predict",
     "gp_pdgpb_predict_moments_workspace_bytes", "gp_pdgpb_predict_moments",
     "gp_pdgpb_sample_workspace_bytes", "gp_pdgpb_sample",
@@ -269,6 +270,9 @@ def load_library():
         "gp_pdgpb_natgrad_adaptive_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_natgrad_adaptive": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, dbl, dbl, dbl, vp, i32, vp, vp, sz]),
         "gp_pdgpb_natgrad_counts": (i32, [vp, vp, vp, i32]),
+        "gp_pdgpb_ties_workspace_bytes": (sz, [i32, i64, i32]),
+        "gp_pdgpb_set_ties": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i64), vp, sz]),
+        "gp_pdgpb_ties_frozen": (i32, [vp, C.POINTER(i32), i32]),
         "gp_pdgpb_predict_workspace_bytes": (sz, [vp]),
         "gp_pdgpb_predict_prepare": (i32, [vp, vp, vp, sz]),
         "gp_pdgpb_predict": (i32, [vp, vp, vp, C.POINTER(i64), vp, vp, vp, vp, sz]),

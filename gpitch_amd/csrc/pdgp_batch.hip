@@ -12,6 +12,8 @@
 //   pdgpb_adam_kernel  the TF-1.2 Adam update over the concatenated free state, frozen per model after a failed Cholesky
 // With a NatGradAdam token (gp_pdgpb_natgrad) two more launches sit between the backward and the Adam kernel:
 //   pdgpb_ng_form_kernel, pdgpb_ng_apply_kernel   the natural-gradient step on q(u) of every stepped latent GP (further down)
+// With tied parameters (gp_pdgpb_set_ties) one more launch sits right before the Adam kernel:
+//   pdgpb_tie_kernel   every tie group's summed gradient into each member's slot; a tied set with a failed model frozen
 // and, for  [m.predict_act_n_com(x) for m, x in zip(models, xnews)], the prediction kernels pdgpb_pred_* further down.
 // Every reduction is one thread's sequential loop or a fixed tree: two runs give bit-identical results.
 #include "common.h"
@@ -56,6 +58,16 @@ struct PbNgGp {
   int64_t ws;          // its [C^-1 (M x M) | w (M)] block, doubles from the first block of the step's workspace
 };
 
+// tied parameters (gp_pdgpb_set_ties): group j is members[group_start[j] .. group_start[j + 1]), offsets into
+// the parameter vector of slots that are ONE parameter; tied set s is set_models[set_start[s] .. set_start[s + 1]), ascending,
+// the models that a chain of groups joins (two models or more); frozen: one sticky word per model of the plan
+struct PbTies {
+  const int32_t* group_start; const int64_t* members;
+  const int32_t* set_start; const int32_t* set_models;
+  int32_t* frozen;
+  int32_t ngroups, nsets;
+};
+
 struct gp_pdgpb_plan_s {
   gp_handle h = nullptr;
   bool predict_only = false;     // created with cfg->batch == NULL
@@ -80,6 +92,9 @@ struct gp_pdgpb_plan_s {
   // gp_pdgpb_natgrad_adaptive: the workspace whose counters the plan has cleared, and their place
   const void* nga_ws = nullptr;
   int64_t* d_ng_halv = nullptr; double* d_ng_short = nullptr;
+  // gp_pdgpb_set_ties: the uploaded tie groups and tied sets (all in the caller's ties workspace); ngroups == 0: no ties, the
+  // step entries launch no pdgpb_tie_kernel and hand pdgpb_adam_kernel a null tie_frozen
+  PbTies ties = {};
   // prediction-only plans: G blocks (doubles; PbGp::ws is a GP's offset among them), the per-call records, and the
   // workspace / parameters of the last gp_pdgpb_predict_prepare
   int64_t pred_g = 0;
@@ -591,13 +606,15 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
                                                          double* __restrict__ m, double* __restrict__ v,
                                                          const int32_t* __restrict__ owner, const int32_t* __restrict__ status,
                                                          const int32_t* __restrict__ refused,
+                                                         const int32_t* __restrict__ tie_frozen,
                                                          const double* __restrict__ lr_t, int64_t n, double b1, double b2,
                                                          double eps, GpLogisticTable T) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint8_t t = tc[i];
     const int k = owner[i];
-    // frozen: a failed Kuu, or (gp_pdgpb_natgrad; null on the Adam-only path) a refused natural-gradient step
-    if (t == 2 || status[k] != 0 || (refused && refused[k] != 0)) continue;
+    // frozen: a failed Kuu, or (gp_pdgpb_natgrad; null on the Adam-only path) a refused natural-gradient step, or
+    // (gp_pdgpb_set_ties; null without ties) a failed model of the same tied set
+    if (t == 2 || status[k] != 0 || (refused && refused[k] != 0) || (tie_frozen && tie_frozen[k] != 0)) continue;
     double x = fs[i];
     double g = -grad[i];
     if (t == 1) g *= 1.0 / (1.0 + exp(-x));
@@ -609,6 +626,41 @@ __global__ void __launch_bounds__(256) pdgpb_adam_kernel(double* __restrict__ fs
     fs[i] = x;
     params[i] = (t == 1) ? pb_softplus_pos(x)
                          : (t >= 3 ? T.a[t - 3] + (T.b[t - 3] - T.a[t - 3]) / (1.0 + exp(-x)) : x);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// tied parameters (gp_pdgpb_set_ties): one launch between the backward pass (and the natural-gradient kernels)
+// and pdgpb_adam_kernel.  One thread per tie group, PB_TIE_GROUPS groups per workgroup; behind the groups one thread per tied
+// set.  A group's thread walks its member list twice, in the listed order: it sums d ELBO / d parameter over the members
+// (sequentially: no atomics, the same bits in every run) and writes the sum into every member's slot of `grad`.  Every slot
+// belongs to one group at most (gp_pdgpb_set_ties checks it), so no two threads touch the same slot.  The members hold the
+// same free state, moments, transform code and step length: pdgpb_adam_kernel's unchanged arithmetic then moves them alike.
+// A set's thread reads its models' Kuu status and refusal words; when one is raised, every model of the set whose sticky
+// `frozen` word is still 0 gets 1 + the lowest failed model's index, which freezes it in the Adam launch behind this one —
+// the failed model's gradient has been summed into the groups above, and is never applied.
+#define PB_TIE_GROUPS 256
+__global__ void __launch_bounds__(PB_TIE_GROUPS) pdgpb_tie_kernel(PbTies t, double* __restrict__ grad,
+                                                                  const int32_t* __restrict__ status,
+                                                                  const int32_t* __restrict__ refused) {
+  const int i = blockIdx.x * PB_TIE_GROUPS + threadIdx.x;
+  if (i < t.ngroups) {
+    const int32_t a = t.group_start[i], b = t.group_start[i + 1];
+    double s = 0.0;
+    for (int32_t j = a; j < b; j++) s += grad[t.members[j]];
+    for (int32_t j = a; j < b; j++) grad[t.members[j]] = s;
+  } else if (i < t.ngroups + t.nsets) {
+    const int32_t a = t.set_start[i - t.ngroups], b = t.set_start[i - t.ngroups + 1];
+    int32_t failed = -1;
+    for (int32_t j = a; j < b && failed < 0; j++) {       // set_models ascends: the first raised word is the lowest model's
+      const int32_t k = t.set_models[j];
+      if (status[k] != 0 || (refused && refused[k] != 0)) failed = k;
+    }
+    if (failed >= 0)
+      for (int32_t j = a; j < b; j++) {
+        const int32_t k = t.set_models[j];
+        if (t.frozen[k] == 0) t.frozen[k] = 1 + failed;
+      }
   }
 }
 
@@ -1333,6 +1385,116 @@ static gp_status pb_upload(gp_pdgpb_plan_s* p) {
   return GP_OK;
 }
 
+// ---- tied parameters -----------------------------------------------------------------------------------
+// gp_pdgpb_set_ties' regions of its workspace, in order; a plan of nmodels models has at most nmodels / 2 tied sets
+struct PbTieRegions { int32_t* group_start; int64_t* members; int32_t* set_start; int32_t* set_models; int32_t* frozen; };
+static PbTieRegions pb_tie_regions(GpArena& ar, size_t ngroups, size_t nmembers, size_t nmodels) {
+  PbTieRegions r;
+  r.group_start = ar.take<int32_t>(ngroups + 1);
+  r.members = ar.take<int64_t>(nmembers);
+  r.set_start = ar.take<int32_t>(nmodels / 2 + 1);
+  r.set_models = ar.take<int32_t>(nmodels);
+  r.frozen = ar.take<int32_t>(nmodels);
+  return r;
+}
+
+size_t gp_pdgpb_ties_workspace_bytes(int32_t ngroups, int64_t nmembers, int32_t nmodels) {
+  if (ngroups <= 0 || nmembers <= 0 || nmodels <= 0) return 0;
+  return gp_measure([&](GpArena& ar) { pb_tie_regions(ar, (size_t)ngroups, (size_t)nmembers, (size_t)nmodels); }) + GP_WS_TAIL_BATCH;
+}
+
+gp_status gp_pdgpb_set_ties(gp_pdgpb_plan p, int32_t ngroups, const int32_t* group_start, const int64_t* members,
+                            void* workspace, size_t bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (p->predict_only || ngroups < 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_set_ties: bad argument or a prediction-only plan");
+  if (ngroups == 0) {                    // no ties: the step entries launch what they launch without this entry
+    p->ties = PbTies{};
+    return GP_OK;
+  }
+  if (!group_start || !members) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_set_ties: null group_start or members");
+  if (group_start[0] != 0) return gp_fail(h, GP_ERR_BAD_ARG, "gp_pdgpb_set_ties: group_start must begin at 0");
+  for (int32_t j = 0; j < ngroups; j++)
+    if (group_start[j + 1] <= group_start[j])
+      return gp_fail(h, GP_ERR_BAD_ARG, ("gp_pdgpb_set_ties: group_start does not ascend at group " + std::to_string(j) +
+                                         " (every group lists one member or more)").c_str());
+  const int64_t nmem = group_start[ngroups];
+  // every member: a slot of the parameter vector, outside every q_mu / q_sqrt block, named once
+  std::vector<int64_t> seen(members, members + nmem);
+  for (int32_t j = 0; j < ngroups; j++)
+    for (int32_t i = group_start[j]; i < group_start[j + 1]; i++) {
+      const int64_t o = members[i];
+      if (o < 0 || o >= p->nparams)
+        return gp_fail(h, GP_ERR_BAD_ARG, ("gp_pdgpb_set_ties: group " + std::to_string(j) + ": offset " + std::to_string(o) +
+                                           " is outside the parameter vector (" + std::to_string(p->nparams) + " slots)").c_str());
+      // the latent GP whose [theta | z | q_mu | q_sqrt] block holds the slot: the last one that starts at or before it
+      auto it = std::upper_bound(p->gps.begin(), p->gps.end(), o, [](int64_t v, const PbGp& g) { return v < g.off_theta; });
+      if (it != p->gps.begin() && o >= (it - 1)->off_qmu && o < (it - 1)->off_qsq + (int64_t)(it - 1)->M * (it - 1)->M)
+        return gp_fail(h, GP_ERR_BAD_ARG, ("gp_pdgpb_set_ties: group " + std::to_string(j) + ": offset " + std::to_string(o) +
+                                           " lies in the q_mu / q_sqrt block of latent GP " + std::to_string((it - 1) - p->gps.begin()) +
+                                           " (q(u) is never tied)").c_str());
+    }
+  std::sort(seen.begin(), seen.end());
+  for (int64_t i = 1; i < nmem; i++)
+    if (seen[i] == seen[i - 1])
+      return gp_fail(h, GP_ERR_BAD_ARG, ("gp_pdgpb_set_ties: offset " + std::to_string(seen[i]) + " is named twice").c_str());
+  if (!workspace || bytes < gp_pdgpb_ties_workspace_bytes(ngroups, nmem, p->nm) || (((uintptr_t)workspace) & 255))
+    return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_ties: workspace too small (gp_pdgpb_ties_workspace_bytes) or not 256-byte aligned");
+  GpArena ar(workspace, bytes);
+  const PbTieRegions r = pb_tie_regions(ar, (size_t)ngroups, (size_t)nmem, (size_t)p->nm);
+  if (!ar.ok) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_set_ties: arena overflow");
+  // the tied sets: connected components of the models under "a group has members in both" (union by the lower index)
+  std::vector<int32_t> root(p->nm);
+  for (int k = 0; k < p->nm; k++) root[k] = k;
+  auto find = [&](int32_t k) { while (root[k] != k) k = root[k] = root[root[k]]; return k; };
+  for (int32_t j = 0; j < ngroups; j++) {
+    int32_t a = find(p->owner[members[group_start[j]]]);
+    for (int32_t i = group_start[j] + 1; i < group_start[j + 1]; i++) {
+      const int32_t b = find(p->owner[members[i]]);
+      root[std::max(a, b)] = std::min(a, b);
+      a = std::min(a, b);
+    }
+  }
+  std::vector<std::vector<int32_t>> comp(p->nm);
+  for (int k = 0; k < p->nm; k++) comp[find(k)].push_back(k);       // k ascends: every set's list ascends
+  std::vector<int32_t> set_start(1, 0), set_models;
+  for (int k = 0; k < p->nm; k++)
+    if (comp[k].size() >= 2) {
+      set_models.insert(set_models.end(), comp[k].begin(), comp[k].end());
+      set_start.push_back((int32_t)set_models.size());
+    }
+  GP_HIP_CHECK(h, hipMemcpyAsync(r.group_start, group_start, ((size_t)ngroups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(r.members, members, (size_t)nmem * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(r.set_start, set_start.data(), set_start.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  if (!set_models.empty())
+    GP_HIP_CHECK(h, hipMemcpyAsync(r.set_models, set_models.data(), set_models.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemsetAsync(r.frozen, 0, p->nm * sizeof(int32_t), h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));      // pageable host memory: the caller's arrays and the vectors above go away
+  p->ties = PbTies{r.group_start, r.members, r.set_start, r.set_models, r.frozen, ngroups, (int32_t)set_start.size() - 1};
+  return GP_OK;
+}
+
+gp_status gp_pdgpb_ties_frozen(gp_pdgpb_plan p, int32_t* host_words, int32_t clear) {
+  if (!p || !host_words) return GP_ERR_BAD_ARG;
+  gp_handle h = p->h;
+  if (!p->ties.frozen) return gp_fail(h, GP_ERR_WORKSPACE, "gp_pdgpb_ties_frozen: no ties set (gp_pdgpb_set_ties)");
+  GP_HIP_CHECK(h, hipMemcpyAsync(host_words, p->ties.frozen, p->nm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  if (clear) GP_HIP_CHECK(h, hipMemsetAsync(p->ties.frozen, 0, p->nm * sizeof(int32_t), h->stream));
+  return GP_OK;
+}
+
+// the tie launch of one iteration (none without ties); `refused`: the step's refusal words, null on the Adam-only path
+static gp_status pb_tie(gp_pdgpb_plan_s* p, const int32_t* refused) {
+  if (p->ties.ngroups == 0) return GP_OK;
+  gp_handle h = p->h;
+  const int n = p->ties.ngroups + p->ties.nsets;
+  hipLaunchKernelGGL(pdgpb_tie_kernel, dim3((n + PB_TIE_GROUPS - 1) / PB_TIE_GROUPS), dim3(PB_TIE_GROUPS), 0, h->stream, p->ties,
+                     p->d_grad, (const int32_t*)p->d_status, refused);
+  GP_HIP_CHECK(h, hipGetLastError());
+  return GP_OK;
+}
+
 gp_status gp_pdgpb_objective(gp_pdgpb_plan p, const double* params, const double* x, const double* y, const int32_t* idx,
                              double* elbo_dev, double* grad) {
   if (!p || !params || !x || !y || !idx || !elbo_dev || p->predict_only)
@@ -1352,9 +1514,10 @@ gp_status gp_pdgpb_adam(gp_pdgpb_plan p, double* free_state, double* params, con
   const int blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n + 255) / 256));
   for (int s = 0; s < steps; s++) {
     GP_CHECK(pb_eval(p, params, x, y, idx + (int64_t)s * p->sumB, p->d_elbo, p->d_grad));
+    GP_CHECK(pb_tie(p, nullptr));
     hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
-                       p->d_owner, p->d_status, (const int32_t*)nullptr, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps,
-                       h->logistic);
+                       p->d_owner, p->d_status, (const int32_t*)nullptr, (const int32_t*)p->ties.frozen,
+                       lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps, h->logistic);
     GP_HIP_CHECK(h, hipGetLastError());
   }
   return GP_OK;
@@ -1471,9 +1634,10 @@ static gp_status pb_natgrad_run(gp_pdgpb_plan p, const char* name, double* free_
                          (const int32_t*)p->d_status, (const int32_t*)r.refused);
       GP_HIP_CHECK(h, hipGetLastError());
     }
+    GP_CHECK(pb_tie(p, r.refused));
     hipLaunchKernelGGL(pdgpb_adam_kernel, dim3(blocks), dim3(256), 0, h->stream, free_state, params, p->d_grad, tcode, m, v,
-                       p->d_owner, p->d_status, (const int32_t*)r.refused, lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps,
-                       h->logistic);
+                       p->d_owner, p->d_status, (const int32_t*)r.refused, (const int32_t*)p->ties.frozen,
+                       lr_t + (int64_t)s * p->nm, n, beta1, beta2, eps, h->logistic);
     GP_HIP_CHECK(h, hipGetLastError());
   }
   return GP_OK;

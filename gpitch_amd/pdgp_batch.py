@@ -17,6 +17,13 @@ whose q_mu and q_sqrt are both free, Adam on the rest, two more launches per ite
 of its GPs not positive definite) is refused on its own: it is left as it was and its result carries the error, the
 others go on.
 
+    results = optimize_many(segments, method=..., maxiter=1000, tied=tie_groups(segments))
+
+trains the segments of one recording as ONE model of it: the Params of each group in `tied` are one parameter (one noise
+variance, one set of kernels; q(u) and by default the inducing inputs stay each segment's own), the objective is the sum of
+the segments' ELBOs, and one more launch per iteration hands every member the group's summed gradient (check_tied() is the
+host check, gp_pdgpb_set_ties the device entry).  Models joined by ties stop together when one of them fails.
+
     preds = predict_many(models, xnews)
 
 replaces  [m.predict_act_n_com(x) for m, x in zip(models, xnews)]  with one factorisation launch for every latent GP and
@@ -36,7 +43,7 @@ import numpy as np
 from . import _lib, flatvec
 from .flatvec import col, free_index, latent_gps  # noqa: F401  (free_index: part of this module's interface)
 from .methods import nlin_code
-from .param import draw_in_lockstep
+from .param import Logistic, Param, ParamList, Parameterized, draw_in_lockstep
 from .pdgp import Pdgp, jitter
 from .sgpr_ss import _KERN_NAMES, _sample_generator, merged_order
 from .train import AdamOptimizer, NatGradAdam, OptimizeResult
@@ -146,6 +153,190 @@ def _segments(models):
     return segs, ranges, base
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# tied parameters: Params of one model or of several that are ONE parameter (csrc/pdgp_batch.hip pdgpb_tie_kernel,
+# gp_pdgpb_set_ties)
+def _param_names(kern):
+    """id(Param) -> its name in the kernel ("lengthscales", "energy[1]"), through nested kernels; theta_params() names a
+    Param by its position ("theta[j]") when no attribute holds it"""
+    names = {}
+
+    def walk(obj, prefix):
+        for name in sorted(obj.__dict__):
+            v = obj.__dict__[name]
+            if isinstance(v, Param):
+                names.setdefault(id(v), prefix + name)
+            elif isinstance(v, (list, tuple, ParamList)):
+                for j, it in enumerate(v):
+                    if isinstance(it, Param):
+                        names.setdefault(id(it), "%s%s[%d]" % (prefix, name, j))
+                    elif isinstance(it, Parameterized):
+                        walk(it, "%s%s[%d]." % (prefix, name, j))
+            elif isinstance(v, Parameterized):
+                walk(v, prefix + name + ".")
+
+    walk(kern, "")
+    for j, p in enumerate(kern.theta_params()):
+        names.setdefault(id(p), "theta[%d]" % j)
+    return names
+
+
+def _tie_roles(models, segs):
+    """id(Param) -> (model, offset, role text, is it q(u)?) of every Param of the batch's parameter vector"""
+    roles = {}
+    for k, m in enumerate(models):
+        off = {id(p): o for o, p in segs[k]}
+        P = m.num_sources
+        v = m.likelihood.variance
+        roles[id(v)] = (k, off[id(v)], "model %d, noise, variance" % k, False)
+        for r, (kern, z, q_mu, q_sqrt) in enumerate(latent_gps(m)):
+            gp = "model %d, %s %d" % (k, "act" if r < P else "com", r if r < P else r - P)
+            names = _param_names(kern)
+            for p in kern.theta_params():
+                roles[id(p)] = (k, off[id(p)], "%s, %s" % (gp, names[id(p)]), False)
+            roles[id(z)] = (k, off[id(z)], "%s, %s" % (gp, "za" if r < P else "zc"), False)
+            roles[id(q_mu)] = (k, off[id(q_mu)], "%s, q_mu" % gp, True)
+            roles[id(q_sqrt)] = (k, off[id(q_sqrt)], "%s, q_sqrt" % gp, True)
+    return roles
+
+
+def tie_groups(models, noise=True, kernels=True, inducing=False):
+    """The `tied=` groups that make structurally identical models — the segments of one recording — one model of it: one
+    group per noise variance (noise), one per position of every latent GP's kernel.theta_params() (kernels) and, with
+    inducing=True, one per za[i] / zc[i] (which needs equal M; q(u) stays each model's own).  Identical: the same P and,
+    latent GP by latent GP in the order [g_0..g_{P-1}, f_0..f_{P-1}], the same kernel type and partial count; ValueError
+    names the first model that differs from model 0.  Host only; reads no value and changes none (whether the members' values,
+    transforms and flags agree is check_tied's matter)."""
+    models = list(models)
+    if not models:
+        raise ValueError("tie_groups needs at least one model")
+    shape = lambda m: [(type(g[0]).__name__, int(g[0].num_partials)) for g in latent_gps(m)]
+    first = shape(models[0])
+    for k, m in enumerate(models[1:], 1):
+        if m.num_sources != models[0].num_sources:
+            raise ValueError("tie_groups: model %d has %d sources, model 0 has %d" % (k, m.num_sources, models[0].num_sources))
+        for r, (a, b) in enumerate(zip(shape(m), first)):
+            if a != b:
+                raise ValueError("tie_groups: model %d: latent GP %d of [g_0..g_{P-1}, f_0..f_{P-1}] has kernel %s with %d "
+                                 "partials, model 0 has %s with %d" % (k, r, a[0], a[1], b[0], b[1]))
+        if inducing:
+            for r, (g, g0) in enumerate(zip(latent_gps(m), latent_gps(models[0]))):
+                if g[1].size != g0[1].size:
+                    raise ValueError("tie_groups: inducing=True: model %d: latent GP %d has %d inducing points, model 0 has %d"
+                                     % (k, r, g[1].size, g0[1].size))
+    groups = []
+    if noise:
+        groups.append([m.likelihood.variance for m in models])
+    gps = [latent_gps(m) for m in models]
+    for r in range(len(first)):
+        if kernels:
+            groups += [list(ps) for ps in zip(*[g[r][0].theta_params() for g in gps])]
+        if inducing:
+            groups.append([g[r][1] for g in gps])
+    return groups
+
+
+def _tie_list(tied):
+    """`tied` as a list of lists (None: no group)"""
+    return [] if tied is None else [list(g) for g in tied]
+
+
+def check_tied(models, tied):
+    """Host-only scope check of `tied=` (optimize_many, PdgpBatch), in the style of check_batchable: run before any device
+    work, it builds no plan.  tied: an iterable of groups, each an iterable of one or more Params of the listed models —
+    likelihood.variance, a Param of a kernel's theta_params(), za[i] / zc[i] — that are ONE parameter.  ValueError names the
+    group's index and the offending Param's role (model, noise / act i / com i, Param name) for: a Param of none of the
+    models; a Param named twice, in one group or in two; a q_mu / q_sqrt Param (q(u) is each model's own); members whose
+    shapes, transforms (type, Logistic bounds), `.fixed` flags, current values (bit for bit) or stored Adam moments differ;
+    models joined by a group whose _adam_t differ (their bias-corrected step lengths would).
+    Returns the scalar groups the device takes: per group of free Params with two members or more and per element (array
+    Params tie element by element) the members' offsets into the batch's parameter vector (model_segments, models back to
+    back), in the listed order.  A group whose members are all `.fixed`, and a group of one member, pass the checks and
+    yield nothing."""
+    models = list(models)
+    tied = _tie_list(tied)
+    if not tied:
+        return []
+    segs, _, _ = _segments(models)
+    roles = _tie_roles(models, segs)
+    moments = {}
+
+    def moment(p):
+        k = roles[id(p)][0]
+        if k not in moments:
+            state = models[k]._adam_state()
+            moments[k] = {} if state is None else {id(q): mv for (_, q), mv in zip(segs[k], state)}
+        zero = np.zeros(p.size)
+        mv = moments[k].get(id(p), (zero, zero))
+        return np.asarray(mv[0], dtype=np.float64).reshape(-1), np.asarray(mv[1], dtype=np.float64).reshape(-1)
+
+    same_bits = lambda a, b: a.shape == b.shape and a.tobytes() == b.tobytes()
+    seen, out = {}, []
+    for gi, group in enumerate(tied):
+        if not group:
+            raise ValueError("check_tied: group %d is empty" % gi)
+        for j, p in enumerate(group):
+            if not isinstance(p, Param) or id(p) not in roles:
+                raise ValueError("check_tied: group %d: member %d (%r) is not a Param of the listed models (taken: "
+                                 "likelihood.variance, a kernel's theta_params(), za[i] / zc[i])" % (gi, j, p))
+            k, _, role, is_q = roles[id(p)]
+            if id(p) in seen:
+                raise ValueError("check_tied: group %d: %s appears twice (first in group %d)" % (gi, role, seen[id(p)]))
+            seen[id(p)] = gi
+            if is_q:
+                raise ValueError("check_tied: group %d: %s: q(u) is never tied (it is what differs per model, and the "
+                                 "natural-gradient step moves it per latent GP)" % (gi, role))
+        p0 = group[0]
+        k0, _, role0, _ = roles[id(p0)]
+        for p in group[1:]:
+            k, _, role, _ = roles[id(p)]
+            what = None
+            t, t0 = p.transform, p0.transform
+            if p.shape != p0.shape:
+                what = "has shape %r, %s has %r" % (p.shape, role0, p0.shape)
+            elif type(t) is not type(t0) or (isinstance(t, Logistic) and (t.a, t.b) != (t0.a, t0.b)):
+                describe = lambda u: "Logistic(%r, %r)" % (u.a, u.b) if isinstance(u, Logistic) else type(u).__name__
+                what = "has transform %s, %s has %s" % (describe(t), role0, describe(t0))
+            elif bool(p.fixed) != bool(p0.fixed):
+                what = "has fixed=%s, %s has fixed=%s" % (bool(p.fixed), role0, bool(p0.fixed))
+            elif not same_bits(p._array, p0._array):
+                what = "holds %s, %s holds %s (tied Params start from the same value, bit for bit)" % (
+                    np.array2string(p._array.reshape(-1), threshold=4), role0, np.array2string(p0._array.reshape(-1), threshold=4))
+            elif not p.fixed and not all(same_bits(a, b) for a, b in zip(moment(p), moment(p0))):
+                what = "and %s have different stored Adam moments" % role0
+            elif not p.fixed and models[k]._adam_t != models[k0]._adam_t:
+                what = "belongs to a model at Adam step %d, %s to one at step %d (their step lengths would differ)" % (
+                    models[k]._adam_t, role0, models[k0]._adam_t)
+            if what is not None:
+                raise ValueError("check_tied: group %d: %s %s" % (gi, role, what))
+        if len(group) >= 2 and not p0.fixed:
+            offs = [roles[id(p)][1] for p in group]
+            out += [[o + e for o in offs] for e in range(p0.size)]
+    return out
+
+
+def _tied_sets(models, segs, groups):
+    """the tied sets of scalar groups (check_tied's result): lists of model indices, ascending, that a chain of groups
+    joins — two models or more; what gp_pdgpb_set_ties derives on its side"""
+    starts = np.array([s[0][0] for s in segs])
+    root = list(range(len(models)))
+
+    def find(k):
+        while root[k] != k:
+            root[k] = root[root[k]]
+            k = root[k]
+        return k
+
+    for g in groups:
+        ks = [find(int(np.searchsorted(starts, o, side="right")) - 1) for o in g]
+        for k in ks:
+            root[find(k)] = find(min(ks))
+    sets = {}
+    for k in range(len(models)):
+        sets.setdefault(find(k), []).append(k)
+    return [s for s in sets.values() if len(s) >= 2]
+
+
 def _config(models, train):
     """gp_pdgpb_config of the models — a training plan's with the minibatch sizes B and the data counts N, a predict-only
     plan's without — and the ctypes arrays it points to, which the caller keeps alive as long as the config"""
@@ -206,8 +397,10 @@ class PdgpBatch(object):
     """The plan behind optimize_many: every model's parameters in one device vector, one gp_pdgpb plan sized by the
     batch's own shapes (no single-model engine plan is built)."""
 
-    def __init__(self, models, handle=None):
+    def __init__(self, models, handle=None, tied=None):
         self.models = check_batchable(models)
+        self._tied = _tie_list(tied)               # the groups as given: optimize() checks them again at every call
+        groups = check_tied(self.models, self._tied)
         h = self._handle = handle or _lib.default_handle()
         self._free_idx = []
         self._segs, self._range, self.num_params = _segments(self.models)
@@ -231,6 +424,8 @@ class PdgpBatch(object):
         self._ng_ws = None             # gp_pdgpb_natgrad's workspace, from the first NatGradAdam call on
         self._nga_ws = None            # gp_pdgpb_natgrad_adaptive's (per-role lengths / halving), likewise
         self._ng_last = None           # the one of the two the plan has seen last (its refusal words)
+        self._tie_groups, self._tie_sets, self._tie_ws = [], [], None
+        self._set_ties(groups)
 
     # ------------------------------------------------------------------------------------------
     def _pack(self):
@@ -293,6 +488,40 @@ class PdgpBatch(object):
         h.check(h.lib.gp_pdgpb_natgrad_refused(self._plan, out, int(bool(clear))))
         return np.array(out[:], dtype=np.int64)
 
+    def _set_ties(self, groups):
+        """hand the plan the scalar tie groups of check_tied (none: clear its ties) in a workspace of their own"""
+        if groups == self._tie_groups:
+            return
+        h = self._handle
+        if not groups:
+            h.check(h.lib.gp_pdgpb_set_ties(self._plan, 0, None, None, None, 0))
+            self._tie_groups, self._tie_sets, self._tie_ws = [], [], None
+            return
+        start = np.concatenate([[0], np.cumsum([len(g) for g in groups])])
+        gs = (C.c_int32 * start.size)(*[int(v) for v in start])
+        mem = (C.c_int64 * int(start[-1]))(*[int(o) for g in groups for o in g])
+        h.sync()                                   # nothing in flight still reads the workspace this one replaces
+        ws = h.workspace(h.lib.gp_pdgpb_ties_workspace_bytes(len(groups), int(start[-1]), len(self.models)))
+        h.check(h.lib.gp_pdgpb_set_ties(self._plan, len(groups), gs, mem, ws.data_ptr(), ws.numel()))
+        self._tie_groups, self._tie_sets, self._tie_ws = groups, _tied_sets(self.models, self._segs, groups), ws
+
+    def set_tied(self, tied):
+        """replace the plan's tie groups (None or []: no ties, optimize() then launches what it launches without them)"""
+        tied = _tie_list(tied)
+        groups = check_tied(self.models, tied)
+        self._tied = tied
+        self._set_ties(groups)
+
+    def ties_frozen(self, clear=True):
+        """per model: 0, or 1 + the index of the lowest failed model of its tied set at the iteration the set stopped; all
+        0 without ties"""
+        if not self._tie_groups:
+            return np.zeros(len(self.models), dtype=np.int64)
+        out = (C.c_int32 * len(self.models))()
+        h = self._handle
+        h.check(h.lib.gp_pdgpb_ties_frozen(self._plan, out, int(bool(clear))))
+        return np.array(out[:], dtype=np.int64)
+
     def objective_many(self):
         """every model's (-ELBO, -gradient over its free state) on a fresh minibatch of its own, as Pdgp._objective at
         the models' current Params (same draws, same free-state order)"""
@@ -312,8 +541,11 @@ class PdgpBatch(object):
     def optimize(self, method, maxiter=1000, chunk=64):
         """`maxiter` iterations of every model with an AdamOptimizer or a NatGradAdam token (see optimize_many)"""
         _, flags = _check_for(self.models, method)
+        groups = check_tied(self.models, self._tied)     # values, flags and moments may have changed since the last call
         natgrad = flags is not None
         h = self._handle
+        self._set_ties(groups)
+        self.ties_frozen(clear=True)
         self._pack()
         self._load_moments()
         self.not_pd(clear=True)
@@ -366,12 +598,18 @@ class PdgpBatch(object):
         bad = self.not_pd(clear=True)
         # a model whose Kuu failed is reported as that (its garbage gradient may have raised the refusal word as well)
         refused = self.refused(clear=True) if natgrad else np.zeros(nm, dtype=np.int64)
+        frozen = self.ties_frozen(clear=True)
         counts = self._natgrad_counts(method) if adaptive else None      # one read, after the last iteration
         # GPflow evaluates the returned fun / jac on a fresh minibatch (Pdgp.optimize)
         draws = [draw_indices(m, 1) for m in self.models]
         elbo, grad = self._evaluate(draws)
         final_bad = self.not_pd(clear=True)     # a failure in the final evaluation voids that model's fun / jac
         bad = np.where(bad != 0, bad, final_bad)
+        for tset in self._tie_sets:             # a set whose only failure is the final evaluation's stops together as well
+            failed = [k for k in tset if bad[k] or refused[k]]
+            for k in tset:
+                if failed and not frozen[k]:
+                    frozen[k] = 1 + failed[0]
         h.sync()
         del keep
         free = self._free.cpu().numpy()
@@ -379,17 +617,22 @@ class PdgpBatch(object):
         mom_m, mom_v = self._adam_m.cpu().numpy(), self._adam_v.cpu().numpy()
         results = []
         for k, m in enumerate(self.models):
-            if bad[k] or refused[k]:
-                # frozen since its failed step: the model keeps its Params, Adam state and generators
+            if bad[k] or refused[k] or frozen[k]:
+                # frozen since its failed step (or that of a model it is tied to): the model keeps its Params, Adam state
+                # and generators
                 xs, ys = rng_keep[k]
                 if xs is not None:
                     m.x.rng.set_state(xs)
                 if ys is not None:
                     m.y.rng.set_state(ys)
-                if bad[k]:
-                    msg = "Cholesky failed: %s" % _describe_not_pd(bad[k])
+                j = k if bad[k] or refused[k] else int(frozen[k]) - 1      # the model whose failure stopped this one
+                if bad[j]:
+                    msg = "Cholesky failed: %s" % _describe_not_pd(bad[j])
                 else:
-                    msg = _describe_refused(k, refused[k], m.num_sources, method.gamma, method if adaptive else None)
+                    msg = _describe_refused(j, refused[j], self.models[j].num_sources, method.gamma,
+                                            method if adaptive else None)
+                if j != k:
+                    msg = "model %d: stopped together with model %d, to which it is tied: %s" % (k, j, msg)
                 results.append(OptimizeResult(fun=None, jac=None, x=None, success=False, status="error", message=msg,
                                               error=_lib.NotPositiveDefiniteError(_lib.GP_ERR_NOT_PD, msg)))
                 if adaptive:                         # what it had accumulated up to the refusing iteration
@@ -432,7 +675,7 @@ class PdgpBatch(object):
             pass
 
 
-def optimize_many(models, method=None, maxiter=1000, callback=None):
+def optimize_many(models, method=None, maxiter=1000, callback=None, tied=None):
     """Train every model in `models` (ordinary Pdgp objects) as  m.optimize(method=method, maxiter=maxiter)  would, all
     of them together: one OptimizeResult per model.  A model whose Cholesky fails is frozen and its result carries
     `error`; the others go on.  method: an AdamOptimizer or a NatGradAdam token shared by all models (default
@@ -445,10 +688,18 @@ def optimize_many(models, method=None, maxiter=1000, callback=None):
     ends as a model with a failed Cholesky does (Params, Adam state, _adam_t and generators as before the call,
     success=False, error a NotPositiveDefiniteError naming NatGradAdam, the model, the GP, the pivot and gamma).  The
     Moments that an earlier AdamOptimizer run left on q_mu / q_sqrt are not cleared: Adam then keeps coasting on them
-    beside the step, as in Pdgp.optimize.  Start NatGradAdam on fresh models, or accept that."""
+    beside the step, as in Pdgp.optimize.  Start NatGradAdam on fresh models, or accept that.
+
+    tied: groups of Params that are ONE parameter (check_tied; tie_groups builds them for the segments of one recording:
+    one noise variance, one set of kernels, q(u) and by default the inducing inputs per segment).  The objective is then
+    the sum of the models' ELBOs: per iteration the shared parameter's gradient is the sum over the group's members, one
+    Adam update is applied, and every member ends on the same value and the same Adam moments, bit for bit (DESIGN.md
+    3l).  One result per model as without ties, `fun` / `jac` / `x` its own.  Models that ties join, directly or through
+    a chain, stop together: when one of them fails, all of them are frozen at that iteration and end as a failed model
+    does; the others' messages name the model they are tied to and repeat its cause.  Without `tied` nothing changes."""
     method = AdamOptimizer() if method is None else method
     models, _ = _check_for(models, method, callback)
-    return PdgpBatch(models).optimize(method, maxiter)
+    return PdgpBatch(models, tied=tied).optimize(method, maxiter)
 
 
 # ------------------------------------------------------------------------------------------------------------------

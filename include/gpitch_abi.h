@@ -809,6 +809,33 @@ gp_status gp_pdgpb_natgrad_adaptive(gp_pdgpb_plan p, double* free_state, double*
                                     const double* lr_t, double beta1, double beta2, double eps, const double* gamma_gp_host,
                                     int32_t halvings, const int32_t* step_gp_host, void* workspace, size_t workspace_bytes);
 gp_status gp_pdgpb_natgrad_counts(gp_pdgpb_plan p, int64_t* halvings_host, double* shortest_host, int32_t clear);
+/* Tied parameters: slots of the parameter vector that are ONE parameter, in one model or across models (the
+ * segments of one recording share their noise variance and kernels).  The objective is the sum of the models' ELBOs, so the
+ * shared parameter's gradient is the sum over its slots.  With ties set, gp_pdgpb_adam, gp_pdgpb_natgrad and
+ * gp_pdgpb_natgrad_adaptive launch pdgpb_tie_kernel once per iteration behind the backward pass and the natural-gradient
+ * kernels: per group it sums `grad` over the members in the listed order (no atomics: bit-identical between calls) and writes
+ * the sum into every member's slot; the caller gives all members the same free state, moments, transform code and step length,
+ * so the unchanged Adam update moves them alike, bit for bit.  gp_pdgpb_objective is not changed: elbo and grad stay per model.
+ * gp_pdgpb_set_ties (HOST arrays): group j is members[group_start[j] .. group_start[j + 1]), group_start[0] = 0, every group
+ * with one member or more.  Checked before anything is uploaded: group_start ascends; every offset lies in [0,
+ * gp_pdgpb_num_params), outside every q_mu / q_sqrt block (q(u) is never tied), and is named once (GP_ERR_BAD_ARG); the
+ * workspace holds gp_pdgpb_ties_workspace_bytes(ngroups, group_start[ngroups], num_models) bytes and is 256-byte aligned
+ * (GP_ERR_WORKSPACE).  A refused call leaves the plan and its earlier ties as they were.  The entry derives the tied sets — the
+ * connected components of the models under "a group has slots in both", those of two models or more — uploads groups and sets,
+ * zeroes the frozen words and synchronises the stream; the workspace stays the caller's and in use until the ties are replaced
+ * or cleared.  ngroups = 0 clears the ties (the other arguments are ignored): the step entries then launch exactly what they
+ * launch without this entry.  gp_pdgpb_workspace_bytes does not change.
+ * A tied set stops together: when the Kuu status or the refusal word of one of its models is raised, the tie launch of that
+ * iteration writes 1 + the lowest failed model's index into the sticky frozen word of every model of the set that has none
+ * yet, and the Adam launch behind it skips those models from then on.  The words of gp_pdgpb_not_pd and
+ * gp_pdgpb_natgrad_refused keep reporting real failures only.  gp_pdgpb_ties_frozen copies the frozen words to the host (one
+ * per model; synchronises the stream), clear != 0 resets them afterwards; without ties: GP_ERR_WORKSPACE.
+ * gp_pdgpb_ties_workspace_bytes needs no plan: the measured carve [group_start | members | set_start | set_models | frozen]
+ * plus the batch margin; 0 when an argument is not positive. */
+size_t gp_pdgpb_ties_workspace_bytes(int32_t ngroups, int64_t nmembers, int32_t nmodels);
+gp_status gp_pdgpb_set_ties(gp_pdgpb_plan p, int32_t ngroups, const int32_t* group_start, const int64_t* members,
+                            void* workspace, size_t bytes);
+gp_status gp_pdgpb_ties_frozen(gp_pdgpb_plan p, int32_t* host_words, int32_t clear);
 /* ---- prediction of many models: Pdgp.predict_act_n_com (pdgp.py:190-208) of every model at its own inputs --------------
  * A prediction-only plan is created by gp_pdgpb_create with cfg->batch == NULL (num_data is then ignored).  It has the
  * parameter layout of a training plan (gp_pdgpb_layout) and no training workspace: gp_pdgpb_workspace_bytes returns 0,

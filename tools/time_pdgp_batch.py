@@ -18,6 +18,11 @@ in the same process: medians of --repeats windows each, the three alternating, w
 times optimize_many with the plain token NatGradAdam(GAMMA, 0.0025) against the token with gamma_com = G and / or
 halvings = H (gp_pdgpb_natgrad_adaptive) on twin batches, the two alternating: the cost of the loop around the
 form kernel when nothing is halved.  The halving counts of the last window are printed with it.
+
+    python tools/time_pdgp_batch.py --tied [--natgrad GAMMA] [--models 12 88] [--steps 200] [--repeats 5]
+
+times optimize_many with the noise variance and the kernels of all models tied (tie_groups; DESIGN.md 3l: one more launch
+per iteration) against the untied twin batch, the two alternating.
 """
 import argparse
 import json
@@ -132,6 +137,44 @@ def adaptive_main(a):
                           "adaptive_over_plain": med["adaptive"] / med["plain"]}), flush=True)
 
 
+def tied_main(a):
+    """the batch with noise and kernels of all models tied (tie_groups) against its untied twin, alternating windows"""
+    import copy
+    import torch
+    import gpitch_amd
+    from gpitch_amd.pdgp_batch import PdgpBatch, tie_groups
+    tok = gpitch_amd.train.AdamOptimizer(0.0025) if a.natgrad is None else gpitch_amd.train.NatGradAdam(a.natgrad, 0.0025)
+    base = demo_model()
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for W in a.models:
+        mt = [copy.deepcopy(base) for _ in range(W)]
+        bt = PdgpBatch(mt, tied=tie_groups(mt))
+        bu = PdgpBatch([copy.deepcopy(base) for _ in range(W)])
+        bt.optimize(tok, a.warmup)
+        bu.optimize(tok, a.warmup)
+        t = {"tied": [], "untied": []}
+        ok = True
+        for _ in range(a.repeats):
+            rt, ru = [], []
+            t["untied"].append(1e3 * window(lambda: ru.extend(bu.optimize(tok, a.steps))) / a.steps)
+            t["tied"].append(1e3 * window(lambda: rt.extend(bt.optimize(tok, a.steps))) / a.steps)
+            ok = ok and all(r.success for r in rt + ru)
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"models": W, "method": "adam" if a.natgrad is None else "natgrad %g" % a.natgrad, "steps": a.steps,
+                          "repeats": a.repeats, "every_model_succeeded": ok, "tie_groups": len(bt._tie_groups),
+                          "members_per_group": W,
+                          "untied_ms_per_step": med["untied"], "untied_range": [min(t["untied"]), max(t["untied"])],
+                          "tied_ms_per_step": med["tied"], "tied_range": [min(t["tied"]), max(t["tied"])],
+                          "tied_minus_untied_ms": med["tied"] - med["untied"],
+                          "tied_over_untied": med["tied"] / med["untied"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", type=int, nargs="+", default=[1, 12, 88])
@@ -143,7 +186,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="windows per figure with --natgrad (the median is reported)")
     ap.add_argument("--gamma-com", type=float, default=None, help="with --natgrad: the component GPs' own step length")
     ap.add_argument("--halvings", type=int, default=0, help="with --natgrad: the halving budget (0..10)")
+    ap.add_argument("--tied", action="store_true",
+                    help="time the batch with noise and kernels of all models tied (tie_groups) against its untied twin")
     a = ap.parse_args()
+    if a.tied:
+        return tied_main(a)
     if a.natgrad is not None and (a.gamma_com is not None or a.halvings):
         return adaptive_main(a)
     if a.natgrad is not None:
