@@ -25,7 +25,7 @@ TIMER_NAMES = ["kuf_build", "cond_A", "cond_LTA", "nt_gemm", "kuf_bar", "chol", 
 
 # every symbol include/gpitch_abi.h declares
 ABI_SYMBOLS = [
-    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_last_not_pd_index",
+    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_debug_gemm", "gp_last_not_pd_index",
     "gp_kernel_build", "gp_kernel_build_f32", "gp_kernel_diag", "gp_chol_workspace_bytes", "gp_kuu_cholesky", "gp_cholesky_inplace",
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
     "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
@@ -99,6 +99,22 @@ class PdgpBatchConfig(C.Structure):
                 ("kern_type", C.POINTER(C.c_int32)), ("partials", C.POINTER(C.c_int32)), ("jitter", C.c_double)]
 
 
+class DebugGemmProblem(C.Structure):
+    """gp_debug_gemm_problem: one problem of a gp_debug_gemm launch (device pointers)"""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("v0", C.c_void_p), ("v1", C.c_void_p),
+                ("v2", C.c_void_p), ("o0", C.c_void_p), ("o1", C.c_void_p), ("o2", C.c_void_p), ("xa", C.c_void_p),
+                ("xb", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("pad_", C.c_int32),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64)]
+
+
+class DebugGemmFlags(C.Structure):
+    """gp_debug_gemm_flags: the fields of the library's GEMM flags a caller can set"""
+    _fields_ = [("transA", C.c_int32), ("transB", C.c_int32), ("triA", C.c_int32), ("triB", C.c_int32), ("triC", C.c_int32),
+                ("big_tiles", C.c_int32), ("epilogue", C.c_int32), ("scale_mode", C.c_int32), ("role", C.c_int32),
+                ("tile_m0", C.c_int32), ("tile_mcount", C.c_int32), ("uniform_aligned", C.c_int32), ("a32_ok", C.c_int32),
+                ("rows64_ok", C.c_int32), ("alpha", C.c_double), ("beta", C.c_double)]
+
+
 _lib = None
 
 
@@ -138,6 +154,8 @@ def load_library():
         "gp_last_error": (C.c_char_p, [vp]),
         "gp_abi_version": (i32, []),
         "gp_debug_wave_takes": (i32, [i32, i32, i32, i32]),
+        "gp_debug_gemm": (i32, [vp, C.POINTER(DebugGemmProblem), i32, i32, i32, C.POINTER(DebugGemmFlags), i32, i32, i32, vp, sz,
+                                C.POINTER(i32)]),
         "gp_last_not_pd_index": (i32, [vp]),
         "gp_kernel_build": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),
         "gp_kernel_build_f32": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),

@@ -528,6 +528,10 @@ bool launch_gemm_wave(gp_handle h, const GemmProblem* d_probs, int batch, int ma
     return true;
   }
   if (f.role == 1) *st = gw_launch<1>(h, d_probs, batch, maxM, maxN, f);
+  // role 2 holds its tile with the rows permuted inside each 64-row tile (gw_tile: op(A) row-contiguous): only what does not
+  // depend on the row order comes out right — the column sums of squares, all the engine asks of Lq^T A.  A caller that has
+  // sized its partial rows for this form cannot fall back, so anything else is an error, not "not taken".
+  else if (f.role == 2 && f.epilogue != EPI_COLSUMSQ) *st = gp_fail(h, GP_ERR_UNSUPPORTED, "Lq^T A in the wave form: column sums of squares only (EPI_COLSUMSQ)");
   else if (f.role == 2) *st = gw_launch<2>(h, d_probs, batch, maxM, maxN, f);
   else *st = gw_launch<3>(h, d_probs, batch, maxM, maxN, f);
   return true;

@@ -88,6 +88,34 @@ int32_t gp_abi_version(void);
  * 3: Kuf_bar, 5: Kuf_bar with the stationary contraction) over an M x N strip take the wave form (f32 != 0: float32
  * strips)?  Strips of 2^31 bytes or more never do. */
 int32_t gp_debug_wave_takes(int32_t role, int32_t M, int32_t N, int32_t f32);
+/* For tests; synchronises nothing.  ONE launch of a GEMM host entry on the caller's device buffers, no arithmetic of its
+ * own.  `probs` is a HOST array of `batch` records (copied into the library's descriptors with every other field zero and
+ * uploaded into `workspace`, a 16-byte aligned DEVICE buffer of at least 160 bytes per problem, on the handle's stream).
+ *   kind  0 float64 product C = alpha op(A) op(B) + beta C with the column-sum epilogues, 1 float64 split-K H = X [D] Y^T
+ *         with slab reduction (triC lower = symmetric, scale_mode 2 = D given in v1), 2 / 3 the same two on float32 strips
+ *   form  0 as the library dispatches, 1 the wave form only, 2 the lean strip form only, 3 the generic kernel (the launch is
+ *         passed with uniform_aligned = rows64_ok = 0); a form that does not take the launch: GP_ERR_UNSUPPORTED, nothing runs
+ *   nsplit  kinds 1 / 3: K-slices (0 = the library's own choice)
+ * Roles 5, 6 and 7 are refused (GP_ERR_UNSUPPORTED).  *partial_rows: rows of the partial-sum arrays o0 / o1 as the engine
+ * sizes them, by role and shape (kinds 0 / 2: one per 64-row tile where the wave form takes that role and shape, else one per
+ * row block; kinds 1 / 3: K-slices).  An upper bound: a dispatched launch that the wave form declines for its flags (alpha,
+ * beta, triC) writes the fewer rows of the form that runs instead. */
+typedef struct {
+  const void* A; const void* B; void* C;
+  const double* v0; const double* v1; const double* v2;
+  double* o0; double* o1; double* o2;
+  const void* xa; const void* xb;
+  int32_t M, N, K, pad_;
+  int64_t lda, ldb, ldc;
+} gp_debug_gemm_problem;
+typedef struct {
+  int32_t transA, transB, triA, triB, triC;   /* tri*: 0 none, 1 lower, 2 upper */
+  int32_t big_tiles, epilogue, scale_mode, role, tile_m0, tile_mcount, uniform_aligned, a32_ok, rows64_ok;
+  double alpha, beta;
+} gp_debug_gemm_flags;
+gp_status gp_debug_gemm(gp_handle h, const gp_debug_gemm_problem* probs, int32_t batch, int32_t maxM, int32_t maxN,
+                        const gp_debug_gemm_flags* flags, int32_t kind, int32_t form, int32_t nsplit, void* workspace,
+                        size_t workspace_bytes, int32_t* partial_rows);
 /* pivot index reported by the last GP_ERR_NOT_PD (−1 if none) */
 int32_t gp_last_not_pd_index(gp_handle h);
 
