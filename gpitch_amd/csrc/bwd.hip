@@ -132,6 +132,72 @@ gp_status launch_matvec_batched(gp_handle h, const GemmProblem* d, int batch, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// The kernel-gradient chain (engine.h: ChainSlot) of pdgp_bwd.hip, sgpr.hip and sgpr_batch.hip: the one place that says
+// which operands its products read and which triangles they mask or trust (the operator contracts: DESIGN.md 3m).
+void gemm_problem_square(GemmProblem& r, int M) {
+  memset(&r, 0, sizeof(r));
+  r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+}
+
+void chain_fill(const ChainSlots& host, int idx, int M, const ChainBufs& b) {
+  auto P = [&](int q) -> GemmProblem& { GemmProblem& r = host.p[q][idx]; gemm_problem_square(r, M); return r; };
+  { GemmProblem& r = P(CH_EH); r.A = b.E; r.B = b.H; r.C = b.T1; }
+  { GemmProblem& r = P(CH_WBAR); r.A = b.T1; r.B = b.L; r.C = b.Wbar; }
+  { GemmProblem& r = P(CH_LU); r.A = b.L; r.v0 = b.u; r.o0 = b.Lu; }
+  { GemmProblem& r = P(CH_RANK1); r.C = b.Wbar; r.v0 = b.v; r.v1 = b.Lu; }
+  { GemmProblem& r = P(CH_R); r.A = b.W; r.B = b.E; r.C = b.R; }
+  { GemmProblem& r = P(CH_ALPHA); r.A = b.W; r.v0 = b.v; r.o0 = b.alpha; }
+  { GemmProblem& r = P(CH_T2); r.A = b.W; r.B = b.Wbar; r.C = b.T2; }
+  { GemmProblem& r = P(CH_LBAR); r.A = b.T2; r.B = b.W; r.C = b.T1; }
+  { GemmProblem& r = P(CH_P); r.A = b.L; r.B = b.T1; r.C = b.T2; }
+  { GemmProblem& r = P(CH_T3); r.A = b.W; r.B = b.T2; r.C = b.H; }      // H is free once E H is taken
+  { GemmProblem& r = P(CH_S); r.A = b.H; r.B = b.W; r.C = b.E; }        // Kuu_bar, over E
+}
+
+// E = Lq Lq^T - I
+gp_status launch_chain_e(gp_handle h, const GemmProblem* e, int count, int maxM) {
+  GemmFlags f; f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
+  GP_CHECK(launch_gemm_batched(h, e, count, maxM, maxM, f));
+  return launch_sub_identity_batched(h, e, count, maxM);
+}
+
+// R = W^T E;  alpha = W^T v
+gp_status launch_chain_r_alpha(gp_handle h, const GemmProblem* r, const GemmProblem* alpha, int count, int maxM) {
+  GemmFlags f; f.transA = 1; f.triA = TRI_UPPER;
+  GP_CHECK(launch_gemm_batched(h, r, count, maxM, maxM, f));
+  return launch_matvec_batched(h, alpha, count, maxM, 1);
+}
+
+// T1 = E H;  Wbar = tril(T1 L^T);  Lu = L u;  Wbar += tril(v (L u)^T)
+gp_status launch_chain_wbar(gp_handle h, const ChainSlots& dev, int count, int maxM) {
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_EH], count, maxM, maxM, GemmFlags()));
+  GemmFlags f; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_WBAR], count, maxM, maxM, f));
+  GP_CHECK(launch_matvec_batched(h, dev.p[CH_LU], count, maxM, 0));
+  return launch_rank1_tril_batched(h, dev.p[CH_RANK1], count, maxM);
+}
+
+// The Cholesky adjoint: T2 = W^T Wbar;  Lbar = -tril(T2 W^T);  P = Phi(L^T Lbar);  T3 = W^T P;  Kuu_bar = T3 W
+gp_status launch_chain_adjoint(gp_handle h, const ChainSlots& dev, int count, int maxM) {
+  GemmFlags wt; wt.transA = 1; wt.triA = TRI_UPPER; wt.triB = TRI_LOWER;      // op(A) = W^T or L^T, B a lower triangle
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_T2], count, maxM, maxM, wt));
+  GemmFlags f; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_LBAR], count, maxM, maxM, f));
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_P], count, maxM, maxM, wt));
+  GP_CHECK(launch_phi_batched(h, dev.p[CH_P], count, maxM));
+  GP_CHECK(launch_gemm_batched(h, dev.p[CH_T3], count, maxM, maxM, wt));
+  f = GemmFlags(); f.triB = TRI_LOWER;
+  return launch_gemm_batched(h, dev.p[CH_S], count, maxM, maxM, f);
+}
+
+// The SGPRSS B side: Binv = WB^T WB;  ubar = WB^T c
+gp_status launch_chain_b_head(gp_handle h, const GemmProblem* binv, const GemmProblem* ubar, int count, int maxM) {
+  GemmFlags f; f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
+  GP_CHECK(launch_gemm_batched(h, binv, count, maxM, maxM, f));
+  return launch_matvec_batched(h, ubar, count, maxM, 1);
+}
+
+// ---------------------------------------------------------------------------------------------
 // hyper-parameter contraction:  sums[s] = sum_{i,j} Gw[i][j] * dK[i][j]/dtheta_s
 //   Gw[i][j] = G[i*ldg + j] (+ alpha[i]*gm[j])            (Kuf side, symmetric = 0)
 //   Gw[i][j] = (G[i][j] + G[j][i]) / 2                     (Kuu side, symmetric = 1, x2 == x1)

@@ -28,6 +28,32 @@ gp_status launch_phi_batched(gp_handle h, const GemmProblem* d_probs, int batch,
 gp_status launch_rank1_tril_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_matvec_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int trans);
 gp_status launch_batched_sum(gp_handle h, const double* v, int64_t stride, int n, int rows, double* out);   // out[r] = sum_n v[r * stride + n]
+// The kernel-gradient chain under the Pdgp, SGPRSS and window backward passes (bwd.hip; formulas there).  Every plan stores
+// its problems slot-major and keeps these twelve slots in this order; G (the Kuf_bar product) is filled and launched by the plan.
+enum ChainSlot { CH_EH = 0, CH_WBAR, CH_LU, CH_RANK1, CH_R, CH_ALPHA, CH_G, CH_T2, CH_LBAR, CH_P, CH_T3, CH_S, CH_COUNT };
+struct ChainSlots { GemmProblem* p[CH_COUNT]; };     // first record of every slot: host records to fill, device ones to launch
+// slot q at base + off[q] bytes (a plan's region offsets from its first chain slot on), records from `first` on
+static inline ChainSlots chain_slots(char* base, const size_t* off, int first = 0) {
+  ChainSlots s;
+  for (int q = 0; q < CH_COUNT; q++) s.p[q] = (GemmProblem*)(base + off[q]) + first;
+  return s;
+}
+static inline ChainSlots chain_slots_run(GemmProblem* first) {      // the twelve slots as one run of records, one each
+  ChainSlots s;
+  for (int q = 0; q < CH_COUNT; q++) s.p[q] = first + q;
+  return s;
+}
+// one matrix's buffers: M x M each but the vectors u, v, Lu, alpha; v is what the rank-1 term and alpha read (q_mu / ubar).
+// The adjoint ends in H (T3) and E (Kuu_bar), which it is free to overwrite by then.
+struct ChainBufs { const double *L, *W; double *E, *H; const double *u, *v; double *T1, *T2, *Wbar, *R, *Lu, *alpha; };
+void gemm_problem_square(GemmProblem& r, int M);     // zeroed, M = N = K = lda = ldb = ldc = M
+void chain_fill(const ChainSlots& host, int idx, int M, const ChainBufs& b);     // every slot's record idx but CH_G's
+// each enqueues on h->stream over `count` records
+gp_status launch_chain_e(gp_handle h, const GemmProblem* e, int count, int maxM);
+gp_status launch_chain_r_alpha(gp_handle h, const GemmProblem* r, const GemmProblem* alpha, int count, int maxM);
+gp_status launch_chain_wbar(gp_handle h, const ChainSlots& dev, int count, int maxM);
+gp_status launch_chain_adjoint(gp_handle h, const ChainSlots& dev, int count, int maxM);
+gp_status launch_chain_b_head(gp_handle h, const GemmProblem* binv, const GemmProblem* ubar, int count, int maxM);
 gp_status launch_addvec_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_tril_add_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM);
 gp_status launch_hyper_contract(gp_handle h, DevKern k, const double* x1, int n1, const double* x2, int n2,

@@ -1,6 +1,7 @@
 // pdgp_bwd.hip — host orchestration of the Pdgp ELBO's reverse pass: descriptor slots, the Q route's host code and guard
 // kernel, the bind-time descriptor upload and the backward schedule.  The algebra, the element-wise helpers and the
-// contraction kernels it launches are in bwd.hip.
+// contraction kernels it launches are in bwd.hip, and so is the kernel-gradient chain (Wbar, R and alpha, the Cholesky
+// adjoint: engine.h ChainSlot), which this plan shares with sgpr.hip and sgpr_batch.hip.
 #include "pdgp_plan.h"
 #include <string.h>
 #include <stdlib.h>
@@ -8,9 +9,10 @@
 // ---------------------------------------------------------------------------------------------
 // orchestration
 // slots below S_E are batched over all latent GPs, slots from S_E on over the GPs whose kernel gradients are needed.
-// S_QW_* / S_GQ_* / S_WB_*: unwhitened model only (see pdgp_backward).
+// S_CHAIN: the first of the shared chain's CH_COUNT slots (engine.h ChainSlot), S_CHAIN + CH_x each; this file names the three
+// it launches itself.  S_QW_* / S_GQ_* / S_WB_*: unwhitened model only (see pdgp_backward).
 enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
-               S_E, S_EH, S_WBAR, S_LU, S_RANK1, S_R, S_ALPHA, S_G, S_T2, S_LBAR, S_P, S_T3, S_S, S_WB_R1, S_WB_L,
+               S_E, S_CHAIN, S_R = S_CHAIN + CH_R, S_ALPHA = S_CHAIN + CH_ALPHA, S_G = S_CHAIN + CH_G, S_WB_R1 = S_CHAIN + CH_COUNT, S_WB_L,
                // Q route, entry i = latent GP q0 + i: E, R, beta and Q = R W of the forward pass (filled whether or
                // not a gradient is asked), then T = W Qbar, H = T W^T and u = W v of the backward pass
                S_QE, S_QR, S_QALPHA, S_QQ, S_QT, S_QHH, S_QU,
@@ -19,6 +21,12 @@ enum BwdSlot { S_H = 0, S_U, S_HLQ, S_QW_MU, S_QW_L, S_GQ_MU, S_GQ_L,
                S_COUNT };
 static_assert(S_COUNT <= PDGP_KLTR_SLOT, "pdgp_plan.h: the backward slots must stay below the KL trace slot");
 static inline const GemmProblem* slot_probs(gp_pdgp_plan p, int slot) { return (const GemmProblem*)(p->d_misc + p->off.bwd[slot]); }
+// record i of a slot's host copy, zeroed and square
+static inline GemmProblem& host_prob(gp_pdgp_plan p, int slot, int i, int M) {
+  GemmProblem& r = *((GemmProblem*)(p->h_misc.data() + p->off.bwd[slot]) + i);
+  gemm_problem_square(r, M);
+  return r;
+}
 
 // ---- Q route --------------------------------------------------------------------------------------------------------
 // With E = Lq Lq^T - I, Q = W^T E W and beta = W^T q_mu the whitened conditional is
@@ -78,12 +86,7 @@ void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
     const CondTask& t = p->cb.tasks[g];
     const BwdBufs& b = p->bw[g];
     const int M = q.M;
-    auto P = [&](int slot) -> GemmProblem& {
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + i * sizeof(GemmProblem));
-      memset(&r, 0, sizeof(r));
-      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-      return r;
-    };
+    auto P = [&](int slot) -> GemmProblem& { return host_prob(p, slot, i, M); };
     const double* q_sqrt = params + q.off_qsqrt;
     { GemmProblem& r = P(S_QE); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
     { GemmProblem& r = P(S_QR); r.A = t.W; r.B = b.E; r.C = b.R; }
@@ -125,14 +128,9 @@ __global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __r
 static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wait) {
   gp_handle h = p->h;
   const int nq = p->nq, maxM = p->maxM;
-  GemmFlags f;
-  f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QE), nq, maxM, maxM, f));
-  GP_CHECK(launch_sub_identity_batched(h, slot_probs(p, S_QE), nq, maxM));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QR), nq, maxM, maxM, f));
-  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QALPHA), nq, maxM, 1));
-  f = GemmFlags(); f.triB = TRI_LOWER;
+  GP_CHECK(launch_chain_e(h, slot_probs(p, S_QE), nq, maxM));
+  GP_CHECK(launch_chain_r_alpha(h, slot_probs(p, S_QR), slot_probs(p, S_QALPHA), nq, maxM));
+  GemmFlags f; f.triB = TRI_LOWER;        // Q = R W
   GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QQ), nq, maxM, maxM, f));
   if (p->q_far) {
     if (far_wait && hipStreamWaitEvent(h->stream, h->ev_feat, 0) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
@@ -193,9 +191,7 @@ void pdgp_upload_afar(gp_pdgp_plan p, const double* params) {
     const CondTask& t = p->cb.tasks[g];
     const BwdBufs& b = p->bw[g];
     const int M = q.M;
-    GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[S_AC] + i * sizeof(GemmProblem));
-    memset(&r, 0, sizeof(r));
-    r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+    GemmProblem& r = host_prob(p, S_AC, i, M);
     r.A = params + q.off_qsqrt; r.B = t.W; r.C = b.af_C;
     AfarItem& it = *(AfarItem*)(p->h_misc.data() + p->off.af_items + i * sizeof(AfarItem));
     it = AfarItem{t.z, t.kern.theta, t.W, b.af_C, t.Kuf, t.q_mu, t.A, t.s1, t.s2, t.dot,
@@ -222,17 +218,8 @@ static gp_status pdgp_era(gp_pdgp_plan p, int parts) {
   const int s0[2] = {0, behind}, cnt[2] = {p->qk0, p->nK - behind};
   for (int r = 0; r < 2; r++) {
     if (cnt[r] <= 0) continue;
-    GemmFlags f;
-    if (parts & ERA_E) {
-      f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM, maxM, f));
-      GP_CHECK(launch_sub_identity_batched(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM));
-    }
-    if (parts & ERA_R) {
-      f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-      GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_R) + s0[r], cnt[r], maxM, maxM, f));
-      GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_ALPHA) + s0[r], cnt[r], maxM, 1));
-    }
+    if (parts & ERA_E) GP_CHECK(launch_chain_e(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM));
+    if (parts & ERA_R) GP_CHECK(launch_chain_r_alpha(h, slot_probs(p, S_R) + s0[r], slot_probs(p, S_ALPHA) + s0[r], cnt[r], maxM));
   }
   return GP_OK;
 }
@@ -313,14 +300,10 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
     const double* gv = p->gFvar + (size_t)g * n;
     const bool kneed = (q.need_theta || q.need_z);
     auto P = [&](int slot) -> GemmProblem& {
-      // the kernel-gradient chain (slots S_R..S_S) is batched over the GPs that need it only
-      const bool kchain = (slot >= S_E);   // E, Wbar, R, alpha, Kuf_bar and the Cholesky-adjoint chain
+      // E, Kuf_bar and the unwhitened additions to Wbar are batched, as the chain is, over the GPs that need kernel gradients only
+      const bool kchain = (slot >= S_E);
       if (kchain && !kneed) { memset(&p->dummy_prob, 0, sizeof(p->dummy_prob)); return p->dummy_prob; }
-      const int idx = kchain ? kslot : g;
-      GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + idx * sizeof(GemmProblem));
-      memset(&r, 0, sizeof(r));
-      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-      return r;
+      return host_prob(p, slot, kchain ? kslot : g, M);
     };
     { GemmProblem& r = P(S_H); r.A = t.A; r.lda = ldN; r.B = t.A; r.ldb = ldN; r.K = n; r.v1 = gv; r.C = b.H;
       r.o2 = p->slabs + slab_off; slab_off += gp_align_up((size_t)p->nsplit * M * M * sizeof(double), 256) / sizeof(double);
@@ -329,12 +312,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       // Q route: the same product on Kuf gives Qbar (into T2) and v = Kuf gm (into Lu); H and u follow from S_QT / S_QHH / S_QU
       if (pdgp_on_q_route(p, g)) { r.A = t.Kuf; r.B = t.Kuf; r.C = b.T2; r.o0 = b.Lu; r.xa = nullptr; } }
     if (pdgp_on_q_route(p, g)) {
-      auto PQ = [&](int slot) -> GemmProblem& {
-        GemmProblem& r = *(GemmProblem*)(p->h_misc.data() + p->off.bwd[slot] + (g - p->q0) * sizeof(GemmProblem));
-        memset(&r, 0, sizeof(r));
-        r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
-        return r;
-      };
+      auto PQ = [&](int slot) -> GemmProblem& { return host_prob(p, slot, g - p->q0, M); };
       { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
       { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
       { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
@@ -359,20 +337,12 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
                    b.g_Lq_w);
     }
     { GemmProblem& r = P(S_E); r.A = q_sqrt; r.B = q_sqrt; r.C = b.E; }
-    { GemmProblem& r = P(S_EH); r.A = b.E; r.B = b.H; r.C = b.T1; }
-    { GemmProblem& r = P(S_WBAR); r.A = b.T1; r.B = t.L; r.C = b.Wbar; }
-    { GemmProblem& r = P(S_LU); r.A = t.L; r.v0 = b.u; r.o0 = b.Lu; }
-    { GemmProblem& r = P(S_RANK1); r.C = b.Wbar; r.v0 = q_mu; r.v1 = b.Lu; }
-    { GemmProblem& r = P(S_R); r.A = t.W; r.B = b.E; r.C = b.R; }
-    { GemmProblem& r = P(S_ALPHA); r.A = t.W; r.v0 = q_mu; r.o0 = b.alpha; }
+    if (kneed)
+      chain_fill(chain_slots(p->h_misc.data(), &p->off.bwd[S_CHAIN]), kslot, M,
+                 ChainBufs{t.L, t.W, b.E, b.H, b.u, q_mu, b.T1, b.T2, b.Wbar, b.R, b.Lu, b.alpha});
     { GemmProblem& r = P(S_G); r.A = b.R; r.B = t.A; r.ldb = ldN; r.N = n; r.v1 = gv; r.C = b.G; r.ldc = ldN; r.xb = b.R32;
       // (read only by the form that contracts Kuf_bar with dK/dtheta in its epilogue — gemm_strip.hip role 5)
       r.kern = t.kern; r.xa = params + q.off_z; r.v0 = b.alpha; r.v2 = gm; r.o0 = b.hyp_part; }
-    { GemmProblem& r = P(S_T2); r.A = t.W; r.B = b.Wbar; r.C = b.T2; }
-    { GemmProblem& r = P(S_LBAR); r.A = b.T2; r.B = t.W; r.C = b.T1; }
-    { GemmProblem& r = P(S_P); r.A = t.L; r.B = b.T1; r.C = b.T2; }
-    { GemmProblem& r = P(S_T3); r.A = t.W; r.B = b.T2; r.C = b.H; }
-    { GemmProblem& r = P(S_S); r.A = b.H; r.B = t.W; r.C = b.E; }
     if (kneed) kslot++;
   }
   // Kuf-side contractions, one launch per kernel family (same type and partial count): item array in kgps order inside
@@ -535,15 +505,10 @@ static gp_status bwd_h_chain(const BwdCall& c) {
 static gp_status bwd_wbar_chain(const BwdCall& c) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
   const int nK = p->nK, maxM = p->maxM;
-  GemmFlags f;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_EH), nK, maxM, maxM, f));
-  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_WBAR), nK, maxM, maxM, f));
-  GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_LU), nK, maxM, 0));
-  GP_CHECK(launch_rank1_tril_batched(h, slot_probs(p, S_RANK1), nK, maxM));
-  if (!p->whiten) {
+  GP_CHECK(launch_chain_wbar(h, chain_slots(p->d_misc, &p->off.bwd[S_CHAIN]), nK, maxM));
+  if (!p->whiten) {      // Wbar += tril(g' q_mu^T + G' Lq^T)
     GP_CHECK(launch_rank1_tril_batched(h, slot_probs(p, S_WB_R1), nK, maxM));
-    f = GemmFlags(); f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.beta = 1.0;
+    GemmFlags f; f.triA = TRI_LOWER; f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.beta = 1.0;
     GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_WB_L), nK, maxM, maxM, f));
   }
   return GP_OK;
@@ -555,18 +520,7 @@ static gp_status bwd_wbar_chain(const BwdCall& c) {
 static gp_status bwd_kuu_side(const BwdCall& c) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
   const int nK = p->nK, maxM = p->maxM;
-  GemmFlags f;
-  f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_T2), nK, maxM, maxM, f));
-  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_LBAR), nK, maxM, maxM, f));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_P), nK, maxM, maxM, f));
-  GP_CHECK(launch_phi_batched(h, slot_probs(p, S_P), nK, maxM));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_T3), nK, maxM, maxM, f));
-  f = GemmFlags(); f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_S), nK, maxM, maxM, f));
+  GP_CHECK(launch_chain_adjoint(h, chain_slots(p->d_misc, &p->off.bwd[S_CHAIN]), nK, maxM));
   for (auto& fam : p->hy_fams)
     if (fam.batched)
       GP_CHECK(launch_hyper_contract_items(h, fam.type, fam.m, (const HyperItem*)(p->d_misc + p->off.hy_items) + p->G + fam.first,

@@ -4,8 +4,10 @@
 //   c = LB^-1 (A err) / sigma; bound = -N/2 log 2pi - sum log diag LB - N/2 log s2 - |err|^2/(2 s2)
 //                                     + |c|^2/2 - sum Kdiag/(2 s2) + tr(A A^T)/2  [- 1000 sum |v_p|]
 // Everything is assembled from the same kernels as the Pdgp path (cov.hip, chol.hip, gemm.hip); the only
-// new device code is the handful of small scalar/vector kernels below.
+// new device code is the handful of small scalar/vector kernels below.  The backward pass's Wbar / R, alpha / Cholesky-adjoint
+// chain is bwd.hip's (engine.h ChainSlot), shared with the Pdgp and window plans; the scalar formulas are sgpr_terms.h's.
 #include "engine.h"
+#include "sgpr_terms.h"
 #include <string.h>
 
 // what gp_sgpr_set_workspace carves out of the caller's memory (sgpr_carve)
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(256) sgpr_B_kernel(const double* __restrict__ 
   const double inv = 1.0 / s2[0];
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < (int64_t)M * M; idx += (int64_t)gridDim.x * 256) {
     const int i = (int)(idx / M), j = (int)(idx % M);
-    B[idx] = H[idx] * inv + (i == j ? 1.0 : 0.0);
+    B[idx] = sgpr_B_entry(H[idx], inv, i, j);
   }
 }
 
@@ -166,31 +168,7 @@ __global__ void __launch_bounds__(256) sgpr_finish_kernel(const double* __restri
   red[threadIdx.x] = logd; __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   logd = red[0];
-  if (threadIdx.x == 0) {
-    double kd = 0.0, vabs = 0.0;
-    for (int p = 0; p < P; p++) {
-      const double* th = params + toff[p];
-      double v = th[0];
-      vabs += fabs(v);
-      if (gp_kern_kdiag_energy(ktype[p])) {
-        double s = 0.0;
-        for (int q = 0; q < km[p]; q++) s += th[2 + q];
-        v *= s;
-      }
-      kd += v;
-    }
-    const double LOG2PI = 1.8378770664093453;
-    double b = -0.5 * N * LOG2PI;          // sgpr_ss.py:56
-    b += -logd;                            // :57  (output_dim = 1)
-    b -= 0.5 * N * log(s2);                // :58
-    b += -0.5 * scal[1] / s2;              // :59
-    b += 0.5 * csq;                        // :60
-    b += -0.5 * (N * kd) / s2;             // :61
-    b += 0.5 * scal[2] / s2;               // :62  tr(A A^T) with A = A'/sigma
-    if (reg) b -= 1000.0 * vabs;           // :64-68
-    scal[0] = b;
-    scal[3] = kd;
-  }
+  if (threadIdx.x == 0) sgpr_bound_scalar(params, P, toff, ktype, km, reg, N, s2, logd, csq, scal);
 }
 
 // mean[n] = sum_rb dot[rb][n];  var[n] = kd + sum_rb s2[rb][n] - sum_rb s1[rb][n]   (SGPR.build_predict)
@@ -475,7 +453,7 @@ __global__ void __launch_bounds__(256) sgpr_E2_kernel(const double* __restrict__
   const double inv = 1.0 / s2[0];
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < (int64_t)M * M; idx += (int64_t)gridDim.x * 256) {
     const int i = (int)(idx / M), j = (int)(idx % M);
-    E2[idx] = inv * ((i == j ? 1.0 : 0.0) - Binv[idx] - ubar[i] * ubar[j]);
+    E2[idx] = sgpr_E2_entry(Binv, ubar, inv, idx, i, j);
   }
 }
 
@@ -524,16 +502,7 @@ __global__ void __launch_bounds__(256) sgpr_noise_grad_kernel(const double* __re
     if ((int)threadIdx.x < o) for (int q = 0; q < 3; q++) red[q][threadIdx.x] += red[q][threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    const double s = s2[0];
-    const double trBH = -0.5 * red[0][0] - 0.5 * red[1][0];
-    const double trH = scal[2];   // sum colsumsq(A') = tr(H)
-    double g = -trBH / (s * s) - red[2][0] / (s * s) - 0.5 * trH / (s * s) - 0.5 * N / s + 0.5 * scal[1] / (s * s) +
-               0.5 * N * scal[3] / (s * s);
-    g_noise[0] = g;
-    scal[4] = -0.5 * N / s;
-    scal[5] = g;
-  }
+  if (threadIdx.x == 0) sgpr_noise_grad_scalar(red[0][0], red[1][0], red[2][0], s2[0], N, scal, g_noise);
 }
 
 // d(-1000 sum |v_p|)/dv_p
@@ -569,24 +538,15 @@ static gp_status sgpr_backward(gp_sgpr_plan p, const double* params, const doubl
   const int f32 = p->f32;
   const int64_t ld = gp_strip_ld(N, f32 != 0);
   GP_HIP_CHECK(h, hipMemsetAsync(grad, 0, (size_t)p->nparams * sizeof(double), h->stream));
-  enum { Q_BINV = 0, Q_UBAR, Q_EH, Q_WBAR, Q_LU, Q_RANK1, Q_R, Q_ALPHA, Q_G, Q_T2, Q_LBAR, Q_P, Q_T3, Q_S, Q_COUNT };
+  // one record per slot: the B-side head, then the shared chain on (E, v) = (E2, ubar); H is free once E2 H and the noise terms are done
+  enum { Q_BINV = 0, Q_UBAR, Q_CHAIN, Q_G = Q_CHAIN + CH_G, Q_COUNT = Q_CHAIN + CH_COUNT };
   std::vector<GemmProblem> pr(Q_COUNT);
-  memset(pr.data(), 0, pr.size() * sizeof(GemmProblem));
-  auto sq = [&](int q) -> GemmProblem& { GemmProblem& r = pr[q]; r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M; return r; };
+  auto sq = [&](int q) -> GemmProblem& { gemm_problem_square(pr[q], M); return pr[q]; };
   { GemmProblem& r = sq(Q_BINV); r.A = p->WB; r.B = p->WB; r.C = p->Binv; }
   { GemmProblem& r = sq(Q_UBAR); r.A = p->WB; r.v0 = p->c; r.o0 = p->ubar; }
-  { GemmProblem& r = sq(Q_EH); r.A = p->E2; r.B = p->H; r.C = p->T1; }
-  { GemmProblem& r = sq(Q_WBAR); r.A = p->T1; r.B = p->L; r.C = p->Wbar; }
-  { GemmProblem& r = sq(Q_LU); r.A = p->L; r.v0 = p->u; r.o0 = p->Lu; }
-  { GemmProblem& r = sq(Q_RANK1); r.C = p->Wbar; r.v0 = p->ubar; r.v1 = p->Lu; }
-  { GemmProblem& r = sq(Q_R); r.A = p->W; r.B = p->E2; r.C = p->R; }
-  { GemmProblem& r = sq(Q_ALPHA); r.A = p->W; r.v0 = p->ubar; r.o0 = p->alpha; }
+  chain_fill(chain_slots_run(pr.data() + Q_CHAIN), 0, M,
+             ChainBufs{p->L, p->W, p->E2, p->H, p->u, p->ubar, p->T1, p->T2, p->Wbar, p->R, p->Lu, p->alpha});
   { GemmProblem& r = sq(Q_G); r.A = p->R; r.B = p->A; r.ldb = ld; r.N = N; r.v1 = p->ones; r.C = p->G; r.ldc = ld; }
-  { GemmProblem& r = sq(Q_T2); r.A = p->W; r.B = p->Wbar; r.C = p->T2; }
-  { GemmProblem& r = sq(Q_LBAR); r.A = p->T2; r.B = p->W; r.C = p->T1; }
-  { GemmProblem& r = sq(Q_P); r.A = p->L; r.B = p->T1; r.C = p->T2; }
-  { GemmProblem& r = sq(Q_T3); r.A = p->W; r.B = p->T2; r.C = p->H; }     // H is free once E2 H and the noise terms are done
-  { GemmProblem& r = sq(Q_S); r.A = p->H; r.B = p->W; r.C = p->E2; }
   // The gradient's tail — per kernel of the sum a Kuu-side contraction and two finish launches, 15 launches of a few
   // workgroups for five kernels — as ONE contraction launch over an item array and ONE finish launch (bwd.hip's item forms,
   // as the Pdgp plan uses them) when the kernels share type and partial count and the Kuf side went through the fused pass.
@@ -604,12 +564,10 @@ static gp_status sgpr_backward(gp_sgpr_plan p, const double* params, const doubl
   SgDesc d2;
   GP_CHECK(sg_upload(p, pr, &d2, 1, uu_items.data(), uu_items.size() * sizeof(HyperItem)));
   GemmProblem* D = d2.probs;
+  const ChainSlots chain = chain_slots_run(D + Q_CHAIN);
   char* const d_block1 = (char*)d2.probs;
-  GemmFlags f;
   // Binv = WB^T WB ; ubar = WB^T c (= Binv u / s)
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D + Q_BINV, 1, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D + Q_UBAR, 1, M, 1));
+  GP_CHECK(launch_chain_b_head(h, D + Q_BINV, D + Q_UBAR, 1, M));
   hipLaunchKernelGGL(sgpr_E2_kernel, dim3(64), dim3(256), 0, h->stream, p->Binv, p->ubar, p->E2, M, params);
   {
     const int nb = M < SG_NOISE_BLOCKS ? M : SG_NOISE_BLOCKS;       // partials in the (free by now) split-K slab buffer
@@ -620,45 +578,23 @@ static gp_status sgpr_backward(gp_sgpr_plan p, const double* params, const doubl
   // from here on ubar holds dF/du = ubar / s
   hipLaunchKernelGGL(div_scalar_kernel, dim3((M + 255) / 256), dim3(256), 0, h->stream, p->ubar, M, params);
   // Wbar = tril(E2 H L^T + ubar (L u)^T)
-  f = GemmFlags();
-  GP_CHECK(launch_gemm_batched(h, D + Q_EH, 1, M, M, f));
-  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D + Q_WBAR, 1, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D + Q_LU, 1, M, 0));
-  GP_CHECK(launch_rank1_tril_batched(h, D + Q_RANK1, 1, M));
+  GP_CHECK(launch_chain_wbar(h, chain, 1, M));
   // R = W^T E2 ; alpha = W^T ubar ; Kuf_bar = R A' + alpha y^T
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  GP_CHECK(launch_gemm_batched(h, D + Q_R, 1, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D + Q_ALPHA, 1, M, 1));
+  GP_CHECK(launch_chain_r_alpha(h, chain.p[CH_R], chain.p[CH_ALPHA], 1, M));
   // Kuu side (same Cholesky-adjoint chain as the Pdgp backward): five dependent M x M products that end in Kuu_bar (in E2).
   // Nothing on the Kuf side reads what they write (T1, T2, H, E2 — R = W^T E2 is already there), so for long batches the
   // chain runs on the helper stream underneath the Kuf_bar product and its contraction.
-  auto kuu_chain = [&]() -> gp_status {
-    GemmFlags f;
-    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D + Q_T2, 1, M, M, f));
-    f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
-    GP_CHECK(launch_gemm_batched(h, D + Q_LBAR, 1, M, M, f));
-    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D + Q_P, 1, M, M, f));
-    GP_CHECK(launch_phi_batched(h, D + Q_P, 1, M));
-    f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D + Q_T3, 1, M, M, f));
-    f = GemmFlags(); f.triB = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, D + Q_S, 1, M, M, f));
-    return GP_OK;
-  };
   const bool forked = (N >= 4096) && gp_aux_fork(h);
   if (forked) {
-    gp_status st = kuu_chain();
+    gp_status st = launch_chain_adjoint(h, chain, 1, M);
     gp_status s2 = gp_aux_end(h);
     GP_CHECK(st); GP_CHECK(s2);
   }
   hipLaunchKernelGGL(fill_kernel, dim3((N + 255) / 256), dim3(256), 0, h->stream, p->ones, N, 1.0);
-  f = GemmFlags(); f.big_tiles = (M > 64); f.scale_mode = 1; f.timer = GP_TIMER_KUF_BAR; f.role = (M > 64) ? 3 : 0; f.uniform_aligned = 1;
+  GemmFlags f; f.big_tiles = (M > 64); f.scale_mode = 1; f.timer = GP_TIMER_KUF_BAR; f.role = (M > 64) ? 3 : 0; f.uniform_aligned = 1;
   if (f32) { f.role = 3; GP_CHECK(launch_gemm_f32_role(h, D + Q_G, 1, M, N, f)); }
   else GP_CHECK(launch_gemm_batched(h, D + Q_G, 1, M, N, f));
-  if (!forked) GP_CHECK(kuu_chain());
+  if (!forked) GP_CHECK(launch_chain_adjoint(h, chain, 1, M));
   // every kernel of the sum sees the same Kuf_bar / Kuu_bar (K = sum_p K_p)
   // (Kuf side: all-Mercer sums of up to six kernels with at most four partials each go through ONE pass over Kuf_bar)
   bool fused = false;

@@ -6,7 +6,9 @@
 // of grids that occupy a few CUs each (0.59 ms per evaluation on an MI355X, nearly all of it launch latency).  Windows
 // are independent, so this plan carries W of them through the same ~50 launches: every kernel below runs over a
 // window index (blockIdx.z / a batch of GemmProblems / item arrays), with per-window parameters, data, workspaces and
-// results.  The arithmetic per window is exactly sgpr.hip's (same kernels, same operation order).
+// results.  The arithmetic per window is sgpr.hip's: the same kernels and operation order, the GEMM chain of the backward pass
+// from the one module both call (bwd.hip, engine.h ChainSlot), the scalar formulas from the one header (sgpr_terms.h); only
+// the small reductions around those formulas are this file's own.
 //
 // All windows share N, M and the kernel structure (number of kernels, their types and partial counts); parameters,
 // X, Y, Z differ.  Layout: params [W][nparams], X / Y [W][N], Z [W][M], bound [W], grad [W][nparams], contiguous.
@@ -21,6 +23,7 @@
 // sgb_kuu_pad_kernel writes the pad block of Kuu before every factorisation (the Cholesky runs in place), the pad rows
 // of the Kuf strip are zeroed once per descriptor upload (only the k-row builds write that strip afterwards).
 #include "engine.h"
+#include "sgpr_terms.h"
 #include <string.h>
 
 struct SgbWin {            // per-window device pointers (device array, indexed by the window slot)
@@ -38,7 +41,7 @@ struct SgbPredWin {        // per-window pointers of the prediction launches
 
 // The plan's three descriptor blocks: each layout function walks its regions once and yields every offset and the total.
 // (item arrays are kernel-major, [p][w]; C = windows in the block, P = kernels of the sum)
-enum SgbProb { F_A = 0, F_H, F_U, Q_BINV, Q_UBAR, Q_EH, Q_WBAR, Q_LU, Q_RANK1, Q_R, Q_ALPHA, Q_G, Q_T2, Q_LBAR, Q_P, Q_T3, Q_S, Q_COUNT };
+enum SgbProb { F_A = 0, F_H, F_U, Q_BINV, Q_UBAR, Q_CHAIN, Q_G = Q_CHAIN + CH_G, Q_COUNT = Q_CHAIN + CH_COUNT };   // the shared chain's slots from Q_CHAIN on
 struct SgbDescLayout {          // bound + gradient (sgb_upload)
   size_t win, ptr_L, ptr_W, ptr_LB, ptr_WB, M, ld, feat, cov_uu, cov_uf, hy_uf, hy_uu, fin, prob[Q_COUNT], bytes;
 };
@@ -133,11 +136,11 @@ __global__ void __launch_bounds__(256) sgb_B_kernel(const SgbWin* __restrict__ w
   const double inv = 1.0 / w.params[0];
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < (int64_t)M * M; idx += (int64_t)gridDim.x * 256) {
     const int i = (int)(idx / M), j = (int)(idx % M);
-    w.LB[idx] = w.H[idx] * inv + (i == j ? 1.0 : 0.0);
+    w.LB[idx] = sgpr_B_entry(w.H[idx], inv, i, j);
   }
 }
 
-// c = WB (u / s2) and the bound scalar (sgpr_ss.py:56-68); one block per window.  Same arithmetic as sgpr_finish_kernel.
+// c = WB (u / s2) and the bound scalar (sgpr_ss.py:56-68); one block per window.  The scalar is sgpr_finish_kernel's.
 __global__ void __launch_bounds__(256) sgb_finish_kernel(const SgbWin* __restrict__ wins, int M, int N, int P,
                                                          const int* __restrict__ toff, const int* __restrict__ ktype,
                                                          const int* __restrict__ km, int reg, double* __restrict__ bound) {
@@ -159,32 +162,7 @@ __global__ void __launch_bounds__(256) sgb_finish_kernel(const SgbWin* __restric
   red[threadIdx.x] = logd; __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   logd = red[0];
-  if (threadIdx.x == 0) {
-    double kd = 0.0, vabs = 0.0;
-    for (int p = 0; p < P; p++) {
-      const double* th = w.params + toff[p];
-      double v = th[0];
-      vabs += fabs(v);
-      if (gp_kern_kdiag_energy(ktype[p])) {
-        double s = 0.0;
-        for (int q = 0; q < km[p]; q++) s += th[2 + q];
-        v *= s;
-      }
-      kd += v;
-    }
-    const double LOG2PI = 1.8378770664093453;
-    double b = -0.5 * N * LOG2PI;
-    b += -logd;
-    b -= 0.5 * N * log(s2);
-    b += -0.5 * w.scal[1] / s2;
-    b += 0.5 * csq;
-    b += -0.5 * (N * kd) / s2;
-    b += 0.5 * w.scal[2] / s2;
-    if (reg) b -= 1000.0 * vabs;
-    w.scal[0] = b;
-    w.scal[3] = kd;
-    bound[blockIdx.x] = b;
-  }
+  if (threadIdx.x == 0) bound[blockIdx.x] = sgpr_bound_scalar(w.params, P, toff, ktype, km, reg, N, s2, logd, csq, w.scal);
 }
 
 // E2 = (I - Binv - ubar ubar^T) / s
@@ -193,7 +171,7 @@ __global__ void __launch_bounds__(256) sgb_E2_kernel(const SgbWin* __restrict__ 
   const double inv = 1.0 / w.params[0];
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < (int64_t)M * M; idx += (int64_t)gridDim.x * 256) {
     const int i = (int)(idx / M), j = (int)(idx % M);
-    w.E2[idx] = inv * ((i == j ? 1.0 : 0.0) - w.Binv[idx] - w.ubar[i] * w.ubar[j]);
+    w.E2[idx] = sgpr_E2_entry(w.Binv, w.ubar, inv, idx, i, j);
   }
 }
 
@@ -221,13 +199,7 @@ __global__ void __launch_bounds__(256) sgb_noise_grad_kernel(const SgbWin* __res
   for (int64_t i = threadIdx.x; i < nparams; i += 256) w.grad[i] = 0.0;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double trBH = -0.5 * red[0][0] - 0.5 * red[1][0];
-    const double trH = w.scal[2];
-    const double g = -trBH / (s * s) - red[2][0] / (s * s) - 0.5 * trH / (s * s) - 0.5 * N / s + 0.5 * w.scal[1] / (s * s) +
-                     0.5 * N * w.scal[3] / (s * s);
-    w.grad[0] = g;
-    w.scal[4] = -0.5 * N / s;
-    w.scal[5] = g;
+    sgpr_noise_grad_scalar(red[0][0], red[1][0], red[2][0], s, N, w.scal, w.grad);
     if (reg)       // d(-1000 sum |v_p|)/dv_p
       for (int p = 0; p < P; p++) { const double v = w.params[toff[p]]; w.grad[toff[p]] -= 1000.0 * (v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0)); }
   }
@@ -392,8 +364,7 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
     pL[w] = b + p->o_L; pW[w] = b + p->o_W; pLB[w] = b + p->o_LB; pWB[w] = b + p->o_WB; pM[w] = M; pld[w] = M;
     auto prob = [&](int q) -> GemmProblem& {
       GemmProblem& r = *((GemmProblem*)(hd + p->off.prob[q]) + w);
-      memset(&r, 0, sizeof(r));
-      r.M = M; r.N = M; r.K = M; r.lda = M; r.ldb = M; r.ldc = M;
+      gemm_problem_square(r, M);
       return r;
     };
     double *L = b + p->o_L, *Wm = b + p->o_W, *H = b + p->o_H, *WB = b + p->o_WB, *Kuf = b + p->o_Kuf, *A = b + p->o_A,
@@ -405,18 +376,8 @@ static gp_status sgb_upload(gp_sgprb_plan_t p, const double* params, const doubl
     { GemmProblem& r = prob(F_U); r.A = A; r.lda = ld; r.N = N; r.v0 = Yw; r.o0 = u; }
     { GemmProblem& r = prob(Q_BINV); r.A = WB; r.B = WB; r.C = Binv; }
     { GemmProblem& r = prob(Q_UBAR); r.A = WB; r.v0 = c; r.o0 = ubar; }
-    { GemmProblem& r = prob(Q_EH); r.A = E2; r.B = H; r.C = T1; }
-    { GemmProblem& r = prob(Q_WBAR); r.A = T1; r.B = L; r.C = Wbar; }
-    { GemmProblem& r = prob(Q_LU); r.A = L; r.v0 = u; r.o0 = Lu; }
-    { GemmProblem& r = prob(Q_RANK1); r.C = Wbar; r.v0 = ubar; r.v1 = Lu; }
-    { GemmProblem& r = prob(Q_R); r.A = Wm; r.B = E2; r.C = R; }
-    { GemmProblem& r = prob(Q_ALPHA); r.A = Wm; r.v0 = ubar; r.o0 = alpha; }
+    chain_fill(chain_slots(hd, &p->off.prob[Q_CHAIN]), w, M, ChainBufs{L, Wm, E2, H, u, ubar, T1, T2, Wbar, R, Lu, alpha});
     { GemmProblem& r = prob(Q_G); r.A = R; r.B = A; r.ldb = ld; r.N = N; r.v1 = p->ones; r.C = G; r.ldc = ld; }
-    { GemmProblem& r = prob(Q_T2); r.A = Wm; r.B = Wbar; r.C = T2; }
-    { GemmProblem& r = prob(Q_LBAR); r.A = T2; r.B = Wm; r.C = T1; }
-    { GemmProblem& r = prob(Q_P); r.A = L; r.B = T1; r.C = T2; }
-    { GemmProblem& r = prob(Q_T3); r.A = Wm; r.B = T2; r.C = H; }
-    { GemmProblem& r = prob(Q_S); r.A = H; r.B = Wm; r.C = E2; }
     for (int i = 0; i < P; i++) {
       DevKern k{p->ktype[i], p->m[i], par + p->off_theta[i]};
       double* ft = b + p->o_feat + (size_t)i * p->feat_stride;
@@ -484,34 +445,15 @@ static gp_status sgb_enqueue(gp_sgprb_plan_t p, int count, double* bound_dev, bo
   GP_HIP_CHECK(h, hipGetLastError());
   if (!with_grad) return GP_OK;
   // ---- backward (sgpr.hip: sgpr_backward, window-batched) ----
-  GemmFlags f;
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_BINV), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(Q_UBAR), W, M, 1));
+  const ChainSlots chain = chain_slots(dd, &p->off.prob[Q_CHAIN]);
+  GP_CHECK(launch_chain_b_head(h, D(Q_BINV), D(Q_UBAR), W, M));
   hipLaunchKernelGGL(sgb_E2_kernel, dim3(16, W), dim3(256), 0, h->stream, wins, M);
   hipLaunchKernelGGL(sgb_noise_grad_kernel, dim3(W), dim3(256), 0, h->stream, wins, M, N, p->nparams, P, p->d_toff, p->reg);
-  f = GemmFlags();
-  GP_CHECK(launch_gemm_batched(h, D(Q_EH), W, M, M, f));
-  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_WBAR), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(Q_LU), W, M, 0));
-  GP_CHECK(launch_rank1_tril_batched(h, D(Q_RANK1), W, M));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_R), W, M, M, f));
-  GP_CHECK(launch_matvec_batched(h, D(Q_ALPHA), W, M, 1));
-  f = GemmFlags(); f.big_tiles = (M > 64); f.scale_mode = 1; f.timer = GP_TIMER_KUF_BAR; f.role = (M > 64) ? 3 : 0;
+  GP_CHECK(launch_chain_wbar(h, chain, W, M));
+  GP_CHECK(launch_chain_r_alpha(h, chain.p[CH_R], chain.p[CH_ALPHA], W, M));
+  GemmFlags f; f.big_tiles = (M > 64); f.scale_mode = 1; f.timer = GP_TIMER_KUF_BAR; f.role = (M > 64) ? 3 : 0;
   GP_CHECK(launch_gemm_batched(h, D(Q_G), W, M, N, f));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_T2), W, M, M, f));
-  f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER; f.triC = TRI_LOWER; f.alpha = -1.0;
-  GP_CHECK(launch_gemm_batched(h, D(Q_LBAR), W, M, M, f));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_P), W, M, M, f));
-  GP_CHECK(launch_phi_batched(h, D(Q_P), W, M));
-  f = GemmFlags(); f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_T3), W, M, M, f));
-  f = GemmFlags(); f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, D(Q_S), W, M, M, f));
+  GP_CHECK(launch_chain_adjoint(h, chain, W, M));
   const HyperItem* hyf = (const HyperItem*)(dd + p->off.hy_uf);
   const HyperItem* hyu = (const HyperItem*)(dd + p->off.hy_uu);
   const HyperFinishItem* fin = (const HyperFinishItem*)(dd + p->off.fin);
