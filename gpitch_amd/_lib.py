@@ -25,7 +25,8 @@ TIMER_NAMES = ["kuf_build", "cond_A", "cond_LTA", "nt_gemm", "kuf_bar", "chol", 
 
 # every symbol include/gpitch_abi.h declares
 ABI_SYMBOLS = [
-    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_debug_gemm", "gp_last_not_pd_index",
+    "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_debug_gemm",
+    "gp_debug_hyper_contract", "gp_debug_hyper_records", "gp_debug_hyper_lean_takes", "gp_last_not_pd_index",
     "gp_kernel_build", "gp_kernel_build_f32", "gp_kernel_diag", "gp_chol_workspace_bytes", "gp_kuu_cholesky", "gp_cholesky_inplace",
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
     "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
@@ -115,6 +116,27 @@ class DebugGemmFlags(C.Structure):
                 ("rows64_ok", C.c_int32), ("alpha", C.c_double), ("beta", C.c_double)]
 
 
+class DebugHyperItem(C.Structure):
+    """gp_debug_hyper_item: one contraction of a gp_debug_hyper_contract launch (device pointers)"""
+    _fields_ = [("kern", KernelDesc), ("x1", C.c_void_p), ("x2", C.c_void_p), ("G", C.c_void_p), ("alpha", C.c_void_p),
+                ("gm", C.c_void_p), ("kvals", C.c_void_p), ("gscale", C.c_void_p), ("partials", C.c_void_p), ("gz", C.c_void_p),
+                ("feat", C.c_void_p), ("ldg", C.c_int64), ("ldk", C.c_int64), ("n1", C.c_int32), ("n2", C.c_int32),
+                ("symmetric", C.c_int32), ("g32", C.c_int32), ("feat_from", C.c_int32), ("pad_", C.c_int32)]
+
+
+class DebugHyperFinish(C.Structure):
+    """gp_debug_hyper_finish: one finish record of a gp_debug_hyper_contract launch (device pointers)"""
+    _fields_ = [("kern", KernelDesc), ("p_uf", C.c_void_p), ("p_uu", C.c_void_p), ("gv_sum", C.c_void_p), ("g_theta", C.c_void_p),
+                ("gz_uf", C.c_void_p), ("gz_uu", C.c_void_p), ("g_z", C.c_void_p), ("np_uf", C.c_int32), ("np_uu", C.c_int32),
+                ("cb_uf", C.c_int32), ("cb_uu", C.c_int32), ("n1", C.c_int32), ("pad_", C.c_int32)]
+
+
+class DebugHyperFlags(C.Structure):
+    """gp_debug_hyper_flags: what launch_hyper_contract_items takes beside its records"""
+    _fields_ = [("with_gz", C.c_int32), ("use_mfma", C.c_int32), ("g32_items", C.c_int32), ("lean_items", C.c_int32),
+                ("gscale_items", C.c_int32), ("n2_shared", C.c_int32), ("x2_shared", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -156,6 +178,10 @@ def load_library():
         "gp_debug_wave_takes": (i32, [i32, i32, i32, i32]),
         "gp_debug_gemm": (i32, [vp, C.POINTER(DebugGemmProblem), i32, i32, i32, C.POINTER(DebugGemmFlags), i32, i32, i32, vp, sz,
                                 C.POINTER(i32)]),
+        "gp_debug_hyper_contract": (i32, [vp, i32, C.POINTER(DebugHyperItem), C.POINTER(DebugHyperFinish), i32,
+                                          C.POINTER(DebugHyperFlags), vp, sz, C.POINTER(i32), C.POINTER(i32)]),
+        "gp_debug_hyper_records": (i64, [i32, i32]),
+        "gp_debug_hyper_lean_takes": (i32, [i32, i32, i32, i32, i32]),
         "gp_last_not_pd_index": (i32, [vp]),
         "gp_kernel_build": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),
         "gp_kernel_build_f32": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),

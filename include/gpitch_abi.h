@@ -116,6 +116,49 @@ typedef struct {
 gp_status gp_debug_gemm(gp_handle h, const gp_debug_gemm_problem* probs, int32_t batch, int32_t maxM, int32_t maxN,
                         const gp_debug_gemm_flags* flags, int32_t kind, int32_t form, int32_t nsplit, void* workspace,
                         size_t workspace_bytes, int32_t* partial_rows);
+/* For tests; synchronises nothing.  ONE launch of a kernel-gradient contraction host entry (or of its finish) on the caller's
+ * device buffers, no arithmetic of its own.  `items` / `fins` are HOST arrays of `count` records, uploaded (entries 1, 4) into
+ * `workspace`, a 16-byte aligned DEVICE buffer of at least 160 bytes per record, on the handle's stream.
+ *   entry 0  the single-record contraction (count = 1)
+ *         1  the items form of one kernel family with the flags' with_gz, use_mfma, x2_shared, g32_items, lean_items, gscale_items
+ *            (a record with x2 NULL reads the launch's shared x2 / n2_shared)
+ *         2  the one-pass contraction for the kernels of a sum: the records share x1, x2, G, alpha, gm; *taken = 0 and
+ *            GP_ERR_UNSUPPORTED when the sum kernel declines (nothing is contracted)
+ *         3  the single finish (fins[0]; no Kuu side)      4  the items finish, its grid sized by the largest record
+ * Contraction sums: partials[record][2 + 2 m] = sum_ij Gw_ij dK_ij/dtheta, Gw = G + alpha gm^T (G symmetrised when `symmetric`,
+ * columns scaled by 2 gscale[j] where gscale is given), gz[column block][n1] the same for d/dx1.  G / kvals are float32 strips
+ * when g32.  Mercer kernels: feat_from = -1 builds the record's feature tables into `feat` (16-byte aligned, 2 mpad (n1 + n2)
+ * + 64 doubles, mpad = m rounded up to 4), k >= 0 uses record k's (k < the record's index; same kernel and inputs).
+ * *nparts: the partial records each contraction left (entry 4: the grid's blocks per record).  A launch the selected form does
+ * not take: GP_ERR_UNSUPPORTED; records that break what the form reads unasked (matrix-core forms: kvals, alpha and gm in every
+ * record; lean_items: 16-byte aligned strips with even strides): GP_ERR_BAD_ARG.  Nothing is launched then. */
+typedef struct {
+  gp_kernel_desc kern;
+  const double* x1; const double* x2;
+  const void* G; const double* alpha; const double* gm;
+  const void* kvals; const double* gscale;
+  double* partials; double* gz; double* feat;
+  int64_t ldg, ldk;
+  int32_t n1, n2, symmetric, g32, feat_from, pad_;
+} gp_debug_hyper_item;
+typedef struct {
+  gp_kernel_desc kern;
+  const double* p_uf; const double* p_uu; const double* gv_sum; double* g_theta;
+  const double* gz_uf; const double* gz_uu; double* g_z;
+  int32_t np_uf, np_uu, cb_uf, cb_uu, n1, pad_;
+} gp_debug_hyper_finish;
+typedef struct {
+  int32_t with_gz, use_mfma, g32_items, lean_items, gscale_items, n2_shared;
+  const double* x2_shared;
+} gp_debug_hyper_flags;
+gp_status gp_debug_hyper_contract(gp_handle h, int32_t entry, const gp_debug_hyper_item* items, const gp_debug_hyper_finish* fins,
+                                  int32_t count, const gp_debug_hyper_flags* flags, void* workspace, size_t workspace_bytes,
+                                  int32_t* nparts, int32_t* taken);
+/* host-only queries, no device work: the partial records a plan reserves for one Kuf-side contraction of an M x N strip (-1 for
+ * an empty shape), and whether an items launch (use_mfma, lean_items, float64 strips) of `count` n1 x n2 records takes the
+ * lean matrix-core form, the one that applies gscale */
+int64_t gp_debug_hyper_records(int32_t N, int32_t M);
+int32_t gp_debug_hyper_lean_takes(int32_t type, int32_t m, int32_t n1, int32_t n2, int32_t count);
 /* pivot index reported by the last GP_ERR_NOT_PD (−1 if none) */
 int32_t gp_last_not_pd_index(gp_handle h);
 
