@@ -169,6 +169,7 @@ gp_status gp_destroy(gp_handle h) {
   if (h->ev_era) (void)hipEventDestroy(h->ev_era);
   if (h->ev_kuu) (void)hipEventDestroy(h->ev_kuu);
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
+  if (h->ev_guard) (void)hipEventDestroy(h->ev_guard);
   if (h->ev_feat) (void)hipEventDestroy(h->ev_feat);
   if (h->ev_diag) (void)hipEventDestroy(h->ev_diag);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);

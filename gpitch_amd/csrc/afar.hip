@@ -16,16 +16,14 @@
 //   afar_t_kernel     T-_X upwards and T+_X downwards over the groups, one thread per row j, side and factor: moving the reference
 //                     point by a = c (ref' - ref) >= 0 is m0' = e^{-a} m0, m1' = e^{-a} (m1 + a m0) (kuf_scan_prefix_kernel's
 //                     shift), then the rows that became far enter.  A fixed order, no atomics: two runs agree bit for bit.
-//   afar_prod_kernel  one workgroup per (group, GP), a thread per frame: Kuf[near, n] on chip, the rows walked eight at a time with
-//                     W, C and T as wave-uniform operands; stores A and leaves the complete column sums colsum(A^2),
-//                     colsum((C Kuf)^2) and A^T q_mu as ONE partial row each for cond_finish_kernel.
+//   afar_prod_kernel  a wavefront per 32 frames and GP on v_mfma_f64_16x16x4_f64: Kuf[near, S] and Psi in its
+//                     registers as the B operand, tiles of W, C and T as the A operand, all M / 16 row tiles walked; stores A and
+//                     leaves the complete column sums colsum(A^2), colsum((C Kuf)^2) and A^T q_mu as ONE partial row each for
+//                     cond_finish_kernel.
 #include "engine.h"
-#include <type_traits>
 
 #define AF_KAPPA (1.0 - 1.5e-12)
 #define AF_SQRT3 1.7320508075688772
-#define AF_NKL 32            // near rows a workgroup keeps in LDS (two tiles: what the benchmark's groups have); more are re-read
-#define AF_JB 8              // rows per register block of the product
 
 AfarSizes afar_sizes(int M, int N) {
   const size_t ng = ((size_t)N + AFAR_GROUP - 1) / AFAR_GROUP;
@@ -141,83 +139,179 @@ __global__ void __launch_bounds__(256) afar_t_kernel(const AfarItem* __restrict_
   }
 }
 
-// (pointers read out of an item are generic to the compiler.  AfG / AfGW say "global memory": plain global loads and stores.
-// AfK says "global memory that no one writes while this kernel runs" — W, C, T and q_mu, which earlier launches of the stream
-// left: their wave-uniform reads then take the scalar path, eight rows' operands per load, instead of one vector load per lane)
-typedef __attribute__((address_space(1))) const double AfG;
-typedef __attribute__((address_space(1))) double AfGW;
-typedef __attribute__((address_space(4))) const double AfK;
+// ---- the product on v_mfma_f64_16x16x4_f64 ---------------------------------------------------------
+// A wavefront owns AF_COLS = 32 frames of one group and walks all M / 16 row tiles; a workgroup is four wavefronts on
+// adjacent column blocks (they read the same tiles of W, C and T at the same time), eight wavefronts cover a group.  Per row
+// tile and factor X (W, C) one contraction over the far field's four columns and the near rows:
+//   A operand, lane (kq, lc):  far step  T[S][16 a + lc][fac * 4 + kq]              (k = Psi-0, Psi-1, Psi+0, Psi+1)
+//                              near      X[16 a + lc][k0 + 2 kq], [k0 + 2 kq + 1]   one 16-byte load = k-steps s = 0, 1
+//   B operand, lane (kq, lc):  far step  Psi[kq][n0 + 2 lc], [n0 + 2 lc + 1]         one 16-byte load = column tiles p = 0, 1
+//                              near      Kuf[k0 + 2 kq + s][n0 + 2 lc], [+ 1]        (gemm_wave.hip's fragment order)
+// so the accumulator of column tile p holds column n0 + 2 lc + p, rows 16 a + kq + 4 r: a store of A is 16 bytes per lane, 256
+// bytes per row.  The B operand does not depend on the row tile: the first AF_CT = 2 near tiles (32 rows: every group of the
+// usual layouts) and Psi stay in registers for the whole walk, further near tiles are read again per row tile from the strip,
+// which the caches hold.  Any near-row count: nothing depends on what fits on chip.
+// W is lower triangular: a 16 x 16 tile of W[:, near] wholly above the diagonal is skipped (wave-uniform), and in the tile on
+// the diagonal the entries above it are MASKED in the registers — like afar_t_kernel, the product does not rely on what the
+// buffer holds there.
+// Column sums: a lane keeps running s1, s2 and dot for its two columns over its rows (ascending); the four lane quarters are
+// added once at the end as ((q0 + q1) + q2) + q3.  A fixed order: two runs agree bit for bit.
+// W, C and T go through buffer loads (scalar base and offset, one constant lane offset); the strips, which may pass 2 GiB,
+// through 64-bit addresses; q_mu is copied to LDS once (8 KB at most, the kernel's only barrier).  The operands of row tile
+// a + 1 are requested behind the MFMAs of row tile a and ahead of its stores.
+typedef double af_d4 __attribute__((ext_vector_type(4)));
+typedef double af_d2 __attribute__((ext_vector_type(2)));
+typedef const af_d2 __attribute__((address_space(1))) * af_gc2;
+typedef af_d2 __attribute__((address_space(1))) * af_g2;
 
-// Eight rows j0 .. j0 + 7 of both products for the thread's frame.  kv: the thread's column of Kuf[near, S] — its own slots of the
-// workgroup's LDS array (stride 256) or, beyond AF_NKL near rows, the stored strip itself (stride ld).  W, C, T are read at
-// wave-uniform addresses.  The restrict qualifiers tell the compiler that the A stores leave them alone.
-template <bool LDS>
-static __device__ __forceinline__ void afar_rows(AfK* __restrict__ W, AfK* __restrict__ C, AfK* __restrict__ T8,
-                                                 typename std::conditional<LDS, const double, AfG>::type* kv, size_t kstride, AfK* __restrict__ q_mu,
-                                                 AfGW* __restrict__ Acol, size_t ld, int M, int kbeg, int kend,
-                                                 const double psi[4], double& s1, double& s2, double& dot) {
-  for (int j0 = 0; j0 < M; j0 += AF_JB) {
-    double aw[AF_JB], ac[AF_JB];
+#define AF_COLS 32           // frames per wavefront
+#define AF_CT 2              // near 16-row tiles of the B operand a wavefront keeps in registers
+#define AF_SB __builtin_amdgcn_sched_barrier(0)
+
+struct AfFrag {              // the A operands of one row tile: near tiles t < AF_CT (two 8-deep chunks each), the far step
+  af_d2 w[AF_CT][2], c[AF_CT][2];
+  double tw, tc;
+};
+
+// the entries above the diagonal of the tile on it: lane (kq, lc) holds row lc, columns 8 h + 2 kq and the next one
+static __device__ __forceinline__ void af_mask_diag(af_d2 (&w)[2], int lc, int kq) {
 #pragma unroll
-    for (int r = 0; r < AF_JB; r++) {
-      AfK* t = T8 + (size_t)(j0 + r) * 8;
-      aw[r] = fma(t[3], psi[3], fma(t[2], psi[2], fma(t[1], psi[1], t[0] * psi[0])));
-      ac[r] = fma(t[7], psi[3], fma(t[6], psi[2], fma(t[5], psi[1], t[4] * psi[0])));
-    }
-    for (int k = kbeg; k < kend; k += 2) {
-      const double k0 = kv[(size_t)(k - kbeg) * kstride], k1 = kv[(size_t)(k - kbeg + 1) * kstride];
-#pragma unroll
-      for (int r = 0; r < AF_JB; r++) {
-        AfK* cr = C + (size_t)(j0 + r) * M + k;
-        ac[r] = fma(cr[1], k1, fma(cr[0], k0, ac[r]));
-      }
-    }
-    // W is lower triangular: row j takes the rows k <= j only
-    const int kf = min(kend, j0), kw = min(kend, j0 + AF_JB);
-    for (int k = kbeg; k < kf; k += 2) {               // whole columns: k < j0
-      const double k0 = kv[(size_t)(k - kbeg) * kstride], k1 = kv[(size_t)(k - kbeg + 1) * kstride];
-#pragma unroll
-      for (int r = 0; r < AF_JB; r++) {
-        AfK* wr = W + (size_t)(j0 + r) * M + k;
-        aw[r] = fma(wr[1], k1, fma(wr[0], k0, aw[r]));
-      }
-    }
-    for (int k = max(kbeg, j0); k < kw; k += 2) {      // the diagonal block
-      const double k0 = kv[(size_t)(k - kbeg) * kstride], k1 = kv[(size_t)(k - kbeg + 1) * kstride];
-#pragma unroll
-      for (int r = 0; r < AF_JB; r++) {
-        AfK* wr = W + (size_t)(j0 + r) * M + k;
-        const double w0 = (k <= j0 + r) ? wr[0] : 0.0, w1 = (k + 1 <= j0 + r) ? wr[1] : 0.0;
-        aw[r] = fma(w1, k1, fma(w0, k0, aw[r]));
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < AF_JB; r++) {
-      Acol[(size_t)(j0 + r) * ld] = aw[r];
-      s1 = fma(aw[r], aw[r], s1);
-      s2 = fma(ac[r], ac[r], s2);
-      dot = fma(aw[r], q_mu[j0 + r], dot);
-    }
+  for (int h = 0; h < 2; h++) {
+    const int d = 8 * h + 2 * kq - lc;
+    if (d > 0) w[h].x = 0.0;
+    if (d + 1 > 0) w[h].y = 0.0;
   }
 }
 
-__global__ void __launch_bounds__(AFAR_GROUP) afar_prod_kernel(const AfarItem* __restrict__ items, int N) {
+// one near tile (four k-steps) into both factors' accumulators; WF: the tile of W has entries on or below the diagonal
+template <bool WF>
+static __device__ __forceinline__ void af_tile(const af_d2 (&w)[2], const af_d2 (&c)[2], const af_d2 (&b)[2][2], af_d4 (&aw)[2], af_d4 (&ac)[2]) {
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const double cf = s ? c[h].y : c[h].x, wf = s ? w[h].y : w[h].x;
+      ac[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(cf, b[h][s].x, ac[0], 0, 0, 0);
+      ac[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(cf, b[h][s].y, ac[1], 0, 0, 0);
+      if (WF) {
+        aw[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf, b[h][s].x, aw[0], 0, 0, 0);
+        aw[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf, b[h][s].y, aw[1], 0, 0, 0);
+      }
+    }
+}
+
+__global__ void __launch_bounds__(256, 3) afar_prod_kernel(const AfarItem* __restrict__ items, int N) {
   const AfarItem it = items[blockIdx.y];
-  const int S = blockIdx.x, tid = threadIdx.x, n = S * AFAR_GROUP + tid, M = it.M;
-  // (the range is the same for the whole workgroup: said so, the loop counters and the operand addresses stay in scalar registers)
-  const int kbeg = __builtin_amdgcn_readfirstlane(it.rng[2 * S]), kend = __builtin_amdgcn_readfirstlane(it.rng[2 * S + 1]), nk = kend - kbeg;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lc = lane & 15, kq = lane >> 4;
+  const int n0 = (blockIdx.x * 4 + wave) * AF_COLS, S = n0 / AFAR_GROUP, M = it.M, nt = M / 16;
+  // (the range is the same for the whole wavefront: said so, the loop counters and the operand offsets stay in scalar registers)
+  const int kbeg = __builtin_amdgcn_readfirstlane(it.rng[2 * S]), kend = __builtin_amdgcn_readfirstlane(it.rng[2 * S + 1]);
+  const int ntile = (kend - kbeg) / 16, tb = kbeg / 16;
   const size_t ld = (size_t)it.ld;
-  __shared__ double kl[AF_NKL * AFAR_GROUP];         // [near row][frame]: a thread reads back only what it wrote itself — no barrier
-  const double psi[4] = {it.Psi[n], it.Psi[(size_t)N + n], it.Psi[2 * (size_t)N + n], it.Psi[3 * (size_t)N + n]};
-  const double* T8 = it.T + (size_t)S * M * 8;
-  double s1 = 0.0, s2 = 0.0, dot = 0.0;
-  if (nk <= AF_NKL) {
-    for (int k = 0; k < nk; k++) kl[k * AFAR_GROUP + tid] = it.Kuf[(size_t)(kbeg + k) * ld + n];
-    afar_rows<true>((AfK*)it.W, (AfK*)it.C, (AfK*)T8, kl + tid, AFAR_GROUP, (AfK*)it.q_mu, (AfGW*)(it.A + n), ld, M, kbeg, kend, psi, s1, s2, dot);
-  } else {
-    afar_rows<false>((AfK*)it.W, (AfK*)it.C, (AfK*)T8, (AfG*)(it.Kuf + (size_t)kbeg * ld + n), ld, (AfK*)it.q_mu, (AfGW*)(it.A + n), ld, M, kbeg, kend, psi, s1, s2, dot);
+
+  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)it.W, 0, M * M * 8, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)it.C, 0, M * M * 8, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc((void*)(it.T + (size_t)S * M * 8), 0, M * 64, 0x00020000);
+  const int voffX = (lc * M + 2 * kq) * 8, voffT = (lc * 8 + kq) * 8;
+  __shared__ double qs[1024];                                                      // q_mu (M <= 1024), read back in every epilogue
+  for (int j = threadIdx.x; j < M; j += 256) qs[j] = it.q_mu[j];
+  __syncthreads();
+
+  // the B operand: Psi and the first AF_CT near tiles, for the whole walk
+  const af_d2 Pf = *(af_gc2)(it.Psi + (size_t)kq * N + n0 + 2 * lc);
+  const double* kp = it.Kuf + ((size_t)kbeg + 2 * kq) * ld + n0 + 2 * lc;          // row kbeg + 2 kq of the lane's two columns
+  af_d2 Bc[AF_CT][2][2];
+#pragma unroll
+  for (int t = 0; t < AF_CT; t++)
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        Bc[t][h][s] = af_d2{0.0, 0.0};
+        if (t < ntile) Bc[t][h][s] = *(af_gc2)(kp + (size_t)(16 * t + 8 * h + s) * ld);
+      }
+
+  // requests only: nothing here consumes a loaded value
+  auto load_frag = [&](AfFrag& f, const int a) {
+    const int so = (a * 16 * M + kbeg) * 8, ntw = min(a - tb + 1, ntile);
+#pragma unroll
+    for (int t = 0; t < AF_CT; t++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        f.c[t][h] = f.w[t][h] = af_d2{0.0, 0.0};
+        if (t < ntile) f.c[t][h] = __builtin_bit_cast(af_d2, __builtin_amdgcn_raw_buffer_load_b128(rC, voffX + (16 * t + 8 * h) * 8, so, 0));
+        if (t < ntw) f.w[t][h] = __builtin_bit_cast(af_d2, __builtin_amdgcn_raw_buffer_load_b128(rW, voffX + (16 * t + 8 * h) * 8, so, 0));
+      }
+    f.tw = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rT, voffT, a * 16 * 64, 0));
+    f.tc = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rT, voffT + 32, a * 16 * 64, 0));
+  };
+
+  AfFrag f;
+  load_frag(f, 0);
+
+  af_g2 pA = (af_g2)(it.A + (size_t)kq * ld + n0 + 2 * lc);
+  const af_d4 zero4 = {0.0, 0.0, 0.0, 0.0};
+  double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0}, dot[2] = {0.0, 0.0};
+  for (int a = 0; a < nt; a++) {
+    const int ntw = min(a - tb + 1, ntile), tdiag = a - tb;       // tiles of W[16 a .. 16 a + 15, near] with anything in them
+    af_d4 aw[2], ac[2];
+    aw[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.tw, Pf.x, zero4, 0, 0, 0);
+    aw[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.tw, Pf.y, zero4, 0, 0, 0);
+    ac[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.tc, Pf.x, zero4, 0, 0, 0);
+    ac[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.tc, Pf.y, zero4, 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < AF_CT; t++) {
+      if (t < ntw) {
+        if (t == tdiag) af_mask_diag(f.w[t], lc, kq);
+        af_tile<true>(f.w[t], f.c[t], Bc[t], aw, ac);
+      } else if (t < ntile) {
+        af_tile<false>(f.w[t], f.c[t], Bc[t], aw, ac);
+      }
+    }
+    for (int t = AF_CT; t < ntile; t++) {                          // more than 32 near rows: the strip again
+      af_d2 b[2][2], w[2], c[2];
+      const int so = (a * 16 * M + kbeg + 16 * t) * 8;
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+#pragma unroll
+        for (int s = 0; s < 2; s++) b[h][s] = *(af_gc2)(kp + ((size_t)16 * t + 8 * h + s) * ld);
+        c[h] = __builtin_bit_cast(af_d2, __builtin_amdgcn_raw_buffer_load_b128(rC, voffX + 8 * h * 8, so, 0));
+        w[h] = af_d2{0.0, 0.0};
+        if (t < ntw) w[h] = __builtin_bit_cast(af_d2, __builtin_amdgcn_raw_buffer_load_b128(rW, voffX + 8 * h * 8, so, 0));
+      }
+      if (t < ntw) {
+        if (t == tdiag) af_mask_diag(w, lc, kq);
+        af_tile<true>(w, c, b, aw, ac);
+      } else {
+        af_tile<false>(w, c, b, aw, ac);
+      }
+    }
+    AF_SB;
+    load_frag(f, min(a + 1, nt - 1));                               // (behind the last row tile: that tile again, from the cache)
+    AF_SB;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {                                   // rows 16 a + kq + 4 r
+      const double v0 = aw[0][r], v1 = aw[1][r];
+      *pA = af_d2{v0, v1};
+      pA += 2 * ld;
+      s1[0] = fma(v0, v0, s1[0]); s1[1] = fma(v1, v1, s1[1]);
+      const double q = qs[16 * a + kq + 4 * r];
+      dot[0] = fma(v0, q, dot[0]); dot[1] = fma(v1, q, dot[1]);
+      s2[0] = fma(ac[0][r], ac[0][r], s2[0]); s2[1] = fma(ac[1][r], ac[1][r], s2[1]);
+    }
   }
-  it.s1[n] = s1; it.s2[n] = s2; it.dot[n] = dot;
+  // the four lane quarters hold rows = 0, 1, 2, 3 (mod 4) of the same columns
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    double t1 = 0.0, t2 = 0.0, td = 0.0;
+#pragma unroll
+    for (int qq = 0; qq < 4; qq++) {
+      const double u1 = __shfl(s1[p], lc + 16 * qq, 64), u2 = __shfl(s2[p], lc + 16 * qq, 64), ud = __shfl(dot[p], lc + 16 * qq, 64);
+      t1 = qq ? t1 + u1 : u1; t2 = qq ? t2 + u2 : u2; td = qq ? td + ud : ud;
+    }
+    if (kq == 0) { const int n = n0 + 2 * lc + p; it.s1[n] = t1; it.s2[n] = t2; it.dot[n] = td; }
+  }
 }
 
 gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, const double* x, int n) {
@@ -228,7 +322,7 @@ gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, co
   GP_HIP_CHECK(h, hipGetLastError());
   {
     GpTimerScope ts(h, GP_TIMER_COND_A);
-    hipLaunchKernelGGL(afar_prod_kernel, dim3(n / AFAR_GROUP, count), dim3(AFAR_GROUP), 0, h->stream, d_items, n);
+    hipLaunchKernelGGL(afar_prod_kernel, dim3(n / (4 * AF_COLS), count), dim3(256), 0, h->stream, d_items, n);
     GP_HIP_CHECK(h, hipGetLastError());
   }
   return GP_OK;

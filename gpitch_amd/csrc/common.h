@@ -25,8 +25,8 @@ struct gp_handle_s {
   GpLogisticTable logistic = {}; int num_logistic = 0;
   // helper stream for work that can overlap the main stream (the latency-bound Kuu factorisation runs on ~24 CUs
   // while the Kuf builds stream over the rest): created on first use, joined through events
-  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr, ev_q = nullptr, ev_feat = nullptr;
-  hipStream_t main_stream_saved = nullptr; bool aux_active = false, aux_pending = false;
+  hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr, ev_era = nullptr, ev_kuu = nullptr, ev_diag = nullptr, ev_q = nullptr, ev_guard = nullptr, ev_feat = nullptr;
+  hipStream_t main_stream_saved = nullptr; bool aux_active = false, aux_pending = false, guard_pending = false;   // guard_pending: ev_guard is recorded and h->stream has not waited for it yet
   // second helper stream ("side"): one more independent piece of a step (the spectral-mixture Kuf-side contractions
   // underneath the second half of the Kuf_bar product); gp_side_begin / _end / _join
   hipStream_t side_stream = nullptr; hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;

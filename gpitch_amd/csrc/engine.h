@@ -145,15 +145,15 @@ gp_status launch_qbar(gp_handle h, const QbarItem* d_items, int count, int M, in
 
 // afar.hip: the activations' A = W Kuf and colsum((Lq^T A)^2) from near rows plus an exact rank-4 far field,
 // one item per latent GP of the run: the conditional's operands and outputs, C = tril(Lq)^T W, and the tables of this step
-// W, C, T, q_mu are read through the constant address space (scalar loads at wave-uniform addresses): none of them may alias
-// A, s1, s2 or dot, and nothing may write them while afar_prod_kernel runs — they are left by earlier launches of the stream.
+// W, C, T, q_mu are the matrix cores' A operand and the epilogue's weights (buffer loads): none of them may
+// alias A, s1, s2 or dot, and nothing may write them while afar_prod_kernel runs — they are left by earlier launches of the stream.
 struct AfarItem {
   const double* z; const double* theta; const double* W; const double* C; const double* Kuf; const double* q_mu;
   double* A; double* s1; double* s2; double* dot;    // the stored strip; ONE partial row each of colsum(A^2), colsum((C Kuf)^2), A^T q_mu
   int* rng; double* ref; double* T; double* Psi;     // [groups][2] near range, [groups][2] xmin / xmax, T [groups][M][8], Psi [4][N]
   int64_t ld; int M, pad;
 };
-#define AFAR_GROUP 256       // frames per column group: one workgroup of the product
+#define AFAR_GROUP 256       // frames per column group: one workgroup of the tables' kernels, eight wavefronts of the product
 struct AfarSizes { size_t rng, ref, T, Psi, C; };    // doubles
 AfarSizes afar_sizes(int M, int N);
 bool afar_takes(int M, int N);

@@ -317,6 +317,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
 void pdgp_qform_select(gp_pdgp_plan p, int n);
 void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
 gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n);
+gp_status pdgp_qform_join(gp_pdgp_plan p);
 void pdgp_afar_select(gp_pdgp_plan p, int n);
 void pdgp_upload_afar(gp_pdgp_plan p, const double* params);
 gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n);
@@ -397,7 +398,12 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
   const std::function<gp_status()> q_prepare = [&]() -> gp_status { return pdgp_qform_prepare(p, x, n); };
   // (so does the activations' far field: predictions keep the dense products)
   const std::function<gp_status()> a_run = [&]() -> gp_status { return pdgp_afar_run(p, x, n); };
-  GP_CHECK(cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr, p->na > 0 ? &a_run : nullptr));
+  {
+    const gp_status st = cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr, p->na > 0 ? &a_run : nullptr);
+    // the Q run's product is enqueued (or the run failed): the guard joins the main stream ahead of everything that follows
+    const gp_status sj = pdgp_qform_join(p);
+    GP_CHECK(st); GP_CHECK(sj);
+  }
   bool kl_done = false;   // the whitened KL kernel went to the helper stream with the backward prefetch
   if (grad) GP_CHECK(pdgp_prefetch_backward(p, n, &kl_done));
   if (kl_done) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_era, 0));   // behind the forward strips: no stall

@@ -124,8 +124,10 @@ __global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __r
 // far_wait: the far field's tables (qfar.hip) follow Q and precede the guard — the guard is one workgroup per GP and, beside
 // the other GPs' strip products, the longest link of this chain, while the tables are what the product waits for.  They read
 // the feature tables of the Kuf builds, which the main stream has enqueued: on the helper stream (far_wait) they first wait
-// for the event cond_batch_run left behind those builds.
-static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wait) {
+// for the event cond_batch_run left behind those builds.  tables_done: recorded between the tables and the guard — the product
+// reads Q and the tables, not the guard's verdict.
+gp_status pdgp_qform_join(gp_pdgp_plan p);
+static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wait, hipEvent_t tables_done = nullptr) {
   gp_handle h = p->h;
   const int nq = p->nq, maxM = p->maxM;
   GP_CHECK(launch_chain_e(h, slot_probs(p, S_QE), nq, maxM));
@@ -136,28 +138,46 @@ static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wa
     if (far_wait && hipStreamWaitEvent(h->stream, h->ev_feat, 0) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
     GP_CHECK(launch_qfar_tables(h, (const QfarItem*)(p->d_misc + p->off.qf_items), nq, maxM, p->gps[p->q0].m, x, n));
   }
+  if (tables_done && hipEventRecord(tables_done, h->stream) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
   hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
   if (hipGetLastError() != hipSuccess) return gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
   return GP_OK;
 }
 
 // E, R, beta, Q, the far field's tables and the guard of the Q run: cond_batch_run's hook (pdgp.hip).  On the helper stream when the plan overlaps
-// (behind the factorisation it has just run, beside the other GPs' strip products), else in line; h->stream waits either way.
+// (behind the factorisation it has just run, beside the other GPs' strip products), else in line.  From the helper stream
+// h->stream waits here for Q and the tables only (ev_q, recorded ahead of the guard); the guard's event (ev_guard) is waited
+// for by pdgp_qform_join, which pdgp_forward calls once the product is enqueued: the status word is complete before anything
+// of the step's tail and before any host-scalar read, with or without a gradient.
 gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n) {
   gp_handle h = p->h;
+  h->guard_pending = false;
   if (p->nq <= 0) return GP_OK;
   bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
   if (aux && p->q_far && !p->cb.feat_ready) aux = false;
   if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
+  if (aux && !h->ev_guard && hipEventCreateWithFlags(&h->ev_guard, hipEventDisableTiming) != hipSuccess) { h->ev_guard = nullptr; aux = false; }
   gp_status st;
-  { GpStreamScope on(h, aux ? h->aux_stream : nullptr); st = qform_chain(p, x, n, aux); }
+  { GpStreamScope on(h, aux ? h->aux_stream : nullptr); st = qform_chain(p, x, n, aux, aux ? h->ev_q : nullptr); }
   hipError_t e = hipSuccess;
   if (aux) {
-    e = hipEventRecord(h->ev_q, h->aux_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_q, 0);
+    // (whatever the chain enqueued on the helper stream is joined, also when it failed half way)
+    e = hipEventRecord(h->ev_guard, h->aux_stream);
+    if (e == hipSuccess) h->guard_pending = true;
+    if (e == hipSuccess && st == GP_OK) e = hipStreamWaitEvent(h->stream, h->ev_q, 0);
+    if (st != GP_OK) (void)pdgp_qform_join(p);
   }
   GP_CHECK(st);
   if (e != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
+  return GP_OK;
+}
+
+// h->stream waits for the guard that pdgp_qform_prepare left on the helper stream (nothing to do when it ran in line)
+gp_status pdgp_qform_join(gp_pdgp_plan p) {
+  gp_handle h = p->h;
+  if (!h->guard_pending) return GP_OK;
+  h->guard_pending = false;
+  if (hipStreamWaitEvent(h->stream, h->ev_guard, 0) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
   return GP_OK;
 }
 
