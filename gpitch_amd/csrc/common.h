@@ -454,6 +454,15 @@ gp_status pdgp_sample_check(gp_handle h, const PsmGP* gps, int G, int n, int S, 
 gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int nlin, double jitter, const double* xnew, int n,
                           int S, const int32_t* order_host, const double* eps_x, const double* eps_z, const double* eps_u,
                           double* latents, double* sources, void* ws, size_t ws_bytes);
+// ssm_smooth.hip: the exact per-source posterior of SGPRSS windows by a Kalman filter and a Bryson-Frazier backward pass
+// (gp_sgpr_predict_source_ssm, gp_sgprb_predict_source_ssm).  Every argument is checked before anything is enqueued.  Window
+// w < count: params + w * param_stride, X / Y + w * N, Xnew + w * n, order_host + w * (N + n) (its first steps_host[w] entries),
+// out_step_host + w * n, mean / var + w * P * n, loglik + w.  Synchronises.
+size_t ssm_smooth_workspace_bytes(int d, int steps, int P, int count);
+gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
+                         double* var, double* loglik, void* ws, size_t ws_bytes);
 gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int64_t ldy, int n, int square, double* out);
 // lik.hip
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)

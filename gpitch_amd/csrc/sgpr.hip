@@ -946,6 +946,18 @@ size_t gp_sgpr_sample_source_workspace_bytes(int32_t M, int32_t P, int32_t C, in
   return sgpr_sample_workspace_bytes(M, P, C, n, S, count);
 }
 
+// The exact per-source posterior by the state-space smoother (ssm_smooth.hip).  The plan gives the kernel structure and the
+// parameter layout only: Z is not an argument, no forward pass of the bound runs and the plan's own workspace and recorded
+// graph are left alone.  Every argument, the host arrays included, is checked before anything is enqueued.
+gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                     const double* Xnew, int32_t n, const int32_t* order_host, const int32_t* out_step_host,
+                                     int32_t steps, double* mean, double* var, double* loglik, void* workspace,
+                                     size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  return ssm_smooth_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, N, Xnew, n, 1,
+                        order_host, out_step_host, &steps, mean, var, loglik, workspace, workspace_bytes);
+}
+
 // sgpr_predict_source_impl's workspace
 struct SgprSrcBufs { char* d_desc; double *L, *W; void* chol_ws; double *Kx, *A, *feat, *s1, *dot, *V, *scal; };
 static SgprSrcBufs sgpr_src_carve(GpArena& ar, int N, int n) {

@@ -777,6 +777,19 @@ extern "C" gp_status gp_sgprb_sample_source_sparse(gp_sgprb_plan_t p, const doub
   return check_not_pd(h);
 }
 
+// gp_sgpr_predict_source_ssm of the first `count` windows (ssm_smooth.hip): one workgroup per window in every launch.  Only the
+// kernel structure and the parameter layout come from the plan: Z, the inducing counts and the strip precision play no part.
+extern "C" gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
+                                                 const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
+                                                 const int32_t* out_step_host, const int32_t* steps_host, double* mean, double* var,
+                                                 double* loglik, void* workspace, size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (count < 1 || count > p->W)
+    return gp_fail(p->h, GP_ERR_BAD_ARG, "gp_sgprb_predict_source_ssm: bad argument (1 <= count <= num_windows)");
+  return ssm_smooth_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, p->N, Xnew, n,
+                        count, order_host, out_step_host, steps_host, mean, var, loglik, workspace, workspace_bytes);
+}
+
 // gp_sgprb_predict_source's workspace: descriptor block, the batched factorisation's own, then per window
 // K -> L, W = L^-1, K_p(X, Xnew), one feature table, the two [rb][n] partials, V = W y and the scalars
 struct SgbSrcWin { double *L, *W, *Kx, *feat, *s1, *dot, *V, *scal; };

@@ -1,0 +1,498 @@
+// ssm_smooth.hip — the exact per-source posterior of an SGPRSS window in O(N) by a Kalman filter and a Bryson-Frazier (de Jong)
+// backward pass (gfx950, float64 throughout).  Beside gpitch/sgpr_ss.py:73-114 (the N x N exact posterior this computes
+// without the N x N matrix) and sample.hip (the state-space form of the Matern-1/2 families it rests on).
+//
+// Every kernel of the sum must be Matern12, MercerMatern12sm or Matern12sm.  Such a source is
+//   f_p(t) = sum_k sqrt(e_k) [a_k(t) cos 2 pi f_k t + b_k(t) sin 2 pi f_k t],   a_k, b_k independent OU(variance v_p, lengthscale l_p)
+// (Matern12: one OU process observed through 1), so y_t = sum_p f_p(t) + noise is a linear-Gaussian state-space model with
+// state x in R^d, d = sum_p c_p (c_p = 1 or 2 m_p; the sources' blocks in kern_list order, (a_0, b_0, a_1, b_1, ...) inside
+// a mixture), diagonal transition, scalar time-varying observation row h_j and a stationary start P_0 = diag(v).
+//
+// Timeline: `order` lists the steps in ascending time, entry < N the training frame X[entry] (an observed step), entry >= N
+// the new frame Xnew[entry - N] (unobserved); out_step[i] is the step of new frame i (a new frame bit-equal to a training
+// frame shares its step).  Per step j and coordinate i of source p, D_j = t_j - t_(j-1) >= 0:
+//   phi_j[i] = exp(-D_j / l_p),   q_j[i] = v_p (-expm1(-2 D_j / l_p))          (exactly 1 and 0 at D = 0 and at j = 0)
+//   h_j[i]   = 1 | sqrt(e_k) cos 2 pi f_k t_j | sqrt(e_k) sin 2 pi f_k t_j      (the feature kernel of cov.hip on t)
+// Forward (a = 0, P = diag(v)):  a <- phi a;  P <- phi P phi + diag(q);  keep a^-, P^-;  observed: g = P h, F = h.g + s2,
+//   e = y - h.a, a <- a + g e / F, P <- P - g g^T / F; keep g, e, F.   loglik = -1/2 sum_obs (log(2 pi F) + e^2 / F)
+// Backward (r = 0, Nm = 0 behind the last step):  r <- phi_(j+1) r;  Nm <- phi_(j+1) Nm phi_(j+1);  observed: k = g / F, u = Nm k,
+//   Nm <- Nm - h u^T - u h^T + h h^T (k.u + 1/F),  r <- r - h (k.r) + h e / F;   s = a^- + P^- r;  per source p with
+//   w_p = P^- h_p (h_p = h with the other sources' coordinates zeroed):  mean_p = h_p.s,  var_p = h_p.w_p - w_p^T Nm w_p.
+//
+// Launches per call (all windows of the call in each):
+//   1. ssms_times_kernel       t_j and y_j of every step in walk order
+//   2. sm_features_kernel      cov.hip's feature tables of the merged times, one launch per spectral-mixture source
+//   3. ssms_rows_kernel        h_j as rows [steps][d], phi and q as [steps][P]: no exp, sin or cos is left for the walks
+//   4. ssms_forward_kernel     one workgroup of DP = 64 (d <= 64: one wavefront) or 128 (d <= 128: two) threads per window; thread
+//                              i holds row i of P in registers (DP doubles), h, phi and g are broadcast through LDS, F and e
+//                              are one butterfly (+ one LDS exchange between the two wavefronts).  The history a^-, g, e, F
+//                              and P^- (d^2 doubles per step, stored transposed so that a wavefront's stores are contiguous)
+//                              goes to the workspace.
+//   5. ssms_backward_kernel    the same shape with row i of Nm in registers; P^- comes back once per wanted step (thread i reads
+//                              its own row, contiguous across the wavefront), a source's block of columns at a time with
+//                              SSMS_BATCH loads in flight.  A source's w_p goes through LDS.
+//   6. ssms_loglik_kernel      the sum over the observed steps in a fixed order (the walk carries no log)
+//   7. ssms_gather_kernel      mean / var [P][n] through out_step
+// Determinism: no atomics, every sum in a fixed order; a window is one workgroup and reads nothing of the others', so its
+// result is bit-identical between calls and whatever shares the launch.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+
+#define SSMS_MAX_D 128
+// columns of P^- the backward walk fetches at a time: 32 with two wavefronts (a mixture of up to 16 partials in one fetch), 4 with
+// one (measured: 32.9 - 35.8 ms per N = 2001, d = 60 window against 38.8 ms with 32)
+#define SSMS_BATCH (DP == 64 ? 4 : 32)
+
+// one per window: what the kernels of a call read
+struct SsmsWin {
+  const double* params; const double* X; const double* Y; const double* xnew;
+  const int* order; const int* want; const int* ostep;
+  double *t, *ys, *feat, *hrow, *phi, *q;          // prologue
+  double *am, *g, *ef, *Pm;                        // history: a^- [steps][d], g [steps][d], (e, F) [steps][2], P^- [steps][d][d]
+  double *smean, *svar;                            // [P][steps]
+  double *mean, *var, *loglik;                     // the caller's
+  int steps, hist;                                 // hist: the backward pass will run (n > 0)
+};
+// the structure of the state, shared by the windows of a call
+struct SsmsMeta {
+  int d, P, N, n;
+  int coff[SSMS_MAX_D + 1];                        // first coordinate of source p; coff[P] = d
+  int toff[SSMS_MAX_D];                            // source p's theta within a parameter row
+  int crow[SSMS_MAX_D];                            // coordinate i's row among the window's feature rows, -1: h = 1 (Matern12)
+  int csrc[SSMS_MAX_D];                            // coordinate i's source
+};
+
+static inline bool ssms_kernel_ok(int type) {
+  return type == GP_KERN_MATERN12 || type == GP_KERN_MERCER_MATERN12SM || type == GP_KERN_MATERN12SM;
+}
+
+// ---- 1. ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ssms_times_kernel(const SsmsWin* __restrict__ wins, int N) {
+  const SsmsWin w = wins[blockIdx.y];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= w.steps) return;
+  const int o = w.order[j];
+  w.t[j] = o < N ? w.X[o] : w.xnew[o - N];
+  w.ys[j] = o < N ? w.Y[o] : 0.0;
+}
+
+// ---- 3. ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ssms_rows_kernel(const SsmsWin* __restrict__ wins, const SsmsMeta* __restrict__ mt) {
+  const SsmsWin w = wins[blockIdx.y];
+  const int d = mt->d, np = mt->P;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t j = e / d;
+  const int i = (int)(e % d);
+  if (j >= (size_t)w.steps) return;
+  const int r = mt->crow[i];
+  w.hrow[j * d + i] = r < 0 ? 1.0 : w.feat[(size_t)r * w.steps + j];
+  if (i < np) {                                    // (P <= d: every source has a coordinate)
+    const double* th = w.params + mt->toff[i];
+    const double dt = j > 0 ? fmax(w.t[j] - w.t[j - 1], 0.0) : 0.0;
+    const double dl = dt / th[1];
+    w.phi[j * np + i] = exp(-dl);
+    w.q[j * np + i] = th[0] * (-expm1(-2.0 * dl));
+  }
+}
+
+// the sum of x and of y over a wavefront, the same bits in every lane (a + b = b + a at every level of the butterfly)
+__device__ __forceinline__ void ssms_wave_sum2(double& x, double& y) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { x += __shfl_xor(x, o, 64); y += __shfl_xor(y, o, 64); }
+}
+__device__ __forceinline__ void ssms_wave_sum(double& x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+}
+// sum_k row[k] * b[k] over the DP registers of a row, b broadcast from LDS: four chains, added in a fixed order
+template <int DP>
+__device__ __forceinline__ double ssms_row_dot(const double (&row)[DP], const double* b) {
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+  for (int k = 0; k < DP; k += 4) {
+    a0 = fma(row[k], b[k], a0); a1 = fma(row[k + 1], b[k + 1], a1);
+    a2 = fma(row[k + 2], b[k + 2], a2); a3 = fma(row[k + 3], b[k + 3], a3);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+// ---- 4. forward: one workgroup of DP threads per window, thread i = row i of P ------------------------------------------------
+// Lanes i >= d and columns k >= d carry zeros throughout (h = phi = q = v = 0 there).  The values of step j + 1 are loaded while
+// step j is computed.  Barriers: hb / pb alternate between two buffers, so a step's reads end before the buffer is written
+// again two steps later (the barrier of the step between lies in every thread's way); gb and red are written behind the
+// step's first barrier and read behind its second.
+template <int DP>
+__global__ void __launch_bounds__(DP) ssms_forward_kernel(const SsmsWin* __restrict__ wins, const SsmsMeta* __restrict__ mt) {
+  constexpr int NW = DP / 64;
+  __shared__ double hb[2][DP], pb[2][DP], gb[DP], red[NW][2];
+  const SsmsWin w = wins[blockIdx.x];
+  const int i = threadIdx.x, d = mt->d, N = mt->N, np = mt->P, steps = w.steps;
+  const bool on = i < d;
+  const int src = on ? mt->csrc[i] : 0;
+  const double s2 = w.params[0];
+  const double vi = on ? w.params[mt->toff[src]] : 0.0;
+  const size_t dd = (size_t)d * d;
+  double P[DP];
+#pragma unroll
+  for (int k = 0; k < DP; k++) P[k] = (k == i) ? vi : 0.0;
+  double a = 0.0;
+  double hn = on ? w.hrow[i] : 0.0, pn = on ? w.phi[src] : 0.0, qn = on ? w.q[src] : 0.0, yn = w.ys[0];
+  int on_ = w.order[0];
+  for (int j = 0; j < steps; j++) {
+    const int b = j & 1;
+    const double hh = hn, ph = pn, qq = qn, y = yn;
+    const int o = on_;
+    if (j + 1 < steps) {
+      const size_t j1 = (size_t)j + 1;
+      hn = on ? w.hrow[j1 * d + i] : 0.0;
+      pn = on ? w.phi[j1 * np + src] : 0.0;
+      qn = on ? w.q[j1 * np + src] : 0.0;
+      yn = w.ys[j1];
+      on_ = w.order[j1];
+    }
+    hb[b][i] = hh; pb[b][i] = ph;
+    __syncthreads();
+    a *= ph;
+#pragma unroll
+    for (int k = 0; k < DP; k++) P[k] = fma(ph * pb[b][k], P[k], (k == i) ? qq : 0.0);
+    if (w.hist && on) {
+      w.am[(size_t)j * d + i] = a;
+      double* dst = w.Pm + (size_t)j * dd + i;     // P^- transposed: element (row i, column k) at [k][i]
+#pragma unroll
+      for (int k = 0; k < DP; k++)
+        if (k < d) dst[(size_t)k * d] = P[k];
+    }
+    if (o < N) {                                   // observed (the same for the whole workgroup)
+      const double g = ssms_row_dot<DP>(P, hb[b]);
+      double x1 = hh * g, x2 = hh * a;
+      ssms_wave_sum2(x1, x2);
+      if (NW > 1 && (i & 63) == 0) { red[i >> 6][0] = x1; red[i >> 6][1] = x2; }
+      gb[i] = g;
+      __syncthreads();
+      if (NW > 1) { x1 = red[0][0] + red[NW - 1][0]; x2 = red[0][1] + red[NW - 1][1]; }
+      const double F = x1 + s2, e = y - x2, c = 1.0 / F;
+      a = fma(g, e * c, a);
+#pragma unroll
+      for (int k = 0; k < DP; k++) P[k] = fma(-(g * gb[k]), c, P[k]);
+      if (on) w.g[(size_t)j * d + i] = g;
+      if (i == 0) { w.ef[2 * (size_t)j] = e; w.ef[2 * (size_t)j + 1] = F; }
+    }
+  }
+}
+
+// ---- 5. backward: thread i = row i of Nm -------------------------------------------------------------------------------------
+// Barriers as in the forward walk: hb / pb alternate; kb, ub, rb, mb, red and outv are each written once per step behind the
+// step's first barrier and read behind a later one of the same step; wb alternates between two buffers along the sources.
+template <int DP>
+__global__ void __launch_bounds__(DP) ssms_backward_kernel(const SsmsWin* __restrict__ wins, const SsmsMeta* __restrict__ mt) {
+  constexpr int NW = DP / 64;
+  __shared__ double hb[2][DP], pb[2][DP], kb[DP], ub[DP], rb[DP], mb[DP], wb[2][DP], outv[NW][SSMS_MAX_D], red[NW][2];
+  const SsmsWin w = wins[blockIdx.x];
+  const int i = threadIdx.x, d = mt->d, N = mt->N, np = mt->P, steps = w.steps;
+  const bool on = i < d;
+  const int src = on ? mt->csrc[i] : 0;
+  const size_t dd = (size_t)d * d;
+  double Nm[DP];
+#pragma unroll
+  for (int k = 0; k < DP; k++) Nm[k] = 0.0;
+  double r = 0.0;
+  // the values of step j - 1 are loaded while step j is computed; `pn` is phi of the step above (the transition into step j)
+  int j = steps - 1;
+  double hn = on ? w.hrow[(size_t)j * d + i] : 0.0, pn = 1.0, an = on ? w.am[(size_t)j * d + i] : 0.0;
+  int on_ = w.order[j], wn = w.want[j];
+  double gn = (on && on_ < N) ? w.g[(size_t)j * d + i] : 0.0;
+  double en = on_ < N ? w.ef[2 * (size_t)j] : 0.0, Fn = on_ < N ? w.ef[2 * (size_t)j + 1] : 1.0;
+  for (; j >= 0; j--) {
+    const int b = j & 1;
+    const double hh = hn, ph = pn, am = an, g = gn, e = en, F = Fn;
+    const int o = on_, want = wn;
+    if (j > 0) {
+      const size_t j1 = (size_t)j - 1;
+      hn = on ? w.hrow[j1 * d + i] : 0.0;
+      pn = on ? w.phi[(size_t)j * np + src] : 0.0;
+      an = on ? w.am[j1 * d + i] : 0.0;
+      on_ = w.order[j1]; wn = w.want[j1];
+      gn = (on && on_ < N) ? w.g[j1 * d + i] : 0.0;
+      en = on_ < N ? w.ef[2 * j1] : 0.0; Fn = on_ < N ? w.ef[2 * j1 + 1] : 1.0;
+    }
+    hb[b][i] = hh; pb[b][i] = ph;
+    const double* __restrict__ Pj = w.Pm + (size_t)j * dd + i;
+    __syncthreads();
+    r *= ph;
+#pragma unroll
+    for (int k = 0; k < DP; k++) Nm[k] = (ph * pb[b][k]) * Nm[k];
+    if (o < N) {
+      const double c = 1.0 / F, kk = g * c;
+      kb[i] = kk;
+      __syncthreads();
+      const double u = ssms_row_dot<DP>(Nm, kb);
+      double x1 = kk * u, x2 = kk * r;
+      ssms_wave_sum2(x1, x2);
+      if (NW > 1 && (i & 63) == 0) { red[i >> 6][0] = x1; red[i >> 6][1] = x2; }
+      ub[i] = u;
+      __syncthreads();
+      if (NW > 1) { x1 = red[0][0] + red[NW - 1][0]; x2 = red[0][1] + red[NW - 1][1]; }
+      const double cc = x1 + c;
+#pragma unroll
+      for (int k = 0; k < DP; k++) Nm[k] += fma(hh, fma(hb[b][k], cc, -ub[k]), -(u * hb[b][k]));
+      r = fma(hh, e * c - x2, r);
+    }
+    if (want) {
+      rb[i] = r;
+      __syncthreads();
+      double sacc = 0.0;
+      for (int p = 0; p < np; p++) {
+        const int k0 = mt->coff[p], k1 = mt->coff[p + 1];
+        double wp = 0.0;
+        if (on) {                                  // the source's columns of the row, SSMS_BATCH loads in flight at a time
+          for (int kb0 = k0; kb0 < k1; kb0 += SSMS_BATCH) {
+            double pv[SSMS_BATCH];
+#pragma unroll
+            for (int c = 0; c < SSMS_BATCH; c++) pv[c] = kb0 + c < k1 ? Pj[(size_t)(kb0 + c) * d] : 0.0;
+#pragma unroll
+            for (int c = 0; c < SSMS_BATCH; c++) {
+              const int k = kb0 + c < k1 ? kb0 + c : k0;       // (a column past the block: its pv is 0, the index stays inside)
+              sacc = fma(pv[c], rb[k], sacc);
+              wp = fma(pv[c], hb[b][k], wp);
+            }
+          }
+        }
+        wb[p & 1][i] = wp;
+        __syncthreads();
+        const double v = ssms_row_dot<DP>(Nm, wb[p & 1]);
+        double vp = wp * (((i >= k0 && i < k1) ? hh : 0.0) - v);
+        ssms_wave_sum(vp);
+        if ((i & 63) == 0) outv[i >> 6][p] = vp;
+      }
+      mb[i] = hh * (am + sacc);
+      __syncthreads();
+      if (i < np) {
+        double m = 0.0;
+        for (int k = mt->coff[i]; k < mt->coff[i + 1]; k++) m += mb[k];
+        w.smean[(size_t)i * steps + j] = m;
+        w.svar[(size_t)i * steps + j] = NW > 1 ? outv[0][i] + outv[NW - 1][i] : outv[0][i];
+      }
+    }
+  }
+}
+
+// ---- 6. loglik = -1/2 sum over the observed steps of log(2 pi F) + e^2 / F; one workgroup per window -------------------------
+__global__ void __launch_bounds__(256) ssms_loglik_kernel(const SsmsWin* __restrict__ wins, int N) {
+  __shared__ double red[256];
+  const SsmsWin w = wins[blockIdx.x];
+  double a = 0.0;
+  for (int j = threadIdx.x; j < w.steps; j += 256)
+    if (w.order[j] < N) {
+      const double e = w.ef[2 * (size_t)j], F = w.ef[2 * (size_t)j + 1];
+      a += log(6.283185307179586 * F) + e * e / F;
+    }
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) w.loglik[0] = -0.5 * red[0];
+}
+
+// ---- 7. new frames i0 .. i0 + cnt - 1 of every window through out_step (ostep holds that slice) ------------------------------
+__global__ void __launch_bounds__(256) ssms_gather_kernel(const SsmsWin* __restrict__ wins, int np, int n, int i0, int cnt) {
+  const SsmsWin w = wins[blockIdx.z];
+  const int p = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cnt) return;
+  const int s = w.ostep[c];
+  w.mean[(size_t)p * n + i0 + c] = w.smean[(size_t)p * w.steps + s];
+  w.var[(size_t)p * n + i0 + c] = w.svar[(size_t)p * w.steps + s];
+}
+
+// ==== host ===================================================================================================================
+struct SsmsDesc { size_t wins, meta, feat, bytes; };
+static SsmsDesc ssms_desc_layout(size_t count, size_t P) {
+  SsmsDesc o;
+  GpRegions region;
+  o.wins = region(count * sizeof(SsmsWin));
+  o.meta = region(sizeof(SsmsMeta));
+  o.feat = region(count * P * sizeof(FeatItem));
+  o.bytes = region.off;
+  return o;
+}
+// the operator's one carve; every per-window block has the size of the longest timeline (`steps`).  Feature tables: a
+// mixture of m partials takes 2 sm_mpad(m) <= c_p + 6 rows, so d + 6 P rows cover a window
+struct SsmsBufs { char* desc; int *order, *want, *ostep; double *t, *ys, *feat, *hrow, *phi, *q, *am, *g, *ef, *smean, *svar, *Pm; };
+static SsmsBufs ssms_carve(GpArena& ar, size_t d, size_t steps, size_t P, size_t count) {
+  SsmsBufs b;
+  b.desc = ar.take<char>(ssms_desc_layout(count, P).bytes);
+  b.order = ar.take<int>(count * steps);
+  b.want = ar.take<int>(count * steps);
+  b.ostep = ar.take<int>(count * steps);
+  b.t = ar.take<double>(count * steps);
+  b.ys = ar.take<double>(count * steps);
+  b.feat = ar.take<double>(count * (d + 6 * P) * steps);
+  b.hrow = ar.take<double>(count * steps * d);
+  b.phi = ar.take<double>(count * steps * P);
+  b.q = ar.take<double>(count * steps * P);
+  b.am = ar.take<double>(count * steps * d);
+  b.g = ar.take<double>(count * steps * d);
+  b.ef = ar.take<double>(count * steps * 2);
+  b.smean = ar.take<double>(count * steps * P);
+  b.svar = ar.take<double>(count * steps * P);
+  b.Pm = ar.take<double>(count * steps * d * d);
+  return b;
+}
+
+size_t ssm_smooth_workspace_bytes(int d, int steps, int P, int count) {
+  if (d < 1 || d > SSMS_MAX_D || steps < 1 || P < 1 || P > d || count < 1) return 0;
+  return gp_measure([&](GpArena& ar) { ssms_carve(ar, d, steps, P, count); }) + GP_WS_TAIL_OP;
+}
+
+// Every check, then the launches.  Windows w < count: params + w * param_stride, X / Y + w * N, Xnew + w * n, order_host
+// + w * (N + n) (the first steps_host[w] entries), out_step_host + w * n, mean / var + w * P * n, loglik + w.
+gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
+                         double* var, double* loglik, void* ws, size_t ws_bytes) {
+  if (!params || !X || !Y || !order_host || !steps_host || !loglik || !ws || N < 1 || n < 0 || count < 1 || P < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: bad argument (N >= 1, n >= 0, no null pointers)");
+  if (n > 0 && (!Xnew || !out_step_host || !mean || !var))
+    return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: Xnew, out_step, mean and var may be null only with n = 0");
+  int d = 0;
+  for (int i = 0; i < P; i++) {
+    if (!ssms_kernel_ok(ktype[i]))
+      return gp_fail(h, GP_ERR_UNSUPPORTED,
+                     "state-space smoother: every kernel of the sum must have a Matern-1/2 envelope (MercerMatern12sm, Matern12sm, "
+                     "Matern12)");
+    if (ktype[i] != GP_KERN_MATERN12 && (km[i] < 1 || km[i] > 32))
+      return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space smoother: num_partials must be in [1, 32]");
+    d += ktype[i] == GP_KERN_MATERN12 ? 1 : 2 * km[i];
+    if (d > SSMS_MAX_D)
+      return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space smoother: the state dimension d = sum of the sources' components must be in [1, 128]");
+  }
+  if ((int64_t)N + n > INT32_MAX / 2) return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space smoother: N + n too large");
+  if ((int64_t)count * P > 65535 || count > 65535)
+    return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space smoother: at most 65535 (window, source) pairs per call");
+  int steps = 0;
+  for (int w = 0; w < count; w++) {
+    if (steps_host[w] < N || steps_host[w] > N + n)
+      return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: steps must be in [N, N + n]");
+    steps = std::max(steps, (int)steps_host[w]);
+  }
+  if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_smooth_workspace_bytes(d, steps, P, count))
+    return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small for steps * d^2 doubles of history per window "
+                                      "(gp_ssm_smooth_workspace_bytes) or not 256-byte aligned");
+  // `order` and `out_step` become device addresses
+  std::vector<int> want((size_t)count * steps, 0);
+  {
+    std::vector<char> seen;
+    for (int w = 0; w < count; w++) {
+      const int32_t* o = order_host + (size_t)w * (N + n);
+      const int sw = steps_host[w];
+      seen.assign((size_t)N + n, 0);
+      int train = 0;
+      for (int j = 0; j < sw; j++) {
+        if (o[j] < 0 || o[j] >= N + n || seen[o[j]])
+          return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: order is not a permutation (every training frame once, no "
+                                            "frame twice, entries in [0, N + n))");
+        seen[o[j]] = 1;
+        train += o[j] < N;
+      }
+      if (train != N)
+        return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: order is not a permutation (every training frame once, no frame "
+                                          "twice, entries in [0, N + n))");
+      for (int i = 0; i < n; i++) {
+        const int s = out_step_host[(size_t)w * n + i];
+        if (s < 0 || s >= sw) return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: out_step out of range [0, steps)");
+        want[(size_t)w * steps + s] = 1;
+      }
+    }
+  }
+  GpArena ar(ws, ws_bytes);
+  const SsmsBufs b = ssms_carve(ar, d, steps, P, count);
+  if (!ar.ok) return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small");
+  const SsmsDesc lay = ssms_desc_layout(count, P);
+  std::vector<char> hd(lay.bytes, 0);
+  SsmsWin* wins = (SsmsWin*)(hd.data() + lay.wins);
+  SsmsMeta* mt = (SsmsMeta*)(hd.data() + lay.meta);
+  FeatItem* feats = (FeatItem*)(hd.data() + lay.feat);
+  mt->d = d; mt->P = P; mt->N = N; mt->n = n;
+  std::vector<int> foff(P), mpad(P);
+  {
+    int c = 0, row = 0;
+    for (int p = 0; p < P; p++) {
+      mt->coff[p] = c; mt->toff[p] = (int)off_theta[p];
+      const bool sm = ktype[p] != GP_KERN_MATERN12;
+      mpad[p] = sm ? sm_mpad(km[p]) : 0;
+      foff[p] = row;
+      const int cp = sm ? 2 * km[p] : 1;
+      for (int q = 0; q < cp; q++) {
+        mt->csrc[c + q] = p;
+        mt->crow[c + q] = sm ? row + ((q & 1) ? mpad[p] + (q >> 1) : (q >> 1)) : -1;    // (a_0, b_0, a_1, b_1, ...)
+      }
+      c += cp; row += 2 * mpad[p];
+    }
+    mt->coff[P] = c;
+  }
+  const size_t frows = (size_t)d + 6 * (size_t)P;
+  std::vector<int> order_dev((size_t)count * steps, 0);
+  for (int w = 0; w < count; w++) {
+    SsmsWin& sw = wins[w];
+    const size_t s0 = (size_t)w * steps;
+    sw.params = params + (size_t)w * param_stride; sw.X = X + (size_t)w * N; sw.Y = Y + (size_t)w * N;
+    sw.xnew = n > 0 ? Xnew + (size_t)w * n : nullptr;
+    sw.order = b.order + s0; sw.want = b.want + s0; sw.ostep = b.ostep + s0;
+    sw.t = b.t + s0; sw.ys = b.ys + s0; sw.feat = b.feat + s0 * frows; sw.hrow = b.hrow + s0 * d;
+    sw.phi = b.phi + s0 * P; sw.q = b.q + s0 * P; sw.am = b.am + s0 * d; sw.g = b.g + s0 * d; sw.ef = b.ef + s0 * 2;
+    sw.Pm = b.Pm + s0 * d * d; sw.smean = b.smean + s0 * P; sw.svar = b.svar + s0 * P;
+    sw.mean = n > 0 ? mean + (size_t)w * P * n : nullptr; sw.var = n > 0 ? var + (size_t)w * P * n : nullptr;
+    sw.loglik = loglik + w;
+    sw.steps = steps_host[w]; sw.hist = n > 0;
+    memcpy(order_dev.data() + s0, order_host + (size_t)w * (N + n), (size_t)sw.steps * sizeof(int));
+    for (int p = 0; p < P; p++)
+      feats[(size_t)p * count + w] = FeatItem{DevKern{ktype[p], km[p], sw.params + off_theta[p]}, sw.t,
+                                              sw.feat + (size_t)foff[p] * sw.steps, sw.steps, 0};
+  }
+  GP_HIP_CHECK(h, hipMemcpyAsync(b.desc, hd.data(), lay.bytes, hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(b.order, order_dev.data(), order_dev.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipMemcpyAsync(b.want, want.data(), want.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // the three are host vectors
+  const SsmsWin* d_wins = (const SsmsWin*)(b.desc + lay.wins);
+  const SsmsMeta* d_meta = (const SsmsMeta*)(b.desc + lay.meta);
+  const FeatItem* d_feat = (const FeatItem*)(b.desc + lay.feat);
+  hipLaunchKernelGGL(ssms_times_kernel, dim3((steps + 255) / 256, count), dim3(256), 0, h->stream, d_wins, N);
+  GP_HIP_CHECK(h, hipGetLastError());
+  for (int p = 0; p < P; p++)
+    if (mpad[p]) GP_CHECK(launch_sm_features_items(h, d_feat + (size_t)p * count, count, steps, mpad[p], nullptr, 0));
+  hipLaunchKernelGGL(ssms_rows_kernel, dim3((unsigned)(((size_t)steps * d + 255) / 256), count), dim3(256), 0, h->stream, d_wins,
+                     d_meta);
+  GP_HIP_CHECK(h, hipGetLastError());
+  const bool narrow = d <= 64 && !gp_switches().ssm_wide;
+  if (narrow) hipLaunchKernelGGL(ssms_forward_kernel<64>, dim3(count), dim3(64), 0, h->stream, d_wins, d_meta);
+  else hipLaunchKernelGGL(ssms_forward_kernel<128>, dim3(count), dim3(128), 0, h->stream, d_wins, d_meta);
+  GP_HIP_CHECK(h, hipGetLastError());
+  hipLaunchKernelGGL(ssms_loglik_kernel, dim3(count), dim3(256), 0, h->stream, d_wins, N);
+  GP_HIP_CHECK(h, hipGetLastError());
+  if (n > 0) {
+    if (narrow) hipLaunchKernelGGL(ssms_backward_kernel<64>, dim3(count), dim3(64), 0, h->stream, d_wins, d_meta);
+    else hipLaunchKernelGGL(ssms_backward_kernel<128>, dim3(count), dim3(128), 0, h->stream, d_wins, d_meta);
+    GP_HIP_CHECK(h, hipGetLastError());
+    // out_step goes through a staging area of `steps` entries per window: new frames may outnumber the steps (repeated frames)
+    std::vector<int> stage((size_t)count * steps);
+    for (int i0 = 0; i0 < n; i0 += steps) {
+      const int cnt = std::min(steps, n - i0);
+      for (int w = 0; w < count; w++)
+        memcpy(stage.data() + (size_t)w * steps, out_step_host + (size_t)w * n + i0, (size_t)cnt * sizeof(int));
+      GP_HIP_CHECK(h, hipMemcpyAsync(b.ostep, stage.data(), stage.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+      hipLaunchKernelGGL(ssms_gather_kernel, dim3((cnt + 255) / 256, P, count), dim3(256), 0, h->stream, d_wins, P, n, i0, cnt);
+      GP_HIP_CHECK(h, hipGetLastError());
+    }
+  }
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return GP_OK;
+}
+
+extern "C" size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count) {
+  return ssm_smooth_workspace_bytes(d, steps, P, count);
+}

@@ -37,15 +37,16 @@ def _kern_codes(kern_list):
     return [(int(k[0]), int(k[1])) if isinstance(k, (tuple, list)) else (int(k.type_code), int(k.num_partials)) for k in kl]
 
 
-def sample_components(kern_list):
+def sample_components(kern_list, who="sample_s_sparse", what="joint draws need"):
     """Ornstein-Uhlenbeck components per source for sample_s_sparse: 2 m for a Matern-1/2 spectral mixture of m partials
     (a_k and b_k of every partial), 1 for Matern12.  Raises NotImplementedError, naming the kernel, for a sum that holds a
-    kernel without a Matern-1/2 envelope: only those have the exact first-order prior sampler."""
+    kernel without a Matern-1/2 envelope: only those have the exact first-order prior sampler.  (`who`, `what`: the caller
+    and its need, for the message: the state-space smoother asks the same question.)"""
     comps = []
     for i, (code, m) in enumerate(_kern_codes(kern_list)):
         if code not in _SAMPLE_KERNS:
-            raise NotImplementedError("sample_s_sparse: kernel %d of the sum is %s; joint draws need a Matern-1/2 envelope "
-                                      "(supported: %s)" % (i, _KERN_NAMES.get(code, "type %d" % code),
+            raise NotImplementedError("%s: kernel %d of the sum is %s; %s a Matern-1/2 envelope "
+                                      "(supported: %s)" % (who, i, _KERN_NAMES.get(code, "type %d" % code), what,
                                                            ", ".join(_KERN_NAMES[c] for c in _SAMPLE_KERNS)))
         comps.append(1 if code == _lib.KERN_MATERN12 else 2 * m)
     return comps
@@ -65,6 +66,56 @@ def merged_order(xnew, z):
     Ties keep the caller's order (a frame that coincides with an inducing input comes first)."""
     t = np.concatenate([np.asarray(xnew, dtype=np.float64).reshape(-1), np.asarray(z, dtype=np.float64).reshape(-1)])
     return np.argsort(t, kind="stable").astype(np.int32)
+
+
+# ---- the exact posterior by the state-space smoother (csrc/ssm_smooth.hip): host-only helpers, no device work ----
+SSM_MAX_D = 128
+# the forward walk's history (steps * d^2 doubles per window and a little more) of one library call stays below this many
+# bytes: a batch of windows is cut into chunks, which changes no bit of any window's result
+MAX_SSM_BYTES = 32 << 30
+
+
+def ssm_state_dim(kern_list, who="predict_s_ssm"):
+    """(d, P) of the state-space model of a kernel sum: d = the sum of sample_components.  Raises NotImplementedError
+    naming the kernel and its index for a kernel without the Ornstein-Uhlenbeck form, and naming d for d > SSM_MAX_D."""
+    comps = sample_components(kern_list, who, "the state-space smoother needs")
+    d = int(sum(comps))
+    if d > SSM_MAX_D:
+        raise NotImplementedError("%s: the state dimension d = %d (the sources' components: %s) exceeds %d"
+                                  % (who, d, comps, SSM_MAX_D))
+    return d, len(comps)
+
+
+def ssm_timeline(X, Xnew):
+    """The smoother's timeline (order, out_step, steps), int32 / int32 / int: the N training frames in stable ascending
+    order with, merged in, every distinct value of Xnew that is not bit-equal to a training frame.  order[j] < N is training
+    frame X[order[j]] (an observed step), order[j] >= N new frame Xnew[order[j] - N] (the first with that value);
+    out_step[i] is the step of new frame i.  A new frame bit-equal to a training frame shares that frame's step (the first of
+    them, should the training frame repeat); duplicate training frames stay separate steps; a tie between a training frame
+    and a new one that is equal but not bit-equal (0.0 and -0.0) keeps the training frame first."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(-1))
+    Xnew = np.ascontiguousarray(np.asarray(Xnew, dtype=np.float64).reshape(-1))
+    N, n = X.size, Xnew.size
+    if n == 0:
+        return np.argsort(X, kind="stable").astype(np.int32), np.zeros(0, dtype=np.int32), N
+    xb, nb = X.view(np.int64), Xnew.view(np.int64)
+    ub, first, inv = np.unique(nb, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    fresh = ~np.isin(ub, xb)                               # distinct new values that are no training frame
+    reps = first[fresh]                                    # their first occurrence in Xnew
+    t = np.concatenate([X, Xnew[reps]])
+    ids = np.concatenate([np.arange(N), N + reps])
+    order = ids[np.argsort(t, kind="stable")].astype(np.int32)
+    steps = order.size
+    step_of = np.full(N + n, -1, dtype=np.int64)
+    step_of[order] = np.arange(steps)
+    ustep = np.empty(ub.size, dtype=np.int64)              # the step of every distinct new value
+    ustep[fresh] = step_of[N + reps]
+    if (~fresh).any():
+        tr = order[order < N]                              # training frames in step order
+        tb, tfirst = np.unique(xb[tr], return_index=True)  # a value's first training frame along the timeline
+        ustep[~fresh] = step_of[tr[tfirst[np.searchsorted(tb, ub[~fresh])]]]
+    return order, ustep[inv].astype(np.int32), int(steps)
 
 
 def _sample_chunk(num_samples, doubles_per_sample):
@@ -415,6 +466,60 @@ class SGPRSS(Parameterized):
             m[:, :, d] = mean.cpu().numpy()
         v = var.cpu().numpy()
         return [m[i] for i in range(P)], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(P)]
+
+    def _ssm_call(self, Xnew, who):
+        """the smoother on every output column: (means (P, n, D), variances (P, n), log-likelihoods (D,))"""
+        if self._shard:
+            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        kl = self.kern.kern_list
+        d, P = ssm_state_dim(kl, who)                 # raises for an unsupported kernel or d, before any device work
+        Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        n, N, D = Xnew.size, self.X.shape[0], self.num_latent
+        order, out_step, steps = ssm_timeline(self.X._array, Xnew)
+        order, out_step = np.ascontiguousarray(order), np.ascontiguousarray(out_step)
+        self._compile()
+        self._pack()
+        h = self._handle
+        xs = h.to_device(Xnew) if n else None
+        mean, var = (h.empty(P, n), h.empty(P, n)) if n else (None, None)
+        ll = h.empty(1)
+        ws = h.workspace(h.lib.gp_ssm_smooth_workspace_bytes(d, steps, P, 1))
+        m, lls = np.empty((P, n, D)), np.empty(D)
+        for c in self._columns():
+            h.check(h.lib.gp_sgpr_predict_source_ssm(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                     self._Yd.data_ptr(), N, xs.data_ptr() if n else None, n,
+                                                     order.ctypes.data, out_step.ctypes.data if n else None, steps,
+                                                     mean.data_ptr() if n else None, var.data_ptr() if n else None,
+                                                     ll.data_ptr(), ws.data_ptr(), ws.numel()))
+            if n:
+                m[:, :, c] = mean.cpu().numpy()
+            lls[c] = float(ll.cpu().numpy()[0])
+        return m, (var.cpu().numpy() if n else np.empty((P, 0))), lls
+
+    def predict_s_ssm(self, Xnew):
+        """The exact posterior of every source at Xnew: (list of P means (n, D), list of P variances (n, D)).
+
+        What predict_s computes (sgpr_ss.py:73-114), without its N x N factorisation: a sum of kernels with a Matern-1/2
+        envelope (Matern12, MercerMatern12sm, Matern12sm) is a linear-Gaussian state-space model of dimension d = the sum of
+        sample_components(kern), and a Kalman filter with a Bryson-Frazier backward pass (gp_sgpr_predict_source_ssm) gives
+        p(f_p | y) at every frame in O((N + n) d^2), for any N, with no inducing points (Z plays no part).  Conventions as
+        predict_s_sparse: the variance starts from the source's OWN k_p(x, x) where predict_s starts from the sum kernel's,
+        so svar of predict_s = this variance + (Kdiag_sum - Kdiag_p); the mean function is NOT added (the residual
+        Y - mean_function(X) is what is filtered); columns are looped, the variance computed once.  Exact for the idealised
+        kernels r = |x - x'|: predict_s's kernels carry the reference's 1e-12 under the square root, a first-order
+        difference that grows with 1 / noise variance (about 1e-6 of the mean at noise 0.01).  Xnew may lie on training frames,
+        between them or outside the window, in any order, with repeats.  NotImplementedError, before any device work, for a
+        kernel without the Ornstein-Uhlenbeck form (naming it and its index in the sum) and for d > 128 (naming d)."""
+        m, v, _ = self._ssm_call(Xnew, "predict_s_ssm")
+        D = self.num_latent
+        return [m[i] for i in range(m.shape[0])], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(v.shape[0])]
+
+    def exact_log_likelihood(self):
+        """log p(Y | parameters) of the exact GP (the quantity the collapsed bound of build_likelihood lies below, at any
+        Z), from the forward walk of the smoother alone: the sum over the D columns, the mean function subtracted.  Exact
+        for the idealised kernels r = |x - x'|, so it differs from a dense evaluation with the reference's kernels (1e-12
+        under the square root) in about the fifth significant digit.  Same scope as predict_s_ssm."""
+        return float(self._ssm_call(np.zeros(0), "exact_log_likelihood")[2].sum())
 
     def sample_s_sparse(self, Xnew, num_samples=1, seed=None, eps=None):
         """Joint posterior draws of every source at Xnew under the q(u) of predict_s_sparse: a list of P arrays

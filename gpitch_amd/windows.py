@@ -263,6 +263,45 @@ class SgprWindowBatch(object):
                                                      var.data_ptr()))
         return mean.cpu().numpy(), var.cpu().numpy()
 
+    def predict_s_ssm(self, params_host, xnews=None, chunk=None, return_loglik=False):
+        """SGPRSS.predict_s_ssm (the exact per-source posteriors by the state-space smoother, gp_sgprb_predict_source_ssm) of
+        every loaded window: (mean, var), each (count, P, n) [, the exact log-likelihoods (count,)].  One workgroup per
+        window; `chunk` windows share a launch sequence (default: as many as keep the forward walk's history, steps * d^2
+        doubles per window, below sgpr_ss.MAX_SSM_BYTES).  Chunking changes no bit of any window's result.  Z, the windows'
+        inducing counts and the plan's precision play no part; n may exceed N."""
+        from . import sgpr_ss
+        h = self.h
+        cnt, N = self.count, self.N
+        codes = list(zip(self._keep[0], self._keep[1]))
+        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.predict_s_ssm")    # raises before any device work
+        xn, n = self._load_xnew(xnews, cnt)
+        xh = self.X[:cnt].cpu().numpy()
+        nh = xh if xnews is None else xn.cpu().numpy()
+        order = np.zeros((cnt, N + n), dtype=np.int32)
+        ostep = np.zeros((cnt, n), dtype=np.int32)
+        steps = np.zeros(cnt, dtype=np.int32)
+        for w in range(cnt):
+            o, s, k = sgpr_ss.ssm_timeline(xh[w], nh[w])
+            order[w, :k], ostep[w], steps[w] = o, s, k
+        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        smax = int(steps.max())
+        if chunk is None:
+            per = max(1, int(h.lib.gp_ssm_smooth_workspace_bytes(d, smax, P, 1)))
+            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // per)
+        chunk = int(max(1, min(int(chunk), cnt)))
+        ws = h.workspace(h.lib.gp_ssm_smooth_workspace_bytes(d, smax, P, chunk))
+        mean, var, ll = h.empty(cnt, P, n), h.empty(cnt, P, n), h.empty(cnt)
+        for b0 in range(0, cnt, chunk):
+            c = min(chunk, cnt - b0)
+            h.check(h.lib.gp_sgprb_predict_source_ssm(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
+                                                      self.Y[b0:].data_ptr(), xn[b0:].data_ptr(), n, c,
+                                                      order[b0:].ctypes.data, ostep[b0:].ctypes.data, steps[b0:].ctypes.data,
+                                                      mean[b0:].data_ptr(), var[b0:].data_ptr(), ll[b0:].data_ptr(),
+                                                      ws.data_ptr(), ws.numel()))
+        out = (mean.cpu().numpy(), var.cpu().numpy())
+        return out + (ll.cpu().numpy(),) if return_loglik else out
+
     def sample_s_sparse(self, params_host, xnews=None, num_samples=1, seed=None, eps=None):
         """SGPRSS.sample_s_sparse (joint posterior draws of every source, gp_sgprb_sample_source_sparse) of every loaded
         window from one launch sequence: (count, P, num_samples, n); ragged windows included.  eps=None: standard normals
@@ -362,7 +401,9 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     predict=True adds what SoSp.optimize computes after every window's optimisation (separation.py:300-313), batched the
     same way: "mean", "var" (predict_f at the window's frames, (N, 1)) and "smean", "svar" (predict_s: lists over the
     sources of (N, 1) arrays).  predict="sparse" is the same with "smean", "svar" from the sparse per-source posterior
-    (SGPRSS.predict_s_sparse: no N x N factorisation) instead of predict_s; `merge_sources` takes either.
+    (SGPRSS.predict_s_sparse: no N x N factorisation) instead of predict_s; predict="ssm" takes them from the state-space
+    smoother (SGPRSS.predict_s_ssm: predict_s's exact posterior without the N x N factorisation, the variance from the
+    source's own Kdiag; kernels with a Matern-1/2 envelope only).  `merge_sources` takes any of the three.
     Windows must share N; their inducing-point counts may differ (each window's Z from its own audio, as the drivers'
     init_liv picks it).  Windows of different counts are sorted by count and batched with their neighbours
     (`ragged_batches`), each batch on a plan sized by its largest count; plans are made when first needed and freed once no
@@ -385,9 +426,10 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     if not lbfgsb_batch.available():
         raise RuntimeError("fit_windows_batched needs scipy >= 1.15 (its reverse-communication L-BFGS-B routine); "
                            "use fit_windows")
-    if not (isinstance(predict, (bool, np.bool_)) or predict == "sparse"):
-        raise ValueError('fit_windows_batched: predict is False, True or "sparse"')
-    sparse = isinstance(predict, str)
+    if not (isinstance(predict, (bool, np.bool_)) or predict in ("sparse", "ssm")):
+        raise ValueError('fit_windows_batched: predict is False, True, "sparse" or "ssm"')
+    sparse = predict == "sparse" if isinstance(predict, str) else False
+    ssm = predict == "ssm" if isinstance(predict, str) else False
     mine = window_assignment(len(windows), world_size, rank)
     results = [None] * len(windows)
     if not mine:
@@ -418,6 +460,9 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                 hs.close()
     h = handle
     model = make_model(h)
+    if ssm:                                    # the smoother's scope, before any fitting
+        from .sgpr_ss import ssm_state_dim
+        ssm_state_dim(model.kern.kern_list, 'fit_windows_batched(predict="ssm")')
     init_vals = [p.value.copy() for p in model._param_list()]      # (the single-engine windows start from these)
     # what the batched plan takes from the template model: kernel structure, `reg`, the parameter values after ONE
     # reset() (on this rank's first window).  It does not carry a mean function or float32 strips: refuse, do not drop.
@@ -529,7 +574,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                 results[i].update(error=r.failed[q], bound=float("nan"))
         if predict:
             fm, fv = r.dev.predict_f(pfin)
-            sm, sv = r.dev.predict_s_sparse(pfin) if sparse else r.dev.predict_s(pfin)
+            sm, sv = r.dev.predict_s_sparse(pfin) if sparse else (r.dev.predict_s_ssm(pfin) if ssm else r.dev.predict_s(pfin))
             for q, i in enumerate(r.ids):
                 if q in r.failed:           # (predicted at the starting parameters only to keep the batch whole)
                     continue
@@ -576,7 +621,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                       "variances": pv[var_idx].copy(), "noise": float(pv[0]), "params": pv, "engine": "single"}
         if predict:
             m1, v1 = model.predict_f(x)
-            ms, vs = model.predict_s_sparse(x) if sparse else model.predict_s(x)
+            ms, vs = model.predict_s_sparse(x) if sparse else (model.predict_s_ssm(x) if ssm else model.predict_s(x))
             results[i].update(mean=m1, var=v1, smean=list(ms), svar=list(vs))
     model._destroy()
     return results

@@ -728,6 +728,39 @@ gp_status gp_sgpr_sample_source_sparse(gp_sgpr_plan p, const double* params, con
 /* handle-free, runs without a device: the one carve of the sampling operator (also the window-batched entry's), measured */
 size_t gp_sgpr_sample_source_workspace_bytes(int32_t M, int32_t P, int32_t C, int32_t n, int32_t S, int32_t count);
 
+/* The EXACT per-source posterior p(f_p | y) of sgpr_ss.py:73-114 in O(N d^2) instead of O(N^3), with no N x N array and no
+ * inducing points: every kernel of the sum must have a Matern-1/2 envelope (GP_KERN_MATERN12, GP_KERN_MERCER_MATERN12SM,
+ * GP_KERN_MATERN12SM; anything else: GP_ERR_UNSUPPORTED), so that y = sum_p f_p + noise is a linear-Gaussian state-space
+ * model of dimension d = sum_p c_p (c_p = 1 for Matern12, 2 m for a mixture of m partials; 1 <= d <= 128 and 1 <= m <= 32,
+ * GP_ERR_UNSUPPORTED otherwise).  A Kalman filter and a Bryson-Frazier backward pass (ssm_smooth.hip) give the smoothed mean
+ * and variance of every source at every new frame and the exact log marginal likelihood log p(y).  "Exact" is for the
+ * idealised kernels, r = |x - x'|: the covariance builds carry the reference's 1e-12 under the square root, so
+ * gp_sgpr_predict_source differs from this by that first-order effect times 1 / noise variance (DESIGN has the figures).
+ *   params       the plan's layout [noise variance | theta_0 | ...] (device); Z is not an argument and nothing of the plan's
+ *                state is read or changed: no forward pass of the bound runs
+ *   order_host   HOST, `steps` entries: the timeline in stable ascending order of time.  Entry < N is training frame X[entry]
+ *                (an observed step), entry >= N is new frame Xnew[entry - N].  The N training frames all appear, once each;
+ *                a new frame that is bit-equal to a training frame, or to an earlier new frame, shares that step and does not
+ *                appear, so N <= steps <= N + n.  Duplicate training frames are separate steps.
+ *   out_step_host HOST, n entries: the step of each new frame, in [0, steps)
+ *   mean, var    [P][n] (device).  The variance starts from the source's OWN k_p(x, x), as gp_sgpr_predict_source_sparse does;
+ *                sgpr_ss.py:101 starts from the sum kernel's: svar_ref = var_p + (Kdiag_sum - Kdiag_p).  The mean function
+ *                is not added (Y is the residual).  Both may be null with n = 0 (Xnew and out_step_host too): then only the
+ *                forward walk runs
+ *   loglik       one double (device): log p(y), from the forward walk
+ *   workspace    gp_ssm_smooth_workspace_bytes(d, steps, P, 1) bytes, 256-byte aligned: the history of the forward walk is
+ *                steps * d^2 doubles per window.  A short one is GP_ERR_BAD_ARG.
+ * Both host arrays are checked before anything is enqueued (order: every training frame once, no entry twice, entries in
+ * [0, N + n); out_step in range): GP_ERR_BAD_ARG otherwise.  float64 throughout whatever the plan's precision.  Synchronises.
+ * Deterministic, no atomics: two calls are bit-identical and a window's result does not depend on what shares the launch. */
+gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                     const double* Xnew, int32_t n, const int32_t* order_host, const int32_t* out_step_host,
+                                     int32_t steps, double* mean, double* var, double* loglik, void* workspace,
+                                     size_t workspace_bytes);
+/* handle-free, runs without a device: the one carve of the smoother (also the window-batched entry's, with `steps` the longest
+ * timeline of the call), measured.  0 for arguments outside 1 <= P <= d <= 128, steps >= 1, count >= 1. */
+size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count);
+
 /* ---- many independent SGPRSS windows per launch sequence -------------------------------------------------------
  * replaces the window loop of AMT.optimize / SoSp.optimize (gpitch/transcription.py:265-288, gpitch/separation.py:279-313):
  * for each window, reset_model then model.optimize(maxiter) = a dozen-odd evaluations of SGPRSS.build_likelihood
@@ -784,6 +817,16 @@ gp_status gp_sgprb_sample_source_sparse(gp_sgprb_plan p, const double* params, c
                                         const double* Z, const double* Xnew, int32_t n, int32_t count,
                                         const int32_t* order_host, int32_t S, const double* eps_x, const double* eps_z,
                                         const double* eps_u, double* out, void* workspace, size_t workspace_bytes);
+
+/* gp_sgpr_predict_source_ssm of the first `count` windows from one launch sequence, one workgroup per window: params
+ * [count][num_params], X / Y [count][N], Xnew [count][n], order_host [count][N + n] (HOST; window w's first steps_host[w]
+ * entries), out_step_host [count][n], steps_host [count] (HOST), mean / var [count][P][n], loglik [count].  workspace:
+ * gp_ssm_smooth_workspace_bytes(d, max_w steps_host[w], P, count).  float32 plans and ragged inducing counts are taken: neither
+ * plays a part.  A window's bits are those of the one-window call, whatever `count`. */
+gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
+                                      const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
+                                      const int32_t* out_step_host, const int32_t* steps_host, double* mean, double* var,
+                                      double* loglik, void* workspace, size_t workspace_bytes);
 
 /* ---- many small, independent Pdgp models per launch sequence ------------------------------------------------------
  * replaces the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)  over single-pitch models trained

@@ -1,0 +1,135 @@
+"""Times the state-space smoother (predict_s_ssm) next to the two per-source posteriors it sits beside, in one process on one
+GPU: a warm-up call of each arm, then `--reps` timed calls with the arms interleaved; medians with the smallest and largest run.
+
+  one    one window, N = n = 2001, M = 64, 3 sources x 10 partials (d = 60): predict_s, predict_s_sparse, predict_s_ssm and
+         exact_log_likelihood (the forward walk alone)
+  batch  256 such windows through SgprWindowBatch, the same three
+  fit    fit_windows_batched (maxiter 10) with predict=True, "sparse" and "ssm", as windows/s
+  cfg5   one window of N = 65536, 5 sources x 10 partials (d = 100), Xnew = X: predict_s_ssm next to predict_s_sparse (M = 512).
+         predict_s cannot run there (one N x N float64 matrix is 34 GB) and is recorded as such.
+
+Writes one JSON file (default profiles/ssm/ssm_smooth_time.json) and prints it.  GPITCH_AMD_SWITCHES=ssm_wide=1 times the
+two-wavefront walks at d = 60 (the switch is read once per process; it is recorded in the output).
+python tools/time_ssm_smooth.py [--parts one,batch,fit,cfg5] [--reps 5] [--windows 256] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _kernels(P, npart):
+    from gpitch_amd.matern12_spectral_mixture import MercerMatern12sm
+    ks = []
+    for p in range(P):
+        f0 = 220. * 2 ** (p * 4 / 12.)
+        e = 1. / np.arange(1., npart + 1.)
+        ks.append(MercerMatern12sm(1, energy=e / e.sum(), frequency=f0 * np.arange(1., npart + 1.),
+                                   variance=1.0 + 0.1 * p, lengthscales=0.05 + 0.02 * p))
+    return ks
+
+
+def _window(N, M, P, w):
+    rng = np.random.RandomState(w)
+    X = np.linspace(0, (N - 1) / 16000., N).reshape(-1, 1) + 0.125 * w
+    Y = np.zeros((N, 1))
+    for p in range(P):
+        f0 = 220. * 2 ** (p * 4 / 12.)
+        Y += np.sin(2 * np.pi * f0 * X) * np.exp(-((X - X.mean()) / (0.3 * np.ptp(X))) ** 2)
+    Y += 0.05 * rng.randn(N, 1)
+    Z = X[np.linspace(0, N - 1, M).round().astype(int)].copy()
+    return X, Y, Z
+
+
+def _time(arms, reps, sync):
+    """{name: {"median_ms", "min_ms", "max_ms", "runs"}} of callables, interleaved after one warm-up call of each"""
+    for _, f in arms:
+        f()
+    t = {k: [] for k, _ in arms}
+    for _ in range(reps):
+        for k, f in arms:
+            sync()
+            t0 = time.perf_counter()
+            f()
+            sync()
+            t[k].append(1e3 * (time.perf_counter() - t0))
+    return {k: {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v)), "runs": len(v)}
+            for k, v in t.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="one,batch,fit,cfg5")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--windows", type=int, default=256)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ssm", "ssm_smooth_time.json"))
+    a = ap.parse_args()
+    parts = a.parts.split(",")
+    import torch
+    from gpitch_amd import _lib
+    from gpitch_amd.sgpr_ss import SGPRSS
+    from gpitch_amd.windows import SgprWindowBatch, fit_windows_batched
+    sync = torch.cuda.synchronize
+    h = _lib.default_handle()
+    out = {"device": torch.cuda.get_device_name(0), "switches": os.environ.get("GPITCH_AMD_SWITCHES", ""), "reps": a.reps}
+    N, M, P, W = 2001, 64, 3, a.windows
+    wins = [_window(N, M, P, w) for w in range(W if ("batch" in parts or "fit" in parts) else 1)]
+
+    def make(handle):
+        return SGPRSS(wins[0][0], wins[0][1], np.sum(_kernels(P, 10)), wins[0][2], handle=handle)
+
+    if "one" in parts:
+        m = make(h)
+        X = wins[0][0]
+        out["one_window_N2001_d60"] = _time([("predict_s", lambda: m.predict_s(X)), ("predict_s_sparse", lambda: m.predict_s_sparse(X)),
+                                             ("predict_s_ssm", lambda: m.predict_s_ssm(X)),
+                                             ("exact_log_likelihood", lambda: m.exact_log_likelihood())], a.reps, sync)
+        m._destroy()
+        print("one window: done", file=sys.stderr, flush=True)
+    if "batch" in parts:
+        tmpl = make(h)
+        dev = SgprWindowBatch(tmpl, W, N, M, handle=h)
+        dev.load([w[0] for w in wins], [w[1] for w in wins], [w[2] for w in wins])
+        tmpl._compile()
+        tmpl._pack()
+        pv = np.tile(tmpl._params.cpu().numpy(), (W, 1))
+        res = _time([("predict_s", lambda: dev.predict_s(pv)), ("predict_s_sparse", lambda: dev.predict_s_sparse(pv)),
+                     ("predict_s_ssm", lambda: dev.predict_s_ssm(pv))], a.reps, sync)
+        for v in res.values():
+            v["windows_per_s"] = W / (1e-3 * v["median_ms"])
+        out["batch_%d_windows_N2001_d60" % W] = res
+        dev.close()
+        tmpl._destroy()
+        print("batch: done", file=sys.stderr, flush=True)
+    if "fit" in parts:
+        arms = [("predict_True", True), ("predict_sparse", "sparse"), ("predict_ssm", "ssm"), ("fit_only", False)]
+        res = _time([(k, (lambda pr=pr: fit_windows_batched(make, wins, maxiter=10, batch=W, predict=pr))) for k, pr in arms],
+                    max(3, a.reps // 2), sync)
+        for v in res.values():
+            v["windows_per_s"] = W / (1e-3 * v["median_ms"])
+        out["fit_windows_batched_%d_windows" % W] = res
+        print("fit: done", file=sys.stderr, flush=True)
+    if "cfg5" in parts:
+        N5, M5, P5 = 65536, 512, 5
+        X, Y, Z = _window(N5, M5, P5, 1)
+        m = SGPRSS(X, Y, np.sum(_kernels(P5, 10)), Z, handle=h)
+        res = _time([("predict_s_sparse", lambda: m.predict_s_sparse(X)), ("predict_s_ssm", lambda: m.predict_s_ssm(X)),
+                     ("exact_log_likelihood", lambda: m.exact_log_likelihood())], max(3, a.reps // 2), sync)
+        res["predict_s"] = "cannot run: one N x N float64 matrix is %.0f GB" % (8e-9 * N5 * N5)
+        res["ssm_workspace_GB"] = 1e-9 * int(h.lib.gp_ssm_smooth_workspace_bytes(100, N5, P5, 1))
+        out["one_window_N65536_d100"] = res
+        m._destroy()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
