@@ -102,13 +102,17 @@ struct KufScanItem {
   const double* theta;                                      // [variance, lengthscale]
   double* mom; double* near; double* partials;              // moments [chunk][side][q][M + 1], near sums [chunk][2], records
   int64_t lda; int M, pad;
+  // the far-field form of launch 1 only: the stored Kuf strip (ld lda), W, and afar.hip's tables of this step
+  const double* Kuf; const double* W; const int* rng; const double* T; const double* Psi;
 };
-int kuf_scan_nq(int ktype);                 // moment orders a kernel type needs (3 Matern-3/2, 4 Matern-5/2; 0: not a scan type)
+int kuf_scan_nq(int ktype);                // moment orders a kernel type needs (3 Matern-3/2, 4 Matern-5/2; 0: not a scan type)
 int kuf_scan_chunks(int N);
 size_t kuf_scan_moment_doubles(int N, int M, int ktype);
 int kuf_scan_records(int M);                // partial records one GP leaves (never more than hyper_kuf_records gives it)
-// all `count` GPs of one family (same kernel type) over the n ascending frames x: three launches, no Kuf_bar product
-gp_status launch_kuf_scan(gp_handle h, int ktype, const KufScanItem* d_items, int count, int maxM, const double* x, int n);
+// all `count` GPs of one family (same kernel type) over the n ascending frames x: three launches, no Kuf_bar product.
+// far: the first launch forms the moments and the near sums from the items' Kuf, W, rng, T and Psi instead of a pass over A
+// (Matern-3/2 on the shapes afar_takes admits; every GP's A of this step came from launch_afar)
+gp_status launch_kuf_scan(gp_handle h, int ktype, const KufScanItem* d_items, int count, int maxM, const double* x, int n, int far = 0);
 
 // qfar.hip: the tables of the Q route's far field, one item per latent GP of the run
 struct QfarItem {

@@ -155,6 +155,16 @@ gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable) {
   return GP_OK;
 }
 int32_t gp_pdgp_far_field_act(gp_pdgp_plan p) { return (p && p->na > 0) ? 1 : 0; }
+gp_status gp_pdgp_set_scan_far(gp_pdgp_plan p, int32_t enable) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (p->scan_far_ok != (enable != 0)) { p->scan_far_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
+  return GP_OK;
+}
+int32_t gp_pdgp_scan_far(gp_pdgp_plan p) {
+  if (!p || p->na <= 0 || !p->last_grad) return 0;
+  for (const auto& fam : p->hy_fams) if (fam.route == KUF_SCAN && fam.scan_far) return 1;
+  return 0;
+}
 // debug: the device's own ranges and reference points of the last evaluation's activation far field, copied to the host
 int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref) {
   if (!p || !p->ws || p->na <= 0 || i < 0 || i >= p->na || p->last_n <= 0 || !rng || !ref) return 0;
@@ -245,7 +255,10 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
         }
       }
       // (activation far field, pdgp_bwd.hip pdgp_afar_select: reserved before its setters have spoken, for the plan's largest
-      // batch — at M = 512, N = 32768: 4 MB of T, 1 MB of Psi, 2 MB of C per GP beside two 134 MB strips)
+      // batch — at M = 512, N = 32768: 4 MB of T, 1 MB of Psi, 2 MB of C per GP beside two 134 MB strips.
+      // The backward window reads rng, T and Psi again, with W and the Kuf strip (kuf_scan_far_moments_kernel):
+      // each has a region of its own in this walk and in cond_task_carve, nothing of the backward pass is carved over them, and
+      // its launches only read W and Kuf — they stay the forward pass's until the next step's forward pass rewrites them)
       if (gp_switches().act_far != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MATERN32 && afar_takes((int)M, p->maxN)) {
         const AfarSizes as = afar_sizes((int)M, p->maxN);
         b.af_rng = (int*)ar.take<double>(as.rng); b.af_ref = ar.take<double>(as.ref);

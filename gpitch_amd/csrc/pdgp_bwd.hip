@@ -274,13 +274,18 @@ static void pdgp_select_routes(gp_pdgp_plan p, int n) {
   }
   p->any_scan = p->any_routed = false;
   for (auto& fam : p->hy_fams) {
-    fam.route = KUF_PRODUCT; fam.np_uf = fam.np_uu = 0;
+    fam.route = KUF_PRODUCT; fam.np_uf = fam.np_uu = 0; fam.scan_far = false;
     if (p->nq > 0 && fam.gps[0] == p->q0) {
       fam.route = KUF_QFORM;
     } else if (p->contiguous && gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
                kuf_scan_nq(fam.type) > 0 && fam.M <= 1024) {
       fam.route = KUF_SCAN; fam.np_uf = kuf_scan_records(fam.M);
       p->any_scan = true;
+      // its moments from the factored A: a Matern-3/2 family all of whose GPs are in the run whose A
+      // afar.hip forms at this batch size (that run's conditions — float64, one M, n a multiple of 256 — come with it)
+      fam.scan_far = gp_switches().scan_far != 0 && p->scan_far_ok && fam.type == GP_KERN_MATERN32 && p->na > 0;
+      for (int g : fam.gps) if (g < p->a0 || g >= p->a0 + p->na) fam.scan_far = false;
+      for (const PdgpGP& q : p->gps) if (q.f32) fam.scan_far = false;        // (a plan of float64 strips throughout)
     } else if (p->contiguous && p->kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM &&
                (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type))) {
       fam.route = KUF_FUSED;
@@ -406,6 +411,7 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
           si.A = t.A; si.lda = gp_strip_ld(n, q.f32 != 0); si.gv = p->gFvar + (size_t)g * n; si.gm = p->gFmu + (size_t)g * n;
           si.R = bb.R; si.alpha = bb.alpha; si.z = params + q.off_z; si.theta = t.kern.theta;
           si.mom = bb.ks_mom; si.near = bb.ks_near; si.partials = bb.hyp_part; si.M = q.M;
+          if (fam.route == KUF_SCAN && fam.scan_far) { si.Kuf = t.Kuf; si.W = t.W; si.rng = bb.af_rng; si.T = bb.af_T; si.Psi = bb.af_Psi; }
         }
         HyperItem& it = items[pos++];
         memset(&it, 0, sizeof(it));
@@ -584,7 +590,7 @@ static gp_status bwd_kuf_bar_step(const BwdCall& c, const HyFamily& fam, bool sc
   switch (fam.route) {
     case KUF_QFORM: return GP_OK;      // Kuf_bar = G diag(2 gv) + beta gm^T needs no product: the contraction scales G's columns
     case KUF_SCAN: {
-      auto scan = [&]() { return launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, c.x, c.n); };
+      auto scan = [&]() { return launch_kuf_scan(h, fam.type, (const KufScanItem*)(p->d_misc + p->off.ks_items) + fam.first, fam.count, fam.M, c.x, c.n, fam.scan_far ? 1 : 0); };
       bool side;
       GP_CHECK(gp_on_side(h, scan_to_side, &side, scan));
       return side ? GP_OK : scan();

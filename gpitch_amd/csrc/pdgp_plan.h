@@ -110,6 +110,7 @@ struct gp_pdgp_plan_s {
     int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; bool scan_ws = false;
     int slot0 = -1;                  // its first slot in the compacted batch; -1: its GPs do not sit in one run of it
     KufRoute route = KUF_PRODUCT;
+    bool scan_far = false;           // KUF_SCAN: its first launch takes the moments from afar.hip's factored A
     int np_uf = 0, np_uu = 0;        // batched family: partial records per GP.  np_uf is fixed at bind by the fused and scan routes;
                                      // the contractions report the others at launch
     std::vector<int> gps;
@@ -155,6 +156,9 @@ struct gp_pdgp_plan_s {
   // that the inducing inputs of every Matern-3/2 GP ascend — and the run [a0, a0 + na) that takes it at the bound batch size
   bool afar_ok = false;
   int a0 = 0, na = 0;
+  // the scan's moments from that far field (pdgp_select_routes): gp_pdgp_set_scan_far's permission, given by
+  // default — it exists so that one handle can evaluate both forms
+  bool scan_far_ok = true;
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

@@ -369,6 +369,14 @@ gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable);
 /* 1 when the batch last bound qualifies for that route, else 0.  It speaks of ELBO evaluations (gp_pdgp_elbo and its staged
  * forms), which take the route when it is 1; a prediction binds the batch too and always runs the dense products. */
 int32_t gp_pdgp_far_field_act(gp_pdgp_plan p);
+/* Permission for the scan's far-field moments.  enable != 0 (the default): a Matern-3/2 family that contracts its
+ * Kuf_bar by the scan (fixed inducing inputs, frames promised ascending) and whose latent GPs are all in the run that takes the
+ * activations' far field above forms the scan's chunk moments and near sums from that far field's factors instead of a pass
+ * over the stored A: the same sums to rounding.  enable == 0: the pass over A.  GPITCH_AMD_SWITCHES=scan_far=0 overrides an
+ * enable.  It lets one handle evaluate both forms. */
+gp_status gp_pdgp_set_scan_far(gp_pdgp_plan p, int32_t enable);
+/* 1 when the last gradient evaluation's bind chose that form for some family, else 0 (0 after a bind without a gradient). */
+int32_t gp_pdgp_scan_far(gp_pdgp_plan p);
 /* Debug, read-only: as gp_debug_pdgp_far_ranges for latent GP number `i` of the activation far field's run — rng [2 groups]
  * (kbeg, kend per group of 256 frames), ref [2 groups] (the group's smallest and largest frame time).  Returns the groups written. */
 int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref);
