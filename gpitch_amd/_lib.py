@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
     "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
     "gp_pdgp_create", "gp_pdgp_destroy", "gp_pdgp_num_params", "gp_pdgp_layout", "gp_pdgp_workspace_bytes",
-    "gp_pdgp_set_workspace", "gp_pdgp_set_precision", "gp_pdgp_set_gp_precision", "gp_pdgp_set_grad_needs", "gp_pdgp_set_overlap", "gp_pdgp_set_frames_ascending", "gp_pdgp_set_qform", "gp_pdgp_far_field", "gp_pdgp_far_field_backward", "gp_debug_pdgp_far_ranges", "gp_pdgp_set_far_act", "gp_pdgp_far_field_act", "gp_pdgp_set_scan_far", "gp_pdgp_scan_far", "gp_debug_pdgp_act_ranges", "gp_pdgp_elbo", "gp_pdgp_elbo_begin", "gp_pdgp_elbo_end", "gp_pdgp_create_subset", "gp_pdgp_cond_begin", "gp_pdgp_cond_end", "gp_pdgp_predict", "gp_pdgp_predict_reuse",
+    "gp_pdgp_set_workspace", "gp_pdgp_set_precision", "gp_pdgp_set_gp_precision", "gp_pdgp_set_grad_needs", "gp_pdgp_set_overlap", "gp_pdgp_set_frames_ascending", "gp_pdgp_set_qform", "gp_pdgp_far_field", "gp_pdgp_far_field_backward", "gp_debug_pdgp_far_ranges", "gp_pdgp_set_far_act", "gp_pdgp_far_field_act", "gp_pdgp_set_scan_far", "gp_pdgp_scan_far", "gp_pdgp_set_h_far", "gp_pdgp_h_far", "gp_debug_pdgp_act_ranges", "gp_pdgp_elbo", "gp_pdgp_elbo_begin", "gp_pdgp_elbo_end", "gp_pdgp_create_subset", "gp_pdgp_cond_begin", "gp_pdgp_cond_end", "gp_pdgp_predict", "gp_pdgp_predict_reuse",
     "gp_pdgp_sample", "gp_pdgp_sample_reuse", "gp_pdgp_sample_workspace_bytes",
     "gp_overlap_merge", "gp_transform_register_logistic", "gp_transform_forward", "gp_transform_backward", "gp_poll_not_pd", "gp_check_not_pd", "gp_take_not_pd", "gp_adam_step",
     "gp_pdgp_natgrad_workspace_bytes", "gp_pdgp_natgrad_step",
@@ -220,6 +220,8 @@ def load_library():
         "gp_pdgp_far_field_act": (i32, [vp]),
         "gp_pdgp_set_scan_far": (i32, [vp, i32]),
         "gp_pdgp_scan_far": (i32, [vp]),
+        "gp_pdgp_set_h_far": (i32, [vp, i32]),
+        "gp_pdgp_h_far": (i32, [vp]),
         "gp_debug_pdgp_act_ranges": (i32, [vp, i32, i32, C.POINTER(i32), vp, vp]),
         "gp_pdgp_elbo": (i32, [vp, vp, vp, vp, i32, dbl, vp, C.POINTER(dbl), vp]),
         "gp_pdgp_elbo_begin": (i32, [vp, vp, vp, vp, i32, vp, vp]),

@@ -942,7 +942,7 @@ gp_status check_not_pd(gp_handle h) {
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   if (st[0] != 0) {
     h->not_pd_index = st[1];
-    char buf[256];
+    char buf[384];
     const bool stalled = (st[0] == 2);      // chol_cluster.hip: a wavefront gave up waiting for the cluster's exchange
     if (st[0] == 3) {                       // kuf_scan.hip: a descending pair of frames under gp_pdgp_set_frames_ascending
       snprintf(buf, sizeof(buf), "frames not ascending: frame %d is below frame %d although gp_pdgp_set_frames_ascending promised time order", st[1] + 1, st[1]);
@@ -955,6 +955,13 @@ gp_status check_not_pd(gp_handle h) {
       h->last_error = buf;
       GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
       return GP_ERR_UNSUPPORTED;
+    }
+    if (st[0] == 5) {                       // hfar.hip: the store of Y would collide, or a near range is not whole tiles inside [0, M]
+      if (st[3]) snprintf(buf, sizeof(buf), "activations' H from the factors: two (tile, group) pairs of latent GP %d share slot %d (equal frames across a group boundary together with equal inducing inputs across a tile boundary); gp_pdgp_set_h_far(plan, 0) or GPITCH_AMD_SWITCHES=h_far=0 selects the dense product", st[2], st[1]);
+      else snprintf(buf, sizeof(buf), "activations' H from the factors: the near range of group %d of latent GP %d is not whole tiles inside its rows", st[1], st[2]);
+      h->last_error = buf;
+      GP_HIP_CHECK(h, hipMemsetAsync(h->d_status, 0, sizeof(st), h->stream));
+      return GP_ERR_BAD_ARG;
     }
     if (stalled) snprintf(buf, sizeof(buf), "Cholesky failed: the workgroup cluster stalled (GPITCH_AMD_SWITCHES=chol_cluster=0 selects the one-workgroup kernels)");
     else snprintf(buf, sizeof(buf), "Cholesky failed: matrix %d is not positive definite (pivot %d)", st[2], st[1]);

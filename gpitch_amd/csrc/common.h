@@ -20,7 +20,7 @@ struct gp_handle_s {
   bool own_stream = false;
   std::string last_error;
   int32_t not_pd_index = -1;
-  int32_t* d_status = nullptr;   // device int[4]: {flag (1 not PD, 2 cluster stalled, 3 frames not ascending, 4 qform guard), pivot / frame index, gp_index, spare}
+  int32_t* d_status = nullptr;   // device int[4]: {flag (1 not PD, 2 cluster stalled, 3 frames not ascending, 4 qform guard, 5 hfar store), pivot / frame index, gp_index, spare}
   int num_cus = 256;
   GpLogisticTable logistic = {}; int num_logistic = 0;
   // helper stream for work that can overlap the main stream (the latency-bound Kuu factorisation runs on ~24 CUs
@@ -333,10 +333,14 @@ gp_status launch_gemm_nt_reduce_batched(gp_handle h, const GemmProblem* d_probs,
                                         int nsplit, int sym, int scale_by_k, double alpha, int uniform_aligned = 0);
 bool launch_gemm_strip_f32_lean(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxN, const GemmFlags& f,
                                 gp_status* st);
+bool gemm_strip_nt_lean_takes(int M, int Nlong, int nsplit);     // would launch_gemm_strip_nt_lean take the shape?
 bool launch_gemm_strip_nt_lean(gp_handle h, const GemmProblem* d_probs, int batch, int M, int Nlong, int nsplit, int sym,
                                int scale_by_k, gp_status* st);
 gp_status launch_tri_inverse_batched(gp_handle h, const double* const* d_L, double* const* d_W, const int* d_M,
                                      const int* d_ld, int batch);
+// scopes launch_gemm_nt_reduce_batched opens under the split-K product's timer for this shape: one for the lean form it tries
+// first and, where that does not take the shape, one more for the form it falls back to
+int gemm_nt_reduce_charges(int maxM, int maxNlong, int nsplit, int uniform_aligned);
 int gemm_nt_nsplit(int M, int Nlong, int batch);
 gp_status launch_slab_reduce(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int nsplit, int sym, double alpha);
 // gemm_f32.hip: the strip products on float32 strips (roles 1-3: A float64 M x M, B / C float32 strips; nt: float32

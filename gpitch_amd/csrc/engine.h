@@ -164,6 +164,24 @@ bool afar_takes(int M, int N);
 // count GPs of one family (M) over the n ascending frames x, behind C: the tables' two launches and the product's one on h->stream
 gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, const double* x, int n);
 
+// hfar.hip: the activations' H = A diag(2 gv) A^T and u = A gm from the stored A once and afar.hip's factors once
+// (DESIGN.md 3.10), one item per latent GP of the run: the strips, W, the likelihood's two rows, afar.hip's tables of this
+// step, the store of Y, and the split-K product's slabs and u partials, which launch_slab_reduce sums as it does the product's
+struct HfarItem {
+  const double* A; const double* Kuf; const double* W; const double* gv; const double* gm;
+  const int* rng; const double* T; const double* Psi;      // [groups][2] near range, T [groups][M][8], Psi [4][N]
+  double* Yn; double* Yf; double* up; int* flag;           // near columns [slot = tile + group][M][16], far columns [groups][M][4],
+                                                            // A gm per group [groups][M], the check's verdict
+  double* slabs; double* upart;                            // [nsplit][M][M] (lower 16 x 16 tiles written), [nsplit][M]
+  int64_t ld; int M, gp;                                   // gp: the latent GP's index, for the status word
+};
+struct HfarSizes { size_t Yn, Yf, up, flag; };             // doubles
+HfarSizes hfar_sizes(int M, int N);
+bool hfar_takes(int M, int N);
+// count GPs of one family (M) over n frames, behind afar.hip's launches of this step and the likelihood's gv / gm: three
+// launches on h->stream.  charges: the scopes they open under the split-K product's timer (0: none — a dense launch remains)
+gp_status launch_hfar(gp_handle h, const HfarItem* d_items, int count, int M, int n, int nsplit, int charges);
+
 #define CB_NB 128          // panel width of the blocked Kuu factorisation
 #define CB_MAX_PANELS 8    // M <= 1024
 

@@ -675,6 +675,10 @@ int gemm_nt_nsplit(int M, int Nlong, int batch) {
   return s;
 }
 
+int gemm_nt_reduce_charges(int maxM, int maxNlong, int nsplit, int uniform_aligned) {
+  return (uniform_aligned && !gemm_strip_nt_lean_takes(maxM, maxNlong, nsplit > 1 ? nsplit : 2)) ? 2 : 1;
+}
+
 gp_status launch_gemm_nt_reduce_batched(gp_handle h, const GemmProblem* d_probs, int batch, int maxM, int maxNlong,
                                         int nsplit, int sym, int scale_by_k, double alpha, int uniform_aligned) {
   if (batch <= 0 || maxM <= 0) return GP_OK;

@@ -700,10 +700,13 @@ __global__ void __launch_bounds__(256, 2) gemm_strip_nt_kernel(const GemmProblem
 #endif
 }
 
+bool gemm_strip_nt_lean_takes(int M, int Nlong, int nsplit) {
+  return gp_switches().strip_lean != 0 && (M % GS_BM) == 0 && (Nlong % GS_BK) == 0 && nsplit >= 2;
+}
+
 bool launch_gemm_strip_nt_lean(gp_handle h, const GemmProblem* d_probs, int batch, int M, int Nlong, int nsplit, int sym,
                                int scale_by_k, gp_status* st) {
-  const bool enabled = gp_switches().strip_lean != 0;
-  if (!enabled || (M % GS_BM) != 0 || (Nlong % GS_BK) != 0 || nsplit < 2) return false;
+  if (!gemm_strip_nt_lean_takes(M, Nlong, nsplit)) return false;
   using S = StripSmem<false>;
   StripNtFlags nf;
   nf.tilesM = M / GS_BM; nf.ksplit = nsplit; nf.sym = sym; nf.scale = scale_by_k;

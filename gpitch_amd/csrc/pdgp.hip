@@ -165,6 +165,12 @@ int32_t gp_pdgp_scan_far(gp_pdgp_plan p) {
   for (const auto& fam : p->hy_fams) if (fam.route == KUF_SCAN && fam.scan_far) return 1;
   return 0;
 }
+gp_status gp_pdgp_set_h_far(gp_pdgp_plan p, int32_t enable) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (p->h_far_ok != (enable != 0)) { p->h_far_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
+  return GP_OK;
+}
+int32_t gp_pdgp_h_far(gp_pdgp_plan p) { return (p && p->na > 0 && p->last_grad && p->nhf > 0) ? 1 : 0; }
 // debug: the device's own ranges and reference points of the last evaluation's activation far field, copied to the host
 int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref) {
   if (!p || !p->ws || p->na <= 0 || i < 0 || i >= p->na || p->last_n <= 0 || !rng || !ref) return 0;
@@ -263,6 +269,14 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
         const AfarSizes as = afar_sizes((int)M, p->maxN);
         b.af_rng = (int*)ar.take<double>(as.rng); b.af_ref = ar.take<double>(as.ref);
         b.af_T = ar.take<double>(as.T); b.af_Psi = ar.take<double>(as.Psi); b.af_C = ar.take<double>(as.C);
+        // (H from the stored A and these factors, DESIGN.md 3.10: the ranges are the device's own every step, so the store of Y is
+        // sized by its bound — M / 16 + N / 256 - 1 slots of M x 16, the four far columns and A gm per group: at M = 512,
+        // N = 32768 10.4 + 2.1 + 0.5 MB per GP — reserved like the tables, before the setters have spoken)
+        if (gp_switches().h_far != 0 && hfar_takes((int)M, p->maxN)) {
+          const HfarSizes hs = hfar_sizes((int)M, p->maxN);
+          b.hf_Yn = ar.take<double>(hs.Yn); b.hf_Yf = ar.take<double>(hs.Yf); b.hf_up = ar.take<double>(hs.up);
+          b.hf_flag = (int*)ar.take<double>(hs.flag);
+        }
       }
       b.R32 = p->gps[g].f32 ? ar.take<double>((M * M + 1) / 2) : nullptr;
       b.u = ar.take<double>(M); b.Lu = ar.take<double>(M); b.alpha = ar.take<double>(M);

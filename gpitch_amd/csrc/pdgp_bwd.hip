@@ -294,6 +294,22 @@ static void pdgp_select_routes(gp_pdgp_plan p, int n) {
     }
     if (fam.route != KUF_PRODUCT) p->any_routed = true;
   }
+  // H = A diag(2 gv) A^T and u = A gm of the run whose A afar.hip forms, from that A once and its factors once:
+  // the switch, gp_pdgp_set_h_far, a plan of float64 strips throughout, the workspace — and the latent GPs left to the dense
+  // split-K product (neither in this run nor in the Q run when qbar.hip has its Qbar) are one run of the batch, or none
+  p->nhf = p->hd0 = p->hdn = 0;
+  bool hf = gp_switches().h_far != 0 && p->h_far_ok && p->na > 0 && p->n64 == p->G && hfar_takes(maxM, n);
+  for (const PdgpGP& q : p->gps) if (q.f32) hf = false;
+  for (int g = p->a0; hf && g < p->a0 + p->na; g++) if (!p->bw[g].hf_Yn || !p->bw[g].hf_Yf || !p->bw[g].hf_up || !p->bw[g].hf_flag) hf = false;
+  if (hf) {
+    int first = -1, last = -1, cnt = 0;
+    for (int g = 0; g < p->G; g++) {
+      if ((g >= p->a0 && g < p->a0 + p->na) || (p->q_bar && pdgp_on_q_route(p, g))) continue;
+      if (first < 0) first = g;
+      last = g; cnt++;
+    }
+    if (cnt == 0 || last - first + 1 == cnt) { p->nhf = p->na; p->hd0 = cnt ? first : 0; p->hdn = cnt; }
+  }
 }
 // do the family's Kuf-side partial sums come with its Kuf_bar step (no contraction launch of its own)?
 static inline bool kuf_sums_with_step(const gp_pdgp_plan_s::HyFamily& fam) { return fam.route == KUF_FUSED || fam.route == KUF_SCAN; }
@@ -396,6 +412,15 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
     for (int g : fam.gps) if (!p->bw[g].ks_mom || !p->bw[g].ks_near) fam.scan_ws = false;
   }
   pdgp_select_routes(p, n);
+  for (int i = 0; i < p->nhf; i++) {      // hfar.hip's items: the product's own slabs and u partials, which the slab reduction sums
+    const int g = p->a0 + i;
+    const CondTask& t = p->cb.tasks[g];
+    const BwdBufs& b = p->bw[g];
+    const GemmProblem& r = *((const GemmProblem*)(p->h_misc.data() + p->off.bwd[S_H]) + g);
+    HfarItem& it = *(HfarItem*)(p->h_misc.data() + p->off.hf_items + i * sizeof(HfarItem));
+    it = HfarItem{t.A, t.Kuf, t.W, p->gFvar + (size_t)g * n, p->gFmu + (size_t)g * n, b.af_rng, b.af_T, b.af_Psi,
+                  b.hf_Yn, b.hf_Yf, b.hf_up, b.hf_flag, r.o2, r.o1, gp_strip_ld(n, false), p->gps[g].M, g};
+  }
   {
     HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
     KufScanItem* sitems = (KufScanItem*)(p->h_misc.data() + p->off.ks_items);
@@ -507,7 +532,14 @@ static gp_status bwd_h_chain(const BwdCall& c) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
   const int G = p->G, maxM = p->maxM, n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
   GemmFlags f;
-  if (p->q_bar) {       // the Q run's Qbar and v from its far field (four launches, no timer class); the product on the other run
+  if (p->nhf > 0) {     // the activations' run from the stored A once and its factors once (hfar.hip), the dense product on the others
+    if (p->q_bar && !p->qbar_ahead) GP_CHECK(bwd_qbar(c));
+    if (p->hdn > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + p->hd0, p->hdn, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+    GP_CHECK(launch_hfar(h, (const HfarItem*)(p->d_misc + p->off.hf_items), p->nhf, maxM, c.n, p->nsplit,
+                        p->hdn == 0 ? gemm_nt_reduce_charges(maxM, c.n, p->nsplit, p->nt_uniform) : 0));
+    GP_CHECK(launch_slab_reduce(h, slot_probs(p, S_H) + p->a0, p->nhf, maxM, p->nsplit, 1, 1.0));      // (Y carries the factor 2)
+    if (p->q_bar && p->qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
+  } else if (p->q_bar) {       // the Q run's Qbar and v from its far field (four launches, no timer class); the product on the other run
     const int rest0 = (p->q0 == 0) ? p->nq : 0;
     if (!p->qbar_ahead) GP_CHECK(bwd_qbar(c));
     GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + rest0, n64 - p->nq, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));

@@ -12,7 +12,7 @@ static inline size_t pdgp_kl_region_bytes(int G) {
 // (pdgp_bwd.hip, checked there), the last one holds the trace-term problems of the unwhitened KL.
 #define PDGP_BWD_SLOTS 32
 #define PDGP_KLTR_SLOT (PDGP_BWD_SLOTS - 1)
-struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, qb_items, af_items, bytes; };
+struct PdgpMiscLayout { size_t kl_items, bwd[PDGP_BWD_SLOTS], kltr, kl2, fin_items, hy_items, ks_items, qf_items, qb_items, af_items, hf_items, bytes; };
 static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   PdgpMiscLayout o;
   GpRegions region;
@@ -26,6 +26,7 @@ static inline PdgpMiscLayout pdgp_misc_layout(int G) {
   o.qf_items = region((size_t)G * sizeof(QfarItem));          // qfar.hip: one per latent GP of the Q run
   o.qb_items = region((size_t)G * sizeof(QbarItem));          // qbar.hip: one per latent GP of the Q run
   o.af_items = region((size_t)G * sizeof(AfarItem));          // afar.hip: one per latent GP of the activation far-field run
+  o.hf_items = region((size_t)G * sizeof(HfarItem));          // hfar.hip: one per latent GP of the run whose H comes from the factors
   o.bytes = region.off;
   return o;
 }
@@ -65,6 +66,9 @@ struct BwdBufs {  // per-GP backward workspace (device)
   // the activations' far field (afar.hip): near ranges, xmin / xmax, T, Psi and C = tril(Lq)^T W — Matern-3/2 GPs
   // of a whitened float64 plan whose shape admits it
   int* af_rng = nullptr; double* af_ref = nullptr; double* af_T = nullptr; double* af_Psi = nullptr; double* af_C = nullptr;
+  // H = A D A^T from the stored A once and those factors once (hfar.hip): Y's near columns by slot, its far
+  // columns, the per-group A gm, the check's verdict — carved behind the tables, nothing else is carved over them
+  double* hf_Yn = nullptr; double* hf_Yf = nullptr; double* hf_up = nullptr; int* hf_flag = nullptr;
   double* R32 = nullptr;    // float32 strips only: M * M floats, the float32 copy of R (gemm_wave_f32.hip)
   double* G = nullptr;      // M x N   K̄uf (dense part R (A D))
   double* u = nullptr;      // M       A gm
@@ -159,6 +163,11 @@ struct gp_pdgp_plan_s {
   // the scan's moments from that far field (pdgp_select_routes): gp_pdgp_set_scan_far's permission, given by
   // default — it exists so that one handle can evaluate both forms
   bool scan_far_ok = true;
+  // H and u of that run from the factored A (pdgp_select_routes): gp_pdgp_set_h_far's permission, given by
+  // default; nhf = na when the bound gradient evaluation takes the form (the run is then [a0, a0 + na)), else 0; the latent
+  // GPs left to the dense split-K product are the run [hd0, hd0 + hdn), possibly empty
+  bool h_far_ok = true;
+  int nhf = 0, hd0 = 0, hdn = 0;
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;

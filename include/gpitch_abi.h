@@ -377,6 +377,17 @@ int32_t gp_pdgp_far_field_act(gp_pdgp_plan p);
 gp_status gp_pdgp_set_scan_far(gp_pdgp_plan p, int32_t enable);
 /* 1 when the last gradient evaluation's bind chose that form for some family, else 0 (0 after a bind without a gradient). */
 int32_t gp_pdgp_scan_far(gp_pdgp_plan p);
+/* Permission for H = A diag(2 gv) A^T and u = A gm of the activations from the stored A once and the far field's factors once
+ * (DESIGN.md 3.10).  enable != 0 (the default): in a plan of float64 strips throughout, the run that takes the activations' far
+ * field above forms, per group of 256 frames, Y = A diag(2 gv) B^T (B: the rows of Kuf near the group and the four rows of Psi)
+ * in one pass over the stored A and then H = sum Y P^T (P: W's near columns and the far field's tables) instead of the dense
+ * split-K product over all frames: the same H to rounding, symmetric to the bit.  The latent GPs left to the dense product must
+ * be one run of the batch, or none; else every GP keeps it.  enable == 0: the dense product.  GPITCH_AMD_SWITCHES=h_far=0 overrides
+ * an enable.  Equal frames across a group boundary together with equal inducing inputs across a tile boundary — which
+ * gp_pdgp_set_frames_ascending and gp_pdgp_set_far_act promise away — fail the evaluation with GP_ERR_BAD_ARG. */
+gp_status gp_pdgp_set_h_far(gp_pdgp_plan p, int32_t enable);
+/* 1 when the last gradient evaluation's bind chose that form, else 0 (0 after a bind without a gradient). */
+int32_t gp_pdgp_h_far(gp_pdgp_plan p);
 /* Debug, read-only: as gp_debug_pdgp_far_ranges for latent GP number `i` of the activation far field's run — rng [2 groups]
  * (kbeg, kend per group of 256 frames), ref [2 groups] (the group's smallest and largest frame time).  Returns the groups written. */
 int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref);
