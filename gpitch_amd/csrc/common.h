@@ -463,6 +463,10 @@ gp_status pdgp_sample_run(gp_handle h, const PsmGP* gps, int P, bool whiten, int
 // w < count: params + w * param_stride, X / Y + w * N, Xnew + w * n, order_host + w * (N + n) (its first steps_host[w] entries),
 // out_step_host + w * n, mean / var + w * P * n, loglik + w.  Synchronises.
 size_t ssm_smooth_workspace_bytes(int d, int steps, int P, int count);
+size_t ssm_score_workspace_bytes(int d, int steps, int P, int count);
+gp_status ssm_score_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                        const double* params, const double* X, const double* Y, int N, int count, const int32_t* order_host,
+                        double* loglik, double* grad, double* resid_grad, void* ws, size_t ws_bytes);
 gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
                          const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
                          const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,

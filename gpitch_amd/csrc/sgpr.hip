@@ -958,6 +958,16 @@ gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const
                         order_host, out_step_host, &steps, mean, var, loglik, workspace, workspace_bytes);
 }
 
+// The exact log-likelihood and its gradient in the plan's parameter layout by the state-space score walk (ssm_smooth.hip): as
+// above, the plan gives the kernel structure and the layout only.
+gp_status gp_sgpr_exact_loglik_grad(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                    const int32_t* order_host, double* loglik, double* grad, double* resid_grad, void* workspace,
+                                    size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  return ssm_score_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, N, 1, order_host,
+                       loglik, grad, resid_grad, workspace, workspace_bytes);
+}
+
 // sgpr_predict_source_impl's workspace
 struct SgprSrcBufs { char* d_desc; double *L, *W; void* chol_ws; double *Kx, *A, *feat, *s1, *dot, *V, *scal; };
 static SgprSrcBufs sgpr_src_carve(GpArena& ar, int N, int n) {

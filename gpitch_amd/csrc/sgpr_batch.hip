@@ -790,6 +790,17 @@ extern "C" gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan_t p, const double
                         count, order_host, out_step_host, steps_host, mean, var, loglik, workspace, workspace_bytes);
 }
 
+// gp_sgpr_exact_loglik_grad of the first `count` windows: one workgroup per window in the walks
+extern "C" gp_status gp_sgprb_exact_loglik_grad(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
+                                                int32_t count, const int32_t* order_host, double* loglik, double* grad,
+                                                double* resid_grad, void* workspace, size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (count < 1 || count > p->W)
+    return gp_fail(p->h, GP_ERR_BAD_ARG, "gp_sgprb_exact_loglik_grad: bad argument (1 <= count <= num_windows)");
+  return ssm_score_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, p->N, count,
+                       order_host, loglik, grad, resid_grad, workspace, workspace_bytes);
+}
+
 // gp_sgprb_predict_source's workspace: descriptor block, the batched factorisation's own, then per window
 // K -> L, W = L^-1, K_p(X, Xnew), one feature table, the two [rb][n] partials, V = W y and the scalars
 struct SgbSrcWin { double *L, *W, *Kx, *feat, *s1, *dot, *V, *scal; };

@@ -35,6 +35,23 @@
 //   7. ssms_gather_kernel      mean / var [P][n] through out_step
 // Determinism: no atomics, every sum in a fixed order; a window is one workgroup and reads nothing of the others', so its
 // result is bit-identical between calls and whatever shares the launch.
+//
+// The score (ssm_score_run: the gradient of loglik in [noise | theta_0 | ...]).  Timeline = the N training frames,
+// launches 1 - 4 and 6 as above with the history on, then
+//   8. ssms_score_kernel       the backward walk's shape with every step wanted.  Before step j + 1's (r, Nm) are propagated to
+//                              step j:  P+ = P^-_j - g g^T / F,  a+ = a^-_j + g e / F,  phi = phi_(j+1),
+//                                gphi[j+1][i] = r_i a+_i + sum_k (r_i r_k - Nm_ik) phi_k P+_ik,    gq[j+1][i] = (r_i^2 - Nm_ii) / 2
+//                              then with the propagated pair:  k = g / F, u = Nm k, kr = k.r, ku = k.u, uu = e / F - kr,
+//                              Fb = (uu^2 - (1 / F + ku)) / 2:   gs2 += Fb,  gres[j] = -uu (= d loglik / d y_j),
+//                                gh[j] = uu a^- + P^- (uu r + u + Fb h) + Fb g
+//                              and the backward walk's update.  After step 0: gv0[i] = (r_i^2 - Nm_ii) / 2 (the start diag(v)).
+//                              u and the scalars come from the unpropagated row (u_i = phi_i sum_k Nm_ik phi_k k_k), so that
+//                              ONE pass over row i of P^-_j feeds both row sums.
+//   9. ssms_score_reduce_kernel  one workgroup per (window, parameter): for the coordinates i of source p, D_j = t_j - t_(j-1),
+//                                d/d v_p = sum_(j,i) gq[j][i] q_j / v_p + sum_i gv0[i]        (q_j / v_p = 1 - phi^2)
+//                                d/d l_p = sum_(j,i) (gphi[j][i] - 2 v_p phi gq[j][i]) phi D_j / l_p^2
+//                                d/d e_k = sum_j (gh_c h_c + gh_s h_s) / (2 e_k),   d/d f_k = sum_j 2 pi t_j (gh_s h_c - gh_c h_s)
+//                              and d/d noise = gs2; one more workgroup per window scatters gres through `order`.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -64,6 +81,26 @@ struct SsmsMeta {
   int crow[SSMS_MAX_D];                            // coordinate i's row among the window's feature rows, -1: h = 1 (Matern12)
   int csrc[SSMS_MAX_D];                            // coordinate i's source
 };
+
+// the score's own blocks of a window (beside its SsmsWin)
+struct SsmsScoreWin {
+  double *gphi, *gq, *gh;                          // [steps][d]; row 0 of gphi and gq is never written nor read
+  double *gres, *gs2, *gv0;                        // [steps], one, [d]
+  double *grad, *resid;                            // the caller's: [num_params], [N] or null
+};
+// what entry q of a parameter row is: a source has at most 2 + its components entries, so 1 + 3 * 128 cover a row
+#define SSMS_MAX_PARAMS (1 + 3 * SSMS_MAX_D)
+enum { SSMS_PAR_NONE = 0, SSMS_PAR_NOISE, SSMS_PAR_VARIANCE, SSMS_PAR_LENGTHSCALE, SSMS_PAR_ENERGY, SSMS_PAR_FREQUENCY };
+struct SsmsScoreMeta {
+  int nparams;
+  int kind[SSMS_MAX_PARAMS];
+  int src[SSMS_MAX_PARAMS];                        // the entry's source
+  int coord[SSMS_MAX_PARAMS];                      // energy / frequency: the partial's cosine coordinate (its sine: + 1)
+};
+// columns of P^- the score walk fetches at a time (a measurement variant may set its own: tools/build_variant.sh)
+#ifndef SSMS_SCORE_BATCH
+#define SSMS_SCORE_BATCH (DP == 64 ? 8 : 16)
+#endif
 
 static inline bool ssms_kernel_ok(int type) {
   return type == GP_KERN_MATERN12 || type == GP_KERN_MERCER_MATERN12SM || type == GP_KERN_MATERN12SM;
@@ -308,6 +345,158 @@ __global__ void __launch_bounds__(256) ssms_gather_kernel(const SsmsWin* __restr
   w.var[(size_t)p * n + i0 + c] = w.svar[(size_t)p * w.steps + s];
 }
 
+// ---- 8. score: thread i = row i of Nm, every step observed -------------------------------------------------------------------
+// Barriers as in the backward walk: hb / cb alternate between two buffers; ub, zb and red are written behind the step's first
+// barrier and read behind a later one of the same step.  cb[k] = (k_k, phi_k r_k, phi_k, phi_k k_k): what the row sums take of
+// column k, one 32-byte record.  Lanes i >= d and columns k >= d carry zeros (h = phi = g = 0 there).  `nmd` is Nm_ii, carried
+// beside the row by the row's own operations.
+template <int DP>
+__global__ void __launch_bounds__(DP) ssms_score_kernel(const SsmsWin* __restrict__ wins, const SsmsScoreWin* __restrict__ swins,
+                                                        const SsmsMeta* __restrict__ mt) {
+  constexpr int NW = DP / 64;
+  constexpr int NB = SSMS_SCORE_BATCH;
+  __shared__ double hb[2][DP], cb[2][DP][4], ub[DP], zb[DP], red[NW][2];
+  const SsmsWin w = wins[blockIdx.x];
+  const SsmsScoreWin s = swins[blockIdx.x];
+  const int i = threadIdx.x, d = mt->d, np = mt->P, steps = w.steps;
+  const bool on = i < d;
+  const int src = on ? mt->csrc[i] : 0;
+  const size_t dd = (size_t)d * d;
+  double Nm[DP];
+#pragma unroll
+  for (int k = 0; k < DP; k++) Nm[k] = 0.0;
+  double r = 0.0, nmd = 0.0, gs2 = 0.0;
+  // the values of step j - 1 are loaded while step j is computed; `pn` is phi of the step above (the transition into step j + 1)
+  int j = steps - 1;
+  double hn = on ? w.hrow[(size_t)j * d + i] : 0.0, pn = on ? 1.0 : 0.0, an = on ? w.am[(size_t)j * d + i] : 0.0;
+  double gn = on ? w.g[(size_t)j * d + i] : 0.0, en = w.ef[2 * (size_t)j], Fn = w.ef[2 * (size_t)j + 1];
+  for (; j >= 0; j--) {
+    const int b = j & 1;
+    const double hh = hn, ph = pn, am = an, g = gn, e = en, F = Fn;
+    if (j > 0) {
+      const size_t j1 = (size_t)j - 1;
+      hn = on ? w.hrow[j1 * d + i] : 0.0;
+      pn = on ? w.phi[(size_t)j * np + src] : 0.0;
+      an = on ? w.am[j1 * d + i] : 0.0;
+      gn = on ? w.g[j1 * d + i] : 0.0;
+      en = w.ef[2 * j1]; Fn = w.ef[2 * j1 + 1];
+    }
+    const double c = 1.0 / F, kk = g * c, pr = ph * r;
+    hb[b][i] = hh;
+    cb[b][i][0] = kk; cb[b][i][1] = pr; cb[b][i][2] = ph; cb[b][i][3] = ph * kk;
+    const double* __restrict__ Pj = w.Pm + (size_t)j * dd + i;
+    __syncthreads();
+    // u = (phi Nm phi) k from the unpropagated row: four chains, added in a fixed order
+    double u;
+    {
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+      for (int k = 0; k < DP; k += 4) {
+        a0 = fma(Nm[k], cb[b][k][3], a0); a1 = fma(Nm[k + 1], cb[b][k + 1][3], a1);
+        a2 = fma(Nm[k + 2], cb[b][k + 2][3], a2); a3 = fma(Nm[k + 3], cb[b][k + 3][3], a3);
+      }
+      u = ph * ((a0 + a1) + (a2 + a3));
+    }
+    double x1 = kk * u, x2 = kk * pr;              // k.u and k.r of the propagated pair
+    ssms_wave_sum2(x1, x2);
+    if (NW > 1) {
+      if ((i & 63) == 0) { red[i >> 6][0] = x1; red[i >> 6][1] = x2; }
+      __syncthreads();
+      x1 = red[0][0] + red[NW - 1][0]; x2 = red[0][1] + red[NW - 1][1];
+    }
+    const double cc = x1 + c, uu = e * c - x2, Fb = 0.5 * (uu * uu - cc);
+    ub[i] = u;
+    zb[i] = fma(uu, pr, fma(Fb, hh, u));
+    __syncthreads();
+    // one pass over row i of P^-_j, NB loads in flight: the transition sum (the unpropagated row) and P^- z
+    double at = 0.0, az = 0.0;
+#pragma unroll
+    for (int kb0 = 0; kb0 < DP; kb0 += NB) {
+      if (kb0 < d) {                               // (the same for the whole workgroup)
+        double pv[NB];
+#pragma unroll
+        for (int q = 0; q < NB; q++) pv[q] = (on && kb0 + q < d) ? Pj[(size_t)(kb0 + q) * d] : 0.0;
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+          const int k = kb0 + q;
+          const double pp = fma(-g, cb[b][k][0], pv[q]);                          // P+_ik
+          const double co = fma(r, cb[b][k][1], -(Nm[k] * cb[b][k][2]));          // (r_i r_k - Nm_ik) phi_k
+          at = fma(co, pp, at);
+          az = fma(pv[q], zb[k], az);
+        }
+      }
+    }
+    if (on) {
+      if (j + 1 < steps) {
+        s.gphi[((size_t)j + 1) * d + i] = fma(r, fma(g, e * c, am), at);
+        s.gq[((size_t)j + 1) * d + i] = 0.5 * (r * r - nmd);
+      }
+      s.gh[(size_t)j * d + i] = fma(uu, am, az) + Fb * g;
+    }
+    if (i == 0) s.gres[j] = -uu;
+    gs2 += Fb;
+    // propagate, then the update of the backward walk
+#pragma unroll
+    for (int k = 0; k < DP; k++)
+      Nm[k] = fma(ph * cb[b][k][2], Nm[k], fma(hh, fma(hb[b][k], cc, -ub[k]), -(u * hb[b][k])));
+    nmd = fma(ph * ph, nmd, fma(hh, fma(hh, cc, -u), -(u * hh)));
+    r = fma(hh, e * c - x2, pr);
+  }
+  if (on) s.gv0[i] = 0.5 * (r * r - nmd);
+  if (i == 0) s.gs2[0] = gs2;
+}
+
+// ---- 9. the chain rule: workgroup (window, q) sums entry q of the window's gradient, thread t the items t, t + 256, ... in
+// order, then a tree; workgroup (window, nparams) scatters gres to training-frame order --------------------------------------
+__global__ void __launch_bounds__(256) ssms_score_reduce_kernel(const SsmsWin* __restrict__ wins, const SsmsScoreWin* __restrict__ swins,
+                                                               const SsmsMeta* __restrict__ mt, const SsmsScoreMeta* __restrict__ sm) {
+  __shared__ double red[256];
+  const SsmsWin w = wins[blockIdx.x];
+  const SsmsScoreWin s = swins[blockIdx.x];
+  const int q = blockIdx.y, tid = threadIdx.x, d = mt->d, np = mt->P, steps = w.steps;
+  if (q >= sm->nparams) {
+    if (s.resid)
+      for (int j = tid; j < steps; j += 256) s.resid[w.order[j]] = s.gres[j];
+    return;
+  }
+  const int kind = sm->kind[q], p = sm->src[q];
+  double a = 0.0;
+  if (kind == SSMS_PAR_NOISE) {
+    if (tid == 0) a = s.gs2[0];
+  } else if (kind == SSMS_PAR_VARIANCE || kind == SSMS_PAR_LENGTHSCALE) {
+    const int k0 = mt->coff[p], cp = mt->coff[p + 1] - k0;
+    const double v = w.params[mt->toff[p]], l = w.params[mt->toff[p] + 1];
+    const size_t items = (size_t)steps * cp;
+    for (size_t it = tid; it < items; it += 256) {
+      const size_t j = it / cp;
+      const int i = k0 + (int)(it % cp);
+      if (j == 0) {
+        if (kind == SSMS_PAR_VARIANCE) a += s.gv0[i];
+      } else if (kind == SSMS_PAR_VARIANCE) {
+        a += s.gq[j * d + i] * (w.q[j * np + p] / v);
+      } else {
+        const double phi = w.phi[j * np + p], dt = fmax(w.t[j] - w.t[j - 1], 0.0);
+        a += (s.gphi[j * d + i] - 2.0 * v * phi * s.gq[j * d + i]) * (phi * dt / (l * l));
+      }
+    }
+  } else if (kind == SSMS_PAR_ENERGY || kind == SSMS_PAR_FREQUENCY) {
+    const int c = sm->coord[q];
+    for (int j = tid; j < steps; j += 256) {
+      const double hc = w.hrow[(size_t)j * d + c], hs = w.hrow[(size_t)j * d + c + 1];
+      const double gc = s.gh[(size_t)j * d + c], gs = s.gh[(size_t)j * d + c + 1];
+      a += kind == SSMS_PAR_ENERGY ? gc * hc + gs * hs : w.t[j] * (gs * hc - gc * hs);
+    }
+    a *= kind == SSMS_PAR_ENERGY ? 0.5 / w.params[q] : 6.283185307179586;
+  }
+  red[tid] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) s.grad[q] = red[0];
+}
+
 // ==== host ===================================================================================================================
 struct SsmsDesc { size_t wins, meta, feat, bytes; };
 static SsmsDesc ssms_desc_layout(size_t count, size_t P) {
@@ -348,12 +537,42 @@ size_t ssm_smooth_workspace_bytes(int d, int steps, int P, int count) {
   return gp_measure([&](GpArena& ar) { ssms_carve(ar, d, steps, P, count); }) + GP_WS_TAIL_OP;
 }
 
+// the score's carve: the smoother's, then its own descriptor block and per-step terms
+struct SsmsScoreDesc { size_t wins, meta, bytes; };
+static SsmsScoreDesc ssms_score_desc_layout(size_t count) {
+  SsmsScoreDesc o;
+  GpRegions region;
+  o.wins = region(count * sizeof(SsmsScoreWin));
+  o.meta = region(sizeof(SsmsScoreMeta));
+  o.bytes = region.off;
+  return o;
+}
+struct SsmsScoreBufs { char* desc; double *gphi, *gq, *gh, *gres, *gs2, *gv0; };
+static SsmsScoreBufs ssms_score_carve(GpArena& ar, size_t d, size_t steps, size_t count) {
+  SsmsScoreBufs b;
+  b.desc = ar.take<char>(ssms_score_desc_layout(count).bytes);
+  b.gphi = ar.take<double>(count * steps * d);
+  b.gq = ar.take<double>(count * steps * d);
+  b.gh = ar.take<double>(count * steps * d);
+  b.gres = ar.take<double>(count * steps);
+  b.gs2 = ar.take<double>(count);
+  b.gv0 = ar.take<double>(count * d);
+  return b;
+}
+
+size_t ssm_score_workspace_bytes(int d, int steps, int P, int count) {
+  if (d < 1 || d > SSMS_MAX_D || steps < 1 || P < 1 || P > d || count < 1) return 0;
+  return gp_measure([&](GpArena& ar) { ssms_carve(ar, d, steps, P, count); ssms_score_carve(ar, d, steps, count); }) + GP_WS_TAIL_OP;
+}
+
 // Every check, then the launches.  Windows w < count: params + w * param_stride, X / Y + w * N, Xnew + w * n, order_host
 // + w * (N + n) (the first steps_host[w] entries), out_step_host + w * n, mean / var + w * P * n, loglik + w.
-gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
-                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
-                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
-                         double* var, double* loglik, void* ws, size_t ws_bytes) {
+// (`score`: the call is ssm_score_run's; n = 0, the history is kept and launches 8 and 9 follow the forward walk)
+struct SsmsScoreOut { double* grad; double* resid; };
+static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                          const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                          const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
+                          double* var, double* loglik, void* ws, size_t ws_bytes, const SsmsScoreOut* score) {
   if (!params || !X || !Y || !order_host || !steps_host || !loglik || !ws || N < 1 || n < 0 || count < 1 || P < 1)
     return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: bad argument (N >= 1, n >= 0, no null pointers)");
   if (n > 0 && (!Xnew || !out_step_host || !mean || !var))
@@ -379,7 +598,16 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
       return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: steps must be in [N, N + n]");
     steps = std::max(steps, (int)steps_host[w]);
   }
-  if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_smooth_workspace_bytes(d, steps, P, count))
+  if (score) {
+    if (param_stride < 1 || param_stride > SSMS_MAX_PARAMS)
+      return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space score: the parameter row is longer than 1 + 3 * 128 entries");
+    for (int p = 0; p < P; p++)
+      if (off_theta[p] < 1 || off_theta[p] + 2 + (ktype[p] == GP_KERN_MATERN12 ? 0 : 2 * km[p]) > param_stride)
+        return gp_fail(h, GP_ERR_BAD_ARG, "state-space score: a source's parameters lie outside the parameter row");
+    if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_score_workspace_bytes(d, steps, P, count))
+      return gp_fail(h, GP_ERR_BAD_ARG, "state-space score: workspace too small for steps * d^2 doubles of history per window "
+                                        "(gp_ssm_score_workspace_bytes) or not 256-byte aligned");
+  } else if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_smooth_workspace_bytes(d, steps, P, count))
     return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small for steps * d^2 doubles of history per window "
                                       "(gp_ssm_smooth_workspace_bytes) or not 256-byte aligned");
   // `order` and `out_step` become device addresses
@@ -410,6 +638,8 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
   }
   GpArena ar(ws, ws_bytes);
   const SsmsBufs b = ssms_carve(ar, d, steps, P, count);
+  SsmsScoreBufs sb{};
+  if (score) sb = ssms_score_carve(ar, d, steps, count);
   if (!ar.ok) return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small");
   const SsmsDesc lay = ssms_desc_layout(count, P);
   std::vector<char> hd(lay.bytes, 0);
@@ -447,7 +677,7 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
     sw.Pm = b.Pm + s0 * d * d; sw.smean = b.smean + s0 * P; sw.svar = b.svar + s0 * P;
     sw.mean = n > 0 ? mean + (size_t)w * P * n : nullptr; sw.var = n > 0 ? var + (size_t)w * P * n : nullptr;
     sw.loglik = loglik + w;
-    sw.steps = steps_host[w]; sw.hist = n > 0;
+    sw.steps = steps_host[w]; sw.hist = n > 0 || score;
     memcpy(order_dev.data() + s0, order_host + (size_t)w * (N + n), (size_t)sw.steps * sizeof(int));
     for (int p = 0; p < P; p++)
       feats[(size_t)p * count + w] = FeatItem{DevKern{ktype[p], km[p], sw.params + off_theta[p]}, sw.t,
@@ -456,6 +686,32 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
   GP_HIP_CHECK(h, hipMemcpyAsync(b.desc, hd.data(), lay.bytes, hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipMemcpyAsync(b.order, order_dev.data(), order_dev.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   GP_HIP_CHECK(h, hipMemcpyAsync(b.want, want.data(), want.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  std::vector<char> hs;                                   // the score's descriptor block
+  const SsmsScoreDesc slay = ssms_score_desc_layout(count);
+  if (score) {
+    hs.assign(slay.bytes, 0);
+    SsmsScoreWin* swins = (SsmsScoreWin*)(hs.data() + slay.wins);
+    SsmsScoreMeta* sm = (SsmsScoreMeta*)(hs.data() + slay.meta);
+    sm->nparams = (int)param_stride;
+    sm->kind[0] = SSMS_PAR_NOISE;
+    for (int p = 0; p < P; p++) {
+      const int o = (int)off_theta[p], mp = ktype[p] == GP_KERN_MATERN12 ? 0 : km[p];
+      for (int e = 0; e < 2 + 2 * mp; e++) {
+        sm->kind[o + e] = e == 0 ? SSMS_PAR_VARIANCE : e == 1 ? SSMS_PAR_LENGTHSCALE : e < 2 + mp ? SSMS_PAR_ENERGY : SSMS_PAR_FREQUENCY;
+        sm->src[o + e] = p;
+        sm->coord[o + e] = e < 2 ? 0 : mt->coff[p] + 2 * ((e - 2) % mp);
+      }
+    }
+    for (int w = 0; w < count; w++) {
+      SsmsScoreWin& s = swins[w];
+      const size_t s0 = (size_t)w * steps;
+      s.gphi = sb.gphi + s0 * d; s.gq = sb.gq + s0 * d; s.gh = sb.gh + s0 * d; s.gres = sb.gres + s0;
+      s.gs2 = sb.gs2 + w; s.gv0 = sb.gv0 + (size_t)w * d;
+      s.grad = score->grad + (size_t)w * param_stride;
+      s.resid = score->resid ? score->resid + (size_t)w * N : nullptr;
+    }
+    GP_HIP_CHECK(h, hipMemcpyAsync(sb.desc, hs.data(), slay.bytes, hipMemcpyHostToDevice, h->stream));
+  }
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // the three are host vectors
   const SsmsWin* d_wins = (const SsmsWin*)(b.desc + lay.wins);
   const SsmsMeta* d_meta = (const SsmsMeta*)(b.desc + lay.meta);
@@ -489,10 +745,44 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
       GP_HIP_CHECK(h, hipGetLastError());
     }
   }
+  if (score) {
+    const SsmsScoreWin* d_swins = (const SsmsScoreWin*)(sb.desc + slay.wins);
+    const SsmsScoreMeta* d_smeta = (const SsmsScoreMeta*)(sb.desc + slay.meta);
+    if (narrow) hipLaunchKernelGGL(ssms_score_kernel<64>, dim3(count), dim3(64), 0, h->stream, d_wins, d_swins, d_meta);
+    else hipLaunchKernelGGL(ssms_score_kernel<128>, dim3(count), dim3(128), 0, h->stream, d_wins, d_swins, d_meta);
+    GP_HIP_CHECK(h, hipGetLastError());
+    hipLaunchKernelGGL(ssms_score_reduce_kernel, dim3(count, (unsigned)param_stride + 1), dim3(256), 0, h->stream, d_wins, d_swins,
+                       d_meta, d_smeta);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
   GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
   return GP_OK;
 }
 
+gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
+                         double* var, double* loglik, void* ws, size_t ws_bytes) {
+  return ssms_run(h, ktype, km, off_theta, P, param_stride, params, X, Y, N, Xnew, n, count, order_host, out_step_host, steps_host,
+                  mean, var, loglik, ws, ws_bytes, nullptr);
+}
+
+// loglik [count], grad [count][param_stride] and, if not null, resid_grad [count][N] = d loglik / d Y of windows w < count, whose
+// timelines are their N training frames: order_host + w * N, a permutation of 0 .. N - 1 in ascending time
+gp_status ssm_score_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                        const double* params, const double* X, const double* Y, int N, int count, const int32_t* order_host,
+                        double* loglik, double* grad, double* resid_grad, void* ws, size_t ws_bytes) {
+  if (!grad || N < 1 || count < 1)
+    return gp_fail(h, GP_ERR_BAD_ARG, "state-space score: bad argument (N >= 1, no null pointers but resid_grad)");
+  const std::vector<int32_t> steps((size_t)count, N);
+  const SsmsScoreOut out{grad, resid_grad};
+  return ssms_run(h, ktype, km, off_theta, P, param_stride, params, X, Y, N, nullptr, 0, count, order_host, nullptr, steps.data(),
+                  nullptr, nullptr, loglik, ws, ws_bytes, &out);
+}
+
 extern "C" size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count) {
   return ssm_smooth_workspace_bytes(d, steps, P, count);
+}
+extern "C" size_t gp_ssm_score_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count) {
+  return ssm_score_workspace_bytes(d, steps, P, count);
 }

@@ -521,6 +521,53 @@ class SGPRSS(Parameterized):
         under the square root) in about the fifth significant digit.  Same scope as predict_s_ssm."""
         return float(self._ssm_call(np.zeros(0), "exact_log_likelihood")[2].sum())
 
+    def _exact_setup(self, who):
+        """what an evaluation of the exact likelihood and its gradient needs beside the parameters: the timeline of the
+        training frames, the workspace and the result buffers.  Raises before any device work (scope as predict_s_ssm)."""
+        if self._shard:
+            raise NotImplementedError("%s: a frame-sharded window has no exact likelihood (the state-space walk is sequential "
+                                      "in the frames): build the model unsharded on one GPU" % who)
+        d, P = ssm_state_dim(self.kern.kern_list, who)
+        N = self.X.shape[0]
+        order = np.ascontiguousarray(np.argsort(self.X._array.reshape(-1), kind="stable").astype(np.int32))
+        self._compile()
+        self._pack()
+        h = self._handle
+        ex = {"N": N, "order": order, "ws": h.workspace(h.lib.gp_ssm_score_workspace_bytes(d, N, P, 1)), "ll": h.empty(1),
+              "grad": h.empty(self._nparams), "resid": h.empty(N) if self._mean_params() else None}
+        object.__setattr__(self, "_exact_st", ex)
+        return ex
+
+    def _exact_eval(self, ex, mean_grad):
+        """(log-likelihood, its gradient in the engine's parameters, the mean function's entries) at the device's `_params` and
+        residual columns: the sum over the D columns of gp_sgpr_exact_loglik_grad"""
+        h = self._handle
+        value, g = 0.0, np.zeros(self._nparams)
+        mps = self._mean_params()
+        gm = np.zeros(len(mps))
+        r = ex["resid"] if mean_grad else None
+        for _ in self._columns():
+            h.check(h.lib.gp_sgpr_exact_loglik_grad(self._plan, self._params.data_ptr(), self._Xd.data_ptr(), self._Yd.data_ptr(),
+                                                    ex["N"], ex["order"].ctypes.data, ex["ll"].data_ptr(), ex["grad"].data_ptr(),
+                                                    r.data_ptr() if r is not None else None, ex["ws"].data_ptr(),
+                                                    ex["ws"].numel()))
+            value += float(ex["ll"].cpu().numpy()[0])
+            g += ex["grad"].cpu().numpy()
+            if r is not None:
+                gm += np.concatenate(self.mean_function.grad_from_residual(self.X._array, r.cpu().numpy()))
+        return value, g, gm
+
+    def exact_log_likelihood_and_grad(self):
+        """(exact_log_likelihood(), its gradient over _param_list() in constrained parameters): noise variance, every
+        kernel's variance, lengthscale, energies and frequencies, then the mean function's Params.  One forward walk with
+        its history and one backward walk that carries the score (gp_sgpr_exact_loglik_grad), O(N d^2) per column, summed
+        over the D columns; Z plays no part.  The value has the bits of exact_log_likelihood().  Same scope as
+        predict_s_ssm."""
+        ex = self._exact_setup("exact_log_likelihood_and_grad")
+        value, g, gm = self._exact_eval(ex, bool(self._mean_params()))
+        object.__setattr__(self, "_exact_st", None)
+        return value, np.concatenate([g, gm])
+
     def sample_s_sparse(self, Xnew, num_samples=1, seed=None, eps=None):
         """Joint posterior draws of every source at Xnew under the q(u) of predict_s_sparse: a list of P arrays
         (num_samples, n, D).  A draw is joint across the n frames and across the P sources (gp_sgpr_sample_source_sparse:
@@ -663,15 +710,50 @@ class SGPRSS(Parameterized):
             g = np.concatenate([g, gm])
         return -value, -(g[st["free_idx"]] * dy)
 
-    def optimize(self, method='L-BFGS-B', tol=None, callback=None, maxiter=1000, disp=False, **kw):
+    def _objective_exact(self, x_free):
+        """(-(exact log-likelihood), -d / d free-state): _objective with the state-space score in the bound's place"""
+        st, ex = self._obj_state, self._exact_st
+        y, dy = self._free_to_params(st, x_free)
+        vals = st["vals0"].copy()
+        vals[st["free_idx"]] = y
+        nd = self._nparams
+        mps = self._mean_params()
+        train_mean = bool(mps) and bool(np.any(st["free_idx"] >= nd))
+        if train_mean:
+            for p_, v in zip(mps, vals[nd:]):
+                p_._array = np.array([v], dtype=np.float64)
+            self._upload_err()
+        self._dev("_params", vals[:nd])
+        value, g, gm = self._exact_eval(ex, train_mean)
+        g = np.concatenate([g, gm])
+        return -value, -(g[st["free_idx"]] * dy)
+
+    def optimize(self, method='L-BFGS-B', tol=None, callback=None, maxiter=1000, disp=False, objective="bound", **kw):
+        """GPflow's Model.optimize on the free state.  objective="bound" (the default) climbs the collapsed bound of
+        build_likelihood; objective="exact" climbs exact_log_likelihood() by its exact gradient
+        (exact_log_likelihood_and_grad): same driver, transforms and .fixed handling, Z plays no part, res.fun is minus the
+        exact log-likelihood.  "exact" has the scope of predict_s_ssm and takes neither a frame-sharded window nor reg=True
+        (the L1 term belongs to the bound): NotImplementedError before any device work."""
         from scipy.optimize import minimize
-        self._compile()
-        self._pack()
+        if objective not in ("bound", "exact"):
+            raise ValueError('optimize: objective is "bound" or "exact"')
+        exact = objective == "exact"
+        if exact:
+            if self.reg:
+                raise NotImplementedError('optimize(objective="exact"): reg=True adds its L1 term to the collapsed bound; the '
+                                          'exact likelihood has none (build the model with reg=False)')
+            self._exact_setup('optimize(objective="exact")')
+        else:
+            self._compile()
+            self._pack()
         st = self._objective_setup()
         ps, free_idx = st["ps"], st["free_idx"]
         x0 = np.array([ps[i].transform.backward(ps[i].value)[0] for i in free_idx])
-        res = minimize(self._objective, x0, jac=True, method=method, tol=tol, callback=callback,
-                       options=dict(maxiter=maxiter, disp=disp))
+        try:
+            res = minimize(self._objective_exact if exact else self._objective, x0, jac=True, method=method, tol=tol,
+                           callback=callback, options=dict(maxiter=maxiter, disp=disp))
+        finally:
+            object.__setattr__(self, "_exact_st", None)
         y, _ = self._free_to_params(st, res.x)
         for j, i in enumerate(free_idx):
             ps[i].value = y[j:j + 1]

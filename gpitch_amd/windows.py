@@ -155,6 +155,7 @@ class SgprWindowBatch(object):
             self._ragged = ragged
         self.count = n
         self.counts = counts
+        self._exact_order = None
 
     def submit(self, params_host, with_grad=True):
         """enqueue one evaluation (parameter upload, the launch sequence, result download) and return at once; `collect`
@@ -301,6 +302,44 @@ class SgprWindowBatch(object):
                                                       ws.data_ptr(), ws.numel()))
         out = (mean.cpu().numpy(), var.cpu().numpy())
         return out + (ll.cpu().numpy(),) if return_loglik else out
+
+    def exact_loglik_grad(self, params_host, with_grad=True, chunk=None):
+        """SGPRSS.exact_log_likelihood_and_grad of every loaded window at its constrained parameter vector params_host[i]
+        (gp_sgprb_exact_loglik_grad: one workgroup per window): (loglik (count,), grad (count, nparams)); with_grad=False
+        runs the forward walk alone and returns (loglik, None).  `chunk` windows share a launch sequence (default: as many as
+        keep the forward walk's history below sgpr_ss.MAX_SSM_BYTES); chunking changes no bit of any window's result.  Z, the
+        windows' inducing counts and the plan's precision play no part.  Synchronous."""
+        from . import sgpr_ss
+        h = self.h
+        cnt, N = self.count, self.N
+        codes = list(zip(self._keep[0], self._keep[1]))
+        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.exact_loglik_grad")    # raises before any device work
+        if self._exact_order is None:
+            xh = self.X[:cnt].cpu().numpy()
+            self._exact_order = np.ascontiguousarray(np.argsort(xh, axis=1, kind="stable").astype(np.int32))
+        order = self._exact_order
+        steps = np.full(cnt, N, dtype=np.int32)
+        size = h.lib.gp_ssm_score_workspace_bytes if with_grad else h.lib.gp_ssm_smooth_workspace_bytes
+        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        if chunk is None:
+            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // max(1, int(size(d, N, P, 1))))
+        chunk = int(max(1, min(int(chunk), cnt)))
+        ws = h.workspace(size(d, N, P, chunk))
+        ll = h.empty(cnt)
+        grad = h.empty(cnt, self.nparams) if with_grad else None
+        for b0 in range(0, cnt, chunk):
+            c = min(chunk, cnt - b0)
+            if with_grad:
+                h.check(h.lib.gp_sgprb_exact_loglik_grad(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
+                                                         self.Y[b0:].data_ptr(), c, order[b0:].ctypes.data, ll[b0:].data_ptr(),
+                                                         grad[b0:].data_ptr(), None, ws.data_ptr(), ws.numel()))
+            else:
+                h.check(h.lib.gp_sgprb_predict_source_ssm(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
+                                                          self.Y[b0:].data_ptr(), None, 0, c, order[b0:].ctypes.data, None,
+                                                          steps[b0:].ctypes.data, None, None, ll[b0:].data_ptr(),
+                                                          ws.data_ptr(), ws.numel()))
+        return ll.cpu().numpy(), (grad.cpu().numpy() if with_grad else None)
 
     def sample_s_sparse(self, params_host, xnews=None, num_samples=1, seed=None, eps=None):
         """SGPRSS.sample_s_sparse (joint posterior draws of every source, gp_sgprb_sample_source_sparse) of every loaded
@@ -624,6 +663,80 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
             ms, vs = model.predict_s_sparse(x) if sparse else (model.predict_s_ssm(x) if ssm else model.predict_s(x))
             results[i].update(mean=m1, var=v1, smean=list(ms), svar=list(vs))
     model._destroy()
+    return results
+
+
+def fit_windows_exact(make_model, windows, maxiter=10, batch=64, params0=None, handle=None):
+    """Fit every window (x_i, y_i[, z_i]) by exact maximum likelihood: SGPRSS.optimize(objective="exact") of each window,
+    `batch` windows going through every evaluation of the exact log-likelihood and its gradient together
+    (SgprWindowBatch.exact_loglik_grad), each driven by its own instance of scipy's L-BFGS-B routine
+    (lbfgsb_batch.minimize_many: the iterates of the window's own optimize, given the same f and g).  Inducing inputs play no
+    part: a window's z is ignored.
+
+    Every window starts from the parameter values of make_model(handle), or from params0[i] (constrained vector
+    [noise | theta_0 | ...]) when given; .fixed Params keep the template's values.  Windows must share N; the template must
+    have no mean function, reg=False and kernels in the scope of predict_s_ssm (NotImplementedError otherwise, before any
+    device work).  Synchronous: one evaluation at a time, no recorded graph, no batches in flight.
+    Returns a list over windows of dicts: loglik, nfev, nit, variances, noise, params."""
+    from . import _lib, lbfgsb_batch
+    from .sgpr_ss import SGPRSS, ssm_state_dim
+    if not lbfgsb_batch.available():
+        raise RuntimeError("fit_windows_exact needs scipy >= 1.15 (its reverse-communication L-BFGS-B routine)")
+    results = [None] * len(windows)
+    if not len(windows):
+        return results
+    N = int(np.asarray(windows[0][0]).size)
+    for w in windows:
+        if np.asarray(w[0]).size != N or np.asarray(w[1]).size != N:
+            raise ValueError("fit_windows_exact: all windows must have the same number of frames (one output column)")
+    model = make_model(handle)
+    if getattr(model, "mean_function", None) is not None and type(model.mean_function).__name__ != "Zero":
+        raise NotImplementedError("fit_windows_exact: the template model has a mean_function; the batched plan has none "
+                                  '(use optimize(objective="exact") per window)')
+    if getattr(model, "_shard", None):
+        raise NotImplementedError("fit_windows_exact: the template model is a frame-sharded window; the state-space walk is "
+                                  "sequential in the frames (build it unsharded)")
+    if model.reg:
+        raise NotImplementedError("fit_windows_exact: reg=True adds its L1 term to the collapsed bound; the exact likelihood "
+                                  "has none (build the template with reg=False)")
+    ssm_state_dim(model.kern.kern_list, "fit_windows_exact")
+    h = handle or model._handle or _lib.default_handle()
+    st = model._objective_setup()
+    ps, free_idx, vals0 = st["ps"], st["free_idx"], st["vals0"]
+    back = np.array([ps[i].transform.backward(np.atleast_1d(vals0[i]))[0] for i in free_idx])
+    var_idx = [int(o) for o in np.cumsum([1] + [2 + 2 * int(k.num_partials) for k in model.kern.kern_list])[:-1]]
+    z = model.Z._array.reshape(-1)
+    B = max(1, min(int(batch), len(windows)))
+    dev = SgprWindowBatch(model, B, N, z.size, handle=h)
+    try:
+        for b0 in range(0, len(windows), B):
+            ids = list(range(b0, min(b0 + B, len(windows))))
+            dev.load([windows[i][0] for i in ids], [windows[i][1] for i in ids], [z for _ in ids])
+            base = np.tile(vals0, (len(ids), 1))
+            x0s = [back.copy() for _ in ids]
+            if params0 is not None:
+                base = np.stack([np.asarray(params0[i], dtype=np.float64) for i in ids])
+                x0s = [np.array([ps[j].transform.backward(np.atleast_1d(base[q, j]))[0] for j in free_idx])
+                       for q in range(len(ids))]
+
+            def fg(Xf, active, base=base):
+                y, dy = SGPRSS._free_to_params(st, Xf)
+                pv = base.copy()
+                pv[:, free_idx] = y
+                ll, grad = dev.exact_loglik_grad(pv)
+                return -ll, -(grad[:, free_idx] * dy)
+
+            runs = lbfgsb_batch.minimize_many(fg, x0s, maxiter=maxiter)
+            yfin, _ = SGPRSS._free_to_params(st, np.stack([r.x for r in runs]))
+            pfin = base.copy()
+            pfin[:, free_idx] = yfin
+            for q, i in enumerate(ids):
+                results[i] = {"loglik": -runs[q].fun, "nfev": runs[q].nfev, "nit": runs[q].nit,
+                              "variances": pfin[q, var_idx].copy(), "noise": float(pfin[q, 0]), "params": pfin[q].copy()}
+    finally:
+        dev.close()
+        model._destroy()
+        object.__setattr__(model, "_obj_state", None)
     return results
 
 

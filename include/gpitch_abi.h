@@ -780,6 +780,23 @@ gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const
  * timeline of the call), measured.  0 for arguments outside 1 <= P <= d <= 128, steps >= 1, count >= 1. */
 size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count);
 
+/* The exact log marginal likelihood log p(y) of gp_sgpr_predict_source_ssm AND its gradient in the plan's parameter layout, in
+ * O(N d^2): the forward walk with its history, then a Bryson-Frazier walk over every step that carries the score (ssm_smooth.hip,
+ * DESIGN 3c-5).  Same scope and errors as gp_sgpr_predict_source_ssm; the timeline is the N training frames.
+ *   order_host   HOST, N entries: a permutation of 0 .. N - 1, the training frames in stable ascending order of time
+ *   loglik       one double (device): the bits gp_sgpr_predict_source_ssm writes with n = 0
+ *   grad         [gp_sgpr_num_params] (device): d loglik / d [noise variance | theta_0 | ...], constrained parameters
+ *   resid_grad   [N] (device) or null: d loglik / d Y in training-frame order (the chain to a mean function)
+ *   workspace    gp_ssm_score_workspace_bytes(d, N, P, 1) bytes, 256-byte aligned; a short one is GP_ERR_BAD_ARG
+ * Every check precedes the first launch.  float64 whatever the plan's precision.  Synchronises.  No atomics, every sum in a fixed
+ * order: two calls are bit-identical. */
+gp_status gp_sgpr_exact_loglik_grad(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                    const int32_t* order_host, double* loglik, double* grad, double* resid_grad, void* workspace,
+                                    size_t workspace_bytes);
+/* handle-free, runs without a device: the one carve of the score call (the smoother's carve and the per-step terms), measured.
+ * 0 for arguments outside 1 <= P <= d <= 128, steps >= 1, count >= 1. */
+size_t gp_ssm_score_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count);
+
 /* ---- many independent SGPRSS windows per launch sequence -------------------------------------------------------
  * replaces the window loop of AMT.optimize / SoSp.optimize (gpitch/transcription.py:265-288, gpitch/separation.py:279-313):
  * for each window, reset_model then model.optimize(maxiter) = a dozen-odd evaluations of SGPRSS.build_likelihood
@@ -846,6 +863,13 @@ gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan p, const double* params, con
                                       const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
                                       const int32_t* out_step_host, const int32_t* steps_host, double* mean, double* var,
                                       double* loglik, void* workspace, size_t workspace_bytes);
+
+/* gp_sgpr_exact_loglik_grad of the first `count` windows, one workgroup per window in the walks: params [count][num_params],
+ * X / Y [count][N], order_host [count][N] (HOST), loglik [count], grad [count][num_params], resid_grad [count][N] or null.
+ * workspace: gp_ssm_score_workspace_bytes(d, N, P, count).  A window's bits are those of the one-window call, whatever `count`. */
+gp_status gp_sgprb_exact_loglik_grad(gp_sgprb_plan p, const double* params, const double* X, const double* Y, int32_t count,
+                                     const int32_t* order_host, double* loglik, double* grad, double* resid_grad, void* workspace,
+                                     size_t workspace_bytes);
 
 /* ---- many small, independent Pdgp models per launch sequence ------------------------------------------------------
  * replaces the loop  for m in models: m.optimize(method=AdamOptimizer(...), maxiter)  over single-pitch models trained

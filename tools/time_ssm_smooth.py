@@ -5,12 +5,16 @@ GPU: a warm-up call of each arm, then `--reps` timed calls with the arms interle
          exact_log_likelihood (the forward walk alone)
   batch  256 such windows through SgprWindowBatch, the same three
   fit    fit_windows_batched (maxiter 10) with predict=True, "sparse" and "ssm", as windows/s
+  score  the exact likelihood's gradient: exact_log_likelihood_and_grad of the one window beside exact_log_likelihood
+         and predict_s_ssm at Xnew = X; SgprWindowBatch.exact_loglik_grad of the 256 windows beside its forward walk alone and
+         predict_s_ssm; fit_windows_exact (maxiter 10) beside fit_windows_batched as windows/s, with the mean exact
+         log-likelihood per window that each fit reaches
   cfg5   one window of N = 65536, 5 sources x 10 partials (d = 100), Xnew = X: predict_s_ssm next to predict_s_sparse (M = 512).
          predict_s cannot run there (one N x N float64 matrix is 34 GB) and is recorded as such.
 
 Writes one JSON file (default profiles/ssm/ssm_smooth_time.json) and prints it.  GPITCH_AMD_SWITCHES=ssm_wide=1 times the
 two-wavefront walks at d = 60 (the switch is read once per process; it is recorded in the output).
-python tools/time_ssm_smooth.py [--parts one,batch,fit,cfg5] [--reps 5] [--windows 256] [--out FILE]"""
+python tools/time_ssm_smooth.py [--parts one,batch,fit,cfg5,score] [--reps 5] [--windows 256] [--out FILE]"""
 import argparse
 import json
 import os
@@ -46,6 +50,13 @@ def _window(N, M, P, w):
     return X, Y, Z
 
 
+def _data_only(model, x, y, z):
+    """a `reset` for fit_windows_batched that keeps the template's parameter values (what fit_windows_exact starts from)"""
+    model.X = x
+    model.Y = y
+    model.Z = z
+
+
 def _time(arms, reps, sync):
     """{name: {"median_ms", "min_ms", "max_ms", "runs"}} of callables, interleaved after one warm-up call of each"""
     for _, f in arms:
@@ -78,7 +89,7 @@ def main():
     h = _lib.default_handle()
     out = {"device": torch.cuda.get_device_name(0), "switches": os.environ.get("GPITCH_AMD_SWITCHES", ""), "reps": a.reps}
     N, M, P, W = 2001, 64, 3, a.windows
-    wins = [_window(N, M, P, w) for w in range(W if ("batch" in parts or "fit" in parts) else 1)]
+    wins = [_window(N, M, P, w) for w in range(W if ("batch" in parts or "fit" in parts or "score" in parts) else 1)]
 
     def make(handle):
         return SGPRSS(wins[0][0], wins[0][1], np.sum(_kernels(P, 10)), wins[0][2], handle=handle)
@@ -114,6 +125,44 @@ def main():
             v["windows_per_s"] = W / (1e-3 * v["median_ms"])
         out["fit_windows_batched_%d_windows" % W] = res
         print("fit: done", file=sys.stderr, flush=True)
+    if "score" in parts:
+        from gpitch_amd.windows import fit_windows_exact
+        m = make(h)
+        X = wins[0][0]
+        out["score_one_window_N2001_d60"] = _time([("exact_log_likelihood_and_grad", lambda: m.exact_log_likelihood_and_grad()),
+                                                   ("exact_log_likelihood", lambda: m.exact_log_likelihood()),
+                                                   ("predict_s_ssm", lambda: m.predict_s_ssm(X))], a.reps, sync)
+        m._compile()
+        m._pack()
+        pv = np.tile(m._params.cpu().numpy(), (W, 1))
+        dev = SgprWindowBatch(m, W, N, M, handle=h)
+        dev.load([w[0] for w in wins], [w[1] for w in wins], [w[2] for w in wins])
+        res = _time([("exact_loglik_grad", lambda: dev.exact_loglik_grad(pv)),
+                     ("exact_loglik", lambda: dev.exact_loglik_grad(pv, with_grad=False)),
+                     ("predict_s_ssm", lambda: dev.predict_s_ssm(pv))], a.reps, sync)
+        for v in res.values():
+            v["windows_per_s"] = W / (1e-3 * v["median_ms"])
+        out["score_batch_%d_windows_N2001_d60" % W] = res
+        print("score, batch: done", file=sys.stderr, flush=True)
+        kept = {}
+
+        def fit(name, f):
+            kept[name] = f()
+
+        res = _time([("fit_windows_exact", lambda: fit("exact", lambda: fit_windows_exact(make, wins, maxiter=10, batch=W))),
+                     ("fit_windows_batched", lambda: fit("bound", lambda: fit_windows_batched(make, wins, maxiter=10, batch=W,
+                                                                                                reset=_data_only)))],
+                    max(3, a.reps // 2), sync)
+        for k, name in (("fit_windows_exact", "exact"), ("fit_windows_batched", "bound")):
+            res[k]["windows_per_s"] = W / (1e-3 * res[k]["median_ms"])
+            ll = dev.exact_loglik_grad(np.stack([r["params"] for r in kept[name]]), with_grad=False)[0]
+            res[k]["mean_exact_loglik_reached"] = float(np.mean(ll))
+            res[k]["mean_nfev"] = float(np.mean([r["nfev"] for r in kept[name]]))
+        res["mean_exact_loglik_at_start"] = float(np.mean(dev.exact_loglik_grad(pv, with_grad=False)[0]))
+        out["score_fit_%d_windows" % W] = res
+        dev.close()
+        m._destroy()
+        print("score, fit: done", file=sys.stderr, flush=True)
     if "cfg5" in parts:
         N5, M5, P5 = 65536, 512, 5
         X, Y, Z = _window(N5, M5, P5, 1)
