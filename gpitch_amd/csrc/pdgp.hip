@@ -113,78 +113,60 @@ gp_status gp_pdgp_set_overlap(gp_pdgp_plan p, int32_t level) {
   p->cb.overlap = (level >= 1);
   return GP_OK;
 }
-gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) {
-  if (!p) return GP_ERR_BAD_ARG;
-  if (p->frames_ascending != (ascending != 0)) { p->frames_ascending = (ascending != 0); p->last_params = nullptr; }   // the routes depend on the promise
-  return GP_OK;
-}
+gp_status gp_pdgp_set_frames_ascending(gp_pdgp_plan p, int32_t ascending) { return pdgp_set_perm(p, &PdgpPerms::frames_ascending, ascending != 0); }
+gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable) { return pdgp_set_perm(p, &PdgpPerms::afar_ok, enable != 0); }
+gp_status gp_pdgp_set_scan_far(gp_pdgp_plan p, int32_t enable) { return pdgp_set_perm(p, &PdgpPerms::scan_far_ok, enable != 0); }
+gp_status gp_pdgp_set_h_far(gp_pdgp_plan p, int32_t enable) { return pdgp_set_perm(p, &PdgpPerms::h_far_ok, enable != 0); }
 gp_status gp_pdgp_set_qform(gp_pdgp_plan p, int32_t enable) {
-  if (!p) return GP_ERR_BAD_ARG;
   // bit 0: the Q route is allowed; bit 1: every MercerMatern12sm GP's inducing inputs ascend (the far field of its product);
   // bit 2: the backward pass may form Qbar and v from that far field too
   const bool on = (enable & 1) != 0, zasc = on && (enable & 2) != 0, bar = zasc && (enable & 4) != 0;
-  if (p->qform != on || p->q_zasc != zasc || p->q_bar_ok != bar) { p->qform = on; p->q_zasc = zasc; p->q_bar_ok = bar; p->last_params = nullptr; }   // the descriptors depend on the route
-  return GP_OK;
+  (void)pdgp_set_perm(p, &PdgpPerms::qform, on); (void)pdgp_set_perm(p, &PdgpPerms::q_zasc, zasc);
+  return pdgp_set_perm(p, &PdgpPerms::q_bar_ok, bar);
 }
-int32_t gp_pdgp_far_field(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far) ? 1 : 0; }
-int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p) { return (p && p->nq > 0 && p->q_far && p->q_bar) ? 1 : 0; }
-// debug: the device's own ranges of the last evaluation, copied to the host (tests compare them with the numpy rule)
-int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref,
-                                 int32_t* rng2, int32_t* s0, int32_t* sa) {
-  if (!p || !p->ws || p->nq <= 0 || !p->q_far || i < 0 || i >= p->nq || p->last_n <= 0 || !rng || !ref) return 0;
-  const int ng = p->last_n / QFAR_GROUP, g = p->q0 + i, nt = p->gps[g].M / 16;
-  const BwdBufs& b = p->bw[g];
-  if (ng <= 0 || ng > cap_groups || !b.qf_rng || !b.qf_ref) return 0;
+// what the batch last bound takes (pdgp_decide_routes); the backward pass's forms: of a bind with a gradient
+int32_t gp_pdgp_far_field(gp_pdgp_plan p) { return (p && p->routes.nq > 0 && p->routes.q_far) ? 1 : 0; }
+int32_t gp_pdgp_far_field_backward(gp_pdgp_plan p) { return (gp_pdgp_far_field(p) && p->routes.q_bar) ? 1 : 0; }
+int32_t gp_pdgp_far_field_act(gp_pdgp_plan p) { return (p && p->routes.na > 0) ? 1 : 0; }
+int32_t gp_pdgp_h_far(gp_pdgp_plan p) { return (gp_pdgp_far_field_act(p) && p->last_grad && p->routes.nhf > 0) ? 1 : 0; }
+int32_t gp_pdgp_scan_far(gp_pdgp_plan p) {
+  if (!gp_pdgp_far_field_act(p) || !p->last_grad) return 0;
+  for (const auto& fam : p->hy_fams) if (fam.route == KUF_SCAN && fam.scan_far) return 1;
+  return 0;
+}
+// debug: the device's own ranges and reference points of the last evaluation for latent GP i of the run [g0, g0 + nrun), whose
+// groups are `group` frames, copied to the host (tests compare them with the numpy rules).  Returns the groups written.
+static int32_t pdgp_debug_ranges(gp_pdgp_plan p, int32_t i, int g0, int nrun, int group, int32_t cap_groups, int* BwdBufs::*d_rng,
+                                 double* BwdBufs::*d_ref, int32_t* gp_index, int32_t* rng, double* ref) {
+  if (!p->ws || i < 0 || i >= nrun || p->last_n <= 0 || !rng || !ref) return 0;
+  const int ng = p->last_n / group;
+  const BwdBufs& b = p->bw[g0 + i];
+  if (ng <= 0 || ng > cap_groups || !(b.*d_rng) || !(b.*d_ref)) return 0;
   gp_handle h = p->h;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
   if (h->aux_stream && hipStreamSynchronize(h->aux_stream) != hipSuccess) return 0;
   if (h->side_stream && hipStreamSynchronize(h->side_stream) != hipSuccess) return 0;
-  if (hipMemcpy(rng, b.qf_rng, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (hipMemcpy(ref, b.qf_ref, (size_t)2 * ng * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (p->q_bar && rng2 && s0 && sa && b.qb_rng2 && b.qb_tS) {
+  if (hipMemcpy(rng, b.*d_rng, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (hipMemcpy(ref, b.*d_ref, (size_t)2 * ng * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (gp_index) *gp_index = g0 + i;
+  return ng;
+}
+int32_t gp_debug_pdgp_far_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref,
+                                 int32_t* rng2, int32_t* s0, int32_t* sa) {
+  if (!p) return 0;
+  const PdgpRoutes& r = p->routes;
+  const int ng = pdgp_debug_ranges(p, i, r.q0, r.q_far ? r.nq : 0, QFAR_GROUP, cap_groups, &BwdBufs::qf_rng, &BwdBufs::qf_ref, gp_index, rng, ref);
+  if (ng > 0 && r.q_bar && rng2 && s0 && sa && p->bw[r.q0 + i].qb_rng2 && p->bw[r.q0 + i].qb_tS) {
+    const BwdBufs& b = p->bw[r.q0 + i];
+    const int nt = p->gps[r.q0 + i].M / 16;
     if (hipMemcpy(rng2, b.qb_rng2, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     if (hipMemcpy(s0, b.qb_tS, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     if (hipMemcpy(sa, b.qb_tS + QBAR_MAX_TILES, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
   }
-  if (gp_index) *gp_index = g;
   return ng;
 }
-gp_status gp_pdgp_set_far_act(gp_pdgp_plan p, int32_t enable) {
-  if (!p) return GP_ERR_BAD_ARG;
-  if (p->afar_ok != (enable != 0)) { p->afar_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
-  return GP_OK;
-}
-int32_t gp_pdgp_far_field_act(gp_pdgp_plan p) { return (p && p->na > 0) ? 1 : 0; }
-gp_status gp_pdgp_set_scan_far(gp_pdgp_plan p, int32_t enable) {
-  if (!p) return GP_ERR_BAD_ARG;
-  if (p->scan_far_ok != (enable != 0)) { p->scan_far_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
-  return GP_OK;
-}
-int32_t gp_pdgp_scan_far(gp_pdgp_plan p) {
-  if (!p || p->na <= 0 || !p->last_grad) return 0;
-  for (const auto& fam : p->hy_fams) if (fam.route == KUF_SCAN && fam.scan_far) return 1;
-  return 0;
-}
-gp_status gp_pdgp_set_h_far(gp_pdgp_plan p, int32_t enable) {
-  if (!p) return GP_ERR_BAD_ARG;
-  if (p->h_far_ok != (enable != 0)) { p->h_far_ok = (enable != 0); p->last_params = nullptr; }   // the descriptors depend on the route
-  return GP_OK;
-}
-int32_t gp_pdgp_h_far(gp_pdgp_plan p) { return (p && p->na > 0 && p->last_grad && p->nhf > 0) ? 1 : 0; }
-// debug: the device's own ranges and reference points of the last evaluation's activation far field, copied to the host
 int32_t gp_debug_pdgp_act_ranges(gp_pdgp_plan p, int32_t i, int32_t cap_groups, int32_t* gp_index, int32_t* rng, double* ref) {
-  if (!p || !p->ws || p->na <= 0 || i < 0 || i >= p->na || p->last_n <= 0 || !rng || !ref) return 0;
-  const int ng = p->last_n / AFAR_GROUP, g = p->a0 + i;
-  const BwdBufs& b = p->bw[g];
-  if (ng <= 0 || ng > cap_groups || !b.af_rng || !b.af_ref) return 0;
-  gp_handle h = p->h;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
-  if (h->aux_stream && hipStreamSynchronize(h->aux_stream) != hipSuccess) return 0;
-  if (h->side_stream && hipStreamSynchronize(h->side_stream) != hipSuccess) return 0;
-  if (hipMemcpy(rng, b.af_rng, (size_t)2 * ng * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (hipMemcpy(ref, b.af_ref, (size_t)2 * ng * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (gp_index) *gp_index = g;
-  return ng;
+  return p ? pdgp_debug_ranges(p, i, p->routes.a0, p->routes.na, AFAR_GROUP, cap_groups, &BwdBufs::af_rng, &BwdBufs::af_ref, gp_index, rng, ref) : 0;
 }
 int64_t gp_pdgp_num_params(gp_pdgp_plan p) { return p ? p->nparams : 0; }
 
@@ -202,10 +184,8 @@ gp_status gp_pdgp_layout(gp_pdgp_plan p, int32_t g, int64_t* off_theta, int64_t*
 // throwaway copy of the plan and a measuring arena.
 static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
   p->cb.tasks.assign(p->G, CondTask());
-  p->cb.q_desc = false;      // (the Q route's descriptor regions: only where a latent GP could take it — as b.Q below)
-  for (const PdgpGP& q : p->gps) if (gp_switches().qform != 0 && p->whiten && !q.f32 && q.ktype == GP_KERN_MERCER_MATERN12SM) p->cb.q_desc = true;
-  // (so do the activation far field's finish records, pdgp_afar_select)
-  for (const PdgpGP& q : p->gps) if (gp_switches().act_far != 0 && p->whiten && !q.f32 && q.ktype == GP_KERN_MATERN32 && afar_takes(q.M, p->maxN)) p->cb.q_desc = true;
+  p->cb.q_desc = false;      // (the Q route's descriptor regions, the activation far field's finish records: only where a GP could take one)
+  for (int g = 0; g < p->G; g++) if (pdgp_may_q(p, g) || pdgp_may_afar(p, g)) p->cb.q_desc = true;
   p->cb.d_desc = ar.take<char>(cond_batch_desc_bytes(p->G, p->cb.q_desc));
   p->off = pdgp_misc_layout(p->G);
   p->d_misc = ar.take<char>(p->off.bytes);
@@ -239,19 +219,19 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       b.H = ar.take<double>(M * M); b.E = ar.take<double>(M * M); b.T1 = ar.take<double>(M * M);
       b.T2 = ar.take<double>(M * M); b.Wbar = ar.take<double>(M * M); b.R = ar.take<double>(M * M);
       b.G = ar.take<double>(gp_strip_doubles(M, p->maxN, p->gps[g].f32 != 0));
-      // (Q route, pdgp_bwd.hip pdgp_qform_select: like the scan's arrays below, reserved before its setters have spoken)
-      if (gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM) {
+      // (Q route: like the scan's arrays below, reserved before its setters have spoken)
+      if (pdgp_may_q(p, g)) {
         b.Q = ar.take<double>(M * M);
         // (its far field's tables, where the shape admits them: T and Psi are 4 mpad (N / 256 + N / M) rows of M doubles.  They
         // would fit the b.G strip a Q-route GP never uses only while 4 mpad (1 / 256 + 1 / M) <= 1 — not at M = 64 — so they
         // have a home of their own at every shape)
-        if (gp_switches().qform_far != 0 && qfar_takes((int)M, p->maxN, p->gps[g].m)) {
+        if (pdgp_may_qfar(p, g)) {
           const QfarSizes qs = qfar_sizes((int)M, p->maxN, p->gps[g].m);
           b.qf_rng = (int*)ar.take<double>(qs.rng); b.qf_ref = ar.take<double>(qs.ref);
           b.qf_T = ar.take<double>(qs.T); b.qf_Psi = ar.take<double>(qs.Psi);
           // (the backward pass's use of the same far field, DESIGN.md 3.06: sized for every range — the lengthscale is trained on
           // the device.  At M = 512, N = 32768, m = 20 it is 0.41 of the b.G strip; like the tables it has a home of its own)
-          if (gp_switches().qform_qbar != 0 && qbar_takes((int)M, p->maxN, p->gps[g].m)) {
+          if (pdgp_may_qbar(p, g)) {
             const QbarSizes bs = qbar_sizes((int)M, p->maxN, p->gps[g].m);
             b.qb_rng2 = (int*)ar.take<double>(bs.rng2); b.qb_tS = (int*)ar.take<double>(bs.tS);
             b.qb_CnF = ar.take<double>(bs.CnF); b.qb_CFF = ar.take<double>(bs.CFF); b.qb_cn = ar.take<double>(bs.cn);
@@ -260,19 +240,19 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
           }
         }
       }
-      // (activation far field, pdgp_bwd.hip pdgp_afar_select: reserved before its setters have spoken, for the plan's largest
+      // (activation far field: reserved before its setters have spoken, for the plan's largest
       // batch — at M = 512, N = 32768: 4 MB of T, 1 MB of Psi, 2 MB of C per GP beside two 134 MB strips.
       // The backward window reads rng, T and Psi again, with W and the Kuf strip (kuf_scan_far_moments_kernel):
       // each has a region of its own in this walk and in cond_task_carve, nothing of the backward pass is carved over them, and
       // its launches only read W and Kuf — they stay the forward pass's until the next step's forward pass rewrites them)
-      if (gp_switches().act_far != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MATERN32 && afar_takes((int)M, p->maxN)) {
+      if (pdgp_may_afar(p, g)) {
         const AfarSizes as = afar_sizes((int)M, p->maxN);
         b.af_rng = (int*)ar.take<double>(as.rng); b.af_ref = ar.take<double>(as.ref);
         b.af_T = ar.take<double>(as.T); b.af_Psi = ar.take<double>(as.Psi); b.af_C = ar.take<double>(as.C);
         // (H from the stored A and these factors, DESIGN.md 3.10: the ranges are the device's own every step, so the store of Y is
         // sized by its bound — M / 16 + N / 256 - 1 slots of M x 16, the four far columns and A gm per group: at M = 512,
         // N = 32768 10.4 + 2.1 + 0.5 MB per GP — reserved like the tables, before the setters have spoken)
-        if (gp_switches().h_far != 0 && hfar_takes((int)M, p->maxN)) {
+        if (pdgp_may_hfar(p, g)) {
           const HfarSizes hs = hfar_sizes((int)M, p->maxN);
           b.hf_Yn = ar.take<double>(hs.Yn); b.hf_Yf = ar.take<double>(hs.Yf); b.hf_up = ar.take<double>(hs.up);
           b.hf_flag = (int*)ar.take<double>(hs.flag);
@@ -290,7 +270,7 @@ static bool pdgp_carve(gp_pdgp_plan_s* p, GpArena& ar) {
       // 2 NQ (M + 1) doubles per chunk of 64 frames, 12.6 MB per GP at N = 32768, M = 512.  gp_pdgp_set_frames_ascending and
       // gp_pdgp_set_grad_needs may both be called after the workspace is set, so the carve cannot wait for them: the arrays
       // are reserved whether or not the caller goes on to make the promise.  With kuf_scan=0 nothing is reserved.
-      if (gp_switches().kuf_scan != 0 && p->whiten && !p->gps[g].f32 && kuf_scan_nq(p->gps[g].ktype) > 0) {
+      if (pdgp_may_scan(p, g)) {
         b.ks_mom = ar.take<double>(kuf_scan_moment_doubles(p->maxN, (int)M, p->gps[g].ktype));
         b.ks_near = ar.take<double>(2 * (size_t)kuf_scan_chunks(p->maxN));
       }
@@ -338,18 +318,8 @@ gp_status gp_pdgp_set_workspace(gp_pdgp_plan p, void* workspace, size_t bytes) {
 
 }  // extern "C"
 
-gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);  // pdgp_bwd.hip
-gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done);
-gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);
-void pdgp_qform_select(gp_pdgp_plan p, int n);
-void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
-gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n);
-gp_status pdgp_qform_join(gp_pdgp_plan p);
-void pdgp_afar_select(gp_pdgp_plan p, int n);
-void pdgp_upload_afar(gp_pdgp_plan p, const double* params);
-gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n);
-
-// (re)bind the parameter vector / batch to the device descriptors
+// (re)bind the parameter vector / batch to the device descriptors: task pointers, the families (with a gradient), the routes —
+// which need both — then the forward descriptors, the backward ones, one upload
 static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad,
                            double* fmean, double* fvar) {
   gp_handle h = p->h;
@@ -370,18 +340,18 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   }
   p->cb.N = n;
   p->cb.maxM = p->maxM;
-  pdgp_qform_select(p, n);
-  p->cb.q0 = p->q0; p->cb.nq = p->nq; p->cb.q_far = p->q_far;
-  pdgp_afar_select(p, n);
-  p->cb.a0 = p->a0; p->cb.na = p->na;
+  if (grad) pdgp_build_families(p);
+  pdgp_decide_routes(p, n, grad != nullptr);
+  const PdgpRoutes& rt = p->routes;
+  p->cb.q0 = rt.q0; p->cb.nq = rt.nq; p->cb.q_far = rt.q_far; p->cb.a0 = rt.a0; p->cb.na = rt.na;     // (the one copy CondBatch gets)
   for (int g = 0; g < p->G; g++) {
     const bool q = pdgp_on_q_route(p, g);
     CondTask& t = p->cb.tasks[g];
     t.Qm = q ? p->bw[g].Q : nullptr;
     t.beta = q ? p->bw[g].alpha : nullptr;
-    t.far_rng = (q && p->q_far) ? p->bw[g].qf_rng : nullptr;
-    t.far_T = (q && p->q_far) ? p->bw[g].qf_T : nullptr;
-    t.far_Psi = (q && p->q_far) ? p->bw[g].qf_Psi : nullptr;
+    t.far_rng = (q && rt.q_far) ? p->bw[g].qf_rng : nullptr;
+    t.far_T = (q && rt.q_far) ? p->bw[g].qf_T : nullptr;
+    t.far_Psi = (q && rt.q_far) ? p->bw[g].qf_Psi : nullptr;
   }
   GP_CHECK(cond_batch_upload(h, p->cb, p->whiten != 0, p->jitter));
   // KL items
@@ -404,7 +374,7 @@ static gp_status pdgp_bind(gp_pdgp_plan p, const double* params, const double* x
   }
   pdgp_upload_qform(p, params);
   pdgp_upload_afar(p, params);
-  if (grad) GP_CHECK(pdgp_upload_bwd(p, params, x, n, grad));
+  if (grad) pdgp_upload_bwd(p, params, n, grad);
   GP_HIP_CHECK(h, hipMemcpyAsync(p->d_misc, p->h_misc.data(), p->off.bytes, hipMemcpyHostToDevice, h->stream));
   p->last_params = params; p->last_x = x; p->last_n = n; p->last_grad = grad;
   return GP_OK;
@@ -426,7 +396,7 @@ static gp_status pdgp_forward(gp_pdgp_plan p, const double* params, const double
   // (so does the activations' far field: predictions keep the dense products)
   const std::function<gp_status()> a_run = [&]() -> gp_status { return pdgp_afar_run(p, x, n); };
   {
-    const gp_status st = cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->nq > 0 ? &q_prepare : nullptr, p->na > 0 ? &a_run : nullptr);
+    const gp_status st = cond_batch_run(h, p->cb, x, n, p->whiten != 0, p->jitter, false, p->routes.nq > 0 ? &q_prepare : nullptr, p->routes.na > 0 ? &a_run : nullptr);
     // the Q run's product is enqueued (or the run failed): the guard joins the main stream ahead of everything that follows
     const gp_status sj = pdgp_qform_join(p);
     GP_CHECK(st); GP_CHECK(sj);

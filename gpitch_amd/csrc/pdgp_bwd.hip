@@ -34,54 +34,11 @@ static inline GemmProblem& host_prob(gp_pdgp_plan p, int slot, int i, int M) {
 // and its reverse pass
 //   Kuf_bar = G diag(2 gv) + beta gm^T        (no product: the contraction reads G and scales its columns)
 //   Qbar = Kuf diag(2 gv) Kuf^T, v = Kuf gm   (the split-K product on Kuf);  H = W Qbar W^T, u = W v: the chain's H and u.
-// Which latent GPs take it at n frames (p->q0, p->nq, p->qk0): shapes, types, the gradient needs and gp_pdgp_set_qform alone,
-// never the overlap level.  All MercerMatern12sm GPs of a whitened plan, when they are float64, train their hyper-parameters
-// over fixed inducing inputs, share the partial count, sit in one run of the batch (as every other family of the compacted
-// batch does), and the wave product and the lean contraction — the one kernel that applies the column scale — take the shape.
-void pdgp_qform_select(gp_pdgp_plan p, int n) {
-  p->q0 = p->nq = p->qk0 = 0; p->q_far = p->q_bar = false;
-  if (!gp_switches().qform || !p->qform || !p->whiten) return;
-  int first = -1, last = -1, cnt = 0, m = -1;
-  for (int g = 0; g < p->G; g++) {
-    const PdgpGP& q = p->gps[g];
-    if (q.ktype != GP_KERN_MERCER_MATERN12SM) continue;
-    if (q.f32 || !q.need_theta || q.need_z || !p->bw[g].Q || (m >= 0 && q.m != m)) return;
-    m = q.m;
-    if (first < 0) first = g;
-    last = g; cnt++;
-  }
-  if (cnt == 0 || last - first + 1 != cnt) return;
-  struct Key { int type, m, f32; };
-  std::vector<Key> seen;
-  int qk0 = 0;
-  for (int g = 0; g < p->G; g++) {
-    const PdgpGP& q = p->gps[g];
-    if (!(q.need_theta || q.need_z)) continue;
-    if (g < first) qk0++;
-    const Key k{q.ktype, gp_kern_has_partials(q.ktype) ? q.m : 0, q.f32};
-    const bool same = !seen.empty() && seen.back().type == k.type && seen.back().m == k.m && seen.back().f32 == k.f32;
-    if (same) continue;
-    for (const Key& s : seen) if (s.type == k.type && s.m == k.m && s.f32 == k.f32) return;
-    seen.push_back(k);
-  }
-  if (!cond_batch_uniform(p->cb, n) || !gemm_wave_takes(6, p->maxM, n, 1) || !hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, p->maxM, n, cnt)) return;
-  p->q0 = first; p->nq = cnt; p->qk0 = qk0;
-  // the product's far field: frames and inducing inputs both promised ascending, the switch, the shape, the tables
-  bool far = gp_switches().qform_far != 0 && p->frames_ascending && p->q_zasc && gemm_wave_takes(7, p->maxM, n, 1) && qfar_takes(p->maxM, n, m);
-  for (int g = first; g <= last; g++) far = far && p->bw[g].qf_T && p->gps[g].M == p->maxM;
-  p->q_far = far;
-  // the backward pass's Qbar and v from the same far field: the switch, the caller's bit, the shape, the workspace
-  // — and the latent GPs left to the split-K product are one non-empty run of its float64 problems, so it stays one launch
-  bool bar = far && gp_switches().qform_qbar != 0 && p->q_bar_ok && qbar_takes(p->maxM, n, m) &&
-             (first == 0 || last + 1 == p->n64) && p->n64 > cnt;
-  for (int g = first; g <= last; g++) bar = bar && p->bw[g].qb_Wv;
-  p->q_bar = bar;
-}
-
+// Which latent GPs take it at n frames: pdgp_decide_routes.
 // the forward pass's descriptors of the Q run (pdgp_bind, with or without a gradient)
 void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
-  for (int i = 0; i < p->nq; i++) {
-    const int g = p->q0 + i;
+  for (int i = 0; i < p->routes.nq; i++) {
+    const int g = p->routes.q0 + i;
     const PdgpGP& q = p->gps[g];
     const CondTask& t = p->cb.tasks[g];
     const BwdBufs& b = p->bw[g];
@@ -93,7 +50,7 @@ void pdgp_upload_qform(gp_pdgp_plan p, const double* params) {
     { GemmProblem& r = P(S_QALPHA); r.A = t.W; r.v0 = params + q.off_qmu; r.o0 = b.alpha; }
     // (the guard reads L through v0: qform_guard_kernel)
     { GemmProblem& r = P(S_QQ); r.A = b.R; r.B = t.W; r.C = b.Q; r.v0 = t.L; }
-    if (p->q_far) {     // (feature tables: cov_item_fill's layout of t.feat — z first, then the frames)
+    if (p->routes.q_far) {     // (feature tables: cov_item_fill's layout of t.feat — z first, then the frames)
       QfarItem& it = *(QfarItem*)(p->h_misc.data() + p->off.qf_items + i * sizeof(QfarItem));
       const size_t nfz = gp_align_up((size_t)2 * sm_mpad(q.m) * M, 32);
       it = QfarItem{t.z, t.kern.theta, t.feat, t.feat + nfz, b.Q, b.qf_rng, b.qf_ref, b.qf_T, b.qf_Psi, M, 0};
@@ -129,17 +86,17 @@ __global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __r
 gp_status pdgp_qform_join(gp_pdgp_plan p);
 static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wait, hipEvent_t tables_done = nullptr) {
   gp_handle h = p->h;
-  const int nq = p->nq, maxM = p->maxM;
+  const int nq = p->routes.nq, maxM = p->maxM;
   GP_CHECK(launch_chain_e(h, slot_probs(p, S_QE), nq, maxM));
   GP_CHECK(launch_chain_r_alpha(h, slot_probs(p, S_QR), slot_probs(p, S_QALPHA), nq, maxM));
   GemmFlags f; f.triB = TRI_LOWER;        // Q = R W
   GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QQ), nq, maxM, maxM, f));
-  if (p->q_far) {
+  if (p->routes.q_far) {
     if (far_wait && hipStreamWaitEvent(h->stream, h->ev_feat, 0) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
-    GP_CHECK(launch_qfar_tables(h, (const QfarItem*)(p->d_misc + p->off.qf_items), nq, maxM, p->gps[p->q0].m, x, n));
+    GP_CHECK(launch_qfar_tables(h, (const QfarItem*)(p->d_misc + p->off.qf_items), nq, maxM, p->gps[p->routes.q0].m, x, n));
   }
   if (tables_done && hipEventRecord(tables_done, h->stream) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
-  hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->q0, (double)GP_QFORM_COND_MAX, h->d_status);
+  hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->routes.q0, (double)GP_QFORM_COND_MAX, h->d_status);
   if (hipGetLastError() != hipSuccess) return gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
   return GP_OK;
 }
@@ -152,9 +109,9 @@ static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wa
 gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n) {
   gp_handle h = p->h;
   h->guard_pending = false;
-  if (p->nq <= 0) return GP_OK;
+  if (p->routes.nq <= 0) return GP_OK;
   bool aux = (n >= 4096) && p->overlap >= 2 && h->aux_stream && !h->aux_active;
-  if (aux && p->q_far && !p->cb.feat_ready) aux = false;
+  if (aux && p->routes.q_far && !p->cb.feat_ready) aux = false;
   if (aux && !h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) { h->ev_q = nullptr; aux = false; }
   if (aux && !h->ev_guard && hipEventCreateWithFlags(&h->ev_guard, hipEventDisableTiming) != hipSuccess) { h->ev_guard = nullptr; aux = false; }
   gp_status st;
@@ -184,29 +141,11 @@ gp_status pdgp_qform_join(gp_pdgp_plan p) {
 // ---- activation far field ---------------------------------------------------------------------------
 // A Matern-3/2 Kuf is exactly semiseparable along sorted inputs, so A = W Kuf and Lq^T A = (Lq^T W) Kuf need, per 256-frame
 // group, only the rows of Kuf near the group plus two M x 2 tables per factor (afar.hip).  Nothing is inverted that the Cholesky
-// route does not invert, and the backward pass reads the same A strip.  Which latent GPs take it at n frames (p->a0, p->na):
-// the switch, gp_pdgp_set_far_act, shapes, types, the gradient needs and the frames' promise — never the overlap level.  All
-// Matern-3/2 GPs of a whitened plan, when they are float64, over fixed inducing inputs, of the batch's one M, in one run.
-void pdgp_afar_select(gp_pdgp_plan p, int n) {
-  p->a0 = p->na = 0;
-  if (!gp_switches().act_far || !p->afar_ok || !p->whiten || !p->frames_ascending) return;
-  int first = -1, last = -1, cnt = 0;
-  for (int g = 0; g < p->G; g++) {
-    const PdgpGP& q = p->gps[g];
-    if (q.ktype != GP_KERN_MATERN32) continue;
-    if (q.f32 || q.need_z || q.M != p->maxM || !p->bw[g].af_T || pdgp_on_q_route(p, g)) return;
-    if (first < 0) first = g;
-    last = g; cnt++;
-  }
-  if (cnt == 0 || last - first + 1 != cnt) return;
-  if (!cond_batch_uniform(p->cb, n) || !afar_takes(p->maxM, n)) return;
-  p->a0 = first; p->na = cnt;
-}
-
+// route does not invert, and the backward pass reads the same A strip.  Which latent GPs take it at n frames: pdgp_decide_routes.
 // the forward pass's descriptors of that run (pdgp_bind, with or without a gradient)
 void pdgp_upload_afar(gp_pdgp_plan p, const double* params) {
-  for (int i = 0; i < p->na; i++) {
-    const int g = p->a0 + i;
+  for (int i = 0; i < p->routes.na; i++) {
+    const int g = p->routes.a0 + i;
     const PdgpGP& q = p->gps[g];
     const CondTask& t = p->cb.tasks[g];
     const BwdBufs& b = p->bw[g];
@@ -222,11 +161,11 @@ void pdgp_upload_afar(gp_pdgp_plan p, const double* params) {
 // C = tril(Lq)^T W, the tables and the product of the run: cond_batch_run's hook (pdgp.hip), on the main stream behind W
 gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n) {
   gp_handle h = p->h;
-  if (p->na <= 0) return GP_OK;
+  if (p->routes.na <= 0) return GP_OK;
   GemmFlags f;
   f.transA = 1; f.triA = TRI_UPPER; f.triB = TRI_LOWER;
-  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_AC), p->na, p->maxM, p->maxM, f));
-  return launch_afar(h, (const AfarItem*)(p->d_misc + p->off.af_items), p->na, p->maxM, x, n);
+  GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_AC), p->routes.na, p->maxM, p->maxM, f));
+  return launch_afar(h, (const AfarItem*)(p->d_misc + p->off.af_items), p->routes.na, p->maxM, x, n);
 }
 
 // E = Lq Lq^T - I (ERA_E) and R = W^T E, alpha = W^T q_mu (ERA_R) over the compacted batch without the Q run, whose E, R and
@@ -234,8 +173,8 @@ gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n) {
 enum { ERA_E = 1, ERA_R = 2 };
 static gp_status pdgp_era(gp_pdgp_plan p, int parts) {
   gp_handle h = p->h;
-  const int maxM = p->maxM, behind = p->qk0 + p->nq;
-  const int s0[2] = {0, behind}, cnt[2] = {p->qk0, p->nK - behind};
+  const int maxM = p->maxM, behind = p->routes.qk0 + p->routes.nq;
+  const int s0[2] = {0, behind}, cnt[2] = {p->routes.qk0, p->nK - behind};
   for (int r = 0; r < 2; r++) {
     if (cnt[r] <= 0) continue;
     if (parts & ERA_E) GP_CHECK(launch_chain_e(h, slot_probs(p, S_E) + s0[r], cnt[r], maxM));
@@ -244,86 +183,151 @@ static gp_status pdgp_era(gp_pdgp_plan p, int parts) {
   return GP_OK;
 }
 
-// The Kuf route of every family and the shape facts the launches share, once per bind.  Priority: the Q
-// route (pdgp_qform_select's run, taken as it is), the scan, the fused epilogue, else the stored product.  The scan and the
-// fused form need every family in one run of the compacted batch, since Kuf_bar is then issued family by family; fam.batched
-// says one M, hyper-parameter gradients of every GP, no inducing-input gradient.
-//   scan : Matern-3/2 / Matern-5/2 over frames the caller promised ascending (kuf_scan.hip), float64 strips, M <= 1024.
-//          Matern-1/2 (kink at 0) and RBF (not semiseparable) have no such form.
-//   fused: a stationary family that wants Kuf_bar for two sums per GP only: they come out of the product's epilogue
-//          (gemm_strip.hip role 5; whole tiles) and neither the strip nor the separate contraction exists.
-// The overlap level and the schedule's switches (scan_side, kufbar_split) have no say here: every level must give the same bits.
-static void pdgp_select_routes(gp_pdgp_plan p, int n) {
-  const int maxM = p->maxM;
-  p->nt_uniform = ((n & 3) == 0) ? 1 : 0;
-  for (const PdgpGP& q : p->gps) if (q.M != maxM) p->nt_uniform = 0;
-  p->kuf_uniform = ((n & 1) == 0) ? 1 : 0;
-  p->k64 = 0;             // (slots of the compacted batch keep the GPs' order: its float64 GPs come first)
-  for (int g : p->kgps) {
-    if (p->gps[g].M != maxM) p->kuf_uniform = 0;
-    if (!p->gps[g].f32) p->k64++;
+// The compacted batch (the latent GPs whose kernel gradients are asked) and its kernel families — same type, partial count and
+// precision, in kgps order; one contraction launch per family and side.  Host work on the plan alone, ahead of the routes.
+void pdgp_build_families(gp_pdgp_plan p) {
+  p->kgps.clear();
+  for (int g = 0; g < p->G; g++) if (p->gps[g].need_theta || p->gps[g].need_z) p->kgps.push_back(g);
+  p->nK = (int)p->kgps.size();
+  p->hy_fams.clear();
+  for (auto& q : p->gps) q.fam = -1;
+  for (size_t s = 0; s < p->kgps.size(); s++) {
+    const int g = p->kgps[s];
+    const PdgpGP& q = p->gps[g];
+    const int key_m = gp_kern_has_partials(q.ktype) ? q.m : 0;
+    int fi = -1;
+    for (size_t f = 0; f < p->hy_fams.size(); f++)
+      if (p->hy_fams[f].type == q.ktype && p->hy_fams[f].m == key_m && p->hy_fams[f].f32 == q.f32) fi = (int)f;
+    if (fi < 0) { gp_pdgp_plan_s::HyFamily nf; nf.type = q.ktype; nf.m = key_m; nf.M = q.M; nf.f32 = q.f32; nf.batched = true; p->hy_fams.push_back(nf); fi = (int)p->hy_fams.size() - 1; }
+    gp_pdgp_plan_s::HyFamily& fam = p->hy_fams[fi];
+    fam.gps.push_back(g);
+    p->gps[g].fam = fi;
+    if (q.M != fam.M || q.need_z || !q.need_theta) fam.batched = false;   // the per-GP path handles those
   }
-  p->contiguous = p->whiten && !p->hy_fams.empty();
+  int nitems = 0;
   for (auto& fam : p->hy_fams) {
-    int s0 = -1;
+    fam.first = nitems; fam.count = (int)fam.gps.size(); nitems += fam.count;
+    fam.mfma = (gp_kern_is_mercer(fam.type) && fam.batched) ? 1 : 0;
+    fam.scan_ws = true;
+    for (int g : fam.gps) if (!pdgp_may_scan(p, g)) fam.scan_ws = false;
+    int s0 = -1;             // its first slot, when its GPs sit in one run of the compacted batch
     for (size_t s = 0; s < p->kgps.size(); s++) if (p->kgps[s] == fam.gps[0]) s0 = (int)s;
     for (size_t i = 0; i < fam.gps.size(); i++)
       if (s0 < 0 || s0 + (int)i >= (int)p->kgps.size() || p->kgps[s0 + i] != fam.gps[i]) { s0 = -1; break; }
     fam.slot0 = s0;
-    if (s0 < 0) p->contiguous = false;
   }
-  p->any_scan = p->any_routed = false;
+}
+
+// Every route of the bound batch (DESIGN.md 3.04's table), once per bind: from shapes, types, precision, the gradient needs, the
+// switches and the permissions — never from the overlap level or the schedule's switches (scan_side, kufbar_split): every level
+// must give the same bits.  Writes p->routes and the families' route, scan_far and np_uf; launches nothing, reads no device
+// memory.  A decision may rest on the ones above it, never on one below.  Whether a GP's workspace has a route's regions is
+// asked of the pdgp_may_* predicate that carved them, not of the pointers: nothing the predicates read can change once the
+// workspace is set (pdgp_plan.h), so an item never gets a null table.
+void pdgp_decide_routes(gp_pdgp_plan p, int n, bool grad) {
+  const GpSwitches& sw = gp_switches();
+  const PdgpPerms& pm = p->perms;
+  const int G = p->G, maxM = p->maxM;
+  PdgpRoutes& r = p->routes;
+  r = PdgpRoutes();
+  auto kernel_is = [p](int type) { return [p, type](int g) { return p->gps[g].ktype == type; }; };
+  int first = 0, cnt = 0, m = -1, qk0 = 0;
+  // 1. The Q run (3.03): ALL MercerMatern12sm GPs of a whitened plan, float64, trained hyper-parameters over fixed inducing inputs,
+  // one partial count, one run — as every other family of the compacted batch is, since Kuf_bar is then issued family by family
+  // — and the wave product and the lean contraction, the one kernel that applies the column scale, take the shape
+  auto q_bad = [&](int g) {
+    const PdgpGP& q = p->gps[g];
+    const bool bad = q.f32 || !q.need_theta || q.need_z || !pdgp_may_q(p, g) || (m >= 0 && q.m != m);
+    m = q.m;
+    return bad;
+  };
+  auto families_distinct = [&]() {       // in the compacted batch; counts the slots ahead of the run on its way
+    struct Key { int type, m, f32; };
+    std::vector<Key> seen;
+    for (int g = 0; g < G; g++) {
+      const PdgpGP& q = p->gps[g];
+      if (!(q.need_theta || q.need_z)) continue;
+      if (g < first) qk0++;
+      const Key k{q.ktype, gp_kern_has_partials(q.ktype) ? q.m : 0, q.f32};
+      if (!seen.empty() && seen.back().type == k.type && seen.back().m == k.m && seen.back().f32 == k.f32) continue;
+      for (const Key& s : seen) if (s.type == k.type && s.m == k.m && s.f32 == k.f32) return false;
+      seen.push_back(k);
+    }
+    return true;
+  };
+  if (sw.qform && pm.qform && p->whiten && pdgp_single_run(G, kernel_is(GP_KERN_MERCER_MATERN12SM), q_bad, &first, &cnt) && cnt > 0 &&
+      families_distinct() && cond_batch_uniform(p->cb, n) && gemm_wave_takes(6, maxM, n, 1) && hyper_lean_takes(GP_KERN_MERCER_MATERN12SM, m, maxM, n, cnt)) {
+    r.q0 = first; r.nq = cnt; r.qk0 = qk0;
+    // 2. its product's far field (3.05): frames and inducing inputs both promised ascending, the switch, the shape, the tables
+    r.q_far = sw.qform_far != 0 && pm.frames_ascending && pm.q_zasc && gemm_wave_takes(7, maxM, n, 1) && qfar_takes(maxM, n, m);
+    for (int g = first; g < first + cnt; g++) r.q_far = r.q_far && pdgp_may_qfar(p, g) && p->gps[g].M == maxM;
+    // 3. Qbar and v from the same far field (3.06): the switch, the caller's bit, the shape, the workspace — and the latent GPs left
+    // to the split-K product are one non-empty run of its float64 problems, so it stays one launch
+    r.q_bar = r.q_far && sw.qform_qbar != 0 && pm.q_bar_ok && qbar_takes(maxM, n, m) && (first == 0 || first + cnt == p->n64) && p->n64 > cnt;
+    for (int g = first; g < first + cnt; g++) r.q_bar = r.q_bar && pdgp_may_qbar(p, g);
+  }
+  // 4. The activations' run (3.07): ALL Matern-3/2 GPs of a whitened plan, float64, over fixed inducing inputs, of the batch's one
+  // M, in one run, none of them on the Q route; frames promised ascending
+  auto a_bad = [&](int g) { const PdgpGP& q = p->gps[g]; return q.f32 || q.need_z || q.M != maxM || !pdgp_may_afar(p, g) || pdgp_on_q_route(p, g); };
+  if (sw.act_far && pm.afar_ok && p->whiten && pm.frames_ascending && pdgp_single_run(G, kernel_is(GP_KERN_MATERN32), a_bad, &first, &cnt) &&
+      cnt > 0 && cond_batch_uniform(p->cb, n) && afar_takes(maxM, n)) { r.a0 = first; r.na = cnt; }
+  if (!grad) return;
+  auto on_a_run = [&r](int g) { return g >= r.a0 && g < r.a0 + r.na; };
+  r.nt_uniform = ((n & 3) == 0) ? 1 : 0;
+  for (const PdgpGP& q : p->gps) if (q.M != maxM) r.nt_uniform = 0;
+  r.kuf_uniform = ((n & 1) == 0) ? 1 : 0;
+  for (int g : p->kgps) {          // (slots of the compacted batch keep the GPs' order: its float64 GPs come first)
+    if (p->gps[g].M != maxM) r.kuf_uniform = 0;
+    if (!p->gps[g].f32) r.k64++;
+  }
+  r.contiguous = p->whiten && !p->hy_fams.empty();
+  for (const auto& fam : p->hy_fams) if (fam.slot0 < 0) r.contiguous = false;
+  // 5. Each family's Kuf route.  Priority: the Q run's family, the scan, the fused epilogue, else the stored product.  The scan and
+  // the fused form need every family in one run of the compacted batch, since Kuf_bar is then issued family by family;
+  // fam.batched says one M, hyper-parameter gradients of every GP, no inducing-input gradient.
+  //   scan : Matern-3/2 / Matern-5/2 over frames the caller promised ascending (kuf_scan.hip), float64 strips, M <= 1024.
+  //          Matern-1/2 (kink at 0) and RBF (not semiseparable) have no such form.
+  //   fused: a stationary family that wants Kuf_bar for two sums per GP only: they come out of the product's epilogue
+  //          (gemm_strip.hip role 5; whole tiles) and neither the strip nor the separate contraction exists.
   for (auto& fam : p->hy_fams) {
     fam.route = KUF_PRODUCT; fam.np_uf = fam.np_uu = 0; fam.scan_far = false;
-    if (p->nq > 0 && fam.gps[0] == p->q0) {
+    if (r.nq > 0 && fam.gps[0] == r.q0) {
       fam.route = KUF_QFORM;
-    } else if (p->contiguous && gp_switches().kuf_scan != 0 && p->frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
+    } else if (r.contiguous && sw.kuf_scan != 0 && pm.frames_ascending && fam.batched && !fam.f32 && fam.scan_ws &&
                kuf_scan_nq(fam.type) > 0 && fam.M <= 1024) {
       fam.route = KUF_SCAN; fam.np_uf = kuf_scan_records(fam.M);
-      p->any_scan = true;
-      // its moments from the factored A: a Matern-3/2 family all of whose GPs are in the run whose A
-      // afar.hip forms at this batch size (that run's conditions — float64, one M, n a multiple of 256 — come with it)
-      fam.scan_far = gp_switches().scan_far != 0 && p->scan_far_ok && fam.type == GP_KERN_MATERN32 && p->na > 0;
-      for (int g : fam.gps) if (g < p->a0 || g >= p->a0 + p->na) fam.scan_far = false;
-      for (const PdgpGP& q : p->gps) if (q.f32) fam.scan_far = false;        // (a plan of float64 strips throughout)
-    } else if (p->contiguous && p->kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM &&
+      r.any_scan = true;
+      // its moments from the factored A (3.09): a Matern-3/2 family all of whose GPs are in the activations' run at this batch
+      // size (that run's conditions — float64, one M, n a multiple of 256 — come with it), in a plan of float64 strips throughout
+      fam.scan_far = sw.scan_far != 0 && pm.scan_far_ok && fam.type == GP_KERN_MATERN32 && r.na > 0;
+      for (int g : fam.gps) if (!on_a_run(g)) fam.scan_far = false;
+      for (const PdgpGP& q : p->gps) if (q.f32) fam.scan_far = false;
+    } else if (r.contiguous && r.kuf_uniform && fam.batched && !fam.mfma && fam.M == maxM &&
                (fam.f32 ? gemm_f32_fused_contraction_ok(maxM, n, fam.type) : gemm_strip_fused_contraction_ok(maxM, n, fam.type))) {
       fam.route = KUF_FUSED;
       fam.np_uf = !fam.f32 ? gemm_fused_contraction_records(maxM, n, fam.type)
-                           : gemm_wave_f32_takes(5, maxM, n, p->kuf_uniform) ? (maxM / 64) * (n / 64) : (maxM / 128) * (n / 128);
+                           : gemm_wave_f32_takes(5, maxM, n, r.kuf_uniform) ? (maxM / 64) * (n / 64) : (maxM / 128) * (n / 128);
     }
-    if (fam.route != KUF_PRODUCT) p->any_routed = true;
+    if (fam.route != KUF_PRODUCT) r.any_routed = true;
   }
-  // H = A diag(2 gv) A^T and u = A gm of the run whose A afar.hip forms, from that A once and its factors once:
-  // the switch, gp_pdgp_set_h_far, a plan of float64 strips throughout, the workspace — and the latent GPs left to the dense
-  // split-K product (neither in this run nor in the Q run when qbar.hip has its Qbar) are one run of the batch, or none
-  p->nhf = p->hd0 = p->hdn = 0;
-  bool hf = gp_switches().h_far != 0 && p->h_far_ok && p->na > 0 && p->n64 == p->G && hfar_takes(maxM, n);
+  // 6. H and u of the activations' run from the stored A once and its factors once (3.10): the switch, gp_pdgp_set_h_far, a plan of
+  // float64 strips throughout, the workspace — and the latent GPs left to the dense split-K product (neither in this run nor in
+  // the Q run when qbar.hip has its Qbar) are one run of the batch, or none
+  bool hf = sw.h_far != 0 && pm.h_far_ok && r.na > 0 && p->n64 == G && hfar_takes(maxM, n);
   for (const PdgpGP& q : p->gps) if (q.f32) hf = false;
-  for (int g = p->a0; hf && g < p->a0 + p->na; g++) if (!p->bw[g].hf_Yn || !p->bw[g].hf_Yf || !p->bw[g].hf_up || !p->bw[g].hf_flag) hf = false;
-  if (hf) {
-    int first = -1, last = -1, cnt = 0;
-    for (int g = 0; g < p->G; g++) {
-      if ((g >= p->a0 && g < p->a0 + p->na) || (p->q_bar && pdgp_on_q_route(p, g))) continue;
-      if (first < 0) first = g;
-      last = g; cnt++;
-    }
-    if (cnt == 0 || last - first + 1 == cnt) { p->nhf = p->na; p->hd0 = cnt ? first : 0; p->hdn = cnt; }
-  }
+  for (int g = r.a0; g < r.a0 + r.na; g++) if (!pdgp_may_hfar(p, g)) hf = false;
+  auto left_dense = [&](int g) { return !on_a_run(g) && !(r.q_bar && pdgp_on_q_route(p, g)); };
+  if (hf && pdgp_single_run(G, left_dense, [](int) { return false; }, &first, &cnt)) { r.nhf = r.na; r.hd0 = first; r.hdn = cnt; }
 }
 // do the family's Kuf-side partial sums come with its Kuf_bar step (no contraction launch of its own)?
 static inline bool kuf_sums_with_step(const gp_pdgp_plan_s::HyFamily& fam) { return fam.route == KUF_FUSED || fam.route == KUF_SCAN; }
 
-gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
-  (void)x;
+// the backward pass's descriptors (pdgp_bind with a gradient, behind the families and the routes)
+void pdgp_upload_bwd(gp_pdgp_plan p, const double* params, int n, double* grad) {
   const int G = p->G;
   p->h_fin_items.clear();       // the descriptor block is rewritten: force a fresh upload of the finish items
   const bool white = p->whiten != 0;
   size_t slab_off = 0;
-  p->kgps.clear();
-  for (int g = 0; g < G; g++)
-    if (p->gps[g].need_theta || p->gps[g].need_z) p->kgps.push_back(g);
-  p->nK = (int)p->kgps.size();
   int kslot = 0;
   for (int g = 0; g < G; g++) {
     const PdgpGP& q = p->gps[g];
@@ -353,12 +357,12 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       // Q route: the same product on Kuf gives Qbar (into T2) and v = Kuf gm (into Lu); H and u follow from S_QT / S_QHH / S_QU
       if (pdgp_on_q_route(p, g)) { r.A = t.Kuf; r.B = t.Kuf; r.C = b.T2; r.o0 = b.Lu; r.xa = nullptr; } }
     if (pdgp_on_q_route(p, g)) {
-      auto PQ = [&](int slot) -> GemmProblem& { return host_prob(p, slot, g - p->q0, M); };
+      auto PQ = [&](int slot) -> GemmProblem& { return host_prob(p, slot, g - p->routes.q0, M); };
       { GemmProblem& r = PQ(S_QT); r.A = t.W; r.B = b.T2; r.C = b.T1; }
       { GemmProblem& r = PQ(S_QHH); r.A = b.T1; r.B = t.W; r.C = b.H; }
       { GemmProblem& r = PQ(S_QU); r.A = t.W; r.v0 = b.Lu; r.o0 = b.u; r.o1 = g_mu; }
-      if (p->q_bar) {   // Qbar and v from the far field (qbar.hip) into the same T2 and Lu; the split-K launch skips this GP
-        QbarItem& it = *(QbarItem*)(p->h_misc.data() + p->off.qb_items + (g - p->q0) * sizeof(QbarItem));
+      if (p->routes.q_bar) {   // Qbar and v from the far field (qbar.hip) into the same T2 and Lu; the split-K launch skips this GP
+        QbarItem& it = *(QbarItem*)(p->h_misc.data() + p->off.qb_items + (g - p->routes.q0) * sizeof(QbarItem));
         it = QbarItem{t.Kuf, ldN, gv, gm, t.z, t.kern.theta, t.feat, b.qf_rng, b.qf_ref, b.qf_Psi, b.qb_rng2, b.qb_tS,
                       b.qb_CnF, b.qb_CFF, b.qb_cn, b.qb_cF, b.qb_Um, b.qb_Vp, b.qb_Wv, b.T2, b.Lu, M, 0};
       }
@@ -386,34 +390,8 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       r.kern = t.kern; r.xa = params + q.off_z; r.v0 = b.alpha; r.v2 = gm; r.o0 = b.hyp_part; }
     if (kneed) kslot++;
   }
-  // Kuf-side contractions, one launch per kernel family (same type and partial count): item array in kgps order inside
-  // each family.  x2 stays null in the items: the frames of the batch come with the launch (their pointer may change
-  // from step to step without a descriptor upload).
-  p->hy_fams.clear();
-  for (auto& q : p->gps) q.fam = -1;
-  for (size_t s = 0; s < p->kgps.size(); s++) {
-    const int g = p->kgps[s];
-    const PdgpGP& q = p->gps[g];
-    const int key_m = gp_kern_has_partials(q.ktype) ? q.m : 0;
-    int fi = -1;
-    for (size_t f = 0; f < p->hy_fams.size(); f++)
-      if (p->hy_fams[f].type == q.ktype && p->hy_fams[f].m == key_m && p->hy_fams[f].f32 == q.f32) fi = (int)f;
-    if (fi < 0) { gp_pdgp_plan_s::HyFamily nf; nf.type = q.ktype; nf.m = key_m; nf.M = q.M; nf.f32 = q.f32; nf.batched = true; p->hy_fams.push_back(nf); fi = (int)p->hy_fams.size() - 1; }
-    gp_pdgp_plan_s::HyFamily& fam = p->hy_fams[fi];
-    fam.gps.push_back(g);
-    p->gps[g].fam = fi;
-    if (q.M != fam.M || q.need_z || !q.need_theta) fam.batched = false;   // the per-GP path handles those
-  }
-  int nitems = 0;
-  for (auto& fam : p->hy_fams) {
-    fam.first = nitems; fam.count = (int)fam.gps.size(); nitems += fam.count;
-    fam.mfma = (gp_kern_is_mercer(fam.type) && fam.batched) ? 1 : 0;
-    fam.scan_ws = true;
-    for (int g : fam.gps) if (!p->bw[g].ks_mom || !p->bw[g].ks_near) fam.scan_ws = false;
-  }
-  pdgp_select_routes(p, n);
-  for (int i = 0; i < p->nhf; i++) {      // hfar.hip's items: the product's own slabs and u partials, which the slab reduction sums
-    const int g = p->a0 + i;
+  for (int i = 0; i < p->routes.nhf; i++) {      // hfar.hip's items: the product's own slabs and u partials, which the slab reduction sums
+    const int g = p->routes.a0 + i;
     const CondTask& t = p->cb.tasks[g];
     const BwdBufs& b = p->bw[g];
     const GemmProblem& r = *((const GemmProblem*)(p->h_misc.data() + p->off.bwd[S_H]) + g);
@@ -421,6 +399,8 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
     it = HfarItem{t.A, t.Kuf, t.W, p->gFvar + (size_t)g * n, p->gFmu + (size_t)g * n, b.af_rng, b.af_T, b.af_Psi,
                   b.hf_Yn, b.hf_Yf, b.hf_up, b.hf_flag, r.o2, r.o1, gp_strip_ld(n, false), p->gps[g].M, g};
   }
+  // Kuf-side contractions: the families' item arrays.  x2 stays null in the items: the frames of the batch come with the launch
+  // (their pointer may change from step to step without a descriptor upload).
   {
     HyperItem* items = (HyperItem*)(p->h_misc.data() + p->off.hy_items);
     KufScanItem* sitems = (KufScanItem*)(p->h_misc.data() + p->off.ks_items);
@@ -458,7 +438,6 @@ gp_status pdgp_upload_bwd(gp_pdgp_plan p, const double* params, const double* x,
       }
     }
   }
-  return GP_OK;
 }
 
 // R = W^T (Lq Lq^T - I) and alpha = W^T q_mu depend on the parameters and on W only: when the helper stream exists they
@@ -489,7 +468,8 @@ gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
 }
 
 // ---- the backward pass's steps: each enqueues on h->stream, wherever the schedule (pdgp_backward) has pointed it ----------
-struct BwdCall { gp_pdgp_plan p; const double* params; const double* x; int n; double* grad; };
+struct BwdCall { gp_pdgp_plan p; const double* params; const double* x; int n; double* grad;
+                 bool qbar_ahead; };      // this pass has put the far-field Qbar's launches on the main stream (pdgp_backward)
 typedef gp_pdgp_plan_s::HyFamily HyFamily;
 
 // conditional(whiten=False) + gauss_kl(q_mu, q_sqrt, K) (pdgp.py:123-129, 147-155) is the whitened model at
@@ -524,7 +504,7 @@ static gp_status bwd_late_sums(const BwdCall& c) {
 
 static gp_status bwd_qbar(const BwdCall& c) {
   gp_pdgp_plan p = c.p;
-  return launch_qbar(p->h, (const QbarItem*)(p->d_misc + p->off.qb_items), p->nq, p->maxM, p->gps[p->q0].m, c.n);
+  return launch_qbar(p->h, (const QbarItem*)(p->d_misc + p->off.qb_items), p->routes.nq, p->maxM, p->gps[p->routes.q0].m, c.n);
 }
 
 // H = A diag(2 gv) A^T (symmetric, split-K over the frames; u = A gm and grad q_mu += u are fused into it), grad q_sqrt
@@ -532,27 +512,27 @@ static gp_status bwd_h_chain(const BwdCall& c) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
   const int G = p->G, maxM = p->maxM, n64 = p->n64;     // latent GPs [0, n64): float64 strips, [n64, G): float32 strips
   GemmFlags f;
-  if (p->nhf > 0) {     // the activations' run from the stored A once and its factors once (hfar.hip), the dense product on the others
-    if (p->q_bar && !p->qbar_ahead) GP_CHECK(bwd_qbar(c));
-    if (p->hdn > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + p->hd0, p->hdn, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
-    GP_CHECK(launch_hfar(h, (const HfarItem*)(p->d_misc + p->off.hf_items), p->nhf, maxM, c.n, p->nsplit,
-                        p->hdn == 0 ? gemm_nt_reduce_charges(maxM, c.n, p->nsplit, p->nt_uniform) : 0));
-    GP_CHECK(launch_slab_reduce(h, slot_probs(p, S_H) + p->a0, p->nhf, maxM, p->nsplit, 1, 1.0));      // (Y carries the factor 2)
-    if (p->q_bar && p->qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
-  } else if (p->q_bar) {       // the Q run's Qbar and v from its far field (four launches, no timer class); the product on the other run
-    const int rest0 = (p->q0 == 0) ? p->nq : 0;
-    if (!p->qbar_ahead) GP_CHECK(bwd_qbar(c));
-    GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + rest0, n64 - p->nq, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
+  if (p->routes.nhf > 0) {     // the activations' run from the stored A once and its factors once (hfar.hip), the dense product on the others
+    if (p->routes.q_bar && !c.qbar_ahead) GP_CHECK(bwd_qbar(c));
+    if (p->routes.hdn > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + p->routes.hd0, p->routes.hdn, maxM, c.n, p->nsplit, 1, 1, 2.0, p->routes.nt_uniform));
+    GP_CHECK(launch_hfar(h, (const HfarItem*)(p->d_misc + p->off.hf_items), p->routes.nhf, maxM, c.n, p->nsplit,
+                        p->routes.hdn == 0 ? gemm_nt_reduce_charges(maxM, c.n, p->nsplit, p->routes.nt_uniform) : 0));
+    GP_CHECK(launch_slab_reduce(h, slot_probs(p, S_H) + p->routes.a0, p->routes.nhf, maxM, p->nsplit, 1, 1.0));      // (Y carries the factor 2)
+    if (p->routes.q_bar && c.qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
+  } else if (p->routes.q_bar) {       // the Q run's Qbar and v from its far field (four launches, no timer class); the product on the other run
+    const int rest0 = (p->routes.q0 == 0) ? p->routes.nq : 0;
+    if (!c.qbar_ahead) GP_CHECK(bwd_qbar(c));
+    GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H) + rest0, n64 - p->routes.nq, maxM, c.n, p->nsplit, 1, 1, 2.0, p->routes.nt_uniform));
     // (pdgp_backward put them on the main stream, beside this product: S_QT waits for them here)
-    if (p->qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
-  } else if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H), n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
-  if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, slot_probs(p, S_H) + n64, G - n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->nt_uniform));
-  if (p->nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
+    if (c.qbar_ahead) GP_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_q, 0));
+  } else if (n64 > 0) GP_CHECK(launch_gemm_nt_reduce_batched(h, slot_probs(p, S_H), n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->routes.nt_uniform));
+  if (n64 < G) GP_CHECK(launch_gemm_f32_nt_reduce_batched(h, slot_probs(p, S_H) + n64, G - n64, maxM, c.n, p->nsplit, 1, 1, 2.0, p->routes.nt_uniform));
+  if (p->routes.nq > 0) {      // Q route: that product gave Qbar and v; H = (W Qbar) W^T, u = W v, grad q_mu += u
     f = GemmFlags(); f.triA = TRI_LOWER;
-    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QT), p->nq, maxM, maxM, f));
+    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QT), p->routes.nq, maxM, maxM, f));
     f = GemmFlags(); f.transB = 1; f.triB = TRI_UPPER;
-    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QHH), p->nq, maxM, maxM, f));
-    GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QU), p->nq, maxM, 0));
+    GP_CHECK(launch_gemm_batched(h, slot_probs(p, S_QHH), p->routes.nq, maxM, maxM, f));
+    GP_CHECK(launch_matvec_batched(h, slot_probs(p, S_QU), p->routes.nq, maxM, 0));
   }
   // grad q_sqrt += tril(H Lq)
   f = GemmFlags(); f.triB = TRI_LOWER; f.triC = TRI_LOWER; f.beta = 1.0;
@@ -600,10 +580,10 @@ static gp_status bwd_kuu_side(const BwdCall& c) {
 // family's, and its Kuf-side contraction is the product's epilogue, nothing stored (one precision per family).
 static gp_status bwd_kuf_product(const BwdCall& c, int slot0, int count, const HyFamily* fused = nullptr) {
   gp_pdgp_plan p = c.p; gp_handle h = p->h;
-  const int maxM = p->maxM, k64 = p->k64;
+  const int maxM = p->maxM, k64 = p->routes.k64;
   GemmFlags f;
   f.big_tiles = 1; f.scale_mode = 1; f.alpha = 2.0; f.timer = GP_TIMER_KUF_BAR; f.role = 3;
-  f.uniform_aligned = p->kuf_uniform;
+  f.uniform_aligned = p->routes.kuf_uniform;
   f.a32_ok = 1;          // (float32 GPs: b.R32 is in every problem's xb)
   if (fused) {
     f.role = 5; f.epilogue = 0; f.aux_x = c.x; f.aux_ktype = fused->type;
@@ -719,9 +699,8 @@ static bool bwd_two_family_order(gp_pdgp_plan p, HyFamily** first, HyFamily** se
 // reorder independent ones, never add or drop one that changes a bit.
 gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad) {
   gp_handle h = p->h;
-  const BwdCall c{p, params, x, n, grad};
+  BwdCall c{p, params, x, n, grad, false};
   const bool white = p->whiten != 0;
-  p->qbar_ahead = false;
   if (!white) GP_CHECK(bwd_unwhitened_head(c));
   // Everything that hangs off H = A diag(2 gv) A^T — grad q_sqrt, Wbar, the whole Kuu side — is independent of the
   // Kuf_bar product, which needs only R = W^T (Lq Lq^T - I) and alpha = W^T q_mu.  With early_fork the H chain
@@ -743,7 +722,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   // With a scan family (switches.h scan_side; measurements: DESIGN.md 3.02) the scan's launches go to the side stream, beside
   // the other families' Kuf_bar product.  The side stream serves ONE fork per backward pass — gp_side_begin refuses until
   // gp_side_join — so only the first taker gets it: a further scan family, or a contraction that asks after it, stays in line.
-  const bool scan_side = p->any_scan && gp_switches().scan_side != 0 && n >= 4096 && p->overlap >= 2;
+  const bool scan_side = p->routes.any_scan && gp_switches().scan_side != 0 && n >= 4096 && p->overlap >= 2;
   const bool forked = n >= 4096 && p->overlap >= 1 && gp_aux_fork(h);
   HyFamily *first = nullptr, *second = nullptr;
   const bool two = forked && p->overlap >= 2 && bwd_two_family_order(p, &first, &second);
@@ -752,7 +731,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   // family that contracts by the scan is issued ahead of it, so that the side stream starts at once.  qform_qbar = 2 keeps
   // the launches on the helper stream.  The same launches either way, the same bits.
   bool first_issued = false;
-  if (forked && early_fork && p->q_bar && gp_switches().qform_qbar != 2 &&
+  if (forked && early_fork && p->routes.q_bar && gp_switches().qform_qbar != 2 &&
       (h->ev_q || hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) == hipSuccess)) {
     hipStream_t helper = h->stream;       // (not a GpStreamScope: the main stream may be the null stream, which it reads as "stay")
     h->stream = h->main_stream_saved;
@@ -764,7 +743,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
       (void)gp_aux_end(h);
       return st != GP_OK ? st : gp_fail(h, GP_ERR_HIP, "event hand-over to the helper stream failed");
     }
-    p->qbar_ahead = true;
+    c.qbar_ahead = true;
   }
   if (forked) {
     const gp_status st = bwd_helper_chain(c, early_fork);
@@ -784,7 +763,7 @@ gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, i
   } else {
     // one product over the whole batch, or family by family when some family has a route of its own; then the families'
     // contractions side by side: the matrix-core ones on this stream, the others (short, HBM-bound) on the side stream
-    if (p->any_routed) { for (const auto& fam : p->hy_fams) GP_CHECK(bwd_kuf_bar_step(c, fam, scan_side)); }
+    if (p->routes.any_routed) { for (const auto& fam : p->hy_fams) GP_CHECK(bwd_kuf_bar_step(c, fam, scan_side)); }
     else GP_CHECK(bwd_kuf_product(c, 0, p->nK));
     if (!forked) {       // (no helper stream to be had)
       if (early_fork) { GP_CHECK(bwd_h_chain(c)); GP_CHECK(bwd_wbar_chain(c)); }

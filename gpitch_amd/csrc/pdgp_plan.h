@@ -36,11 +36,11 @@ struct PdgpGP {
   int need_theta = 1, need_z = 1;   // gp_pdgp_set_grad_needs
   int f32 = 0;                      // this GP's M x N strips are float32 (gp_pdgp_set_precision / gp_pdgp_set_gp_precision)
   int64_t off_theta = 0, off_z = 0, off_qmu = 0, off_qsqrt = 0;
-  int fam = -1;                     // its family in hy_fams (pdgp_upload_bwd; -1: no kernel gradient asked)
+  int fam = -1;                     // its family in hy_fams (pdgp_build_families; -1: no kernel gradient asked)
   int np_uf = 0, np_uu = 0;         // GPs of an unbatched family: partial records its own contractions left this step
 };
 
-// How a kernel family gets its Kuf-side hyper-gradient sums.  Decided at bind (pdgp_bwd.hip: pdgp_select_routes),
+// How a kernel family gets its Kuf-side hyper-gradient sums.  Decided at bind (pdgp_bwd.hip: pdgp_decide_routes),
 // from shapes, kernel types, precision, the gradient needs, the switches and the two setters — never from the overlap level.
 enum KufRoute {
   KUF_PRODUCT,   // Kuf_bar = R (A diag(2 gv)) stored, then the family's contraction
@@ -86,6 +86,30 @@ struct BwdBufs {  // per-GP backward workspace (device)
   double* g_qmu_w = nullptr; double* g_Lq_w = nullptr;   // M, M x M
 };
 
+// What the caller said about the routes (DESIGN.md 3.04's table has every rule); written by pdgp_set_perm alone.
+struct PdgpPerms {
+  bool frames_ascending = false;                          // gp_pdgp_set_frames_ascending: every batch is in time order
+  bool qform = false, q_zasc = false, q_bar_ok = false;   // gp_pdgp_set_qform's bits 0, 1 (the inducing inputs ascend), 2
+  bool afar_ok = false;                                   // gp_pdgp_set_far_act (they ascend for the Matern-3/2 GPs too)
+  bool scan_far_ok = true, h_far_ok = true;               // gp_pdgp_set_scan_far, gp_pdgp_set_h_far: one handle, both forms
+};
+
+// What the bound batch takes: written by pdgp_decide_routes (pdgp_bwd.hip) alone, at bind.  All zero: dense everywhere — and
+// so are the backward pass's fields after a bind without a gradient.
+struct PdgpRoutes {
+  int q0 = 0, nq = 0, qk0 = 0;          // Q route (3.03): latent GPs [q0, q0 + nq); qk0 = the run's first slot in the compacted batch
+  bool q_far = false, q_bar = false;    // the run's product (3.05) / its Qbar and v (3.06) from the far field; with q_bar its
+                                        // problems leave the split-K launch, which covers the other latent GPs
+  int a0 = 0, na = 0;                   // activation far field (3.07): latent GPs [a0, a0 + na).  The rest: the backward pass's
+  int nhf = 0, hd0 = 0, hdn = 0;        // H from the factors (3.10): nhf = na when taken; [hd0, hd0 + hdn) is left to the dense product
+  bool contiguous = false;              // whitened, and every family sits in one run of the compacted batch
+  bool any_scan = false;                // some family takes KUF_SCAN
+  bool any_routed = false;              // some family's route is not KUF_PRODUCT: Kuf_bar is then issued family by family
+  int kuf_uniform = 0;                  // even n and every GP of the compacted batch M = maxM (R, A, G: arena buffers, even ld)
+  int nt_uniform = 0;                   // the split-K product: n a multiple of 4 and every latent GP M = maxM
+  int k64 = 0;                          // float64 GPs of the compacted batch (they come first)
+};
+
 struct gp_pdgp_plan_s {
   gp_handle h = nullptr;
   int P = 0, G = 0, whiten = 1, nlin = 0, maxN = 0;
@@ -113,20 +137,13 @@ struct gp_pdgp_plan_s {
   struct HyFamily {
     int type = 0, m = 0, first = 0, count = 0, M = 0, mfma = 0, f32 = 0; bool batched = false; bool scan_ws = false;
     int slot0 = -1;                  // its first slot in the compacted batch; -1: its GPs do not sit in one run of it
-    KufRoute route = KUF_PRODUCT;
+    KufRoute route = KUF_PRODUCT;    // (route, scan_far and np_uf at bind: pdgp_decide_routes; the rest: pdgp_build_families)
     bool scan_far = false;           // KUF_SCAN: its first launch takes the moments from afar.hip's factored A
     int np_uf = 0, np_uu = 0;        // batched family: partial records per GP.  np_uf is fixed at bind by the fused and scan routes;
                                      // the contractions report the others at launch
     std::vector<int> gps;
   };
   std::vector<HyFamily> hy_fams;
-  // shape facts of the bound batch the routes and the launches share (pdgp_select_routes)
-  bool contiguous = false;     // whitened, and every family sits in one run of the compacted batch
-  bool any_scan = false;       // some family takes KUF_SCAN
-  bool any_routed = false;     // some family's route is not KUF_PRODUCT: Kuf_bar is then issued family by family
-  int kuf_uniform = 0;         // even n and every GP of the compacted batch M = maxM (R, A, G: arena buffers, even ld)
-  int nt_uniform = 0;          // the split-K product: n a multiple of 4 and every latent GP M = maxM
-  int k64 = 0;                 // float64 GPs of the compacted batch (they come first)
   double* qw_block = nullptr; size_t qw_doubles = 0;   // [q' | grad q'] of all GPs, contiguous (one memset)
   double* kl_dummy = nullptr;
   int nsplit = 1;
@@ -143,31 +160,9 @@ struct gp_pdgp_plan_s {
            double* g_noise = nullptr; bool pending = false; } fin;
   int overlap = 2;             // gp_pdgp_set_overlap: 0 one stream, 1 Kuu factorisation / Kuu-side backward on the helper
                                // stream, 2 also the H = A D A^T chain next to Kuf_bar
-  bool frames_ascending = false;   // gp_pdgp_set_frames_ascending: the caller promises time-ordered batches
   bool era_ready = false;      // pdgp_prefetch_backward ran for the current evaluation
-  // Q route (pdgp_bwd.hip pdgp_qform_select): gp_pdgp_set_qform's permission, and the run of latent GPs
-  // [q0, q0 + nq) that takes it at the bound batch size (nq = 0: none); qk0 = the run's first slot in the compacted batch
-  bool qform = false;
-  int q0 = 0, nq = 0, qk0 = 0;
-  // far field of the run's product: gp_pdgp_set_qform's second bit — the caller vouches that the inducing inputs
-  // of every MercerMatern12sm GP ascend (they are fixed on this route) — and whether the bound run takes it
-  bool q_zasc = false, q_far = false;
-  // Qbar and v of the run from the far field as well: gp_pdgp_set_qform's third bit allows it, q_bar says
-  // the bound run takes it — its problems then leave the split-K launch, which covers the other latent GPs
-  bool q_bar_ok = false, q_bar = false;
-  bool qbar_ahead = false;     // this backward pass has put those launches on the main stream (pdgp_backward)
-  // activation far field (pdgp_bwd.hip pdgp_afar_select): gp_pdgp_set_far_act's permission — the caller vouches
-  // that the inducing inputs of every Matern-3/2 GP ascend — and the run [a0, a0 + na) that takes it at the bound batch size
-  bool afar_ok = false;
-  int a0 = 0, na = 0;
-  // the scan's moments from that far field (pdgp_select_routes): gp_pdgp_set_scan_far's permission, given by
-  // default — it exists so that one handle can evaluate both forms
-  bool scan_far_ok = true;
-  // H and u of that run from the factored A (pdgp_select_routes): gp_pdgp_set_h_far's permission, given by
-  // default; nhf = na when the bound gradient evaluation takes the form (the run is then [a0, a0 + na)), else 0; the latent
-  // GPs left to the dense split-K product are the run [hd0, hd0 + hdn), possibly empty
-  bool h_far_ok = true;
-  int nhf = 0, hd0 = 0, hdn = 0;
+  PdgpPerms perms;             // what the caller allowed (the setters)
+  PdgpRoutes routes;           // what the bound batch takes (pdgp_decide_routes)
   bool factor_valid = false;   // L / W hold the factorisation of the parameters last passed to gp_pdgp_predict
   // two-stage (pitch-sharded) evaluation: what gp_pdgp_elbo_begin staged for gp_pdgp_elbo_end
   int staged_n = 0; double* staged_grad = nullptr; const double* staged_params = nullptr;
@@ -179,5 +174,60 @@ struct gp_pdgp_plan_s {
 };
 
 // is latent GP g in the run that takes the Q route at the bound batch size?  (A family asks its route field instead.)
-static inline bool pdgp_on_q_route(const gp_pdgp_plan_s* p, int g) { return g >= p->q0 && g < p->q0 + p->nq; }
+static inline bool pdgp_on_q_route(const gp_pdgp_plan_s* p, int g) { return g >= p->routes.q0 && g < p->routes.q0 + p->routes.nq; }
+
+// a setter's body: a permission that changes drops the bind cache, since the routes and the descriptors depend on it
+static inline gp_status pdgp_set_perm(gp_pdgp_plan_s* p, bool PdgpPerms::*field, bool value) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (p->perms.*field != value) { p->perms.*field = value; p->last_params = nullptr; }
+  return GP_OK;
+}
+
+// Could latent GP g EVER take a route?  Switches, the plan's whitening, the GP's precision, kernel and M, the plan's largest
+// batch: all fixed once the workspace is set.  pdgp_carve reserves a route's regions where its predicate holds, and
+// pdgp_decide_routes asks the same predicate — not the carved pointers — so the two cannot disagree.
+static inline bool pdgp_may_q(const gp_pdgp_plan_s* p, int g) {
+  return gp_switches().qform != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MERCER_MATERN12SM;
+}
+static inline bool pdgp_may_qfar(const gp_pdgp_plan_s* p, int g) {
+  return pdgp_may_q(p, g) && gp_switches().qform_far != 0 && qfar_takes(p->gps[g].M, p->maxN, p->gps[g].m);
+}
+static inline bool pdgp_may_qbar(const gp_pdgp_plan_s* p, int g) {
+  return pdgp_may_qfar(p, g) && gp_switches().qform_qbar != 0 && qbar_takes(p->gps[g].M, p->maxN, p->gps[g].m);
+}
+static inline bool pdgp_may_afar(const gp_pdgp_plan_s* p, int g) {
+  return gp_switches().act_far != 0 && p->whiten && !p->gps[g].f32 && p->gps[g].ktype == GP_KERN_MATERN32 && afar_takes(p->gps[g].M, p->maxN);
+}
+static inline bool pdgp_may_hfar(const gp_pdgp_plan_s* p, int g) {
+  return pdgp_may_afar(p, g) && gp_switches().h_far != 0 && hfar_takes(p->gps[g].M, p->maxN);
+}
+static inline bool pdgp_may_scan(const gp_pdgp_plan_s* p, int g) {
+  return gp_switches().kuf_scan != 0 && p->whiten && !p->gps[g].f32 && kuf_scan_nq(p->gps[g].ktype) > 0;
+}
+
+// The one run that the members among g = 0 .. G - 1 form.  False: a member is disqualified (asked of members only, in order),
+// or the members are not neighbours.  True: they are [*first, *first + *count) — count 0, first 0 when there is none.
+template <class Member, class Disqualified>
+static inline bool pdgp_single_run(int G, Member member, Disqualified disqualified, int* first, int* count) {
+  int last = *first = *count = 0;
+  for (int g = 0; g < G; g++) {
+    if (!member(g)) continue;
+    if (disqualified(g)) return false;
+    if (*count == 0) *first = g;
+    last = g; (*count)++;
+  }
+  return *count == 0 || last - *first + 1 == *count;
+}
+
+// pdgp_bwd.hip, for pdgp.hip.  A bind (pdgp_bind) runs: families (with a gradient), routes, forward and backward descriptors.
+void pdgp_build_families(gp_pdgp_plan p);
+void pdgp_decide_routes(gp_pdgp_plan p, int n, bool grad);
+void pdgp_upload_qform(gp_pdgp_plan p, const double* params);
+void pdgp_upload_afar(gp_pdgp_plan p, const double* params);
+void pdgp_upload_bwd(gp_pdgp_plan p, const double* params, int n, double* grad);
+gp_status pdgp_qform_prepare(gp_pdgp_plan p, const double* x, int n);
+gp_status pdgp_qform_join(gp_pdgp_plan p);
+gp_status pdgp_afar_run(gp_pdgp_plan p, const double* x, int n);
+gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done);
+gp_status pdgp_backward(gp_pdgp_plan p, const double* params, const double* x, int n, double* grad);
 
