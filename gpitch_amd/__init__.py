@@ -16,7 +16,7 @@ from .pdgp_batch import optimize_many, predict_many, predict_sources_many, PdgpB
 from .pdgp_batch import sample_sources_many, check_sampleable  # noqa: E402,F401
 from .pdgp_batch import tie_groups, check_tied  # noqa: E402,F401
 from .sgpr_ss import merged_order, sample_eps_shapes, sample_components  # noqa: E402,F401
-from .sgpr_ss import ssm_timeline, ssm_state_dim  # noqa: E402,F401
+from .sgpr_ss import ssm_timeline, ssm_state_dim, ssm_sample_eps_shapes  # noqa: E402,F401
 from . import checkpoint  # noqa: E402,F401  (binds state_dict / load_state_dict to Pdgp, SGPRSS and Kern)
 from .checkpoint import save, load  # noqa: E402,F401
 from .init_models import init_liv, init_iv  # noqa: E402,F401

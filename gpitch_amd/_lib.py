@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "gp_sgpr_sample_source_sparse", "gp_sgpr_sample_source_workspace_bytes",
     "gp_sgpr_predict_source_ssm", "gp_sgprb_predict_source_ssm", "gp_ssm_smooth_workspace_bytes",
     "gp_sgpr_exact_loglik_grad", "gp_sgprb_exact_loglik_grad", "gp_ssm_score_workspace_bytes",
+    "gp_sgpr_sample_source_ssm", "gp_sgprb_sample_source_ssm", "gp_ssm_sample_workspace_bytes",
     "gp_sgprb_create", "gp_sgprb_destroy", "gp_sgprb_num_params", "gp_sgprb_num_windows", "gp_sgprb_workspace_bytes",
     "gp_sgprb_set_workspace", "gp_sgprb_bound_grad", "gp_sgprb_set_graphs", "gp_sgprb_eval_counts",
     "gp_sgprb_set_inducing_counts",
@@ -274,6 +275,9 @@ def load_library():
         "gp_sgpr_exact_loglik_grad": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz]),
         "gp_sgprb_exact_loglik_grad": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz]),
         "gp_ssm_score_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "gp_sgpr_sample_source_ssm": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, sz]),
+        "gp_sgprb_sample_source_ssm": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, sz]),
+        "gp_ssm_sample_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
         "gp_sgpr_predict_f_full": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]),
         "gp_sgpr_predict_source_full": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz]),
         "gp_sgpr_predict_source_workspace_bytes": (sz, [i32, i32]),

@@ -471,6 +471,13 @@ gp_status ssm_smooth_run(gp_handle h, const int* ktype, const int* km, const int
                          const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
                          const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
                          double* var, double* loglik, void* ws, size_t ws_bytes);
+// joint draws from the same posterior by the simulation smoother (gp_sgpr_sample_source_ssm, gp_sgprb_sample_source_ssm): window w's
+// eps_x + w * S * steps * d ([S][steps][d], `steps` the call's longest timeline), eps_y + w * S * N, out + w * P * S * n ([P][S][n])
+size_t ssm_sample_workspace_bytes(int d, int steps, int P, int S, int count);
+gp_status ssm_sample_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, int S,
+                         const double* eps_x, const double* eps_y, double* out, void* ws, size_t ws_bytes);
 gp_status launch_overlap_merge(gp_handle h, const double* y, int nw, int ws, int64_t ldy, int n, int square, double* out);
 // lik.hip
 // whitened KL: each item writes GP_KL_BLOCKS partial sums to out[0..GP_KL_BLOCKS)

@@ -958,6 +958,16 @@ gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const
                         order_host, out_step_host, &steps, mean, var, loglik, workspace, workspace_bytes);
 }
 
+// Joint draws from that posterior by the simulation smoother (ssm_smooth.hip): the plan's part is the same
+gp_status gp_sgpr_sample_source_ssm(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                    const double* Xnew, int32_t n, const int32_t* order_host, const int32_t* out_step_host,
+                                    int32_t steps, int32_t S, const double* eps_x, const double* eps_y, double* out,
+                                    void* workspace, size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  return ssm_sample_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, N, Xnew, n, 1,
+                        order_host, out_step_host, &steps, S, eps_x, eps_y, out, workspace, workspace_bytes);
+}
+
 // The exact log-likelihood and its gradient in the plan's parameter layout by the state-space score walk (ssm_smooth.hip): as
 // above, the plan gives the kernel structure and the layout only.
 gp_status gp_sgpr_exact_loglik_grad(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,

@@ -790,6 +790,19 @@ extern "C" gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan_t p, const double
                         count, order_host, out_step_host, steps_host, mean, var, loglik, workspace, workspace_bytes);
 }
 
+// gp_sgpr_sample_source_ssm of the first `count` windows: one wavefront per (window, draw) in the walks
+extern "C" gp_status gp_sgprb_sample_source_ssm(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
+                                                const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
+                                                const int32_t* out_step_host, const int32_t* steps_host, int32_t S,
+                                                const double* eps_x, const double* eps_y, double* out, void* workspace,
+                                                size_t workspace_bytes) {
+  if (!p) return GP_ERR_BAD_ARG;
+  if (count < 1 || count > p->W)
+    return gp_fail(p->h, GP_ERR_BAD_ARG, "gp_sgprb_sample_source_ssm: bad argument (1 <= count <= num_windows)");
+  return ssm_sample_run(p->h, p->ktype.data(), p->m.data(), p->off_theta.data(), p->P, p->nparams, params, X, Y, p->N, Xnew, n,
+                        count, order_host, out_step_host, steps_host, S, eps_x, eps_y, out, workspace, workspace_bytes);
+}
+
 // gp_sgpr_exact_loglik_grad of the first `count` windows: one workgroup per window in the walks
 extern "C" gp_status gp_sgprb_exact_loglik_grad(gp_sgprb_plan_t p, const double* params, const double* X, const double* Y,
                                                 int32_t count, const int32_t* order_host, double* loglik, double* grad,

@@ -52,6 +52,10 @@
 //                                d/d l_p = sum_(j,i) (gphi[j][i] - 2 v_p phi gq[j][i]) phi D_j / l_p^2
 //                                d/d e_k = sum_j (gh_c h_c + gh_s h_s) / (2 e_k),   d/d f_k = sum_j 2 pi t_j (gh_s h_c - gh_c h_s)
 //                              and d/d noise = gs2; one more workgroup per window scatters gres through `order`.
+//
+// Joint draws from the same posterior (ssm_sample_run): launches 1 - 4 with the history off (the gain walk), then the
+// simulation smoother's ssmp_* kernels, described above them: three elementwise walks of one d-vector per draw, one wavefront per
+// (window, draw), and a gather.  No steps * d^2 block in that call's workspace.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -565,18 +569,315 @@ size_t ssm_score_workspace_bytes(int d, int steps, int P, int count) {
   return gp_measure([&](GpArena& ar) { ssms_carve(ar, d, steps, P, count); ssms_score_carve(ar, d, steps, count); }) + GP_WS_TAIL_OP;
 }
 
+// ==== joint draws: the simulation smoother =====================================================================
+// A draw of all sources at all new frames from the exact posterior, by Durbin and Koopman's simulation smoother written with the
+// disturbance smoother.  Transition, process noise and start covariance are diagonal, so a draw is three elementwise walks of one
+// d-vector on top of the gain walk (ssms_forward_kernel with hist = 0: g and F of the observed steps, no a^-, no P^-).  Per draw s
+// with standard normals ex[j][i] (step j, coordinate i) and ey[o] (training frame o):
+//   1. w = 0;  w <- phi_j w + sq_j ex_j  (sq_0 = sqrt(v), sq_j = sqrt(q_j));  observed: c_j = (y_o - sigma ey_o - h_j.w) / F_j,
+//      w <- w + g_j c_j.   (the prior path and the filter mean of its residual obey one transition: only their sum is carried)
+//   2. r = 0 behind the last step;  r <- phi_(j+1) r;  observed: r <- r + h_j (c_j - (g_j.r) / F_j);  keep r_j.
+//   3. z = 0;  z <- phi_j z + sq_j ex_j + q_j r_j  (q_0 = v);  keep h_j z, of which source p's value at step j is the sum over its
+//      coordinates.
+// The map is affine in (ex, ey); at zero it is the smoothed mean, and its linear part T has T T^T = the joint posterior covariance.
+// Launches behind the prologue and the gain walk (all windows and draws of the call in each):
+//   a. ssmp_prep_kernel        sq [steps][P] (row 0: sqrt(v)), 1 / F per step (0 at an unobserved step), sigma: the walks carry no
+//                              sqrt, exp or division
+//   b. ssmp_obs_kernel         y_o - sigma ey_o per (draw, step), in walk order
+//   c. ssmp_walk1_kernel       one wavefront per (window, draw): lane l holds coordinates l and l + 64 (NC = 2, d > 64), no LDS, no
+//   d. ssmp_walk2_kernel       barrier; the dot product of an observed step is one butterfly (ssms_wave_sum); the rows of step
+//   e. ssmp_walk3_kernel       j + SSMP_PF are loaded while step j is computed (a ring of SSMP_PF register slots)
+//   f. ssmp_gather_kernel      out [P][S][n] through out_step: 32 frames' rows of h_j z through LDS, a source's coordinates summed in
+//                              ascending order
+// Determinism: no atomics, every sum in a fixed order; a (window, draw) is one wavefront that reads nothing of the others', so a
+// draw's bits depend neither on S, nor on the windows that share the call.
+// steps in flight per walk (a measurement variant may set its own: tools/build_variant.sh)
+#ifndef SSMP_PF
+#define SSMP_PF 4
+#endif
+struct SsmpWin {
+  const double* eps_x; const double* eps_y;        // [S][ldx], [S][N]
+  double* out;                                     // [P][S][n]
+  double *sq, *fi, *sg;                            // [steps][P], [steps], one
+  double *yd, *c, *R;                              // [S][lds], [S][lds], [S][lds][d]
+  size_t ldx, lds;                                 // the call's longest timeline times d, and that timeline
+};
+
+__global__ void __launch_bounds__(256) ssmp_prep_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins,
+                                                        const SsmsMeta* __restrict__ mt) {
+  const SsmsWin w = wins[blockIdx.y];
+  const SsmpWin pw = pwins[blockIdx.y];
+  const int np = mt->P;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t j = e / np;
+  const int p = (int)(e % np);
+  if (j >= (size_t)w.steps) return;
+  pw.sq[j * np + p] = sqrt(j == 0 ? w.params[mt->toff[p]] : w.q[j * np + p]);
+  if (p == 0) pw.fi[j] = w.order[j] < mt->N ? 1.0 / w.ef[2 * j + 1] : 0.0;
+  if (e == 0) pw.sg[0] = sqrt(w.params[0]);
+}
+
+__global__ void __launch_bounds__(256) ssmp_obs_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins, int N) {
+  const SsmsWin w = wins[blockIdx.z];
+  const SsmpWin pw = pwins[blockIdx.z];
+  const int j = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (j >= w.steps) return;
+  const int o = w.order[j];
+  pw.yd[(size_t)s * pw.lds + j] = o < N ? w.ys[j] - pw.sg[0] * pw.eps_y[(size_t)s * N + o] : 0.0;
+}
+
+// a lane's coordinates and what does not change along the walk
+template <int NC>
+struct SsmpLane {
+  int i[NC], src[NC];
+  bool on[NC];
+  __device__ __forceinline__ SsmpLane(const SsmsMeta* mt) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      i[c] = (int)threadIdx.x + 64 * c;
+      on[c] = i[c] < mt->d;
+      src[c] = on[c] ? mt->csrc[i[c]] : 0;
+    }
+  }
+};
+
+// ---- c. walk 1 -------------------------------------------------------------------------------------------------------------
+template <int NC>
+__global__ void __launch_bounds__(64) ssmp_walk1_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins,
+                                                        const SsmsMeta* __restrict__ mt) {
+  struct Slot { double h[NC], ph[NC], sq[NC], ex[NC], g[NC], yd, fi; };
+  const SsmsWin w = wins[blockIdx.y];
+  const SsmpWin pw = pwins[blockIdx.y];
+  const int s = blockIdx.x, d = mt->d, np = mt->P, steps = w.steps;
+  const SsmpLane<NC> ln(mt);
+  const double* __restrict__ ex = pw.eps_x + (size_t)s * pw.ldx;
+  const double* __restrict__ yd = pw.yd + (size_t)s * pw.lds;
+  double* __restrict__ cs = pw.c + (size_t)s * pw.lds;
+  auto load = [&](Slot& t, int j) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      const size_t e = (size_t)j * d + ln.i[c], q = (size_t)j * np + ln.src[c];
+      t.h[c] = ln.on[c] ? w.hrow[e] : 0.0;
+      t.ph[c] = ln.on[c] ? w.phi[q] : 0.0;
+      t.sq[c] = ln.on[c] ? pw.sq[q] : 0.0;
+      t.ex[c] = ln.on[c] ? ex[e] : 0.0;
+      t.g[c] = ln.on[c] ? w.g[e] : 0.0;            // (an unobserved step's g was never written and is not used)
+    }
+    t.yd = yd[j]; t.fi = pw.fi[j];
+  };
+  Slot ring[SSMP_PF];
+#pragma unroll
+  for (int k = 0; k < SSMP_PF; k++)
+    if (k < steps) load(ring[k], k);
+  double wv[NC];
+#pragma unroll
+  for (int c = 0; c < NC; c++) wv[c] = 0.0;
+  for (int j0 = 0; j0 < steps; j0 += SSMP_PF) {
+#pragma unroll
+    for (int k = 0; k < SSMP_PF; k++) {
+      const int j = j0 + k;
+      if (j < steps) {                             // (the same for the whole wavefront, as is fi below)
+        const Slot t = ring[k];
+        if (j + SSMP_PF < steps) load(ring[k], j + SSMP_PF);
+#pragma unroll
+        for (int c = 0; c < NC; c++) wv[c] = fma(t.ph[c], wv[c], t.sq[c] * t.ex[c]);
+        if (t.fi != 0.0) {
+          double x = t.h[0] * wv[0];
+#pragma unroll
+          for (int c = 1; c < NC; c++) x = fma(t.h[c], wv[c], x);
+          ssms_wave_sum(x);
+          const double cj = (t.yd - x) * t.fi;
+#pragma unroll
+          for (int c = 0; c < NC; c++) wv[c] = fma(t.g[c], cj, wv[c]);
+          if (threadIdx.x == 0) cs[j] = cj;
+        }
+      }
+    }
+  }
+}
+
+// ---- d. walk 2: slot k holds a step counted from the last ---------------------------------------------------------------------
+template <int NC>
+__global__ void __launch_bounds__(64) ssmp_walk2_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins,
+                                                        const SsmsMeta* __restrict__ mt) {
+  struct Slot { double h[NC], ph[NC], g[NC], c, fi; };
+  const SsmsWin w = wins[blockIdx.y];
+  const SsmpWin pw = pwins[blockIdx.y];
+  const int s = blockIdx.x, d = mt->d, np = mt->P, steps = w.steps;
+  const SsmpLane<NC> ln(mt);
+  const double* __restrict__ cs = pw.c + (size_t)s * pw.lds;
+  double* __restrict__ R = pw.R + (size_t)s * pw.lds * d;
+  auto load = [&](Slot& t, int j) {                // ph: the transition out of step j, 1 behind the last step
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      const size_t e = (size_t)j * d + ln.i[c];
+      t.h[c] = ln.on[c] ? w.hrow[e] : 0.0;
+      t.ph[c] = (ln.on[c] && j + 1 < steps) ? w.phi[((size_t)j + 1) * np + ln.src[c]] : 1.0;
+      t.g[c] = ln.on[c] ? w.g[e] : 0.0;
+    }
+    t.c = cs[j]; t.fi = pw.fi[j];                  // (an unobserved step's c was never written and is not used)
+  };
+  Slot ring[SSMP_PF];
+#pragma unroll
+  for (int k = 0; k < SSMP_PF; k++)
+    if (k < steps) load(ring[k], steps - 1 - k);
+  double r[NC];
+#pragma unroll
+  for (int c = 0; c < NC; c++) r[c] = 0.0;
+  for (int b0 = 0; b0 < steps; b0 += SSMP_PF) {
+#pragma unroll
+    for (int k = 0; k < SSMP_PF; k++) {
+      const int b = b0 + k, j = steps - 1 - b;
+      if (b < steps) {
+        const Slot t = ring[k];
+        if (b + SSMP_PF < steps) load(ring[k], j - SSMP_PF);
+#pragma unroll
+        for (int c = 0; c < NC; c++) r[c] *= t.ph[c];
+        if (t.fi != 0.0) {
+          double x = t.g[0] * r[0];
+#pragma unroll
+          for (int c = 1; c < NC; c++) x = fma(t.g[c], r[c], x);
+          ssms_wave_sum(x);
+          const double u = fma(-x, t.fi, t.c);
+#pragma unroll
+          for (int c = 0; c < NC; c++) r[c] = fma(t.h[c], u, r[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; c++)
+          if (ln.on[c]) R[(size_t)j * d + ln.i[c]] = r[c];
+      }
+    }
+  }
+}
+
+// ---- e. walk 3: r_j is read SSMP_PF steps ahead of the store of h_j z over it (a lane reads and writes its own entries only) ----
+template <int NC>
+__global__ void __launch_bounds__(64) ssmp_walk3_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins,
+                                                        const SsmsMeta* __restrict__ mt) {
+  struct Slot { double h[NC], ph[NC], sq[NC], q[NC], ex[NC], r[NC]; };
+  const SsmsWin w = wins[blockIdx.y];
+  const SsmpWin pw = pwins[blockIdx.y];
+  const int s = blockIdx.x, d = mt->d, np = mt->P, steps = w.steps;
+  const SsmpLane<NC> ln(mt);
+  const double* __restrict__ ex = pw.eps_x + (size_t)s * pw.ldx;
+  double* R = pw.R + (size_t)s * pw.lds * d;
+  double v[NC];
+#pragma unroll
+  for (int c = 0; c < NC; c++) v[c] = ln.on[c] ? w.params[mt->toff[ln.src[c]]] : 0.0;
+  auto load = [&](Slot& t, int j) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      const size_t e = (size_t)j * d + ln.i[c], q = (size_t)j * np + ln.src[c];
+      t.h[c] = ln.on[c] ? w.hrow[e] : 0.0;
+      t.ph[c] = ln.on[c] ? w.phi[q] : 0.0;
+      t.sq[c] = ln.on[c] ? pw.sq[q] : 0.0;
+      t.q[c] = j == 0 ? v[c] : (ln.on[c] ? w.q[q] : 0.0);
+      t.ex[c] = ln.on[c] ? ex[e] : 0.0;
+      t.r[c] = ln.on[c] ? R[e] : 0.0;
+    }
+  };
+  Slot ring[SSMP_PF];
+#pragma unroll
+  for (int k = 0; k < SSMP_PF; k++)
+    if (k < steps) load(ring[k], k);
+  double z[NC];
+#pragma unroll
+  for (int c = 0; c < NC; c++) z[c] = 0.0;
+  for (int j0 = 0; j0 < steps; j0 += SSMP_PF) {
+#pragma unroll
+    for (int k = 0; k < SSMP_PF; k++) {
+      const int j = j0 + k;
+      if (j < steps) {
+        const Slot t = ring[k];
+        if (j + SSMP_PF < steps) load(ring[k], j + SSMP_PF);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+          z[c] = fma(t.ph[c], z[c], fma(t.q[c], t.r[c], t.sq[c] * t.ex[c]));
+          if (ln.on[c]) R[(size_t)j * d + ln.i[c]] = t.h[c] * z[c];
+        }
+      }
+    }
+  }
+}
+
+// ---- f. new frames i0 .. i0 + cnt - 1 of every window and draw through out_step (ostep holds that slice) ----------------------
+// A workgroup takes SSMP_GF frames of one (window, draw): their rows of h_j z come into LDS with the wavefronts reading along the
+// rows (a thread per frame reading its own row would stride by d), then thread (source, frame) adds the source's coordinates
+// in ascending order.  The rows lie an odd number of doubles apart, so the frames of one coordinate fall into different banks.
+#define SSMP_GF 32
+__global__ void __launch_bounds__(256) ssmp_gather_kernel(const SsmsWin* __restrict__ wins, const SsmpWin* __restrict__ pwins,
+                                                          const SsmsMeta* __restrict__ mt, int S, int n, int i0, int cnt) {
+  __shared__ double tile[SSMP_GF * (SSMS_MAX_D + 1)];
+  const SsmsWin w = wins[blockIdx.z];
+  const SsmpWin pw = pwins[blockIdx.z];
+  const int s = blockIdx.y, f0 = blockIdx.x * SSMP_GF, d = mt->d, np = mt->P, ld = d | 1;
+  const int nf = min(SSMP_GF, cnt - f0);
+  const double* __restrict__ R = pw.R + (size_t)s * pw.lds * d;
+  for (int e = threadIdx.x; e < nf * d; e += 256) {
+    const int f = e / d, k = e - f * d;
+    tile[f * ld + k] = R[(size_t)w.ostep[f0 + f] * d + k];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < nf * np; e += 256) {
+    const int p = e / nf, f = e - p * nf;
+    double m = 0.0;
+    for (int k = mt->coff[p]; k < mt->coff[p + 1]; k++) m += tile[f * ld + k];
+    pw.out[((size_t)p * S + s) * n + i0 + f0 + f] = m;
+  }
+}
+
+// the sampler's carve: the smoother's prologue and gain blocks (no a^-, no P^-, no per-step posterior), then its own
+struct SsmpBufs { SsmsBufs b; char* desc; double *sq, *fi, *sg, *yd, *c, *R; };
+static SsmpBufs ssmp_carve(GpArena& ar, size_t d, size_t steps, size_t P, size_t S, size_t count) {
+  SsmpBufs o{};
+  SsmsBufs& b = o.b;
+  b.desc = ar.take<char>(ssms_desc_layout(count, P).bytes);
+  b.order = ar.take<int>(count * steps);
+  b.want = ar.take<int>(count * steps);
+  b.ostep = ar.take<int>(count * steps);
+  b.t = ar.take<double>(count * steps);
+  b.ys = ar.take<double>(count * steps);
+  b.feat = ar.take<double>(count * (d + 6 * P) * steps);
+  b.hrow = ar.take<double>(count * steps * d);
+  b.phi = ar.take<double>(count * steps * P);
+  b.q = ar.take<double>(count * steps * P);
+  b.g = ar.take<double>(count * steps * d);
+  b.ef = ar.take<double>(count * steps * 2);
+  o.desc = ar.take<char>(count * sizeof(SsmpWin));
+  o.sq = ar.take<double>(count * steps * P);
+  o.fi = ar.take<double>(count * steps);
+  o.sg = ar.take<double>(count);
+  o.yd = ar.take<double>(count * S * steps);
+  o.c = ar.take<double>(count * S * steps);
+  o.R = ar.take<double>(count * S * steps * d);
+  return o;
+}
+
+size_t ssm_sample_workspace_bytes(int d, int steps, int P, int S, int count) {
+  if (d < 1 || d > SSMS_MAX_D || steps < 1 || P < 1 || P > d || S < 1 || count < 1) return 0;
+  return gp_measure([&](GpArena& ar) { ssmp_carve(ar, d, steps, P, S, count); }) + GP_WS_TAIL_OP;
+}
+
 // Every check, then the launches.  Windows w < count: params + w * param_stride, X / Y + w * N, Xnew + w * n, order_host
 // + w * (N + n) (the first steps_host[w] entries), out_step_host + w * n, mean / var + w * P * n, loglik + w.
 // (`score`: the call is ssm_score_run's; n = 0, the history is kept and launches 8 and 9 follow the forward walk)
+// (`smp`: the call is ssm_sample_run's; n >= 1, the sampler's carve, no history, and ssmp_launch follows the forward walk; mean,
+// var and loglik are null)
 struct SsmsScoreOut { double* grad; double* resid; };
+struct SsmsSampleIn { int S; const double* eps_x; const double* eps_y; double* out; };
+static gp_status ssmp_launch(gp_handle h, const SsmsSampleIn& smp, const SsmpBufs& pb, const SsmsWin* d_wins,
+                             const SsmsMeta* d_meta, int d, int P, int N, int n, int steps, int count, const int32_t* out_step_host);
 static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
                           const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
                           const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, double* mean,
-                          double* var, double* loglik, void* ws, size_t ws_bytes, const SsmsScoreOut* score) {
-  if (!params || !X || !Y || !order_host || !steps_host || !loglik || !ws || N < 1 || n < 0 || count < 1 || P < 1)
+                          double* var, double* loglik, void* ws, size_t ws_bytes, const SsmsScoreOut* score,
+                          const SsmsSampleIn* smp = nullptr) {
+  if (!params || !X || !Y || !order_host || !steps_host || (!loglik && !smp) || !ws || N < 1 || n < 0 || count < 1 || P < 1)
     return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: bad argument (N >= 1, n >= 0, no null pointers)");
-  if (n > 0 && (!Xnew || !out_step_host || !mean || !var))
+  if (n > 0 && (!Xnew || !out_step_host || ((!mean || !var) && !smp)))
     return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: Xnew, out_step, mean and var may be null only with n = 0");
+  if (smp && (n < 1 || smp->S < 1 || !smp->eps_x || !smp->eps_y || !smp->out))
+    return gp_fail(h, GP_ERR_BAD_ARG, "state-space sampler: bad argument (n >= 1, S >= 1, no null pointers)");
   int d = 0;
   for (int i = 0; i < P; i++) {
     if (!ssms_kernel_ok(ktype[i]))
@@ -607,6 +908,10 @@ static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const in
     if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_score_workspace_bytes(d, steps, P, count))
       return gp_fail(h, GP_ERR_BAD_ARG, "state-space score: workspace too small for steps * d^2 doubles of history per window "
                                         "(gp_ssm_score_workspace_bytes) or not 256-byte aligned");
+  } else if (smp) {
+    if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_sample_workspace_bytes(d, steps, P, smp->S, count))
+      return gp_fail(h, GP_ERR_BAD_ARG, "state-space sampler: workspace too small for S * steps * d doubles per window "
+                                        "(gp_ssm_sample_workspace_bytes) or not 256-byte aligned");
   } else if ((((uintptr_t)ws) & 255) || ws_bytes < ssm_smooth_workspace_bytes(d, steps, P, count))
     return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small for steps * d^2 doubles of history per window "
                                       "(gp_ssm_smooth_workspace_bytes) or not 256-byte aligned");
@@ -637,7 +942,9 @@ static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const in
     }
   }
   GpArena ar(ws, ws_bytes);
-  const SsmsBufs b = ssms_carve(ar, d, steps, P, count);
+  SsmpBufs pb{};
+  if (smp) pb = ssmp_carve(ar, d, steps, P, smp->S, count);
+  const SsmsBufs b = smp ? pb.b : ssms_carve(ar, d, steps, P, count);
   SsmsScoreBufs sb{};
   if (score) sb = ssms_score_carve(ar, d, steps, count);
   if (!ar.ok) return gp_fail(h, GP_ERR_BAD_ARG, "state-space smoother: workspace too small");
@@ -673,11 +980,13 @@ static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const in
     sw.xnew = n > 0 ? Xnew + (size_t)w * n : nullptr;
     sw.order = b.order + s0; sw.want = b.want + s0; sw.ostep = b.ostep + s0;
     sw.t = b.t + s0; sw.ys = b.ys + s0; sw.feat = b.feat + s0 * frows; sw.hrow = b.hrow + s0 * d;
-    sw.phi = b.phi + s0 * P; sw.q = b.q + s0 * P; sw.am = b.am + s0 * d; sw.g = b.g + s0 * d; sw.ef = b.ef + s0 * 2;
-    sw.Pm = b.Pm + s0 * d * d; sw.smean = b.smean + s0 * P; sw.svar = b.svar + s0 * P;
-    sw.mean = n > 0 ? mean + (size_t)w * P * n : nullptr; sw.var = n > 0 ? var + (size_t)w * P * n : nullptr;
-    sw.loglik = loglik + w;
-    sw.steps = steps_host[w]; sw.hist = n > 0 || score;
+    sw.phi = b.phi + s0 * P; sw.q = b.q + s0 * P; sw.g = b.g + s0 * d; sw.ef = b.ef + s0 * 2;
+    if (!smp) {                                    // (the sampler's carve has no history and no per-step posterior)
+      sw.am = b.am + s0 * d; sw.Pm = b.Pm + s0 * d * d; sw.smean = b.smean + s0 * P; sw.svar = b.svar + s0 * P;
+      sw.mean = n > 0 ? mean + (size_t)w * P * n : nullptr; sw.var = n > 0 ? var + (size_t)w * P * n : nullptr;
+      sw.loglik = loglik + w;
+    }
+    sw.steps = steps_host[w]; sw.hist = !smp && (n > 0 || score);
     memcpy(order_dev.data() + s0, order_host + (size_t)w * (N + n), (size_t)sw.steps * sizeof(int));
     for (int p = 0; p < P; p++)
       feats[(size_t)p * count + w] = FeatItem{DevKern{ktype[p], km[p], sw.params + off_theta[p]}, sw.t,
@@ -727,6 +1036,7 @@ static gp_status ssms_run(gp_handle h, const int* ktype, const int* km, const in
   if (narrow) hipLaunchKernelGGL(ssms_forward_kernel<64>, dim3(count), dim3(64), 0, h->stream, d_wins, d_meta);
   else hipLaunchKernelGGL(ssms_forward_kernel<128>, dim3(count), dim3(128), 0, h->stream, d_wins, d_meta);
   GP_HIP_CHECK(h, hipGetLastError());
+  if (smp) return ssmp_launch(h, *smp, pb, d_wins, d_meta, d, P, N, n, steps, count, out_step_host);
   hipLaunchKernelGGL(ssms_loglik_kernel, dim3(count), dim3(256), 0, h->stream, d_wins, N);
   GP_HIP_CHECK(h, hipGetLastError());
   if (n > 0) {
@@ -780,6 +1090,71 @@ gp_status ssm_score_run(gp_handle h, const int* ktype, const int* km, const int6
                   nullptr, nullptr, loglik, ws, ws_bytes, &out);
 }
 
+// The sampler's launches behind the gain walk (ssms_run with `smp`: every check has passed, the prologue and the forward walk are
+// enqueued).
+static gp_status ssmp_launch(gp_handle h, const SsmsSampleIn& smp, const SsmpBufs& pb, const SsmsWin* d_wins,
+                             const SsmsMeta* d_meta, int d, int P, int N, int n, int steps, int count, const int32_t* out_step_host) {
+  const size_t S = (size_t)smp.S;
+  std::vector<SsmpWin> pw((size_t)count);
+  for (int w = 0; w < count; w++) {
+    SsmpWin& x = pw[w];
+    const size_t s0 = (size_t)w * steps;
+    x.eps_x = smp.eps_x + (size_t)w * S * steps * d; x.eps_y = smp.eps_y + (size_t)w * S * N;
+    x.out = smp.out + (size_t)w * P * S * n;
+    x.sq = pb.sq + s0 * P; x.fi = pb.fi + s0; x.sg = pb.sg + w;
+    x.yd = pb.yd + s0 * S; x.c = pb.c + s0 * S; x.R = pb.R + s0 * S * d;
+    x.ldx = (size_t)steps * d; x.lds = (size_t)steps;
+  }
+  GP_HIP_CHECK(h, hipMemcpyAsync(pb.desc, pw.data(), pw.size() * sizeof(SsmpWin), hipMemcpyHostToDevice, h->stream));
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // a host vector
+  const SsmpWin* d_pw = (const SsmpWin*)pb.desc;
+  hipLaunchKernelGGL(ssmp_prep_kernel, dim3((unsigned)(((size_t)steps * P + 255) / 256), count), dim3(256), 0, h->stream, d_wins, d_pw,
+                     d_meta);
+  GP_HIP_CHECK(h, hipGetLastError());
+  hipLaunchKernelGGL(ssmp_obs_kernel, dim3((steps + 255) / 256, smp.S, count), dim3(256), 0, h->stream, d_wins, d_pw, N);
+  GP_HIP_CHECK(h, hipGetLastError());
+  const dim3 grid(smp.S, count), wave(64);
+  if (d <= 64) {
+    hipLaunchKernelGGL(ssmp_walk1_kernel<1>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+    hipLaunchKernelGGL(ssmp_walk2_kernel<1>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+    hipLaunchKernelGGL(ssmp_walk3_kernel<1>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+  } else {
+    hipLaunchKernelGGL(ssmp_walk1_kernel<2>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+    hipLaunchKernelGGL(ssmp_walk2_kernel<2>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+    hipLaunchKernelGGL(ssmp_walk3_kernel<2>, grid, wave, 0, h->stream, d_wins, d_pw, d_meta);
+  }
+  GP_HIP_CHECK(h, hipGetLastError());
+  // out_step through the staging area of `steps` entries per window, as the smoother's gather
+  std::vector<int> stage((size_t)count * steps);
+  for (int i0 = 0; i0 < n; i0 += steps) {
+    const int cnt = std::min(steps, n - i0);
+    for (int w = 0; w < count; w++)
+      memcpy(stage.data() + (size_t)w * steps, out_step_host + (size_t)w * n + i0, (size_t)cnt * sizeof(int));
+    GP_HIP_CHECK(h, hipMemcpyAsync(pb.b.ostep, stage.data(), stage.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    hipLaunchKernelGGL(ssmp_gather_kernel, dim3((cnt + SSMP_GF - 1) / SSMP_GF, smp.S, count), dim3(256), 0, h->stream, d_wins, d_pw, d_meta, smp.S,
+                       n, i0, cnt);
+    GP_HIP_CHECK(h, hipGetLastError());
+  }
+  GP_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+  return GP_OK;
+}
+
+// S joint draws of every source of windows w < count at their new frames: eps_x + w * S * steps * d laid out [S][steps][d] with
+// `steps` the call's longest timeline, eps_y + w * S * N, out + w * P * S * n laid out [P][S][n]; the rest as ssm_smooth_run
+gp_status ssm_sample_run(gp_handle h, const int* ktype, const int* km, const int64_t* off_theta, int P, int64_t param_stride,
+                         const double* params, const double* X, const double* Y, int N, const double* Xnew, int n, int count,
+                         const int32_t* order_host, const int32_t* out_step_host, const int32_t* steps_host, int S,
+                         const double* eps_x, const double* eps_y, double* out, void* ws, size_t ws_bytes) {
+  if (S > 65535) return gp_fail(h, GP_ERR_UNSUPPORTED, "state-space sampler: at most 65535 draws per call");
+  const SsmsSampleIn smp{S, eps_x, eps_y, out};
+  return ssms_run(h, ktype, km, off_theta, P, param_stride, params, X, Y, N, Xnew, n, count, order_host, out_step_host, steps_host,
+                  nullptr, nullptr, nullptr, ws, ws_bytes, nullptr, &smp);
+}
+
+extern "C" size_t gp_ssm_sample_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t S, int32_t count) {
+  return ssm_sample_workspace_bytes(d, steps, P, S, count);
+}
 extern "C" size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count) {
   return ssm_smooth_workspace_bytes(d, steps, P, count);
 }

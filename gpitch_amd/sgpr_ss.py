@@ -118,6 +118,15 @@ def ssm_timeline(X, Xnew):
     return order, ustep[inv].astype(np.int32), int(steps)
 
 
+def ssm_sample_eps_shapes(kern_list, steps, N, num_samples=1):
+    """shapes of the two standard-normal arrays of sample_s_ssm for one window and output column: eps_x (S, steps, d),
+    STEP-major along the merged timeline of ssm_timeline(X, Xnew) (entry [s, j, i] drives coordinate i of the state at step
+    j; d and the coordinates' order as ssm_state_dim / sample_components), and eps_y (S, N) in the caller's frame order."""
+    d, _ = ssm_state_dim(kern_list, "sample_s_ssm")
+    S = int(num_samples)
+    return (S, int(steps), d), (S, int(N))
+
+
 def _sample_chunk(num_samples, doubles_per_sample):
     """draws per library call so that their standard normals stay below SAMPLE_EPS_BYTES"""
     return int(max(1, min(int(num_samples), SAMPLE_EPS_BYTES // (8 * max(1, int(doubles_per_sample))))))
@@ -618,6 +627,63 @@ class SGPRSS(Parameterized):
                                                            ez.data_ptr(), eu.data_ptr(), out.data_ptr(), ws.data_ptr(),
                                                            ws.numel()))
                 res[:, s0:s0 + sc, :, d] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
+        return [res[i] for i in range(P)]
+
+    def sample_s_ssm(self, Xnew, num_samples=1, seed=None, eps=None):
+        """Joint draws of every source at Xnew from the EXACT posterior of predict_s_ssm: a list of P arrays
+        (num_samples, n, D).  A draw is joint across the n frames and across the P sources (gp_sgpr_sample_source_ssm: Durbin
+        and Koopman's simulation smoother in its disturbance form, three O((N + n) d) walks per draw behind one gain walk; no
+        inducing points, no d x d array per step, any N); its mean over many draws is predict_s_ssm's mean and its spread the
+        joint posterior covariance.  Scope and conventions as predict_s_ssm: the mean function is NOT added, Xnew in any
+        order, repeats repeat their value.  NotImplementedError, before any device work, for a kernel without the
+        Ornstein-Uhlenbeck form and for d > 128.
+
+        eps=None: the standard normals are torch.randn on the handle's device from a generator seeded by `seed`, drawn
+        SAMPLE_EPS_BYTES at a time (the same seed and chunk size give the same draws); output columns get independent ones.
+        eps=(eps_x, eps_y) of shapes ssm_sample_eps_shapes(kern, steps, N, num_samples), steps = ssm_timeline(X, Xnew)[2],
+        each with a leading D axis when D > 1, supplies them: the map is affine in eps, and eps = 0 returns the exact
+        posterior mean from a workspace without the smoother's steps * d^2 history.  eps_x is STEP-major and indexed along
+        the MERGED timeline, unlike sample_s_sparse's component-major blocks: the same seed (or eps) with another Xnew is
+        another draw, not the same path seen at other frames."""
+        if self._shard:
+            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        kl = self.kern.kern_list
+        d, P = ssm_state_dim(kl, "sample_s_ssm")      # raises for an unsupported kernel or d, before any device work
+        Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        n, N, S, D = Xnew.size, self.X.shape[0], int(num_samples), self.num_latent
+        if n < 1 or S < 1:
+            raise ValueError("sample_s_ssm: needs at least one new point and one sample")
+        order, out_step, steps = ssm_timeline(self.X._array, Xnew)
+        order, out_step = np.ascontiguousarray(order), np.ascontiguousarray(out_step)
+        shapes = ssm_sample_eps_shapes(kl, steps, N, S)
+        if eps is not None:
+            eps = [np.asarray(e, dtype=np.float64) for e in eps]
+            want = [((D,) if D > 1 else ()) + sh for sh in shapes]
+            if len(eps) != 2 or any(e.shape != w for e, w in zip(eps, want)):
+                raise ValueError("sample_s_ssm: eps must be (eps_x, eps_y) of shapes %s" % (want,))
+            eps = [np.ascontiguousarray(e.reshape((D,) + sh)) for e, sh in zip(eps, shapes)]
+        self._compile()
+        self._pack()
+        h = self._handle
+        xs = h.to_device(Xnew)
+        chunk = S if eps is not None else _sample_chunk(S, steps * d + N)
+        ws = h.workspace(h.lib.gp_ssm_sample_workspace_bytes(d, steps, P, chunk, 1))
+        out = h.empty(P, chunk, n)
+        gen = None if eps is not None else _sample_generator(h, seed)
+        res = np.empty((P, S, n, D))
+        for c in self._columns():
+            for s0 in range(0, S, chunk):
+                sc = min(chunk, S - s0)
+                if eps is not None:
+                    ex, ey = (h.to_device(e[c]) for e in eps)
+                else:
+                    ex, ey = (h.torch.randn(sc, *sh[1:], dtype=h.torch.float64, device=h.device, generator=gen)
+                              for sh in shapes)
+                h.check(h.lib.gp_sgpr_sample_source_ssm(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                        self._Yd.data_ptr(), N, xs.data_ptr(), n, order.ctypes.data,
+                                                        out_step.ctypes.data, steps, sc, ex.data_ptr(), ey.data_ptr(),
+                                                        out.data_ptr(), ws.data_ptr(), ws.numel()))
+                res[:, s0:s0 + sc, :, c] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
         return [res[i] for i in range(P)]
 
     # ---- training: GPflow Model.optimize -> scipy L-BFGS-B on the free state (transcription.py:283) ----

@@ -387,6 +387,71 @@ class SgprWindowBatch(object):
             res[:, :, s0:s0 + sc] = out.cpu().numpy()
         return res
 
+    def sample_s_ssm(self, params_host, xnews=None, num_samples=1, seed=None, eps=None, chunk=None):
+        """SGPRSS.sample_s_ssm (joint draws of every source from the exact posterior by the simulation smoother,
+        gp_sgprb_sample_source_ssm) of every loaded window: (count, P, num_samples, n).  One wavefront per (window, draw);
+        `chunk` windows share a launch sequence (default: as many as keep a call's normals and workspace below
+        sgpr_ss.MAX_SSM_BYTES).  Chunking changes no bit of any draw, seeded ones included: the normals are generated window
+        by window.  eps=None: standard normals from a device generator seeded by `seed`, at most sgpr_ss.SAMPLE_EPS_BYTES of
+        them per window at a time; otherwise eps=(eps_x (count, S, smax, d), eps_y (count, S, N)) with smax the longest
+        timeline among the windows (sgpr_ss.ssm_timeline): a window reads its own first steps of eps_x.  Z, the windows'
+        inducing counts and the plan's precision play no part; n may exceed N."""
+        from . import sgpr_ss
+        h = self.h
+        t = h.torch
+        cnt, N, S = self.count, self.N, int(num_samples)
+        codes = list(zip(self._keep[0], self._keep[1]))
+        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.sample_s_ssm")    # raises before any device work
+        if S < 1:
+            raise ValueError("sample_s_ssm: needs at least one sample")
+        xn, n = self._load_xnew(xnews, cnt)
+        if n < 1:
+            raise ValueError("sample_s_ssm: needs at least one new point")
+        xh = self.X[:cnt].cpu().numpy()
+        nh = xh if xnews is None else xn.cpu().numpy()
+        order = np.zeros((cnt, N + n), dtype=np.int32)
+        ostep = np.zeros((cnt, n), dtype=np.int32)
+        steps = np.zeros(cnt, dtype=np.int32)
+        for w in range(cnt):
+            o, s, k = sgpr_ss.ssm_timeline(xh[w], nh[w])
+            order[w, :k], ostep[w], steps[w] = o, s, k
+        smax = int(steps.max())
+        shapes = [(cnt,) + sh for sh in sgpr_ss.ssm_sample_eps_shapes(codes, smax, N, S)]
+        if eps is not None:
+            eps = [np.asarray(e, dtype=np.float64) for e in eps]
+            if len(eps) != 2 or any(e.shape != sh for e, sh in zip(eps, shapes)):
+                raise ValueError("sample_s_ssm: eps must be (eps_x, eps_y) of shapes %s" % (shapes,))
+        self._p_host[:cnt].copy_(t.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        sch = S if eps is not None else sgpr_ss._sample_chunk(S, smax * d + N)
+        if chunk is None:
+            per = max(1, int(h.lib.gp_ssm_sample_workspace_bytes(d, smax, P, sch, 1)) + 8 * sch * (smax * d + N))
+            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // per)
+        chunk = int(max(1, min(int(chunk), cnt)))
+        ws = h.workspace(h.lib.gp_ssm_sample_workspace_bytes(d, smax, P, sch, chunk))
+        gen = None if eps is not None else sgpr_ss._sample_generator(h, seed)
+        res = np.empty((cnt, P, S, n))
+        for s0 in range(0, S, sch):
+            sc = min(sch, S - s0)
+            for b0 in range(0, cnt, chunk):
+                c = min(chunk, cnt - b0)
+                sm = int(steps[b0:b0 + c].max())          # the library lays eps_x out on the call's own longest timeline
+                if eps is not None:
+                    ex, ey = h.to_device(np.ascontiguousarray(eps[0][b0:b0 + c, :, :sm])), h.to_device(eps[1][b0:b0 + c])
+                else:
+                    ex, ey = h.empty(c, sc, sm, d), h.empty(c, sc, N)
+                    for w in range(c):                    # window by window on the batch's longest timeline: the same stream
+                        ex[w].copy_(t.randn(sc, smax, d, dtype=t.float64, device=h.device, generator=gen)[:, :sm])
+                        ey[w].copy_(t.randn(sc, N, dtype=t.float64, device=h.device, generator=gen))
+                out = h.empty(c, P, sc, n)
+                h.check(h.lib.gp_sgprb_sample_source_ssm(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
+                                                         self.Y[b0:].data_ptr(), xn[b0:].data_ptr(), n, c,
+                                                         order[b0:].ctypes.data, ostep[b0:].ctypes.data,
+                                                         steps[b0:].ctypes.data, sc, ex.data_ptr(), ey.data_ptr(),
+                                                         out.data_ptr(), ws.data_ptr(), ws.numel()))
+                res[b0:b0 + c, :, s0:s0 + sc] = out.cpu().numpy()
+        return res
+
     def close(self):
         if self.plan is not None:
             self.h.sync()

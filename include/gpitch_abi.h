@@ -780,6 +780,29 @@ gp_status gp_sgpr_predict_source_ssm(gp_sgpr_plan p, const double* params, const
  * timeline of the call), measured.  0 for arguments outside 1 <= P <= d <= 128, steps >= 1, count >= 1. */
 size_t gp_ssm_smooth_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t count);
 
+/* S joint draws of every source at the n new frames from the exact posterior of gp_sgpr_predict_source_ssm: joint across frames
+ * and across sources, in O(S (N + n) d) behind one gain walk of O((N + n) d^2), by Durbin and Koopman's simulation smoother in
+ * its disturbance form (ssm_smooth.hip).  No d x d array is kept per step: the workspace holds 3 steps d doubles per
+ * window and steps (d + 2) per draw, where the smoother's holds steps d^2.  Scope, timeline arguments, host checks and error codes
+ * are gp_sgpr_predict_source_ssm's; n >= 1 and 1 <= S <= 65535.
+ *   eps_x   [S][steps][d] standard normals (device), STEP-major along the merged timeline: entry [s][j][i] drives coordinate i of
+ *           the state at step j (the sources' blocks in kern_list order, (a_0, b_0, a_1, b_1, ...) inside a mixture).  The same
+ *           normals with another Xnew are another draw.
+ *   eps_y   [S][N] standard normals (device), in the caller's frame order: the observation noise of the simulated data
+ *   out     [P][S][n] (device).  The map is affine in (eps_x, eps_y): zeros give the smoothed mean of gp_sgpr_predict_source_ssm
+ *           (to rounding), and the linear part T has T T^T = the joint posterior covariance of all sources at all new frames.
+ *           The mean function is not added; a repeated new frame repeats its value.
+ *   workspace  gp_ssm_sample_workspace_bytes(d, steps, P, S, 1) bytes, 256-byte aligned; a short one is GP_ERR_BAD_ARG
+ * Every check precedes the first launch.  float64 whatever the plan's precision.  Synchronises.  No atomics, every sum in a fixed
+ * order, one wavefront per (window, draw): a draw's bits depend on nothing but its own normals, whatever S. */
+gp_status gp_sgpr_sample_source_ssm(gp_sgpr_plan p, const double* params, const double* X, const double* Y, int32_t N,
+                                    const double* Xnew, int32_t n, const int32_t* order_host, const int32_t* out_step_host,
+                                    int32_t steps, int32_t S, const double* eps_x, const double* eps_y, double* out,
+                                    void* workspace, size_t workspace_bytes);
+/* handle-free, runs without a device: the one carve of the sampling call (also the window-batched entry's, with `steps` the
+ * longest timeline of the call), measured.  0 for arguments outside 1 <= P <= d <= 128, steps >= 1, S >= 1, count >= 1. */
+size_t gp_ssm_sample_workspace_bytes(int32_t d, int32_t steps, int32_t P, int32_t S, int32_t count);
+
 /* The exact log marginal likelihood log p(y) of gp_sgpr_predict_source_ssm AND its gradient in the plan's parameter layout, in
  * O(N d^2): the forward walk with its history, then a Bryson-Frazier walk over every step that carries the score (ssm_smooth.hip,
  * DESIGN 3c-5).  Same scope and errors as gp_sgpr_predict_source_ssm; the timeline is the N training frames.
@@ -863,6 +886,15 @@ gp_status gp_sgprb_predict_source_ssm(gp_sgprb_plan p, const double* params, con
                                       const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
                                       const int32_t* out_step_host, const int32_t* steps_host, double* mean, double* var,
                                       double* loglik, void* workspace, size_t workspace_bytes);
+
+/* gp_sgpr_sample_source_ssm of the first `count` windows, one wavefront per (window, draw) in the walks: per-window arguments as
+ * gp_sgprb_predict_source_ssm; eps_x [count][S][max_w steps_host[w]][d] (a window reads its first steps_host[w] steps),
+ * eps_y [count][S][N], out [count][P][S][n].  workspace: gp_ssm_sample_workspace_bytes(d, max_w steps_host[w], P, S, count).
+ * A (window, draw)'s bits are those of the one-window call on the same normals, whatever `count` and S. */
+gp_status gp_sgprb_sample_source_ssm(gp_sgprb_plan p, const double* params, const double* X, const double* Y,
+                                     const double* Xnew, int32_t n, int32_t count, const int32_t* order_host,
+                                     const int32_t* out_step_host, const int32_t* steps_host, int32_t S, const double* eps_x,
+                                     const double* eps_y, double* out, void* workspace, size_t workspace_bytes);
 
 /* gp_sgpr_exact_loglik_grad of the first `count` windows, one workgroup per window in the walks: params [count][num_params],
  * X / Y [count][N], order_host [count][N] (HOST), loglik [count], grad [count][num_params], resid_grad [count][N] or null.

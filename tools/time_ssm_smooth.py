@@ -11,10 +11,14 @@ GPU: a warm-up call of each arm, then `--reps` timed calls with the arms interle
          log-likelihood per window that each fit reaches
   cfg5   one window of N = 65536, 5 sources x 10 partials (d = 100), Xnew = X: predict_s_ssm next to predict_s_sparse (M = 512).
          predict_s cannot run there (one N x N float64 matrix is 34 GB) and is recorded as such.
+  sample joint draws from the exact posterior: sample_s_ssm at S = 1 and 16 (seeded: the normals' generation and
+         the download of the draws are inside the figure) of the one window and of the 256, beside the gain walk alone
+         (exact_log_likelihood), predict_s_ssm and sample_s_sparse (M = 64); then 16 draws of the N = 65536, d = 100 window with
+         the call's workspace beside predict_s_ssm's
 
-Writes one JSON file (default profiles/ssm/ssm_smooth_time.json) and prints it.  GPITCH_AMD_SWITCHES=ssm_wide=1 times the
+Writes one JSON file (default profiles/ssm/ssm_smooth_time.json; profiles/ssm/ssm_sample_time.json for --parts sample) and prints it.  GPITCH_AMD_SWITCHES=ssm_wide=1 times the
 two-wavefront walks at d = 60 (the switch is read once per process; it is recorded in the output).
-python tools/time_ssm_smooth.py [--parts one,batch,fit,cfg5,score] [--reps 5] [--windows 256] [--out FILE]"""
+python tools/time_ssm_smooth.py [--parts one,batch,fit,cfg5,score,sample] [--reps 5] [--windows 256] [--out FILE]"""
 import argparse
 import json
 import os
@@ -78,9 +82,11 @@ def main():
     ap.add_argument("--parts", default="one,batch,fit,cfg5")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--windows", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ssm", "ssm_smooth_time.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     parts = a.parts.split(",")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "ssm", "ssm_sample_time.json" if parts == ["sample"] else "ssm_smooth_time.json")
     import torch
     from gpitch_amd import _lib
     from gpitch_amd.sgpr_ss import SGPRSS
@@ -89,7 +95,7 @@ def main():
     h = _lib.default_handle()
     out = {"device": torch.cuda.get_device_name(0), "switches": os.environ.get("GPITCH_AMD_SWITCHES", ""), "reps": a.reps}
     N, M, P, W = 2001, 64, 3, a.windows
-    wins = [_window(N, M, P, w) for w in range(W if ("batch" in parts or "fit" in parts or "score" in parts) else 1)]
+    wins = [_window(N, M, P, w) for w in range(W if ("batch" in parts or "fit" in parts or "score" in parts or "sample" in parts) else 1)]
 
     def make(handle):
         return SGPRSS(wins[0][0], wins[0][1], np.sum(_kernels(P, 10)), wins[0][2], handle=handle)
@@ -172,6 +178,43 @@ def main():
         res["predict_s"] = "cannot run: one N x N float64 matrix is %.0f GB" % (8e-9 * N5 * N5)
         res["ssm_workspace_GB"] = 1e-9 * int(h.lib.gp_ssm_smooth_workspace_bytes(100, N5, P5, 1))
         out["one_window_N65536_d100"] = res
+        m._destroy()
+    if "sample" in parts:
+        m = make(h)
+        X = wins[0][0]
+        out["sample_one_window_N2001_d60"] = _time(
+            [("sample_s_ssm_S1", lambda: m.sample_s_ssm(X, 1, seed=1)), ("sample_s_ssm_S16", lambda: m.sample_s_ssm(X, 16, seed=1)),
+             ("exact_log_likelihood", lambda: m.exact_log_likelihood()), ("predict_s_ssm", lambda: m.predict_s_ssm(X)),
+             ("sample_s_sparse_S1", lambda: m.sample_s_sparse(X, 1, seed=1)),
+             ("sample_s_sparse_S16", lambda: m.sample_s_sparse(X, 16, seed=1))], a.reps, sync)
+        print("sample, one window: done", file=sys.stderr, flush=True)
+        m._compile()
+        m._pack()
+        pv = np.tile(m._params.cpu().numpy(), (W, 1))
+        dev = SgprWindowBatch(m, W, N, M, handle=h)
+        dev.load([w[0] for w in wins], [w[1] for w in wins], [w[2] for w in wins])
+        res = _time([("sample_s_ssm_S1", lambda: dev.sample_s_ssm(pv, None, 1, seed=1)),
+                     ("sample_s_ssm_S16", lambda: dev.sample_s_ssm(pv, None, 16, seed=1)),
+                     ("exact_loglik", lambda: dev.exact_loglik_grad(pv, with_grad=False)),
+                     ("predict_s_ssm", lambda: dev.predict_s_ssm(pv)),
+                     ("sample_s_sparse_S16", lambda: dev.sample_s_sparse(pv, None, 16, seed=1))], a.reps, sync)
+        for k, v in res.items():
+            v["windows_per_s"] = W / (1e-3 * v["median_ms"])
+        res["sample_workspace_GB_S16"] = 1e-9 * int(h.lib.gp_ssm_sample_workspace_bytes(60, N, P, 16, W))
+        res["smooth_workspace_GB"] = 1e-9 * int(h.lib.gp_ssm_smooth_workspace_bytes(60, N, P, W))
+        out["sample_batch_%d_windows_N2001_d60" % W] = res
+        dev.close()
+        m._destroy()
+        print("sample, batch: done", file=sys.stderr, flush=True)
+        N5, M5, P5 = 65536, 512, 5
+        X, Y, Z = _window(N5, M5, P5, 1)
+        m = SGPRSS(X, Y, np.sum(_kernels(P5, 10)), Z, handle=h)
+        res = _time([("sample_s_ssm_S16", lambda: m.sample_s_ssm(X, 16, seed=1)),
+                     ("exact_log_likelihood", lambda: m.exact_log_likelihood())], max(3, a.reps // 2), sync)
+        res["sample_workspace_GB_S16"] = 1e-9 * int(h.lib.gp_ssm_sample_workspace_bytes(100, N5, P5, 16, 1))
+        res["sample_workspace_GB_S1"] = 1e-9 * int(h.lib.gp_ssm_sample_workspace_bytes(100, N5, P5, 1, 1))
+        res["smooth_workspace_GB"] = 1e-9 * int(h.lib.gp_ssm_smooth_workspace_bytes(100, N5, P5, 1))
+        out["sample_one_window_N65536_d100"] = res
         m._destroy()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
