@@ -381,6 +381,10 @@ gp_status launch_sm_features_items(gp_handle h, const FeatItem* d_items, int cou
 // aligned output, leading dimension gp_strip_ld) — what the lean Mercer form needs to know on the host
 gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem* d_items, int count, int max_n1,
                                     int max_n2, const double* x2_shared, int n2_shared, int engine_strips = 0);
+// the kernel that launch takes (host only, no device work): form 0 generic, 1 staged matrix-core, 2 lean matrix-core; forms 1
+// and 2 split every record's rows into segments of row_seg rows (nseg: the doubling count behind row_seg)
+struct CovItemsForm { int form, nseg, row_seg; };
+CovItemsForm cov_items_form(int type, int m, int count, int max_n1, int max_n2, bool x2_shared, int n2_shared, int engine_strips);
 // predict_sparse.hip: the sparse per-source posterior (gp_sgpr_predict_source_sparse), one fused launch over
 // (frame tile, source, window).  One item per (source, window), kernel-major [P][nwin]: the window's forward state
 // (W = chol(Kuu)^-1 and WB = chol(B)^-1 with leading dimension ldw, c), its kz inducing points z with the kernel's feature

@@ -265,7 +265,9 @@ static int cov_rows_for(int n1, int n2) {
 
 // K = sum_p K_p for up to 8 MercerMatern12sm kernels in ONE pass (SGPRSS: the summed source kernel of sgpr_ss.py:29-71,
 // `kern = sum of per-source kernels`): per entry the arithmetic of cov_build_kernel<1, 2, MPAD, 0> for every kernel, added in
-// kernel order — the value that P accumulate launches leave (float64: bit-identical; float32 output: one rounding instead of P).
+// kernel order — the value that P accumulate launches leave (float64: bit-identical, except that diag_add goes onto the diagonal
+// after the last kernel where the launches add it with the first: P roundings of the total apart; float32 output: one rounding
+// instead of P).
 // The accumulate launches re-read and re-write the whole M x N strip P - 1 times (0.34 ms of a 5.1-ms evaluation at
 // N = 65536, M = 512, P = 5).  Row accumulators of the workgroup's COV_ROWS rows stay in registers while the kernels go by.
 struct CovSumArgs { int P; int pad_; DevKern k[8]; const double* f1[8]; const double* f2[8]; };
@@ -329,7 +331,9 @@ __global__ void __launch_bounds__(COV_THREADS) cov_mercer_sum_kernel(CovSumArgs 
 #pragma unroll
           for (int c = 0; c < CPT; c++) {
             const double r = gp_sqrt_pos(__dadd_rn(r2_expand(av, aa, b[c], bb[c]), 1e-12));
-            res[ii][c] += var * gp_exp_neg(-r, etab) * acc[c];
+            // the entry rounded on its own, then added: `res += entry` contracts to one fma and loses the bit identity
+            // with the accumulate launches (tests/test_gpu_cov.py holds it)
+            res[ii][c] = __dadd_rn(res[ii][c], var * gp_exp_neg(-r, etab) * acc[c]);
           }
         }
       }
@@ -507,9 +511,16 @@ __global__ void __launch_bounds__(1024 / CT, CT == 2 ? 2 : 2) cov_mercer_mfma_ke
   // (s = 1 for the Matern-1/2 envelope, sqrt 5 for Matern-5/2): one exp per ROW of the tile and two multiplies per
   // entry instead of a square root and an exp per entry (~27 of the ~30 float64 vector instructions an entry costs — as
   // much matrix-core-equivalent time as the 40 MFMAs of the tile).  What is dropped is the 1e-12 under the root and the
-  // rounding of the reference's expanded square (GPflow's square_dist): relative 1e-12 / (2 |a - b|) = 5e-13 at the
-  // threshold |a - b| >= 1 (a lengthscale apart), below the 1e-11 the kernel tests hold; inside the band — and for any
-  // tile that straddles it — the entry-by-entry form runs as before.  Column factors are loop-invariant registers.
+  // rounding of the reference's expanded square (GPflow's square_dist).  The first is relative 1e-12 / (2 |a - b|) = 5e-13
+  // at the threshold |a - b| >= 1 (a lengthscale apart).  The second grows with A = max |x / l|: the expanded square
+  // -2ab + a^2 + b^2 carries eps A^2 absolute in r^2, so about eps A^2 / (2 |a - b|) in r, and it is the REFERENCE that
+  // carries it — the product form is the more accurate of the two.  Against the reference at rtol 1e-11 + atol 1e-12 the
+  // product form measures (tests/test_cov_ref_cpu.py, M = 256, N = 4096 frames at 16 kHz, worst error / tolerance):
+  // 0.05 for A <= 26 (l >= 0.01), 0.2 at A = 256 (l = 0.001), and above 1 (1.6 Matern-1/2, 2.1 Matern-5/2; up to 5.5 / 7.7
+  // for other draws of z) at A = 1280 (l = 2e-4), where against a long-double closed form it stays at 0.02 and the
+  // reference is what misses.  So "below the 1e-11 the kernel tests hold" is a statement for A <= 256; beyond it the tests
+  // compare with the closed form.  Inside the band — and for any tile that straddles it — the entry-by-entry form runs
+  // as before, expanded square and all.  Column factors are loop-invariant registers.
   double bmin_w, bmax_w;
   {
     double lo = bsc[0], hi = bsc[0];
@@ -625,6 +636,7 @@ __global__ void __launch_bounds__(1024 / CT, CT == 2 ? 2 : 2) cov_mercer_mfma_ke
 // Whole tiles of the engine's strips only (n2 a multiple of the workgroup's columns, 16-byte alignment, row segments of
 // at most CVL_MAXR): the launcher falls back to cov_mercer_mfma_kernel otherwise.  Entries are bit-identical to it.
 #define CVL_MAXR 512                 // rows per workgroup the LDS tables hold
+#define CVL_NWV 4                    // wavefronts per workgroup (16 * CVM_CT columns each)
 template <int MPAD, int ENV, int CT, int NWV>
 __global__ void __launch_bounds__(64 * NWV, 2) cov_mercer_mfma_lean_kernel(const CovItem* __restrict__ items,
                                                                           const double* __restrict__ x2s, int n2s, int row_seg) {
@@ -841,31 +853,48 @@ gp_status launch_sm_features_items(gp_handle h, const FeatItem* d_items, int cou
   return GP_OK;
 }
 
+// Which kernel launch_kernel_build_items runs for a group, decided on the host from the group's shape alone: form 0 the
+// generic cov_build_kernel, 1 the staged matrix-core form (cov_mercer_mfma_kernel), 2 the lean one
+// (cov_mercer_mfma_lean_kernel); for forms 1 and 2 the rows of every record are split into segments of row_seg rows
+// (a multiple of CVM_ROWS; nseg is the doubling count that led to it, the grid's z is ceil(max_n1 / row_seg)).
+// One function for the launcher and for gp_debug_cov_build (cov_debug.hip), which reports what ran.
+CovItemsForm cov_items_form(int type, int m, int count, int max_n1, int max_n2, bool x2_shared, int n2_shared, int engine_strips) {
+  CovItemsForm f{0, 1, 0};
+  const bool lean_items = engine_strips != 0;
+  const bool big = (int64_t)max_n1 * max_n2 >= (1 << 20);
+  if (!gp_kern_is_mercer(type) || !x2_shared || !big) return f;
+  // Kuf strips (shared frames, nothing accumulated, no diagonal): matrix-core form
+  // rows split only while the grid is smaller than the 512 workgroups the device holds (row segments are multiples of 32)
+  const int colblk = (max_n2 + 255) / 256;
+  int nseg = 1;
+  while (nseg < 8 && (int64_t)colblk * count * nseg < 512 && (max_n1 + nseg * 2 - 1) / (nseg * 2) >= 2 * CVM_ROWS) nseg *= 2;
+  // the lean form takes whole tiles of the engine's strips only, rows in segments its LDS tables hold
+  // (m <= 8 partials: the build is store-bound either way and the staged form's four wavefronts per SIMD are 6 % ahead)
+  // (float32 strips, engine_strips == 2: half the store bytes, so from 5 partials on the lean form wins there too — cfg3
+  // 0.18 -> 0.12 ms per launch, same-box)
+  const int min_mpad = (engine_strips == 2 ? 8 : 12);
+  const bool lean_ok = lean_items && (n2_shared % (16 * CVM_CT * CVL_NWV) == 0) && sm_mpad(m) >= min_mpad;
+  if (lean_ok) while ((max_n1 + nseg - 1) / nseg > CVL_MAXR) nseg *= 2;
+  f.form = lean_ok ? 2 : 1;
+  f.nseg = nseg;
+  f.row_seg = ((max_n1 + nseg - 1) / nseg + CVM_ROWS - 1) / CVM_ROWS * CVM_ROWS;
+  return f;
+}
+
 // type / m describe the whole group (the feature tables of a Mercer group must already be built)
 gp_status launch_kernel_build_items(gp_handle h, int type, int m, const CovItem* d_items, int count, int max_n1,
                                     int max_n2, const double* x2_shared, int n2_shared, int engine_strips) {
-  const bool lean_items = engine_strips != 0;
   if (count <= 0 || max_n1 <= 0 || max_n2 <= 0) return GP_OK;
   const bool big = (int64_t)max_n1 * max_n2 >= (1 << 20);
   GpTimerScope ts(h, !big ? GP_TIMER_SMALL_GEMM : (gp_kern_is_mercer(type) ? GP_TIMER_KUF_BUILD_SM : GP_TIMER_KUF_BUILD));
   if (gp_kern_is_mercer(type)) {
     if (m < 1 || m > 32) return gp_fail(h, GP_ERR_UNSUPPORTED, "num_partials must be in [1, 32]");
-    if (x2_shared && big) {
-      // Kuf strips (shared frames, nothing accumulated, no diagonal): matrix-core form
-      // rows split only while the grid is smaller than the 512 workgroups the device holds (row segments are multiples of 32)
-      const int colblk = (max_n2 + 255) / 256;
-      int nseg = 1;
-      while (nseg < 8 && (int64_t)colblk * count * nseg < 512 && (max_n1 + nseg * 2 - 1) / (nseg * 2) >= 2 * CVM_ROWS) nseg *= 2;
-      constexpr int FREE_NWV = 4;
-      // the lean form takes whole tiles of the engine's strips only, rows in segments its LDS tables hold
-      // (m <= 8 partials: the build is store-bound either way and the staged form's four wavefronts per SIMD are 6 % ahead)
-      // (float32 strips, engine_strips == 2: half the store bytes, so from 5 partials on the lean form wins there too — cfg3
-      // 0.18 -> 0.12 ms per launch, same-box)
-      const int min_mpad = (engine_strips == 2 ? 8 : 12);
-      const bool lean_ok = lean_items && (n2_shared % (16 * CVM_CT * FREE_NWV) == 0) && sm_mpad(m) >= min_mpad;
-      if (lean_ok) while ((max_n1 + nseg - 1) / nseg > CVL_MAXR) nseg *= 2;
-      const int row_seg = ((max_n1 + nseg - 1) / nseg + CVM_ROWS - 1) / CVM_ROWS * CVM_ROWS;
-      dim3 gm(colblk, count, (max_n1 + row_seg - 1) / row_seg);
+    const CovItemsForm cf = cov_items_form(type, m, count, max_n1, max_n2, x2_shared != nullptr, n2_shared, engine_strips);
+    if (cf.form != 0) {
+      constexpr int FREE_NWV = CVL_NWV;
+      const bool lean_ok = cf.form == 2;
+      const int row_seg = cf.row_seg;
+      dim3 gm((max_n2 + 255) / 256, count, (max_n1 + row_seg - 1) / row_seg);
       const dim3 gfree((max_n2 + 16 * CVM_CT * FREE_NWV - 1) / (16 * CVM_CT * FREE_NWV), count, gm.z);
 #define COV_MFMA(MP)                                                                                                   \
       do {                                                                                                             \

@@ -159,6 +159,39 @@ gp_status gp_debug_hyper_contract(gp_handle h, int32_t entry, const gp_debug_hyp
  * lean matrix-core form, the one that applies gscale */
 int64_t gp_debug_hyper_records(int32_t N, int32_t M);
 int32_t gp_debug_hyper_lean_takes(int32_t type, int32_t m, int32_t n1, int32_t n2, int32_t count);
+/* For tests; synchronises nothing.  ONE launch of a covariance-build host entry on the caller's device buffers, no
+ * arithmetic of its own.  `items` is a HOST array of `count` records; entry 1 uploads them into `workspace`, a 16-byte
+ * aligned DEVICE buffer of at least 192 bytes per record, on the handle's stream (entries 0 and 2 need none).
+ *   entry 0  the single-record build (count = 1), the record passed by value; Mercer feature tables are built inside
+ *         1  the grouped build of one kernel family: every record has the same type and the same partial count rounded up
+ *            to 4 (else GP_ERR_BAD_ARG).  The feature tables of Mercer records are built by the grouped feature launch
+ *            (rows, then columns), then ONE grouped build runs with the grid sized by the largest record.  A record with
+ *            n2 < 0 reads the launch's shared x2_shared / n2_shared.  engine_strips is the caller's promise of engine
+ *            strips (1 float64, 2 float32) and is checked here: every record then has n2 < 0, an even leading dimension
+ *            and a 16-byte aligned output, no accumulation and no diagonal, else GP_ERR_BAD_ARG.  The lean matrix-core form,
+ *            which only engine_strips admits, reads whole 128-column blocks of the SHARED frames without a column guard;
+ *            no caller in the library passes a record with frames of its own (n2 >= 0) beside x2_shared into that form,
+ *            and this entry refuses one with GP_ERR_BAD_ARG.  The matrix-core forms write plain strips: a record that
+ *            accumulates or adds a diagonal in a launch that takes one of them is GP_ERR_BAD_ARG too.
+ *         2  the one-pass build of the sum of `count` kernels that share x1, x2, out, ld, diag_add and f32out (record 0's
+ *            are used; accumulate is ignored); when the sum kernel declines: GP_ERR_UNSUPPORTED, *form = -1, nothing is
+ *            written.  The feature tables are built first, one launch_sm_features per kernel.
+ * x2 NULL with n2 >= 0: K(x1).  out is a float32 matrix (ld in floats) when f32out.  feat (Mercer kernels): 16-byte aligned,
+ * 2 mpad (n1 + n2) + 64 doubles, mpad = m rounded up to 4; rows [0, mpad) of each block are the cos features, [mpad, 2 mpad)
+ * the sin features, the x1 block first and the x2 block behind it at 2 mpad n1 doubles rounded up to a multiple of 32.
+ * *form: 0 the generic kernel, 1 the staged matrix-core form, 2 the lean matrix-core form (entry 2: 0 taken, -1 declined);
+ * *row_seg: the row segment of forms 1 and 2 (else 0).  Nothing is launched when a status other than GP_OK comes back from
+ * the checks above. */
+typedef struct {
+  gp_kernel_desc kern;
+  const double* x1; const double* x2;
+  void* out; double* feat;
+  int64_t ld; double diag_add;
+  int32_t n1, n2, accumulate, f32out;
+} gp_debug_cov_item;
+gp_status gp_debug_cov_build(gp_handle h, int32_t entry, const gp_debug_cov_item* items, int32_t count,
+                             const double* x2_shared, int32_t n2_shared, int32_t engine_strips,
+                             void* workspace, size_t workspace_bytes, int32_t* form, int32_t* row_seg);
 /* pivot index reported by the last GP_ERR_NOT_PD (−1 if none) */
 int32_t gp_last_not_pd_index(gp_handle h);
 
