@@ -26,7 +26,7 @@ TIMER_NAMES = ["kuf_build", "cond_A", "cond_LTA", "nt_gemm", "kuf_bar", "chol", 
 # every symbol include/gpitch_abi.h declares
 ABI_SYMBOLS = [
     "gp_create", "gp_destroy", "gp_sync", "gp_last_error", "gp_abi_version", "gp_debug_wave_takes", "gp_debug_gemm",
-    "gp_debug_hyper_contract", "gp_debug_hyper_records", "gp_debug_hyper_lean_takes", "gp_debug_cov_build", "gp_last_not_pd_index",
+    "gp_debug_hyper_contract", "gp_debug_hyper_records", "gp_debug_hyper_lean_takes", "gp_debug_cov_build", "gp_debug_far_tables", "gp_last_not_pd_index",
     "gp_kernel_build", "gp_kernel_build_f32", "gp_kernel_diag", "gp_chol_workspace_bytes", "gp_kuu_cholesky", "gp_cholesky_inplace",
     "gp_conditional_workspace_bytes", "gp_conditional_diag", "gp_conditional_diag_f32", "gp_conditional_diag_f32w", "gp_conditional_full_workspace_bytes", "gp_conditional_full", "gp_gauss_kl_workspace_bytes", "gp_gauss_kl", "gp_gauss_kl_matrix", "gp_mpd_varexp",
     "gp_mpd_predict_moments", "gp_pdgp_predict_moments", "gp_pdgp_predict_moments_reuse",
@@ -193,6 +193,7 @@ def load_library():
         "gp_debug_hyper_records": (i64, [i32, i32]),
         "gp_debug_hyper_lean_takes": (i32, [i32, i32, i32, i32, i32]),
         "gp_debug_cov_build": (i32, [vp, i32, C.POINTER(DebugCovItem), i32, vp, i32, i32, vp, sz, C.POINTER(i32), C.POINTER(i32)]),
+        "gp_debug_far_tables": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz]),
         "gp_last_not_pd_index": (i32, [vp]),
         "gp_kernel_build": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),
         "gp_kernel_build_f32": (i32, [vp, KD, vp, i32, vp, i32, vp, i64, i32]),

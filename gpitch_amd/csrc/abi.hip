@@ -647,7 +647,7 @@ const GpSwitches& gp_switches() {
     struct { const char* name; int* slot; } table[] = {
         {"strip_wave", &w.strip_wave}, {"strip_wave_f32", &w.strip_wave_f32}, {"strip_wave_roles", &w.strip_wave_roles}, {"strip_lean", &w.strip_lean},
         {"hyper_fuse", &w.hyper_fuse}, {"kufbar_split", &w.kufbar_split}, {"cond_a_early", &w.cond_a_early},
-        {"blocked_256", &w.blocked_256}, {"cov_sum", &w.cov_sum}, {"hyper_sum", &w.hyper_sum}, {"chol_cluster", &w.chol_cluster}, {"aux_priority", &w.aux_priority}, {"gemm_tile32", &w.gemm_tile32}, {"nt_cover", &w.nt_cover}, {"kuf_scan", &w.kuf_scan}, {"scan_side", &w.scan_side}, {"qform", &w.qform}, {"qform_far", &w.qform_far}, {"qform_qbar", &w.qform_qbar}, {"act_far", &w.act_far}, {"scan_far", &w.scan_far}, {"h_far", &w.h_far}, {"ssm_wide", &w.ssm_wide}};
+        {"blocked_256", &w.blocked_256}, {"cov_sum", &w.cov_sum}, {"hyper_sum", &w.hyper_sum}, {"chol_cluster", &w.chol_cluster}, {"aux_priority", &w.aux_priority}, {"gemm_tile32", &w.gemm_tile32}, {"nt_cover", &w.nt_cover}, {"kuf_scan", &w.kuf_scan}, {"scan_side", &w.scan_side}, {"qform", &w.qform}, {"qform_far", &w.qform_far}, {"qform_qbar", &w.qform_qbar}, {"act_far", &w.act_far}, {"scan_far", &w.scan_far}, {"h_far", &w.h_far}, {"far_tables", &w.far_tables}, {"ssm_wide", &w.ssm_wide}};
     std::string all(e);
     size_t pos = 0;
     while (pos < all.size()) {

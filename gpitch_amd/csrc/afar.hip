@@ -16,6 +16,8 @@
 //   afar_t_kernel     T-_X upwards and T+_X downwards over the groups, one thread per row j, side and factor: moving the reference
 //                     point by a = c (ref' - ref) >= 0 is m0' = e^{-a} m0, m1' = e^{-a} (m1 + a m0) (kuf_scan_prefix_kernel's
 //                     shift), then the rows that became far enter.  A fixed order, no atomics: two runs agree bit for bit.
+//                     (switches.h far_tables = 1, the default: afar_t_tiled_kernel below — the same chains and bits, 64 rows per
+//                     one-wavefront workgroup, the entering tiles staged in LDS)
 //   afar_prod_kernel  a wavefront per 32 frames and GP on v_mfma_f64_16x16x4_f64: Kuf[near, S] and Psi in its
 //                     registers as the B operand, tiles of W, C and T as the A operand, all M / 16 row tiles walked; stores A and
 //                     leaves the complete column sums colsum(A^2), colsum((C Kuf)^2) and A^T q_mu as ONE partial row each for
@@ -136,6 +138,125 @@ __global__ void __launch_bounds__(256) afar_t_kernel(const AfarItem* __restrict_
       double* t = it.T + ((size_t)S * M + j) * 8 + fac * 4 + side * 2;
       t[0] = m0; t[1] = m1;
     }
+  }
+}
+
+// The same tables, the same chain per (row j, side, factor) and the same operations in the same order — T is byte-identical to
+// afar_t_kernel's — with the operands brought to the thread another way (switch far_tables):
+//   a workgroup is ONE wavefront on AFT_ROWS = 64 rows of one (side, factor, GP): M / 64 x 4 x GPs workgroups instead of 4 x GPs;
+//   what the groups decide is worked out once per workgroup, AFT_CHUNK steps at a time, into LDS: the running maximum of the
+//   entered rows, the shift a and exp(-a) of the reference point, and for every row that enters in the chunk e and e a around
+//   the reference point of the step it enters at (found by bisection over the chunk's counts, as qfar_t_kernel does);
+//   the entering rows' 16 entries of X per row of the workgroup pass through LDS tile by tile: each row's 128 bytes are loaded by
+//   eight adjacent lanes, tile t + 1 is requested into registers ahead of the walk over tile t and written to the other buffer
+//   behind it (one barrier per tile), and a thread reads its own row back (row stride 17 doubles: no bank is hit twice).
+// factor 0 masks i > j in the registers, whatever the buffer or the tile holds: a NaN above W's diagonal reaches no sum.
+typedef double aft_d2 __attribute__((ext_vector_type(2)));
+#define AFT_ROWS 64
+#define AFT_CHUNK 64
+#define AFT_LD 17
+__global__ void __launch_bounds__(AFT_ROWS) afar_t_tiled_kernel(const AfarItem* __restrict__ items, int N) {
+  const AfarItem it = items[blockIdx.z];
+  const int side = blockIdx.y & 1, fac = blockIdx.y >> 1, tid = threadIdx.x, M = it.M, ng = N / AFAR_GROUP;
+  const int j0 = blockIdx.x * AFT_ROWS, j = j0 + tid;
+  const bool act = j < M;
+  const double c = AF_SQRT3 / it.theta[1];
+  const double* __restrict__ X = fac ? it.C : it.W;
+  __shared__ int cnt[AFT_CHUNK];                     // rows that have entered by the end of each step (a running maximum)
+  __shared__ double sref[AFT_CHUNK], sa[AFT_CHUNK], se[AFT_CHUNK];   // the step's reference point; its shift from the step before
+  __shared__ double ew[1024], ea[1024];              // entering order r -> e, e a around the reference point of r's step
+  __shared__ double xs[2][AFT_ROWS * AFT_LD];        // entering tile (r >> 4) & 1: [row][column of the tile, ascending i]
+  // tile t of the entering order holds the columns [i0, i0 + 16): from column 0 upwards, or from column M downwards
+  const int nt = M / 16;
+  auto tile_i0 = [&](int t) { return side ? M - 16 * (t + 1) : 16 * t; };
+  // lane -> (row, 16-byte part) of the eight loads of a tile: eight adjacent lanes take a row's 128 bytes
+  aft_d2 xn[8];
+  auto request = [&](int t) {
+    const int i0 = tile_i0(t);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int row = min(j0 + 8 * k + (tid >> 3), M - 1);
+      xn[k] = *(const aft_d2*)(X + (size_t)row * M + i0 + 2 * (tid & 7));
+    }
+  };
+  auto deposit = [&](int t) {
+    double* b = xs[t & 1];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      double* d = b + (8 * k + (tid >> 3)) * AFT_LD + 2 * (tid & 7);
+      d[0] = xn[k].x; d[1] = xn[k].y;
+    }
+  };
+  request(0);
+  deposit(0);
+  if (nt > 1) request(1);
+  __syncthreads();
+  int have = 0;                                      // the tile in LDS that the walk reads
+  double m0 = 0.0, m1 = 0.0, rcarry = 0.0;
+  int done = 0;                                      // rows entered so far (uniform)
+  for (int c0 = 0; c0 < ng; c0 += AFT_CHUNK) {
+    const int nc = min(AFT_CHUNK, ng - c0);
+    __syncthreads();
+    if (tid < nc) {
+      const int S = side ? ng - 1 - (c0 + tid) : c0 + tid;
+      cnt[tid] = side ? M - it.rng[2 * S + 1] : it.rng[2 * S];
+      sref[tid] = it.ref[2 * S + side];
+    }
+    __syncthreads();
+    int mine = done;
+    double a = 0.0, e = 1.0;
+    if (tid < nc) {
+      for (int q = 0; q <= tid; q++) mine = max(mine, cnt[q]);
+      const double refprev = tid > 0 ? sref[tid - 1] : rcarry, ref = sref[tid];
+      a = side ? c * (refprev - ref) : c * (ref - refprev);
+      e = exp(-a);
+    }
+    __syncthreads();
+    if (tid < nc) { cnt[tid] = mine; sa[tid] = a; se[tid] = e; }
+    __syncthreads();
+    const int cend = min(cnt[nc - 1], M);
+    for (int r = done + tid; r < cend; r += AFT_ROWS) {   // the rows that enter in this chunk: at the first step whose count passes r
+      int lo = 0, hi = nc - 1;
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (cnt[mid] > r) hi = mid; else lo = mid + 1; }
+      const int i = side ? M - 1 - r : r;
+      const double ref = sref[lo];
+      const double ai = side ? c * (it.z[i] - ref) : c * (ref - it.z[i]);
+      const double ei = exp(-ai);
+      ew[r] = ei; ea[r] = ei * ai;
+    }
+    __syncthreads();
+    for (int q = 0; q < nc; q++) {
+      if (c0 + q > 0) {
+        const double aq = sa[q], eq = se[q];
+        m1 = eq * fma(aq, m0, m1);
+        m0 = eq * m0;
+      }
+      const int k1 = min(cnt[q], M);
+      while (done < k1) {                            // (uniform) the part of one tile that enters at this step
+        const int t = done >> 4, r1 = min(k1, 16 * (t + 1));
+        if (t != have) {                             // the walk reaches the next tile: its entries were requested a tile ago
+          deposit(t);
+          if (t + 1 < nt) request(t + 1);
+          __syncthreads();
+          have = t;
+        }
+        const double* xr = xs[t & 1] + tid * AFT_LD;
+        for (int r = done; r < r1; r++) {
+          const int q16 = r & 15, i = side ? M - 1 - r : r;
+          const double xl = xr[side ? 15 - q16 : q16];
+          const double xv = (fac == 0 && i > j) ? 0.0 : xl;
+          m0 = fma(xv, ew[r], m0);
+          m1 = fma(xv, ea[r], m1);
+        }
+        done = r1;
+      }
+      if (act) {
+        const int S = side ? ng - 1 - (c0 + q) : c0 + q;
+        double* t = it.T + ((size_t)S * M + j) * 8 + fac * 4 + side * 2;
+        t[0] = m0; t[1] = m1;
+      }
+    }
+    rcarry = sref[nc - 1];
   }
 }
 
@@ -314,11 +435,17 @@ __global__ void __launch_bounds__(256, 3) afar_prod_kernel(const AfarItem* __res
   }
 }
 
+// the tables' one launch (form 0: afar_t_kernel, 1: afar_t_tiled_kernel); launch_afar and gp_debug_far_tables (far_debug.hip)
+void launch_afar_t(gp_handle h, const AfarItem* d_items, int count, int M, int n, bool tiled) {
+  if (tiled) hipLaunchKernelGGL(afar_t_tiled_kernel, dim3((M + AFT_ROWS - 1) / AFT_ROWS, 4, count), dim3(AFT_ROWS), 0, h->stream, d_items, n);
+  else hipLaunchKernelGGL(afar_t_kernel, dim3((M + 255) / 256, 4, count), dim3(256), 0, h->stream, d_items, n);
+}
+
 gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, const double* x, int n) {
   if (count <= 0) return GP_OK;
   if (!afar_takes(M, n)) return gp_fail(h, GP_ERR_UNSUPPORTED, "activation far field: whole 256-frame groups, M a multiple of 16 up to 1024, strips of 2^20 entries or more");
   hipLaunchKernelGGL(afar_cols_kernel, dim3(n / AFAR_GROUP, count), dim3(AFAR_GROUP), 0, h->stream, d_items, x, n);
-  hipLaunchKernelGGL(afar_t_kernel, dim3((M + 255) / 256, 4, count), dim3(256), 0, h->stream, d_items, n);
+  launch_afar_t(h, d_items, count, M, n, gp_switches().far_tables != 0);
   GP_HIP_CHECK(h, hipGetLastError());
   {
     GpTimerScope ts(h, GP_TIMER_COND_A);

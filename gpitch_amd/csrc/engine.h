@@ -126,6 +126,8 @@ QfarSizes qfar_sizes(int M, int N, int m);
 bool qfar_takes(int M, int N, int m);
 // count GPs of one family (M, m) over the n ascending frames x: two launches on h->stream
 gp_status launch_qfar_tables(gp_handle h, const QfarItem* d_items, int count, int M, int m, const double* x, int n);
+// the second of them alone (lds 0: qfar_t_kernel, 1: qfar_t_lds_kernel — switches.h far_tables); the caller checks hipGetLastError
+void launch_qfar_t(gp_handle h, const QfarItem* d_items, int count, int M, int nf, int n, bool lds);
 
 // qbar.hip: the Q route's backward products Qbar = Kuf diag(2 gv) Kuf^T and v = Kuf gm from the same far field,
 // one item per latent GP of the run: the stored strip, the likelihood's two rows, qfar.hip's tables of this step, the workspace
@@ -163,6 +165,8 @@ AfarSizes afar_sizes(int M, int N);
 bool afar_takes(int M, int N);
 // count GPs of one family (M) over the n ascending frames x, behind C: the tables' two launches and the product's one on h->stream
 gp_status launch_afar(gp_handle h, const AfarItem* d_items, int count, int M, const double* x, int n);
+// the tables' launch alone (tiled 0: afar_t_kernel, 1: afar_t_tiled_kernel — switches.h far_tables); the caller checks hipGetLastError
+void launch_afar_t(gp_handle h, const AfarItem* d_items, int count, int M, int n, bool tiled);
 
 // hfar.hip: the activations' H = A diag(2 gv) A^T and u = A gm from the stored A once and afar.hip's factors once
 // (DESIGN.md 3.10), one item per latent GP of the run: the strips, W, the likelihood's two rows, afar.hip's tables of this

@@ -78,6 +78,56 @@ __global__ void __launch_bounds__(256) qform_guard_kernel(const GemmProblem* __r
   }
 }
 
+// The same verdict from row-wise loads (switch far_tables): 1024 threads per GP, wavefront w takes the rows
+// r = w, w + 16, ... four at a time, a lane the entries 2 l, 2 l + 1 (+ 128 k) of each up to the diagonal as one 16-byte load
+// of L and one of W (M even and both 16-byte aligned; else 8-byte loads), eight independent loads and four accumulators per
+// matrix in flight, no integer division.  Entries above the diagonal are not requested, and the odd one beside the diagonal
+// is zeroed in the registers.  A fixed order — lane sums, the wavefront's shuffle tree, the sixteen wavefronts in turn — and
+// no atomics: two runs agree bit for bit.  The order is not qform_guard_kernel's, so c may differ from its c in the last
+// bits; c is compared with the bound and reaches no output.
+typedef double qg_d2 __attribute__((ext_vector_type(2)));
+__global__ void __launch_bounds__(1024) qform_guard_rows_kernel(const GemmProblem* __restrict__ probs, int g0, double cmax, int32_t* status) {
+  const GemmProblem p = probs[blockIdx.x];
+  const double* L = p.v0;
+  const double* W = p.B;
+  const int M = p.M, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool wide = (M & 1) == 0 && ((((uintptr_t)L) | ((uintptr_t)W)) & 15) == 0;
+  double sl[4] = {0.0, 0.0, 0.0, 0.0}, sw[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int rb = wave; rb < M; rb += 64) {
+    const int rtop = min(rb + 48, M - 1);                        // the longest of the four rows
+    for (int k = lane; 2 * k <= rtop; k += 64) {
+      qg_d2 l[4], w[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int r = rb + 16 * u;
+        l[u] = w[u] = qg_d2{0.0, 0.0};
+        if (r < M && 2 * k <= r) {
+          const size_t o = (size_t)r * M + 2 * k;
+          if (wide) { l[u] = *(const qg_d2*)(L + o); w[u] = *(const qg_d2*)(W + o); }
+          else { l[u].x = L[o]; w[u].x = W[o]; if (2 * k + 1 <= r) { l[u].y = L[o + 1]; w[u].y = W[o + 1]; } }
+          if (2 * k + 1 > r) { l[u].y = 0.0; w[u].y = 0.0; }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        sl[u] = fma(l[u].x, l[u].x, sl[u]); sl[u] = fma(l[u].y, l[u].y, sl[u]);
+        sw[u] = fma(w[u].x, w[u].x, sw[u]); sw[u] = fma(w[u].y, w[u].y, sw[u]);
+      }
+    }
+  }
+  double tl = (sl[0] + sl[1]) + (sl[2] + sl[3]), tw = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+  __shared__ double red[2][16];
+  for (int o = 32; o > 0; o >>= 1) { tl += __shfl_down(tl, o, 64); tw += __shfl_down(tw, o, 64); }
+  if (lane == 0) { red[0][wave] = tl; red[1][wave] = tw; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double al = red[0][0], aw = red[1][0];
+    for (int q = 1; q < 16; q++) { al += red[0][q]; aw += red[1][q]; }
+    const double c = al * aw;
+    if (!(c <= cmax * (double)M * (double)M)) { status[0] = 4; status[1] = 0; status[2] = g0 + (int)blockIdx.x; }
+  }
+}
+
 // far_wait: the far field's tables (qfar.hip) follow Q and precede the guard — the guard is one workgroup per GP and, beside
 // the other GPs' strip products, the longest link of this chain, while the tables are what the product waits for.  They read
 // the feature tables of the Kuf builds, which the main stream has enqueued: on the helper stream (far_wait) they first wait
@@ -96,7 +146,10 @@ static gp_status qform_chain(gp_pdgp_plan p, const double* x, int n, bool far_wa
     GP_CHECK(launch_qfar_tables(h, (const QfarItem*)(p->d_misc + p->off.qf_items), nq, maxM, p->gps[p->routes.q0].m, x, n));
   }
   if (tables_done && hipEventRecord(tables_done, h->stream) != hipSuccess) return gp_fail(h, GP_ERR_HIP, "event hand-over from the helper stream failed");
-  hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->routes.q0, (double)GP_QFORM_COND_MAX, h->d_status);
+  if (gp_switches().far_tables != 0)
+    hipLaunchKernelGGL(qform_guard_rows_kernel, dim3(nq), dim3(1024), 0, h->stream, slot_probs(p, S_QQ), p->routes.q0, (double)GP_QFORM_COND_MAX, h->d_status);
+  else
+    hipLaunchKernelGGL(qform_guard_kernel, dim3(nq), dim3(256), 0, h->stream, slot_probs(p, S_QQ), p->routes.q0, (double)GP_QFORM_COND_MAX, h->d_status);
   if (hipGetLastError() != hipSuccess) return gp_fail(h, GP_ERR_HIP, "qform guard launch failed");
   return GP_OK;
 }
@@ -441,10 +494,11 @@ void pdgp_upload_bwd(gp_pdgp_plan p, const double* params, int n, double* grad) 
 }
 
 // R = W^T (Lq Lq^T - I) and alpha = W^T q_mu depend on the parameters and on W only: when the helper stream exists they
-// are enqueued on it during the FORWARD pass, right behind the Kuu factorisation it has just run (no wait on the main
-// stream, which is busy with the forward GEMM strips), and the backward pass finds them ready.
-// The whitened KL terms (parameters only) ride along: on the main stream they were one of five tiny kernels between
-// the last forward strip product and the first backward one, with the device idle around them.
+// are enqueued on it during the FORWARD pass.  The helper stream is in order: they follow whatever cond_batch_run's hooks have
+// put there, which with a Q run is the factorisation, E, R, beta, Q, the far field's tables and the GUARD (qform_chain), so
+// they start when the guard ends.  pdgp_forward makes the main stream wait for ev_era ahead of the
+// likelihood, since the whitened KL terms (parameters only) ride along here and the ELBO needs them: the prefetch is on the
+// forward pass's path, and so is everything in front of it on the helper stream.  The backward pass finds R and alpha ready.
 gp_status pdgp_prefetch_backward(gp_pdgp_plan p, int n, bool* kl_done) {
   gp_handle h = p->h;
   p->era_ready = false;

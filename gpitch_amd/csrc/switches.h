@@ -37,6 +37,10 @@
 //                            the near rows of Kuf, Psi: kuf_scan_far_moments_kernel; gp_pdgp_set_scan_far can withhold it per plan) (0: the pass over A)
 //   h_far             1      the run whose A afar.hip formed takes H = A diag(2 gv) A^T and u = A gm from the stored A once and the same factors once (hfar.hip,
 //                            DESIGN.md 3.10; a float64 plan; gp_pdgp_set_h_far can withhold it per plan) (0: the dense split-K product)
+//   far_tables        1      the far fields' table kernels and the Q route's guard in their staged forms: afar_t_tiled_kernel (afar.hip) and
+//                            qfar_t_lds_kernel (qfar.hip) pass each entering 16-row tile through LDS once per workgroup and write byte-identical tables;
+//                            qform_guard_rows_kernel (pdgp_bwd.hip) sums the lower triangles row-wise with 1024 threads per GP — the same verdict, c may differ
+//                            in its last bits (0: afar_t_kernel, qfar_t_kernel, qform_guard_kernel)
 //   ssm_wide          0      ssm_smooth.hip: 1 = every state dimension takes the two-wavefront walks (128 rows, two per SIMD pair); 0: d <= 64 takes one
 //                            wavefront with a row of P per lane (the same sums in the same order: the extra rows and columns are zeros)
 //
@@ -44,7 +48,7 @@
 #pragma once
 struct GpSwitches {
   int strip_wave = 1, strip_wave_f32 = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 5), strip_wave_roles = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 5), strip_lean = 1, hyper_fuse = 1, kufbar_split = -1,
-      cond_a_early = 1, blocked_256 = 1, cov_sum = 1, hyper_sum = 1, chol_cluster = 1, aux_priority = 1, gemm_tile32 = 320, nt_cover = 0, kuf_scan = 1, scan_side = 1, qform = 1, qform_far = 1, qform_qbar = 1, act_far = 1, scan_far = 1, h_far = 1, ssm_wide = 0;
+      cond_a_early = 1, blocked_256 = 1, cov_sum = 1, hyper_sum = 1, chol_cluster = 1, aux_priority = 1, gemm_tile32 = 320, nt_cover = 0, kuf_scan = 1, scan_side = 1, qform = 1, qform_far = 1, qform_qbar = 1, act_far = 1, scan_far = 1, h_far = 1, far_tables = 1, ssm_wide = 0;
 };
 // qform guard: the Q route is admitted while c = ||L||_F^2 ||W||_F^2 = tr(K) tr(K^-1) <= GP_QFORM_COND_MAX * M^2 for K = Kuu + jitter I.
 // cond_2(K) <= c, and c / M^2 is (mean eigenvalue) x (mean inverse eigenvalue), so for one spectrum c grows with M^2 and the bound with

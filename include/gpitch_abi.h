@@ -192,6 +192,20 @@ typedef struct {
 gp_status gp_debug_cov_build(gp_handle h, int32_t entry, const gp_debug_cov_item* items, int32_t count,
                              const double* x2_shared, int32_t n2_shared, int32_t engine_strips,
                              void* workspace, size_t workspace_bytes, int32_t* form, int32_t* row_seg);
+/* For tests; synchronises nothing.  ONE launch of a far field's table kernel on the caller's device buffers, no arithmetic of
+ * its own and no cols kernel: the caller writes the ranges rng [N / 256][2] (int32) and the reference points ref [N / 256][2]
+ * itself, so it can hand over ranges that no model produces.  The record is uploaded into `workspace`, a 16-byte aligned
+ * DEVICE buffer of at least 256 bytes, on the handle's stream.
+ *   which 0  the activations' tables (afar.hip): X = W and X2 = C, both M x M; theta = (variance, lengthscale);
+ *            T [N / 256][M][8]; M a multiple of 16 up to 1024; fz NULL and nf 0
+ *         1  the Q route's tables (qfar.hip): X = Q, M x M, X2 NULL; fz the z feature table [nf][M]; T [N / 256][M][2 nf];
+ *            M a multiple of 64 up to 1024, nf a multiple of 8 up to 64; every count a multiple of 16
+ *   form  0  the one-thread-per-chain kernels (switches.h far_tables = 0), 1 the kernels that stage the tiles in LDS
+ * The caller's promise, as the cols kernels keep it: 0 <= rng[2 S] <= rng[2 S + 1] <= M.  N a multiple of 256; X, X2 and
+ * fz 16-byte aligned.  Anything else is GP_ERR_BAD_ARG and launches nothing. */
+gp_status gp_debug_far_tables(gp_handle h, int32_t which, int32_t form, const double* X, const double* X2, const double* z,
+                              const double* theta, const double* fz, int32_t* rng, double* ref, double* T, int32_t M, int32_t N,
+                              int32_t nf, void* workspace, size_t workspace_bytes);
 /* pivot index reported by the last GP_ERR_NOT_PD (−1 if none) */
 int32_t gp_last_not_pd_index(gp_handle h);
 
