@@ -141,6 +141,14 @@ def _sample_generator(h, seed):
     return g
 
 
+def _check_eps(who, names, eps, shapes):
+    """the caller's standard normals as float64 arrays, one per name and of the wanted shape each (ValueError otherwise)"""
+    eps = [np.asarray(e, dtype=np.float64) for e in eps]
+    if len(eps) != len(names) or any(e.shape != sh for e, sh in zip(eps, shapes)):
+        raise ValueError("%s: eps must be (%s) of shapes %s" % (who, ", ".join(names), list(shapes)))
+    return eps
+
+
 class SGPRSS(Parameterized):
     def __init__(self, X, Y, kern, Z, mean_function=None, reg=False, handle=None, shard=None, float_type=None):
         """shard=(rank, world): ONE window spread over `world` GPUs by frames (one process each).  Every rank is
@@ -376,11 +384,31 @@ class SGPRSS(Parameterized):
     def compute_log_likelihood(self):
         return self.build_likelihood()
 
+    # ---- shared by the predictors and the samplers ----
+    def _refuse_shard(self):
+        if self._shard:
+            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+
+    def _source_columns(self, Xnew, call):
+        """the column loop of the per-source predictors, after _compile / _pack: call(xs, mean, var, column) on every output
+        column, with the device copy of Xnew and the (P, n) device arrays it fills: (means (P, n, D), variances (P, n))"""
+        h, P, n = self._handle, len(self.kern.kern_list), Xnew.size
+        xs, mean, var = h.to_device(Xnew), h.empty(P, n), h.empty(P, n)
+        m = np.empty((P, n, self.num_latent))
+        for d in self._columns():
+            call(xs, mean, var, d)
+            m[:, :, d] = mean.cpu().numpy()
+        return m, var.cpu().numpy()
+
+    def _per_source(self, m, v):
+        """what the per-source predictors return: (list of P means (n, D), list of P variances tiled to (n, D))"""
+        D = self.num_latent
+        return [m[i] for i in range(m.shape[0])], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(v.shape[0])]
+
     def predict_f(self, Xnew, full_cov=False):
         """mean and variance of the mixture at Xnew (GPflow 0.5 SGPR.build_predict; full_cov=True — `predict_f_full_cov`
         in GPflow — returns the n x n x 1 covariance)"""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
         n = Xnew.size
         self._compile(n_pred=n)
@@ -414,20 +442,16 @@ class SGPRSS(Parameterized):
     def build_predict_source(self, Xnew, full_cov=False):
         """p(source* | Y): exact GP on the N training frames, one posterior per kernel in kern_list
         (sgpr_ss.py:73-106; the variance uses the SUM kernel's Kdiag as the reference does)."""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
         n, N, P = Xnew.size, self.X.shape[0], len(self.kern.kern_list)
         self._compile()
         self._pack()
         h = self._handle
-        xs = h.to_device(Xnew)
-        mean, var = h.empty(P, n), h.empty(P, n)
         ws = h.workspace(h.lib.gp_sgpr_predict_source_workspace_bytes(N, n))
         cov = h.empty(P, n, n) if full_cov else None
-        D = self.num_latent
-        m = np.empty((P, n, D))
-        for d in self._columns():                   # one exact posterior per column (the reference's callers have one)
+
+        def call(xs, mean, var, _):                 # one exact posterior per column (the reference's callers have one)
             if full_cov:
                 h.check(h.lib.gp_sgpr_predict_source_full(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
                                                           self._Yd.data_ptr(), N, xs.data_ptr(), n, mean.data_ptr(),
@@ -436,14 +460,14 @@ class SGPRSS(Parameterized):
                 h.check(h.lib.gp_sgpr_predict_source(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
                                                      self._Yd.data_ptr(), N, xs.data_ptr(), n, mean.data_ptr(), var.data_ptr(),
                                                      ws.data_ptr(), ws.numel()))
-            m[:, :, d] = mean.cpu().numpy()
-        v = var.cpu().numpy()
+
+        m, v = self._source_columns(Xnew, call)
         if self.mean_function is not None:          # sgpr_ss.py:95 adds it to EVERY source's mean
             m = m + np.asarray(self.mean_function(Xnew.reshape(-1, 1)), dtype=np.float64).reshape(1, n, -1)
         if full_cov:                                # sgpr_ss.py:95-99: tiled to n x n x D
             c = cov.cpu().numpy()
-            return [m[i] for i in range(P)], [np.tile(c[i].reshape(n, n, 1), (1, 1, D)) for i in range(P)]
-        return [m[i] for i in range(P)], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(P)]   # :101-102
+            return [m[i] for i in range(P)], [np.tile(c[i].reshape(n, n, 1), (1, 1, self.num_latent)) for i in range(P)]
+        return self._per_source(m, v)               # :101-102
 
     def predict_s(self, Xnew):
         """sgpr_ss.py:108-114"""
@@ -457,53 +481,44 @@ class SGPRSS(Parameterized):
         predict_s factorises the N x N exact GP.  It approximates predict_s; the variance starts from the source's own
         Kdiag, not the sum kernel's (sgpr_ss.py:101).  The mean function is NOT added: the sources are zero-mean GPs, and
         sum_p smean_p + mean_function(Xnew) is predict_f's mean.  Xnew may be longer than the training window."""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
-        n, P = Xnew.size, len(self.kern.kern_list)
         self._compile()
         self._pack()
         h = self._handle
-        xs = h.to_device(Xnew)
-        mean, var = h.empty(P, n), h.empty(P, n)
-        D = self.num_latent
-        m = np.empty((P, n, D))
-        for d in self._columns():                   # the mean is linear in the column, the variance does not see it
+
+        def call(xs, mean, var, _):                 # the mean is linear in the column, the variance does not see it
             h.check(h.lib.gp_sgpr_predict_source_sparse(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
                                                         self._Yd.data_ptr(), self.X.shape[0], self._Zd.data_ptr(),
-                                                        xs.data_ptr(), n, mean.data_ptr(), var.data_ptr()))
-            m[:, :, d] = mean.cpu().numpy()
-        v = var.cpu().numpy()
-        return [m[i] for i in range(P)], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(P)]
+                                                        xs.data_ptr(), Xnew.size, mean.data_ptr(), var.data_ptr()))
+
+        return self._per_source(*self._source_columns(Xnew, call))
 
     def _ssm_call(self, Xnew, who):
         """the smoother on every output column: (means (P, n, D), variances (P, n), log-likelihoods (D,))"""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         kl = self.kern.kern_list
         d, P = ssm_state_dim(kl, who)                 # raises for an unsupported kernel or d, before any device work
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
-        n, N, D = Xnew.size, self.X.shape[0], self.num_latent
+        n, N = Xnew.size, self.X.shape[0]
         order, out_step, steps = ssm_timeline(self.X._array, Xnew)
         order, out_step = np.ascontiguousarray(order), np.ascontiguousarray(out_step)
         self._compile()
         self._pack()
         h = self._handle
-        xs = h.to_device(Xnew) if n else None
-        mean, var = (h.empty(P, n), h.empty(P, n)) if n else (None, None)
         ll = h.empty(1)
         ws = h.workspace(h.lib.gp_ssm_smooth_workspace_bytes(d, steps, P, 1))
-        m, lls = np.empty((P, n, D)), np.empty(D)
-        for c in self._columns():
+        lls = np.empty(self.num_latent)
+
+        def call(xs, mean, var, c):                   # (no new point: the forward walk alone, nothing but ll is written)
             h.check(h.lib.gp_sgpr_predict_source_ssm(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
                                                      self._Yd.data_ptr(), N, xs.data_ptr() if n else None, n,
                                                      order.ctypes.data, out_step.ctypes.data if n else None, steps,
                                                      mean.data_ptr() if n else None, var.data_ptr() if n else None,
                                                      ll.data_ptr(), ws.data_ptr(), ws.numel()))
-            if n:
-                m[:, :, c] = mean.cpu().numpy()
             lls[c] = float(ll.cpu().numpy()[0])
-        return m, (var.cpu().numpy() if n else np.empty((P, 0))), lls
+
+        return self._source_columns(Xnew, call) + (lls,)
 
     def predict_s_ssm(self, Xnew):
         """The exact posterior of every source at Xnew: (list of P means (n, D), list of P variances (n, D)).
@@ -520,8 +535,7 @@ class SGPRSS(Parameterized):
         between them or outside the window, in any order, with repeats.  NotImplementedError, before any device work, for a
         kernel without the Ornstein-Uhlenbeck form (naming it and its index in the sum) and for d > 128 (naming d)."""
         m, v, _ = self._ssm_call(Xnew, "predict_s_ssm")
-        D = self.num_latent
-        return [m[i] for i in range(m.shape[0])], [np.tile(v[i].reshape(-1, 1), (1, D)) for i in range(v.shape[0])]
+        return self._per_source(m, v)
 
     def exact_log_likelihood(self):
         """log p(Y | parameters) of the exact GP (the quantity the collapsed bound of build_likelihood lies below, at any
@@ -577,6 +591,36 @@ class SGPRSS(Parameterized):
         object.__setattr__(self, "_exact_st", None)
         return value, np.concatenate([g, gm])
 
+    def _draw(self, who, names, shapes, eps, Xnew, S, seed, doubles, ws_bytes, call):
+        """The draw loop of sample_s_sparse / sample_s_ssm: a list of P arrays (S, n, D).  `shapes`: of the standard-normal
+        arrays `names` for one column, S first; `eps`: the caller's (a leading D axis each when D > 1) or None for torch.randn
+        from a generator seeded by `seed`, at most SAMPLE_EPS_BYTES of them (`doubles` per draw) per library call;
+        ws_bytes(chunk): the workspace of `chunk` draws; call(xs, sc, es, out, ws): the library call for sc draws at the
+        device copy xs of Xnew from the normals es into out (P, sc, n).  Both run after _compile, when the handle exists."""
+        P, n, D = len(self.kern.kern_list), Xnew.size, self.num_latent
+        if eps is not None:
+            eps = _check_eps(who, names, eps, [((D,) if D > 1 else ()) + sh for sh in shapes])
+            eps = [e.reshape((D,) + sh) for e, sh in zip(eps, shapes)]
+        self._compile()
+        self._pack()
+        h = self._handle
+        xs = h.to_device(Xnew)
+        chunk = S if eps is not None else _sample_chunk(S, doubles)
+        ws = h.workspace(ws_bytes(chunk))
+        out = h.empty(P, chunk, n)
+        gen = None if eps is not None else _sample_generator(h, seed)
+        res = np.empty((P, S, n, D))
+        for d in self._columns():
+            for s0 in range(0, S, chunk):
+                sc = min(chunk, S - s0)
+                if eps is not None:
+                    es = [h.to_device(e[d]) for e in eps]       # (to_device makes them contiguous)
+                else:
+                    es = [h.torch.randn(sc, *sh[1:], dtype=h.torch.float64, device=h.device, generator=gen) for sh in shapes]
+                call(xs, sc, es, out, ws)
+                res[:, s0:s0 + sc, :, d] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
+        return [res[i] for i in range(P)]
+
     def sample_s_sparse(self, Xnew, num_samples=1, seed=None, eps=None):
         """Joint posterior draws of every source at Xnew under the q(u) of predict_s_sparse: a list of P arrays
         (num_samples, n, D).  A draw is joint across the n frames and across the P sources (gp_sgpr_sample_source_sparse:
@@ -588,46 +632,26 @@ class SGPRSS(Parameterized):
         SAMPLE_EPS_BYTES at a time (the same seed and chunk size give the same draws); output columns get independent ones.
         eps=(eps_x, eps_z, eps_u) of shapes sample_eps_shapes(kern, n, M, num_samples), each with a leading D axis when
         D > 1, supplies them: the map is affine in eps and eps = 0 returns the posterior mean."""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         kl = self.kern.kern_list
         C = int(sum(sample_components(kl)))           # raises for an unsupported kernel, before any device work
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
-        n, P, M, S, D = Xnew.size, len(kl), self.Z.shape[0], int(num_samples), self.num_latent
+        n, P, M, S = Xnew.size, len(kl), self.Z.shape[0], int(num_samples)
         if n < 1 or S < 1:
             raise ValueError("sample_s_sparse: needs at least one new point and one sample")
-        shapes = sample_eps_shapes(kl, n, M, S)
-        if eps is not None:
-            eps = [np.asarray(e, dtype=np.float64) for e in eps]
-            want = [((D,) if D > 1 else ()) + sh for sh in shapes]
-            if len(eps) != 3 or any(e.shape != w for e, w in zip(eps, want)):
-                raise ValueError("sample_s_sparse: eps must be (eps_x, eps_z, eps_u) of shapes %s" % (want,))
-            eps = [e.reshape((D,) + sh) for e, sh in zip(eps, shapes)]
         order = np.ascontiguousarray(merged_order(Xnew, self.Z._array))
-        self._compile()
-        self._pack()
-        h = self._handle
-        xs = h.to_device(Xnew)
-        chunk = S if eps is not None else _sample_chunk(S, C * (n + M) + 2 * M)
-        ws = h.workspace(h.lib.gp_sgpr_sample_source_workspace_bytes(M, P, C, n, chunk, 1))
-        out = h.empty(P, chunk, n)
-        gen = None if eps is not None else _sample_generator(h, seed)
-        res = np.empty((P, S, n, D))
-        for d in self._columns():
-            for s0 in range(0, S, chunk):
-                sc = min(chunk, S - s0)
-                if eps is not None:
-                    ex, ez, eu = (h.to_device(e[d]) for e in eps)
-                else:
-                    ex, ez, eu = (h.torch.randn(sc, *sh[1:], dtype=h.torch.float64, device=h.device, generator=gen)
-                                  for sh in shapes)
-                h.check(h.lib.gp_sgpr_sample_source_sparse(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
-                                                           self._Yd.data_ptr(), self.X.shape[0], self._Zd.data_ptr(),
-                                                           xs.data_ptr(), n, order.ctypes.data, sc, ex.data_ptr(),
-                                                           ez.data_ptr(), eu.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                                           ws.numel()))
-                res[:, s0:s0 + sc, :, d] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
-        return [res[i] for i in range(P)]
+
+        def call(xs, sc, es, out, ws):
+            h = self._handle
+            h.check(h.lib.gp_sgpr_sample_source_sparse(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                       self._Yd.data_ptr(), self.X.shape[0], self._Zd.data_ptr(),
+                                                       xs.data_ptr(), n, order.ctypes.data, sc, es[0].data_ptr(),
+                                                       es[1].data_ptr(), es[2].data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                       ws.numel()))
+
+        return self._draw("sample_s_sparse", ("eps_x", "eps_z", "eps_u"), sample_eps_shapes(kl, n, M, S), eps, Xnew, S, seed,
+                          doubles=C * (n + M) + 2 * M, call=call,
+                          ws_bytes=lambda chunk: self._handle.lib.gp_sgpr_sample_source_workspace_bytes(M, P, C, n, chunk, 1))
 
     def sample_s_ssm(self, Xnew, num_samples=1, seed=None, eps=None):
         """Joint draws of every source at Xnew from the EXACT posterior of predict_s_ssm: a list of P arrays
@@ -645,46 +669,26 @@ class SGPRSS(Parameterized):
         posterior mean from a workspace without the smoother's steps * d^2 history.  eps_x is STEP-major and indexed along
         the MERGED timeline, unlike sample_s_sparse's component-major blocks: the same seed (or eps) with another Xnew is
         another draw, not the same path seen at other frames."""
-        if self._shard:
-            raise NotImplementedError("predictions of a frame-sharded window: build the model unsharded on one GPU")
+        self._refuse_shard()
         kl = self.kern.kern_list
         d, P = ssm_state_dim(kl, "sample_s_ssm")      # raises for an unsupported kernel or d, before any device work
         Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1)
-        n, N, S, D = Xnew.size, self.X.shape[0], int(num_samples), self.num_latent
+        n, N, S = Xnew.size, self.X.shape[0], int(num_samples)
         if n < 1 or S < 1:
             raise ValueError("sample_s_ssm: needs at least one new point and one sample")
         order, out_step, steps = ssm_timeline(self.X._array, Xnew)
         order, out_step = np.ascontiguousarray(order), np.ascontiguousarray(out_step)
-        shapes = ssm_sample_eps_shapes(kl, steps, N, S)
-        if eps is not None:
-            eps = [np.asarray(e, dtype=np.float64) for e in eps]
-            want = [((D,) if D > 1 else ()) + sh for sh in shapes]
-            if len(eps) != 2 or any(e.shape != w for e, w in zip(eps, want)):
-                raise ValueError("sample_s_ssm: eps must be (eps_x, eps_y) of shapes %s" % (want,))
-            eps = [np.ascontiguousarray(e.reshape((D,) + sh)) for e, sh in zip(eps, shapes)]
-        self._compile()
-        self._pack()
-        h = self._handle
-        xs = h.to_device(Xnew)
-        chunk = S if eps is not None else _sample_chunk(S, steps * d + N)
-        ws = h.workspace(h.lib.gp_ssm_sample_workspace_bytes(d, steps, P, chunk, 1))
-        out = h.empty(P, chunk, n)
-        gen = None if eps is not None else _sample_generator(h, seed)
-        res = np.empty((P, S, n, D))
-        for c in self._columns():
-            for s0 in range(0, S, chunk):
-                sc = min(chunk, S - s0)
-                if eps is not None:
-                    ex, ey = (h.to_device(e[c]) for e in eps)
-                else:
-                    ex, ey = (h.torch.randn(sc, *sh[1:], dtype=h.torch.float64, device=h.device, generator=gen)
-                              for sh in shapes)
-                h.check(h.lib.gp_sgpr_sample_source_ssm(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
-                                                        self._Yd.data_ptr(), N, xs.data_ptr(), n, order.ctypes.data,
-                                                        out_step.ctypes.data, steps, sc, ex.data_ptr(), ey.data_ptr(),
-                                                        out.data_ptr(), ws.data_ptr(), ws.numel()))
-                res[:, s0:s0 + sc, :, c] = out.reshape(-1)[:P * sc * n].reshape(P, sc, n).cpu().numpy()
-        return [res[i] for i in range(P)]
+
+        def call(xs, sc, es, out, ws):
+            h = self._handle
+            h.check(h.lib.gp_sgpr_sample_source_ssm(self._plan, self._params.data_ptr(), self._Xd.data_ptr(),
+                                                    self._Yd.data_ptr(), N, xs.data_ptr(), n, order.ctypes.data,
+                                                    out_step.ctypes.data, steps, sc, es[0].data_ptr(), es[1].data_ptr(),
+                                                    out.data_ptr(), ws.data_ptr(), ws.numel()))
+
+        return self._draw("sample_s_ssm", ("eps_x", "eps_y"), ssm_sample_eps_shapes(kl, steps, N, S), eps, Xnew, S, seed,
+                          doubles=steps * d + N, call=call,
+                          ws_bytes=lambda chunk: self._handle.lib.gp_ssm_sample_workspace_bytes(d, steps, P, chunk, 1))
 
     # ---- training: GPflow Model.optimize -> scipy L-BFGS-B on the free state (transcription.py:283) ----
     def _param_list(self):

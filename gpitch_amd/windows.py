@@ -12,6 +12,8 @@ import threading
 
 import numpy as np
 
+from . import sgpr_ss
+
 
 def default_reset(model, x, y, z):
     """AMT.reset_model (transcription.py:253-263): new data, unit noise and kernel variances.  (The reference
@@ -110,6 +112,7 @@ class SgprWindowBatch(object):
         P = len(kl)
         i32 = C.c_int32 * P
         self._keep = (i32(*[k.type_code for k in kl]), i32(*[int(k.num_partials) for k in kl]))
+        self.P, self.codes = P, list(zip(self._keep[0], self._keep[1]))     # (type, partials) of every source
         cfg = _lib.SgprConfig(P, int(N), int(M), self._keep[0], self._keep[1], 1e-6, int(bool(template.reg)))
         plan = C.c_void_p()
         h.check(h.lib.gp_sgprb_create(h.h, C.byref(cfg), int(num_windows), C.byref(plan)))
@@ -157,6 +160,11 @@ class SgprWindowBatch(object):
         self.counts = counts
         self._exact_order = None
 
+    def _upload(self, params_host, cnt):
+        """the constrained parameter vectors of the first `cnt` windows, through the pinned staging buffer"""
+        self._p_host[:cnt].copy_(self.h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
+        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+
     def submit(self, params_host, with_grad=True):
         """enqueue one evaluation (parameter upload, the launch sequence, result download) and return at once; `collect`
         waits for exactly this evaluation — not for whatever else is queued on the stream (another batch's evaluation:
@@ -164,8 +172,7 @@ class SgprWindowBatch(object):
         device's evaluation of the other)"""
         h = self.h
         n = self.count
-        self._p_host[:n].copy_(h.torch.as_tensor(params_host))
-        self.params[:n].copy_(self._p_host[:n], non_blocking=True)
+        self._upload(params_host, n)
         h.check(h.lib.gp_sgprb_bound_grad(self.plan, self.params.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
                                           self.Z.data_ptr(), n, self.bound.data_ptr(),
                                           self.grad.data_ptr() if with_grad else None))
@@ -211,6 +218,29 @@ class SgprWindowBatch(object):
             raise ValueError("one Xnew per loaded window")
         return t.as_tensor(xn).to(self.X.device), int(xn.shape[1])
 
+    def _timelines(self, xnews, xn, n):
+        """every loaded window's smoother timeline (sgpr_ss.ssm_timeline of its frames and its new points `xn`), padded to
+        N + n steps: (order (count, N + n), ostep (count, n), steps (count,)), int32"""
+        cnt = self.count
+        xh = self.X[:cnt].cpu().numpy()
+        nh = xh if xnews is None else xn.cpu().numpy()
+        order = np.zeros((cnt, self.N + n), dtype=np.int32)
+        ostep = np.zeros((cnt, n), dtype=np.int32)
+        steps = np.zeros(cnt, dtype=np.int32)
+        for w in range(cnt):
+            o, s, k = sgpr_ss.ssm_timeline(xh[w], nh[w])
+            order[w, :k], ostep[w], steps[w] = o, s, k
+        return order, ostep, steps
+
+    @staticmethod
+    def _chunks(cnt, chunk, per, cap):
+        """the library calls that cover `cnt` windows, `chunk` at a time: (first window, windows) of each, the first one
+        the largest.  chunk=None: as many windows as keep `per` bytes each below `cap`."""
+        if chunk is None:
+            chunk = cap // max(1, int(per))
+        chunk = int(max(1, min(int(chunk), cnt)))
+        return [(b0, min(chunk, cnt - b0)) for b0 in range(0, cnt, chunk)]
+
     def predict_f(self, params_host, xnews=None):
         """SGPRSS.predict_f of every loaded window at its parameters params_host[i] (constrained vectors, as
         `fit_windows_batched` returns them in "params"): (mean, var), each (count, n) — separation.py:306"""
@@ -219,8 +249,7 @@ class SgprWindowBatch(object):
         xn, n = self._load_xnew(xnews, cnt)
         if n > self.N:
             raise ValueError("window-batched predict_f takes at most N new points per window")
-        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        self._upload(params_host, cnt)
         mean, var = h.empty(cnt, n), h.empty(cnt, n)
         h.check(h.lib.gp_sgprb_predict_f(self.plan, self.params.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
                                          self.Z.data_ptr(), xn.data_ptr(), n, cnt, mean.data_ptr(), var.data_ptr()))
@@ -233,17 +262,13 @@ class SgprWindowBatch(object):
         h = self.h
         cnt = self.count
         xn, n = self._load_xnew(xnews, cnt)
-        P = len(self._keep[0])
-        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
-        if chunk is None:
-            per = max(1, int(h.lib.gp_sgprb_predict_source_workspace_bytes(self.plan, 1, n)))
-            chunk = max(1, min(cnt, (16 << 30) // per))
-        chunk = int(min(chunk, cnt))
-        ws = h.workspace(h.lib.gp_sgprb_predict_source_workspace_bytes(self.plan, chunk, n))
+        P = self.P
+        self._upload(params_host, cnt)
+        size = h.lib.gp_sgprb_predict_source_workspace_bytes
+        calls = self._chunks(cnt, chunk, size(self.plan, 1, n), 16 << 30)
+        ws = h.workspace(size(self.plan, calls[0][1], n))
         mean, var = h.empty(cnt, P, n), h.empty(cnt, P, n)
-        for b0 in range(0, cnt, chunk):
-            c = min(chunk, cnt - b0)
+        for b0, c in calls:
             h.check(h.lib.gp_sgprb_predict_source(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
                                                   self.Y[b0:].data_ptr(), xn[b0:].data_ptr(), n, c,
                                                   mean[b0:].data_ptr(), var[b0:].data_ptr(), ws.data_ptr(), ws.numel()))
@@ -255,9 +280,8 @@ class SgprWindowBatch(object):
         h = self.h
         cnt = self.count
         xn, n = self._load_xnew(xnews, cnt)
-        P = len(self._keep[0])
-        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        P = self.P
+        self._upload(params_host, cnt)
         mean, var = h.empty(cnt, P, n), h.empty(cnt, P, n)
         h.check(h.lib.gp_sgprb_predict_source_sparse(self.plan, self.params.data_ptr(), self.X.data_ptr(), self.Y.data_ptr(),
                                                      self.Z.data_ptr(), xn.data_ptr(), n, cnt, mean.data_ptr(),
@@ -270,31 +294,18 @@ class SgprWindowBatch(object):
         window; `chunk` windows share a launch sequence (default: as many as keep the forward walk's history, steps * d^2
         doubles per window, below sgpr_ss.MAX_SSM_BYTES).  Chunking changes no bit of any window's result.  Z, the windows'
         inducing counts and the plan's precision play no part; n may exceed N."""
-        from . import sgpr_ss
         h = self.h
-        cnt, N = self.count, self.N
-        codes = list(zip(self._keep[0], self._keep[1]))
-        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.predict_s_ssm")    # raises before any device work
+        cnt = self.count
+        d, P = sgpr_ss.ssm_state_dim(self.codes, "SgprWindowBatch.predict_s_ssm")    # raises before any device work
         xn, n = self._load_xnew(xnews, cnt)
-        xh = self.X[:cnt].cpu().numpy()
-        nh = xh if xnews is None else xn.cpu().numpy()
-        order = np.zeros((cnt, N + n), dtype=np.int32)
-        ostep = np.zeros((cnt, n), dtype=np.int32)
-        steps = np.zeros(cnt, dtype=np.int32)
-        for w in range(cnt):
-            o, s, k = sgpr_ss.ssm_timeline(xh[w], nh[w])
-            order[w, :k], ostep[w], steps[w] = o, s, k
-        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        order, ostep, steps = self._timelines(xnews, xn, n)
+        self._upload(params_host, cnt)
         smax = int(steps.max())
-        if chunk is None:
-            per = max(1, int(h.lib.gp_ssm_smooth_workspace_bytes(d, smax, P, 1)))
-            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // per)
-        chunk = int(max(1, min(int(chunk), cnt)))
-        ws = h.workspace(h.lib.gp_ssm_smooth_workspace_bytes(d, smax, P, chunk))
+        size = h.lib.gp_ssm_smooth_workspace_bytes
+        calls = self._chunks(cnt, chunk, size(d, smax, P, 1), sgpr_ss.MAX_SSM_BYTES)
+        ws = h.workspace(size(d, smax, P, calls[0][1]))
         mean, var, ll = h.empty(cnt, P, n), h.empty(cnt, P, n), h.empty(cnt)
-        for b0 in range(0, cnt, chunk):
-            c = min(chunk, cnt - b0)
+        for b0, c in calls:
             h.check(h.lib.gp_sgprb_predict_source_ssm(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
                                                       self.Y[b0:].data_ptr(), xn[b0:].data_ptr(), n, c,
                                                       order[b0:].ctypes.data, ostep[b0:].ctypes.data, steps[b0:].ctypes.data,
@@ -309,27 +320,21 @@ class SgprWindowBatch(object):
         runs the forward walk alone and returns (loglik, None).  `chunk` windows share a launch sequence (default: as many as
         keep the forward walk's history below sgpr_ss.MAX_SSM_BYTES); chunking changes no bit of any window's result.  Z, the
         windows' inducing counts and the plan's precision play no part.  Synchronous."""
-        from . import sgpr_ss
         h = self.h
         cnt, N = self.count, self.N
-        codes = list(zip(self._keep[0], self._keep[1]))
-        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.exact_loglik_grad")    # raises before any device work
+        d, P = sgpr_ss.ssm_state_dim(self.codes, "SgprWindowBatch.exact_loglik_grad")    # raises before any device work
         if self._exact_order is None:
             xh = self.X[:cnt].cpu().numpy()
             self._exact_order = np.ascontiguousarray(np.argsort(xh, axis=1, kind="stable").astype(np.int32))
         order = self._exact_order
         steps = np.full(cnt, N, dtype=np.int32)
         size = h.lib.gp_ssm_score_workspace_bytes if with_grad else h.lib.gp_ssm_smooth_workspace_bytes
-        self._p_host[:cnt].copy_(h.torch.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
-        if chunk is None:
-            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // max(1, int(size(d, N, P, 1))))
-        chunk = int(max(1, min(int(chunk), cnt)))
-        ws = h.workspace(size(d, N, P, chunk))
+        self._upload(params_host, cnt)
+        calls = self._chunks(cnt, chunk, size(d, N, P, 1), sgpr_ss.MAX_SSM_BYTES)
+        ws = h.workspace(size(d, N, P, calls[0][1]))
         ll = h.empty(cnt)
         grad = h.empty(cnt, self.nparams) if with_grad else None
-        for b0 in range(0, cnt, chunk):
-            c = min(chunk, cnt - b0)
+        for b0, c in calls:
             if with_grad:
                 h.check(h.lib.gp_sgprb_exact_loglik_grad(self.plan, self.params[b0:].data_ptr(), self.X[b0:].data_ptr(),
                                                          self.Y[b0:].data_ptr(), c, order[b0:].ctypes.data, ll[b0:].data_ptr(),
@@ -347,28 +352,22 @@ class SgprWindowBatch(object):
         from a device generator seeded by `seed`, sgpr_ss.SAMPLE_EPS_BYTES per library call; otherwise
         eps=(eps_x (count, S, C, n), eps_z (count, S, C, M), eps_u (count, S, 2, M)) with M the plan's: rows of eps_z and
         eps_u past a window's own inducing-point count are never read."""
-        from . import sgpr_ss
         h = self.h
         t = h.torch
-        cnt, S, M = self.count, int(num_samples), self.M
-        codes = list(zip(self._keep[0], self._keep[1]))
-        C = int(sum(sgpr_ss.sample_components(codes)))          # raises for an unsupported kernel, before any device work
+        cnt, S, M, P = self.count, int(num_samples), self.M, self.P
+        C = int(sum(sgpr_ss.sample_components(self.codes)))     # raises for an unsupported kernel, before any device work
         xn, n = self._load_xnew(xnews, cnt)
         if S < 1:
             raise ValueError("sample_s_sparse: needs at least one sample")
-        P = len(codes)
-        shapes = [(cnt,) + sh for sh in sgpr_ss.sample_eps_shapes(codes, n, M, S)]
+        shapes = [(cnt,) + sh for sh in sgpr_ss.sample_eps_shapes(self.codes, n, M, S)]
         if eps is not None:
-            eps = [np.asarray(e, dtype=np.float64) for e in eps]
-            if len(eps) != 3 or any(e.shape != sh for e, sh in zip(eps, shapes)):
-                raise ValueError("sample_s_sparse: eps must be (eps_x, eps_z, eps_u) of shapes %s" % (shapes,))
+            eps = sgpr_ss._check_eps("sample_s_sparse", ("eps_x", "eps_z", "eps_u"), eps, shapes)
         xh, zh = xn.cpu().numpy(), self.Z[:cnt].cpu().numpy()
         order = np.zeros((cnt, n + M), dtype=np.int32)
         for w in range(cnt):
             k = self.counts[w]
             order[w, :n + k] = sgpr_ss.merged_order(xh[w], zh[w, :k])
-        self._p_host[:cnt].copy_(t.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+        self._upload(params_host, cnt)
         chunk = S if eps is not None else sgpr_ss._sample_chunk(S, cnt * (C * (n + M) + 2 * M))
         ws = h.workspace(h.lib.gp_sgpr_sample_source_workspace_bytes(M, P, C, n, chunk, cnt))
         gen = None if eps is not None else sgpr_ss._sample_generator(h, seed)
@@ -396,45 +395,31 @@ class SgprWindowBatch(object):
         them per window at a time; otherwise eps=(eps_x (count, S, smax, d), eps_y (count, S, N)) with smax the longest
         timeline among the windows (sgpr_ss.ssm_timeline): a window reads its own first steps of eps_x.  Z, the windows'
         inducing counts and the plan's precision play no part; n may exceed N."""
-        from . import sgpr_ss
         h = self.h
         t = h.torch
         cnt, N, S = self.count, self.N, int(num_samples)
-        codes = list(zip(self._keep[0], self._keep[1]))
-        d, P = sgpr_ss.ssm_state_dim(codes, "SgprWindowBatch.sample_s_ssm")    # raises before any device work
+        d, P = sgpr_ss.ssm_state_dim(self.codes, "SgprWindowBatch.sample_s_ssm")    # raises before any device work
         if S < 1:
             raise ValueError("sample_s_ssm: needs at least one sample")
         xn, n = self._load_xnew(xnews, cnt)
         if n < 1:
             raise ValueError("sample_s_ssm: needs at least one new point")
-        xh = self.X[:cnt].cpu().numpy()
-        nh = xh if xnews is None else xn.cpu().numpy()
-        order = np.zeros((cnt, N + n), dtype=np.int32)
-        ostep = np.zeros((cnt, n), dtype=np.int32)
-        steps = np.zeros(cnt, dtype=np.int32)
-        for w in range(cnt):
-            o, s, k = sgpr_ss.ssm_timeline(xh[w], nh[w])
-            order[w, :k], ostep[w], steps[w] = o, s, k
+        order, ostep, steps = self._timelines(xnews, xn, n)
         smax = int(steps.max())
-        shapes = [(cnt,) + sh for sh in sgpr_ss.ssm_sample_eps_shapes(codes, smax, N, S)]
+        shapes = [(cnt,) + sh for sh in sgpr_ss.ssm_sample_eps_shapes(self.codes, smax, N, S)]
         if eps is not None:
-            eps = [np.asarray(e, dtype=np.float64) for e in eps]
-            if len(eps) != 2 or any(e.shape != sh for e, sh in zip(eps, shapes)):
-                raise ValueError("sample_s_ssm: eps must be (eps_x, eps_y) of shapes %s" % (shapes,))
-        self._p_host[:cnt].copy_(t.as_tensor(np.asarray(params_host, dtype=np.float64)))
-        self.params[:cnt].copy_(self._p_host[:cnt], non_blocking=True)
+            eps = sgpr_ss._check_eps("sample_s_ssm", ("eps_x", "eps_y"), eps, shapes)
+        self._upload(params_host, cnt)
         sch = S if eps is not None else sgpr_ss._sample_chunk(S, smax * d + N)
-        if chunk is None:
-            per = max(1, int(h.lib.gp_ssm_sample_workspace_bytes(d, smax, P, sch, 1)) + 8 * sch * (smax * d + N))
-            chunk = max(1, sgpr_ss.MAX_SSM_BYTES // per)
-        chunk = int(max(1, min(int(chunk), cnt)))
-        ws = h.workspace(h.lib.gp_ssm_sample_workspace_bytes(d, smax, P, sch, chunk))
+        size = h.lib.gp_ssm_sample_workspace_bytes
+        per = int(size(d, smax, P, sch, 1)) + 8 * sch * (smax * d + N)      # a window's workspace and its normals
+        calls = self._chunks(cnt, chunk, per, sgpr_ss.MAX_SSM_BYTES)
+        ws = h.workspace(size(d, smax, P, sch, calls[0][1]))
         gen = None if eps is not None else sgpr_ss._sample_generator(h, seed)
         res = np.empty((cnt, P, S, n))
         for s0 in range(0, S, sch):
             sc = min(sch, S - s0)
-            for b0 in range(0, cnt, chunk):
-                c = min(chunk, cnt - b0)
+            for b0, c in calls:
                 sm = int(steps[b0:b0 + c].max())          # the library lays eps_x out on the call's own longest timeline
                 if eps is not None:
                     ex, ey = h.to_device(np.ascontiguousarray(eps[0][b0:b0 + c, :, :sm])), h.to_device(eps[1][b0:b0 + c])
@@ -493,6 +478,48 @@ def ragged_batches(counts, batch, granule=16, cap=256):
     return out, single
 
 
+# ---- shared by fit_windows_batched and fit_windows_exact ----
+# `predict` of fit_windows_batched -> the per-source predictor, of SgprWindowBatch and of SGPRSS alike
+_SOURCE_PREDICTOR = {True: "predict_s", "sparse": "predict_s_sparse", "ssm": "predict_s_ssm"}
+
+
+def _refuse_mean_function(model, who, instead):
+    if getattr(model, "mean_function", None) is not None and type(model.mean_function).__name__ != "Zero":
+        raise NotImplementedError("%s: the template model has a mean_function; the batched plan has none (use %s)"
+                                  % (who, instead))
+
+
+def _free_state(model):
+    """(st, ps, free_idx, vals0, back, var_idx) of the template: its _objective_setup(), the free state of its own parameter
+    values (every window's starting point without params0) and where the kernel variances sit in a parameter vector"""
+    st = model._objective_setup()
+    ps, free_idx, vals0 = st["ps"], st["free_idx"], st["vals0"]
+    back = np.array([ps[i].transform.backward(np.atleast_1d(vals0[i]))[0] for i in free_idx])
+    var_idx = [int(o) for o in np.cumsum([1] + [2 + 2 * int(k.num_partials) for k in model.kern.kern_list])[:-1]]
+    return st, ps, free_idx, vals0, back, var_idx
+
+
+def _starting_points(ids, params0, ps, free_idx, vals0, back):
+    """(base, x0s) of windows `ids`: their constrained parameter vectors (params0[i], or the template's) and free states"""
+    if params0 is None:
+        return np.tile(vals0, (len(ids), 1)), [back.copy() for _ in ids]
+    base = np.stack([np.asarray(params0[i], dtype=np.float64) for i in ids])
+    return base, [np.array([ps[j].transform.backward(np.atleast_1d(row[j]))[0] for j in free_idx]) for row in base]
+
+
+def _constrained(st, base, Xf):
+    """(parameter vectors, d constrained / d free) at the free states Xf: `base` with its free entries replaced"""
+    y, dy = sgpr_ss.SGPRSS._free_to_params(st, Xf)
+    pv = base.copy()
+    pv[:, st["free_idx"]] = y
+    return pv, dy
+
+
+def _window_result(key, value, nfev, nit, params, var_idx, **more):
+    return dict({key: value, "nfev": nfev, "nit": nit, "variances": params[var_idx].copy(), "noise": float(params[0]),
+                 "params": params}, **more)
+
+
 def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default_reset, handle=None, rank=0,
                         world_size=1, params0=None, predict=False, inflight=2):
     """fit_windows with the device work batched: `batch` windows go through every bound + gradient evaluation together
@@ -526,14 +553,12 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
     Returns a list over windows of dicts: bound, nfev, nit, variances, noise, params [, error]."""
     from . import _lib, lbfgsb_batch
     from .dist import window_assignment
-    from .sgpr_ss import SGPRSS
     if not lbfgsb_batch.available():
         raise RuntimeError("fit_windows_batched needs scipy >= 1.15 (its reverse-communication L-BFGS-B routine); "
                            "use fit_windows")
     if not (isinstance(predict, (bool, np.bool_)) or predict in ("sparse", "ssm")):
         raise ValueError('fit_windows_batched: predict is False, True, "sparse" or "ssm"')
-    sparse = predict == "sparse" if isinstance(predict, str) else False
-    ssm = predict == "ssm" if isinstance(predict, str) else False
+    source = _SOURCE_PREDICTOR[predict if isinstance(predict, str) else True] if predict else None
     mine = window_assignment(len(windows), world_size, rank)
     results = [None] * len(windows)
     if not mine:
@@ -564,29 +589,22 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
                 hs.close()
     h = handle
     model = make_model(h)
-    if ssm:                                    # the smoother's scope, before any fitting
-        from .sgpr_ss import ssm_state_dim
-        ssm_state_dim(model.kern.kern_list, 'fit_windows_batched(predict="ssm")')
+    if source == "predict_s_ssm":              # the smoother's scope, before any fitting
+        sgpr_ss.ssm_state_dim(model.kern.kern_list, 'fit_windows_batched(predict="ssm")')
     init_vals = [p.value.copy() for p in model._param_list()]      # (the single-engine windows start from these)
     # what the batched plan takes from the template model: kernel structure, `reg`, the parameter values after ONE
     # reset() (on this rank's first window).  It does not carry a mean function or float32 strips: refuse, do not drop.
-    if getattr(model, "mean_function", None) is not None and type(model.mean_function).__name__ != "Zero":
-        raise NotImplementedError("fit_windows_batched: the template model has a mean_function; the batched plan has "
-                                  "none (use fit_windows)")
+    _refuse_mean_function(model, "fit_windows_batched", "fit_windows")
     if getattr(model, "_bits", 64) != 64:
         raise NotImplementedError("fit_windows_batched runs in float64; the template model asks for float32 strips "
                                   "(use fit_windows)")
     x0w, y0w, z0w = windows[mine[0]][:3]
     reset(model, x0w, y0w, z0w)
-    st = model._objective_setup()
-    ps, free_idx = st["ps"], st["free_idx"]
-    vals0 = st["vals0"]
+    st, ps, free_idx, vals0, back, var_idx = _free_state(model)
     groups, single = ragged_batches(counts, batch)
     chunks = [(m, [mine[q] for q in ids]) for m, ids in groups]       # (plan M, window indices)
     single = [mine[q] for q in single]
     B = max(1, min(int(batch), sum(len(ids) for _, ids in chunks)))
-    back = np.array([ps[i].transform.backward(np.atleast_1d(vals0[i]))[0] for i in free_idx])
-    var_idx = [int(o) for o in np.cumsum([1] + [2 + 2 * int(k.num_partials) for k in model.kern.kern_list])[:-1]]
     # Two batches in flight, each on a device plan of its own: while the host steps the L-BFGS-B instances of one batch
     # (setulb and the transforms: as long as a device evaluation at W = 256), the device evaluates the other.
     nslots = max(1, min(int(inflight), len(chunks)))
@@ -611,12 +629,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
         r = _Run()
         r.dev, r.ids, r.n = dev, ids, len(ids)
         dev.load([windows[i][0] for i in ids], [windows[i][1] for i in ids], [windows[i][2] for i in ids])
-        r.base = np.tile(vals0, (r.n, 1))
-        if params0 is not None:
-            r.base = np.stack([np.asarray(params0[i], dtype=np.float64) for i in ids])
-            x0s = [np.array([ps[j].transform.backward(np.atleast_1d(r.base[q, j]))[0] for j in free_idx]) for q in range(r.n)]
-        else:
-            x0s = [back.copy() for _ in range(r.n)]
+        r.base, x0s = _starting_points(ids, params0, ps, free_idx, vals0, back)
         r.runs = [lbfgsb_batch.LbfgsbRC(x0, maxiter=maxiter) for x0 in x0s]
         r.Xf = np.stack(x0s)
         r.active = list(range(r.n))
@@ -625,9 +638,7 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
         return r
 
     def submit(r):
-        y, r.dy = SGPRSS._free_to_params(st, r.Xf)
-        pv = r.base.copy()
-        pv[:, free_idx] = y
+        pv, r.dy = _constrained(st, r.base, r.Xf)
         # retired windows ride along on the parameters of a healthy window (their own starting parameters may be what failed:
         # Kuu depends on the kernel parameters and Z alone, so a healthy window's parameters factorise in any slot)
         donor = r.active[0] if r.active else None
@@ -666,19 +677,16 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
         return bool(nxt)
 
     def finish(r):
-        yfin, _ = SGPRSS._free_to_params(st, np.stack([q.x for q in r.runs]))
-        pfin = r.base.copy()
-        pfin[:, free_idx] = yfin
+        pfin, _ = _constrained(st, r.base, np.stack([q.x for q in r.runs]))
         for q in r.failed:
             pfin[q] = r.base[q]
         for q, i in enumerate(r.ids):
-            results[i] = {"bound": -r.runs[q].fun, "nfev": r.runs[q].nfev, "nit": r.runs[q].nit,
-                          "variances": pfin[q, var_idx].copy(), "noise": float(pfin[q, 0]), "params": pfin[q].copy()}
+            results[i] = _window_result("bound", -r.runs[q].fun, r.runs[q].nfev, r.runs[q].nit, pfin[q].copy(), var_idx)
             if q in r.failed:
                 results[i].update(error=r.failed[q], bound=float("nan"))
-        if predict:
+        if source:
             fm, fv = r.dev.predict_f(pfin)
-            sm, sv = r.dev.predict_s_sparse(pfin) if sparse else (r.dev.predict_s_ssm(pfin) if ssm else r.dev.predict_s(pfin))
+            sm, sv = getattr(r.dev, source)(pfin)
             for q, i in enumerate(r.ids):
                 if q in r.failed:           # (predicted at the starting parameters only to keep the batch whole)
                     continue
@@ -717,15 +725,13 @@ def fit_windows_batched(make_model, windows, maxiter=10, batch=64, reset=default
         try:
             res = model.optimize(method='L-BFGS-B', maxiter=maxiter)
         except _lib.NotPositiveDefiniteError as e:
-            results[i] = {"bound": float("nan"), "nfev": 0, "nit": 0, "variances": start_vals[var_idx].copy(),
-                          "noise": float(start_vals[0]), "params": start_vals, "engine": "single", "error": str(e)}
+            results[i] = _window_result("bound", float("nan"), 0, 0, start_vals, var_idx, engine="single", error=str(e))
             continue
         pv = np.array([float(p.value[0]) for p in ps1])
-        results[i] = {"bound": -float(res.fun), "nfev": int(res.nfev), "nit": int(res.nit),
-                      "variances": pv[var_idx].copy(), "noise": float(pv[0]), "params": pv, "engine": "single"}
-        if predict:
+        results[i] = _window_result("bound", -float(res.fun), int(res.nfev), int(res.nit), pv, var_idx, engine="single")
+        if source:
             m1, v1 = model.predict_f(x)
-            ms, vs = model.predict_s_sparse(x) if sparse else (model.predict_s_ssm(x) if ssm else model.predict_s(x))
+            ms, vs = getattr(model, source)(x)
             results[i].update(mean=m1, var=v1, smean=list(ms), svar=list(vs))
     model._destroy()
     return results
@@ -744,7 +750,6 @@ def fit_windows_exact(make_model, windows, maxiter=10, batch=64, params0=None, h
     device work).  Synchronous: one evaluation at a time, no recorded graph, no batches in flight.
     Returns a list over windows of dicts: loglik, nfev, nit, variances, noise, params."""
     from . import _lib, lbfgsb_batch
-    from .sgpr_ss import SGPRSS, ssm_state_dim
     if not lbfgsb_batch.available():
         raise RuntimeError("fit_windows_exact needs scipy >= 1.15 (its reverse-communication L-BFGS-B routine)")
     results = [None] * len(windows)
@@ -755,21 +760,16 @@ def fit_windows_exact(make_model, windows, maxiter=10, batch=64, params0=None, h
         if np.asarray(w[0]).size != N or np.asarray(w[1]).size != N:
             raise ValueError("fit_windows_exact: all windows must have the same number of frames (one output column)")
     model = make_model(handle)
-    if getattr(model, "mean_function", None) is not None and type(model.mean_function).__name__ != "Zero":
-        raise NotImplementedError("fit_windows_exact: the template model has a mean_function; the batched plan has none "
-                                  '(use optimize(objective="exact") per window)')
+    _refuse_mean_function(model, "fit_windows_exact", 'optimize(objective="exact") per window')
     if getattr(model, "_shard", None):
         raise NotImplementedError("fit_windows_exact: the template model is a frame-sharded window; the state-space walk is "
                                   "sequential in the frames (build it unsharded)")
     if model.reg:
         raise NotImplementedError("fit_windows_exact: reg=True adds its L1 term to the collapsed bound; the exact likelihood "
                                   "has none (build the template with reg=False)")
-    ssm_state_dim(model.kern.kern_list, "fit_windows_exact")
+    sgpr_ss.ssm_state_dim(model.kern.kern_list, "fit_windows_exact")
     h = handle or model._handle or _lib.default_handle()
-    st = model._objective_setup()
-    ps, free_idx, vals0 = st["ps"], st["free_idx"], st["vals0"]
-    back = np.array([ps[i].transform.backward(np.atleast_1d(vals0[i]))[0] for i in free_idx])
-    var_idx = [int(o) for o in np.cumsum([1] + [2 + 2 * int(k.num_partials) for k in model.kern.kern_list])[:-1]]
+    st, ps, free_idx, vals0, back, var_idx = _free_state(model)
     z = model.Z._array.reshape(-1)
     B = max(1, min(int(batch), len(windows)))
     dev = SgprWindowBatch(model, B, N, z.size, handle=h)
@@ -777,27 +777,17 @@ def fit_windows_exact(make_model, windows, maxiter=10, batch=64, params0=None, h
         for b0 in range(0, len(windows), B):
             ids = list(range(b0, min(b0 + B, len(windows))))
             dev.load([windows[i][0] for i in ids], [windows[i][1] for i in ids], [z for _ in ids])
-            base = np.tile(vals0, (len(ids), 1))
-            x0s = [back.copy() for _ in ids]
-            if params0 is not None:
-                base = np.stack([np.asarray(params0[i], dtype=np.float64) for i in ids])
-                x0s = [np.array([ps[j].transform.backward(np.atleast_1d(base[q, j]))[0] for j in free_idx])
-                       for q in range(len(ids))]
+            base, x0s = _starting_points(ids, params0, ps, free_idx, vals0, back)
 
             def fg(Xf, active, base=base):
-                y, dy = SGPRSS._free_to_params(st, Xf)
-                pv = base.copy()
-                pv[:, free_idx] = y
+                pv, dy = _constrained(st, base, Xf)
                 ll, grad = dev.exact_loglik_grad(pv)
                 return -ll, -(grad[:, free_idx] * dy)
 
             runs = lbfgsb_batch.minimize_many(fg, x0s, maxiter=maxiter)
-            yfin, _ = SGPRSS._free_to_params(st, np.stack([r.x for r in runs]))
-            pfin = base.copy()
-            pfin[:, free_idx] = yfin
+            pfin, _ = _constrained(st, base, np.stack([r.x for r in runs]))
             for q, i in enumerate(ids):
-                results[i] = {"loglik": -runs[q].fun, "nfev": runs[q].nfev, "nit": runs[q].nit,
-                              "variances": pfin[q, var_idx].copy(), "noise": float(pfin[q, 0]), "params": pfin[q].copy()}
+                results[i] = _window_result("loglik", -runs[q].fun, runs[q].nfev, runs[q].nit, pfin[q].copy(), var_idx)
     finally:
         dev.close()
         model._destroy()
